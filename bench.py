@@ -81,6 +81,28 @@ def answer_hash(np, final_ct, response):
     return h.hexdigest()
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(np, out_dir, arrays):
+    """--dump-outputs: write the arrays the timed path handed back in its last step as out_dir/<name>.npy.  The words are u64 residues (up to 56
+    bits), which neither float type holds exactly, so each word becomes four float32 16-bit limbs, least significant first, in a new last axis:
+    exact, and a one-unit change in any limb is far outside a float comparison's relative tolerance.  Beyond the size limit, a fixed seeded sample
+    of each array's words is written instead.  Returns {name: shape written} for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    words = {k: np.ascontiguousarray(a).view(np.uint64) for k, a in arrays.items()}
+    total = 16 * sum(a.size for a in words.values())  # 4 float32 limbs per word
+    shapes = {}
+    for name, a in words.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = a.size * DUMP_LIMIT_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        limbs = np.stack([(a >> np.uint64(s)) & np.uint64(0xFFFF) for s in (0, 16, 32, 48)], axis=-1).astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), limbs)
+        shapes[name] = list(limbs.shape)
+    return shapes
+
+
 def inject_fail(tag, rank):
     """test hook: SPIRAL_BENCH_INJECT_FAIL=<tag>[:<rank>] raises at the point named <tag> (a schedule, "stream_item", "cpu_baseline"), on one rank or on all"""
     want = os.environ.get("SPIRAL_BENCH_INJECT_FAIL", "")
@@ -365,10 +387,12 @@ def bench_pack(args):
     gathered = torch.zeros(shp.trials * 2 * sa.N, dtype=torch.int64, device=dev)
     us = []
     coll_ev = []  # HIP events around the collective, every step (one pair per step against an 11 ms step)
+    last = {}  # rank 0: the response of the latest step (--dump-outputs)
 
     def step():
         if not use_dist:
-            us.append(srv.answer(q, want_packed=False)[2])
+            last["response"], _, st = srv.answer(q, want_packed=False)
+            us.append(st)
             return
         srv.fold_trials(q, mine.data_ptr())
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -377,7 +401,7 @@ def bench_pack(args):
         e1.record(stream)
         coll_ev.append((e0, e1))
         if rank == 0:
-            srv.pack_gathered(gathered.data_ptr())
+            last["response"] = srv.pack_gathered(gathered.data_ptr())[0]
         us.append(srv.stage_us())
 
     def fence():
@@ -416,6 +440,8 @@ def bench_pack(args):
     if use_dist:
         out["rccl"] = rccl
         out["collectives_us"] = {"all_gather_folded_trials": round(sum(a.elapsed_time(b) for a, b in coll_ev) / len(coll_ev) * 1e3, 1)}
+    if args.dump_outputs and rank == 0:
+        out["dumped_outputs"] = dump_outputs(np, args.dump_outputs, last)
     srv.close()
     if use_dist:
         dist.destroy_process_group()
@@ -429,7 +455,7 @@ def bench_pack(args):
 STREAM_ITEM_BYTES = 100_000  # BASELINE.json configs[3]: 2^20 x 100 KB
 
 
-def bench_stream(args, ctx, prog, steps=None, warmup=None):
+def bench_stream(args, ctx, prog, steps=None, warmup=None, dump_dir=None):
     """--workload stream: BASELINE.json configs[3] WHOLE.  A 100 KB item is factor = ceil(100000 / 15360) = 7 plaintexts of the "Streaming 20/spiralstream" set
     (n^2 * 2048 * log2(p) / 8 = 15 360 bytes each, select_params.py:297-298), i.e. SEVEN instances of the 2^20-item database, 64 GiB each in the reference's layout
     (56 GiB on the device): 448 GiB.  The client sends one query; the server converts it once and answers it against every instance -- first dimension, folding
@@ -503,12 +529,15 @@ def bench_stream(args, ctx, prog, steps=None, warmup=None):
         ctx.fence()
         ms = ctx.max_over_ranks(time.perf_counter() - t0) * 1e3 / steps
         prog.arm("stream/stage split", 3.0)
-        out_h = None
+        out_h = dumped = None
         if rank == 0:
             h = hashlib.sha256()
             for k in range(factor):
                 h.update(sdist.instance_response(gathered, k, world, slots).cpu().numpy().astype("<i8").tobytes())
             out_h = h.hexdigest()
+            if dump_dir:  # the item's responses as the caller receives them: instance k's switched response, n1 x n2 polynomials
+                responses = np.stack([sdist.instance_response(gathered, k, world, slots).cpu().numpy() for k in range(factor)]).reshape(factor, 3, 2, sa.N)
+                dumped = dump_outputs(np, dump_dir, {"responses": responses})
         # stage split on rank 0's first instance, outside the timed region: conversion alone, one instance's sweep + fold + switch, the sweep kernel alone
         pre_us = inst_us = sweep_ms = None
         if rank == 0 and qsrv is not None:
@@ -552,6 +581,8 @@ def bench_stream(args, ctx, prog, steps=None, warmup=None):
         }
         if ctx.use_dist:
             line["rccl"] = ctx.rccl
+        if dumped:
+            line["dumped_outputs"] = dumped
     for sv in inst:
         sv.close()
     torch.cuda.empty_cache()
@@ -602,6 +633,9 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for the one-GPU self-test)")
     ap.add_argument("--shared-device", action="store_true", help="self-test: all ranks use device 0")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed and run the reduce even with one rank (self-test)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, rank 0 writes what the headline's timed path returned in its last "
+                    "step as DIR/<name>.npy (base workloads: final_ct and response; stream: responses; pack: response), each u64 word as four float32 16-bit "
+                    "limbs, least significant first; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args(argv)
     if args.comm_overlap:
         args.schedule = "comm-overlap"
@@ -619,6 +653,8 @@ def self_launch(args, argv):
     initialised the GPU: this parent never does."""
     import subprocess
 
+    if args.dump_outputs:  # the ranks run in ROOT: hand them the directory as an absolute path (argparse keeps the last occurrence)
+        argv = list(argv) + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL needs it on this driver
     # --standalone: the launcher's own c10d rendezvous on a port it binds itself (no bind-close-reuse race with another job on the box)
@@ -925,14 +961,18 @@ def bench_base(args, ctx, workload, steps, warmup, primary, prog):
         return ctx.max_over_ranks(time.perf_counter() - t0) * 1e3 / steps
 
     timed, hashes, no_prewarm, ev_done = {}, {}, None, [False]
+    outputs = {}  # --dump-outputs, headline leg, rank 0: schedule -> what its last timed step left
     names = ["expand_convert", "sweep", "reduce_lift_fold_switch"]  # the last bucket includes the collective(s)
+
+    def chosen():
+        # N > 1: the headline is ONE fixed schedule (comm-overlap where it applies), not the best of several -- a minimum over noisy
+        # timings is biased low and would not compare like with like between rounds; the others are reported beside it in `schedules`
+        return "comm-overlap" if "comm-overlap" in timed else ("in-order" if "in-order" in timed else min(timed, key=timed.get))
 
     def make_out(extra=None):
         """the JSON line from what has been measured so far (called after every schedule, and at the end with everything else)"""
-        # N > 1: the headline is ONE fixed schedule (comm-overlap where it applies), not the best of several -- a minimum over noisy
-        # timings is biased low and would not compare like with like between rounds; the others are reported beside it in `schedules`
         fastest = min(timed, key=timed.get)
-        best = "comm-overlap" if "comm-overlap" in timed else ("in-order" if "in-order" in timed else fastest)
+        best = chosen()
         ms_per_step = timed[best]
         have_ev = ev_done[0] and bool(sampled)  # the stage events have been recorded (an in-order pass ran)
         stages = {n: sum(ev[k][i].elapsed_time(ev[k][i + 1]) for k in sampled) / len(sampled) * 1e3 for i, n in enumerate(names)} if have_ev else None
@@ -1027,6 +1067,8 @@ def bench_base(args, ctx, workload, steps, warmup, primary, prog):
             timed[sch] = timed_loop(sch, ev if sch == "in-order" else None)
             if sch == "in-order": ev_done[0] = True
             hashes[sch] = read_answer()
+            if primary and rank == 0 and args.dump_outputs:  # what answer() hands its caller: the folded ciphertext and the switched response
+                outputs[sch] = {"final_ct": srv.read(SV.BUF_FINAL), "response": srv.read(SV.BUF_RESPONSE)}
             prog.update(make_out())
         prog.arm(f"{workload}/after the timed schedules", 3.0)
         if "in-order" not in timed:  # a single other schedule was asked for: the stage split still comes from a few in-order steps, outside the timed region
@@ -1193,6 +1235,8 @@ def bench_base(args, ctx, workload, steps, warmup, primary, prog):
                                                          "8 TB/s peak); forward_digits is the launch the stages are built from (8 gadget digits of each of 2048 polynomials: the source is "
                                                          "re-read from cache, every transform writes its 16 KiB) and is bound by VALU issue (3.6 ns)"}
     if pipelined: extra["pipelined"] = pipelined
+    if outputs:
+        extra["dumped_outputs"] = dump_outputs(np, args.dump_outputs, outputs[chosen()])
     out = make_out(extra)
     prog.update(out)
     prog.disarm()
@@ -1296,7 +1340,7 @@ def run(args, prog, np):
     ctx = Ctx(args, prog)
     prog.arm("set-up", 3.0)
     if args.workload == "stream":
-        out = bench_stream(args, ctx, prog)
+        out = bench_stream(args, ctx, prog, dump_dir=args.dump_outputs)
         prog.arm("process group tear-down", 1.0)
         ctx.close()
         prog.disarm()

@@ -142,6 +142,29 @@ def test_bench_self_launch_command_and_cpu_quota(monkeypatch):
     assert a.schedule == "comm-overlap" and bench.parse_args([]).schedule == "all" and bench.parse_args([]).sweep_stages == 4
 
 
+def test_bench_dump_outputs_is_exact_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (no GPU involved): u64 words of up to 64 bits come back exactly from the float32 limbs; int64 views are the same
+    words; beyond the size limit every array is cut to the same seeded sample of its words, run after run"""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.parse_args(["--dump-outputs", "d"]).dump_outputs == "d" and bench.parse_args([]).dump_outputs is None
+    rng = np.random.default_rng(2)
+    fin = rng.integers(0, 2**64 - 1, size=(3, 2, 2048), dtype=np.uint64, endpoint=True)
+    resp = rng.integers(0, 2**20, size=(3, 2, 2048), dtype=np.uint64)
+    shapes = bench.dump_outputs(np, str(tmp_path / "a"), {"final_ct": fin, "response": resp.view(np.int64)})
+    assert shapes == {"final_ct": [3, 2, 2048, 4], "response": [3, 2, 2048, 4]}
+    for name, want in (("final_ct", fin), ("response", resp)):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and (got >= 0).all() and (got < 2**16).all()
+        assert (sum(got[..., i].astype(np.uint64) << np.uint64(16 * i) for i in range(4)) == want).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 << 10)
+    for d in ("b", "c"):
+        shapes = bench.dump_outputs(np, str(tmp_path / d), {"final_ct": fin, "response": resp})
+        assert sum(16 * s[0] for s in shapes.values()) <= 64 << 10
+    assert all((np.load(tmp_path / "b" / f"{n}.npy") == np.load(tmp_path / "c" / f"{n}.npy")).all() for n in ("final_ct", "response"))
+
+
 def test_bench_watchdog_prints_the_line_so_far():
     """bench.py's Progress (no GPU involved): a phase that outlives the watchdog ends the process with exit code 3 and the line-so-far on stdout,
     marked partial with the phase it hung in; the same line was written to the partial file when it was recorded"""
