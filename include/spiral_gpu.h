@@ -449,6 +449,30 @@ int spiral_gpu_pack_server_read_response_wire(spiral_gpu_pack_server *s, void *o
  * num_per ciphertexts base_dim x 1, NTT form (tests) */
 int spiral_gpu_pack_server_read_acc(spiral_gpu_pack_server *s, uint32_t trial, uint64_t *out);
 uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algorithmic bytes of ONE trial's sweep */
+/* Batches on the pack path, beyond the reference (one query per call).  create_lane: a new server with the owner's parameters, out_n and
+ * device that sweeps the OWNER's trial images and has its own public parameters, query and intermediates (loads through a lane fail; the owner
+ * counts its lanes and the images go with the last of them; trial-sharded owners have no lanes).
+ * answer_batch: n <= 8 servers -- an owner and/or its lanes, each with its own client's public parameters -- answer queries[b] each: expansion and
+ * conversion per lane, ONE first-dimension pass over every trial image for all n queries, then folding, packing and the modulus switch per lane,
+ * all on servers[0]'s stream; returns synchronised.  Afterwards every lane's buffers (read_acc of every trial, read_response_wire) hold exactly
+ * what its own answer would have left.  responses[b] / packed_cts[b] (or the arrays) may be NULL.  stage_us (may be NULL): [0] expansion [1]
+ * conversion [3] folding [4] packing, summed over the lanes, [2] = [5] the shared sweep, [6] total, [7] n.  Every server is checked before anything
+ * is launched (n in 1 .. 8, no duplicates, same image, parameters, database and public parameters present): a failing check leaves every lane's
+ * previous results intact.  n = 1 is answer.
+ * The shared pass runs on the matrix cores (csrc/sweep_mfma.hip, the base path's kernel with 2-row records) from the LIMBS form of the trial
+ * images, where that form exists: >= 128 ciphertexts per slot (nu2 >= 7) and a first dimension that is a power of two in [128, 4096].  The first
+ * batch on such a geometry converts the images in place (set_db_format); elsewhere the batch sweeps once per lane on the vector ALU -- same
+ * results, no shared pass.  A single answer on a LIMBS image sweeps it with the one-query instance of the same kernel (bit-identical).
+ * set_db_format / db_format / db_device_bytes: as spiral_gpu_server_set_db_format, for the out_n^2 trial images (on the owner, not a lane; every
+ * loader leaves a correct image whatever form it finds; a conversion that fails partway leaves no database loaded).
+ * time_sweep_batch: the batched sweep alone, iters times with the lanes' current records (each answered once), average ms by device events. */
+int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server *owner, spiral_gpu_pack_server **out);
+int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server *const *servers, uint32_t n, const uint64_t *const *queries,
+                                        uint64_t *const *responses, uint64_t *const *packed_cts, double stage_us[8]);
+int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server *s, int format);
+int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server *s);
+uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server *s);
+int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server *const *servers, uint32_t n, int iters, float *avg_ms);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,7 @@ static uint64_t param(int argc, char** argv, const char* name, uint64_t dflt) {
 static size_t bits_to_bytes(size_t bits) { return (size_t)std::llround((double)bits / 8.0); }
 
 // testHighRate (src/testing.cpp:777-1154): SpiralPack / SpiralStreamPack end to end, summary of :626-733
-static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_target, uint64_t seed, bool nonoise, bool show_diff, uint64_t qnum_first) {
+static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_target, uint64_t seed, bool nonoise, bool show_diff, uint64_t qnum_first, uint32_t batch) {
     cout << "Using n=" << out_n << endl;
     spiral_gpu_pack_shape s;
     GPU_OK(spiral_gpu_pack_get_shape(&p, out_n, &s));
@@ -130,8 +130,54 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     cout << "GPU extras" << endl << endl;
     cout << "      Sweep kernels alone (GPU·us): " << us[5] << "  (" << (double)out_n * out_n * spiral_gpu_pack_server_sweep_bytes(srv) / us[5] / 1e3 << " GB/s)" << endl;
     cout << "      Whole answer, device (GPU·us): " << us[6] << endl;
+    // ---- --batch B: B more clients (own keys, own indices) answered by ONE spiral_gpu_pack_server_answer_batch call: the server and B - 1 lanes
+    // (create_lane), one first-dimension pass over the trial images for all of them
+    bool batch_corr = true;
+    if (batch >= 2 && batch <= 8) {
+        std::vector<spiral_gpu_pack_server*> lanes{srv};
+        std::vector<PackClient> clients;
+        std::vector<Poly> queries, resps(batch, Poly((size_t)(out_n + 1) * out_n * N));
+        std::vector<uint64_t> idxs;
+        clients.reserve(batch);
+        for (uint32_t b = 0; b < batch; b++) {
+            if (b) {
+                spiral_gpu_pack_server* lane = nullptr;
+                GPU_OK(spiral_gpu_pack_server_create_lane(srv, &lane));
+                lanes.push_back(lane);
+            }
+            clients.emplace_back(p, out_n, seed + 1 + b, nonoise);
+            clients[b].keygen();
+            clients[b].gen_pub_params();
+            idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);
+            GPU_OK(spiral_gpu_pack_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].v.data(), clients[b].v_w.data()));
+            queries.push_back(clients[b].query(idxs[b]));
+        }
+        std::vector<const uint64_t*> qp;
+        std::vector<uint64_t*> rp;
+        for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].data()), rp.push_back(resps[b].data());
+        double bus[8];
+        GPU_OK(spiral_gpu_pack_server_answer_batch(lanes.data(), batch, qp.data(), nullptr, nullptr, bus));  // warm-up (converts the image where it can)
+        t0 = now_us();
+        GPU_OK(spiral_gpu_pack_server_answer_batch(lanes.data(), batch, qp.data(), rp.data(), nullptr, bus));
+        const double batch_us = (double)(now_us() - t0);
+        cout << "Batch of " << batch << " queries, Is correct?:";
+        for (uint32_t b = 0; b < batch; b++) {
+            GPU_OK(spiral_gpu_pack_server_read_response_wire(lanes[b], wire.data(), wire.size()));
+            GPU_OK(spiral_gpu_response_from_wire(&p, out_n, wire.data(), resps[b].data()));
+            const bool ok = clients[b].decode(resps[b].data()) == pack_db_item(db_seed, idxs[b], total_n, out_n, p.p_db);
+            batch_corr = batch_corr && ok;
+            cout << " " << (ok ? 1 : 0);
+        }
+        cout << endl;
+        cout << "   Batch of " << batch << " queries, wall (GPU·us): " << batch_us << "  (shared sweep " << bus[2] << ")" << endl;
+        for (uint32_t b = 1; b < batch; b++) spiral_gpu_pack_server_destroy(lanes[b]);
+    } else if (batch) {
+        fprintf(stderr, "spiral: --batch takes 2 .. 8\n");
+        spiral_gpu_pack_server_destroy(srv);
+        return 1;
+    }
     spiral_gpu_pack_server_destroy(srv);
-    return is_corr ? 0 : 2;
+    return (is_corr && batch_corr) ? 0 : 2;
 }
 
 int main(int argc, char** argv) {
@@ -195,7 +241,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: no ROCm device found; this build has no CPU path\n");
         return 1;
     }
-    if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first);
+    if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch);
     spiral_gpu_shape s;
     GPU_OK(spiral_gpu_get_shape(&p, &s));
     cout << "dim0: " << s.dim0 << endl;

@@ -449,5 +449,15 @@ void launch_pack_gsw_from_upload(const uint64_t* query, uint64_t* gsw, uint32_t 
 void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2, hipStream_t s);
 // pack (:198-241): result[row][c] = sum_r sum_k W_r[row][k] * ginv[r*out_n+c][k] + (row >= 1 ? ct2[(row-1)*out_n+c] : 0)
 void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s);
+// the first-dimension sweep of n = 1 .. kMaxLanes queries (records qs1[b] -> accumulators acc[b], launch_sweep1's layouts) on the matrix cores, in ONE
+// pass over `trials` trial images (db_stride / acc_stride u64 words apart) in limb-plane form (sweep_mfma.hip, ROWS = 2).  Coverage (sweep1_mfma_ok):
+// num_per >= 128 a power of two, dim0 a power of two in [128, 4096].  Bit-identical to sweep1_kernel per query.  Returns the launch's error.
+bool sweep1_mfma_ok(uint32_t num_per, uint32_t dim0);
+hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* qs1, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t dim0, uint32_t trials,
+                              size_t db_stride, size_t acc_stride, hipStream_t s);
+// packed trial image <-> limb planes for nz slots z (pointers at the first of them; a slot's region, db1_device_words / kN words, is the same in both
+// forms): the base path's conversion kernels, with nic = num_per columns and dim0 terms per column
+void launch_db1_limb_planes(const uint64_t* packed_img, uint64_t* limbs, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz);
+void launch_db1_limb_unplanes(const uint64_t* limbs, uint64_t* packed_img, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz);
 
 }  // namespace spiral

@@ -1,6 +1,7 @@
 // SpiralPack / SpiralStreamPack kernels (reference src/testing.cpp, `--high-rate`): base_dim x 1 scalar Regev
 // ciphertexts against 1 x 1 plaintexts.  The first-dimension sweep is again the HBM-bound kernel: 4 integer MADs
-// per 8-byte database word.
+// per 8-byte database word.  Several queries against one image share a pass on the matrix cores instead
+// (sweep_mfma.hip, ROWS = 2), from the limb-plane form of the image.
 #include "common.h"
 #include "kernels.h"
 

@@ -1,5 +1,6 @@
 // SpiralPack / SpiralStreamPack: host orchestration and C ABI (server half of testHighRate, reference
-// src/testing.cpp:1009-1081).  Kernels: pack.hip, ntt.hip (LD_PDIGIT / LD_DBGEN1), poly.hip (matmul, rescale).
+// src/testing.cpp:1009-1081).  Kernels: pack.hip, ntt.hip (LD_PDIGIT / LD_DBGEN1), poly.hip (matmul, rescale), sweep_mfma.hip (the batched
+// first-dimension sweep of answer_batch: several lanes' queries in one pass over the trial images, from their limb-plane form).
 #include "host_common.h"
 
 using namespace spiral;
@@ -21,6 +22,13 @@ struct spiral_gpu_pack_server {
     DevBuf db, w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
     DevBuf gs_raw, gs_chat, gs_tmp, gsw, key, qs1, acc, raw, fold_d, fold_c, fold_c2, pk_ginv, pk_ct2, pk_res, pk_raw, resp, stage, wire;
     hipEvent_t ev[8] = {};
+    bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
+    // query lanes (create_lane): a lane has no image of its own and sweeps its owner's; the owner counts its lanes.  Destroying an owner that
+    // still has lanes frees everything but the image and leaves a husk (zombie) that the last lane to go deletes.
+    spiral_gpu_pack_server* db_owner = nullptr;
+    uint32_t n_lanes = 0;
+    bool zombie = false;
+    uint32_t db_format = SPIRAL_GPU_DB_PACKED;  // holder only: the form db is in now (pk_db_set_format)
 };
 
 namespace {
@@ -51,14 +59,20 @@ int pack_shape_of(const spiral_gpu_params* p, uint32_t out_n, spiral_gpu_pack_sh
     return 0;
 }
 
-void pk_free(spiral_gpu_pack_server* S) {
+spiral_gpu_pack_server* pk_holder(spiral_gpu_pack_server* S) { return S->db_owner ? S->db_owner : S; }
+
+void pk_free(spiral_gpu_pack_server* S, bool keep_db = false) {
+    const DevBuf keep = S->db;
     DevBuf* all[] = {&S->db, &S->w_left, &S->w_right, &S->v, &S->v_w, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->gs_raw, &S->gs_chat, &S->gs_tmp,
                      &S->gsw, &S->key, &S->qs1, &S->acc, &S->raw, &S->fold_d, &S->fold_c, &S->fold_c2, &S->pk_ginv, &S->pk_ct2, &S->pk_res, &S->pk_raw, &S->resp,
                      &S->stage, &S->wire};
+    if (keep_db) S->db = DevBuf{};
     for (DevBuf* b : all) b->release();
     for (auto& e : S->ev)
-        if (e) (void)hipEventDestroy(e);
+        if (e) (void)hipEventDestroy(e), e = nullptr;
     if (S->stream && S->own_stream) (void)hipStreamDestroy(S->stream);
+    S->stream = nullptr;
+    if (keep_db) S->db = keep;
 }
 
 int pk_alloc(spiral_gpu_pack_server* S) {
@@ -66,7 +80,7 @@ int pk_alloc(spiral_gpu_pack_server* S) {
     const spiral_gpu_pack_shape& s = S->s;
     const size_t ngs = (size_t)p.nu2 * s.ell, rows = S->out_n + 1;
     S->db_words = db1_device_words(s.num_per, s.dim0);  // u64 words of one trial in the device layout
-    if (S->db.alloc(S->db_words * S->nt)) return -1;
+    if (!S->db_owner && S->db.alloc(S->db_words * S->nt)) return -1;  // (a lane sweeps its owner's image)
     if (S->w_left.alloc((size_t)s.n_left * 2 * p.t_exp * kN)) return -1;
     if (S->w_right.alloc((size_t)s.n_right * 2 * p.t_exp_right * kN)) return -1;
     if (S->v.alloc((size_t)2 * 2 * p.t_conv * kN)) return -1;
@@ -139,6 +153,61 @@ void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_strid
     launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st);
 }
 
+// Converts the holder's trial images between the packed form (kernels.h; sweep1_kernel) and the limb planes (sweep_mfma.hip; the matrix-core
+// sweep) IN PLACE, as the base path's srv_db_set_format: a slot z's region of a trial is the same byte range in both forms, so the images go
+// through a staging buffer of at most 256 MiB a few slots at a time -- never a second image.  A failure once the first region has been
+// rewritten leaves the image in neither form: it is marked invalid (no database loaded) rather than left under the old tag.
+int pk_db_set_format(spiral_gpu_pack_server* H, uint32_t fmt, hipStream_t st) {
+    if (H->db_format == fmt) return 0;
+    const uint32_t np = H->s.num_per, dim0 = H->s.dim0;
+    if (!sweep1_mfma_ok(np, dim0))
+        return fail("this geometry has no limb-plane form (needs >= 128 ciphertexts per slot and a power-of-two first dimension in [128, 4096])");
+    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever reads or writes the image, on whichever stream
+    const size_t per_z = H->db_words / kN;
+    const uint32_t nzc = (uint32_t)std::max<size_t>(1, std::min<size_t>(kN, ((size_t)256 << 20) / (per_z * sizeof(uint64_t))));
+    DevBuf stage;
+    if (stage.alloc(per_z * nzc)) return -1;
+    hipError_t e = hipSuccess;
+    for (uint32_t t = 0; t < H->nt && e == hipSuccess; t++)
+        for (uint32_t z = 0; z < kN && e == hipSuccess; z += nzc) {
+            const uint32_t nz = std::min(nzc, kN - z);
+            uint64_t* region = H->db.p + (size_t)t * H->db_words + (size_t)z * per_z;
+            if (fmt == SPIRAL_GPU_DB_LIMBS)
+                launch_db1_limb_planes(region, stage.p, np, dim0, st, nz);
+            else
+                launch_db1_limb_unplanes(region, stage.p, np, dim0, st, nz);
+            e = hipMemcpyAsync(region, stage.p, (size_t)nz * per_z * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
+        }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    stage.release();
+    if (e != hipSuccess) {
+        H->have_db = false;
+        H->db_format = SPIRAL_GPU_DB_PACKED;
+        return fail("converting the database image failed (%s): the image is invalid, load the database again", hipGetErrorString(e));
+    }
+    H->db_format = fmt;
+    return 0;
+}
+// a loader is about to rewrite the whole image in packed form
+void pk_db_rewrite(spiral_gpu_pack_server* S) { S->db_format = SPIRAL_GPU_DB_PACKED; }
+
+// the first-dimension sweep of n servers' queries (their records and accumulators) over every trial image of servers[0]'s holder, on `st`: one pass on the
+// matrix cores when the image is in limb-plane form, else one sweep1 launch (all trials) per server
+int pk_sweep(spiral_gpu_pack_server* const* servers, uint32_t n, hipStream_t st) {
+    spiral_gpu_pack_server* H = pk_holder(servers[0]);
+    const spiral_gpu_pack_shape& s = H->s;
+    const size_t acc_stride = (size_t)s.num_per * 2 * kN;
+    if (H->db_format == SPIRAL_GPU_DB_LIMBS) {
+        const uint32_t* qs[kMaxLanes];
+        uint64_t* acc[kMaxLanes];
+        for (uint32_t b = 0; b < n; b++) qs[b] = (const uint32_t*)servers[b]->qs1.p, acc[b] = servers[b]->acc.p;
+        const hipError_t e = launch_sweep1_mfma(H->db.p, qs, acc, n, s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
+        return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
+    }
+    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, (const uint32_t*)servers[b]->qs1.p, servers[b]->acc.p, s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -187,8 +256,8 @@ int spiral_gpu_pack_server_create(const spiral_gpu_params* p, uint32_t out_n, in
 // The out_n^2 trials are independent up to the packing step (each has its own database image, sweep and folding), so N GPUs split
 // them: a server created for trials [trial0, trial1) holds only those images; fold_trials leaves their folded ciphertexts in a
 // caller-provided device buffer, one all-gather of out_n^2 x 2 polynomials collects them, pack_gathered finishes on the root.
-int spiral_gpu_pack_server_create_sharded(const spiral_gpu_params* p, uint32_t out_n, int device, uint32_t trial0, uint32_t trial1,
-                                          spiral_gpu_pack_server** out) {
+static int pk_create(const spiral_gpu_params* p, uint32_t out_n, int device, uint32_t trial0, uint32_t trial1, spiral_gpu_pack_server* owner,
+                     spiral_gpu_pack_server** out) {
     if (!p || !out) return fail("null argument");
     spiral_gpu_pack_shape s;
     if (pack_shape_of(p, out_n, &s)) return -1;
@@ -202,6 +271,7 @@ int spiral_gpu_pack_server_create_sharded(const spiral_gpu_params* p, uint32_t o
     S->t0 = trial0;
     S->nt = trial1 - trial0;
     S->device = device;
+    S->db_owner = owner;
     if (tables_get(device, &S->tb) != 0) {
         delete S;
         return fail("twiddle table setup failed on device %d", device);
@@ -214,21 +284,64 @@ int spiral_gpu_pack_server_create_sharded(const spiral_gpu_params* p, uint32_t o
         delete S;
         return -1;
     }
+    if (owner) owner->n_lanes++;
     *out = S;
     return 0;
 }
 
+int spiral_gpu_pack_server_create_sharded(const spiral_gpu_params* p, uint32_t out_n, int device, uint32_t trial0, uint32_t trial1,
+                                          spiral_gpu_pack_server** out) {
+    return pk_create(p, out_n, device, trial0, trial1, nullptr, out);
+}
+
+// a query lane of `owner`: the owner's parameters, out_n and device, its own public parameters, query and intermediates, and the owner's trial images
+int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server* owner, spiral_gpu_pack_server** out) {
+    if (!owner || !out) return fail("null argument");
+    if (owner->db_owner || owner->zombie) return fail("the owner does not own its database image (it is a lane)");
+    if (owner->nt != owner->s.trials) return fail("the owner holds trials [%u, %u) only: trial-sharded servers have no lanes", owner->t0, owner->t0 + owner->nt);
+    if (!owner->have_db) return fail("the owner has no database loaded");
+    return pk_create(&owner->p, owner->out_n, owner->device, 0, 0, owner, out);
+}
+
 void spiral_gpu_pack_server_destroy(spiral_gpu_pack_server* S) {
-    if (!S) return;
+    if (!S || S->zombie) return;
     (void)hipSetDevice(S->device);
     (void)hipDeviceSynchronize();
+    if (S->n_lanes > 0) {  // lanes still sweep this server's images: keep them (only), the last lane frees them
+        pk_free(S, true);
+        S->zombie = true;
+        S->have_pp = false;
+        return;
+    }
+    spiral_gpu_pack_server* owner = S->db_owner;
     pk_free(S);
     delete S;
+    if (owner && --owner->n_lanes == 0 && owner->zombie) {
+        owner->db.release();
+        delete owner;
+    }
+}
+
+int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server* S, int format) {
+    if (!S) return fail("null server");
+    if (format != SPIRAL_GPU_DB_PACKED && format != SPIRAL_GPU_DB_LIMBS) return fail("unknown database image format %d", format);
+    if (S->db_owner) return fail("this server is a lane: convert the image through its owner");
+    if (!S->have_db) return fail("no database loaded");
+    HIP_OK(hipSetDevice(S->device));
+    return pk_db_set_format(S, (uint32_t)format, S->stream);
+}
+int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server* S) { return S ? (int)pk_holder(S)->db_format : -1; }
+uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server* S) {
+    if (!S) return 0;
+    const spiral_gpu_pack_server* H = pk_holder(S);
+    return (uint64_t)(H->db.p ? H->db.words : 0) * 8u;
 }
 
 int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
+    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
+    pk_db_rewrite(S);
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per, chunk = 1u << 18;
     for (uint32_t t = 0; t < S->nt; t++) {
         FwdParams fp{};
@@ -253,8 +366,12 @@ int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
 
 int spiral_gpu_pack_server_load_db(spiral_gpu_pack_server* S, uint32_t trial, const uint64_t* db) {
     if (!S || !db) return fail("null argument");
+    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    // one trial is rewritten: the others keep their words, so an image in limb-plane form goes back to the packed form first
+    if (S->db_format != SPIRAL_GPU_DB_PACKED && S->have_db && pk_db_set_format(S, SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
+    if (!S->have_db) pk_db_rewrite(S);
     DevBuf st;
     const size_t ref_words = (size_t)kN * S->s.dim0 * S->s.num_per;
     if (st.alloc(ref_words)) return -1;
@@ -273,8 +390,12 @@ int spiral_gpu_pack_server_load_db(spiral_gpu_pack_server* S, uint32_t trial, co
 int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, uint64_t first_item,
                                          uint64_t n_items) {
     if (!S) return fail("null server");
+    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    // a partial load scatters packed words into the image: an image in limb-plane form goes back to the packed form first
+    if (S->db_format != SPIRAL_GPU_DB_PACKED && S->have_db && pk_db_set_format(S, SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
+    if (!S->have_db) pk_db_rewrite(S);
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
     if (first_item > total || n_items > total - first_item) return fail("items outside the database");
     FwdParams fp{};
@@ -301,7 +422,9 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
+    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
+    pk_db_rewrite(S);
     for (uint32_t t = 0; t < S->nt; t++) launch_fill_db1_random(S->db.p + (size_t)t * S->db_words, S->s.num_per, S->s.dim0, seed + S->t0 + t, S->stream);
     HIP_OK(hipStreamSynchronize(S->stream));
     S->have_db = true;
@@ -323,13 +446,13 @@ int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server* S, const uint6
     return 0;
 }
 
-// everything up to and including the folding, for this server's trials: their folded ciphertexts end up at the head of each trial's
-// num_per slots of S->raw (events 0..5 bracket the stages)
-static int pk_front(spiral_gpu_pack_server* S, const uint64_t* query) {
+// The answer up to and including the folding, for this server's trials, in three pieces (pk_front; answer_batch puts one shared sweep between the
+// lanes' first and last pieces): the folded ciphertexts end up at the head of each trial's num_per slots of S->raw (events 0..5 bracket the stages).
+// Piece 1: query upload, expansion and conversion -> the sweep's records qs1 and the folding keys, on `st`
+static int pk_expand_convert(spiral_gpu_pack_server* S, const uint64_t* query, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
-    hipStream_t st = S->stream;
-    const uint32_t ell = s.ell, ngs = p.nu2 * ell, nt = S->nt;
+    const uint32_t ell = s.ell, ngs = p.nu2 * ell;
     if (pk_upload_ref_ntt(S, query, S->query.p, (size_t)s.n_query_cts * 2)) return -1;
 
     HIP_OK(hipEventRecord(S->ev[0], st));
@@ -368,8 +491,15 @@ static int pk_front(spiral_gpu_pack_server* S, const uint64_t* query) {
     }
     launch_pack_fold_key(S->gsw.p, S->key.p, ell, p.nu2, st);
     HIP_OK(hipEventRecord(S->ev[2], st));
-    // ---- first dimension for every trial (:1049-1051), then one INTT + CRT lift (:1055-1057)
-    launch_sweep1(S->db.p, (const uint32_t*)S->qs1.p, S->acc.p, s.num_per, s.dim0, nt, S->db_words, (size_t)s.num_per * 2 * kN, st);
+    S->have_records = true;
+    return 0;
+}
+
+// piece 3 (piece 2 is pk_sweep: the first dimension for every trial, :1049-1051): one INTT + CRT lift (:1055-1057) and the folding, on `st`
+static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) {
+    const spiral_gpu_params& p = S->p;
+    const spiral_gpu_pack_shape& s = S->s;
+    const uint32_t ell = s.ell, nt = S->nt;
     HIP_OK(hipEventRecord(S->ev[3], st));
     HIP_OK(hipEventRecord(S->ev[4], st));  // (the lift is chained into the first fold round's digit transforms)
     // ---- foldCiphertextsDim1 (:596-624), all trials batched: each round = fold_chain_kernel (lift of the previous
@@ -436,10 +566,15 @@ static int pk_front(spiral_gpu_pack_server* S, const uint64_t* query) {
     return 0;
 }
 
+static int pk_front(spiral_gpu_pack_server* S, const uint64_t* query) {
+    spiral_gpu_pack_server* one[1] = {S};
+    if (pk_expand_convert(S, query, S->stream) || pk_sweep(one, 1, S->stream)) return -1;
+    return pk_fold(S, S->stream);
+}
+
 // pack + modulus switch (:1064-1081) of out_n^2 folded ciphertexts at a stride of `ct_stride` ciphertexts; event 6 closes it
-static int pk_back(spiral_gpu_pack_server* S, const uint64_t* folded, uint32_t ct_stride) {
+static int pk_back(spiral_gpu_pack_server* S, const uint64_t* folded, uint32_t ct_stride, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
-    hipStream_t st = S->stream;
     const uint32_t rows = S->out_n + 1;
     run_pack(S->tb, folded, ct_stride, S->v_w.p, S->pk_ginv.p, S->pk_ct2.p, S->pk_res.p, S->out_n, p.t_conv, st);
     InvParams ip{};
@@ -468,11 +603,105 @@ static int pk_download(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* 
 
 int spiral_gpu_pack_server_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
     if (!S || !query) return fail("null argument");
+    if (S->zombie) return fail("destroyed server");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db || !S->have_pp) return fail("database and public parameters must be set first");
+    if (!pk_holder(S)->have_db || !S->have_pp) return fail("database and public parameters must be set first");
     if (S->nt != S->s.trials) return fail("this server holds trials [%u, %u) only: fold_trials + pack_gathered", S->t0, S->t0 + S->nt);
-    if (pk_front(S, query) || pk_back(S, S->raw.p, S->s.num_per) || pk_download(S, response, packed_ct)) return -1;
+    if (pk_front(S, query) || pk_back(S, S->raw.p, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
     return stage_us ? spiral_gpu_pack_server_stage_us(S, stage_us) : 0;
+}
+
+// the lanes of a batch: n in 1 .. kMaxLanes distinct servers that sweep the same images (an owner and its lanes), none trial-sharded, every one
+// with its public parameters (and, want_records, a converted query) -- checked before anything is launched
+static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bool want_records, const char* what) {
+    if (!servers) return fail("%s: null argument", what);
+    if (n == 0 || n > kMaxLanes) return fail("%s: %u servers, 1 .. %u per batch", what, n, kMaxLanes);
+    for (uint32_t b = 0; b < n; b++)
+        if (!servers[b] || servers[b]->zombie) return fail("%s: server %u is null or destroyed", what, b);
+    spiral_gpu_pack_server* H = pk_holder(servers[0]);
+    if (H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
+    if (!H->have_db) return fail("%s: no database loaded", what);
+    for (uint32_t b = 0; b < n; b++) {
+        const spiral_gpu_pack_server* L = servers[b];
+        for (uint32_t c = 0; c < b; c++)
+            if (servers[c] == L) return fail("%s: server %u appears twice", what, b);
+        if (pk_holder(servers[b]) != H) return fail("%s: server %u does not sweep server 0's database image (create_lane)", what, b);
+        if (memcmp(&L->p, &H->p, sizeof(L->p)) != 0 || L->out_n != H->out_n || L->device != H->device || L->nt != H->nt)
+            return fail("%s: server %u has other parameters than server 0", what, b);
+        if (!L->have_pp) return fail("%s: server %u has no public parameters", what, b);
+        if (want_records && !L->have_records) return fail("%s: server %u has no converted query (answer it once first)", what, b);
+    }
+    return 0;
+}
+
+// Beyond the reference (one query per call): n <= kMaxLanes queries, one per server, in one launch sequence on servers[0]'s stream -- expansion and
+// conversion per lane, ONE first-dimension pass over the trial images for all of them (matrix cores, once the image is in limb-plane form: the first
+// batch on a covered geometry converts it), then folding, packing and the modulus switch per lane.  Returns synchronised.
+int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
+                                        uint64_t* const* packed_cts, double stage_us[8]) {
+    if (pk_check_lanes(servers, n, false, "answer_batch")) return -1;
+    if (!queries) return fail("answer_batch: null queries");
+    for (uint32_t b = 0; b < n; b++)
+        if (!queries[b]) return fail("answer_batch: query %u is null", b);
+    if (n == 1) return spiral_gpu_pack_server_answer(servers[0], queries[0], responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
+    spiral_gpu_pack_server* S = servers[0];
+    spiral_gpu_pack_server* H = pk_holder(S);
+    HIP_OK(hipSetDevice(S->device));
+    if (H->db_format != SPIRAL_GPU_DB_LIMBS && sweep1_mfma_ok(H->s.num_per, H->s.dim0) && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+    hipStream_t st = S->stream;
+    for (uint32_t b = 0; b < n; b++)
+        if (pk_expand_convert(servers[b], queries[b], st)) return -1;
+    if (pk_sweep(servers, n, st)) return -1;
+    HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at servers[n - 1]'s event 2)
+    for (uint32_t b = 0; b < n; b++) {
+        spiral_gpu_pack_server* L = servers[b];
+        if (pk_fold(L, st) || pk_back(L, L->raw.p, L->s.num_per, st)) return -1;
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    for (uint32_t b = 0; b < n; b++)
+        if (pk_download(servers[b], responses ? responses[b] : nullptr, packed_cts ? packed_cts[b] : nullptr)) return -1;
+    if (!stage_us) return 0;
+    // the lanes' stages ran one after another on one stream: [0], [1], [3], [4] are the sums over the lanes, [2] = [5] the one shared sweep
+    for (int i = 0; i < 8; i++) stage_us[i] = 0;
+    for (uint32_t b = 0; b < n; b++) {
+        spiral_gpu_pack_server* L = servers[b];
+        float ms[4] = {};
+        HIP_OK(hipEventElapsedTime(&ms[0], L->ev[0], L->ev[1]));
+        HIP_OK(hipEventElapsedTime(&ms[1], L->ev[1], L->ev[2]));
+        HIP_OK(hipEventElapsedTime(&ms[2], L->ev[4], L->ev[5]));
+        HIP_OK(hipEventElapsedTime(&ms[3], L->ev[5], L->ev[6]));
+        stage_us[0] += ms[0] * 1e3, stage_us[1] += ms[1] * 1e3, stage_us[3] += ms[2] * 1e3, stage_us[4] += ms[3] * 1e3;
+    }
+    float sw = 0, total = 0;
+    HIP_OK(hipEventElapsedTime(&sw, servers[n - 1]->ev[2], S->ev[7]));
+    HIP_OK(hipEventElapsedTime(&total, S->ev[0], servers[n - 1]->ev[6]));
+    stage_us[2] = stage_us[5] = sw * 1e3;
+    stage_us[6] = total * 1e3;
+    stage_us[7] = n;
+    return 0;
+}
+
+// the batched first-dimension sweep alone (answer_batch's), iters times on servers[0]'s stream with the lanes' current records, timed with device
+// events; as answer_batch, a covered geometry's image is converted to limb planes first
+int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server* const* servers, uint32_t n, int iters, float* avg_ms) {
+    if (!avg_ms || iters <= 0) return fail("time_sweep_batch: bad argument");
+    if (pk_check_lanes(servers, n, true, "time_sweep_batch")) return -1;
+    spiral_gpu_pack_server* S = servers[0];
+    spiral_gpu_pack_server* H = pk_holder(S);
+    HIP_OK(hipSetDevice(S->device));
+    if (H->db_format != SPIRAL_GPU_DB_LIMBS && sweep1_mfma_ok(H->s.num_per, H->s.dim0) && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipEventRecord(S->ev[0], S->stream));
+    for (int i = 0; i < iters; i++)
+        if (pk_sweep(servers, n, S->stream)) return -1;
+    HIP_OK(hipEventRecord(S->ev[1], S->stream));
+    HIP_OK(hipStreamSynchronize(S->stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
+    *avg_ms = ms / iters;
+    for (uint32_t b = 0; b < n; b++) servers[b]->packed_after_front = false;
+    return 0;
 }
 
 // stage times of the last answer (or fold_trials [+ pack_gathered]) from the events between its stages; synchronises the stream.
@@ -501,7 +730,7 @@ int spiral_gpu_pack_server_stage_us(spiral_gpu_pack_server* S, double stage_us[8
 int spiral_gpu_pack_server_fold_trials(spiral_gpu_pack_server* S, const uint64_t* query, void* folded_dev) {
     if (!S || !query || !folded_dev) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db || !S->have_pp) return fail("database and public parameters must be set first");
+    if (!pk_holder(S)->have_db || !S->have_pp) return fail("database and public parameters must be set first");
     if (pk_front(S, query)) return -1;
     HIP_OK(hipMemcpy2DAsync(folded_dev, 2 * kPolyBytes, S->raw.p, (size_t)S->s.num_per * 2 * kPolyBytes, 2 * kPolyBytes, S->nt, hipMemcpyDeviceToDevice,
                             S->stream));
@@ -514,7 +743,7 @@ int spiral_gpu_pack_server_pack_gathered(spiral_gpu_pack_server* S, const void* 
     if (!S || !gathered_dev) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_pp) return fail("public parameters must be set first");
-    if (pk_back(S, (const uint64_t*)gathered_dev, 1)) return -1;
+    if (pk_back(S, (const uint64_t*)gathered_dev, 1, S->stream)) return -1;
     return pk_download(S, response, packed_ct);
 }
 

@@ -24,6 +24,9 @@
 // A wave owns (z, 16 columns) and streams its 2 x K/128 x 7 KiB front to back, one 1 KiB load instruction at a time.
 // The B operands (query limbs) are built in LDS from the lanes' ordinary 48-byte query records by the workgroup (all its waves share z) and read
 // back with conflict-free ds_read_b128.
+// The same kernel (ROWS = 2) is the SpiralPack batch's sweep (pack_server.cpp, answer_batch): 1 x 1 plaintexts and 2-row 16-byte records, K = dim0
+// terms per column, every trial image of the server in one launch.  Coverage: sweep1_mfma_ok (>= 128 ciphertexts per slot, dim0 a power of two in
+// [128, 4096]); other pack geometries sweep once per query on the vector ALU (pack.hip).
 #include <atomic>
 #include <cstdlib>
 #include "common.h"
@@ -160,6 +163,12 @@ struct SweepLanes {
     const uint32_t* qs[kMaxLanes];
     uint64_t* acc[kMaxLanes];
 };
+// ROWS = 2 (the SpiralPack sweep) only: work items are (trial, group of 128 columns, z), the trials' images db_stride uint4 and their accumulators
+// acc_stride words apart, 2^grp_log column groups per trial
+struct SweepTrials {
+    size_t db_stride, acc_stride;
+    uint32_t grp_log;
+};
 
 template <typename T>
 __device__ __forceinline__ T pick_lane(const T (&a)[kMaxLanes], uint32_t q) {  // (a dynamic index would put the argument struct in scratch)
@@ -221,23 +230,25 @@ __device__ __forceinline__ void combine_limbs(const v4i (&acc)[4][NT], uint32_t 
 }
 
 // The query limbs of one piece (work item, prime, 128 terms) are staged in one of two LDS buffers laid out [chunk of 64 terms][n-tile][lane][16 B],
-// lane l of a tile = (column n & 15 = l & 15, term block l >> 4), column n = 12 q + 4 r + limb.  A thread takes R items = (query, row, four
-// consecutive terms): four 28-bit values -> 4 x 4 limb bytes, transposed with v_perm into one dword per limb.  What a thread's items are does not
+// lane l of a tile = (column n & 15 = l & 15, term block l >> 4), column n = 4 ROWS q + 4 r + limb.  A thread takes R items = (query, row, four
+// consecutive terms): four 28-bit values -> 4 x 4 limb bytes, transposed with v_perm into one dword per limb.
+// Query records (u32 residues): term t of slot z, prime pr, row r at (z K + t) 2 ROWS + pr ROWS + r, K = 2 dim0 terms per column.  ROWS = 3: the base
+// path's 48-byte record [m][prime][3 rows] per (z, j), t = 2 j + m; ROWS = 2: SpiralPack's qs1 record {p r0, p r1, b r0, b r1} per (z, j), t = j.  What a thread's items are does not
 // change from piece to piece: source pointer (the query's records + the item's offset inside a piece's block) and LDS offset are computed once.
 // The loads are issued one piece ahead of the stores so that no wave waits for them.
-template <int NT, int R>
+template <int NT, int R, int ROWS>
 struct RecPlan {
     const uint32_t* src[R];
     uint32_t lds[R];  // dword index in a limb buffer; ~0u: this slot has no item
     uint32_t v[R][4];
     __device__ __forceinline__ void init(const SweepLanes& bt, uint32_t nb) {
-        const uint32_t n_items = nb * 96u;  // 3 rows x 32 groups of four terms per query
+        const uint32_t n_items = nb * 32u * ROWS;  // ROWS rows x 32 groups of four terms per query
 #pragma unroll
         for (int i = 0; i < R; i++) {
             const uint32_t t0 = threadIdx.x + (uint32_t)i * blockDim.x, t = min(t0, n_items - 1u);
-            const uint32_t r = t % 3u, q = (t / 3u) % nb, k4 = t / (3u * nb);  // terms 4 k4 .. + 3 = (j, m = 0, 1), (j + 1, m = 0, 1), j = 2 k4
-            src[i] = pick_lane(bt.qs, q) + (size_t)k4 * 24u + r;
-            const uint32_t n = q * 12u + r * 4u, k = k4 * 4u;
+            const uint32_t r = t % ROWS, q = (t / ROWS) % nb, k4 = t / (ROWS * nb);  // terms 4 k4 .. + 3 (ROWS = 3: (j, m = 0, 1), (j + 1, m = 0, 1), j = 2 k4)
+            src[i] = pick_lane(bt.qs, q) + (size_t)k4 * (8u * ROWS) + r;
+            const uint32_t n = q * (4u * ROWS) + r * 4u, k = k4 * 4u;
             lds[i] = t0 < n_items ? ((((k >> 6) * NT + (n >> 4)) * 64u + ((k >> 4) & 3u) * 16u + (n & 15u)) << 2) + ((k & 15u) >> 2) : ~0u;
         }
     }
@@ -250,7 +261,7 @@ struct RecPlan {
             const uint4 x = *reinterpret_cast<const uint4*>(reinterpret_cast<uintptr_t>(rec) & ~(uintptr_t)15);
             v[i][0] = x.x, v[i][1] = x.y, v[i][2] = x.z, v[i][3] = x.w;
 #else
-            v[i][0] = rec[0], v[i][1] = rec[6], v[i][2] = rec[12], v[i][3] = rec[18];
+            v[i][0] = rec[0], v[i][1] = rec[2 * ROWS], v[i][2] = rec[4 * ROWS], v[i][3] = rec[6 * ROWS];
 #endif
         }
     }
@@ -278,7 +289,12 @@ struct RecPlan {
     }
 };
 
-// NT: n-tiles of 16 columns, 12 per query (NT = 1 .. 6 for up to 1, 2, 4, 5, 6, 8 queries).  512 threads = 8 waves = 128 columns of one z.
+// NT: n-tiles of 16 columns, 4 ROWS per query (ROWS = 3: NT = 1 .. 6 for up to 1, 2, 4, 5, 6, 8 queries; ROWS = 2: NT = 1 .. 4 for up to 2, 4, 6, 8).
+// 512 threads = 8 waves = 128 columns of one z.
+// ROWS = 2 is the SpiralPack sweep (pack.hip sweep1_kernel: acc[ii][r][z] = sum_j db[z][j][ii] q[z][j][r], 1 x 1 plaintexts): its packed trial image is
+// byte for byte the base packed image of nic = num_per columns and K = dim0 terms (common.h / kernels.h: both put 16 terms of a lane in one 112-byte
+// group), so the limb planes, the A operands and the piece stream are the base kernel's with nic = num_per, dim0 / 2 in place of dim0; the records
+// (ROWS), the accumulator positions and the trial dimension of the work items differ.
 // Workgroups are persistent, one per CU: each takes a contiguous run of work items w = (group of 128 columns, z), z fastest, and a wave's stream of
 // pieces and the pieces' query limbs run ahead across item boundaries, so the database stream never drains (a workgroup per item, with its limbs
 // built up front, reached 430 - 500 us).  One loop trip = one piece, straight-line: every global load of a trip (7 of the database, 4 R of
@@ -286,9 +302,9 @@ struct RecPlan {
 // The only conditional memory operations are the accumulator stores, once per 2^zs_log items.  (Two and four pieces per trip -- 14 and 28 KiB in
 // flight per wave -- measured 2 - 5 % slower than one: the registers are better spent elsewhere.)
 // dynamic LDS = 2 limb buffers x 2 NT KiB + 8 x NT x 64 x 2^zs_log result words.
-template <int NT>
+template <int NT, int ROWS>
 __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restrict__ dbl, SweepLanes bt, uint32_t nb, uint32_t nic, uint32_t dim0, uint32_t g_log,
-                                                            uint32_t ls_log, uint32_t n_work, uint32_t zs_log) {
+                                                            uint32_t ls_log, uint32_t n_work, uint32_t zs_log, SweepTrials tr) {
     extern __shared__ __attribute__((aligned(16))) uint4 bq[];
     constexpr int R = NT >= 5 ? 2 : 1;  // 96 items per query and piece over 512 threads: one each up to five queries
     constexpr uint32_t buf_sz = 2u * NT * 64u, W = 8;
@@ -301,15 +317,20 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
     const u32x4* const db0 = reinterpret_cast<const u32x4*>(dbl) + lane;
     auto piece_ptr = [&](uint32_t g) -> const u32x4* {  // piece g of this workgroup's run (clamped to its last one)
         g = min(g, total - 1u);
-        const uint32_t w = w0 + (g >> ppi_log), p = g & (ppi - 1u), z = w & (kN - 1u), icb = (w >> kLogN) * W + wv;
+        const uint32_t w = w0 + (g >> ppi_log), p = g & (ppi - 1u), z = w & (kN - 1u);
+        if constexpr (ROWS == 2) {
+            const uint32_t grp = w >> kLogN, trial = grp >> tr.grp_log, icb = (grp & ((1u << tr.grp_log) - 1u)) * W + wv;
+            return db0 + trial * tr.db_stride + ((((size_t)z * (nic >> 4) + icb) << ppi_log) + p) * (7u * 64u);
+        }
+        const uint32_t icb = (w >> kLogN) * W + wv;
         return db0 + ((((size_t)z * (nic >> 4) + icb) << ppi_log) + p) * (7u * 64u);
     };
-    RecPlan<NT, R> rec;
+    RecPlan<NT, R, ROWS> rec;
     rec.init(bt, nb);
     auto rec_issue = [&](uint32_t g) {  // the record loads of piece g of the run (clamped to its last one)
         g = min(g, total - 1u);
         const uint32_t w = w0 + (g >> ppi_log), p = g & (ppi - 1u), z = w & (kN - 1u);
-        rec.issue((z * dim0 + (p >= nk2 ? p - nk2 : p) * 64u) * 12u + (p >= nk2 ? 3u : 0u));
+        rec.issue((z * dim0 + (p >= nk2 ? p - nk2 : p) * 64u) * (4u * ROWS) + (p >= nk2 ? (uint32_t)ROWS : 0u));
     };
     u32x4 d[7];
     {
@@ -376,8 +397,8 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
         } else if (p_end == 0) {
             uint32_t res1[NT];
             combine_limbs<NT, kB>(acc, lane, res1);
-            // A lane's result (column ic, query q, row r) is one 8-byte word of accumulator polynomial (q; 6 ii + 2 r + c) at slot z: 16 KiB from
-            // the next lane's.  The wave parks the words of 2^zs_log consecutive z in its own LDS rows [tile][lane][z] and then writes them as
+            // A lane's result (column ic, query q, row r) is one 8-byte word of accumulator polynomial (q; 6 ii + 2 r + c) at slot z (ROWS = 2:
+            // (q; trial; 2 ic + r)): 16 KiB from the next lane's.  The wave parks the words of 2^zs_log consecutive z in its own LDS rows [tile][lane][z] and then writes them as
             // 8 * 2^zs_log-byte runs, 16 bytes per lane (scattered 8-byte stores cost 80 - 130 us per launch at config 2).
             const uint32_t w = w0 + (g >> ppi_log), z = w & (kN - 1u), zs = 1u << zs_log, zi = z & (zs - 1u);
             uint64_t* const st = reinterpret_cast<uint64_t*>(bq + 2u * buf_sz) + (size_t)wv * (NT * 64u << zs_log);
@@ -386,13 +407,24 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
             if (zi == zs - 1u) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
-                const uint32_t icb = (w >> kLogN) * W + wv, half_log = zs_log - 1u;  // 2^half_log 16-byte pieces per entry
-                for (uint32_t idx = lane; idx < (NT * 64u) << half_log; idx += 64u) {
-                    const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;  // entry = (tile, source lane)
-                    const uint32_t ic = icb * 16u + (ls >> 4) * 4u + (ls & 3u), i0 = ic >> 1, c = ic & 1u, ii = acc_pos(i0, g_log, ls_log);
-                    const uint32_t qr = t * 4u + ((ls & 15u) >> 2), q = qr / 3u, r = qr - q * 3u;
-                    const uint4 v = reinterpret_cast<const uint4*>(st)[idx];
-                    if (q < nb) *reinterpret_cast<uint4*>(pick_lane(bt.acc, q) + ((size_t)(6u * ii + 2u * r + c)) * kN + (z - zi) + 2u * part) = v;
+                const uint32_t half_log = zs_log - 1u;  // 2^half_log 16-byte pieces per entry
+                if constexpr (ROWS == 2) {
+                    const uint32_t grp = w >> kLogN, trial = grp >> tr.grp_log, icb = (grp & ((1u << tr.grp_log) - 1u)) * W + wv;
+                    for (uint32_t idx = lane; idx < (NT * 64u) << half_log; idx += 64u) {
+                        const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;
+                        const uint32_t ic = icb * 16u + (ls >> 4) * 4u + (ls & 3u), qr = t * 4u + ((ls & 15u) >> 2), q = qr >> 1, r = qr & 1u;
+                        const uint4 v = reinterpret_cast<const uint4*>(st)[idx];
+                        if (q < nb) *reinterpret_cast<uint4*>(pick_lane(bt.acc, q) + trial * tr.acc_stride + ((size_t)(2u * ic + r)) * kN + (z - zi) + 2u * part) = v;
+                    }
+                } else {
+                    const uint32_t icb = (w >> kLogN) * W + wv;
+                    for (uint32_t idx = lane; idx < (NT * 64u) << half_log; idx += 64u) {
+                        const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;  // entry = (tile, source lane)
+                        const uint32_t ic = icb * 16u + (ls >> 4) * 4u + (ls & 3u), i0 = ic >> 1, c = ic & 1u, ii = acc_pos(i0, g_log, ls_log);
+                        const uint32_t qr = t * 4u + ((ls & 15u) >> 2), q = qr / 3u, r = qr - q * 3u;
+                        const uint4 v = reinterpret_cast<const uint4*>(st)[idx];
+                        if (q < nb) *reinterpret_cast<uint4*>(pick_lane(bt.acc, q) + ((size_t)(6u * ii + 2u * r + c)) * kN + (z - zi) + 2u * part) = v;
+                    }
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
@@ -424,27 +456,20 @@ void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, 
     const size_t waves = (size_t)nz * (nic >> 4) * (dim0 >> 6);
     if (waves) hipLaunchKernelGGL(db_limb_unplanes_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const uint4*>(db_limbs), db_packed_img, nic, dim0, nz);
 }
-hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
-                             hipStream_t s, uint32_t k_log) {
-    const uint32_t nic = 2 * num_per, dim0 = jm_total / 2;
-    uint32_t ls_log = 0;
-    while ((1u << ls_log) < num_per) ls_log++;
-    ls_log -= g_log + k_log;
-    SweepLanes bt{};
-    for (uint32_t b = 0; b < kMaxLanes; b++) {
-        bt.qs[b] = qs[b < n ? b : 0];
-        bt.acc[b] = acc[b < n ? b : 0];
-    }
-    const uint32_t nt = (12u * n + 15u) / 16u;
-    // one workgroup per CU (two per CU with half the staging measured 5 % slower); per = 8 nic / 128 items each
-    const uint32_t n_work = kN * (nic >> 7), n_wg = 256u, per = n_work / n_wg;
+namespace {
+
+// one launch of sweep_mfma_kernel<nt, ROWS> over n_work items (dim0: half the terms per column, as the kernel takes it)
+template <int ROWS>
+hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint32_t nt, uint32_t nic, uint32_t dim0, uint32_t g_log, uint32_t ls_log, uint32_t n_work,
+                       const SweepTrials& tr, hipStream_t s) {
+    // one workgroup per CU (two per CU with half the staging measured 5 % slower); per = 8 nic / 128 items each (base path)
+    const uint32_t n_wg = 256u, per = n_work / n_wg;
     // results of 2^zs_log consecutive z are staged per wave (8 x nt x 64 x 2^zs_log words) beside the two limb buffers: 8 if that fits the CU's LDS
     const size_t lds_b = (size_t)2u * 2u * nt * 1024u;
     uint32_t zs_log = 3;
     while (zs_log > 1 && ((1u << zs_log) > per || lds_b + ((size_t)8u * nt * 64u * 8u << zs_log) > 160u * 1024u)) zs_log--;
     const size_t lds = lds_b + ((size_t)8u * nt * 64u * 8u << zs_log);
     const dim3 grid(n_wg), block(512);
-    const uint4* dbl = reinterpret_cast<const uint4*>(db_limbs);
     // more than 64 KiB of dynamic LDS has to be asked for per kernel AND per device: a process may drive servers on several GPUs, from several
     // threads, so the opt-in is remembered per (instance, device) in an atomic bit mask (devices beyond 63 ask every time)
     int dev = 0;
@@ -455,23 +480,65 @@ hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs
         static std::atomic<uint64_t> big{0};                                                                                                       \
         const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;                                                                                        \
         if (!(big.load(std::memory_order_relaxed) & bit)) {                                                                                        \
-            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
+            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);            \
             if (e != hipSuccess) return e;                                                                                                         \
             big.fetch_or(bit, std::memory_order_relaxed);                                                                                          \
         }                                                                                                                                          \
-        hipLaunchKernelGGL((sweep_mfma_kernel<NTV>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log);                  \
+        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);         \
     } while (0)
     switch (nt) {
         case 1: SWEEP_MFMA(1); break;
         case 2: SWEEP_MFMA(2); break;
         case 3: SWEEP_MFMA(3); break;
         case 4: SWEEP_MFMA(4); break;
-        case 5: SWEEP_MFMA(5); break;
-        case 6: SWEEP_MFMA(6); break;
+        case 5: if constexpr (ROWS == 3) SWEEP_MFMA(5); else return hipErrorInvalidValue; break;
+        case 6: if constexpr (ROWS == 3) SWEEP_MFMA(6); else return hipErrorInvalidValue; break;
         default: return hipErrorInvalidValue;
     }
 #undef SWEEP_MFMA
     return hipGetLastError();  // a launch that was refused (LDS, grid) is reported here, not at some later synchronisation
+}
+
+SweepLanes sweep_lanes(const uint32_t* const* qs, uint64_t* const* acc, uint32_t n) {
+    SweepLanes bt{};
+    for (uint32_t b = 0; b < kMaxLanes; b++) {
+        bt.qs[b] = qs[b < n ? b : 0];
+        bt.acc[b] = acc[b < n ? b : 0];
+    }
+    return bt;
+}
+
+}  // namespace
+
+hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
+                             hipStream_t s, uint32_t k_log) {
+    const uint32_t nic = 2 * num_per, dim0 = jm_total / 2;
+    uint32_t ls_log = 0;
+    while ((1u << ls_log) < num_per) ls_log++;
+    ls_log -= g_log + k_log;
+    const uint32_t nt = (12u * n + 15u) / 16u;
+    return launch_mfma<3>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs, acc, n), n, nt, nic, dim0, g_log, ls_log, kN * (nic >> 7), SweepTrials{}, s);
+}
+
+bool sweep1_mfma_ok(uint32_t num_per, uint32_t dim0) {
+    // the base rule for nic = num_per columns and K = dim0 terms: num_per >= 128 (whole workgroups of 128 columns, a power of two), dim0 a power of two
+    // in [128, 4096] (whole pieces of 128 terms; K <= 2^12 for combine_limbs' 64-bit sums) -- and the packed trial layout (kernels.h) to convert from
+    return (num_per & 1u) == 0 && sweep_mfma_ok(num_per / 2, dim0) && db1_packed(num_per, dim0);
+}
+void launch_db1_limb_planes(const uint64_t* packed_img, uint64_t* limbs, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz) {
+    launch_db_limb_planes(packed_img, limbs, num_per / 2, dim0, s, nz);  // (the same image: nic = num_per columns, jm_total = dim0 terms)
+}
+void launch_db1_limb_unplanes(const uint64_t* limbs, uint64_t* packed_img, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz) {
+    launch_db_limb_unplanes(limbs, packed_img, num_per / 2, dim0, s, nz);
+}
+hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* qs1, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t dim0, uint32_t trials,
+                              size_t db_stride, size_t acc_stride, hipStream_t s) {
+    if (n == 0 || n > kMaxLanes || trials == 0 || !sweep1_mfma_ok(num_per, dim0) || (db_stride & 1u)) return hipErrorInvalidValue;
+    uint32_t grp_log = 0;
+    while ((128u << grp_log) < num_per) grp_log++;
+    const uint32_t nt = (8u * n + 15u) / 16u;
+    const SweepTrials tr{db_stride / 2u, acc_stride, grp_log};
+    return launch_mfma<2>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0, (kN << grp_log) * trials, tr, s);
 }
 
 }  // namespace spiral

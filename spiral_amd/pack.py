@@ -125,3 +125,67 @@ class PackServer:
 
     def sweep_bytes(self) -> int:
         return int(lib().spiral_gpu_pack_server_sweep_bytes(self.h))
+
+    def create_lane(self) -> "PackServer":
+        """a query lane: a new server with this one's parameters, out_n and device that sweeps THIS server's trial images (answer_batch);
+        its own public parameters, query and intermediates; loads through it fail"""
+        h = C.c_void_p()
+        check(lib().spiral_gpu_pack_server_create_lane(self.h, C.byref(h)))
+        lane = PackServer.__new__(PackServer)
+        lane.params, lane.out_n, lane.shape, lane.h = self.params, self.out_n, self.shape, h
+        lane.trial0, lane.trial1 = self.trial0, self.trial1
+        return lane
+
+    def set_db_format(self, fmt: int):
+        """convert the trial images in place: DB_PACKED (0) or DB_LIMBS (1, the batched matrix-core sweep's form; only where that sweep applies)"""
+        check(lib().spiral_gpu_pack_server_set_db_format(self.h, int(fmt)))
+
+    def db_format(self) -> int:
+        return int(lib().spiral_gpu_pack_server_db_format(self.h))
+
+    def db_device_bytes(self) -> int:
+        return int(lib().spiral_gpu_pack_server_db_device_bytes(self.h))
+
+
+DB_PACKED, DB_LIMBS = 0, 1
+MAX_LANES = 8
+
+
+def _lane_handles(servers, what: str):
+    servers = list(servers)
+    if not 1 <= len(servers) <= MAX_LANES:
+        raise ValueError(f"{what}: {len(servers)} servers, 1 .. {MAX_LANES} per batch")
+    if not all(isinstance(s, PackServer) for s in servers):
+        raise TypeError(f"{what}: every server must be a PackServer")
+    if len({id(s) for s in servers}) != len(servers):
+        raise ValueError(f"{what}: a server appears twice")
+    if any(not getattr(s, "h", None) for s in servers):
+        raise ValueError(f"{what}: a server is closed")
+    return servers, (C.c_void_p * len(servers))(*[s.h for s in servers])
+
+
+def answer_batch(servers, queries, want_packed: bool = False):
+    """n <= 8 queries, one per server (an owner and its lanes, create_lane), answered with ONE first-dimension pass over the trial images:
+    ([(response, packed or None) per server], stage times of the batch).  Each lane's results equal its own answer's."""
+    servers, hs = _lane_handles(servers, "answer_batch")
+    queries = list(queries)
+    if len(queries) != len(servers):
+        raise ValueError(f"answer_batch: {len(queries)} queries for {len(servers)} servers")
+    qs = [_c(q) for q in queries]
+    n = servers[0].out_n
+    resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
+    packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
+    arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
+    us = (C.c_double * 8)()
+    check(lib().spiral_gpu_pack_server_answer_batch(hs, len(servers), arr(qs), arr(resp), arr(packed), us))
+    return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
+
+
+def time_sweep_batch(servers, iters: int = 10) -> float:
+    """the batched first-dimension sweep alone (with the lanes' current queries, each answered once): average ms per pass"""
+    servers, hs = _lane_handles(servers, "time_sweep_batch")
+    if int(iters) < 1:
+        raise ValueError("time_sweep_batch: iters >= 1")
+    ms = C.c_float()
+    check(lib().spiral_gpu_pack_server_time_sweep_batch(hs, len(servers), int(iters), C.byref(ms)))
+    return float(ms.value)
