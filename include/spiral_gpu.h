@@ -186,6 +186,19 @@ int spiral_gpu_server_gen_db(spiral_gpu_server *s, uint64_t seed);
  * larger than host memory). */
 int spiral_gpu_server_load_db_items(spiral_gpu_server *s, const void *items, uint32_t coeff_bits, uint64_t first_item,
                                     uint64_t n_items);
+/* Replace n items, given by index, of the database this server holds, in place and in the image's CURRENT form (packed or limb
+ * planes; with option one_image = 0 a valid second limb-plane image is updated too).  items: n plaintexts laid out as for
+ * load_db_items (coeff_bits wide, bit-packed, or coeff_bits = 64 raw words); item_ids[k] is the database index of plaintext k.  Ids
+ * must be distinct and < dim0 * num_per.  A sharded server writes the ids in its own j-range and skips the rest.
+ * The image is never converted and keeps its address, so graphs captured before replay afterwards and read the new items.
+ * Atomic: a bad argument, a duplicate or out-of-range id, a coefficient >= p_db, a call on a lane or share_db server (update through
+ * the owner), an allocation failure or a call while the server's stream is being captured fails and leaves the image byte-identical.
+ * Ordering: the update is enqueued on this server's stream -- work submitted to that stream earlier reads the old items, work submitted
+ * later the new ones (run_query_batch with this server as servers[0] is ordered by it) -- and nothing synchronises the device.  Lanes on
+ * other streams are the caller's to order, as for loads.  The call returns once `items` and `item_ids` may be reused; it waits for the
+ * previous update's launches (whose workspace it reuses) and for nothing else. */
+int spiral_gpu_server_update_db_items(spiral_gpu_server *s, const void *items, uint32_t coeff_bits, const uint64_t *item_ids,
+                                      uint64_t n);
 /* read the device database back in reference layouts (tests): plaintext `item` as its n0 x n2 NTT-form MatPoly
  * (pts_encd, :1128), or slabs z_begin .. z_begin+nz-1 of load_db's layout restricted to this server's j-range:
  * word (z, ii, c, j, m) at ((((z - z_begin)*num_per + ii)*n2 + c)*(j_end - j_begin) + (j - j_begin))*n0 + m */
@@ -435,6 +448,10 @@ int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server *s, uint64_t se
  * coefficients, bit-packed as for spiral_gpu_server_load_db_items */
 int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server *s, uint32_t trial, const void *items, uint32_t coeff_bits,
                                          uint64_t first_item, uint64_t n_items);
+/* spiral_gpu_server_update_db_items for one trial of this server's trial range (1 x 1 plaintexts of 2048 coefficients): in place, in the
+ * trial image's current form, on this server's stream, with the same rules for failure and ordering; any other trial fails. */
+int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server *s, uint32_t trial, const void *items, uint32_t coeff_bits,
+                                           const uint64_t *item_ids, uint64_t n);
 /* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv) */
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server *s, const uint64_t *w_left, const uint64_t *w_right,
                                           const uint64_t *v, const uint64_t *v_w);

@@ -9,6 +9,8 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # SPIRAL_LIB=<path>: load another build of the library (tuning A/B runs, tools/build_variants.sh: -DSPIRAL_TUNING builds of the same sources);
 # every process of a multi-rank run inherits it.  Whatever is loaded must export every declared entry point.
@@ -106,6 +108,7 @@ PROTOTYPES = {
     "spiral_gpu_server_read_response_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "spiral_gpu_pack_server_read_response_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "spiral_gpu_server_load_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_update_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_server_read_db_item": (C.c_int, [C.c_void_p, C.c_uint64, U64P]),
     "spiral_gpu_server_read_db_slots": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, U64P]),
     "spiral_gpu_server_read_db_columns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, U64P]),
@@ -165,6 +168,7 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_load_db": (C.c_int, [C.c_void_p, C.c_uint32, U64P]),
     "spiral_gpu_pack_server_fill_db_random": (C.c_int, [C.c_void_p, C.c_uint64]),
     "spiral_gpu_pack_server_load_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_pack_server_update_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_pack_server_set_pub_params": (C.c_int, [C.c_void_p, U64P, U64P, U64P, U64P]),
     "spiral_gpu_pack_server_answer": (C.c_int, [C.c_void_p, U64P, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_read_acc": (C.c_int, [C.c_void_p, C.c_uint32, U64P]),
@@ -216,3 +220,27 @@ class SpiralGpuError(RuntimeError):
 def check(rc: int) -> None:
     if rc != 0:
         raise SpiralGpuError(lib().spiral_gpu_last_error().decode() or f"error {rc}")
+
+
+def update_args(items, coeff_bits: int, item_ids, polys_per_item: int):
+    """the argument list of an update_db_items call, checked before anything reaches the library: items as one contiguous array holding exactly
+    len(item_ids) plaintexts of polys_per_item x 2048 coeff_bits-wide coefficients, item_ids as distinct non-negative integers (-> uint64)"""
+    ids = np.asarray(item_ids)
+    if ids.ndim != 1:
+        raise ValueError("item_ids must be a flat list of item indices")
+    if ids.size == 0:
+        ids = ids.astype(np.uint64)
+    elif ids.dtype.kind not in "iu":
+        raise TypeError(f"item_ids must be integers, not {ids.dtype}")
+    if ids.size and ids.dtype.kind == "i" and (ids < 0).any():
+        raise ValueError("item_ids must be non-negative")
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    if np.unique(ids).size != ids.size:
+        raise ValueError("item_ids holds a duplicate id")
+    if not isinstance(coeff_bits, (int, np.integer)) or isinstance(coeff_bits, bool):
+        raise TypeError("coeff_bits must be an integer")
+    items = np.ascontiguousarray(items)
+    want = ids.size * polys_per_item * 2048 * int(coeff_bits)
+    if items.nbytes * 8 != want:
+        raise ValueError(f"items holds {items.nbytes} bytes, {len(ids)} plaintexts of {coeff_bits}-bit coefficients take {want // 8}")
+    return items, ids

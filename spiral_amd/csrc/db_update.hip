@@ -1,0 +1,68 @@
+// In-place update of a few database items (spiral_gpu_server_update_db_items, spiral_gpu_pack_server_update_db_items): the items' words, encoded by
+// the ingest transform (ntt.hip LD_DBGEN / LD_DBGEN1 with a linear ST_PK store), are scattered into the image in the form it is in now.
+//
+// Packed form (common.h db_put_word, kernels.h db1_put_word; the plain layouts of tiny geometries too): every word owns its 7 (or 8) bytes, so one
+// thread per word writes them and threads never meet.
+// Limb planes (sweep_mfma.hip): the three signed limb bytes of a term sit in planes of their own, but the nibble byte of (column, term t) of a
+// 128-term piece holds the top limbs of terms t and t + 64 (low and high nibble).  With the base path's terms k = 2 j + m that is item j and item
+// j ^ 32 of the same column; with SpiralPack's terms k = j, item j and j ^ 64.  The host groups the updated items into such partner pairs and one
+// thread writes both halves of each nibble byte it owns (keeping the old half when only one of the two items changes): no atomics, and no byte
+// is touched by two threads.
+#include "common.h"
+#include "kernels.h"
+
+namespace spiral {
+
+namespace {
+
+constexpr uint32_t kLimbBias = 0x808080u;  // (sweep_mfma.hip)
+
+// residue a mod m in limb form: the three limb bytes go to chunk c of the planes at `b`, the 4-bit top limb is returned
+__device__ __forceinline__ uint32_t put_limbs(uint8_t* b, uint32_t c, uint32_t a, uint32_t m) {
+    const uint32_t w = (a >= (1u << 28) - kLimbBias ? a - m : a) + kLimbBias, x = w ^ kLimbBias;
+#pragma unroll
+    for (uint32_t i = 0; i < 3; i++) b[(2u * i + c) * 1024u] = (uint8_t)(x >> (8u * i));
+    return w >> 24;
+}
+
+// block = (work entry, polynomial mc, 256 slots): entries [0, n_put) write the packed form, [n_put, n_put + n_pairs) the limb planes
+__global__ __launch_bounds__(256) void db_update_kernel(DbUpdateParams p) {
+    if (*p.err) return;  // a coefficient was not below p_db: the image stays as it was
+    const uint32_t polys = p.pack ? 1u : 4u, z = (blockIdx.x & 7u) * 256u + threadIdx.x, q = blockIdx.x >> 3;
+    const uint32_t w = q / polys, mc = q - w * polys, m = mc >> 1, c = mc & 1u;
+    if (w < p.n_put) {
+        const uint4 e = p.put[w];  // {encoded item, j local to the image, column ii, -}
+        const uint64_t v = p.enc[((size_t)e.x * polys + mc) * kN + z];
+        if (p.pack)
+            db1_put_word(p.packed, z, e.y, e.z, p.num_per, p.dim0, v);
+        else
+            db_put_word(p.packed, z, e.y, e.z * 2u + c, m, 2u * p.num_per, p.dim0, v);
+        return;
+    }
+    if (w - p.n_put >= p.n_pairs) return;
+    const uint4 e = p.pairs[w - p.n_put];  // {column ii, j of the low partner, its encoded item, the high partner's} (kDbUpdateNone: unchanged)
+    const uint32_t nic = p.pack ? p.num_per : 2u * p.num_per, col = p.pack ? e.x : e.x * 2u + c;
+    const uint32_t kt = p.pack ? e.y : 2u * e.y + m, nk2 = (p.pack ? p.dim0 : 2u * p.dim0) >> 7, t = kt & 127u;  // t < 64: the high partner is t + 64
+    const bool has_lo = e.z != kDbUpdateNone, has_hi = e.w != kDbUpdateNone;
+    const uint64_t v_lo = has_lo ? p.enc[((size_t)e.z * polys + mc) * kN + z] : 0, v_hi = has_hi ? p.enc[((size_t)e.w * polys + mc) * kN + z] : 0;
+    const uint32_t lane = ((t >> 4) & 3u) * 16u + (col & 15u);
+#pragma unroll
+    for (uint32_t pr = 0; pr < 2; pr++) {
+        const size_t piece = (((size_t)z * (nic >> 4) + (col >> 4)) * 2u + pr) * nk2 + (kt >> 7);  // 7 KiB each
+        uint8_t* b = reinterpret_cast<uint8_t*>(p.limbs) + piece * 7168u + (size_t)lane * 16u + (t & 15u);
+        const uint32_t mod = pr ? kB : kP;
+        uint32_t nib = b[6u * 1024u];
+        if (has_lo) nib = (nib & 0xF0u) | put_limbs(b, 0, pr ? hi32(v_lo) : lo32(v_lo), mod);
+        if (has_hi) nib = (nib & 0x0Fu) | (put_limbs(b, 1, pr ? hi32(v_hi) : lo32(v_hi), mod) << 4);
+        b[6u * 1024u] = (uint8_t)nib;
+    }
+}
+
+}  // namespace
+
+void launch_db_update(const DbUpdateParams& p, hipStream_t s) {
+    const uint64_t blocks = ((uint64_t)p.n_put + p.n_pairs) * (p.pack ? 1u : 4u) * (kN / 256u);
+    if (blocks) hipLaunchKernelGGL(db_update_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, p);
+}
+
+}  // namespace spiral

@@ -294,6 +294,175 @@ inline int ingest_items(const void* items, uint32_t coeff_bits, uint64_t first, 
     return 0;
 }
 
+// ---- in-place item updates (update_db_items of both servers) ---------------------------------------------------------------------
+// The image holder's workspace, reused from call to call: a pinned host buffer holding what goes up (error word, work entries, the raw items) and
+// one device buffer holding the same plus the encoded items.  `done` is recorded on the holder's stream after an update's launches: the next
+// update waits for it (the previous update only, not the device) before it rewrites either buffer.
+struct UpdateWork {
+    DevBuf dev;
+    uint8_t* host = nullptr;
+    size_t host_bytes = 0;
+    hipEvent_t done = nullptr;
+    bool pending = false;
+    void release() {
+        if (pending && done) (void)hipEventSynchronize(done);
+        dev.release();
+        dev.words = 0;
+        if (host) (void)hipHostFree(host);
+        host = nullptr;
+        host_bytes = 0;
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr;
+        pending = false;
+    }
+};
+
+// the ids of an update call: every one below `total`, no two equal (checked before anything else happens)
+inline int check_update_ids(const void* items, const uint64_t* ids, uint64_t n, uint64_t total) {
+    if (n == 0) return 0;
+    if (!items || !ids) return fail("null argument");
+    if (n > (1ull << 24)) return fail("at most 2^24 items per update");
+    std::vector<uint64_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (sorted.back() >= total) return fail("item id %llu outside the database of %llu items", (unsigned long long)sorted.back(), (unsigned long long)total);
+    for (uint64_t k = 1; k < n; k++)
+        if (sorted[k] == sorted[k - 1]) return fail("item id %llu given twice", (unsigned long long)sorted[k]);
+    return 0;
+}
+
+// true when every one of the `count` coeff_bits-wide coefficients at `item` (read as packed_coeff reads them) is below p_db
+inline bool coeffs_below(const uint8_t* item, size_t count, uint32_t coeff_bits, uint64_t p_db) {
+    if (coeff_bits == 64) {
+        for (size_t i = 0; i < count; i++) {
+            uint64_t v;
+            memcpy(&v, item + 8 * i, 8);
+            if (v >= p_db) return false;
+        }
+        return true;
+    }
+    if ((1ull << coeff_bits) <= p_db) return true;  // (every coefficient of that width is)
+    const uint64_t mask = (1ull << coeff_bits) - 1;
+    for (size_t i = 0; i < count; i++) {
+        const uint64_t bit = (uint64_t)i * coeff_bits;
+        const uint32_t sh = (uint32_t)(bit & 7u), nbytes = (sh + coeff_bits + 7u) / 8u;
+        uint64_t w = 0;
+        memcpy(&w, item + (bit >> 3), nbytes);  // (little-endian host, as the device)
+        if (((w >> sh) & mask) >= p_db) return false;
+    }
+    return true;
+}
+
+// One image's items to update: sel[k] = {position of the item in the caller's list, j local to the image, column ii}.
+struct UpdateItem {
+    uint64_t src;
+    uint32_t j, ii;
+};
+struct UpdateImage {
+    uint64_t* packed;  // the image in packed form (null: none)
+    uint64_t* limbs;   // the image in limb-plane form (null: none)
+    uint32_t pack, num_per, dim0;
+};
+// The shared body of update_db_items: checks the coefficients on the host, then ONE upload, ONE encode launch (the ingest transform, linear store)
+// and ONE scatter launch (db_update.hip) on `st`, and returns -- the caller's buffers are copied by then.  Nothing touches the image before every
+// check has passed; the scatter kernel also skips everything when the encode launch flags a coefficient.
+inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, const void* items, uint32_t coeff_bits, uint64_t p_db,
+                        const std::vector<UpdateItem>& sel, const UpdateImage& img) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("update_db_items cannot be called while the server's stream is being captured");
+    if (coeff_bits != 64 && (coeff_bits < 1 || coeff_bits > 40)) return fail("coefficient width %u not in 1..40 or 64", coeff_bits);
+    if (coeff_bits < 64 && (1ull << coeff_bits) < p_db) return fail("%u-bit coefficients cannot hold values below p_db", coeff_bits);
+    if (sel.empty()) return 0;
+    const uint32_t polys = img.pack ? 1u : 4u;
+    const size_t item_bytes = (size_t)polys * kN * coeff_bits / 8, n = sel.size();
+    const uint8_t* src = static_cast<const uint8_t*>(items);
+    for (const UpdateItem& it : sel)
+        if (!coeffs_below(src + it.src * item_bytes, (size_t)polys * kN, coeff_bits, p_db))
+            return fail("a plaintext coefficient of item %llu of the list is not below p_db", (unsigned long long)it.src);
+    // work entries: one per item for the packed form; one per partner pair (j, j ^ 32 / j ^ 64 of a column) for the limb planes
+    std::vector<uint4> put, pairs;
+    if (img.packed) {
+        put.reserve(n);
+        for (size_t k = 0; k < n; k++) put.push_back(make_uint4((uint32_t)k, sel[k].j, sel[k].ii, 0u));
+    }
+    if (img.limbs) {
+        const uint32_t bit = img.pack ? 64u : 32u;
+        std::vector<std::pair<uint64_t, uint32_t>> order(n);  // (column, j of the low partner) -> item
+        for (size_t k = 0; k < n; k++) order[k] = {((uint64_t)sel[k].ii << 32) | (sel[k].j & ~bit), (uint32_t)k};
+        std::sort(order.begin(), order.end());
+        for (size_t k = 0; k < n; k++) {
+            const uint64_t key = order[k].first;
+            if (pairs.empty() || (((uint64_t)pairs.back().x << 32) | pairs.back().y) != key)
+                pairs.push_back(make_uint4((uint32_t)(key >> 32), (uint32_t)key, kDbUpdateNone, kDbUpdateNone));
+            const uint32_t it = order[k].second;
+            (sel[it].j & bit ? pairs.back().w : pairs.back().z) = it;
+        }
+    }
+    // one buffer: [error word][put][pairs][raw items + 16 bytes of over-read room] ++ (device only) [encoded items]
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_put = 16, o_pairs = o_put + put.size() * sizeof(uint4), o_items = up16(o_pairs + pairs.size() * sizeof(uint4));
+    const size_t up_bytes = up16(o_items + n * item_bytes + 16), dev_bytes = up_bytes + n * polys * kPolyBytes;
+    if (W.pending) {
+        HIP_OK(hipEventSynchronize(W.done));  // the previous update's launches have consumed the buffers
+        W.pending = false;
+    }
+    if (!W.done && hipEventCreateWithFlags(&W.done, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate failed");
+    if (W.host_bytes < up_bytes) {
+        if (W.host) (void)hipHostFree(W.host);
+        W.host = nullptr;
+        W.host_bytes = 0;
+        if (hipHostMalloc((void**)&W.host, up_bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("no pinned host memory for an update of %zu items (%zu bytes)", n, up_bytes);
+        }
+        W.host_bytes = up_bytes;
+    }
+    if (W.dev.words * 8 < dev_bytes) {
+        W.dev.release();
+        W.dev.words = 0;
+        if (W.dev.alloc((dev_bytes + 7) / 8)) {
+            (void)hipGetLastError();
+            W.dev.p = nullptr;
+            W.dev.words = 0;
+            return fail("no device memory for an update of %zu items (%zu bytes)", n, dev_bytes);
+        }
+    }
+    memset(W.host, 0, up_bytes);
+    if (!put.empty()) memcpy(W.host + o_put, put.data(), put.size() * sizeof(uint4));
+    if (!pairs.empty()) memcpy(W.host + o_pairs, pairs.data(), pairs.size() * sizeof(uint4));
+    for (size_t k = 0; k < n; k++) memcpy(W.host + o_items + k * item_bytes, src + sel[k].src * item_bytes, item_bytes);
+    uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
+    HIP_OK(hipMemcpyAsync(d, W.host, up_bytes, hipMemcpyHostToDevice, st));
+    uint64_t* enc = reinterpret_cast<uint64_t*>(d + up_bytes);
+    FwdParams fp{};
+    fp.dst = enc;
+    fp.src_map = fp.dst_map = identity_map();
+    fp.n_digits = 1;
+    fp.p_db = p_db;
+    fp.items = d + o_items;
+    fp.coeff_bits = coeff_bits;
+    fp.err = reinterpret_cast<uint32_t*>(d);
+    fp.items_first = fp.item_base = 0;
+    launch_ntt_forward(tb, fp, img.pack ? LD_DBGEN1 : LD_DBGEN, ST_PK, (uint32_t)(n * polys), st);
+    DbUpdateParams up{};
+    up.enc = enc;
+    up.err = reinterpret_cast<const uint32_t*>(d);
+    up.packed = img.packed;
+    up.limbs = img.limbs;
+    up.put = reinterpret_cast<const uint4*>(d + o_put);
+    up.pairs = reinterpret_cast<const uint4*>(d + o_pairs);
+    up.n_put = (uint32_t)put.size();
+    up.n_pairs = (uint32_t)pairs.size();
+    up.pack = img.pack;
+    up.num_per = img.num_per;
+    up.dim0 = img.dim0;
+    launch_db_update(up, st);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipEventRecord(W.done, st));
+    W.pending = true;
+    return 0;
+}
+
 // upload reference NTT-form polynomials and convert to PK / the converse
 inline uint64_t* upload_pk(Scratch& sc, const uint64_t* host_ref, size_t npolys) {
     uint64_t* d_ref = sc.upload(host_ref, npolys * kRefNtt);

@@ -460,4 +460,25 @@ hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* q
 void launch_db1_limb_planes(const uint64_t* packed_img, uint64_t* limbs, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz);
 void launch_db1_limb_unplanes(const uint64_t* limbs, uint64_t* packed_img, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz);
 
+// ---- in-place item update (db_update.hip) ---------------------------------------------------------------------------------
+// Scatters encoded items into an image in packed form and / or in limb-plane form, in ONE launch.  enc: the items' words as the ingest transform
+// leaves them with a linear ST_PK store (LD_DBGEN: 4 polynomials per item, LD_DBGEN1: 1), word z of a polynomial = database slot z.  Nothing is
+// written when *err != 0.  Work entries (built and checked on the host; no two entries may name the same item, pair or column-term):
+//   put:   {encoded item, j local to the image, column ii, 0}, one per item, packed form
+//   pairs: {column ii, j of the low partner (bit 5 of j clear on the base path, bit 6 on SpiralPack), encoded item of the low partner, of the high
+//          partner (j + 32 / j + 64)}, kDbUpdateNone where that partner does not change; limb-plane form
+constexpr uint32_t kDbUpdateNone = 0xFFFFFFFFu;
+struct DbUpdateParams {
+    const uint64_t* enc;
+    const uint32_t* err;
+    uint64_t* packed;  // the image in packed form (null: none)
+    uint64_t* limbs;   // the image in limb-plane form (null: none)
+    const uint4* put;
+    const uint4* pairs;
+    uint32_t n_put, n_pairs;
+    uint32_t pack;           // 0: a base image (columns ic = 2 ii + c, terms 2 j + m), 1: a SpiralPack trial image (columns ii, terms j)
+    uint32_t num_per, dim0;  // the image's geometry (dim0: the shard's first dimension on the base path)
+};
+void launch_db_update(const DbUpdateParams& p, hipStream_t s);
+
 }  // namespace spiral

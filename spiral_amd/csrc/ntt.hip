@@ -747,6 +747,8 @@ void launch_ntt_forward(const DeviceTables& t, const FwdParams& p_in, uint32_t l
     FWD_CASE(LD_EXPAND, ST_PK)
     FWD_CASE(LD_PDIGIT, ST_PK)
     FWD_CASE(LD_DBGEN1, ST_DB1)
+    FWD_CASE(LD_DBGEN, ST_PK)   // (in-place item updates: the items' words into a linear staging buffer, db_update.hip)
+    FWD_CASE(LD_DBGEN1, ST_PK)
     abort();
 }
 

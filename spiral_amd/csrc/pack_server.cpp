@@ -29,6 +29,7 @@ struct spiral_gpu_pack_server {
     uint32_t n_lanes = 0;
     bool zombie = false;
     uint32_t db_format = SPIRAL_GPU_DB_PACKED;  // holder only: the form db is in now (pk_db_set_format)
+    UpdateWork upd;                              // holder only: update_db_items' workspace
 };
 
 namespace {
@@ -68,6 +69,7 @@ void pk_free(spiral_gpu_pack_server* S, bool keep_db = false) {
                      &S->stage, &S->wire};
     if (keep_db) S->db = DevBuf{};
     for (DevBuf* b : all) b->release();
+    S->upd.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     if (S->stream && S->own_stream) (void)hipStreamDestroy(S->stream);
@@ -418,6 +420,27 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
         return -1;
     S->have_db = true;
     return 0;
+}
+
+// In place, in the trial image's current form, on the holder's stream (include/spiral_gpu.h; the base path's update_db_items with 1 x 1 plaintexts)
+int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, const uint64_t* item_ids,
+                                           uint64_t n) {
+    if (!S) return fail("null server");
+    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, update it through the owner");
+    if (!S->have_db) return fail("no database loaded");
+    if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    HIP_OK(hipSetDevice(S->device));
+    const uint64_t np = S->s.num_per;
+    if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
+    std::vector<UpdateItem> sel(n);
+    for (uint64_t k = 0; k < n; k++) sel[k] = UpdateItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
+    uint64_t* image = S->db.p + (size_t)(trial - S->t0) * S->db_words;
+    UpdateImage img{};
+    img.pack = 1;
+    img.num_per = S->s.num_per;
+    img.dim0 = S->s.dim0;
+    (S->db_format == SPIRAL_GPU_DB_LIMBS ? img.limbs : img.packed) = image;
+    return update_items(S->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, img);
 }
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {

@@ -102,6 +102,7 @@ struct spiral_gpu_server {
     uint32_t db_format = SPIRAL_GPU_DB_PACKED;  // holder only: the form db is in now
     uint64_t db_epoch = 1;    // holder only: bumped when the image is reloaded or changes form -- captured sweeps of the old form must not replay
     uint64_t epoch_seen = 0;  // the holder's epoch this server's graphs were captured under
+    UpdateWork upd;           // holder only: update_db_items' workspace
 };
 
 namespace {
@@ -197,6 +198,7 @@ void srv_free(spiral_gpu_server* S, bool keep_db = false) {
                      &S->resp, &S->stage, &S->wire, &S->db_limbs, &S->arena};  // (the arena after its pieces)
     if (S->db_shared) S->db.p = nullptr;
     for (DevBuf* b : all) b->release();
+    S->upd.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e);
     if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
@@ -1046,6 +1048,33 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
         return -1;
     srv_db_loaded(S);
     return 0;
+}
+
+// In place, in the image's current form, on the holder's stream (include/spiral_gpu.h): no conversion, no new epoch -- the image keeps its address
+// and its form, so captured graphs replay unchanged and read the new items.
+int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, uint32_t coeff_bits, const uint64_t* item_ids, uint64_t n) {
+    if (!S) return fail("null server");
+    if (S->db_shared) return fail("this server sweeps another server's database image (share_db or a lane): update it through the owner");
+    if (!S->have_db) return fail("no database loaded");
+    HIP_OK(hipSetDevice(S->device));
+    const uint64_t np = S->s.num_per;
+    if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
+    std::vector<UpdateItem> sel;  // the ids of this shard's j-range
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t j = item_ids[k] / np;
+        if (j >= S->j0 && j < S->j1) sel.push_back(UpdateItem{k, (uint32_t)(j - S->j0), (uint32_t)(item_ids[k] % np)});
+    }
+    UpdateImage img{};
+    img.pack = 0;
+    img.num_per = S->s.num_per;
+    img.dim0 = S->dim0_shard;
+    if (S->db_format == SPIRAL_GPU_DB_LIMBS) {
+        img.limbs = S->db.p;
+    } else {
+        img.packed = S->db.p;
+        if (S->limbs_valid) img.limbs = S->db_limbs.p;  // (option one_image = 0: the second image stays valid)
+    }
+    return update_items(S->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, img);
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, PackShape, Params, check, lib
+from ._lib import U64P, PackShape, Params, check, lib, update_args
 
 N = 2048
 PACK_STAGE_NAMES = ["expansion_us", "conversion_us", "first_dim_us", "folding_us", "packing_us", "sweep_kernels_us", "total_us", "reserved"]
@@ -95,6 +95,12 @@ class PackServer:
         if n_items is None:
             n_items = items.nbytes * 8 // (N * coeff_bits)
         check(lib().spiral_gpu_pack_server_load_db_items(self.h, trial, items.ctypes.data_as(C.c_void_p), coeff_bits, first_item, n_items))
+
+    def update_db_items(self, trial: int, items, coeff_bits: int, item_ids):
+        """replace the items item_ids[k] <- plaintext k of `items` (2048 coefficients each, as load_db_items) of one trial in place, in the image's
+        current form, on this server's stream; see include/spiral_gpu.h spiral_gpu_pack_server_update_db_items"""
+        items, ids = update_args(items, coeff_bits, item_ids, 1)
+        check(lib().spiral_gpu_pack_server_update_db_items(self.h, trial, items.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
 
     def read_acc(self, trial: int) -> np.ndarray:
         """first-dimension accumulators of one trial of the last answer: [num_per][2][2][N] NTT form"""

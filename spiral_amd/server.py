@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, Params, Shape, check, lib
+from ._lib import U64P, Params, Shape, check, lib, update_args
 
 N = 2048
 
@@ -83,6 +83,12 @@ class Server:
         if n_items is None:
             n_items = items.nbytes * 8 // (4 * N * coeff_bits)
         check(lib().spiral_gpu_server_load_db_items(self.h, items.ctypes.data_as(C.c_void_p), coeff_bits, first_item, n_items))
+
+    def update_db_items(self, items: np.ndarray, coeff_bits: int, item_ids):
+        """replace the items item_ids[k] <- plaintext k of `items` (laid out as for load_db_items) in place, in the image's current form, on this
+        server's stream; see include/spiral_gpu.h spiral_gpu_server_update_db_items"""
+        items, ids = update_args(items, coeff_bits, item_ids, 4)
+        check(lib().spiral_gpu_server_update_db_items(self.h, items.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
 
     def read_db_item(self, item: int) -> np.ndarray:
         out = np.zeros((2, 2, 2, N), dtype=np.uint64)
