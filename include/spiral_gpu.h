@@ -75,6 +75,7 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *   "fwd2"            -1 (default) the two-digits-per-workgroup transform kernel from "fwd2_min" transforms per launch; 0 never; 1 always
  *   "fwd2_min"        that threshold (default 8192 transforms per launch, all query lanes together)
  *   "db_stage_bytes"  bytes of the staging buffer of load_db / load_db_items (default 64 MiB).  Initial value: SPIRAL_DB_STAGE_BYTES.
+ *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  * These three environment variables are the only ones the library reads. */
 int spiral_gpu_set_option(const char *name, int64_t value);
 int spiral_gpu_get_option(const char *name, int64_t *value);
@@ -291,6 +292,22 @@ int spiral_gpu_server_run_query_instances(spiral_gpu_server *s, spiral_gpu_serve
  * ciphertexts out; total_us (may be NULL): device time of the whole item query */
 int spiral_gpu_server_answer_instances(spiral_gpu_server *s, spiral_gpu_server *const *instances, uint32_t n,
                                        const uint64_t *query, uint64_t *responses, uint64_t *finals, double *total_us);
+/* Item queries of n_clients <= 8 clients, each against the same n_instances instances: run_query_batch's expansion and conversion of every client's
+ * query (one launch sequence for all of them), then per instance ONE sweep of its image for all clients (a matrix-core pass where the geometry has
+ * limb planes: the image is converted in place on first use, as run_query_batch does), the folding and the switch.  servers: an owner and its lanes
+ * (create_lane), as in run_query_batch, each with its own public parameters and query; instances: as in run_query_instances (the owner may be one).
+ * pre: as in run_query_instances.  Device outputs, client q and instance k at slot q * n_instances + k: responses (6 x 2048 words per slot), finals
+ * (the folded ciphertexts, likewise; may be NULL), wire (spiral_gpu_response_wire_bytes(p, 2) bytes per slot, contiguous; may be NULL); at least one
+ * of responses and wire.  Every argument is checked before anything is launched (a failing call writes no output); not during stream capture.  Runs
+ * on servers[0]'s stream, the other clients' streams ordered around it by events; one hipGraph per (clients, instance images and their forms, pre,
+ * outputs) with use_graphs on servers[0] -- update_db_items on an instance keeps it.  n_clients = 1 is run_query_instances' launch sequence. */
+int spiral_gpu_server_run_query_batch_instances(spiral_gpu_server *const *servers, uint32_t n_clients, spiral_gpu_server *const *instances,
+                                                uint32_t n_instances, int pre, void *responses, void *finals, void *wire);
+/* the same from host buffers: queries[q] in (set_query's layout), responses (n_clients x n_instances x 6 x 2048 words) and / or wire
+ * (n_clients x n_instances wire forms) out; total_us (may be NULL): device time of the item batch */
+int spiral_gpu_server_answer_batch_instances(spiral_gpu_server *const *servers, uint32_t n_clients, spiral_gpu_server *const *instances,
+                                             uint32_t n_instances, const uint64_t *const *queries, uint64_t *responses, void *wire,
+                                             double *total_us);
 int spiral_gpu_server_fold(spiral_gpu_server *s);      /* foldOneFurtherDimension x nu2               */
 int spiral_gpu_server_finish(spiral_gpu_server *s);    /* response modulus switch, :1441-1447         */
 int spiral_gpu_server_sync(spiral_gpu_server *s);

@@ -208,10 +208,17 @@ int main(int argc, char** argv) {
         // plaintext size)): an item of F plaintexts = F instances of the database; the one query is converted once and answered against all of them by ONE
         // call of spiral_gpu_server_answer_instances, every plaintext of the item is decoded and checked
         if (!strcmp(argv[i], "--instances") && i + 1 < argc) instances = (uint32_t)strtoul(argv[++i], nullptr, 10);
+        // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
+        // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
         // --output-err F (src/spiral.cpp:1287-1291) asks the reference to dump its empirical noise statistics (analyze_err.py's
         // input): those are outside this path.  The flag and its file name are consumed so that a driver's
         // command line parses the same way, and the file is not written.
         if (!strcmp(argv[i], "--output-err") && i + 1 < argc) { cout << "--output-err " << argv[++i] << ": noise statistics are not produced by this build (ignored)" << endl; }
+    }
+    const bool item_batch = batch && instances;
+    if (item_batch && (batch < 2 || batch > 8 || instances < 2 || instances > 16 || high_rate)) {
+        fprintf(stderr, "spiral: --batch B --instances F takes B in 2 .. 8 and F in 2 .. 16 (and no --high-rate)\n");
+        return 1;
     }
     if (idx_target >= total_n) {
         fprintf(stderr, "spiral: IDX_TARGET %llu out of range (n = %llu)\n", (unsigned long long)idx_target, (unsigned long long)total_n);
@@ -306,10 +313,11 @@ int main(int argc, char** argv) {
     // ---- --batch B: the same server, B queries of B clients in one launch sequence (include/spiral_gpu.h, spiral_gpu_server_run_query_batch)
     double batch_us = 0;
     bool batch_corr = true;
-    if (batch >= 2 && batch <= 8) {
-        std::vector<spiral_gpu_server*> lanes{srv};
-        std::vector<Client> clients;
-        std::vector<uint64_t> idxs;
+    // B clients on srv and B - 1 lanes of it (--batch alone, or with --instances)
+    std::vector<spiral_gpu_server*> lanes{srv};
+    std::vector<Client> clients;
+    std::vector<uint64_t> idxs;
+    auto make_clients = [&]() {
         clients.reserve(batch);
         for (uint32_t b = 0; b < batch; b++) {
             if (b) {
@@ -326,6 +334,10 @@ int main(int argc, char** argv) {
             Poly qb = clients[b].query(idxs[b]);
             GPU_OK(spiral_gpu_server_set_query(lanes[b], qb.data()));
         }
+        return 0;
+    };
+    if (!item_batch && batch >= 2 && batch <= 8) {
+        if (make_clients()) return 1;
         GPU_OK(spiral_gpu_server_use_graphs(srv, 1));
         const int reps = 10;
         for (int it = 0; it < 2 + reps; it++) {  // two untimed passes (graph capture, first replay), then `reps` timed ones
@@ -349,7 +361,7 @@ int main(int argc, char** argv) {
         cout << endl;
         GPU_OK(spiral_gpu_server_use_graphs(srv, 0));
         for (uint32_t b = 1; b < batch; b++) spiral_gpu_server_destroy(lanes[b]);
-    } else if (batch) {
+    } else if (!item_batch && batch) {
         fprintf(stderr, "spiral: --batch takes 2 .. 8\n");
         return 1;
     }
@@ -357,14 +369,18 @@ int main(int argc, char** argv) {
     // ---- --instances F: the item at idx_target = plaintext idx_target of F databases (instance k seeded db_seed + k; instance 0 is the server above)
     double item_us = 0;
     bool item_corr = true;
-    if (instances >= 2 && instances <= 16) {
-        std::vector<spiral_gpu_server*> inst{srv};
+    std::vector<spiral_gpu_server*> inst{srv};
+    auto make_instances = [&]() {
         for (uint32_t k = 1; k < instances; k++) {
             spiral_gpu_server* sv = nullptr;
             GPU_OK(spiral_gpu_server_create(&p, 0, 0, 0, &sv));
             GPU_OK(spiral_gpu_server_gen_db(sv, db_seed + k));
             inst.push_back(sv);
         }
+        return 0;
+    };
+    if (!item_batch && instances >= 2 && instances <= 16) {
+        if (make_instances()) return 1;
         std::vector<uint64_t> resps((size_t)instances * 6 * N);
         GPU_OK(spiral_gpu_server_use_graphs(srv, 1));
         for (int it = 0; it < 3; it++)  // capture, a replay, the timed replay
@@ -378,9 +394,38 @@ int main(int argc, char** argv) {
         cout << endl;
         GPU_OK(spiral_gpu_server_use_graphs(srv, 0));
         for (uint32_t k = 1; k < instances; k++) spiral_gpu_server_destroy(inst[k]);
-    } else if (instances) {
+    } else if (!item_batch && instances) {
         fprintf(stderr, "spiral: --instances takes 2 .. 16\n");
         return 1;
+    }
+
+    // ---- --batch B --instances F: B clients' items of F plaintexts (client b's item at idxs[b] of the F databases) in one item batch, wire form out
+    double item_batch_us = 0;
+    if (item_batch) {
+        if (make_clients() || make_instances()) return 1;
+        const size_t wb = wire.size();
+        std::vector<uint8_t> wires((size_t)batch * instances * wb);
+        std::vector<Poly> queries;
+        std::vector<const uint64_t*> qp;
+        for (uint32_t b = 0; b < batch; b++) queries.push_back(clients[b].query(idxs[b]));
+        for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].data());
+        GPU_OK(spiral_gpu_server_use_graphs(srv, 1));
+        for (int it = 0; it < 3; it++)  // image conversion + capture, a replay, the timed replay
+            GPU_OK(spiral_gpu_server_answer_batch_instances(lanes.data(), batch, inst.data(), instances, qp.data(), nullptr, wires.data(), &item_batch_us));
+        cout << "Batch of " << batch << " items of " << instances << " plaintexts, Is correct?:";
+        for (uint32_t b = 0; b < batch; b++) {
+            bool ok = true;
+            for (uint32_t k = 0; k < instances; k++) {
+                GPU_OK(spiral_gpu_response_from_wire(&p, 2, wires.data() + ((size_t)b * instances + k) * wb, resp.data()));
+                ok = ok && clients[b].decode(resp.data()) == db_item(db_seed + k, idxs[b], p.p_db);
+            }
+            batch_corr = batch_corr && ok;
+            cout << " " << (ok ? 1 : 0);
+        }
+        cout << "  (device " << item_batch_us << " us)" << endl;
+        GPU_OK(spiral_gpu_server_use_graphs(srv, 0));
+        for (uint32_t b = 1; b < batch; b++) spiral_gpu_server_destroy(lanes[b]);
+        for (uint32_t k = 1; k < instances; k++) spiral_gpu_server_destroy(inst[k]);
     }
 
     // ---- print_summary (src/spiral.cpp:209-265)
@@ -428,6 +473,9 @@ int main(int argc, char** argv) {
     cout << "      Response switch kernel (GPU·us): " << us[4] << endl;
     cout << "        Whole answer, device (GPU·us): " << us[6] << endl;
     if (batch_us > 0) cout << "   Batch of " << batch << " queries, wall (GPU·us): " << batch_us << endl;
+    if (item_batch_us > 0)
+        cout << "   Batch of " << batch << " items of " << instances << " plaintexts (" << batch << " clients, " << instances << " database instances), device (GPU·us): "
+             << item_batch_us << endl;
     if (item_us > 0) cout << "   Item of " << instances << " plaintexts (one query, " << instances << " database instances), device (GPU·us): " << item_us << endl;
     spiral_gpu_server_destroy(srv);
     return (is_corr && batch_corr && item_corr) ? 0 : 2;

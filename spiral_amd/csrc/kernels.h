@@ -54,6 +54,8 @@ struct Lanes {
         for (uint32_t q = 1; q < kMaxLanes; q++) o = z == q ? off[q] : o;
         return o;
     }
+    // lane q's place in a caller's [lane][...] buffer of `stride` words per lane (run_query_batch_instances' outputs)
+    __device__ __forceinline__ int64_t at(int64_t stride) const { return (int64_t)blockIdx.z * stride; }
 #endif
 };
 #ifdef __HIPCC__
@@ -71,6 +73,7 @@ struct NoLanes {
     uint32_t n = 1;
 #ifdef __HIPCC__
     __device__ __forceinline__ int64_t here() const { return 0; }
+    __device__ __forceinline__ int64_t at(int64_t) const { return 0; }
 #endif
 };
 template <class P>
@@ -275,9 +278,12 @@ void launch_invert(const uint64_t* in, uint64_t* out, uint32_t npolys, hipStream
 void launch_gadget_invert(const uint64_t* in, uint64_t* out, uint32_t mx, uint32_t rdim, uint32_t cols, hipStream_t s);
 // response modulus switch (src/poly.cpp:578-601, src/spiral.cpp:1441-1447)
 void launch_rescale(const uint64_t* in, uint64_t* out, uint32_t n, uint64_t inp_mod, uint64_t out_mod, hipStream_t s);
-void launch_response_wire(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, hipStream_t s);
+// lanes.n > 1: lane q's switched response goes to out + q * out_stride words (out_stride = 0: to lane q's arena, out + lanes.off[q]), and its wire form
+// is packed from in + q * in_stride (0: lane q's arena) to out + q * out_stride
+void launch_response_wire(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, hipStream_t s, const Lanes& lanes = Lanes{},
+                          int64_t in_stride = 0, int64_t out_stride = 0);
 void launch_rescale2(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n, uint64_t inp_mod, uint64_t out_mod0, uint64_t out_mod1, hipStream_t s,
-                     const Lanes& lanes = Lanes{});
+                     const Lanes& lanes = Lanes{}, int64_t out_stride = 0);
 
 // ---- expansion / conversion / fold specials ----------------------------------------------------------
 // the same for a whole round in one launch: active ct a < cnt_e even (W_left, t_e digits) else odd (W_right, t_o);

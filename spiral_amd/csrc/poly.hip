@@ -336,20 +336,26 @@ __global__ __launch_bounds__(kTpb) void rescale_kernel(const uint64_t* in, uint6
     const uint32_t i = blockIdx.x * kTpb + threadIdx.x;
     if (i < n) out[i] = rescale_dev(in[i] % kQ, inp_mod, out_mod);
 }
-// the response switch in one launch: elements [0, n0) -> out_mod0 (row 0 -> q'), [n0, n) -> out_mod1 (the rest -> 4p)
+// the response switch in one launch: elements [0, n0) -> out_mod0 (row 0 -> q'), [n0, n) -> out_mod1 (the rest -> 4p).  Lane q writes to its own
+// arena (out_stride = 0) or to out + q * out_stride (a caller's [client][instance] buffer); NoLanes ignores out_stride
 template <class L>
 __global__ __launch_bounds__(kTpb) void rescale2_kernel(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n, uint64_t inp_mod, uint64_t out_mod0,
-                                                        uint64_t out_mod1, L lanes) {
+                                                        uint64_t out_mod1, L lanes, int64_t out_stride) {
     const uint32_t i = blockIdx.x * kTpb + threadIdx.x;
     lane_shift(in, lanes.here());
-    lane_shift(out, lanes.here());
+    lane_shift(out, out_stride ? lanes.at(out_stride) : lanes.here());
     if (i < n) out[i] = rescale_dev(in[i] % kQ, inp_mod, i < n0 ? out_mod0 : out_mod1);
 }
 // wire form of a switched response (the bit stream write_arbitrary_bits builds, src/core.cpp:32-52, along modswitch's walk,
 // src/spiral.cpp:40-76): values [0, n0) at w0 bits each, then values [n0, n0 + n1) at w1 bits; one thread per 64-bit output
-// word gathers the fields that overlap it (both segments are whole words: N = 2048 values per polynomial)
-__global__ __launch_bounds__(kTpb) void response_wire_kernel(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1) {
+// word gathers the fields that overlap it (both segments are whole words: N = 2048 values per polynomial).  Lanes: gridDim.z = clients, client q's
+// response at in + q * in_stride (0: its arena) packed to out + q * out_stride
+template <class L>
+__global__ __launch_bounds__(kTpb) void response_wire_kernel(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, L lanes,
+                                                             int64_t in_stride, int64_t out_stride) {
     const uint32_t k = blockIdx.x * kTpb + threadIdx.x;
+    lane_shift(in, in_stride ? lanes.at(in_stride) : lanes.here());
+    lane_shift(out, lanes.at(out_stride));
     const uint32_t words0 = n0 / 64u * w0, words1 = n1 / 64u * w1;
     if (k >= words0 + words1) return;
     const bool second = k >= words0;
@@ -366,17 +372,25 @@ __global__ __launch_bounds__(kTpb) void response_wire_kernel(const uint64_t* in,
     }
     out[k] = word;
 }
-void launch_response_wire(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, hipStream_t s) {
+void launch_response_wire(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, hipStream_t s, const Lanes& lanes,
+                          int64_t in_stride, int64_t out_stride) {
     const uint32_t words = n0 / 64u * w0 + n1 / 64u * w1;
-    hipLaunchKernelGGL(response_wire_kernel, dim3((words + kTpb - 1) / kTpb), dim3(kTpb), 0, s, in, out, n0, w0, n1, w1);
+    if (lanes.n > 1)
+        hipLaunchKernelGGL(response_wire_kernel<Lanes>, dim3((words + kTpb - 1) / kTpb, 1, lanes.n), dim3(kTpb), 0, s, in, out, n0, w0, n1, w1, lanes, in_stride,
+                           out_stride);
+    else
+        hipLaunchKernelGGL(response_wire_kernel<NoLanes>, dim3((words + kTpb - 1) / kTpb), dim3(kTpb), 0, s, in, out, n0, w0, n1, w1, NoLanes{}, (int64_t)0,
+                           (int64_t)0);
 }
 void launch_rescale2(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n, uint64_t inp_mod, uint64_t out_mod0, uint64_t out_mod1, hipStream_t s,
-                     const Lanes& lanes) {
+                     const Lanes& lanes, int64_t out_stride) {
     if (n == 0) return;
     if (lanes.n > 1)
-        hipLaunchKernelGGL(rescale2_kernel<Lanes>, dim3((n + kTpb - 1) / kTpb, 1, lanes.n), dim3(kTpb), 0, s, in, out, n0, n, inp_mod, out_mod0, out_mod1, lanes);
+        hipLaunchKernelGGL(rescale2_kernel<Lanes>, dim3((n + kTpb - 1) / kTpb, 1, lanes.n), dim3(kTpb), 0, s, in, out, n0, n, inp_mod, out_mod0, out_mod1, lanes,
+                           out_stride);
     else
-        hipLaunchKernelGGL(rescale2_kernel<NoLanes>, dim3((n + kTpb - 1) / kTpb, 1, 1), dim3(kTpb), 0, s, in, out, n0, n, inp_mod, out_mod0, out_mod1, NoLanes{});
+        hipLaunchKernelGGL(rescale2_kernel<NoLanes>, dim3((n + kTpb - 1) / kTpb, 1, 1), dim3(kTpb), 0, s, in, out, n0, n, inp_mod, out_mod0, out_mod1, NoLanes{},
+                           (int64_t)0);
 }
 void launch_rescale(const uint64_t* in, uint64_t* out, uint32_t n, uint64_t inp_mod, uint64_t out_mod, hipStream_t s) {
     if (n) hipLaunchKernelGGL(rescale_kernel, dim3((n + kTpb - 1) / kTpb), dim3(kTpb), 0, s, in, out, n, inp_mod, out_mod);

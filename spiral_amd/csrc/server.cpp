@@ -2,12 +2,17 @@
 // answer path (server halves of runConversionImproved / process_crtd_query / process_query_fast,
 // reference src/spiral.cpp:2040-2406, 1584-1629).  Everything is kernel launches on one HIP stream;
 // there is no CPU arithmetic path -- without a device every compute entry point fails.
+#include <atomic>
+
 #include "host_common.h"
 
 using namespace spiral;
 
 thread_local std::string spiral::host::g_err;
 using namespace spiral::host;
+
+// hipGraphs the servers of this process have captured so far (get_option "graph_captures"): shows a replay is not a re-capture
+static std::atomic<uint64_t> g_captures{0};
 
 // the process-wide options (kernels.h); the three documented environment variables give their initial values, once
 spiral::Options& spiral::options() {
@@ -89,6 +94,9 @@ struct spiral_gpu_server {
     // run_query_instances with this server as the query's server: the captured launch sequence and what it was captured for
     hipGraphExec_t graph_inst = nullptr;
     std::vector<uint64_t> inst_key;
+    // run_query_batch_instances with this server as client 0: the same, for the client set, the instance images and the outputs
+    hipGraphExec_t graph_binst = nullptr;
+    std::vector<uint64_t> binst_key;
     uint32_t batch_n = 0;
     // batched sweeps of sweep_mfma_min or more queries run on the matrix cores (sweep_mfma.hip) from a second image of the database, the "limb
     // planes": built from db on first use by the image's holder (the owner of a shared image), as large as db, dropped when db is reloaded.
@@ -183,6 +191,9 @@ void srv_drop_graphs(spiral_gpu_server* S) {
     if (S->graph_inst) (void)hipGraphExecDestroy(S->graph_inst);
     S->graph_inst = nullptr;
     S->inst_key.clear();
+    if (S->graph_binst) (void)hipGraphExecDestroy(S->graph_binst);
+    S->graph_binst = nullptr;
+    S->binst_key.clear();
 }
 
 void srv_free(spiral_gpu_server* S, bool keep_db = false) {
@@ -279,12 +290,11 @@ void srv_db_loaded(spiral_gpu_server* S) {
     S->db_epoch++;
 }
 
-// the first-dimension sweep of n queries against one database image: one pass on the matrix cores when the limb-plane image is given, else passes of
-// up to kSweepMaxBatch queries on the vector ALU (wide packed geometries), else one sweep per query
-int sweep_queries(const spiral_gpu_server* S, const uint64_t* limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log, hipStream_t st,
+// the first-dimension sweep of n queries against the database image H holds: one pass on the matrix cores when the limb-plane image is given, else
+// passes of up to kSweepMaxBatch queries on the vector ALU (wide packed geometries), else one sweep per query
+int sweep_queries(const spiral_gpu_server* H, const uint64_t* limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log, hipStream_t st,
                   uint32_t k_log = 0) {
-    const uint32_t np = S->s.num_per, jm = 2 * S->dim0_shard;
-    const spiral_gpu_server* H = holder_of(S);
+    const uint32_t np = H->s.num_per, jm = 2 * H->dim0_shard;
     if (!limbs && H->db_format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;  // the one image is in limb-plane form: every sweep is the matrix-core one
     if (limbs) {
         const hipError_t e = launch_sweep_mfma(limbs, qs, acc, n, np, jm, g_log, st, k_log);
@@ -294,9 +304,9 @@ int sweep_queries(const spiral_gpu_server* S, const uint64_t* limbs, const uint3
     for (uint32_t b0 = 0; b0 < n; b0 += step) {
         const uint32_t nb = n - b0 < step ? n - b0 : step;
         if (nb == 1)
-            launch_sweep(S->db.p, qs[b0], acc[b0], np, jm, g_log, st, k_log);
+            launch_sweep(H->db.p, qs[b0], acc[b0], np, jm, g_log, st, k_log);
         else
-            launch_sweep_batch(S->db.p, qs + b0, acc + b0, nb, np, jm, g_log, st);
+            launch_sweep_batch(H->db.p, qs + b0, acc + b0, nb, np, jm, g_log, st);
     }
     return 0;
 }
@@ -316,13 +326,13 @@ int sweep_with(spiral_gpu_server* S, const spiral_gpu_server* H, int stage) {
 }
 int sweep_one(spiral_gpu_server* S, int stage) { return sweep_with(S, holder_of(S), stage); }
 
-// The limb-plane image for a batched sweep of n queries on the matrix cores, or nullptr when that sweep does not apply (threshold, geometry) --
-// then *rc stays 0 -- or could not be built (*rc = -1).  Built once per database load by the image's holder; never call this inside a capture.
-const uint64_t* limb_image(spiral_gpu_server* S, uint32_t n, int* rc) {
+// The limb-plane image of the database H holds for a batched sweep of n queries on the matrix cores, or nullptr when that sweep does not apply
+// (S's threshold, geometry) -- then *rc stays 0 -- or could not be built (*rc = -1).  Built once per database load by the image's holder H, on S's
+// stream; never call this inside a capture.
+const uint64_t* limb_image(spiral_gpu_server* S, spiral_gpu_server* H, uint32_t n, int* rc) {
     *rc = 0;
-    spiral_gpu_server* H = holder_of(S);
     if (H->db_format == SPIRAL_GPU_DB_LIMBS) return H->db.p;  // (whatever the threshold says: there is no other image to sweep)
-    if (S->sweep_mfma_min == 0 || n < S->sweep_mfma_min || !sweep_mfma_ok(S->s.num_per, 2 * S->dim0_shard)) return nullptr;
+    if (S->sweep_mfma_min == 0 || n < S->sweep_mfma_min || !sweep_mfma_ok(H->s.num_per, 2 * H->dim0_shard)) return nullptr;
     if (options().one_image) {  // the one image changes form, in place
         *rc = srv_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream);
         return *rc ? nullptr : H->db.p;
@@ -428,6 +438,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "fwd2") *value = o.fwd2;
     else if (n == "fwd2_min") *value = o.fwd2_min;
     else if (n == "db_stage_bytes") *value = (int64_t)o.db_stage_bytes;
+    else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;
 }
@@ -1414,7 +1425,7 @@ int spiral_gpu_server_first_dim_batch(spiral_gpu_server* const* servers, uint32_
         acc[b] = S->acc;
     }
     int rc = 0;
-    const uint64_t* limbs = limb_image(S0, n, &rc);
+    const uint64_t* limbs = limb_image(S0, holder_of(S0), n, &rc);
     if (rc) return rc;
     if (!limbs && !sweep_batch_ok(S0->s.num_per, 2 * S0->dim0_shard)) {  // (a packed image: limb planes always come back as `limbs`)
         for (uint32_t b = 0; b < n; b++)
@@ -1426,7 +1437,7 @@ int spiral_gpu_server_first_dim_batch(spiral_gpu_server* const* servers, uint32_
         HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
         HIP_OK(hipStreamWaitEvent(S0->stream, servers[b]->ev_batch, 0));
     }
-    if (sweep_queries(S0, limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
+    if (sweep_queries(holder_of(S0), limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
     for (uint32_t b = 0; b < n; b++) servers[b]->raw_from_acc = false;
     HIP_OK(hipEventRecord(S0->ev_batch, S0->stream));
     for (uint32_t b = 1; b < n; b++)
@@ -1667,6 +1678,7 @@ int run_group(spiral_gpu_server* S, int slot, hipStream_t st, F body) {
         e = hipGraphInstantiate(&S->graph[slot], g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(e));
+        g_captures++;
     }
     HIP_OK(hipGraphLaunch(S->graph[slot], st));
     if (slot == 0 || slot == 4 || slot == 7 || slot == 9 || slot == 10 || slot == 12) S->have_records = true;  // the groups that hold ScalToMat
@@ -1724,6 +1736,165 @@ int spiral_gpu_server_run_query(spiral_gpu_server* S) {
     });
 }
 
+}  // extern "C"
+
+namespace {
+// The pieces run_query_batch, run_query_instances and run_query_batch_instances share.
+
+// Checks the query lanes servers[0 .. n) of one launch sequence -- an owner and its lanes, same parameters, device and shard, the default schedule,
+// no server twice -- and fills their arena offsets.  need_db: each must have a database (run_query_batch sweeps servers[0]'s image).
+int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, bool need_query, bool need_db, Lanes* lanes) {
+    spiral_gpu_server* S = servers[0];
+    lanes->n = n;
+    for (uint32_t b = 0; b < n; b++) {
+        spiral_gpu_server* L = servers[b];
+        if ((need_query && !L->have_query) || !L->have_pp) return fail("%s: server %u needs its query and public parameters set first", what, b);
+        if (need_db && !L->have_db) return fail("%s: server %u has no database", what, b);
+        if (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->device != S->device || L->j0 != S->j0 || L->dim0_shard != S->dim0_shard || L->cv.words != S->cv.words)
+            return fail("%s: server %u differs from server 0 in parameters, device or shard", what, b);
+        if (L->db.p != S->db.p) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
+        if (L->acc != L->acc_own.p || L->keep_cts || L->overlap || L->fold_g_log || L->sweep_k_log || L->ex_shard.g_log || L->side_pending || L->fold_pair != S->fold_pair ||
+            L->fold_chain != S->fold_chain)
+            return fail("%s: server %u has an external accumulator, keep_cts, a split / sharded / staged schedule or other fold options set", what, b);
+        for (uint32_t c = 0; c < b; c++)
+            if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
+        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
+    }
+    return 0;
+}
+
+// Checks the instances of an item query answered by S's query (same device, shard, database geometry and plaintext modulus, each with a database)
+// and appends each one's image and epoch to the graph key
+int check_instances(const spiral_gpu_server* S, spiral_gpu_server* const* instances, uint32_t n, const char* what, std::vector<uint64_t>* key) {
+    for (uint32_t k = 0; k < n; k++) {
+        const spiral_gpu_server* I = instances[k];
+        if (!I) return fail("null instance %u", k);
+        const spiral_gpu_server* H = holder_of(I);
+        if (!I->have_db) return fail("%s: instance %u has no database", what, k);
+        if (I->device != S->device || I->j0 != S->j0 || I->dim0_shard != S->dim0_shard || I->p.nu1 != S->p.nu1 || I->p.nu2 != S->p.nu2 || I->p.p_db != S->p.p_db ||
+            I->p.direct_upload != S->p.direct_upload)
+            return fail("%s: instance %u differs from the query's server in device, shard, database geometry or plaintext modulus", what, k);
+        key->push_back((uint64_t)(uintptr_t)I->db.p);
+        key->push_back(H->db_epoch);
+    }
+    return 0;
+}
+
+// the lanes' uploads (and whatever else their streams still hold) come before the sequence on servers[0]'s stream, and what follows on their streams
+// after it.  (Lanes on the sequence's own stream are ordered by it: the cheapest arrangement, each other stream costs ~20 us per batch.)
+int lanes_join(spiral_gpu_server* const* servers, uint32_t n) {
+    spiral_gpu_server* S = servers[0];
+    for (uint32_t b = 1; b < n; b++) {
+        if (servers[b]->stream == S->stream) continue;
+        HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
+        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev_batch, 0));
+    }
+    return 0;
+}
+int lanes_release(spiral_gpu_server* const* servers, uint32_t n) {
+    spiral_gpu_server* S = servers[0];
+    bool other = false;
+    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
+    if (other) HIP_OK(hipEventRecord(S->ev_batch, S->stream));
+    for (uint32_t b = 1; b < n; b++)
+        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev_batch, 0));
+    return 0;
+}
+
+// Expansion and conversion of the queries of `lanes` (lane 0 = S): one query is expand_convert, a batch carries every lane in each launch.
+// Batches of four or more: the Regev->GSW conversion runs as soon as the odd (GSW-bit) tree of the expansion is complete, after round `stopround`
+// (src/spiral.cpp:1700-1702: no odd ciphertext is touched later), and ScalToMat after the last round.  The same launches' work in another order -- at
+// these sizes none of them is launch-bound -- but the 24 MiB of GSW matrices and keys per query are then written ~0.3 ms before the sweep instead of
+// right in front of it: dirty lines draining into the database stream cost the matrix-core sweep 30-70 us (profiles/r06_sweep_in_situ_batch.txt).
+int convert_lanes(spiral_gpu_server* S, const Lanes& lanes) {
+    if (lanes.n == 1) return expand_convert(S);
+    const bool gsw_early = lanes.n >= 4 && !S->p.direct_upload && S->s.stopround > 0 && S->s.stopround + 1 < S->s.g && S->p.nu2 > 0;
+    if (gsw_early && tuning_env("SPIRAL_GSW_ORDER") && atoi(tuning_env("SPIRAL_GSW_ORDER")) == 2) {  // (tuning builds only) ScalToMat first, the GSW side last
+        if (expand_lanes(S, lanes)) return -1;
+        if (convert_part(S, CONV_S2M, S->stream, false, lanes)) return -1;
+        if (convert_part(S, CONV_GSW, S->stream, false, lanes)) return -1;
+    } else if (gsw_early) {
+        if (expand_lanes(S, lanes, 0, S->s.stopround + 1)) return -1;
+        if (convert_part(S, CONV_GSW, S->stream, false, lanes)) return -1;
+        if (expand_lanes(S, lanes, S->s.stopround + 1)) return -1;
+        if (convert_part(S, CONV_S2M, S->stream, false, lanes)) return -1;
+    } else {
+        if (expand_lanes(S, lanes)) return -1;
+        if (convert_part(S, CONV_BOTH, S->stream, false, lanes)) return -1;
+    }
+    return 0;
+}
+
+// the lanes' query records and accumulators, as sweep_queries takes them
+void lane_records(spiral_gpu_server* S, const Lanes& lanes, const uint32_t** qs, uint64_t** acc) {
+    for (uint32_t b = 0; b < lanes.n; b++) {
+        qs[b] = (const uint32_t*)(S->qs.p + lanes.off[b]);
+        acc[b] = S->acc + lanes.off[b];
+    }
+}
+
+// Where an item query's results go (device pointers, each optional): (client q, instance k) at slot q * n_inst + k of resp and fin (6 x 2048 words
+// each) and of wire (wire_bytes(p, 2) each).  via_resp: run_query_instances' sequence -- the switch into S->resp, then copies.
+struct ItemOut {
+    uint64_t *resp = nullptr, *fin = nullptr, *wire = nullptr;
+    bool via_resp = false;
+};
+// The per-instance part of an item query for the queries of `lanes` (lane 0 = S), converted already: for each instance k, the sweep of its image (one
+// matrix-core pass for every lane where limbs[k] is given; sweep_queries), the folding, and the switch and wire form straight into the outputs
+int item_rounds(spiral_gpu_server* S, const Lanes& lanes, spiral_gpu_server* const* instances, const uint64_t* const* limbs, uint32_t n_inst, const ItemOut& o) {
+    const uint32_t* qs[kMaxLanes];
+    uint64_t* acc[kMaxLanes];
+    lane_records(S, lanes, qs, acc);
+    const size_t rw = 6 * kN, ww = wire_bytes(&S->p, 2) / 8;  // (whole words: 2048 values per polynomial)
+    for (uint32_t k = 0; k < n_inst; k++) {
+        if (sweep_queries(holder_of(instances[k]), limbs ? limbs[k] : nullptr, qs, acc, lanes.n, 0, S->stream)) return -1;
+        if (o.via_resp) {
+            if (run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true)) return -1;
+            HIP_OK(hipMemcpyAsync(o.resp + k * rw, S->resp.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
+            if (o.fin) HIP_OK(hipMemcpyAsync(o.fin + k * rw, S->raw.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
+            continue;
+        }
+        if (run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, false, nullptr, lanes)) return -1;
+        // row 0 -> q', rows 1.. -> 4*p_db (src/spiral.cpp:1441-1447), lane q's into its slot; without resp, into each lane's own S->resp (for the wire form)
+        uint64_t* out = o.resp ? o.resp + k * rw : S->resp.p;
+        const int64_t out_stride = o.resp ? (int64_t)(n_inst * rw) : 0;
+        launch_rescale2(S->raw.p, out, 2 * kN, 6 * kN, kQ, S->s.qprime, 4 * S->p.p_db, S->stream, lanes, out_stride);
+        for (uint32_t q = 0; o.fin && q < lanes.n; q++)
+            HIP_OK(hipMemcpyAsync(o.fin + (q * n_inst + k) * rw, S->raw.p + lanes.off[q], 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
+        if (o.wire)
+            launch_response_wire(out, o.wire + k * ww, 2 * kN, S->p.qprime_bits, 4 * kN, wire_bits_rest(&S->p), S->stream, lanes, out_stride, (int64_t)(n_inst * ww));
+    }
+    return 0;
+}
+
+// body() run directly, or -- with use_graphs on S -- captured into *exec on S's stream when there is none or it was captured for another key (!same),
+// then replayed
+template <class F>
+int run_keyed(spiral_gpu_server* S, hipGraphExec_t* exec, bool same, F body) {
+    if (!S->use_graphs) return body();
+    if (!*exec || !same) {
+        if (*exec) (void)hipGraphExecDestroy(*exec);
+        *exec = nullptr;
+        HIP_OK(hipStreamBeginCapture(S->stream, hipStreamCaptureModeRelaxed));
+        const int rc = body();
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(S->stream, &g);
+        if (rc || e != hipSuccess) {
+            if (g) (void)hipGraphDestroy(g);
+            return rc ? rc : fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
+        }
+        const hipError_t e2 = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(g);
+        if (e2 != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(e2));
+        g_captures++;
+    }
+    HIP_OK(hipGraphLaunch(*exec, S->stream));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
 // B <= kMaxLanes whole queries -- one per server: an owner and its lanes (create_lane), all with the same parameters, each with its own
 // client's keys and query -- as ONE launch sequence: every launch of expansion, conversion, lift, folding and the switch carries all B queries
 // (gridDim.z = B, kernels.h Lanes), and the sweep makes one pass over the database for all of them (sweep_mfma_kernel; sweep_queries).  The reference
@@ -1740,96 +1911,34 @@ int spiral_gpu_server_run_query_batch(spiral_gpu_server* const* servers, uint32_
     if (n > kMaxLanes) return fail("at most %u queries per batch", kMaxLanes);
     HIP_OK(hipSetDevice(S->device));
     Lanes lanes;
-    lanes.n = n;
-    for (uint32_t b = 0; b < n; b++) {  // every lane is validated before anything is launched
-        spiral_gpu_server* L = servers[b];
-        if (!L->have_query || !L->have_pp) return fail("run_query_batch: server %u needs its query and public parameters set first", b);
-        if (!L->have_db) return fail("run_query_batch: server %u has no database", b);
-        if (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->device != S->device || L->j0 != S->j0 || L->dim0_shard != S->dim0_shard || L->cv.words != S->cv.words)
-            return fail("run_query_batch: server %u differs from server 0 in parameters, device or shard", b);
-        if (L->db.p != S->db.p) return fail("run_query_batch: server %u does not sweep server 0's database image (create_lane / share_db)", b);
-        if (L->acc != L->acc_own.p || L->keep_cts || L->overlap || L->fold_g_log || L->sweep_k_log || L->ex_shard.g_log || L->side_pending || L->fold_pair != S->fold_pair ||
-            L->fold_chain != S->fold_chain)
-            return fail("run_query_batch: server %u has an external accumulator, keep_cts, a split / sharded / staged schedule or other fold options set", b);
-        for (uint32_t c = 0; c < b; c++)
-            if (servers[c] == L) return fail("run_query_batch: server %u listed twice", b);
-        lanes.off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
-    }
-    for (uint32_t b = 1; b < n; b++) {  // the lanes' uploads (and whatever else their streams still hold) come first
-        if (servers[b]->stream == S->stream) continue;  // (lanes on the batch's own stream are ordered by it: the cheapest arrangement, each other stream costs ~20 us per batch)
-        HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
-        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev_batch, 0));
-    }
+    if (check_lanes(servers, n, "run_query_batch", true, true, &lanes)) return -1;  // every lane is validated before anything is launched
+    if (lanes_join(servers, n)) return -1;
     int rc_l = 0;
-    const uint64_t* limbs = limb_image(S, n, &rc_l);  // (not inside the capture below: it may build the image)
+    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc_l);  // (not inside the capture below: it may build the image)
     if (rc_l) return rc_l;
-    // Batches of four or more: the Regev->GSW conversion runs as soon as the odd (GSW-bit) tree of the expansion is complete, after round `stopround`
-    // (src/spiral.cpp:1700-1702: no odd ciphertext is touched later), and ScalToMat after the last round.  The same launches' work in another order -- at
-    // these sizes none of them is launch-bound -- but the 24 MiB of GSW matrices and keys per query are then written ~0.3 ms before the sweep instead of
-    // right in front of it: dirty lines draining into the database stream cost the matrix-core sweep 30-70 us (profiles/r06_sweep_in_situ_batch.txt).
-    const bool gsw_early = n >= 4 && !S->p.direct_upload && S->s.stopround > 0 && S->s.stopround + 1 < S->s.g && S->p.nu2 > 0;
     auto body = [&]() {
-        if (gsw_early && tuning_env("SPIRAL_GSW_ORDER") && atoi(tuning_env("SPIRAL_GSW_ORDER")) == 2) {  // (tuning builds only) ScalToMat first, the GSW side last
-            if (expand_lanes(S, lanes)) return -1;
-            if (convert_part(S, CONV_S2M, S->stream, false, lanes)) return -1;
-            if (convert_part(S, CONV_GSW, S->stream, false, lanes)) return -1;
-        } else if (gsw_early) {
-            if (expand_lanes(S, lanes, 0, S->s.stopround + 1)) return -1;
-            if (convert_part(S, CONV_GSW, S->stream, false, lanes)) return -1;
-            if (expand_lanes(S, lanes, S->s.stopround + 1)) return -1;
-            if (convert_part(S, CONV_S2M, S->stream, false, lanes)) return -1;
-        } else {
-            if (expand_lanes(S, lanes)) return -1;
-            if (convert_part(S, CONV_BOTH, S->stream, false, lanes)) return -1;
-        }
+        if (convert_lanes(S, lanes)) return -1;
         const uint32_t* qs[kMaxLanes];
         uint64_t* acc[kMaxLanes];
-        for (uint32_t b = 0; b < n; b++) {
-            qs[b] = (const uint32_t*)(S->qs.p + lanes.off[b]);
-            acc[b] = S->acc + lanes.off[b];
-        }
-        if (sweep_queries(S, limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
+        lane_records(S, lanes, qs, acc);
+        if (sweep_queries(holder_of(S), limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
         return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true, nullptr, lanes);
     };
-    int rc = 0;
-    if (!S->use_graphs) {
-        rc = body();
-    } else {
-        srv_check_epoch(S);  // (limb_image above may just have changed the image's form)
-        // the capture bakes in the lanes' arenas, the image the sweep reads and its kernel (limbs or not)
-        bool same = S->graph_batch && S->batch_n == n && S->batch_limbs == limbs;
-        for (uint32_t b = 0; same && b < n; b++) same = S->batch_key[b] == servers[b]->w_left.p;
-        if (!same) {
-            if (S->graph_batch) (void)hipGraphExecDestroy(S->graph_batch);
-            S->graph_batch = nullptr;
-            HIP_OK(hipStreamBeginCapture(S->stream, hipStreamCaptureModeRelaxed));
-            rc = body();
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(S->stream, &g);
-            if (rc || e != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);
-                return rc ? rc : fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-            }
-            const hipError_t e2 = hipGraphInstantiate(&S->graph_batch, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e2 != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(e2));
-            S->batch_n = n;
-            S->batch_limbs = limbs;
-            for (uint32_t b = 0; b < n; b++) S->batch_key[b] = servers[b]->w_left.p;
-        }
-        HIP_OK(hipGraphLaunch(S->graph_batch, S->stream));
+    if (S->use_graphs) srv_check_epoch(S);  // (limb_image above may just have changed the image's form)
+    // the capture bakes in the lanes' arenas, the image the sweep reads and its kernel (limbs or not)
+    bool same = S->batch_n == n && S->batch_limbs == limbs;
+    for (uint32_t b = 0; same && b < n; b++) same = S->batch_key[b] == servers[b]->w_left.p;
+    if (int rc = run_keyed(S, &S->graph_batch, same, body)) return rc;
+    if (S->use_graphs) {
+        S->batch_n = n;
+        S->batch_limbs = limbs;
+        for (uint32_t b = 0; b < n; b++) S->batch_key[b] = servers[b]->w_left.p;
     }
-    if (rc) return rc;
     for (uint32_t b = 0; b < n; b++) {
         servers[b]->have_records = true;
         servers[b]->raw_from_acc = false;
     }
-    bool other = false;
-    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
-    if (other) HIP_OK(hipEventRecord(S->ev_batch, S->stream));
-    for (uint32_t b = 1; b < n; b++)
-        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev_batch, 0));
-    return 0;
+    return lanes_release(servers, n);
 }
 
 // One query against n INSTANCES of the database.  An item larger than one plaintext (configs[3]: 100 KB items, 15 360-byte plaintexts) is
@@ -1848,52 +1957,19 @@ int spiral_gpu_server_run_query_instances(spiral_gpu_server* S, spiral_gpu_serve
     if (S->overlap || S->fold_g_log || S->sweep_k_log || S->ex_shard.g_log || S->keep_cts || S->acc != S->acc_own.p)
         return fail("run_query_instances needs the default schedule on the query's server (own accumulators, no split / sharded / staged options)");
     std::vector<uint64_t> key{(uint64_t)(uintptr_t)responses, (uint64_t)(uintptr_t)finals, (uint64_t)(pre != 0)};
-    for (uint32_t k = 0; k < n; k++) {
-        const spiral_gpu_server* I = instances[k];
-        if (!I) return fail("null instance %u", k);
-        const spiral_gpu_server* H = holder_of(I);
-        if (!I->have_db) return fail("run_query_instances: instance %u has no database", k);
-        if (I->device != S->device || I->j0 != S->j0 || I->dim0_shard != S->dim0_shard || I->p.nu1 != S->p.nu1 || I->p.nu2 != S->p.nu2 || I->p.p_db != S->p.p_db ||
-            I->p.direct_upload != S->p.direct_upload)
-            return fail("run_query_instances: instance %u differs from the query's server in device, shard, database geometry or plaintext modulus", k);
-        key.push_back((uint64_t)(uintptr_t)I->db.p);
-        key.push_back(H->db_epoch);
-    }
+    if (check_instances(S, instances, n, "run_query_instances", &key)) return -1;
     if (srv_join_side(S)) return -1;
+    ItemOut o;
+    o.resp = (uint64_t*)responses;
+    o.fin = (uint64_t*)finals;
+    o.via_resp = true;
     auto body = [&]() {
         if (pre && expand_convert(S)) return -1;
-        for (uint32_t k = 0; k < n; k++) {
-            if (sweep_with(S, holder_of(instances[k]), -1)) return -1;
-            if (run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true)) return -1;
-            HIP_OK(hipMemcpyAsync((uint64_t*)responses + (size_t)k * 6 * kN, S->resp.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
-            if (finals) HIP_OK(hipMemcpyAsync((uint64_t*)finals + (size_t)k * 6 * kN, S->raw.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
-        }
-        return 0;
+        return item_rounds(S, Lanes{}, instances, nullptr, n, o);
     };
-    int rc = 0;
-    if (!S->use_graphs) {
-        rc = body();
-    } else {
-        srv_check_epoch(S);
-        if (!S->graph_inst || S->inst_key != key) {
-            if (S->graph_inst) (void)hipGraphExecDestroy(S->graph_inst);
-            S->graph_inst = nullptr;
-            HIP_OK(hipStreamBeginCapture(S->stream, hipStreamCaptureModeRelaxed));
-            rc = body();
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(S->stream, &g);
-            if (rc || e != hipSuccess) {
-                if (g) (void)hipGraphDestroy(g);
-                return rc ? rc : fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-            }
-            const hipError_t e2 = hipGraphInstantiate(&S->graph_inst, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e2 != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(e2));
-            S->inst_key = key;
-        }
-        HIP_OK(hipGraphLaunch(S->graph_inst, S->stream));
-    }
-    if (rc) return rc;
+    if (S->use_graphs) srv_check_epoch(S);
+    if (int rc = run_keyed(S, &S->graph_inst, S->inst_key == key, body)) return rc;
+    if (S->use_graphs) S->inst_key = key;
     if (pre) S->have_records = true;
     S->raw_from_acc = false;
     return 0;
@@ -1915,6 +1991,113 @@ int spiral_gpu_server_answer_instances(spiral_gpu_server* S, spiral_gpu_server* 
     HIP_OK(hipEventRecord(S->ev[1], S->stream));
     HIP_OK(hipMemcpyAsync(responses, d_resp, (size_t)n * 6 * kPolyBytes, hipMemcpyDeviceToHost, S->stream));
     if (finals) HIP_OK(hipMemcpyAsync(finals, d_fin, (size_t)n * 6 * kPolyBytes, hipMemcpyDeviceToHost, S->stream));
+    HIP_OK(hipStreamSynchronize(S->stream));
+    if (total_us) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
+        *total_us = ms * 1e3;
+    }
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+// every argument check of run_query_batch_instances / answer_batch_instances, before anything is uploaded or launched
+int check_batch_instances(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_server* const* instances, uint32_t n_inst, int pre, bool need_query,
+                          Lanes* lanes, std::vector<uint64_t>* key) {
+    const char* what = "run_query_batch_instances";
+    if (!servers || n == 0 || !instances || n_inst == 0) return fail("%s: no servers or no instances", what);
+    if (n > kMaxLanes) return fail("%s: at most %u clients per batch", what, kMaxLanes);
+    for (uint32_t b = 0; b < n; b++)
+        if (!servers[b]) return fail("null server");
+    spiral_gpu_server* S = servers[0];
+    HIP_OK(hipSetDevice(S->device));
+    if (check_lanes(servers, n, what, need_query, false, lanes)) return -1;
+    for (uint32_t b = 0; b < n; b++) {
+        if (!pre && !servers[b]->have_records) return fail("%s: server %u has not converted its query (run_pre first, or pass pre = 1)", what, b);
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_OK(hipStreamIsCapturing(servers[b]->stream, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
+    }
+    return check_instances(S, instances, n_inst, what, key);
+}
+}  // namespace
+
+extern "C" {
+
+// B <= kMaxLanes clients' item queries against the same n_inst instances (include/spiral_gpu.h): the clients' expansion and conversion as in
+// run_query_batch, then per instance one sweep for all B (sweep_queries: one matrix-core pass where the geometry has limb planes), the folding with
+// every lane in each launch, and the switch and wire form written straight into the callers' [client][instance] slots.  B = 1 is run_query_instances'
+// sequence (NoLanes launches) with the switch into the output and the wire form added.  One hipGraph per key on servers[0] with use_graphs on.
+int spiral_gpu_server_run_query_batch_instances(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_server* const* instances, uint32_t n_inst, int pre,
+                                                void* responses, void* finals, void* wire) {
+    Lanes lanes;
+    std::vector<uint64_t> checked;
+    if (!responses && !wire) return fail("run_query_batch_instances: no output (responses or wire)");
+    if (check_batch_instances(servers, n, instances, n_inst, pre, true, &lanes, &checked)) return -1;
+    spiral_gpu_server* S = servers[0];
+    if (srv_join_side(S)) return -1;
+    if (lanes_join(servers, n)) return -1;
+    // each instance image in the form the sweep of B queries reads, converted in place on first use (never inside the capture)
+    std::vector<const uint64_t*> limbs(n_inst);
+    for (uint32_t k = 0; k < n_inst; k++) {
+        int rc = 0;
+        spiral_gpu_server* H = holder_of(instances[k]);
+        limbs[k] = limb_image(S, H, n, &rc);
+        if (rc) return rc;
+    }
+    // the capture bakes in the clients' arenas, the outputs, and each instance's image, the form it is in and the sweep kernel that reads it (the
+    // holder's epoch covers the form; update_db_items keeps it: captured graphs replay across updates)
+    std::vector<uint64_t> key{(uint64_t)n, (uint64_t)(pre != 0), (uint64_t)(uintptr_t)responses, (uint64_t)(uintptr_t)finals, (uint64_t)(uintptr_t)wire};
+    for (uint32_t b = 0; b < n; b++) key.push_back((uint64_t)(uintptr_t)servers[b]->w_left.p);
+    for (uint32_t k = 0; k < n_inst; k++) {
+        const spiral_gpu_server* H = holder_of(instances[k]);
+        key.push_back((uint64_t)(uintptr_t)H->db.p);
+        key.push_back((uint64_t)(uintptr_t)limbs[k]);
+        key.push_back(H->db_epoch);
+        key.push_back(H->db_format);
+    }
+    ItemOut o;
+    o.resp = (uint64_t*)responses;
+    o.fin = (uint64_t*)finals;
+    o.wire = (uint64_t*)wire;
+    auto body = [&]() {
+        if (pre && convert_lanes(S, lanes)) return -1;
+        return item_rounds(S, lanes, instances, limbs.data(), n_inst, o);
+    };
+    if (S->use_graphs) srv_check_epoch(S);
+    if (int rc = run_keyed(S, &S->graph_binst, S->binst_key == key, body)) return rc;
+    if (S->use_graphs) S->binst_key = key;
+    for (uint32_t b = 0; b < n; b++) {
+        if (pre) servers[b]->have_records = true;
+        servers[b]->raw_from_acc = false;
+    }
+    return lanes_release(servers, n);
+}
+
+// the same from host buffers: upload the B queries, answer them, download the B x n_inst responses and / or wire forms; total_us: device time of the batch
+int spiral_gpu_server_answer_batch_instances(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_server* const* instances, uint32_t n_inst,
+                                             const uint64_t* const* queries, uint64_t* responses, void* wire, double* total_us) {
+    Lanes lanes;
+    std::vector<uint64_t> key;
+    if (!queries || (!responses && !wire)) return fail("answer_batch_instances: null queries or no output (responses or wire)");
+    if (check_batch_instances(servers, n, instances, n_inst, 1, false, &lanes, &key)) return -1;
+    for (uint32_t b = 0; b < n; b++)
+        if (!queries[b]) return fail("answer_batch_instances: null query %u", b);
+    spiral_gpu_server* S = servers[0];
+    const size_t slots = (size_t)n * n_inst, wb = wire_bytes(&S->p, 2);
+    Scratch sc;
+    uint64_t* d_resp = responses ? sc.get(slots * 6 * kN) : nullptr;
+    uint64_t* d_wire = wire ? sc.get(slots * wb / 8) : nullptr;
+    if ((responses && !d_resp) || (wire && !d_wire)) return fail("device allocation failed");
+    for (uint32_t b = 0; b < n; b++)
+        if (spiral_gpu_server_set_query(servers[b], queries[b])) return -1;
+    HIP_OK(hipEventRecord(S->ev[0], S->stream));
+    if (spiral_gpu_server_run_query_batch_instances(servers, n, instances, n_inst, 1, d_resp, nullptr, d_wire)) return -1;
+    HIP_OK(hipEventRecord(S->ev[1], S->stream));
+    if (responses) HIP_OK(hipMemcpyAsync(responses, d_resp, slots * 6 * kPolyBytes, hipMemcpyDeviceToHost, S->stream));
+    if (wire) HIP_OK(hipMemcpyAsync(wire, d_wire, slots * wb, hipMemcpyDeviceToHost, S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     if (total_us) {
         float ms = 0;
@@ -2250,12 +2433,12 @@ int spiral_gpu_server_time_sweep_batch(spiral_gpu_server* const* servers, uint32
         L->raw_from_acc = false;
     }
     int rc = 0;
-    const uint64_t* limbs = limb_image(S, n, &rc);
+    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);
     if (rc) return rc;
     HIP_OK(hipDeviceSynchronize());  // (the lanes' streams: their records are complete)
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
-        if (sweep_queries(S, limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
+        if (sweep_queries(holder_of(S), limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
     HIP_OK(hipEventRecord(S->ev[1], S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     float ms = 0;

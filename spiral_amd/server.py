@@ -40,6 +40,35 @@ def run_query_batch(servers):
     check(lib().spiral_gpu_server_run_query_batch(arr, len(servers)))
 
 
+def run_query_batch_instances(servers, instances, responses_ptr: int = 0, finals_ptr: int = 0, wire_ptr: int = 0, pre: bool = True):
+    """item queries of up to eight clients (an owner and its lanes, each with its own query) against the same database instances: one sweep per instance
+    for all of them; device outputs, client q and instance k at slot q * len(instances) + k: responses / finals 6 x 2048 words, wire
+    spiral_gpu_response_wire_bytes(params, 2) bytes per slot (at least one of responses and wire); see include/spiral_gpu.h"""
+    arr = (C.c_void_p * len(servers))(*[s.h for s in servers])
+    inst = (C.c_void_p * len(instances))(*[s.h for s in instances])
+    check(lib().spiral_gpu_server_run_query_batch_instances(arr, len(servers), inst, len(instances), 1 if pre else 0, C.c_void_p(responses_ptr or None),
+                                                             C.c_void_p(finals_ptr or None), C.c_void_p(wire_ptr or None)))
+
+
+def answer_batch_instances(servers, instances, queries, wire: bool = False):
+    """host-buffer form of run_query_batch_instances: (responses [B][n][3][2][N], device us of the item batch), or with wire=True
+    (wire forms [B][n][bytes] uint8, device us)"""
+    B, n = len(servers), len(instances)
+    arr = (C.c_void_p * B)(*[s.h for s in servers])
+    inst = (C.c_void_p * n)(*[s.h for s in instances])
+    qs = [np.ascontiguousarray(q, dtype=np.uint64) for q in queries]
+    qp = (U64P * B)(*[_p(q) for q in qs])
+    us = C.c_double()
+    if wire:
+        nb = lib().spiral_gpu_response_wire_bytes(C.byref(servers[0].params), 2)
+        out = np.zeros((B, n, nb), dtype=np.uint8)
+        check(lib().spiral_gpu_server_answer_batch_instances(arr, B, inst, n, qp, None, out.ctypes.data_as(C.c_void_p), C.byref(us)))
+    else:
+        out = np.zeros((B, n, 3, 2, N), dtype=np.uint64)
+        check(lib().spiral_gpu_server_answer_batch_instances(arr, B, inst, n, qp, _p(out), None, C.byref(us)))
+    return out, us.value
+
+
 class Server:
     def __init__(self, params: Params, device: int = 0, j_begin: int = 0, j_end: int = 0, share_db_of: "Server | None" = None):
         """share_db_of: make this server a query lane of that one -- same parameters, device and shard, sweeping ITS database
