@@ -242,6 +242,26 @@ int spiral_gpu_server_set_pub_params(spiral_gpu_server *s, const uint64_t *w_lef
 /* query: n_query_cts Regev ciphertexts, n0 x 1 NTT form */
 int spiral_gpu_server_set_query(spiral_gpu_server *s, const uint64_t *query);
 
+/* Wire form of what a client sends: the message is a sequence of polynomials in the raw form's order ([rows][cols][2048]), each
+ * coefficient a value in [0, Q] in 7 little-endian bytes (56 bits = logQ, the width the reference's summary counts, src/spiral.cpp:
+ * 219-242): 14 336 bytes per polynomial instead of the NTT form's 32 768.  A query is its n_query_cts ciphertexts n0 x 1; public
+ * parameters are ONE message holding the matrices of set_pub_params in its argument order (W_exp_left, W_exp_right, W, V; SpiralPack:
+ * W_exp_left, W_exp_right, V, v_W) with the same shapes.  Nothing is seeded or compressed beyond this.
+ * *_wire_bytes: the size of such a message (0 for parameters that get_shape / pack_get_shape refuse).
+ * raw_to_wire / raw_from_wire: the client's half, plain host code (no device): npolys raw polynomials <-> their wire form; raw_to_wire
+ * refuses a value above Q and then writes nothing.
+ * set_query_wire / set_pub_params_wire: the server's half.  The bytes go up through a bounded staging buffer and each chunk is decoded and
+ * transformed on the device straight into the buffers set_query / set_pub_params fill (so the same device state, and graphs captured
+ * before replay the new query without a re-capture; owners and lanes alike); one synchronisation at the end.  A wrong byte count or a
+ * coefficient above Q fails, naming the first bad coefficient, and leaves the server with NO query (resp. no public parameters): nothing
+ * answers from a half-written buffer.  Not during stream capture. */
+size_t spiral_gpu_query_wire_bytes(const spiral_gpu_params *p);
+size_t spiral_gpu_pub_params_wire_bytes(const spiral_gpu_params *p);
+int spiral_gpu_raw_to_wire(const uint64_t *raw, size_t npolys, void *wire);
+int spiral_gpu_raw_from_wire(const void *wire, size_t npolys, uint64_t *raw);
+int spiral_gpu_server_set_query_wire(spiral_gpu_server *s, const void *wire, size_t bytes);
+int spiral_gpu_server_set_pub_params_wire(spiral_gpu_server *s, const void *wire, size_t bytes);
+
 /* stages, asynchronous on the server stream */
 int spiral_gpu_server_expand(spiral_gpu_server *s);    /* expandImproved + reorderFromStopround      */
 int spiral_gpu_server_convert(spiral_gpu_server *s);   /* scalToMat x dim0, regevToGSW x nu2 (Q_neg = G2 - Q is derived where a fold round needs it) */
@@ -395,7 +415,8 @@ enum spiral_gpu_buffer {
     SPIRAL_GPU_BUF_ACC = 3,      /* num_per cts n1 x n2 NTT: the sweep output                              */
     SPIRAL_GPU_BUF_RAW = 4,      /* num_per cts n1 x n2 raw: after lift / after folding rounds             */
     SPIRAL_GPU_BUF_FINAL = 5,    /* n1 x n2 raw                                                            */
-    SPIRAL_GPU_BUF_RESPONSE = 6  /* n1 x n2 rescaled                                                       */
+    SPIRAL_GPU_BUF_RESPONSE = 6, /* n1 x n2 rescaled                                                       */
+    SPIRAL_GPU_BUF_QUERY = 7     /* the resident query: n_query_cts cts n0 x 1 NTT (set_query / set_query_wire) */
 };
 int spiral_gpu_server_keep_cts(spiral_gpu_server *s, int on);
 size_t spiral_gpu_server_buffer_words(spiral_gpu_server *s, int which);
@@ -503,6 +524,18 @@ uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algor
 int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server *owner, spiral_gpu_pack_server **out);
 int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server *const *servers, uint32_t n, const uint64_t *const *queries,
                                         uint64_t *const *responses, uint64_t *const *packed_cts, double stage_us[8]);
+/* SpiralPack from the wire form (see spiral_gpu_query_wire_bytes above): the sizes of a query and of the public parameters for `out_n`, the
+ * public parameters as one message, and answer / answer_batch with the queries in their wire form (there is no set_query on this path).
+ * answer_batch_wire checks every argument, each query's byte count included, before anything is uploaded, and runs the batch only when every
+ * query decoded cleanly: a bad query leaves every lane's previous results intact. */
+size_t spiral_gpu_pack_query_wire_bytes(const spiral_gpu_params *p, uint32_t out_n);
+size_t spiral_gpu_pack_pub_params_wire_bytes(const spiral_gpu_params *p, uint32_t out_n);
+int spiral_gpu_pack_server_set_pub_params_wire(spiral_gpu_pack_server *s, const void *wire, size_t bytes);
+int spiral_gpu_pack_server_answer_wire(spiral_gpu_pack_server *s, const void *query_wire, size_t bytes, uint64_t *response,
+                                       uint64_t *packed_ct, double stage_us[8]);
+int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server *const *servers, uint32_t n, const void *const *query_wires,
+                                             size_t bytes_each, uint64_t *const *responses, uint64_t *const *packed_cts,
+                                             double stage_us[8]);
 int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server *s, int format);
 int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server *s);
 uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server *s);

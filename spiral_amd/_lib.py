@@ -181,6 +181,17 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_db_format": (C.c_int, [C.c_void_p]),
     "spiral_gpu_pack_server_db_device_bytes": (C.c_uint64, [C.c_void_p]),
     "spiral_gpu_pack_server_time_sweep_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_float)]),
+    "spiral_gpu_query_wire_bytes": (C.c_size_t, [C.POINTER(Params)]),
+    "spiral_gpu_pub_params_wire_bytes": (C.c_size_t, [C.POINTER(Params)]),
+    "spiral_gpu_pack_query_wire_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32]),
+    "spiral_gpu_pack_pub_params_wire_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32]),
+    "spiral_gpu_raw_to_wire": (C.c_int, [U64P, C.c_size_t, C.c_void_p]),
+    "spiral_gpu_raw_from_wire": (C.c_int, [C.c_void_p, C.c_size_t, U64P]),
+    "spiral_gpu_server_set_query_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_server_set_pub_params_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_pack_server_set_pub_params_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_pack_server_answer_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, U64P, U64P, C.POINTER(C.c_double)]),
+    "spiral_gpu_pack_server_answer_batch_wire": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
 }
 
 
@@ -222,6 +233,19 @@ class SpiralGpuError(RuntimeError):
 def check(rc: int) -> None:
     if rc != 0:
         raise SpiralGpuError(lib().spiral_gpu_last_error().decode() or f"error {rc}")
+
+
+WIRE_POLY_BYTES = 7 * 2048  # one polynomial of a query / public-parameter message in its wire form (include/spiral_gpu.h)
+
+
+def wire_bytes(wire) -> np.ndarray:
+    """a wire message (bytes, bytearray, memoryview or an array) as one contiguous uint8 array"""
+    if isinstance(wire, (bytes, bytearray, memoryview)):
+        return np.frombuffer(wire, dtype=np.uint8)
+    wire = np.ascontiguousarray(wire)
+    if wire.dtype != np.uint8:
+        raise TypeError(f"a wire message is bytes or a uint8 array, not {wire.dtype}")
+    return wire.reshape(-1)
 
 
 def update_args(items, coeff_bits: int, item_ids, polys_per_item: int):

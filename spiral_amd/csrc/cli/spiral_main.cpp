@@ -2,6 +2,7 @@
 // 209-265), with the server-answer path running on an MI355X through libspiral_gpu.so.
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
+//            [--wire-input]
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -17,6 +18,8 @@
 #include <iostream>
 #include <random>
 #include <string>
+
+#include <hip/hip_runtime_api.h>
 
 #include "client.hpp"
 
@@ -47,6 +50,49 @@ static uint64_t param(int argc, char** argv, const char* name, uint64_t dflt) {
 
 static size_t bits_to_bytes(size_t bits) { return (size_t)std::llround((double)bits / 8.0); }
 
+// --wire-input: every public parameter and query goes to the server in its wire form (include/spiral_gpu.h): the client takes its NTT-form
+// polynomials back to raw form (spiral_gpu_from_ntt) and packs them at 7 bytes per coefficient; the server decodes them on the device
+static bool g_wire = false;
+static uint64_t g_wire_offline = 0, g_wire_online = 0;  // bytes the first client actually sent
+struct Segment {
+    const Poly* ntt;
+    size_t npolys;
+};
+static std::vector<uint8_t> wire_of(std::initializer_list<Segment> segs) {
+    size_t n = 0;
+    for (const Segment& g : segs) n += g.npolys;
+    Poly raw(n * N);
+    size_t at = 0;
+    for (const Segment& g : segs) {
+        if (g.npolys) GPU_OK(spiral_gpu_from_ntt(raw.data() + at * N, g.ntt->data(), g.npolys));
+        at += g.npolys;
+    }
+    std::vector<uint8_t> w(n * 7 * N);
+    GPU_OK(spiral_gpu_raw_to_wire(raw.data(), n, w.data()));
+    return w;
+}
+static std::vector<uint8_t> query_wire(const Poly& q) { return wire_of({{&q, q.size() / (2 * N)}}); }
+static std::vector<uint8_t> pp_wire(const spiral_gpu_params& p, const spiral_gpu_shape& s, const Client& c) {
+    return wire_of({{&c.w_left, (size_t)s.n_left * 2 * p.t_exp}, {&c.w_right, (size_t)s.n_right * 2 * p.t_exp_right}, {&c.w, (size_t)6 * p.t_conv},
+                    {&c.v, (size_t)6 * p.t_conv}});
+}
+static std::vector<uint8_t> pack_pp_wire(const spiral_gpu_params& p, const spiral_gpu_pack_shape& s, uint32_t out_n, const PackClient& c) {
+    const bool ex = !p.direct_upload;
+    return wire_of({{&c.w_left, ex ? (size_t)s.n_left * 2 * p.t_exp : 0}, {&c.w_right, ex ? (size_t)s.n_right * 2 * p.t_exp_right : 0},
+                    {&c.v, ex ? (size_t)4 * p.t_conv : 0}, {&c.v_w, (size_t)out_n * (out_n + 1) * p.t_conv}});
+}
+static void print_wire_bytes() {
+    if (g_wire) cout << "   Wire input, uploaded offline / online (b): " << g_wire_offline << " / " << g_wire_online << endl;
+}
+// device buffers for the resident entry points the wire path drives (the host-buffer ones take NTT-form queries)
+#define HIP_CLI_OK(x)                                                                        \
+    do {                                                                                     \
+        if ((x) != hipSuccess) {                                                             \
+            fprintf(stderr, "spiral: %s failed\n", #x);                                      \
+            exit(1);                                                                         \
+        }                                                                                    \
+    } while (0)
+
 // testHighRate (src/testing.cpp:777-1154): SpiralPack / SpiralStreamPack end to end, summary of :626-733
 static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_target, uint64_t seed, bool nonoise, bool show_diff, uint64_t qnum_first, uint32_t batch) {
     cout << "Using n=" << out_n << endl;
@@ -67,11 +113,19 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     t0 = now_us();
     Poly query = cl.query(idx_target);
     const double time_query_gen = (double)(now_us() - t0);
-    GPU_OK(spiral_gpu_pack_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.v.data(), cl.v_w.data()));
     Poly resp((size_t)(out_n + 1) * out_n * N);
     double us[8];
-    GPU_OK(spiral_gpu_pack_server_answer(srv, query.data(), resp.data(), nullptr, us));  // warm-up
-    GPU_OK(spiral_gpu_pack_server_answer(srv, query.data(), resp.data(), nullptr, us));
+    if (g_wire) {
+        const std::vector<uint8_t> pw = pack_pp_wire(p, s, out_n, cl), qw = query_wire(query);
+        g_wire_offline = pw.size(), g_wire_online = qw.size();
+        GPU_OK(spiral_gpu_pack_server_set_pub_params_wire(srv, pw.data(), pw.size()));
+        GPU_OK(spiral_gpu_pack_server_answer_wire(srv, qw.data(), qw.size(), resp.data(), nullptr, us));  // warm-up
+        GPU_OK(spiral_gpu_pack_server_answer_wire(srv, qw.data(), qw.size(), resp.data(), nullptr, us));
+    } else {
+        GPU_OK(spiral_gpu_pack_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.v.data(), cl.v_w.data()));
+        GPU_OK(spiral_gpu_pack_server_answer(srv, query.data(), resp.data(), nullptr, us));  // warm-up
+        GPU_OK(spiral_gpu_pack_server_answer(srv, query.data(), resp.data(), nullptr, us));
+    }
     // the response travels in its wire form (bit-packed on the device, include/spiral_gpu.h); the client unpacks and decodes it
     std::vector<uint8_t> wire(spiral_gpu_response_wire_bytes(&p, out_n));
     GPU_OK(spiral_gpu_pack_server_read_response_wire(srv, wire.data(), wire.size()));
@@ -149,16 +203,30 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
             clients[b].keygen();
             clients[b].gen_pub_params();
             idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);
-            GPU_OK(spiral_gpu_pack_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].v.data(), clients[b].v_w.data()));
+            if (g_wire) {
+                const std::vector<uint8_t> pw = pack_pp_wire(p, s, out_n, clients[b]);
+                GPU_OK(spiral_gpu_pack_server_set_pub_params_wire(lanes[b], pw.data(), pw.size()));
+            } else {
+                GPU_OK(spiral_gpu_pack_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].v.data(), clients[b].v_w.data()));
+            }
             queries.push_back(clients[b].query(idxs[b]));
         }
         std::vector<const uint64_t*> qp;
         std::vector<uint64_t*> rp;
+        std::vector<std::vector<uint8_t>> qws;
+        std::vector<const void*> qwp;
         for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].data()), rp.push_back(resps[b].data());
+        if (g_wire)
+            for (uint32_t b = 0; b < batch; b++) qws.push_back(query_wire(queries[b]));
+        for (uint32_t b = 0; b < qws.size(); b++) qwp.push_back(qws[b].data());
+        auto run = [&](uint64_t* const* r, double* u) {
+            if (g_wire) GPU_OK(spiral_gpu_pack_server_answer_batch_wire(lanes.data(), batch, qwp.data(), qws[0].size(), r, nullptr, u));
+            else GPU_OK(spiral_gpu_pack_server_answer_batch(lanes.data(), batch, qp.data(), r, nullptr, u));
+        };
         double bus[8];
-        GPU_OK(spiral_gpu_pack_server_answer_batch(lanes.data(), batch, qp.data(), nullptr, nullptr, bus));  // warm-up (converts the image where it can)
+        run(nullptr, bus);  // warm-up (converts the image where it can)
         t0 = now_us();
-        GPU_OK(spiral_gpu_pack_server_answer_batch(lanes.data(), batch, qp.data(), rp.data(), nullptr, bus));
+        run(rp.data(), bus);
         const double batch_us = (double)(now_us() - t0);
         cout << "Batch of " << batch << " queries, Is correct?:";
         for (uint32_t b = 0; b < batch; b++) {
@@ -176,6 +244,7 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
         spiral_gpu_pack_server_destroy(srv);
         return 1;
     }
+    print_wire_bytes();
     spiral_gpu_pack_server_destroy(srv);
     return (is_corr && batch_corr) ? 0 : 2;
 }
@@ -208,6 +277,8 @@ int main(int argc, char** argv) {
         // plaintext size)): an item of F plaintexts = F instances of the database; the one query is converted once and answered against all of them by ONE
         // call of spiral_gpu_server_answer_instances, every plaintext of the item is decoded and checked
         if (!strcmp(argv[i], "--instances") && i + 1 < argc) instances = (uint32_t)strtoul(argv[++i], nullptr, 10);
+        // --wire-input (not a flag of the reference): public parameters and queries reach the server in their 7-byte wire form (include/spiral_gpu.h)
+        if (!strcmp(argv[i], "--wire-input")) { cout << "Sending public parameters and queries in their wire form" << endl; g_wire = true; }
         // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
         // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
         // --output-err F (src/spiral.cpp:1287-1291) asks the reference to dump its empirical noise statistics (analyze_err.py's
@@ -218,6 +289,10 @@ int main(int argc, char** argv) {
     const bool item_batch = batch && instances;
     if (item_batch && (batch < 2 || batch > 8 || instances < 2 || instances > 16 || high_rate)) {
         fprintf(stderr, "spiral: --batch B --instances F takes B in 2 .. 8 and F in 2 .. 16 (and no --high-rate)\n");
+        return 1;
+    }
+    if (g_wire && ((batch && (batch < 2 || batch > 8)) || (instances && (instances < 2 || instances > 16 || high_rate)))) {
+        fprintf(stderr, "spiral: --wire-input takes --batch B in 2 .. 8 and --instances F in 2 .. 16 (not with --high-rate)\n");
         return 1;
     }
     if (idx_target >= total_n) {
@@ -281,11 +356,23 @@ int main(int argc, char** argv) {
 
     // ---- server
     cout << "Beginning query processing..." << endl;
-    GPU_OK(spiral_gpu_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.w.data(), cl.v.data()));
     Poly final_ct(6 * N), resp(6 * N);
     double us[8];
-    GPU_OK(spiral_gpu_server_answer(srv, query.data(), final_ct.data(), resp.data(), us));  // warm-up (table upload, first launches)
-    GPU_OK(spiral_gpu_server_answer(srv, query.data(), final_ct.data(), resp.data(), us));
+    std::vector<uint8_t> qwire;  // (--wire-input) the query as sent
+    if (g_wire) {
+        const std::vector<uint8_t> pw = pp_wire(p, s, cl);
+        qwire = query_wire(query);
+        g_wire_offline = pw.size(), g_wire_online = qwire.size();
+        GPU_OK(spiral_gpu_server_set_pub_params_wire(srv, pw.data(), pw.size()));
+        for (int it = 0; it < 2; it++) {  // warm-up (table upload, first launches), then the answer
+            GPU_OK(spiral_gpu_server_set_query_wire(srv, qwire.data(), qwire.size()));
+            GPU_OK(spiral_gpu_server_answer_resident(srv, us));
+        }
+    } else {
+        GPU_OK(spiral_gpu_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.w.data(), cl.v.data()));
+        GPU_OK(spiral_gpu_server_answer(srv, query.data(), final_ct.data(), resp.data(), us));  // warm-up (table upload, first launches)
+        GPU_OK(spiral_gpu_server_answer(srv, query.data(), final_ct.data(), resp.data(), us));
+    }
     const double time_expansion_main = us[0], time_conversion = us[1], time_first_multiply = us[2], time_folding = us[3];
     cout << std::fixed << std::setprecision(0);
     cout << "Expansion took (CPU·us): " << time_expansion_main << endl;
@@ -330,9 +417,15 @@ int main(int argc, char** argv) {
             clients[b].keygen();
             clients[b].gen_pub_params();
             idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);
-            GPU_OK(spiral_gpu_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].w.data(), clients[b].v.data()));
             Poly qb = clients[b].query(idxs[b]);
-            GPU_OK(spiral_gpu_server_set_query(lanes[b], qb.data()));
+            if (g_wire) {
+                const std::vector<uint8_t> pw = pp_wire(p, s, clients[b]), qw = query_wire(qb);
+                GPU_OK(spiral_gpu_server_set_pub_params_wire(lanes[b], pw.data(), pw.size()));
+                GPU_OK(spiral_gpu_server_set_query_wire(lanes[b], qw.data(), qw.size()));
+            } else {
+                GPU_OK(spiral_gpu_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].w.data(), clients[b].v.data()));
+                GPU_OK(spiral_gpu_server_set_query(lanes[b], qb.data()));
+            }
         }
         return 0;
     };
@@ -383,8 +476,22 @@ int main(int argc, char** argv) {
         if (make_instances()) return 1;
         std::vector<uint64_t> resps((size_t)instances * 6 * N);
         GPU_OK(spiral_gpu_server_use_graphs(srv, 1));
-        for (int it = 0; it < 3; it++)  // capture, a replay, the timed replay
-            GPU_OK(spiral_gpu_server_answer_instances(srv, inst.data(), instances, query.data(), resps.data(), nullptr, &item_us));
+        if (g_wire) {  // the query decoded into srv's buffer, the item answered by the resident entry point into device buffers
+            void* d_resp = nullptr;
+            HIP_CLI_OK(hipMalloc(&d_resp, resps.size() * sizeof(uint64_t)));
+            for (int it = 0; it < 3; it++) {
+                GPU_OK(spiral_gpu_server_set_query_wire(srv, qwire.data(), qwire.size()));
+                t0 = now_us();
+                GPU_OK(spiral_gpu_server_run_query_instances(srv, inst.data(), instances, 1, d_resp, nullptr));
+                GPU_OK(spiral_gpu_server_sync(srv));
+                item_us = (double)(now_us() - t0);
+            }
+            HIP_CLI_OK(hipMemcpy(resps.data(), d_resp, resps.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+            HIP_CLI_OK(hipFree(d_resp));
+        } else {
+            for (int it = 0; it < 3; it++)  // capture, a replay, the timed replay
+                GPU_OK(spiral_gpu_server_answer_instances(srv, inst.data(), instances, query.data(), resps.data(), nullptr, &item_us));
+        }
         cout << "Item of " << instances << " plaintexts, Is correct?:";
         for (uint32_t k = 0; k < instances; k++) {
             const bool ok = cl.decode(resps.data() + (size_t)k * 6 * N) == db_item(db_seed + k, idx_target, p.p_db);
@@ -410,8 +517,24 @@ int main(int argc, char** argv) {
         for (uint32_t b = 0; b < batch; b++) queries.push_back(clients[b].query(idxs[b]));
         for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].data());
         GPU_OK(spiral_gpu_server_use_graphs(srv, 1));
-        for (int it = 0; it < 3; it++)  // image conversion + capture, a replay, the timed replay
-            GPU_OK(spiral_gpu_server_answer_batch_instances(lanes.data(), batch, inst.data(), instances, qp.data(), nullptr, wires.data(), &item_batch_us));
+        if (g_wire) {  // each client's query decoded into its lane, the item batch answered by the resident entry point, wire forms to the host
+            std::vector<std::vector<uint8_t>> qws;
+            for (uint32_t b = 0; b < batch; b++) qws.push_back(query_wire(queries[b]));
+            void* d_wire = nullptr;
+            HIP_CLI_OK(hipMalloc(&d_wire, wires.size()));
+            for (int it = 0; it < 3; it++) {
+                for (uint32_t b = 0; b < batch; b++) GPU_OK(spiral_gpu_server_set_query_wire(lanes[b], qws[b].data(), qws[b].size()));
+                t0 = now_us();
+                GPU_OK(spiral_gpu_server_run_query_batch_instances(lanes.data(), batch, inst.data(), instances, 1, nullptr, nullptr, d_wire));
+                GPU_OK(spiral_gpu_server_sync(srv));
+                item_batch_us = (double)(now_us() - t0);
+            }
+            HIP_CLI_OK(hipMemcpy(wires.data(), d_wire, wires.size(), hipMemcpyDeviceToHost));
+            HIP_CLI_OK(hipFree(d_wire));
+        } else {
+            for (int it = 0; it < 3; it++)  // image conversion + capture, a replay, the timed replay
+                GPU_OK(spiral_gpu_server_answer_batch_instances(lanes.data(), batch, inst.data(), instances, qp.data(), nullptr, wires.data(), &item_batch_us));
+        }
         cout << "Batch of " << batch << " items of " << instances << " plaintexts, Is correct?:";
         for (uint32_t b = 0; b < batch; b++) {
             bool ok = true;
@@ -476,6 +599,7 @@ int main(int argc, char** argv) {
     if (item_batch_us > 0)
         cout << "   Batch of " << batch << " items of " << instances << " plaintexts (" << batch << " clients, " << instances << " database instances), device (GPU·us): "
              << item_batch_us << endl;
+    print_wire_bytes();
     if (item_us > 0) cout << "   Item of " << instances << " plaintexts (one query, " << instances << " database instances), device (GPU·us): " << item_us << endl;
     spiral_gpu_server_destroy(srv);
     return (is_corr && batch_corr && item_corr) ? 0 : 2;

@@ -463,6 +463,121 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
     return 0;
 }
 
+// ---- query and key ingest of both servers ----------------------------------------------------------------------------------------
+// NTT form: stage a host buffer of reference NTT-form polynomials ([2][N] u64 each) through `stage` and convert to PK
+inline int upload_ref_ntt(DevBuf& stage, hipStream_t st, const uint64_t* host, uint64_t* pk, size_t npolys) {
+    if (npolys == 0) return 0;
+    if (!host) return fail("null host buffer");
+    const size_t chunk = 4096;  // polynomials per staging pass (128 MiB)
+    if (stage.words < std::min(npolys, chunk) * kRefNtt) {
+        stage.release();
+        if (stage.alloc(std::min(npolys, chunk) * kRefNtt)) return -1;
+    }
+    for (size_t done = 0; done < npolys; done += chunk) {
+        const size_t n = std::min(chunk, npolys - done);
+        HIP_OK(hipMemcpyAsync(stage.p, host + done * kRefNtt, n * kRefNtt * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        launch_ref_to_pk(stage.p, pk + done * kN, (uint32_t)n, identity_map(), st);
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+// Wire form (include/spiral_gpu.h): one message = the segments' polynomials back to back, 7 bytes per raw coefficient.  The bytes go up through a
+// device staging buffer a chunk at a time and each chunk is decoded + transformed straight into its PK destination by one launch (LD_WIRE); the
+// launches and copies are ordered by the stream, so the host waits once, at the end, and then reads the lowest index of a coefficient above Q.
+// The error word is tagged with the call's generation instead of being reset, and read back through a pinned word (messages of at most
+// kWireHostCheckPolys polynomials are checked on the host instead: one copy up, one launch).  On failure the destinations hold a partial message: the caller drops what they held (have_query / have_pp).
+struct WireSegment {
+    uint64_t* pk;   // PK destination
+    size_t npolys;
+};
+struct WireIn {  // a server's ingest workspace, reused from call to call
+    DevBuf stage;                // [chunk bytes][u64 error word]
+    size_t chunk_polys = 0;
+    uint64_t* host_err = nullptr;  // pinned
+    uint32_t gen = 0;
+    void release() {
+        stage.release();
+        stage.words = 0;
+        chunk_polys = 0;
+        if (host_err) (void)hipHostFree(host_err);
+        host_err = nullptr;
+    }
+};
+constexpr size_t kWireChunkPolys = 4096;  // polynomials per staging pass (56 MiB)
+// Up to this many polynomials (a compressed query: 2) the host checks the coefficients before anything goes up -- about 1 ns per coefficient, less
+// than the readback of the device's error word, which is then skipped (a 2-polynomial set_query_wire took 34 us with the readback, set_query 28)
+constexpr size_t kWireHostCheckPolys = 4;
+inline int64_t wire_first_above_q(const uint8_t* b, size_t n) {
+    for (size_t i = 0; i < n; i++, b += kWireCoeffBytes) {
+        uint64_t v = 0;
+        memcpy(&v, b, kWireCoeffBytes);  // (little-endian host)
+        if (v > kQ) return (int64_t)i;
+    }
+    return -1;
+}
+inline int ingest_wire(WireIn& W, const DeviceTables& tb, hipStream_t st, const void* wire, size_t bytes, const WireSegment* seg, size_t nseg,
+                       const char* what) {
+    size_t npolys = 0;
+    for (size_t i = 0; i < nseg; i++) npolys += seg[i].npolys;
+    if (!wire) return fail("%s: null wire buffer", what);
+    if (bytes != npolys * kWirePolyBytes)
+        return fail("%s: %zu bytes, the wire form of %zu polynomials takes %zu", what, bytes, npolys, npolys * kWirePolyBytes);
+    if ((uint64_t)npolys * kN >= 0xffffffffull) return fail("%s: %zu polynomials exceed the coefficient index range", what, npolys);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("%s: the server's stream is capturing (call it outside stream capture)", what);
+    if (npolys == 0) return 0;
+    const bool host_checked = npolys <= kWireHostCheckPolys;
+    if (host_checked) {
+        const int64_t i = wire_first_above_q((const uint8_t*)wire, npolys * kN);
+        if (i >= 0) return fail("%s: coefficient %u (polynomial %u, index %u) is above Q", what, (uint32_t)i, (uint32_t)i / kN, (uint32_t)i % kN);
+    }
+    const size_t chunk = std::min(npolys, kWireChunkPolys);
+    if (W.chunk_polys < chunk || W.gen == 0xffffffffu) {  // (re)allocated: the error word starts at generation 0 (all ones)
+        W.stage.release();
+        W.chunk_polys = 0;
+        if (W.stage.alloc(chunk * kWirePolyBytes / 8 + 1)) return -1;
+        HIP_OK(hipMemset(W.stage.p + chunk * kWirePolyBytes / 8, 0xff, sizeof(uint64_t)));
+        W.chunk_polys = chunk;
+        W.gen = 0;
+    }
+    if (!W.host_err) HIP_OK(hipHostMalloc((void**)&W.host_err, sizeof(uint64_t), hipHostMallocDefault));
+    const uint32_t gen = ++W.gen;
+    uint8_t* d_wire = reinterpret_cast<uint8_t*>(W.stage.p);
+    uint64_t* d_err = W.stage.p + W.chunk_polys * kWirePolyBytes / 8;
+    FwdParams fp{};
+    fp.src_map = fp.dst_map = identity_map();
+    fp.n_digits = 1;
+    fp.items = d_wire;
+    fp.err = reinterpret_cast<uint32_t*>(d_err);
+    fp.seed = gen;
+    size_t first = 0;  // message index of the segment's first polynomial
+    for (size_t i = 0; i < nseg; i++) {
+        for (size_t done = 0; done < seg[i].npolys; done += W.chunk_polys) {
+            const size_t n = std::min(W.chunk_polys, seg[i].npolys - done);
+            HIP_OK(hipMemcpyAsync(d_wire, (const uint8_t*)wire + (first + done) * kWirePolyBytes, n * kWirePolyBytes, hipMemcpyHostToDevice, st));
+            fp.dst = seg[i].pk + done * kN;
+            fp.item_base = first + done;
+            launch_ntt_forward(tb, fp, LD_WIRE, ST_PK, (uint32_t)n, st);
+        }
+        first += seg[i].npolys;
+    }
+    HIP_OK(hipGetLastError());
+    if (host_checked) {
+        HIP_OK(hipStreamSynchronize(st));
+        return 0;
+    }
+    HIP_OK(hipMemcpyAsync(W.host_err, d_err, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    const uint64_t err = *W.host_err;
+    if ((uint32_t)(err >> 32) == ~gen) {
+        const uint32_t i = (uint32_t)err;
+        return fail("%s: coefficient %u (polynomial %u, index %u) is above Q", what, i, i / kN, i % kN);
+    }
+    return 0;
+}
+
 // upload reference NTT-form polynomials and convert to PK / the converse
 inline uint64_t* upload_pk(Scratch& sc, const uint64_t* host_ref, size_t npolys) {
     uint64_t* d_ref = sc.upload(host_ref, npolys * kRefNtt);

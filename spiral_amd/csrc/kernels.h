@@ -117,7 +117,12 @@ enum FwdLoad : uint32_t {
                     // ct np + i and ct i, destination D'[trial][i][row + 2k]  (foldCiphertextsDim1 through the same identity as LD_SDIFF)
     LD_EXPAND = 5,  // one expansion round: digits of automorph(c)[0] and the reduced automorph(c)[1] of every
                     // active ciphertext, both parities, in one launch      (src/spiral.cpp:1711-1720)
+    LD_WIRE = 10,   // raw coefficient in its 7-byte wire form (kWirePolyBytes per polynomial at `items`), reduced as LD_RAW; a value above Q
+                    // atomicMin's (~seed << 32 | its message-wide index) into the u64 at err (item_base = the chunk's first polynomial, seed = the
+                    // call's generation: a later call's entries compare below every earlier one's, so the word is never reset; ST_PK only, no lanes)
 };
+constexpr uint32_t kWireCoeffBytes = 7;                        // logQ = 56 bits, little-endian
+constexpr uint32_t kWirePolyBytes = kWireCoeffBytes * 2048u;   // 14 336: a multiple of 16
 enum FwdStore : uint32_t {
     ST_PK = 0,      // packed slot words
     ST_REF = 1,     // reference layout [2][N] u64

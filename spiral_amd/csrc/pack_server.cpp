@@ -21,6 +21,7 @@ struct spiral_gpu_pack_server {
     size_t db_words = 0;  // per trial
     DevBuf db, w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
     DevBuf gs_raw, gs_chat, gs_tmp, gsw, key, qs1, acc, raw, fold_d, fold_c, fold_c2, pk_ginv, pk_ct2, pk_res, pk_raw, resp, stage, wire;
+    WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
     hipEvent_t ev[8] = {};
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
     // query lanes (create_lane): a lane has no image of its own and sweeps its owner's; the owner counts its lanes.  Destroying an owner that
@@ -70,6 +71,7 @@ void pk_free(spiral_gpu_pack_server* S, bool keep_db = false) {
     if (keep_db) S->db = DevBuf{};
     for (DevBuf* b : all) b->release();
     S->upd.release();
+    S->wire_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     if (S->stream && S->own_stream) (void)hipStreamDestroy(S->stream);
@@ -115,22 +117,7 @@ int pk_alloc(spiral_gpu_pack_server* S) {
     return 0;
 }
 
-int pk_upload_ref_ntt(spiral_gpu_pack_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) {
-    if (npolys == 0) return 0;
-    if (!host) return fail("null host buffer");
-    const size_t chunk = 4096;
-    if (S->stage.words < std::min(npolys, chunk) * kRefNtt) {
-        S->stage.release();
-        if (S->stage.alloc(std::min(npolys, chunk) * kRefNtt)) return -1;
-    }
-    for (size_t done = 0; done < npolys; done += chunk) {
-        const size_t n = std::min(chunk, npolys - done);
-        HIP_OK(hipMemcpyAsync(S->stage.p, host + done * kRefNtt, n * kRefNtt * sizeof(uint64_t), hipMemcpyHostToDevice, S->stream));
-        launch_ref_to_pk(S->stage.p, pk + done * kN, (uint32_t)n, identity_map(), S->stream);
-        HIP_OK(hipStreamSynchronize(S->stream));
-    }
-    return 0;
-}
+int pk_upload_ref_ntt(spiral_gpu_pack_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) { return host::upload_ref_ntt(S->stage, S->stream, host, pk, npolys); }
 
 // pack (src/testing.cpp:198-241) on device buffers: raw cts at trial stride `ct_stride` polynomials
 void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_stride_cts, const uint64_t* v_w, uint64_t* ginv, uint64_t* ct2, uint64_t* result,
@@ -469,14 +456,44 @@ int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server* S, const uint6
     return 0;
 }
 
+// the same from the wire form: one message W_exp_left, W_exp_right, V (expansion only), v_W; a failure leaves no public parameters
+int spiral_gpu_pack_server_set_pub_params_wire(spiral_gpu_pack_server* S, const void* wire, size_t bytes) {
+    if (!S) return fail("null server");
+    if (S->zombie) return fail("destroyed server");
+    HIP_OK(hipSetDevice(S->device));
+    const spiral_gpu_params& p = S->p;
+    const bool ex = !p.direct_upload;
+    const WireSegment seg[4] = {{S->w_left.p, ex ? (size_t)S->s.n_left * 2 * p.t_exp : 0},
+                                {S->w_right.p, ex ? (size_t)S->s.n_right * 2 * p.t_exp_right : 0},
+                                {S->v.p, ex ? (size_t)2 * 2 * p.t_conv : 0},
+                                {S->v_w.p, (size_t)S->out_n * (S->out_n + 1) * p.t_conv}};
+    S->have_pp = false;
+    if (ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, seg, 4, "set_pub_params_wire")) return -1;
+    S->have_pp = true;
+    return 0;
+}
+
+size_t spiral_gpu_pack_query_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) {
+    spiral_gpu_pack_shape s;
+    if (!p || pack_shape_of(p, out_n, &s)) return 0;
+    return (size_t)s.n_query_cts * 2 * kWirePolyBytes;
+}
+
+size_t spiral_gpu_pack_pub_params_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) {
+    spiral_gpu_pack_shape s;
+    if (!p || pack_shape_of(p, out_n, &s)) return 0;
+    const size_t ex = p->direct_upload ? 0 : (size_t)s.n_left * 2 * p->t_exp + (size_t)s.n_right * 2 * p->t_exp_right + (size_t)2 * 2 * p->t_conv;
+    return (ex + (size_t)out_n * (out_n + 1) * p->t_conv) * kWirePolyBytes;
+}
+
 // The answer up to and including the folding, for this server's trials, in three pieces (pk_front; answer_batch puts one shared sweep between the
 // lanes' first and last pieces): the folded ciphertexts end up at the head of each trial's num_per slots of S->raw (events 0..5 bracket the stages).
-// Piece 1: query upload, expansion and conversion -> the sweep's records qs1 and the folding keys, on `st`
+// Piece 1: query upload (none with query = null: the wire entry points decoded it into S->query), expansion and conversion -> the sweep's records qs1 and the folding keys, on `st`
 static int pk_expand_convert(spiral_gpu_pack_server* S, const uint64_t* query, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
     const uint32_t ell = s.ell, ngs = p.nu2 * ell;
-    if (pk_upload_ref_ntt(S, query, S->query.p, (size_t)s.n_query_cts * 2)) return -1;
+    if (query && pk_upload_ref_ntt(S, query, S->query.p, (size_t)s.n_query_cts * 2)) return -1;  // (null: decoded from the wire form already)
 
     HIP_OK(hipEventRecord(S->ev[0], st));
     // ---- coefficientExpansion + reorientCiphertextsDim1 (src/testing.cpp:1009-1020)
@@ -624,14 +641,39 @@ static int pk_download(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* 
     return 0;
 }
 
-int spiral_gpu_pack_server_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
-    if (!S || !query) return fail("null argument");
+// what answer and answer_wire check before anything is uploaded
+static int pk_check_answer(spiral_gpu_pack_server* S) {
     if (S->zombie) return fail("destroyed server");
     HIP_OK(hipSetDevice(S->device));
     if (!pk_holder(S)->have_db || !S->have_pp) return fail("database and public parameters must be set first");
     if (S->nt != S->s.trials) return fail("this server holds trials [%u, %u) only: fold_trials + pack_gathered", S->t0, S->t0 + S->nt);
+    return 0;
+}
+
+// the query's wire form decoded into S->query on S's stream (returns synchronised)
+static int pk_query_wire(spiral_gpu_pack_server* S, const void* wire, size_t bytes, const char* what) {
+    HIP_OK(hipSetDevice(S->device));
+    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2};
+    return ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, &seg, 1, what);
+}
+
+// answer with the query in S->query already when query is null
+static int pk_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
     if (pk_front(S, query) || pk_back(S, S->raw.p, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
     return stage_us ? spiral_gpu_pack_server_stage_us(S, stage_us) : 0;
+}
+
+int spiral_gpu_pack_server_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
+    if (!S || !query) return fail("null argument");
+    if (pk_check_answer(S)) return -1;
+    return pk_answer(S, query, response, packed_ct, stage_us);
+}
+
+int spiral_gpu_pack_server_answer_wire(spiral_gpu_pack_server* S, const void* query_wire, size_t bytes, uint64_t* response, uint64_t* packed_ct,
+                                       double stage_us[8]) {
+    if (!S || !query_wire) return fail("null argument");
+    if (pk_check_answer(S) || pk_query_wire(S, query_wire, bytes, "answer_wire")) return -1;
+    return pk_answer(S, nullptr, response, packed_ct, stage_us);
 }
 
 // the lanes of a batch: n in 1 .. kMaxLanes distinct servers that sweep the same images (an owner and its lanes), none trial-sharded, every one
@@ -660,6 +702,9 @@ static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bo
 // Beyond the reference (one query per call): n <= kMaxLanes queries, one per server, in one launch sequence on servers[0]'s stream -- expansion and
 // conversion per lane, ONE first-dimension pass over the trial images for all of them (matrix cores, once the image is in limb-plane form: the first
 // batch on a covered geometry converts it), then folding, packing and the modulus switch per lane.  Returns synchronised.
+static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
+                           uint64_t* const* packed_cts, double stage_us[8]);
+
 int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
                                         uint64_t* const* packed_cts, double stage_us[8]) {
     if (pk_check_lanes(servers, n, false, "answer_batch")) return -1;
@@ -667,13 +712,39 @@ int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server* const* servers, 
     for (uint32_t b = 0; b < n; b++)
         if (!queries[b]) return fail("answer_batch: query %u is null", b);
     if (n == 1) return spiral_gpu_pack_server_answer(servers[0], queries[0], responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
+    return pk_answer_batch(servers, n, queries, responses, packed_cts, stage_us);
+}
+
+// answer_batch from the queries' wire forms: every argument (each query's byte count included) is checked before anything is uploaded; then every
+// lane's query is decoded into its own buffer, and only when all of them decoded cleanly does the batch run -- a bad query leaves every lane's
+// previous results intact
+int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_wires, size_t bytes_each,
+                                             uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
+    if (pk_check_lanes(servers, n, false, "answer_batch_wire")) return -1;
+    if (!query_wires) return fail("answer_batch_wire: null queries");
+    const size_t want = (size_t)servers[0]->s.n_query_cts * 2 * kWirePolyBytes;
+    if (bytes_each != want) return fail("answer_batch_wire: %zu bytes per query, the wire form of a query takes %zu", bytes_each, want);
+    for (uint32_t b = 0; b < n; b++)
+        if (!query_wires[b]) return fail("answer_batch_wire: query %u is null", b);
+    for (uint32_t b = 0; b < n; b++) {
+        char what[48];
+        snprintf(what, sizeof(what), "answer_batch_wire: query %u", b);
+        if (pk_query_wire(servers[b], query_wires[b], bytes_each, what)) return -1;
+    }
+    if (n == 1) return pk_answer(servers[0], nullptr, responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
+    return pk_answer_batch(servers, n, nullptr, responses, packed_cts, stage_us);
+}
+
+// the batch after its checks; queries null: every lane's query was decoded into its buffer already
+static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
+                           uint64_t* const* packed_cts, double stage_us[8]) {
     spiral_gpu_pack_server* S = servers[0];
     spiral_gpu_pack_server* H = pk_holder(S);
     HIP_OK(hipSetDevice(S->device));
     if (H->db_format != SPIRAL_GPU_DB_LIMBS && sweep1_mfma_ok(H->s.num_per, H->s.dim0) && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     hipStream_t st = S->stream;
     for (uint32_t b = 0; b < n; b++)
-        if (pk_expand_convert(servers[b], queries[b], st)) return -1;
+        if (pk_expand_convert(servers[b], queries ? queries[b] : nullptr, st)) return -1;
     if (pk_sweep(servers, n, st)) return -1;
     HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at servers[n - 1]'s event 2)
     for (uint32_t b = 0; b < n; b++) {

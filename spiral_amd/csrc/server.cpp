@@ -56,6 +56,7 @@ struct spiral_gpu_server {
     DevBuf cv_raw, cv_g, key, cts_keep;  // key: [d][3][m2]: the GSW matrices Q (src/spiral.cpp:2324) -- the fold key; Q_neg = G2 - Q (:2361-2379) is never stored (poly.hip fold_mac_two_kernel)
     uint64_t *gs_raw_p = nullptr, *gs_chat_p = nullptr;  // the Regev->GSW halves of cv_raw / cv_g
     DevBuf qs, acc_own, raw, fold_d, fold_c, fold_c2, resp, stage;
+    WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
     uint64_t* acc = nullptr;
     hipEvent_t ev[8] = {};
     // captured stage groups (hipGraph): [0] expand + convert, [1] lift + fold + finish, [2] the same with
@@ -210,6 +211,7 @@ void srv_free(spiral_gpu_server* S, bool keep_db = false) {
     if (S->db_shared) S->db.p = nullptr;
     for (DevBuf* b : all) b->release();
     S->upd.release();
+    S->wire_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e);
     if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
@@ -368,23 +370,7 @@ int srv_join_side(spiral_gpu_server* S) {
     return 0;
 }
 
-// stage a host buffer through a device staging area and convert reference NTT layout -> PK
-int upload_ref_ntt(spiral_gpu_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) {
-    if (npolys == 0) return 0;
-    if (!host) return fail("null host buffer");
-    const size_t chunk = 4096;  // polynomials per staging pass (128 MiB)
-    if (S->stage.words < std::min(npolys, chunk) * kRefNtt) {
-        S->stage.release();
-        if (S->stage.alloc(std::min(npolys, chunk) * kRefNtt)) return -1;
-    }
-    for (size_t done = 0; done < npolys; done += chunk) {
-        const size_t n = std::min(chunk, npolys - done);
-        HIP_OK(hipMemcpyAsync(S->stage.p, host + done * kRefNtt, n * kRefNtt * sizeof(uint64_t), hipMemcpyHostToDevice, S->stream));
-        launch_ref_to_pk(S->stage.p, pk + done * kN, (uint32_t)n, identity_map(), S->stream);
-        HIP_OK(hipStreamSynchronize(S->stream));
-    }
-    return 0;
-}
+int upload_ref_ntt(spiral_gpu_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) { return host::upload_ref_ntt(S->stage, S->stream, host, pk, npolys); }
 
 int download_pk_as_ref(spiral_gpu_server* S, const uint64_t* pk, IndexMap map, uint64_t* host, size_t npolys) {
     if (npolys == 0) return 0;
@@ -1209,6 +1195,69 @@ int spiral_gpu_server_set_query(spiral_gpu_server* S, const uint64_t* query) {
     if (upload_ref_ntt(S, query, S->query.p, (size_t)S->s.n_query_cts * 2)) return -1;
     S->have_query = true;
     S->have_records = false;
+    return 0;
+}
+
+// the same from the wire form (include/spiral_gpu.h): decoded and transformed on the device into the same buffers, so graphs captured on them replay
+// the new query; any failure leaves no public parameters / no query behind
+int spiral_gpu_server_set_pub_params_wire(spiral_gpu_server* S, const void* wire, size_t bytes) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const spiral_gpu_params& p = S->p;
+    const WireSegment seg[4] = {{S->w_left.p, (size_t)S->s.n_left * 2 * p.t_exp},
+                                {S->w_right.p, (size_t)S->s.n_right * 2 * p.t_exp_right},
+                                {S->w.p, (size_t)3 * 2 * p.t_conv},
+                                {S->v.p, (size_t)3 * 2 * p.t_conv}};
+    S->have_pp = false;
+    if (ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, seg, 4, "set_pub_params_wire")) return -1;
+    S->have_pp = true;
+    return 0;
+}
+
+int spiral_gpu_server_set_query_wire(spiral_gpu_server* S, const void* wire, size_t bytes) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2};
+    S->have_query = S->have_records = false;
+    if (ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, &seg, 1, "set_query_wire")) return -1;
+    S->have_query = true;
+    return 0;
+}
+
+size_t spiral_gpu_query_wire_bytes(const spiral_gpu_params* p) {
+    spiral_gpu_shape s;
+    if (shape_of(p, &s)) return 0;
+    return (size_t)s.n_query_cts * 2 * kWirePolyBytes;
+}
+
+size_t spiral_gpu_pub_params_wire_bytes(const spiral_gpu_params* p) {
+    spiral_gpu_shape s;
+    if (shape_of(p, &s)) return 0;
+    return ((size_t)s.n_left * 2 * p->t_exp + (size_t)s.n_right * 2 * p->t_exp_right + (size_t)12 * p->t_conv) * kWirePolyBytes;
+}
+
+// the client's half of the wire form: plain host code, no device involved
+int spiral_gpu_raw_to_wire(const uint64_t* raw, size_t npolys, void* wire) {
+    if (!raw || !wire) return fail("raw_to_wire: null argument");
+    const size_t n = npolys * kN;
+    for (size_t i = 0; i < n; i++)  // checked before anything is written
+        if (raw[i] > kQ)
+            return fail("raw_to_wire: coefficient %zu (polynomial %zu, index %zu) is %llu, above Q", i, i / kN, i % kN, (unsigned long long)raw[i]);
+    uint8_t* b = (uint8_t*)wire;
+    for (size_t i = 0; i < n; i++, b += kWireCoeffBytes)
+        for (uint32_t k = 0; k < kWireCoeffBytes; k++) b[k] = (uint8_t)(raw[i] >> (8 * k));
+    return 0;
+}
+
+int spiral_gpu_raw_from_wire(const void* wire, size_t npolys, uint64_t* raw) {
+    if (!raw || !wire) return fail("raw_from_wire: null argument");
+    const uint8_t* b = (const uint8_t*)wire;
+    const size_t n = npolys * kN;
+    for (size_t i = 0; i < n; i++, b += kWireCoeffBytes) {
+        uint64_t v = 0;
+        for (uint32_t k = 0; k < kWireCoeffBytes; k++) v |= (uint64_t)b[k] << (8 * k);
+        raw[i] = v;
+    }
     return 0;
 }
 
@@ -2327,6 +2376,7 @@ size_t spiral_gpu_server_buffer_words(spiral_gpu_server* S, int which) {
         case SPIRAL_GPU_BUF_RAW: return (size_t)s.num_per * 6 * kN;
         case SPIRAL_GPU_BUF_FINAL: return (size_t)6 * kN;
         case SPIRAL_GPU_BUF_RESPONSE: return (size_t)6 * kN;
+        case SPIRAL_GPU_BUF_QUERY: return (size_t)s.n_query_cts * 2 * kRefNtt;
         default: return 0;
     }
 }
@@ -2352,6 +2402,7 @@ int spiral_gpu_server_read(spiral_gpu_server* S, int which, uint64_t* out) {
         case SPIRAL_GPU_BUF_RAW: HIP_OK(hipMemcpy(out, S->raw.p, (size_t)s.num_per * 6 * kPolyBytes, hipMemcpyDeviceToHost)); return 0;
         case SPIRAL_GPU_BUF_FINAL: HIP_OK(hipMemcpy(out, S->raw.p, 6 * kPolyBytes, hipMemcpyDeviceToHost)); return 0;
         case SPIRAL_GPU_BUF_RESPONSE: HIP_OK(hipMemcpy(out, S->resp.p, 6 * kPolyBytes, hipMemcpyDeviceToHost)); return 0;
+        case SPIRAL_GPU_BUF_QUERY: return download_pk_as_ref(S, S->query.p, identity_map(), out, (size_t)s.n_query_cts * 2);
         default: return fail("unknown buffer %d", which);
     }
 }

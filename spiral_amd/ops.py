@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, Params, Shape, check, lib
+from ._lib import WIRE_POLY_BYTES, U64P, Params, Shape, check, lib, wire_bytes
 
 N = 2048
 P = 268369921
@@ -17,6 +17,7 @@ __all__ = [
     "N", "P", "B", "Q", "make_params", "get_shape", "get_tables", "ntt_forward", "ntt_inverse", "to_ntt", "to_ntt_no_reduce", "from_ntt",
     "multiply", "add", "mul_by_const", "automorph", "invert", "gadget_invert", "getRescaled", "multiplyQueryByDatabase", "multiplyQueriesByDatabase", "split_and_crt",
     "foldOneFurtherDimension", "expandImproved", "scalToMat", "regevToGSW", "time_ntt", "time_ntt_digits", "response_wire_bytes", "response_from_wire",
+    "query_wire_bytes", "pub_params_wire_bytes", "pack_query_wire_bytes", "pack_pub_params_wire_bytes", "raw_to_wire", "raw_from_wire",
     "set_option", "get_option", "options",
 ]
 
@@ -172,6 +173,47 @@ def response_from_wire(params, wire, out_n: int = 2) -> np.ndarray:
     assert wire.size >= response_wire_bytes(params, out_n)
     out = np.zeros((out_n + 1, out_n, N), dtype=np.uint64)
     check(lib().spiral_gpu_response_from_wire(C.byref(params), out_n, wire.ctypes.data_as(C.c_void_p), _p(out)))
+    return out
+
+
+def query_wire_bytes(params) -> int:
+    """size of a query's wire form (include/spiral_gpu.h): n_query_cts ciphertexts n0 x 1 at 7 bytes per coefficient; 0 for refused parameters"""
+    return int(lib().spiral_gpu_query_wire_bytes(C.byref(params)))
+
+
+def pub_params_wire_bytes(params) -> int:
+    """size of the public parameters' wire form (W_exp_left, W_exp_right, W, V in one message); 0 for refused parameters"""
+    return int(lib().spiral_gpu_pub_params_wire_bytes(C.byref(params)))
+
+
+def pack_query_wire_bytes(params, out_n: int) -> int:
+    """SpiralPack: size of a query's wire form; 0 for refused parameters"""
+    return int(lib().spiral_gpu_pack_query_wire_bytes(C.byref(params), int(out_n)))
+
+
+def pack_pub_params_wire_bytes(params, out_n: int) -> int:
+    """SpiralPack: size of the public parameters' wire form (W_exp_left, W_exp_right, V, v_W in one message); 0 for refused parameters"""
+    return int(lib().spiral_gpu_pack_pub_params_wire_bytes(C.byref(params), int(out_n)))
+
+
+def raw_to_wire(raw) -> np.ndarray:
+    """the client's half of the wire form: raw polynomials (values in [0, Q], 2048 per polynomial) -> 7 bytes per coefficient, uint8; host code.
+    A value above Q is refused (SpiralGpuError naming it)"""
+    raw = _c(raw)
+    if raw.size % N:
+        raise ValueError(f"raw_to_wire: {raw.size} values are not whole polynomials of {N}")
+    out = np.zeros(raw.size // N * WIRE_POLY_BYTES, dtype=np.uint8)
+    check(lib().spiral_gpu_raw_to_wire(_p(raw), raw.size // N, out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def raw_from_wire(wire) -> np.ndarray:
+    """the converse: a wire message -> [npolys][2048] raw values; host code"""
+    wire = wire_bytes(wire)
+    if wire.size % WIRE_POLY_BYTES:
+        raise ValueError(f"raw_from_wire: {wire.size} bytes are not whole polynomials of {WIRE_POLY_BYTES}")
+    out = np.zeros((wire.size // WIRE_POLY_BYTES, N), dtype=np.uint64)
+    check(lib().spiral_gpu_raw_from_wire(wire.ctypes.data_as(C.c_void_p), out.shape[0], _p(out)))
     return out
 
 

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, PackShape, Params, check, lib, update_args
+from ._lib import U64P, PackShape, Params, check, lib, update_args, wire_bytes
 
 N = 2048
 PACK_STAGE_NAMES = ["expansion_us", "conversion_us", "first_dim_us", "folding_us", "packing_us", "sweep_kernels_us", "total_us", "reserved"]
@@ -121,6 +121,21 @@ class PackServer:
     def set_pub_params(self, w_left, w_right, v, v_w):
         check(lib().spiral_gpu_pack_server_set_pub_params(self.h, _p(w_left), _p(w_right), _p(v), _p(v_w)))
 
+    def set_pub_params_wire(self, wire):
+        """the public parameters as one wire message (W_exp_left, W_exp_right, V -- expansion only -- and v_W); decoded on the device"""
+        w = wire_bytes(wire)
+        check(lib().spiral_gpu_pack_server_set_pub_params_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
+    def answer_wire(self, query_wire, want_packed: bool = True):
+        """answer with the query in its wire form: as answer"""
+        w = wire_bytes(query_wire)
+        n = self.out_n
+        resp = np.zeros((n + 1, n, N), dtype=np.uint64)
+        packed = np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None
+        us = (C.c_double * 8)()
+        check(lib().spiral_gpu_pack_server_answer_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size, _p(resp), _p(packed) if want_packed else None, us))
+        return resp, packed, dict(zip(PACK_STAGE_NAMES, list(us)))
+
     def answer(self, query, want_packed: bool = True):
         n = self.out_n
         resp = np.zeros((n + 1, n, N), dtype=np.uint64)
@@ -184,6 +199,24 @@ def answer_batch(servers, queries, want_packed: bool = False):
     arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
     us = (C.c_double * 8)()
     check(lib().spiral_gpu_pack_server_answer_batch(hs, len(servers), arr(qs), arr(resp), arr(packed), us))
+    return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
+
+
+def answer_batch_wire(servers, query_wires, want_packed: bool = False):
+    """answer_batch with the queries in their wire form (all of one size); every query is checked and decoded before the batch runs"""
+    servers, hs = _lane_handles(servers, "answer_batch_wire")
+    ws = [wire_bytes(w) for w in query_wires]
+    if len(ws) != len(servers):
+        raise ValueError(f"answer_batch_wire: {len(ws)} queries for {len(servers)} servers")
+    if len({w.size for w in ws}) != 1:
+        raise ValueError("answer_batch_wire: the queries differ in size")
+    n = servers[0].out_n
+    resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
+    packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
+    arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
+    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+    us = (C.c_double * 8)()
+    check(lib().spiral_gpu_pack_server_answer_batch_wire(hs, len(servers), wp, ws[0].size, arr(resp), arr(packed), us))
     return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
 
 

@@ -6,11 +6,11 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, Params, Shape, check, lib, update_args
+from ._lib import U64P, Params, Shape, check, lib, update_args, wire_bytes
 
 N = 2048
 
-BUF_EXPANDED, BUF_CTS, BUF_GSW, BUF_ACC, BUF_RAW, BUF_FINAL, BUF_RESPONSE = range(7)
+BUF_EXPANDED, BUF_CTS, BUF_GSW, BUF_ACC, BUF_RAW, BUF_FINAL, BUF_RESPONSE, BUF_QUERY = range(8)
 DB_PACKED, DB_LIMBS = 0, 1  # spiral_gpu_db_format
 STAGE_NAMES = ["expansion_us", "conversion_us", "first_dim_us", "folding_us", "response_us", "sweep_kernel_us", "total_us", "scaltomat_us"]
 
@@ -175,6 +175,17 @@ class Server:
     def set_query(self, query):
         check(lib().spiral_gpu_server_set_query(self.h, _p(np.ascontiguousarray(query, dtype=np.uint64))))
 
+    def set_pub_params_wire(self, wire):
+        """the public parameters as one wire message (ops.raw_to_wire of W_exp_left, W_exp_right, W, V); decoded on the device"""
+        w = wire_bytes(wire)
+        check(lib().spiral_gpu_server_set_pub_params_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
+    def set_query_wire(self, wire):
+        """the query in its wire form (ops.raw_to_wire of the raw ciphertexts); decoded on the device into set_query's buffer.  A failure
+        leaves no query set"""
+        w = wire_bytes(wire)
+        check(lib().spiral_gpu_server_set_query_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
     # ---- stages ----
     def expand(self):
         check(lib().spiral_gpu_server_expand(self.h))
@@ -320,6 +331,7 @@ class Server:
             BUF_RAW: (s.num_per, 3, 2, N),
             BUF_FINAL: (3, 2, N),
             BUF_RESPONSE: (3, 2, N),
+            BUF_QUERY: (s.n_query_cts, 2, 2, N),
         }
         return out.reshape(shapes[which])
 
