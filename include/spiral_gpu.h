@@ -394,6 +394,31 @@ int spiral_gpu_server_set_sweep_stages(spiral_gpu_server *s, uint32_t n_stages);
 uint32_t spiral_gpu_server_max_sweep_stages(spiral_gpu_server *s);
 int spiral_gpu_server_first_dim_stage(spiral_gpu_server *s, uint32_t stage);
 int spiral_gpu_server_run_scal2mat(spiral_gpu_server *s);
+/* Batches of a sharded answer: the flow above (run_pre_sweep or run_expand_pack + run_unpack_convert_sweep, reduce-scatter, fold_local,
+ * all-gather, fold_root) for n <= 8 clients per step, ONE collective of each kind per batch.  servers: this rank's owner (created on its j-shard,
+ * set_fold_ranks(G), optionally set_expand_shard(rank, G)) and its lanes (create_lane), each with its own client's public parameters and query, the
+ * same fold ranks and expansion shard.  L = num_per / G, CT = 6 x 2048 words (one n1 x n2 ciphertext).  Device buffers:
+ *   acc            n x num_per x CT words, rank-major [rank g][lane b][k < L]: lane b's ciphertext ii = g + G k at (g n + b) L + k (packed words,
+ *                  fields < 2^28).  One reduce-scatter(SUM) of it hands rank g its chunk [lane][k < L] (n x L x CT words).
+ *   bits_out       [lane][gsw_bits_words()] (sharded expansion); one all-gather gives gathered_bits = [rank][lane][gsw_bits_words()].
+ *   chunk          rank g's reduce-scattered [lane][k < L] (lazy sums of G shards; read, never written).
+ *   out_cts        [lane][CT]: each lane's ciphertext after the first nu2 - log2 G rounds (raw words); one all-gather gives
+ *                  gathered_cts = [rank][lane][CT].
+ *   responses      optional [lane][CT]: the switched responses; wire: optional [lane][spiral_gpu_response_wire_bytes(p, 2)] bytes, their wire forms.
+ * run_pre_sweep_batch: every lane's expansion and conversion in one launch sequence (ScalToMat for this rank's j-range), then ONE pass over the shard
+ * for all n queries (matrix cores where the image has limb planes, else passes of two on the vector ALU) into acc.  With a sharded expansion it is
+ * run_expand_pack_batch, the all-gather, then run_unpack_convert_sweep_batch.  fold_local_batch lifts each lane's chunk and runs the first
+ * nu2 - log2 G rounds for all lanes; fold_root_batch (the root rank) the last log2 G rounds and the switch: afterwards every lane's own buffers
+ * (SPIRAL_GPU_BUF_FINAL, SPIRAL_GPU_BUF_RESPONSE, read_response_wire) hold exactly what its run_query on the unsharded database would have left.
+ * set_fold_ranks(1) is the root-fold form: acc is [lane][num_per], reduce(SUM) to the root, fold_local_batch there runs every round and
+ * fold_root_batch only the switch.  The library issues no collective.  Every argument and lane is checked before anything is launched (a failing
+ * call writes nothing); not during stream capture.  Runs on servers[0]'s stream, the other lanes' streams ordered around it by events; with
+ * use_graphs on servers[0] each call is captured once per (lanes, buffers, image form) and replayed (update_db_items keeps the capture). */
+int spiral_gpu_server_run_pre_sweep_batch(spiral_gpu_server *const *servers, uint32_t n, void *acc);
+int spiral_gpu_server_run_expand_pack_batch(spiral_gpu_server *const *servers, uint32_t n, void *bits_out);
+int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server *const *servers, uint32_t n, const void *gathered_bits, void *acc);
+int spiral_gpu_server_fold_local_batch(spiral_gpu_server *const *servers, uint32_t n, const void *chunk, void *out_cts);
+int spiral_gpu_server_fold_root_batch(spiral_gpu_server *const *servers, uint32_t n, const void *gathered_cts, void *responses, void *wire);
 /* make the sweep write into caller-owned device memory (e.g. a torch tensor) */
 int spiral_gpu_server_set_acc(spiral_gpu_server *s, void *device_ptr);
 

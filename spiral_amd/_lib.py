@@ -138,6 +138,11 @@ PROTOTYPES = {
     "spiral_gpu_server_gsw_bits_unpack": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_run_expand_pack": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_run_unpack_convert_sweep": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "spiral_gpu_server_run_pre_sweep_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p]),
+    "spiral_gpu_server_run_expand_pack_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p]),
+    "spiral_gpu_server_run_unpack_convert_sweep_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p]),
+    "spiral_gpu_server_fold_local_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p]),
+    "spiral_gpu_server_fold_root_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_run_scal2mat_sweep": (C.c_int, [C.c_void_p]),
     "spiral_gpu_server_run_unpack_gsw": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_set_sweep_stages": (C.c_int, [C.c_void_p, C.c_uint32]),

@@ -373,8 +373,10 @@ bool sweep_stages_ok(uint32_t num_per, uint32_t jm_total, uint32_t g_log, uint32
 // sweep_batch_ok (the packed layout with at least 64 output columns: every published geometry but the smallest streaming ones)
 constexpr uint32_t kSweepMaxBatch = 2;
 bool sweep_batch_ok(uint32_t num_per, uint32_t jm_total);
+// g_extra > 0: the rank-major accumulators of a batch of a sharded answer -- acc[b] is query b's first chunk of a caller's [rank][lane][k < num_per / G]
+// buffer, and rank g's chunk of it is g * g_extra ciphertexts further on than in the one-query layout (g_extra = (lanes - 1) * num_per / G)
 void launch_sweep_batch(const uint64_t* db, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
-                        hipStream_t s);
+                        hipStream_t s, uint32_t g_extra = 0);
 // the same on the matrix cores for n = 1 .. kMaxLanes queries per pass (sweep_mfma.hip): needs the "limb plane" image of the database, built
 // from the packed one by launch_db_limb_planes (as many words); where sweep_mfma_ok (>= 64 ciphertexts per slot, first dimension a power of two in
 // [64, 2048]).  Returns the launch's error (the > 64 KiB LDS opt-in is per device).  k_log: the accumulators' stage layout, as launch_sweep
@@ -383,8 +385,9 @@ bool sweep_mfma_ok(uint32_t num_per, uint32_t jm_total);
 // a few slots at a time through a staging buffer); launch_db_limb_unplanes is the inverse map (limb planes -> packed), bit-exact both ways
 void launch_db_limb_planes(const uint64_t* db_packed_img, uint64_t* db_limbs, uint32_t num_per, uint32_t jm_total, hipStream_t s, uint32_t nz = kN);
 void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, uint32_t num_per, uint32_t jm_total, hipStream_t s, uint32_t nz = kN);
+// g_extra: the rank-major batch layout, as launch_sweep_batch (k_log = 0 then)
 hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
-                             hipStream_t s, uint32_t k_log = 0);
+                             hipStream_t s, uint32_t k_log = 0, uint32_t g_extra = 0);
 // reference DB layout (src/spiral.cpp:1139-1153) -> device layout, for the j-range [j0, j0 + dim0_shard): db_ref holds the nz
 // consecutive z slabs z0 .. z0+nz-1, db_dev is the base of the shard's device database
 void launch_db_relayout(const uint64_t* db_ref, uint64_t* db_dev, uint32_t num_per, uint32_t dim0, uint32_t j0, uint32_t dim0_shard, uint32_t z0,
@@ -406,6 +409,10 @@ void launch_fill_db1_random(uint64_t* db_dev, uint32_t num_per, uint32_t dim0, u
 // its block of the all-gather buffer [rank][a < n_max][2 polynomials]; pack: cv -> this rank's block, unpack: all blocks -> cv
 void launch_gsw_bits_pack(const uint64_t* cv, uint64_t* block, uint32_t rank, uint32_t n_ranks, uint32_t n_bits, hipStream_t s);
 void launch_gsw_bits_unpack(uint64_t* cv, const uint64_t* gathered, uint32_t n_ranks, uint32_t n_bits, hipStream_t s);
+// the same for the query lanes of a batch (gridDim.z = lanes.n; cv per lane): pack writes lane q's block to block + q * words, unpack reads rank r's
+// block of lane q at gathered + (r * lanes.n + q) * words -- one all-gather of the [lane][words] blocks gives that [rank][lane][words] layout
+void launch_gsw_bits_pack_lanes(const uint64_t* cv, uint64_t* block, uint32_t rank, uint32_t n_ranks, uint32_t n_bits, const Lanes& lanes, hipStream_t s);
+void launch_gsw_bits_unpack_lanes(uint64_t* cv, const uint64_t* gathered, uint32_t n_ranks, uint32_t n_bits, const Lanes& lanes, hipStream_t s);
 
 // ---- SpiralPack (pack.hip; reference src/testing.cpp) -----------------------------------------------------------
 // device DB layout, 1 x 1 plaintexts.  Packed (dim0 % 16 == 0; as the base path's, common.h): a word is two 28-bit

@@ -1060,5 +1060,33 @@ void launch_gsw_bits_unpack(uint64_t* cv, const uint64_t* gathered, uint32_t n_r
     const uint32_t n_max = (n_bits + n_ranks - 1) / n_ranks;
     if (n_max) hipLaunchKernelGGL(gsw_bits_copy_kernel, dim3(kBpp, 2 * n_max * n_ranks), dim3(kTpb), 0, s, cv, const_cast<uint64_t*>(gathered), 0u, n_ranks, n_bits, n_max, 1);
 }
+// the lanes of a batch (kernels.h): query lane blockIdx.z's cv, its block at buf + q * words (pack: [lane][words]) or its rank r block at
+// buf + (r * lanes + q) * words (unpack: the all-gathered [rank][lane][words])
+__global__ __launch_bounds__(kTpb) void gsw_bits_copy_lanes_kernel(uint64_t* cv, uint64_t* buf, uint32_t rank, uint32_t n_ranks, uint32_t n_bits, uint32_t n_max,
+                                                                   int unpack, Lanes lanes) {
+    const uint32_t z = blockIdx.x * kTpb + threadIdx.x, row = blockIdx.y & 1u, slot = blockIdx.y >> 1;  // slot = r * n_max + a (unpack) or a (pack)
+    const uint32_t r = unpack ? slot / n_max : rank, a = unpack ? slot - r * n_max : slot, i = a * n_ranks + r;
+    if (i >= n_bits) return;
+    lane_shift(cv, lanes.here());
+    const size_t words = (size_t)n_max * 2u * kN;
+    uint64_t* c = cv + ((size_t)(2u * i + 1u) * 2u + row) * kN + z;
+    uint64_t* b = buf + (unpack ? (size_t)r * lanes.n * words : 0) + (size_t)blockIdx.z * words + ((size_t)a * 2u + row) * kN + z;
+    if (unpack)
+        *c = *b;
+    else
+        *b = *c;
+}
+void launch_gsw_bits_pack_lanes(const uint64_t* cv, uint64_t* block, uint32_t rank, uint32_t n_ranks, uint32_t n_bits, const Lanes& lanes, hipStream_t s) {
+    const uint32_t n_max = (n_bits + n_ranks - 1) / n_ranks;
+    if (n_max)
+        hipLaunchKernelGGL(gsw_bits_copy_lanes_kernel, dim3(kBpp, 2 * n_max, lanes.n), dim3(kTpb), 0, s, const_cast<uint64_t*>(cv), block, rank, n_ranks, n_bits, n_max, 0,
+                           lanes);
+}
+void launch_gsw_bits_unpack_lanes(uint64_t* cv, const uint64_t* gathered, uint32_t n_ranks, uint32_t n_bits, const Lanes& lanes, hipStream_t s) {
+    const uint32_t n_max = (n_bits + n_ranks - 1) / n_ranks;
+    if (n_max)
+        hipLaunchKernelGGL(gsw_bits_copy_lanes_kernel, dim3(kBpp, 2 * n_max * n_ranks, lanes.n), dim3(kTpb), 0, s, cv, const_cast<uint64_t*>(gathered), 0u, n_ranks, n_bits,
+                           n_max, 1, lanes);
+}
 
 }  // namespace spiral

@@ -98,6 +98,10 @@ struct spiral_gpu_server {
     // run_query_batch_instances with this server as client 0: the same, for the client set, the instance images and the outputs
     hipGraphExec_t graph_binst = nullptr;
     std::vector<uint64_t> binst_key;
+    // the batch calls of a sharded answer (run_pre_sweep_batch ... fold_root_batch) with this server as servers[0]: one captured sequence per call and
+    // what it was captured for (the lanes, the caller's buffers, the image form)
+    hipGraphExec_t graph_shard[5] = {};
+    std::vector<uint64_t> shard_key[5];
     uint32_t batch_n = 0;
     // batched sweeps of sweep_mfma_min or more queries run on the matrix cores (sweep_mfma.hip) from a second image of the database, the "limb
     // planes": built from db on first use by the image's holder (the owner of a shared image), as large as db, dropped when db is reloaded.
@@ -195,6 +199,11 @@ void srv_drop_graphs(spiral_gpu_server* S) {
     if (S->graph_binst) (void)hipGraphExecDestroy(S->graph_binst);
     S->graph_binst = nullptr;
     S->binst_key.clear();
+    for (int k = 0; k < 5; k++) {
+        if (S->graph_shard[k]) (void)hipGraphExecDestroy(S->graph_shard[k]);
+        S->graph_shard[k] = nullptr;
+        S->shard_key[k].clear();
+    }
 }
 
 void srv_free(spiral_gpu_server* S, bool keep_db = false) {
@@ -2278,6 +2287,209 @@ int spiral_gpu_server_run_unpack_gsw(spiral_gpu_server* S, const void* gathered)
         if (spiral_gpu_server_gsw_bits_unpack(S, gathered)) return -1;
         return convert_gsw(S, S->stream);
     });
+}
+
+}  // extern "C"
+
+namespace {
+// ---- batches of a sharded answer (include/spiral_gpu.h: run_pre_sweep_batch ... fold_root_batch) ----------------------------------------------
+enum ShardCall : int { SH_PRE_SWEEP = 0, SH_EXPAND_PACK = 1, SH_UNPACK_SWEEP = 2, SH_FOLD_LOCAL = 3, SH_FOLD_ROOT = 4 };
+
+// Every check of a batch call of a sharded answer, before anything is launched: the lanes are an owner and its lanes (same parameters, device,
+// j-shard, image, fold ranks and expansion shard; the default schedule otherwise), none twice, no stream capturing.  check_lanes stays as it is:
+// run_query_batch keeps refusing every distributed setting.
+int check_shard_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, bool need_query, bool need_db, Lanes* lanes) {
+    if (!servers || n == 0) return fail("%s: no servers", what);
+    if (n > kMaxLanes) return fail("%s: at most %u clients per batch", what, kMaxLanes);
+    for (uint32_t b = 0; b < n; b++)
+        if (!servers[b]) return fail("%s: null server %u", what, b);
+    spiral_gpu_server* S = servers[0];
+    HIP_OK(hipSetDevice(S->device));
+    lanes->n = n;
+    for (uint32_t b = 0; b < n; b++) {
+        spiral_gpu_server* L = servers[b];
+        if ((need_query && !L->have_query) || !L->have_pp) return fail("%s: server %u needs its query and public parameters set first", what, b);
+        if (need_db && !L->have_db) return fail("%s: server %u has no database", what, b);
+        if (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->device != S->device || L->j0 != S->j0 || L->j1 != S->j1 || L->dim0_shard != S->dim0_shard ||
+            L->cv.words != S->cv.words)
+            return fail("%s: server %u differs from server 0 in parameters, device or j-shard", what, b);
+        if (L->db.p != S->db.p) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
+        if (L->fold_g_log != S->fold_g_log) return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
+        if (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank)
+            return fail("%s: server %u has another expansion shard than server 0", what, b);
+        if (L->keep_cts || L->overlap || L->sweep_k_log || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain)
+            return fail("%s: server %u has keep_cts, a split or staged schedule or other fold options set", what, b);
+        for (uint32_t c = 0; c < b; c++)
+            if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_OK(hipStreamIsCapturing(L->stream, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
+        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
+    }
+    return 0;
+}
+
+// the graph key of a batch call: the lanes' arenas, the caller's buffers and the image the sweep reads
+std::vector<uint64_t> shard_key(spiral_gpu_server* const* servers, uint32_t n, std::initializer_list<const void*> bufs, const uint64_t* limbs = nullptr) {
+    std::vector<uint64_t> key{n, (uint64_t)(uintptr_t)limbs};
+    for (uint32_t b = 0; b < n; b++) key.push_back((uint64_t)(uintptr_t)servers[b]->w_left.p);
+    for (const void* p : bufs) key.push_back((uint64_t)(uintptr_t)p);
+    return key;
+}
+
+// body() run directly, or captured once per key into servers[0]'s graph of this call and replayed; the lanes' streams are ordered around it
+template <class F>
+int run_shard(spiral_gpu_server* const* servers, uint32_t n, int call, std::vector<uint64_t> key, F body) {
+    spiral_gpu_server* S = servers[0];
+    if (lanes_join(servers, n)) return -1;
+    if (S->use_graphs) srv_check_epoch(S);  // (limb_image may just have changed the image's form)
+    const bool same = S->shard_key[call] == key;
+    if (int rc = run_keyed(S, &S->graph_shard[call], same, body)) return rc;
+    if (S->use_graphs) S->shard_key[call] = std::move(key);
+    return lanes_release(servers, n);
+}
+
+// The sweep of every lane's query over this rank's shard into the caller's rank-major buffer acc = [rank g][lane b][k < L], L = num_per / G: lane b's
+// ciphertext ii = g + G k at (g n + b) L + k.  One pass on the matrix cores where the image is in limb-plane form, else passes of two on the vector
+// ALU; a geometry neither kernel covers sweeps each query into its own accumulators and copies its G chunks into place (one strided copy).
+int sweep_rank_major(spiral_gpu_server* S, const Lanes& lanes, const uint64_t* limbs, uint64_t* acc_out) {
+    const spiral_gpu_server* H = holder_of(S);
+    const uint32_t n = lanes.n, G = 1u << S->fold_g_log, L = S->s.num_per >> S->fold_g_log, np = S->s.num_per, jm = 2 * S->dim0_shard;
+    const size_t chunk = (size_t)L * 6 * kN;
+    const uint32_t* qs[kMaxLanes];
+    uint64_t* acc[kMaxLanes];
+    uint64_t* own[kMaxLanes];
+    lane_records(S, lanes, qs, own);
+    for (uint32_t b = 0; b < n; b++) {
+        acc[b] = acc_out + b * chunk;
+        own[b] = S->acc_own.p + lanes.off[b];  // (scratch of the fallback: whatever set_acc says, the lane's own buffer)
+    }
+    if (n == 1 || G == 1)  // [lane][num_per] or one query's own layout: the grouping by ii mod G of the one-query sweep
+        return sweep_queries(H, limbs, qs, acc, n, S->fold_g_log, S->stream);
+    const uint32_t g_extra = (n - 1) * L;
+    if (!limbs && H->db_format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;
+    if (limbs) {
+        const hipError_t e = launch_sweep_mfma(limbs, qs, acc, n, np, jm, S->fold_g_log, S->stream, 0, g_extra);
+        return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
+    }
+    const uint32_t step = sweep_batch_ok(np, jm) ? kSweepMaxBatch : 1;
+    for (uint32_t b0 = 0; b0 < n; b0 += step) {
+        if (n - b0 >= 2 && step == 2) {
+            launch_sweep_batch(H->db.p, qs + b0, acc + b0, 2, np, jm, S->fold_g_log, S->stream, g_extra);
+            continue;
+        }
+        for (uint32_t b = b0; b < std::min(n, b0 + step); b++) {
+            launch_sweep(H->db.p, qs[b], own[b], np, jm, S->fold_g_log, S->stream);
+            HIP_OK(hipMemcpy2DAsync(acc[b], n * chunk * sizeof(uint64_t), own[b], chunk * sizeof(uint64_t), chunk * sizeof(uint64_t), G, hipMemcpyDeviceToDevice,
+                                    S->stream));
+        }
+    }
+    return 0;
+}
+
+void shard_mark_swept(spiral_gpu_server* const* servers, uint32_t n) {
+    for (uint32_t b = 0; b < n; b++) {
+        servers[b]->have_records = true;
+        servers[b]->raw_from_acc = false;
+    }
+}
+}  // namespace
+
+extern "C" {
+
+int spiral_gpu_server_run_pre_sweep_batch(spiral_gpu_server* const* servers, uint32_t n, void* acc) {
+    const char* what = "run_pre_sweep_batch";
+    Lanes lanes;
+    if (check_shard_lanes(servers, n, what, true, true, &lanes)) return -1;
+    if (!acc) return fail("%s: null accumulator buffer", what);
+    spiral_gpu_server* S = servers[0];
+    if (S->ex_shard.g_log) return fail("%s: the expansion is sharded: run_expand_pack_batch, the all-gather, then run_unpack_convert_sweep_batch", what);
+    int rc = 0;
+    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);  // (not inside a capture: it may convert the image)
+    if (rc) return rc;
+    rc = run_shard(servers, n, SH_PRE_SWEEP, shard_key(servers, n, {acc}, limbs), [&]() {
+        if (convert_lanes(S, lanes)) return -1;
+        return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
+    });
+    if (!rc) shard_mark_swept(servers, n);
+    return rc;
+}
+
+int spiral_gpu_server_run_expand_pack_batch(spiral_gpu_server* const* servers, uint32_t n, void* bits_out) {
+    const char* what = "run_expand_pack_batch";
+    Lanes lanes;
+    if (check_shard_lanes(servers, n, what, true, false, &lanes)) return -1;
+    if (!bits_out) return fail("%s: null output buffer", what);
+    spiral_gpu_server* S = servers[0];
+    return run_shard(servers, n, SH_EXPAND_PACK, shard_key(servers, n, {bits_out}), [&]() {
+        if (expand_lanes(S, lanes)) return -1;
+        launch_gsw_bits_pack_lanes(S->cv.p, (uint64_t*)bits_out, S->ex_shard.rank, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
+        return 0;
+    });
+}
+
+int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server* const* servers, uint32_t n, const void* gathered_bits, void* acc) {
+    const char* what = "run_unpack_convert_sweep_batch";
+    Lanes lanes;
+    if (check_shard_lanes(servers, n, what, true, true, &lanes)) return -1;
+    if (!gathered_bits || !acc) return fail("%s: null buffer", what);
+    spiral_gpu_server* S = servers[0];
+    int rc = 0;
+    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);
+    if (rc) return rc;
+    rc = run_shard(servers, n, SH_UNPACK_SWEEP, shard_key(servers, n, {gathered_bits, acc}, limbs), [&]() {
+        launch_gsw_bits_unpack_lanes(S->cv.p, (const uint64_t*)gathered_bits, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
+        if (convert_part(S, CONV_BOTH, S->stream, false, lanes)) return -1;
+        return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
+    });
+    if (!rc) shard_mark_swept(servers, n);
+    return rc;
+}
+
+// the caller's reduce-scattered chunk [lane][k < L] into each lane's own accumulators (the fold's first round reads them with the lanes' arena
+// offsets), the first nu2 - log2 G rounds for every lane in the same launches, each lane's folded ciphertext out to out_cts + b * 6 * 2048
+int spiral_gpu_server_fold_local_batch(spiral_gpu_server* const* servers, uint32_t n, const void* chunk, void* out_cts) {
+    const char* what = "fold_local_batch";
+    Lanes lanes;
+    if (check_shard_lanes(servers, n, what, false, false, &lanes)) return -1;
+    if (!chunk || !out_cts) return fail("%s: null buffer", what);
+    spiral_gpu_server* S = servers[0];
+    const uint32_t L = S->s.num_per >> S->fold_g_log;
+    const size_t ctw = 6 * kN, cw = (size_t)L * ctw;
+    const int rc = run_shard(servers, n, SH_FOLD_LOCAL, shard_key(servers, n, {chunk, out_cts}), [&]() {
+        for (uint32_t b = 0; b < n; b++)
+            HIP_OK(hipMemcpyAsync(S->acc_own.p + lanes.off[b], (const uint64_t*)chunk + b * cw, cw * sizeof(uint64_t), hipMemcpyDeviceToDevice, S->stream));
+        if (run_fold_rounds(S, L, 0, S->p.nu2 - S->fold_g_log, S->acc_own.p, true, false, nullptr, lanes)) return -1;
+        for (uint32_t b = 0; b < n; b++)
+            HIP_OK(hipMemcpyAsync((uint64_t*)out_cts + b * ctw, S->raw.p + lanes.off[b], ctw * sizeof(uint64_t), hipMemcpyDeviceToDevice, S->stream));
+        return 0;
+    });
+    for (uint32_t b = 0; !rc && b < n; b++) servers[b]->raw_from_acc = false;
+    return rc;
+}
+
+// the all-gathered [rank][lane][6 x 2048] into each lane's raw buffer (one strided copy per lane), the last log2 G rounds and the switch for every lane;
+// optionally the responses to responses + b * 6 * 2048 and the wire forms to wire + b * wire_bytes
+int spiral_gpu_server_fold_root_batch(spiral_gpu_server* const* servers, uint32_t n, const void* gathered_cts, void* responses, void* wire) {
+    const char* what = "fold_root_batch";
+    Lanes lanes;
+    if (check_shard_lanes(servers, n, what, false, false, &lanes)) return -1;
+    if (!gathered_cts) return fail("%s: null buffer", what);
+    spiral_gpu_server* S = servers[0];
+    const uint32_t G = 1u << S->fold_g_log;
+    const size_t ctw = 6 * kN, ww = wire_bytes(&S->p, 2) / 8;
+    const int rc = run_shard(servers, n, SH_FOLD_ROOT, shard_key(servers, n, {gathered_cts, responses, wire}), [&]() {
+        for (uint32_t b = 0; b < n; b++)
+            HIP_OK(hipMemcpy2DAsync(S->raw.p + lanes.off[b], ctw * sizeof(uint64_t), (const uint64_t*)gathered_cts + b * ctw, n * ctw * sizeof(uint64_t),
+                                    ctw * sizeof(uint64_t), G, hipMemcpyDeviceToDevice, S->stream));
+        if (run_fold_rounds(S, G, S->p.nu2 - S->fold_g_log, S->fold_g_log, nullptr, false, true, nullptr, lanes)) return -1;
+        if (responses)  // (the same switch again, into the caller's [lane] slots)
+            launch_rescale2(S->raw.p, (uint64_t*)responses, 2 * kN, 6 * kN, kQ, S->s.qprime, 4 * S->p.p_db, S->stream, lanes, (int64_t)ctw);
+        if (wire) launch_response_wire(S->resp.p, (uint64_t*)wire, 2 * kN, S->p.qprime_bits, 4 * kN, wire_bits_rest(&S->p), S->stream, lanes, 0, (int64_t)ww);
+        return 0;
+    });
+    for (uint32_t b = 0; !rc && b < n; b++) servers[b]->raw_from_acc = false;
+    return rc;
 }
 
 int spiral_gpu_server_run_post(spiral_gpu_server* S, int reduce_first) {

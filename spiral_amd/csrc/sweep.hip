@@ -112,9 +112,11 @@ struct SweepBatch {
     const uint32_t* qs[kSweepMaxBatch];
     uint64_t* acc[kSweepMaxBatch];
 };
-template <int MODE, int NB = 1, uint32_t Z = kSweepZ>
+// GS (batches of a sharded answer): the caller's accumulator buffer is rank-major over the whole batch, [rank g][lane][k < L]; acc points at this
+// query's first chunk and rank g's chunk of it lies g_extra = (lanes - 1) * L ciphertexts further on than in the one-query layout (ls_log = log2 L)
+template <int MODE, int NB = 1, uint32_t Z = kSweepZ, bool GS = false>
 __global__ __launch_bounds__(Z * 64) void sweep_kernel(const uint64_t* __restrict__ db, SweepBatch bt, uint32_t nic, uint32_t dim0, uint32_t g_log, uint32_t ls_log,
-                                                             uint32_t icb0, uint32_t n_icb) {
+                                                             uint32_t icb0, uint32_t n_icb, uint32_t g_extra) {
     static_assert(NB == 1 || MODE == 0, "batched sweeps use the wide geometry");
     const uint32_t* __restrict__ qs = bt.qs[0];
     uint64_t* __restrict__ acc = bt.acc[0];
@@ -222,7 +224,8 @@ __global__ __launch_bounds__(Z * 64) void sweep_kernel(const uint64_t* __restric
         for (uint32_t m = 0; m < 3; m++) {
             const uint32_t idx = threadIdx.x + Z * 64u * m, res = idx / Z, zz = idx - res * Z;
             const uint32_t col = res / 3u, r = res - col * 3u, ic = icb * 64u + col, i0 = ic >> 1, c = ic & 1u;
-            const uint32_t ii = acc_pos(i0, g_log, ls_log);
+            uint32_t ii = acc_pos(i0, g_log, ls_log);
+            if constexpr (GS) ii += (i0 & ((1u << g_log) - 1u)) * g_extra;
             acc[((size_t)(6u * ii + 2u * r + c)) * kN + zg * Z + zz] = sh[zz * kSweepRow + res];
         }
     } else if (threadIdx.x < 192u) {  // 64 lanes x 3 results of this tile, each the sum of the Z waves' partials (< 16 * 2^28)
@@ -234,7 +237,8 @@ __global__ __launch_bounds__(Z * 64) void sweep_kernel(const uint64_t* __restric
             sp += lo32(x);
             sb += hi32(x);
         }
-        const uint32_t ii = acc_pos(i0, g_log, ls_log);
+        uint32_t ii = acc_pos(i0, g_log, ls_log);
+        if constexpr (GS) ii += (i0 & ((1u << g_log) - 1u)) * g_extra;
         acc[((size_t)(6u * ii + 2u * r + c)) * kN + zg * pz + zz] = pack(mod_p(sp), mod_b(sb));
     }
     }  // batch
@@ -264,7 +268,7 @@ static uint32_t log2u(uint32_t x) {
 }
 bool sweep_batch_ok(uint32_t num_per, uint32_t jm_total) { return 2 * num_per >= 64 && db_packed(2 * num_per, jm_total / 2); }
 void launch_sweep_batch(const uint64_t* db, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
-                        hipStream_t s) {
+                        hipStream_t s, uint32_t g_extra) {
     const uint32_t nic = 2 * num_per, dim0 = jm_total / 2, ls_log = log2u(num_per) - g_log;
     SweepBatch bt{};
     for (uint32_t b = 0; b < n; b++) {
@@ -273,7 +277,12 @@ void launch_sweep_batch(const uint64_t* db, const uint32_t* const* qs, uint64_t*
     }
     const dim3 grid((kN / kSweepZ) * (nic >> 6)), block(kSweepZ * 64);
     switch (n) {
-        case 2: hipLaunchKernelGGL((sweep_kernel<0, 2>), grid, block, 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, nic >> 6); break;
+        case 2:
+            if (g_extra)
+                hipLaunchKernelGGL((sweep_kernel<0, 2, kSweepZ, true>), grid, block, 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, nic >> 6, g_extra);
+            else
+                hipLaunchKernelGGL((sweep_kernel<0, 2>), grid, block, 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, nic >> 6, 0u);
+            break;
         default: abort();
     }
 }
@@ -301,13 +310,13 @@ void launch_sweep(const uint64_t* db, const uint32_t* qs, uint64_t* acc, uint32_
             // 64 columns (nu2 = 5; one stage of a pipelined sweep) are only 128 workgroups of 16 slots, half the chip: 8 slots per workgroup there
             // (177 -> 146 us = 6.4 -> 7.8 TB/s at nu1 = 9, nu2 = 5; no difference from 128 columns up)
             if ((kN / kSweepZ) * n_icb < 256u)
-                hipLaunchKernelGGL((sweep_kernel<0, 1, 8>), dim3((kN / 8) * n_icb), dim3(8 * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, icb0, n_icb);
+                hipLaunchKernelGGL((sweep_kernel<0, 1, 8>), dim3((kN / 8) * n_icb), dim3(8 * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, icb0, n_icb, 0u);
             else
-                hipLaunchKernelGGL(sweep_kernel<0>, dim3((kN / kSweepZ) * n_icb), dim3(kSweepZ * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, icb0, n_icb);
+                hipLaunchKernelGGL(sweep_kernel<0>, dim3((kN / kSweepZ) * n_icb), dim3(kSweepZ * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, icb0, n_icb, 0u);
         } else if (nic >= 8 && stage_recs)  // one workgroup per tile of 64/nic <= 8 slots, its waves split the j range; records staged in LDS
-            hipLaunchKernelGGL(sweep_kernel<2>, dim3(kN / (64 / nic)), dim3(kSweepZ * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, 1u);
+            hipLaunchKernelGGL(sweep_kernel<2>, dim3(kN / (64 / nic)), dim3(kSweepZ * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, 1u, 0u);
         else
-            hipLaunchKernelGGL(sweep_kernel<1>, dim3(kN / (64 / nic)), dim3(kSweepZ * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, 1u);
+            hipLaunchKernelGGL(sweep_kernel<1>, dim3(kN / (64 / nic)), dim3(kSweepZ * 64), 0, s, db, bt, nic, dim0, g_log, ls_log, 0u, 1u, 0u);
     } else {
         const uint32_t threads = kN * nic;
         hipLaunchKernelGGL(sweep_small_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, db, qs, acc, nic, dim0, g_log, ls_log);

@@ -302,7 +302,9 @@ struct RecPlan {
 // The only conditional memory operations are the accumulator stores, once per 2^zs_log items.  (Two and four pieces per trip -- 14 and 28 KiB in
 // flight per wave -- measured 2 - 5 % slower than one: the registers are better spent elsewhere.)
 // dynamic LDS = 2 limb buffers x 2 NT KiB + 8 x NT x 64 x 2^zs_log result words.
-template <int NT, int ROWS>
+// GS (ROWS = 3, batches of a sharded answer): the accumulators are rank-major over the whole batch, [rank g][lane][k < L]; rank g's chunk of a
+// query lies tr.acc_stride = (lanes - 1) * L ciphertexts further on than in the one-query layout (sweep.hip sweep_kernel)
+template <int NT, int ROWS, bool GS = false>
 __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restrict__ dbl, SweepLanes bt, uint32_t nb, uint32_t nic, uint32_t dim0, uint32_t g_log,
                                                             uint32_t ls_log, uint32_t n_work, uint32_t zs_log, SweepTrials tr) {
     extern __shared__ __attribute__((aligned(16))) uint4 bq[];
@@ -420,7 +422,9 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
                     const uint32_t icb = (w >> kLogN) * W + wv;
                     for (uint32_t idx = lane; idx < (NT * 64u) << half_log; idx += 64u) {
                         const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;  // entry = (tile, source lane)
-                        const uint32_t ic = icb * 16u + (ls >> 4) * 4u + (ls & 3u), i0 = ic >> 1, c = ic & 1u, ii = acc_pos(i0, g_log, ls_log);
+                        const uint32_t ic = icb * 16u + (ls >> 4) * 4u + (ls & 3u), i0 = ic >> 1, c = ic & 1u;
+                        uint32_t ii = acc_pos(i0, g_log, ls_log);
+                        if constexpr (GS) ii += (i0 & ((1u << g_log) - 1u)) * (uint32_t)tr.acc_stride;
                         const uint32_t qr = t * 4u + ((ls & 15u) >> 2), q = qr / 3u, r = qr - q * 3u;
                         const uint4 v = reinterpret_cast<const uint4*>(st)[idx];
                         if (q < nb) *reinterpret_cast<uint4*>(pick_lane(bt.acc, q) + ((size_t)(6u * ii + 2u * r + c)) * kN + (z - zi) + 2u * part) = v;
@@ -459,7 +463,7 @@ void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, 
 namespace {
 
 // one launch of sweep_mfma_kernel<nt, ROWS> over n_work items (dim0: half the terms per column, as the kernel takes it)
-template <int ROWS>
+template <int ROWS, bool GS = false>
 hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint32_t nt, uint32_t nic, uint32_t dim0, uint32_t g_log, uint32_t ls_log, uint32_t n_work,
                        const SweepTrials& tr, hipStream_t s) {
     // one workgroup per CU (two per CU with half the staging measured 5 % slower); per = 8 nic / 128 items each (base path)
@@ -480,11 +484,11 @@ hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint3
         static std::atomic<uint64_t> big{0};                                                                                                       \
         const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;                                                                                        \
         if (!(big.load(std::memory_order_relaxed) & bit)) {                                                                                        \
-            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);            \
+            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
             if (e != hipSuccess) return e;                                                                                                         \
             big.fetch_or(bit, std::memory_order_relaxed);                                                                                          \
         }                                                                                                                                          \
-        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);         \
+        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
     } while (0)
     switch (nt) {
         case 1: SWEEP_MFMA(1); break;
@@ -511,12 +515,17 @@ SweepLanes sweep_lanes(const uint32_t* const* qs, uint64_t* const* acc, uint32_t
 }  // namespace
 
 hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
-                             hipStream_t s, uint32_t k_log) {
+                             hipStream_t s, uint32_t k_log, uint32_t g_extra) {
     const uint32_t nic = 2 * num_per, dim0 = jm_total / 2;
     uint32_t ls_log = 0;
     while ((1u << ls_log) < num_per) ls_log++;
     ls_log -= g_log + k_log;
     const uint32_t nt = (12u * n + 15u) / 16u;
+    if (g_extra) {  // (the rank-major batch layout: no stages)
+        SweepTrials tr{};
+        tr.acc_stride = g_extra;
+        return launch_mfma<3, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs, acc, n), n, nt, nic, dim0, g_log, ls_log, kN * (nic >> 7), tr, s);
+    }
     return launch_mfma<3>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs, acc, n), n, nt, nic, dim0, g_log, ls_log, kN * (nic >> 7), SweepTrials{}, s);
 }
 

@@ -138,3 +138,156 @@ def all_gather_gsw_bits(gathered, mine, group=None, async_op=False):
 def expand_shard_ok(shape, params, world: int) -> bool:
     """can the expansion be sharded over `world` ranks: query compression with the reordered layout, power-of-two ranks"""
     return world >= 1 and (world & (world - 1)) == 0 and not params.direct_upload and shape.stopround > 0 and world <= shape.dim0
+
+
+# ---- batches of a sharded answer (include/spiral_gpu.h run_pre_sweep_batch ... fold_root_batch) -------------------------------------------------
+CT_WORDS = 6 * 2048  # one n1 x n2 ciphertext: 96 KiB
+MAX_BATCH = 8        # clients per batch step (the query lanes of one launch)
+
+
+def _batch_n(n: int) -> int:
+    if not 1 <= n <= MAX_BATCH:
+        raise ValueError(f"a batch holds 1 .. {MAX_BATCH} clients, got {n}")
+    return n
+
+
+def batch_acc_words(shape, n: int) -> int:
+    """words of one rank's rank-major accumulator buffer [rank][lane][num_per / G][CT] (the reduce-scatter's input)"""
+    return _batch_n(n) * shape.num_per * CT_WORDS
+
+
+def batch_chunk_words(shape, n: int, G: int) -> int:
+    """words of rank g's reduce-scattered chunk [lane][num_per / G][CT] (fold_local_batch's input)"""
+    if G < 1 or shape.num_per % G:
+        raise ValueError(f"{G} fold ranks do not divide num_per = {shape.num_per}")
+    return _batch_n(n) * (shape.num_per // G) * CT_WORDS
+
+
+def batch_ct_words(n: int) -> int:
+    """words of fold_local_batch's output [lane][CT] (the all-gather's input; also the responses output)"""
+    return _batch_n(n) * CT_WORDS
+
+
+def batch_gathered_ct_words(n: int, G: int) -> int:
+    """words of the all-gathered [rank][lane][CT] (fold_root_batch's input)"""
+    return G * batch_ct_words(n)
+
+
+def batch_bits_words(gsw_bits_words: int, n: int) -> int:
+    """words of one rank's [lane][gsw_bits_words] block of a sharded expansion (the all-gather's input; x world = its output)"""
+    return _batch_n(n) * gsw_bits_words
+
+
+def batch_acc_position(ii: int, lane: int, n: int, G: int, num_per: int) -> int:
+    """where the batch sweep writes lane b's ciphertext ii = g + G k (in ciphertexts): (g n + b) L + k, L = num_per / G -- reduce-scattered, rank g
+    receives [lane][k]"""
+    L = num_per // G
+    g, k = ii % G, ii // G
+    return (g * n + lane) * L + k
+
+
+def batch_collective_bytes(shape, n: int, G: int, gsw_bits_words: int = 0) -> dict:
+    """bytes each collective of one batch step moves per rank, from the shapes alone (nothing timed): the accumulator reduce-scatter (its input; with
+    G = 1 the reduce to the root), the all-gather of the folded ciphertexts (its output) and, with a sharded expansion, the all-gather of the GSW bits
+    (its output)"""
+    out = {"reduce_scatter_in_bytes" if G > 1 else "reduce_in_bytes": batch_acc_words(shape, n) * 8}
+    if G > 1:
+        out["all_gather_cts_out_bytes"] = batch_gathered_ct_words(n, G) * 8
+    if gsw_bits_words:
+        out["all_gather_bits_out_bytes"] = G * batch_bits_words(gsw_bits_words, n) * 8
+    return out
+
+
+def batch_buffers(servers, world: int, fold_ranks: int, sharded_expansion: bool, device=None) -> dict:
+    """the device buffers of one rank's batch steps (int64 tensors, zeroed), sized for len(servers) clients.  Keep them across batches: the calls'
+    hipGraphs are keyed by these pointers"""
+    import torch
+
+    n, s = _batch_n(len(servers)), servers[0].shape
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    z = lambda words: torch.zeros(words, dtype=torch.int64, device=dev)
+    b = {"acc": z(batch_acc_words(s, n)), "cts": z(batch_ct_words(n)), "responses": z(batch_ct_words(n))}
+    if fold_ranks > 1:
+        b["chunk"] = z(batch_chunk_words(s, n, fold_ranks))
+        b["gathered_cts"] = z(batch_gathered_ct_words(n, fold_ranks))
+    if sharded_expansion:
+        w = servers[0].gsw_bits_words()
+        b["bits"] = z(batch_bits_words(w, n))
+        b["gathered_bits"] = z(world * batch_bits_words(w, n))
+    return b
+
+
+def reduce_scatter_batch(chunk, acc, group=None, async_op=False):
+    """the batch's one accumulator reduce-scatter: acc is rank-major [rank][lane][k], so rank g's contiguous slice is its [lane][k] chunk"""
+    return reduce_scatter_accumulators(chunk, acc, group=group, async_op=async_op)
+
+
+def all_gather_batch_cts(gathered, cts, group=None):
+    """the batch's one all-gather of the locally folded ciphertexts: [lane][CT] per rank -> [rank][lane][CT]"""
+    return all_gather_cts(gathered, cts, group=group)
+
+
+def all_gather_batch_bits(gathered, bits, group=None, async_op=False):
+    """the batch's one all-gather of the GSW bits of a sharded expansion: [lane][words] per rank -> [rank][lane][words]"""
+    return all_gather_gsw_bits(gathered, bits, group=group, async_op=async_op)
+
+
+def answer_batch_sharded(servers, group=None, bufs=None, *, fold_ranks=None, sharded_expansion=False, root=0, wire_ptr: int = 0):
+    """One rank's whole answer of a batch of up to eight clients on a j-sharded database, in order: pre + sweep (with a sharded expansion: expand + pack,
+    all-gather, unpack + convert + sweep), ONE reduce-scatter of the rank-major accumulators, fold_local_batch, ONE all-gather, fold_root_batch on
+    `root`.  fold_ranks = 1 (servers set up with set_fold_ranks(1)): a reduce(SUM) to the root, which folds alone.  servers: this rank's owner (created
+    on its j-shard, set_fold_ranks(G), with sharded_expansion also set_expand_shard(rank, world)) and its lanes, each with its client's public
+    parameters and query set.  bufs: batch_buffers(...) (allocated here when None; keep them across batches).  Returns bufs; on the root every lane's
+    BUF_FINAL / BUF_RESPONSE hold its answer and bufs["responses"] the [lane][CT] responses (wire_ptr: optional device [lane] wire forms)."""
+    import torch
+    import torch.distributed as dist
+
+    from . import server as SV
+
+    n = _batch_n(len(servers))
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    G = world if fold_ranks is None else fold_ranks
+    if G not in (1, world):
+        raise ValueError(f"fold ranks must be 1 or the world size {world}, got {G}")
+    if world > MAX_RANKS:
+        raise ValueError(f"world size {world} above the packed-sum carry bound {MAX_RANKS}")
+    if bufs is None:
+        bufs = batch_buffers(servers, world, G, sharded_expansion)
+    s = servers[0].shape
+    _check("answer_batch_sharded: acc", bufs["acc"], batch_acc_words(s, n))
+    _check("answer_batch_sharded: cts", bufs["cts"], batch_ct_words(n))
+    _check("answer_batch_sharded: responses", bufs["responses"], batch_ct_words(n))
+
+    def settle():  # the servers' stream -> the collective (on torch's stream) -> the servers' stream
+        servers[0].sync()
+
+    def landed():
+        torch.cuda.current_stream(bufs["acc"].device).synchronize()
+
+    if sharded_expansion:
+        SV.run_expand_pack_batch(servers, bufs["bits"].data_ptr())
+        settle()
+        all_gather_batch_bits(bufs["gathered_bits"], bufs["bits"], group=group)
+        landed()
+        SV.run_unpack_convert_sweep_batch(servers, bufs["gathered_bits"].data_ptr(), bufs["acc"].data_ptr())
+    else:
+        SV.run_pre_sweep_batch(servers, bufs["acc"].data_ptr())
+    settle()
+    if G == 1:
+        reduce_accumulators(bufs["acc"], dst=root, group=group)
+        landed()
+        if rank == root:
+            SV.fold_local_batch(servers, bufs["acc"].data_ptr(), bufs["cts"].data_ptr())
+            SV.fold_root_batch(servers, bufs["cts"].data_ptr(), bufs["responses"].data_ptr(), wire_ptr)
+            settle()
+        return bufs
+    reduce_scatter_batch(bufs["chunk"], bufs["acc"], group=group)
+    landed()
+    SV.fold_local_batch(servers, bufs["chunk"].data_ptr(), bufs["cts"].data_ptr())
+    settle()
+    all_gather_batch_cts(bufs["gathered_cts"], bufs["cts"], group=group)
+    landed()
+    if rank == root:
+        SV.fold_root_batch(servers, bufs["gathered_cts"].data_ptr(), bufs["responses"].data_ptr(), wire_ptr)
+        settle()
+    return bufs

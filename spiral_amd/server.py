@@ -40,6 +40,37 @@ def run_query_batch(servers):
     check(lib().spiral_gpu_server_run_query_batch(arr, len(servers)))
 
 
+def _lanes(servers):
+    return (C.c_void_p * len(servers))(*[s.h if s is not None else None for s in servers])
+
+
+def run_pre_sweep_batch(servers, acc_ptr: int):
+    """one rank's expansion, conversion and sweep for up to eight clients (an owner on its j-shard and its lanes) into the rank-major accumulator
+    buffer [rank][lane][num_per / G][6][2048]; see include/spiral_gpu.h"""
+    check(lib().spiral_gpu_server_run_pre_sweep_batch(_lanes(servers), len(servers), C.c_void_p(acc_ptr or None)))
+
+
+def run_expand_pack_batch(servers, bits_ptr: int):
+    """sharded expansion of every client's query and the pack of this rank's GSW bits into [lane][gsw_bits_words]"""
+    check(lib().spiral_gpu_server_run_expand_pack_batch(_lanes(servers), len(servers), C.c_void_p(bits_ptr or None)))
+
+
+def run_unpack_convert_sweep_batch(servers, gathered_bits_ptr: int, acc_ptr: int):
+    """unpack of the all-gathered [rank][lane][gsw_bits_words] blocks, conversion and the sweep into the rank-major accumulator buffer"""
+    check(lib().spiral_gpu_server_run_unpack_convert_sweep_batch(_lanes(servers), len(servers), C.c_void_p(gathered_bits_ptr or None), C.c_void_p(acc_ptr or None)))
+
+
+def fold_local_batch(servers, chunk_ptr: int, out_cts_ptr: int):
+    """every lane's reduce-scattered chunk ([lane][num_per / G] ciphertexts) through the local folding rounds -> [lane][6][2048] raw ciphertexts"""
+    check(lib().spiral_gpu_server_fold_local_batch(_lanes(servers), len(servers), C.c_void_p(chunk_ptr or None), C.c_void_p(out_cts_ptr or None)))
+
+
+def fold_root_batch(servers, gathered_cts_ptr: int, responses_ptr: int = 0, wire_ptr: int = 0):
+    """the root's last log2(G) rounds and the switch on the all-gathered [rank][lane][6][2048]; optional [lane] outputs of the responses and wire forms"""
+    check(lib().spiral_gpu_server_fold_root_batch(_lanes(servers), len(servers), C.c_void_p(gathered_cts_ptr or None), C.c_void_p(responses_ptr or None),
+                                                  C.c_void_p(wire_ptr or None)))
+
+
 def run_query_batch_instances(servers, instances, responses_ptr: int = 0, finals_ptr: int = 0, wire_ptr: int = 0, pre: bool = True):
     """item queries of up to eight clients (an owner and its lanes, each with its own query) against the same database instances: one sweep per instance
     for all of them; device outputs, client q and instance k at slot q * len(instances) + k: responses / finals 6 x 2048 words, wire
