@@ -75,6 +75,7 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *   "fwd2"            -1 (default) the two-digits-per-workgroup transform kernel from "fwd2_min" transforms per launch; 0 never; 1 always
  *   "fwd2_min"        that threshold (default 8192 transforms per launch, all query lanes together)
  *   "db_stage_bytes"  bytes of the staging buffer of load_db / load_db_items (default 64 MiB).  Initial value: SPIRAL_DB_STAGE_BYTES.
+ *   "pack_item_group" instances per group of spiral_gpu_pack_server_answer_batch_instances (default 0: automatic; g: at most g)
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  * These three environment variables are the only ones the library reads. */
 int spiral_gpu_set_option(const char *name, int64_t value);
@@ -561,6 +562,30 @@ int spiral_gpu_pack_server_answer_wire(spiral_gpu_pack_server *s, const void *qu
 int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server *const *servers, uint32_t n, const void *const *query_wires,
                                              size_t bytes_each, uint64_t *const *responses, uint64_t *const *packed_cts,
                                              double stage_us[8]);
+/* An item larger than one plaintext is factor = ceil(item size / plaintext size) database INSTANCES (select_params.py:297-298): n_instances pack
+ * servers, each holding all out_n^2 trial images of its own database.  n_clients <= 8 clients -- servers[q]: an owner and its lanes (create_lane), as in
+ * answer_batch, each with its own public parameters -- send one query each, and every client gets one packed response per instance: slot
+ * q * n_instances + k is what answer on a server sweeping instance k's images would return for client q's public parameters and query.  Per call: the
+ * expansion and conversion once per client (not per instance); per instance ONE first-dimension pass over its images for all clients (the
+ * matrix-core pass of answer_batch where the geometry has limb planes: with two or more clients each instance image is converted in place on first
+ * use); then per client and group of G instances ONE folding, packing, switch and wire-form sequence whose launches carry the whole group.  Option
+ * "pack_item_group" sets G (0: automatic -- the largest G whose arenas fit a quarter of the free device memory; an allocation that fails halves G,
+ * G = 1 uses only the clients' own buffers); the arenas stay on the client servers for the next call and go with destroy.  The clients' own image
+ * is read only where it is one of the instances (typically the owner is instance 0).
+ * Host buffers: queries[q] as answer's; responses: (out_n + 1) x out_n x 2048 words per slot (answer's layout); wire:
+ * spiral_gpu_response_wire_bytes(p, out_n) bytes per slot, contiguous; at least one of the two; total_us (may be NULL): device time of the call.
+ * Every argument is checked before anything is uploaded or launched (clients as answer_batch, less the owner's database; instances non-null, same
+ * parameters, out_n and device, all trials, a database loaded; the queries and their size; an output): a failing check writes no output.  The _wire
+ * form decodes every query first and runs only when all of them decoded cleanly.  Runs on servers[0]'s stream; the other clients' streams and every
+ * instance's (and its holder's) stream are ordered in front of it with events, and wait for it afterwards, so an update_db_items enqueued on an
+ * instance before the call is seen by it.  Returns synchronised.  n_clients = n_instances = 1 gives answer's words. */
+int spiral_gpu_pack_server_answer_batch_instances(spiral_gpu_pack_server *const *servers, uint32_t n_clients,
+                                                  spiral_gpu_pack_server *const *instances, uint32_t n_instances,
+                                                  const uint64_t *const *queries, uint64_t *responses, void *wire, double *total_us);
+int spiral_gpu_pack_server_answer_batch_instances_wire(spiral_gpu_pack_server *const *servers, uint32_t n_clients,
+                                                       spiral_gpu_pack_server *const *instances, uint32_t n_instances,
+                                                       const void *const *query_wires, size_t bytes_each, uint64_t *responses,
+                                                       void *wire, double *total_us);
 int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server *s, int format);
 int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server *s);
 uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server *s);

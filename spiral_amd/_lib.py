@@ -197,6 +197,8 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_set_pub_params_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "spiral_gpu_pack_server_answer_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_answer_batch_wire": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
+    "spiral_gpu_pack_server_answer_batch_instances": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(U64P), U64P, C.c_void_p, C.POINTER(C.c_double)]),
+    "spiral_gpu_pack_server_answer_batch_instances_wire": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, U64P, C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 

@@ -94,7 +94,8 @@ static void print_wire_bytes() {
     } while (0)
 
 // testHighRate (src/testing.cpp:777-1154): SpiralPack / SpiralStreamPack end to end, summary of :626-733
-static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_target, uint64_t seed, bool nonoise, bool show_diff, uint64_t qnum_first, uint32_t batch) {
+static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_target, uint64_t seed, bool nonoise, bool show_diff, uint64_t qnum_first, uint32_t batch,
+                         uint32_t instances) {
     cout << "Using n=" << out_n << endl;
     spiral_gpu_pack_shape s;
     GPU_OK(spiral_gpu_pack_get_shape(&p, out_n, &s));
@@ -134,8 +135,43 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     Poly pt = cl.decode(resp.data());
     const double time_decoding = (double)(now_us() - t0);
     Poly corr = pack_db_item(db_seed, idx_target, total_n, out_n, p.p_db);
-    const bool is_corr = pt == corr;
+    // ---- --instances F: the item at idx_target = plaintext idx_target of F databases (instance k seeded db_seed + k; instance 0 is the server above),
+    // the one query answered against all of them by ONE call of spiral_gpu_pack_server_answer_batch_instances (expansion and conversion once); every
+    // plaintext of the item is decoded from its wire form and checked
+    double item_us = 0;
+    std::vector<bool> item_ok;
+    if (instances >= 2 && instances <= 16) {
+        std::vector<spiral_gpu_pack_server*> inst{srv};
+        for (uint32_t k = 1; k < instances; k++) {
+            spiral_gpu_pack_server* sv = nullptr;
+            GPU_OK(spiral_gpu_pack_server_create(&p, out_n, 0, &sv));
+            GPU_OK(spiral_gpu_pack_server_gen_db(sv, db_seed + k));
+            inst.push_back(sv);
+        }
+        std::vector<uint8_t> wires((size_t)instances * wire.size());
+        const uint64_t* qp[1] = {query.data()};
+        for (int it = 0; it < 2; it++)  // a warm-up, the timed call
+            GPU_OK(spiral_gpu_pack_server_answer_batch_instances(&srv, 1, inst.data(), instances, qp, nullptr, wires.data(), &item_us));
+        Poly r((size_t)(out_n + 1) * out_n * N);
+        for (uint32_t k = 0; k < instances; k++) {
+            GPU_OK(spiral_gpu_response_from_wire(&p, out_n, wires.data() + (size_t)k * wire.size(), r.data()));
+            item_ok.push_back(cl.decode(r.data()) == pack_db_item(db_seed + k, idx_target, total_n, out_n, p.p_db));
+        }
+        for (uint32_t k = 1; k < instances; k++) spiral_gpu_pack_server_destroy(inst[k]);
+    } else if (instances) {
+        fprintf(stderr, "spiral: --instances takes 2 .. 16\n");
+        spiral_gpu_pack_server_destroy(srv);
+        return 1;
+    }
+    bool item_corr = true;
+    for (bool ok : item_ok) item_corr = item_corr && ok;
+    const bool is_corr = pt == corr && item_corr;
     cout << "Is correct? : " << (is_corr ? 1 : 0) << endl;
+    if (!item_ok.empty()) {
+        cout << "Item of " << instances << " plaintexts, Is correct?:";
+        for (bool ok : item_ok) cout << " " << (ok ? 1 : 0);
+        cout << endl;
+    }
     if (show_diff) {
         size_t shown = 0;
         for (size_t i = 0; i < pt.size() && shown < 10; i++)
@@ -184,6 +220,7 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     cout << "GPU extras" << endl << endl;
     cout << "      Sweep kernels alone (GPU·us): " << us[5] << "  (" << (double)out_n * out_n * spiral_gpu_pack_server_sweep_bytes(srv) / us[5] / 1e3 << " GB/s)" << endl;
     cout << "      Whole answer, device (GPU·us): " << us[6] << endl;
+    if (item_us > 0) cout << "   Item of " << instances << " plaintexts (one query, " << instances << " database instances), device (GPU·us): " << item_us << endl;
     // ---- --batch B: B more clients (own keys, own indices) answered by ONE spiral_gpu_pack_server_answer_batch call: the server and B - 1 lanes
     // (create_lane), one first-dimension pass over the trial images for all of them
     bool batch_corr = true;
@@ -323,7 +360,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: no ROCm device found; this build has no CPU path\n");
         return 1;
     }
-    if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch);
+    if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch, instances);
     spiral_gpu_shape s;
     GPU_OK(spiral_gpu_get_shape(&p, &s));
     cout << "dim0: " << s.dim0 << endl;

@@ -29,6 +29,7 @@ struct Options {
     uint32_t fold_blocks = 768, sweep_mfma_min = 2, fwd2_min = 8192;
     size_t db_stage_bytes = (size_t)64 << 20;
     int one_image = 1;  // a server that batches on the matrix cores keeps ONLY the limb-plane image of its database (server.cpp)
+    uint32_t pack_item_group = 0;  // pack answer_batch_instances: instances per group, 0 = automatic (pack_server.cpp)
 };
 Options& options();  // server.cpp; the three documented environment variables are read once, on first use
 
@@ -74,6 +75,16 @@ struct NoLanes {
 #ifdef __HIPCC__
     __device__ __forceinline__ int64_t here() const { return 0; }
     __device__ __forceinline__ int64_t at(int64_t) const { return 0; }
+#endif
+};
+// The n responses of one client's item group (pack_server.cpp answer_batch_instances): slot k = blockIdx.z, `stride` words after slot k - 1 in the
+// input, and in the output where the launch takes no stride of its own.  Only the switch and the wire form take it.
+struct Slots {
+    uint32_t n = 1;
+    int64_t stride = 0;
+#ifdef __HIPCC__
+    __device__ __forceinline__ int64_t here() const { return (int64_t)blockIdx.z * stride; }
+    __device__ __forceinline__ int64_t at(int64_t s) const { return (int64_t)blockIdx.z * s; }
 #endif
 };
 template <class P>
@@ -289,6 +300,11 @@ void launch_response_wire(const uint64_t* in, uint64_t* out, uint32_t n0, uint32
                           int64_t in_stride = 0, int64_t out_stride = 0);
 void launch_rescale2(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n, uint64_t inp_mod, uint64_t out_mod0, uint64_t out_mod1, hipStream_t s,
                      const Lanes& lanes = Lanes{}, int64_t out_stride = 0);
+// the same for slots.n responses, slot k at in / out + k * slots.stride words (wire: in + k * slots.stride, out + k * out_stride words)
+void launch_rescale2_slots(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n, uint64_t inp_mod, uint64_t out_mod0, uint64_t out_mod1, const Slots& slots,
+                           hipStream_t s);
+void launch_response_wire_slots(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, const Slots& slots, int64_t out_stride,
+                                hipStream_t s);
 
 // ---- expansion / conversion / fold specials ----------------------------------------------------------
 // the same for a whole round in one launch: active ct a < cnt_e even (W_left, t_e digits) else odd (W_right, t_o);
@@ -466,7 +482,10 @@ void launch_pack_gsw_from_upload(const uint64_t* query, uint64_t* gsw, uint32_t 
 // key[cur][r][0..2ell) = gadget - F, [2ell..4ell) = F with F = gsw[nu2-1-cur]   (:1027-1032, 611-618)
 void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2, hipStream_t s);
 // pack (:198-241): result[row][c] = sum_r sum_k W_r[row][k] * ginv[r*out_n+c][k] + (row >= 1 ? ct2[(row-1)*out_n+c] : 0)
-void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s);
+// n_inst > 1: n_inst such products in one launch (an item group of answer_batch_instances), instance k's ginv / ct2 / result k x (out_n^2 t_conv,
+// out_n^2, (out_n + 1) out_n) polynomials further on, the same v_w
+void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s,
+                     uint32_t n_inst = 1);
 // the first-dimension sweep of n = 1 .. kMaxLanes queries (records qs1[b] -> accumulators acc[b], launch_sweep1's layouts) on the matrix cores, in ONE
 // pass over `trials` trial images (db_stride / acc_stride u64 words apart) in limb-plane form (sweep_mfma.hip, ROWS = 2).  Coverage (sweep1_mfma_ok):
 // num_per >= 128 a power of two, dim0 a power of two in [128, 4096].  Bit-identical to sweep1_kernel per query.  Returns the launch's error.

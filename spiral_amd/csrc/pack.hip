@@ -249,9 +249,18 @@ void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint
     hipLaunchKernelGGL(pack_fold_key_kernel, dim3(kBpp, 4 * ell, nu2), dim3(kTpb), 0, s, gsw, key, ell, nu2);
 }
 
+// ITEMS: gridDim.z = the instances of one client's item group (answer_batch_instances), instance k's digits, ct2 and result k x their per-instance
+// size further on; the key matrices v_w are the client's, shared.  !ITEMS is the one-response launch.
+template <bool ITEMS>
 __global__ __launch_bounds__(kTpb) void pack_mac_kernel(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n,
                                                         uint32_t t_conv) {
     const uint32_t z = blockIdx.x * kTpb + threadIdx.x, rc = blockIdx.y, row = rc / out_n, c = rc - row * out_n, rows = out_n + 1;
+    if constexpr (ITEMS) {
+        const size_t k = blockIdx.z, trials = (size_t)out_n * out_n;
+        ginv += k * trials * t_conv * kN;
+        ct2 += k * trials * kN;
+        result += k * rows * out_n * kN;
+    }
     // the reference multiplies per r (t_conv <= 56 terms, one reduction, src/poly.cpp:62) and adds the out_n products mod m
     // (src/testing.cpp:225-238); a u64 holds 256 terms of < 2^56, so the sum over r is reduced whenever the next r's terms
     // would pass that (out_n * t_conv goes up to 16 * 56 = 896)
@@ -280,8 +289,12 @@ __global__ __launch_bounds__(kTpb) void pack_mac_kernel(const uint64_t* v_w, con
     }
     result[(size_t)rc * kN + z] = pack(rp, rb);
 }
-void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s) {
-    hipLaunchKernelGGL(pack_mac_kernel, dim3(kBpp, (out_n + 1) * out_n), dim3(kTpb), 0, s, v_w, ginv, ct2, result, out_n, t_conv);
+void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s,
+                     uint32_t n_inst) {
+    if (n_inst > 1)
+        hipLaunchKernelGGL(pack_mac_kernel<true>, dim3(kBpp, (out_n + 1) * out_n, n_inst), dim3(kTpb), 0, s, v_w, ginv, ct2, result, out_n, t_conv);
+    else
+        hipLaunchKernelGGL(pack_mac_kernel<false>, dim3(kBpp, (out_n + 1) * out_n), dim3(kTpb), 0, s, v_w, ginv, ct2, result, out_n, t_conv);
 }
 
 // ---- foldCiphertextsDim1 product (src/testing.cpp:596-624): out[b][r] = sum_m key[r][m] * d[b][m], r < 2, m < K = 4*ell.

@@ -22,7 +22,7 @@ struct spiral_gpu_pack_server {
     DevBuf db, w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
     DevBuf gs_raw, gs_chat, gs_tmp, gsw, key, qs1, acc, raw, fold_d, fold_c, fold_c2, pk_ginv, pk_ct2, pk_res, pk_raw, resp, stage, wire;
     WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
-    hipEvent_t ev[8] = {};
+    hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch / item call end, [8] ordering another call's stream in front of an item call
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
     // query lanes (create_lane): a lane has no image of its own and sweeps its owner's; the owner counts its lanes.  Destroying an owner that
     // still has lanes frees everything but the image and leaves a husk (zombie) that the last lane to go deletes.
@@ -31,6 +31,8 @@ struct spiral_gpu_pack_server {
     bool zombie = false;
     uint32_t db_format = SPIRAL_GPU_DB_PACKED;  // holder only: the form db is in now (pk_db_set_format)
     UpdateWork upd;                              // holder only: update_db_items' workspace
+    DevBuf item;            // answer_batch_instances as a client: the arena of its item groups of more than one instance, kept for the next call
+    uint32_t item_cap = 0;  // instances per group the arena holds
 };
 
 namespace {
@@ -67,9 +69,10 @@ void pk_free(spiral_gpu_pack_server* S, bool keep_db = false) {
     const DevBuf keep = S->db;
     DevBuf* all[] = {&S->db, &S->w_left, &S->w_right, &S->v, &S->v_w, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->gs_raw, &S->gs_chat, &S->gs_tmp,
                      &S->gsw, &S->key, &S->qs1, &S->acc, &S->raw, &S->fold_d, &S->fold_c, &S->fold_c2, &S->pk_ginv, &S->pk_ct2, &S->pk_res, &S->pk_raw, &S->resp,
-                     &S->stage, &S->wire};
+                     &S->stage, &S->wire, &S->item};
     if (keep_db) S->db = DevBuf{};
     for (DevBuf* b : all) b->release();
+    S->item_cap = 0;
     S->upd.release();
     S->wire_in.release();
     for (auto& e : S->ev)
@@ -120,9 +123,10 @@ int pk_alloc(spiral_gpu_pack_server* S) {
 int pk_upload_ref_ntt(spiral_gpu_pack_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) { return host::upload_ref_ntt(S->stage, S->stream, host, pk, npolys); }
 
 // pack (src/testing.cpp:198-241) on device buffers: raw cts at trial stride `ct_stride` polynomials
+// n_inst > 1: an item group, n_inst instances' trials one after another in raw_cts, ginv, ct2 and result (answer_batch_instances)
 void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_stride_cts, const uint64_t* v_w, uint64_t* ginv, uint64_t* ct2, uint64_t* result,
-              uint32_t out_n, uint32_t t_conv, hipStream_t st) {
-    const uint32_t trials = out_n * out_n;
+              uint32_t out_n, uint32_t t_conv, hipStream_t st, uint32_t n_inst = 1) {
+    const uint32_t trials = n_inst * out_n * out_n;
     FwdParams fp{};
     fp.src = raw_cts;
     fp.dst = ginv;
@@ -139,7 +143,7 @@ void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_strid
     fa.dst_map = identity_map();
     fa.n_digits = 1;
     launch_ntt_forward(tb, fa, LD_RAW, ST_PK, trials, st);
-    launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st);
+    launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st, n_inst);
 }
 
 // Converts the holder's trial images between the packed form (kernels.h; sweep1_kernel) and the limb planes (sweep_mfma.hip; the matrix-core
@@ -180,21 +184,58 @@ int pk_db_set_format(spiral_gpu_pack_server* H, uint32_t fmt, hipStream_t st) {
 // a loader is about to rewrite the whole image in packed form
 void pk_db_rewrite(spiral_gpu_pack_server* S) { S->db_format = SPIRAL_GPU_DB_PACKED; }
 
-// the first-dimension sweep of n servers' queries (their records and accumulators) over every trial image of servers[0]'s holder, on `st`: one pass on the
-// matrix cores when the image is in limb-plane form, else one sweep1 launch (all trials) per server
-int pk_sweep(spiral_gpu_pack_server* const* servers, uint32_t n, hipStream_t st) {
-    spiral_gpu_pack_server* H = pk_holder(servers[0]);
+// the first-dimension sweep of n servers' queries (their records) over every trial image of H into accs[b], on `st`: one pass on the matrix cores when
+// the image is in limb-plane form, else one sweep1 launch (all trials) per server
+int pk_sweep_into(const spiral_gpu_pack_server* H, spiral_gpu_pack_server* const* servers, uint64_t* const* accs, uint32_t n, hipStream_t st) {
     const spiral_gpu_pack_shape& s = H->s;
     const size_t acc_stride = (size_t)s.num_per * 2 * kN;
     if (H->db_format == SPIRAL_GPU_DB_LIMBS) {
         const uint32_t* qs[kMaxLanes];
         uint64_t* acc[kMaxLanes];
-        for (uint32_t b = 0; b < n; b++) qs[b] = (const uint32_t*)servers[b]->qs1.p, acc[b] = servers[b]->acc.p;
+        for (uint32_t b = 0; b < n; b++) qs[b] = (const uint32_t*)servers[b]->qs1.p, acc[b] = accs[b];
         const hipError_t e = launch_sweep1_mfma(H->db.p, qs, acc, n, s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
         return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
     }
-    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, (const uint32_t*)servers[b]->qs1.p, servers[b]->acc.p, s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
+    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, (const uint32_t*)servers[b]->qs1.p, accs[b], s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
     return 0;
+}
+// ... over servers[0]'s holder, into each server's own accumulators
+int pk_sweep(spiral_gpu_pack_server* const* servers, uint32_t n, hipStream_t st) {
+    uint64_t* acc[kMaxLanes];
+    for (uint32_t b = 0; b < n; b++) acc[b] = servers[b]->acc.p;
+    return pk_sweep_into(pk_holder(servers[0]), servers, acc, n, st);
+}
+
+// The buffers the folding, packing and switch of one client write: its own (one instance), or one group of G instances of answer_batch_instances
+// (instance j's part of each buffer j x its one-instance size further on: the folding and packing launches take the group as G * n^2 trials)
+struct PkBufs {
+    uint64_t *acc, *raw, *fold_d, *fold_c, *fold_c2, *ginv, *ct2, *res, *pk_raw, *resp, *wire;
+};
+constexpr int kPkBufs = 11;
+PkBufs pk_own_bufs(spiral_gpu_pack_server* S) {
+    return PkBufs{S->acc.p, S->raw.p, S->fold_d.p, S->fold_c.p, S->fold_c2.p, S->pk_ginv.p, S->pk_ct2.p, S->pk_res.p, S->pk_raw.p, S->resp.p, S->wire.p};
+}
+// one instance's words of each PkBufs buffer (pk_alloc's sizes; the wire form in whole words)
+void pk_inst_words(const spiral_gpu_pack_server* S, size_t w[kPkBufs]) {
+    const spiral_gpu_pack_shape& s = S->s;
+    const size_t half = s.num_per / 2, rows = S->out_n + 1, slot = rows * S->out_n * kN;
+    const size_t v[kPkBufs] = {(size_t)S->nt * s.num_per * 2 * kN, (size_t)S->nt * s.num_per * 2 * kN, (size_t)S->nt * half * 4 * s.ell * kN,
+                               (size_t)S->nt * half * 2 * kN, (size_t)S->nt * half * 2 * kN, (size_t)s.trials * S->p.t_conv * kN, (size_t)s.trials * kN,
+                               slot, slot, slot, (wire_bytes(&S->p, S->out_n) + 7) / 8};
+    for (int i = 0; i < kPkBufs; i++) w[i] = v[i];
+}
+// the arena of a group of g instances: carved from base into *b (b null: sizing only); returns its words
+size_t pk_group_carve(const spiral_gpu_pack_server* S, uint32_t g, uint64_t* base, PkBufs* b) {
+    PkBufs sizing;
+    if (!b) b = &sizing;
+    size_t w[kPkBufs], used = 0;
+    pk_inst_words(S, w);
+    uint64_t** dst[kPkBufs] = {&b->acc, &b->raw, &b->fold_d, &b->fold_c, &b->fold_c2, &b->ginv, &b->ct2, &b->res, &b->pk_raw, &b->resp, &b->wire};
+    for (int i = 0; i < kPkBufs; i++) {
+        *dst[i] = base ? base + used : nullptr;
+        used += ((size_t)g * w[i] + 31u) & ~(size_t)31u;  // 256-byte pieces
+    }
+    return used;
 }
 
 }  // namespace
@@ -535,50 +576,51 @@ static int pk_expand_convert(spiral_gpu_pack_server* S, const uint64_t* query, h
     return 0;
 }
 
-// piece 3 (piece 2 is pk_sweep: the first dimension for every trial, :1049-1051): one INTT + CRT lift (:1055-1057) and the folding, on `st`
-static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) {
+// piece 3 (piece 2 is pk_sweep: the first dimension for every trial, :1049-1051): one INTT + CRT lift (:1055-1057) and the folding, on `st`, of nt
+// trials in the buffers B (pk_fold: S's own trials in its own buffers)
+static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
-    const uint32_t ell = s.ell, nt = S->nt;
+    const uint32_t ell = s.ell;
     HIP_OK(hipEventRecord(S->ev[3], st));
     HIP_OK(hipEventRecord(S->ev[4], st));  // (the lift is chained into the first fold round's digit transforms)
     // ---- foldCiphertextsDim1 (:596-624), all trials batched: each round = fold_chain_kernel (lift of the previous
     // product or of the accumulators + unsigned digits + forward transforms) and one product; a last lift to raw
     uint32_t np = s.num_per;
-    const uint64_t* src = S->acc.p;
+    const uint64_t* src = B.acc;
     uint32_t src_stride = s.num_per;
     // Pair form (option fold_pair = 0 keeps the reference's two products): folding_neg = gadget - F (:1027-1032), so
     // F_neg G^-1(L) + F G^-1(H) = L + F (G^-1(H) - G^-1(L)) -- the unsigned digits always recompose their value -- i.e. per round one lift
     // of the 2 np ciphertexts, ell digit-difference transforms per polynomial pair (LD_PDIFF) and a product of K = 2 ell terms + L.
     const bool pair = options().fold_pair != 0;  // (read per call: tests switch it inside one process)
-    uint64_t* out = S->fold_c.p;
+    uint64_t* out = B.fold_c;
     for (uint32_t cur = 0; cur < p.nu2; cur++) {
         np /= 2;
-        if (src == out) out = out == S->fold_c.p ? S->fold_c2.p : S->fold_c.p;
+        if (src == out) out = out == B.fold_c ? B.fold_c2 : B.fold_c;
         if (pair) {
             InvParams ip{};
             ip.src = src;
-            ip.dst = S->raw.p;  // [t][2 np][2], compact
+            ip.dst = B.raw;  // [t][2 np][2], compact
             ip.src_map = IndexMap{4 * np, 2 * src_stride, 0};
             ip.dst_map = identity_map();
             launch_ntt_inverse(S->tb, ip, IST_CRT, nt * 4 * np, st);
             FwdParams fp{};
-            fp.src = S->raw.p;
-            fp.dst = S->fold_d.p;
+            fp.src = B.raw;
+            fp.dst = B.fold_d;
             fp.src_map = fp.dst_map = identity_map();
             fp.n_digits = ell;
             fp.bits = get_bits_per(ell);
             fp.fold_np = np;
             fp.lazy_out = lazy_ok(2 * ell + 1) ? 1 : 0;  // pack_fold_mac sums 2 ell products and the addend per accumulator
             launch_ntt_forward(S->tb, fp, LD_PDIFF, ST_PK, nt * np * 2 * ell, st);
-            launch_pack_fold_mac(S->key.p + ((size_t)cur * 2 * 4 * ell + 2 * ell) * kN, S->fold_d.p, out, 2 * ell, nt * np, st, 4 * ell, src, np, src_stride);
+            launch_pack_fold_mac(S->key.p + ((size_t)cur * 2 * 4 * ell + 2 * ell) * kN, B.fold_d, out, 2 * ell, nt * np, st, 4 * ell, src, np, src_stride);
             src = out;
             src_stride = np;
             continue;
         }
         FoldChainParams cp{};
         cp.src = src;
-        cp.dst = S->fold_d.p;
+        cp.dst = B.fold_d;
         cp.ell = ell;
         cp.bits = get_bits_per(ell);
         cp.fold_np = np;
@@ -589,14 +631,14 @@ static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) {
         while (dpb > 1 && n_src * ((ell + dpb - 1) / dpb) < 768u) dpb = (dpb + 1) / 2;
         cp.dpb = dpb;
         launch_fold_chain(S->tb, cp, n_src, st);
-        launch_pack_fold_mac(S->key.p + (size_t)cur * 2 * 4 * ell * kN, S->fold_d.p, out, 4 * ell, nt * np, st);
+        launch_pack_fold_mac(S->key.p + (size_t)cur * 2 * 4 * ell * kN, B.fold_d, out, 4 * ell, nt * np, st);
         src = out;
         src_stride = np;
     }
     {
         InvParams ip{};
         ip.src = src;
-        ip.dst = S->raw.p;
+        ip.dst = B.raw;
         ip.src_map = p.nu2 ? identity_map() : IndexMap{2 * s.num_per, 2 * s.num_per, 0};
         ip.dst_map = IndexMap{2 * np, 2 * s.num_per, 0};  // the trial's surviving np cts at the head of its num_per slots
         launch_ntt_inverse(S->tb, ip, IST_CRT, nt * np * 2, st);
@@ -605,6 +647,8 @@ static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) {
     S->packed_after_front = false;
     return 0;
 }
+
+static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) { return pk_fold_into(S, pk_own_bufs(S), S->nt, st); }
 
 static int pk_front(spiral_gpu_pack_server* S, const uint64_t* query) {
     spiral_gpu_pack_server* one[1] = {S};
@@ -678,14 +722,14 @@ int spiral_gpu_pack_server_answer_wire(spiral_gpu_pack_server* S, const void* qu
 
 // the lanes of a batch: n in 1 .. kMaxLanes distinct servers that sweep the same images (an owner and its lanes), none trial-sharded, every one
 // with its public parameters (and, want_records, a converted query) -- checked before anything is launched
-static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bool want_records, const char* what) {
+static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bool want_records, const char* what, bool need_db = true) {
     if (!servers) return fail("%s: null argument", what);
     if (n == 0 || n > kMaxLanes) return fail("%s: %u servers, 1 .. %u per batch", what, n, kMaxLanes);
     for (uint32_t b = 0; b < n; b++)
         if (!servers[b] || servers[b]->zombie) return fail("%s: server %u is null or destroyed", what, b);
     spiral_gpu_pack_server* H = pk_holder(servers[0]);
     if (H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
-    if (!H->have_db) return fail("%s: no database loaded", what);
+    if (need_db && !H->have_db) return fail("%s: no database loaded", what);
     for (uint32_t b = 0; b < n; b++) {
         const spiral_gpu_pack_server* L = servers[b];
         for (uint32_t c = 0; c < b; c++)
@@ -774,6 +818,185 @@ static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, c
     stage_us[6] = total * 1e3;
     stage_us[7] = n;
     return 0;
+}
+
+// ---- items of several database instances (answer_batch_instances, include/spiral_gpu.h) ----
+// every argument check, before anything is uploaded or launched; what the clients' own image holds does not matter (it is read only as an instance)
+static int pk_check_items(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_pack_server* const* instances, uint32_t n_inst, const void* queries,
+                          const void* responses, const void* wire, const char* what) {
+    if (!servers || !instances || !queries) return fail("%s: null servers, instances or queries", what);
+    if (n == 0 || n > kMaxLanes) return fail("%s: %u clients, 1 .. %u per call", what, n, kMaxLanes);
+    if (n_inst == 0) return fail("%s: no instances", what);
+    if (!responses && !wire) return fail("%s: no output (responses or wire)", what);
+    if (pk_check_lanes(servers, n, false, what, false)) return -1;
+    const spiral_gpu_pack_server* S = servers[0];
+    for (uint32_t k = 0; k < n_inst; k++) {
+        const spiral_gpu_pack_server* I = instances[k];
+        if (!I || I->zombie) return fail("%s: instance %u is null or destroyed", what, k);
+        if (memcmp(&I->p, &S->p, sizeof(S->p)) != 0 || I->out_n != S->out_n || I->device != S->device)
+            return fail("%s: instance %u has other parameters, out_n or device than the clients", what, k);
+        if (I->nt != I->s.trials) return fail("%s: instance %u holds trials [%u, %u) only: trial-sharded servers are no instances", what, k, I->t0, I->t0 + I->nt);
+        if (!pk_holder(const_cast<spiral_gpu_pack_server*>(I))->have_db) return fail("%s: instance %u has no database loaded", what, k);
+    }
+    return 0;
+}
+
+// the group size: option pack_item_group (0 = automatic: the largest G <= n_inst whose arenas, on every client, fit a quarter of the device memory free
+// now, counting what the clients' arenas already hold), never more launch rows than the folding's product takes in one grid dimension; then the
+// arenas, halving G while an allocation fails.  G = 1 needs none: the clients' own buffers.
+static uint32_t pk_item_group(spiral_gpu_pack_server* const* servers, uint32_t n, uint32_t n_inst) {
+    const spiral_gpu_pack_server* S = servers[0];
+    const size_t per_group = (size_t)S->nt * (S->s.num_per / 2);  // the first fold round's ciphertexts per instance: grid rows of pack_fold_mac
+    uint32_t G = options().pack_item_group ? std::min(options().pack_item_group, n_inst) : n_inst;
+    G = (uint32_t)std::max<size_t>(1, std::min<size_t>(G, 65535 / std::max<size_t>(1, per_group)));
+    if (G > 1 && options().pack_item_group == 0) {
+        size_t free_b = 0, total_b = 0, held = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        (void)hipGetLastError();
+        for (uint32_t b = 0; b < n; b++) held += servers[b]->item.p ? servers[b]->item.words * 8 : 0;
+        const size_t budget = (free_b + held) / 4;
+        while (G > 1 && (size_t)n * pk_group_carve(S, G, nullptr, nullptr) * 8 > budget) G--;
+    }
+    for (; G > 1; G /= 2) {
+        bool ok = true;
+        for (uint32_t b = 0; b < n && ok; b++) {
+            spiral_gpu_pack_server* L = servers[b];
+            if (L->item_cap >= G) continue;
+            L->item.release();
+            L->item_cap = 0;
+            const size_t words = pk_group_carve(L, G, nullptr, nullptr);
+            if (hipMalloc(&L->item.p, words * 8) != hipSuccess) {
+                (void)hipGetLastError();  // (no sticky out-of-memory for the launches that follow)
+                L->item.p = nullptr;
+                ok = false;
+            } else {
+                L->item.words = words, L->item.carved = false, L->item_cap = G;
+            }
+        }
+        if (ok) return G;
+    }
+    return 1;
+}
+
+// the packing, switch and wire form of one client's group of g instances (folded in B): one launch sequence for all g
+static int pk_item_back(spiral_gpu_pack_server* L, const PkBufs& B, uint32_t g, bool want_wire, hipStream_t st) {
+    const spiral_gpu_params& p = L->p;
+    const uint32_t rows = L->out_n + 1;
+    const int64_t slot = (int64_t)rows * L->out_n * kN;
+    run_pack(L->tb, B.raw, L->s.num_per, L->v_w.p, B.ginv, B.ct2, B.res, L->out_n, p.t_conv, st, g);
+    InvParams ip{};
+    ip.src = B.res;
+    ip.dst = B.pk_raw;
+    ip.src_map = ip.dst_map = identity_map();
+    launch_ntt_inverse(L->tb, ip, IST_CRT, g * rows * L->out_n, st);
+    const Slots slots{g, slot};
+    launch_rescale2_slots(B.pk_raw, B.resp, L->out_n * kN, (uint32_t)slot, kQ, L->s.qprime, 4 * p.p_db, slots, st);
+    if (want_wire) {
+        size_t w[kPkBufs];
+        pk_inst_words(L, w);
+        launch_response_wire_slots(B.resp, B.wire, L->out_n * kN, p.qprime_bits, L->out_n * L->out_n * kN, wire_bits_rest(&p), slots, (int64_t)w[kPkBufs - 1], st);
+    }
+    L->packed_after_front = false;
+    return 0;
+}
+
+// the item call after its checks; queries null: every client's query was decoded into its buffer already
+static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_pack_server* const* instances, uint32_t n_inst,
+                           const uint64_t* const* queries, uint64_t* responses, void* wire, double* total_us) {
+    spiral_gpu_pack_server* S = servers[0];
+    HIP_OK(hipSetDevice(S->device));
+    hipStream_t st = S->stream;
+    // whatever the clients' and the instances' streams hold (an update_db_items on an instance's holder) comes first
+    auto join = [&](spiral_gpu_pack_server* X) -> int {
+        if (X->stream == st) return 0;
+        HIP_OK(hipEventRecord(X->ev[8], X->stream));
+        HIP_OK(hipStreamWaitEvent(st, X->ev[8], 0));
+        return 0;
+    };
+    for (uint32_t b = 1; b < n; b++)
+        if (join(servers[b])) return -1;
+    for (uint32_t k = 0; k < n_inst; k++)
+        if (join(instances[k]) || join(pk_holder(instances[k]))) return -1;
+    // a batch sweeps each instance image on the matrix cores where the geometry has limb planes: converted in place on first use, as answer_batch's holder
+    if (n >= 2 && sweep1_mfma_ok(S->s.num_per, S->s.dim0))
+        for (uint32_t k = 0; k < n_inst; k++) {
+            spiral_gpu_pack_server* H = pk_holder(instances[k]);
+            if (H->db_format != SPIRAL_GPU_DB_LIMBS && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, st)) return -1;
+        }
+    const uint32_t G = pk_item_group(servers, n, n_inst);
+    size_t w[kPkBufs];
+    pk_inst_words(S, w);
+    const size_t slot_words = w[kPkBufs - 2], wire_b = wire_bytes(&S->p, S->out_n);
+    PkBufs bufs[kMaxLanes];
+    for (uint32_t b = 0; b < n; b++) {
+        spiral_gpu_pack_server* L = servers[b];
+        if (G == 1) {
+            if (wire && L->wire.words * 8 < wire_b && (L->wire.release(), L->wire.alloc(wire_b / 8))) return -1;
+            bufs[b] = pk_own_bufs(L);
+        } else {
+            pk_group_carve(L, G, L->item.p, &bufs[b]);
+        }
+    }
+    for (uint32_t b = 0; b < n; b++)
+        if (pk_expand_convert(servers[b], queries ? queries[b] : nullptr, st)) return -1;  // once per client, whatever the number of instances
+    for (uint32_t k0 = 0; k0 < n_inst; k0 += G) {
+        const uint32_t g = std::min(G, n_inst - k0);
+        for (uint32_t j = 0; j < g; j++) {  // one first-dimension pass per instance for all clients, into instance j's part of each group arena
+            uint64_t* acc[kMaxLanes];
+            for (uint32_t b = 0; b < n; b++) acc[b] = bufs[b].acc + (size_t)j * w[0];
+            if (pk_sweep_into(pk_holder(instances[k0 + j]), servers, acc, n, st)) return -1;
+        }
+        for (uint32_t b = 0; b < n; b++) {  // folding, packing, switch and wire form: one sequence per client and group
+            spiral_gpu_pack_server* L = servers[b];
+            if (pk_fold_into(L, bufs[b], g * L->nt, st) || pk_item_back(L, bufs[b], g, wire != nullptr, st)) return -1;
+            const size_t first = (size_t)b * n_inst + k0;
+            if (responses) HIP_OK(hipMemcpyAsync(responses + first * slot_words, bufs[b].resp, g * slot_words * 8, hipMemcpyDeviceToHost, st));
+            if (wire) HIP_OK(hipMemcpyAsync((uint8_t*)wire + first * wire_b, bufs[b].wire, g * wire_b, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIP_OK(hipEventRecord(S->ev[7], st));
+    for (uint32_t b = 1; b < n; b++)  // and what follows on the other streams comes after
+        if (servers[b]->stream != st) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev[7], 0));
+    for (uint32_t k = 0; k < n_inst; k++) {
+        spiral_gpu_pack_server* I = instances[k];
+        if (I->stream != st) HIP_OK(hipStreamWaitEvent(I->stream, S->ev[7], 0));
+        if (pk_holder(I)->stream != st) HIP_OK(hipStreamWaitEvent(pk_holder(I)->stream, S->ev[7], 0));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    if (total_us) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, S->ev[0], S->ev[7]));
+        *total_us = ms * 1e3;
+    }
+    return 0;
+}
+
+int spiral_gpu_pack_server_answer_batch_instances(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
+                                                  uint32_t n_instances, const uint64_t* const* queries, uint64_t* responses, void* wire, double* total_us) {
+    const char* what = "answer_batch_instances";
+    if (pk_check_items(servers, n_clients, instances, n_instances, queries, responses, wire, what)) return -1;
+    for (uint32_t b = 0; b < n_clients; b++)
+        if (!queries[b]) return fail("%s: query %u is null", what, b);
+    return pk_answer_items(servers, n_clients, instances, n_instances, queries, responses, wire, total_us);
+}
+
+// from the queries' wire forms: every argument checked, then every query decoded; the call runs only when all of them decoded cleanly
+int spiral_gpu_pack_server_answer_batch_instances_wire(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
+                                                       uint32_t n_instances, const void* const* query_wires, size_t bytes_each, uint64_t* responses, void* wire,
+                                                       double* total_us) {
+    const char* what = "answer_batch_instances_wire";
+    if (pk_check_items(servers, n_clients, instances, n_instances, query_wires, responses, wire, what)) return -1;
+    const size_t want = (size_t)servers[0]->s.n_query_cts * 2 * kWirePolyBytes;
+    if (bytes_each != want) return fail("%s: %zu bytes per query, the wire form of a query takes %zu", what, bytes_each, want);
+    for (uint32_t b = 0; b < n_clients; b++)
+        if (!query_wires[b]) return fail("%s: query %u is null", what, b);
+    for (uint32_t b = 0; b < n_clients; b++) {
+        char w[64];
+        snprintf(w, sizeof(w), "%s: query %u", what, b);
+        if (pk_query_wire(servers[b], query_wires[b], bytes_each, w)) return -1;
+    }
+    return pk_answer_items(servers, n_clients, instances, n_instances, nullptr, responses, wire, total_us);
 }
 
 // the batched first-dimension sweep alone (answer_batch's), iters times on servers[0]'s stream with the lanes' current records, timed with device

@@ -392,6 +392,19 @@ void launch_rescale2(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n,
         hipLaunchKernelGGL(rescale2_kernel<NoLanes>, dim3((n + kTpb - 1) / kTpb, 1, 1), dim3(kTpb), 0, s, in, out, n0, n, inp_mod, out_mod0, out_mod1, NoLanes{},
                            (int64_t)0);
 }
+void launch_rescale2_slots(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t n, uint64_t inp_mod, uint64_t out_mod0, uint64_t out_mod1, const Slots& slots,
+                           hipStream_t s) {
+    if (n && slots.n)
+        hipLaunchKernelGGL(rescale2_kernel<Slots>, dim3((n + kTpb - 1) / kTpb, 1, slots.n), dim3(kTpb), 0, s, in, out, n0, n, inp_mod, out_mod0, out_mod1, slots,
+                           (int64_t)slots.stride);
+}
+void launch_response_wire_slots(const uint64_t* in, uint64_t* out, uint32_t n0, uint32_t w0, uint32_t n1, uint32_t w1, const Slots& slots, int64_t out_stride,
+                                hipStream_t s) {
+    const uint32_t words = n0 / 64u * w0 + n1 / 64u * w1;
+    if (slots.n)
+        hipLaunchKernelGGL(response_wire_kernel<Slots>, dim3((words + kTpb - 1) / kTpb, 1, slots.n), dim3(kTpb), 0, s, in, out, n0, w0, n1, w1, slots,
+                           (int64_t)slots.stride, out_stride);
+}
 void launch_rescale(const uint64_t* in, uint64_t* out, uint32_t n, uint64_t inp_mod, uint64_t out_mod, hipStream_t s) {
     if (n) hipLaunchKernelGGL(rescale_kernel, dim3((n + kTpb - 1) / kTpb), dim3(kTpb), 0, s, in, out, n, inp_mod, out_mod);
 }

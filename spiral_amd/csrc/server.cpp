@@ -418,6 +418,7 @@ int spiral_gpu_set_option(const char* name, int64_t value) {
     else if (n == "fwd2" && value >= -1 && value <= 1) o.fwd2 = (int)value;
     else if (n == "fwd2_min" && value >= 0) o.fwd2_min = (uint32_t)value;
     else if (n == "db_stage_bytes" && value > 0) o.db_stage_bytes = (size_t)value;
+    else if (n == "pack_item_group" && value >= 0 && value <= 0xFFFFFFFFll) o.pack_item_group = (uint32_t)value;
     else return fail("unknown option '%s' or value %lld out of range", name, (long long)value);
     return 0;
 }
@@ -433,6 +434,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "fwd2") *value = o.fwd2;
     else if (n == "fwd2_min") *value = o.fwd2_min;
     else if (n == "db_stage_bytes") *value = (int64_t)o.db_stage_bytes;
+    else if (n == "pack_item_group") *value = o.pack_item_group;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;

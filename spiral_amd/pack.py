@@ -228,3 +228,79 @@ def time_sweep_batch(servers, iters: int = 10) -> float:
     ms = C.c_float()
     check(lib().spiral_gpu_pack_server_time_sweep_batch(hs, len(servers), int(iters), C.byref(ms)))
     return float(ms.value)
+
+
+def _item_args(servers, instances, what: str):
+    """the clients' and the instances' handle arrays, checked in Python first (the library checks everything again)"""
+    servers, hs = _lane_handles(servers, what)
+    instances = list(instances)
+    if not instances:
+        raise ValueError(f"{what}: no instances")
+    if not all(isinstance(s, PackServer) for s in instances):
+        raise TypeError(f"{what}: every instance must be a PackServer")
+    if any(not getattr(s, "h", None) for s in instances):
+        raise ValueError(f"{what}: an instance is closed")
+    return servers, hs, instances, (C.c_void_p * len(instances))(*[s.h for s in instances])
+
+
+def _item_call(servers, instances, wire: bool, stats, call):
+    """the outputs of an item call, [B, F, out_n + 1, out_n, 2048] uint64 (and [B, F, wire bytes] uint8 with wire=True), filled by call(resp, wire)"""
+    s0 = servers[0]
+    n, B, F = s0.out_n, len(servers), len(instances)
+    resp = np.zeros((B, F, n + 1, n, N), dtype=np.uint64)
+    wb = lib().spiral_gpu_response_wire_bytes(C.byref(s0.params), n)
+    wires = np.zeros((B, F, wb), dtype=np.uint8) if wire else None
+    us = C.c_double()
+    call(_p(resp), wires.ctypes.data_as(C.c_void_p) if wire else None, C.byref(us))
+    if stats is not None:
+        stats["total_us"] = us.value
+    return (resp, wires) if wire else resp
+
+
+def answer_batch_instances(servers, instances, queries, wire: bool = False, stats: dict = None):
+    """B <= 8 clients (an owner and its lanes, each with its own public parameters) fetch an item of F = len(instances) plaintexts each: one query per
+    client, F instances (PackServers holding all trial images of their own database).  Returns [B, F, out_n + 1, out_n, 2048] uint64 responses -- slot
+    [q, k] equals client q's own answer against instance k -- and with wire=True also their wire forms [B, F, bytes] uint8.  stats (a dict, optional)
+    receives total_us, the device time of the call.  See include/spiral_gpu.h spiral_gpu_pack_server_answer_batch_instances."""
+    what = "answer_batch_instances"
+    servers, hs, instances, ins = _item_args(servers, instances, what)
+    queries = list(queries)
+    if len(queries) != len(servers):
+        raise ValueError(f"{what}: {len(queries)} queries for {len(servers)} clients")
+    words = servers[0].shape.n_query_cts * 2 * 2 * N  # ([ct][row] polynomials of the reference's NTT form, two words per coefficient)
+    for q in queries:
+        if not isinstance(q, np.ndarray) or q.dtype != np.uint64:
+            raise TypeError(f"{what}: a query is a uint64 array, not {getattr(q, 'dtype', type(q).__name__)}")
+        if q.size != words:
+            raise ValueError(f"{what}: a query of {q.size} words, this geometry's takes {words}")
+    qs = [_c(q) for q in queries]
+    qp = (U64P * len(qs))(*[_p(q) for q in qs])
+    return _item_call(servers, instances, wire, stats,
+                      lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances(hs, len(servers), ins, len(instances), qp, r, w, us)))
+
+
+def answer_batch_instances_wire(servers, instances, query_wires, wire: bool = False, stats: dict = None):
+    """answer_batch_instances with the queries in their wire form (each spiral_gpu_pack_query_wire_bytes long); every query is decoded before the call runs"""
+    what = "answer_batch_instances_wire"
+    servers, hs, instances, ins = _item_args(servers, instances, what)
+    ws = [wire_bytes(w) for w in query_wires]
+    if len(ws) != len(servers):
+        raise ValueError(f"{what}: {len(ws)} queries for {len(servers)} clients")
+    want = lib().spiral_gpu_pack_query_wire_bytes(C.byref(servers[0].params), servers[0].out_n)
+    if any(w.size != want for w in ws):
+        raise ValueError(f"{what}: the wire form of a query takes {want} bytes, got {[w.size for w in ws]}")
+    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+    return _item_call(servers, instances, wire, stats,
+                      lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances_wire(hs, len(servers), ins, len(instances), wp, want, r, w, us)))
+
+
+def answer_instances(server, instances, query, wire: bool = False, stats: dict = None):
+    """one client's item of F = len(instances) plaintexts: [F, out_n + 1, out_n, 2048] uint64 (and [F, bytes] uint8 with wire=True)"""
+    out = answer_batch_instances([server], instances, [query], wire, stats)
+    return (out[0][0], out[1][0]) if wire else out[0]
+
+
+def answer_instances_wire(server, instances, query_wire, wire: bool = False, stats: dict = None):
+    """answer_instances with the query in its wire form"""
+    out = answer_batch_instances_wire([server], instances, [query_wire], wire, stats)
+    return (out[0][0], out[1][0]) if wire else out[0]
