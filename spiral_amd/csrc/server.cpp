@@ -29,6 +29,38 @@ spiral::Options& spiral::options() {
 // =================================================================================================
 // resident server
 // =================================================================================================
+// The launch sequences a server captures into hipGraphs, one graph each, named after the entry point that runs it (the number is the
+// SPIRAL_GRAPH_DOT file's).  A batch or shard sequence is kept by the call's servers[0].
+enum GraphId : int {
+    G_PRE = 0,  // (split schedule: the even tree + ScalToMat on the main stream)
+    G_POST = 1,
+    G_POST_REDUCE = 2,
+    G_PRE_SIDE = 3,  // run_pre, split schedule: the odd tree + Regev->GSW on the side stream
+    G_QUERY = 4,
+    G_FOLD_LOCAL = 5,
+    G_FOLD_ROOT = 6,
+    G_PRE_SWEEP = 7,
+    G_EXPAND_PACK = 8,
+    G_UNPACK_CONVERT_SWEEP = 9,
+    G_SCAL2MAT_SWEEP = 10,
+    G_UNPACK_GSW = 11,
+    G_SCAL2MAT = 12,
+    G_BATCH,
+    G_INSTANCES,
+    G_BATCH_INSTANCES,
+    G_SHARD_PRE_SWEEP,  // run_pre_sweep_batch ... fold_root_batch
+    G_SHARD_EXPAND_PACK,
+    G_SHARD_UNPACK_SWEEP,
+    G_SHARD_FOLD_LOCAL,
+    G_SHARD_FOLD_ROOT,
+    G_COUNT
+};
+// a captured sequence and the words it was captured for beyond the server's own state (the caller's buffers, the lanes, the images; run_graph)
+struct Captured {
+    hipGraphExec_t exec = nullptr;
+    std::vector<uint64_t> key;
+};
+
 struct spiral_gpu_server {
     spiral_gpu_params p;
     spiral_gpu_shape s;
@@ -59,13 +91,10 @@ struct spiral_gpu_server {
     WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
     uint64_t* acc = nullptr;
     hipEvent_t ev[8] = {};
-    // captured stage groups (hipGraph): [0] expand + convert, [1] lift + fold + finish, [2] the same with
-    // reduce_first; instantiated lazily, invalidated when a captured pointer or flag changes
+    // captured launch sequences (hipGraph), used while use_graphs is on: captured on first use, re-captured when their key changes, all dropped
+    // (srv_drop_graphs) when server state they bake in changes
     bool use_graphs = false;
-    // [3] = Regev->GSW conversion on the side stream, [4] = whole query, [5] = fold_local, [6] = fold_root, [7] = run_pre + sweep
-    hipGraphExec_t graph[13] = {};  // [12] = ScalToMat alone  // [8] = sharded expansion + pack, [9] = unpack + convert + sweep, [10] = ScalToMat + sweep, [11] = unpack + Regev->GSW
-    const void *cap_chunk = nullptr, *cap_gathered = nullptr;
-    void* cap_ct = nullptr;  // the caller's buffers captured into graphs 5 and 6
+    Captured graphs[G_COUNT];
     // overlap 2 ("split"): the whole GSW side of the query -- the odd-index tree of the expansion AND the Regev->GSW conversion -- runs as its
     // own launch sequence on side_stream, beside the even tree + ScalToMat + sweep on the main stream; only the folding needs it.
     // (Modes 1 and 3 -- only the conversion forked, under the sweep -- measured slower and were removed in round 5, HISTORY.md.)
@@ -86,23 +115,6 @@ struct spiral_gpu_server {
     uint32_t fold_g_log = 0;  // distributed fold over 2^fold_g_log ranks: the sweep groups its output by ii mod G
     uint32_t sweep_k_log = 0; // pipelined sweep in 2^sweep_k_log stages (set_sweep_stages): accumulators laid out [stage][rank][ct]
     ExpandShard ex_shard{};   // sharded expansion (set_expand_shard): what this rank expands itself
-    const void* cap_bits_out = nullptr;  // the caller's exchange buffers captured into graphs 8 and 9
-    const void* cap_bits_in = nullptr;
-    // run_query_batch with this server as lane 0: the captured launch sequence and the lane set it was captured for
-    hipGraphExec_t graph_batch = nullptr;
-    const uint64_t* batch_key[kMaxLanes] = {};  // the lanes' arenas: every pointer the capture holds is one of them plus a fixed offset
-    const uint64_t* batch_limbs = nullptr;      // the image the captured sweep reads (null: the packed one, vector-ALU passes)
-    // run_query_instances with this server as the query's server: the captured launch sequence and what it was captured for
-    hipGraphExec_t graph_inst = nullptr;
-    std::vector<uint64_t> inst_key;
-    // run_query_batch_instances with this server as client 0: the same, for the client set, the instance images and the outputs
-    hipGraphExec_t graph_binst = nullptr;
-    std::vector<uint64_t> binst_key;
-    // the batch calls of a sharded answer (run_pre_sweep_batch ... fold_root_batch) with this server as servers[0]: one captured sequence per call and
-    // what it was captured for (the lanes, the caller's buffers, the image form)
-    hipGraphExec_t graph_shard[5] = {};
-    std::vector<uint64_t> shard_key[5];
-    uint32_t batch_n = 0;
     // batched sweeps of sweep_mfma_min or more queries run on the matrix cores (sweep_mfma.hip) from a second image of the database, the "limb
     // planes": built from db on first use by the image's holder (the owner of a shared image), as large as db, dropped when db is reloaded.
     // SPIRAL_SWEEP_MFMA=n sets the threshold (0 = never: at most kSweepMaxBatch queries per pass, on the vector ALU)
@@ -185,24 +197,9 @@ int srv_alloc(spiral_gpu_server* S, const spiral_gpu_server* db_owner) {
 }
 
 void srv_drop_graphs(spiral_gpu_server* S) {
-    for (auto& g : S->graph)
-        if (g) {
-            (void)hipGraphExecDestroy(g);
-            g = nullptr;
-        }
-    if (S->graph_batch) (void)hipGraphExecDestroy(S->graph_batch);
-    S->graph_batch = nullptr;
-    S->batch_n = 0;
-    if (S->graph_inst) (void)hipGraphExecDestroy(S->graph_inst);
-    S->graph_inst = nullptr;
-    S->inst_key.clear();
-    if (S->graph_binst) (void)hipGraphExecDestroy(S->graph_binst);
-    S->graph_binst = nullptr;
-    S->binst_key.clear();
-    for (int k = 0; k < 5; k++) {
-        if (S->graph_shard[k]) (void)hipGraphExecDestroy(S->graph_shard[k]);
-        S->graph_shard[k] = nullptr;
-        S->shard_key[k].clear();
+    for (Captured& c : S->graphs) {
+        if (c.exec) (void)hipGraphExecDestroy(c.exec);
+        c = Captured{};
     }
 }
 
@@ -1313,7 +1310,7 @@ int convert_part(spiral_gpu_server* S, uint32_t what, hipStream_t st, bool mark_
     const spiral_gpu_shape& s = S->s;
     const uint32_t ps = S->pos_stride, ngs = p.nu2 * s.ell;
     if (ngs == 0) what &= ~CONV_GSW;
-    if (what & CONV_S2M) S->have_records = true;  // (a replayed graph sets it in run_group)
+    if (what & CONV_S2M) S->have_records = true;  // (eager runs; after a replayed graph the entry point that launched it sets it)
     const uint32_t n1 = (what & CONV_S2M) ? S->dim0_shard : 0, n2 = (what & CONV_GSW) ? 2 * ngs : 0;
     const IndexMap map1{1, 2 * ps, 2 * (S->j0 * ps + S->pos_first)};  // row 0 of ct pos(j0 + a)
     const IndexMap map2{2, 2 * ps, 2 * S->pos_rest};                   // rows 0, 1 of the nu2*ell GSW-bit cts
@@ -1715,35 +1712,57 @@ int spiral_gpu_server_set_acc(spiral_gpu_server* S, void* device_ptr) {
 }  // extern "C"
 
 namespace {
-// run `body` (kernel launches on S->stream) directly, or capture it once into a hipGraph and replay it
+// the key of a captured sequence: the words it bakes in that server state does not cover (a braced list is compared without allocating)
+struct GraphKey {
+    const uint64_t* p;
+    size_t n;
+    GraphKey(const uint64_t* p, size_t n) : p(p), n(n) {}
+    GraphKey(std::initializer_list<uint64_t> k) : GraphKey(k.begin(), k.size()) {}
+    GraphKey(const std::vector<uint64_t>& k) : GraphKey(k.data(), k.size()) {}
+};
+uint64_t word(const void* p) { return (uint64_t)(uintptr_t)p; }
+
+// run `body` (kernel launches on st) directly, or -- with use_graphs on -- replay S's graph `id`, captured from body() first when there is none or it
+// was captured for another key.  Host state the sequence changes is the caller's to set: a replay runs no host code.
 template <class F>
-int run_group(spiral_gpu_server* S, int slot, hipStream_t st, F body) {
+int run_graph(spiral_gpu_server* S, GraphId id, hipStream_t st, GraphKey key, F body) {
     if (!S->use_graphs) return body();
     srv_check_epoch(S);
-    if (!S->graph[slot]) {
+    Captured& c = S->graphs[id];
+    if (c.exec && !(c.key.size() == key.n && std::equal(key.p, key.p + key.n, c.key.begin()))) {
+        (void)hipGraphExecDestroy(c.exec);
+        c.exec = nullptr;
+    }
+    if (!c.exec) {
         if (st == nullptr) return fail("graph capture needs a non-default stream");
         HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = body();
+        const int rc = body();
         hipGraph_t g = nullptr;
         hipError_t e = hipStreamEndCapture(st, &g);
-        if (rc) {
+        if (rc || e != hipSuccess) {
             if (g) (void)hipGraphDestroy(g);
-            return rc;
+            return rc ? rc : fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
         }
-        if (e != hipSuccess) return fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        if (const char* dot = tuning_env("SPIRAL_GRAPH_DOT")) {  // debugging aid: <prefix>.<slot>.dot
-            const std::string path = std::string(dot) + "." + std::to_string(slot) + ".dot";
+        if (const char* dot = tuning_env("SPIRAL_GRAPH_DOT")) {  // debugging aid: <prefix>.<id>.dot
+            const std::string path = std::string(dot) + "." + std::to_string(id) + ".dot";
             (void)hipGraphDebugDotPrint(g, path.c_str(), 0);
         }
-        e = hipGraphInstantiate(&S->graph[slot], g, nullptr, nullptr, 0);
+        e = hipGraphInstantiate(&c.exec, g, nullptr, nullptr, 0);
         (void)hipGraphDestroy(g);
         if (e != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(e));
+        c.key.assign(key.p, key.p + key.n);
         g_captures++;
     }
-    HIP_OK(hipGraphLaunch(S->graph[slot], st));
-    if (slot == 0 || slot == 4 || slot == 7 || slot == 9 || slot == 10 || slot == 12) S->have_records = true;  // the groups that hold ScalToMat
-    if (slot == 4 || slot == 7 || slot == 9 || slot == 10) S->raw_from_acc = false;  // the groups that hold the sweep: a replay overwrites the accumulators (the eager calls clear it themselves)
+    HIP_OK(hipGraphLaunch(c.exec, st));
     return 0;
+}
+
+// what converting and sweeping the queries of servers[0 .. n) leaves: their records enqueued, their accumulators overwritten (S->raw no longer their lift)
+void mark_swept(spiral_gpu_server* const* servers, uint32_t n) {
+    for (uint32_t b = 0; b < n; b++) {
+        servers[b]->have_records = true;
+        servers[b]->raw_from_acc = false;
+    }
 }
 }  // namespace
 
@@ -1753,29 +1772,34 @@ int spiral_gpu_server_run_pre(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
-    if (!S->overlap) return run_group(S, 0, S->stream, [&]() { return expand_convert(S); });
     // split: [odd tree of the expansion + Regev->GSW + fold keys] on the side stream, [even tree + ScalToMat] on the main stream, forked
     // HERE (the side depends on the query only: it runs beside the even tree); the fold joins the side stream
-    if (srv_join_side(S)) return -1;
     const spiral_gpu_params& p = S->p;
-    HIP_OK(hipEventRecord(S->ev_fork, S->stream));  // the previous query's fold has read its keys; the new query is uploaded
-    HIP_OK(hipStreamWaitEvent(S->side_stream, S->ev_fork, 0));
     auto half = [&](uint32_t parity, hipStream_t st, uint64_t* raw, uint64_t* g) {
         ExpandWork wk{raw, g};
         run_expand(S->tb, S->cv.p, S->s.g, p.t_exp, S->w_left.p, p.t_exp_right, S->w_right.p, S->s.ell * p.nu2, S->s.stopround, wk, st, S->query.p, 0, 0xffffffffu,
                    ExpandShard{}, parity);
     };
-    if (run_group(S, 3, S->side_stream, [&]() {
-            half(2u, S->side_stream, S->ex_raw2.p, S->ex_g2.p);
-            return convert_gsw(S, S->side_stream);
+    if (S->overlap) {
+        if (srv_join_side(S)) return -1;
+        HIP_OK(hipEventRecord(S->ev_fork, S->stream));  // the previous query's fold has read its keys; the new query is uploaded
+        HIP_OK(hipStreamWaitEvent(S->side_stream, S->ev_fork, 0));
+        if (run_graph(S, G_PRE_SIDE, S->side_stream, {}, [&]() {
+                half(2u, S->side_stream, S->ex_raw2.p, S->ex_g2.p);
+                return convert_gsw(S, S->side_stream);
+            }))
+            return -1;
+        HIP_OK(hipEventRecord(S->ev_join, S->side_stream));
+        S->side_pending = true;
+    }
+    if (int rc = run_graph(S, G_PRE, S->stream, {}, [&]() {
+            if (!S->overlap) return expand_convert(S);
+            half(1u, S->stream, S->ex_raw.p, S->ex_g.p);
+            return convert_scal2mat(S, S->stream);
         }))
-        return -1;
-    HIP_OK(hipEventRecord(S->ev_join, S->side_stream));
-    S->side_pending = true;
-    return run_group(S, 0, S->stream, [&]() {
-        half(1u, S->stream, S->ex_raw.p, S->ex_g.p);
-        return convert_scal2mat(S, S->stream);
-    });
+        return rc;
+    S->have_records = true;
+    return 0;
 }
 
 int spiral_gpu_server_run_query(spiral_gpu_server* S) {
@@ -1789,11 +1813,14 @@ int spiral_gpu_server_run_query(spiral_gpu_server* S) {
         return spiral_gpu_server_run_post(S, 0);
     }
     if (srv_join_side(S)) return -1;
-    return run_group(S, 4, S->stream, [&]() {
-        if (expand_convert(S)) return -1;
-        if (spiral_gpu_server_first_dim(S)) return -1;
-        return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true);
-    });
+    if (int rc = run_graph(S, G_QUERY, S->stream, {}, [&]() {
+            if (expand_convert(S)) return -1;
+            if (spiral_gpu_server_first_dim(S)) return -1;
+            return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true);
+        }))
+        return rc;
+    mark_swept(&S, 1);
+    return 0;
 }
 
 }  // extern "C"
@@ -1926,31 +1953,6 @@ int item_rounds(spiral_gpu_server* S, const Lanes& lanes, spiral_gpu_server* con
     }
     return 0;
 }
-
-// body() run directly, or -- with use_graphs on S -- captured into *exec on S's stream when there is none or it was captured for another key (!same),
-// then replayed
-template <class F>
-int run_keyed(spiral_gpu_server* S, hipGraphExec_t* exec, bool same, F body) {
-    if (!S->use_graphs) return body();
-    if (!*exec || !same) {
-        if (*exec) (void)hipGraphExecDestroy(*exec);
-        *exec = nullptr;
-        HIP_OK(hipStreamBeginCapture(S->stream, hipStreamCaptureModeRelaxed));
-        const int rc = body();
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(S->stream, &g);
-        if (rc || e != hipSuccess) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc ? rc : fail("hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        }
-        const hipError_t e2 = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        if (e2 != hipSuccess) return fail("hipGraphInstantiate failed: %s", hipGetErrorString(e2));
-        g_captures++;
-    }
-    HIP_OK(hipGraphLaunch(*exec, S->stream));
-    return 0;
-}
 }  // namespace
 
 extern "C" {
@@ -1984,20 +1986,12 @@ int spiral_gpu_server_run_query_batch(spiral_gpu_server* const* servers, uint32_
         if (sweep_queries(holder_of(S), limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
         return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true, nullptr, lanes);
     };
-    if (S->use_graphs) srv_check_epoch(S);  // (limb_image above may just have changed the image's form)
-    // the capture bakes in the lanes' arenas, the image the sweep reads and its kernel (limbs or not)
-    bool same = S->batch_n == n && S->batch_limbs == limbs;
-    for (uint32_t b = 0; same && b < n; b++) same = S->batch_key[b] == servers[b]->w_left.p;
-    if (int rc = run_keyed(S, &S->graph_batch, same, body)) return rc;
-    if (S->use_graphs) {
-        S->batch_n = n;
-        S->batch_limbs = limbs;
-        for (uint32_t b = 0; b < n; b++) S->batch_key[b] = servers[b]->w_left.p;
-    }
-    for (uint32_t b = 0; b < n; b++) {
-        servers[b]->have_records = true;
-        servers[b]->raw_from_acc = false;
-    }
+    // the capture bakes in the lanes' arenas (every pointer it holds is one of them plus a fixed offset), the image the sweep reads and its kernel
+    // (limbs or not)
+    uint64_t key[2 + kMaxLanes] = {n, word(limbs)};
+    for (uint32_t b = 0; b < n; b++) key[2 + b] = word(servers[b]->w_left.p);
+    if (int rc = run_graph(S, G_BATCH, S->stream, GraphKey(key, 2 + n), body)) return rc;
+    mark_swept(servers, n);
     return lanes_release(servers, n);
 }
 
@@ -2027,9 +2021,7 @@ int spiral_gpu_server_run_query_instances(spiral_gpu_server* S, spiral_gpu_serve
         if (pre && expand_convert(S)) return -1;
         return item_rounds(S, Lanes{}, instances, nullptr, n, o);
     };
-    if (S->use_graphs) srv_check_epoch(S);
-    if (int rc = run_keyed(S, &S->graph_inst, S->inst_key == key, body)) return rc;
-    if (S->use_graphs) S->inst_key = key;
+    if (int rc = run_graph(S, G_INSTANCES, S->stream, key, body)) return rc;
     if (pre) S->have_records = true;
     S->raw_from_acc = false;
     return 0;
@@ -2126,9 +2118,7 @@ int spiral_gpu_server_run_query_batch_instances(spiral_gpu_server* const* server
         if (pre && convert_lanes(S, lanes)) return -1;
         return item_rounds(S, lanes, instances, limbs.data(), n_inst, o);
     };
-    if (S->use_graphs) srv_check_epoch(S);
-    if (int rc = run_keyed(S, &S->graph_binst, S->binst_key == key, body)) return rc;
-    if (S->use_graphs) S->binst_key = key;
+    if (int rc = run_graph(S, G_BATCH_INSTANCES, S->stream, key, body)) return rc;
     for (uint32_t b = 0; b < n; b++) {
         if (pre) servers[b]->have_records = true;
         servers[b]->raw_from_acc = false;
@@ -2167,24 +2157,21 @@ int spiral_gpu_server_answer_batch_instances(spiral_gpu_server* const* servers, 
     return 0;
 }
 
-// The two halves of a distributed fold.  With use_graphs on they replay as hipGraphs too; the buffers the caller hands
-// in are baked into the capture, so a graph is dropped when a different pointer arrives.
+// The two halves of a distributed fold.  With use_graphs on they replay as hipGraphs too, keyed on the buffers the caller hands in (the
+// capture bakes them in).
 int spiral_gpu_server_fold_local(spiral_gpu_server* S, const void* acc_chunk, void* out_ct) {
     if (!S || !acc_chunk || !out_ct) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     const uint32_t L = S->s.num_per >> S->fold_g_log;
     if (srv_join_side(S)) return -1;
-    if (S->graph[5] && (S->cap_chunk != acc_chunk || S->cap_ct != out_ct)) {
-        (void)hipGraphExecDestroy(S->graph[5]);
-        S->graph[5] = nullptr;
-    }
-    S->cap_chunk = acc_chunk;
-    S->cap_ct = out_ct;
-    return run_group(S, 5, S->stream, [&]() {
-        if (run_fold_rounds(S, L, 0, S->p.nu2 - S->fold_g_log, (const uint64_t*)acc_chunk, true)) return -1;
-        HIP_OK(hipMemcpyAsync(out_ct, S->raw.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
-        return 0;
-    });
+    if (int rc = run_graph(S, G_FOLD_LOCAL, S->stream, {word(acc_chunk), word(out_ct)}, [&]() {
+            if (run_fold_rounds(S, L, 0, S->p.nu2 - S->fold_g_log, (const uint64_t*)acc_chunk, true)) return -1;
+            HIP_OK(hipMemcpyAsync(out_ct, S->raw.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
+            return 0;
+        }))
+        return rc;
+    S->raw_from_acc = false;
+    return 0;
 }
 
 int spiral_gpu_server_fold_root(spiral_gpu_server* S, const void* gathered_cts) {
@@ -2192,15 +2179,13 @@ int spiral_gpu_server_fold_root(spiral_gpu_server* S, const void* gathered_cts) 
     HIP_OK(hipSetDevice(S->device));
     const uint32_t G = 1u << S->fold_g_log;
     if (srv_join_side(S)) return -1;
-    if (S->graph[6] && S->cap_gathered != gathered_cts) {
-        (void)hipGraphExecDestroy(S->graph[6]);
-        S->graph[6] = nullptr;
-    }
-    S->cap_gathered = gathered_cts;
-    return run_group(S, 6, S->stream, [&]() {
-        HIP_OK(hipMemcpyAsync(S->raw.p, gathered_cts, (size_t)G * 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
-        return run_fold_rounds(S, G, S->p.nu2 - S->fold_g_log, S->fold_g_log, nullptr, false, true);
-    });
+    if (int rc = run_graph(S, G_FOLD_ROOT, S->stream, {word(gathered_cts)}, [&]() {
+            HIP_OK(hipMemcpyAsync(S->raw.p, gathered_cts, (size_t)G * 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
+            return run_fold_rounds(S, G, S->p.nu2 - S->fold_g_log, S->fold_g_log, nullptr, false, true);
+        }))
+        return rc;
+    S->raw_from_acc = false;
+    return 0;
 }
 
 // run_pre + first_dim as one group: what a rank does before the collective
@@ -2213,10 +2198,13 @@ int spiral_gpu_server_run_pre_sweep(spiral_gpu_server* S) {
         if (spiral_gpu_server_run_pre(S)) return -1;
         return spiral_gpu_server_first_dim(S);
     }
-    return run_group(S, 7, S->stream, [&]() {
-        if (expand_convert(S)) return -1;
-        return spiral_gpu_server_first_dim(S);
-    });
+    if (int rc = run_graph(S, G_PRE_SWEEP, S->stream, {}, [&]() {
+            if (expand_convert(S)) return -1;
+            return spiral_gpu_server_first_dim(S);
+        }))
+        return rc;
+    mark_swept(&S, 1);
+    return 0;
 }
 
 // the two halves of everything before the accumulator reduce when the expansion is sharded: run_expand_pack = expand + pack of
@@ -2225,12 +2213,7 @@ int spiral_gpu_server_run_expand_pack(spiral_gpu_server* S, void* bits_out) {
     if (!S || !bits_out) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
-    if (S->graph[8] && S->cap_bits_out != bits_out) {
-        (void)hipGraphExecDestroy(S->graph[8]);
-        S->graph[8] = nullptr;
-    }
-    S->cap_bits_out = bits_out;
-    return run_group(S, 8, S->stream, [&]() {
+    return run_graph(S, G_EXPAND_PACK, S->stream, {word(bits_out)}, [&]() {
         if (spiral_gpu_server_expand(S)) return -1;
         return spiral_gpu_server_gsw_bits_pack(S, bits_out);
     });
@@ -2240,18 +2223,14 @@ int spiral_gpu_server_run_unpack_convert_sweep(spiral_gpu_server* S, const void*
     if (!S || !gathered) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_db) return fail("no database loaded");
-    if (S->cap_bits_in != gathered)
-        for (int g : {9, 11})
-            if (S->graph[g]) {
-                (void)hipGraphExecDestroy(S->graph[g]);
-                S->graph[g] = nullptr;
-            }
-    S->cap_bits_in = gathered;
-    return run_group(S, 9, S->stream, [&]() {
-        if (spiral_gpu_server_gsw_bits_unpack(S, gathered)) return -1;
-        if (spiral_gpu_server_convert(S)) return -1;
-        return spiral_gpu_server_first_dim(S);
-    });
+    if (int rc = run_graph(S, G_UNPACK_CONVERT_SWEEP, S->stream, {word(gathered)}, [&]() {
+            if (spiral_gpu_server_gsw_bits_unpack(S, gathered)) return -1;
+            if (spiral_gpu_server_convert(S)) return -1;
+            return spiral_gpu_server_first_dim(S);
+        }))
+        return rc;
+    mark_swept(&S, 1);
+    return 0;
 }
 
 // The same split so that the all-gather of the GSW bits can run UNDER the database-dependent work: the sweep needs only the
@@ -2262,30 +2241,28 @@ int spiral_gpu_server_run_scal2mat_sweep(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_db) return fail("no database loaded");
-    return run_group(S, 10, S->stream, [&]() {
-        if (convert_scal2mat(S, S->stream)) return -1;
-        return spiral_gpu_server_first_dim(S);
-    });
+    if (int rc = run_graph(S, G_SCAL2MAT_SWEEP, S->stream, {}, [&]() {
+            if (convert_scal2mat(S, S->stream)) return -1;
+            return spiral_gpu_server_first_dim(S);
+        }))
+        return rc;
+    mark_swept(&S, 1);
+    return 0;
 }
 
 // ScalToMat alone (the pipelined schedule issues the sweep stage by stage after it)
 int spiral_gpu_server_run_scal2mat(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
-    return run_group(S, 12, S->stream, [&]() { return convert_scal2mat(S, S->stream); });
+    if (int rc = run_graph(S, G_SCAL2MAT, S->stream, {}, [&]() { return convert_scal2mat(S, S->stream); })) return rc;
+    S->have_records = true;
+    return 0;
 }
 
 int spiral_gpu_server_run_unpack_gsw(spiral_gpu_server* S, const void* gathered) {
     if (!S || !gathered) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
-    if (S->cap_bits_in != gathered)
-        for (int g : {9, 11})
-            if (S->graph[g]) {
-                (void)hipGraphExecDestroy(S->graph[g]);
-                S->graph[g] = nullptr;
-            }
-    S->cap_bits_in = gathered;
-    return run_group(S, 11, S->stream, [&]() {
+    return run_graph(S, G_UNPACK_GSW, S->stream, {word(gathered)}, [&]() {
         if (spiral_gpu_server_gsw_bits_unpack(S, gathered)) return -1;
         return convert_gsw(S, S->stream);
     });
@@ -2295,8 +2272,6 @@ int spiral_gpu_server_run_unpack_gsw(spiral_gpu_server* S, const void* gathered)
 
 namespace {
 // ---- batches of a sharded answer (include/spiral_gpu.h: run_pre_sweep_batch ... fold_root_batch) ----------------------------------------------
-enum ShardCall : int { SH_PRE_SWEEP = 0, SH_EXPAND_PACK = 1, SH_UNPACK_SWEEP = 2, SH_FOLD_LOCAL = 3, SH_FOLD_ROOT = 4 };
-
 // Every check of a batch call of a sharded answer, before anything is launched: the lanes are an owner and its lanes (same parameters, device,
 // j-shard, image, fold ranks and expansion shard; the default schedule otherwise), none twice, no stream capturing.  check_lanes stays as it is:
 // run_query_batch keeps refusing every distributed setting.
@@ -2339,15 +2314,11 @@ std::vector<uint64_t> shard_key(spiral_gpu_server* const* servers, uint32_t n, s
     return key;
 }
 
-// body() run directly, or captured once per key into servers[0]'s graph of this call and replayed; the lanes' streams are ordered around it
+// body() as servers[0]'s graph `id` (run_graph), the lanes' streams ordered around it
 template <class F>
-int run_shard(spiral_gpu_server* const* servers, uint32_t n, int call, std::vector<uint64_t> key, F body) {
-    spiral_gpu_server* S = servers[0];
+int run_shard(spiral_gpu_server* const* servers, uint32_t n, GraphId id, const std::vector<uint64_t>& key, F body) {
     if (lanes_join(servers, n)) return -1;
-    if (S->use_graphs) srv_check_epoch(S);  // (limb_image may just have changed the image's form)
-    const bool same = S->shard_key[call] == key;
-    if (int rc = run_keyed(S, &S->graph_shard[call], same, body)) return rc;
-    if (S->use_graphs) S->shard_key[call] = std::move(key);
+    if (int rc = run_graph(servers[0], id, servers[0]->stream, key, body)) return rc;
     return lanes_release(servers, n);
 }
 
@@ -2388,13 +2359,6 @@ int sweep_rank_major(spiral_gpu_server* S, const Lanes& lanes, const uint64_t* l
     }
     return 0;
 }
-
-void shard_mark_swept(spiral_gpu_server* const* servers, uint32_t n) {
-    for (uint32_t b = 0; b < n; b++) {
-        servers[b]->have_records = true;
-        servers[b]->raw_from_acc = false;
-    }
-}
 }  // namespace
 
 extern "C" {
@@ -2409,11 +2373,11 @@ int spiral_gpu_server_run_pre_sweep_batch(spiral_gpu_server* const* servers, uin
     int rc = 0;
     const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);  // (not inside a capture: it may convert the image)
     if (rc) return rc;
-    rc = run_shard(servers, n, SH_PRE_SWEEP, shard_key(servers, n, {acc}, limbs), [&]() {
+    rc = run_shard(servers, n, G_SHARD_PRE_SWEEP, shard_key(servers, n, {acc}, limbs), [&]() {
         if (convert_lanes(S, lanes)) return -1;
         return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
     });
-    if (!rc) shard_mark_swept(servers, n);
+    if (!rc) mark_swept(servers, n);
     return rc;
 }
 
@@ -2423,7 +2387,7 @@ int spiral_gpu_server_run_expand_pack_batch(spiral_gpu_server* const* servers, u
     if (check_shard_lanes(servers, n, what, true, false, &lanes)) return -1;
     if (!bits_out) return fail("%s: null output buffer", what);
     spiral_gpu_server* S = servers[0];
-    return run_shard(servers, n, SH_EXPAND_PACK, shard_key(servers, n, {bits_out}), [&]() {
+    return run_shard(servers, n, G_SHARD_EXPAND_PACK, shard_key(servers, n, {bits_out}), [&]() {
         if (expand_lanes(S, lanes)) return -1;
         launch_gsw_bits_pack_lanes(S->cv.p, (uint64_t*)bits_out, S->ex_shard.rank, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
         return 0;
@@ -2439,12 +2403,12 @@ int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server* const* s
     int rc = 0;
     const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);
     if (rc) return rc;
-    rc = run_shard(servers, n, SH_UNPACK_SWEEP, shard_key(servers, n, {gathered_bits, acc}, limbs), [&]() {
+    rc = run_shard(servers, n, G_SHARD_UNPACK_SWEEP, shard_key(servers, n, {gathered_bits, acc}, limbs), [&]() {
         launch_gsw_bits_unpack_lanes(S->cv.p, (const uint64_t*)gathered_bits, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
         if (convert_part(S, CONV_BOTH, S->stream, false, lanes)) return -1;
         return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
     });
-    if (!rc) shard_mark_swept(servers, n);
+    if (!rc) mark_swept(servers, n);
     return rc;
 }
 
@@ -2458,7 +2422,7 @@ int spiral_gpu_server_fold_local_batch(spiral_gpu_server* const* servers, uint32
     spiral_gpu_server* S = servers[0];
     const uint32_t L = S->s.num_per >> S->fold_g_log;
     const size_t ctw = 6 * kN, cw = (size_t)L * ctw;
-    const int rc = run_shard(servers, n, SH_FOLD_LOCAL, shard_key(servers, n, {chunk, out_cts}), [&]() {
+    const int rc = run_shard(servers, n, G_SHARD_FOLD_LOCAL, shard_key(servers, n, {chunk, out_cts}), [&]() {
         for (uint32_t b = 0; b < n; b++)
             HIP_OK(hipMemcpyAsync(S->acc_own.p + lanes.off[b], (const uint64_t*)chunk + b * cw, cw * sizeof(uint64_t), hipMemcpyDeviceToDevice, S->stream));
         if (run_fold_rounds(S, L, 0, S->p.nu2 - S->fold_g_log, S->acc_own.p, true, false, nullptr, lanes)) return -1;
@@ -2480,7 +2444,7 @@ int spiral_gpu_server_fold_root_batch(spiral_gpu_server* const* servers, uint32_
     spiral_gpu_server* S = servers[0];
     const uint32_t G = 1u << S->fold_g_log;
     const size_t ctw = 6 * kN, ww = wire_bytes(&S->p, 2) / 8;
-    const int rc = run_shard(servers, n, SH_FOLD_ROOT, shard_key(servers, n, {gathered_cts, responses, wire}), [&]() {
+    const int rc = run_shard(servers, n, G_SHARD_FOLD_ROOT, shard_key(servers, n, {gathered_cts, responses, wire}), [&]() {
         for (uint32_t b = 0; b < n; b++)
             HIP_OK(hipMemcpy2DAsync(S->raw.p + lanes.off[b], ctw * sizeof(uint64_t), (const uint64_t*)gathered_cts + b * ctw, n * ctw * sizeof(uint64_t),
                                     ctw * sizeof(uint64_t), G, hipMemcpyDeviceToDevice, S->stream));
@@ -2498,9 +2462,12 @@ int spiral_gpu_server_run_post(spiral_gpu_server* S, int reduce_first) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
     if (srv_join_side(S)) return -1;
-    return run_group(S, reduce_first ? 2 : 1, S->stream, [&]() {
-        return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, reduce_first != 0, true);  // lift chained into round 0, switch into the last
-    });
+    if (int rc = run_graph(S, reduce_first ? G_POST_REDUCE : G_POST, S->stream, {}, [&]() {
+            return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, reduce_first != 0, true);  // lift chained into round 0, switch into the last
+        }))
+        return rc;
+    S->raw_from_acc = false;
+    return 0;
 }
 
 int spiral_gpu_server_answer_resident(spiral_gpu_server* S, double stage_us[8]) {

@@ -39,6 +39,15 @@ def assert_eq(got, exp, what):
         raise AssertionError(f"{what}: {len(bad)} of {got.size} words differ, first at {bad[:5].tolist()}: got {got[tuple(bad[0])]}, exp {exp[tuple(bad[0])]}")
 
 
+def captures(sa):
+    """hipGraphs captured so far by this process"""
+    import ctypes as C
+
+    v = C.c_int64()
+    assert sa.lib().spiral_gpu_get_option(b"graph_captures", C.byref(v)) == 0
+    return v.value
+
+
 # ---- L1 / L2 -----------------------------------------------------------------------------------------------
 def test_ntt_forward_inverse(sa, oracle):
     O = oracle
@@ -401,24 +410,67 @@ def test_graph_replay_matches_eager(sa, oracle, graphs, overlap):
     db = O.gen_db(po, 8)
     srv.use_graphs(graphs)
     srv.set_overlap(overlap)
-    for idx in (3, 100, 127, 3):
+    # the first query captures run_pre (its two halves with the split schedule) and run_post; everything after replays them
+    for k, idx in enumerate((3, 100, 127, 3)):
+        c0 = captures(sa)
         q = cl.query(idx)
         srv.set_query(q)
         srv.run_pre()
         srv.first_dim()
         srv.run_post()
         srv.sync()
+        assert captures(sa) - c0 == (0 if not graphs or k else (3 if overlap else 2)), f"captures of query {k}"
         assert_eq(srv.read(SV.BUF_FINAL), O.answer(po, q, wl, wr, w, v, db), f"graph replay idx={idx}")
         assert_eq(cl.decode(srv.read(SV.BUF_RESPONSE)), O.db_item(po, 8, idx), "decoded plaintext")
+    c0 = captures(sa)
     fin, resp, us = srv.answer(cl.query(5))  # answer() through the graphs too
+    assert captures(sa) == c0, "answer() captured again"
     assert_eq(cl.decode(resp), O.db_item(po, 8, 5), "decoded plaintext via answer()")
-    for idx in (9, 64):  # the whole query as one group
+    # the whole query as one group, captured once; the split schedule runs it as run_pre / first_dim / run_post, captured already
+    want = [0, 0, 3] if overlap else [1, 0, 1]
+    for k, idx in enumerate((9, 64, 77)):
+        if k == 2:
+            srv.gen_db(8)  # a reload: graphs captured over the old image do not replay
+        c0 = captures(sa)
         q = cl.query(idx)
         srv.set_query(q)
         srv.run_query()
         srv.sync()
+        assert captures(sa) - c0 == (want[k] if graphs else 0), f"captures of run_query {k}"
         assert_eq(srv.read(SV.BUF_FINAL), O.answer(po, q, wl, wr, w, v, db), f"run_query idx={idx}")
     srv.close()
+
+
+def test_replayed_run_post_leaves_the_fold_form(sa, oracle):
+    """lift -> run_post -> fold twice, graphs off and on (the second run_post replays its graph): the fold after run_post reads what run_post left in
+    the lifted-ciphertext buffer, not the lift of the accumulators, so it must not take the pair form with the accumulators as addend -- after a replay
+    no more than after an eager run"""
+    O = oracle
+    from spiral_amd import server as SV
+
+    kw = dict(t_gsw=4)  # (digits that recompose: the default pair-form fold applies)
+    po, pg = O.make_params(4, 3, **kw), sa.make_params(4, 3, **kw)
+    cl = O.Client(po, seed=23)
+    pp, q = cl.pub_params(), cl.query(42)
+    finals = {}
+    for graphs in (False, True):
+        srv = sa.Server(pg)
+        srv.gen_db(8)
+        srv.set_pub_params(*pp)
+        srv.use_graphs(graphs)
+        srv.set_query(q)
+        srv.run_pre()
+        srv.first_dim()
+        finals[graphs] = []
+        for _ in range(2):
+            srv.lift()
+            srv.run_post()
+            srv.fold()
+            srv.sync()
+            finals[graphs].append(srv.read(SV.BUF_FINAL))
+        srv.close()
+    for k in range(2):
+        assert_eq(finals[True][k], finals[False][k], f"fold after a {'replayed' if k else 'captured'} run_post")
 
 
 @pytest.mark.parametrize("kw", [dict(t_gsw=4), dict(t_gsw=4, qprime_bits=27, p_db=32768, direct_upload=1), dict(t_gsw=5, qprime_bits=36, p_db=8388592),
@@ -1235,7 +1287,13 @@ def test_distributed_fold_emulated_on_one_gpu(sa, oracle, G, graphs):
         srv.use_graphs(graphs)
         srvs.append(srv)
     gathered = torch.zeros(G * 6 * N, dtype=torch.int64, device=dev)
-    for idx in ((201, 7, 255) if graphs else (201,)):
+    # with graphs: the first round captures run_pre_sweep and fold_local on every rank and fold_root on rank 0, the next two replay them; the last
+    # gives rank 1 a new fold_local output buffer, which re-captures that one graph
+    want = [2 * G + 1, 0, 0, 1] if graphs else [0]
+    for rnd, idx in enumerate((201, 7, 255, 7) if graphs else (201,)):
+        c0 = captures(sa)
+        if rnd == 3:
+            cts[1] = torch.zeros(6 * N, dtype=torch.int64, device=dev)
         q = cl.query(idx)
         for g in range(G):
             srvs[g].set_query(q)
@@ -1255,6 +1313,7 @@ def test_distributed_fold_emulated_on_one_gpu(sa, oracle, G, graphs):
         torch.cuda.synchronize()
         srvs[0].fold_root(gathered.data_ptr())
         srvs[0].sync()
+        assert captures(sa) - c0 == want[rnd], f"captures of round {rnd}"
         assert_eq(srvs[0].read(SV.BUF_FINAL), O.answer(po, q, wl, wr, w, v, db), f"distributed fold G={G} idx={idx}")
         assert_eq(cl.decode(srvs[0].read(SV.BUF_RESPONSE)), O.db_item(po, 77, idx), "decoded plaintext")
     for srv in srvs:
@@ -1513,7 +1572,11 @@ def test_sharded_expansion_emulated_on_one_gpu(sa, oracle, nu1, nu2, kw, G, grap
         srvs.append(srv)
     gathered = torch.zeros(G * blocks[0].numel(), dtype=torch.int64, device=dev)
     total = s.dim0 * s.num_per
-    for idx in ((total - 1, 5, total // 2) if graphs else (total // 3,)):
+    # with graphs: the first round captures run_expand_pack and run_unpack_convert_sweep on every rank and run_post on rank 0; the later rounds replay the
+    # other ranks' graphs and re-capture rank 0's three, which set_acc below dropped
+    want = [2 * G + 1, 3, 3] if graphs else [0]
+    for rnd, idx in enumerate((total - 1, 5, total // 2) if graphs else (total // 3,)):
+        c0 = captures(sa)
         q = cl.query(idx)
         cts, gsw = O.stage_convert(po, O.stage_expand(po, q, wl, wr), w, v)
         for g in range(G):
@@ -1533,6 +1596,7 @@ def test_sharded_expansion_emulated_on_one_gpu(sa, oracle, nu1, nu2, kw, G, grap
         srvs[0].set_acc(tot.data_ptr())
         srvs[0].run_post(reduce_first=True)
         srvs[0].sync()
+        assert captures(sa) - c0 == want[rnd], f"captures of round {rnd}"
         assert_eq(srvs[0].read(SV.BUF_FINAL), O.answer(po, q, wl, wr, w, v, db), f"answer with sharded expansion, G={G} idx={idx}")
         assert_eq(cl.decode(srvs[0].read(SV.BUF_RESPONSE)), O.db_item(po, 19, idx), "decoded plaintext")
         srvs[0].set_acc(accs[0].data_ptr())
