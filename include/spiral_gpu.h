@@ -247,7 +247,7 @@ int spiral_gpu_server_set_query(spiral_gpu_server *s, const uint64_t *query);
  * coefficient a value in [0, Q] in 7 little-endian bytes (56 bits = logQ, the width the reference's summary counts, src/spiral.cpp:
  * 219-242): 14 336 bytes per polynomial instead of the NTT form's 32 768.  A query is its n_query_cts ciphertexts n0 x 1; public
  * parameters are ONE message holding the matrices of set_pub_params in its argument order (W_exp_left, W_exp_right, W, V; SpiralPack:
- * W_exp_left, W_exp_right, V, v_W) with the same shapes.  Nothing is seeded or compressed beyond this.
+ * W_exp_left, W_exp_right, V, v_W) with the same shapes.  The seeded form below also leaves out every matrix's random row 0.
  * *_wire_bytes: the size of such a message (0 for parameters that get_shape / pack_get_shape refuse).
  * raw_to_wire / raw_from_wire: the client's half, plain host code (no device): npolys raw polynomials <-> their wire form; raw_to_wire
  * refuses a value above Q and then writes nothing.
@@ -262,6 +262,28 @@ int spiral_gpu_raw_to_wire(const uint64_t *raw, size_t npolys, void *wire);
 int spiral_gpu_raw_from_wire(const void *wire, size_t npolys, uint64_t *raw);
 int spiral_gpu_server_set_query_wire(spiral_gpu_server *s, const void *wire, size_t bytes);
 int spiral_gpu_server_set_pub_params_wire(spiral_gpu_server *s, const void *wire, size_t bytes);
+
+/* Seeded form: the wire form with the uniformly random row 0 of every matrix replaced by one 32-byte seed.  A message is the seed followed by the
+ * wire form of the same matrices (same order and shapes as set_query_wire / set_pub_params_wire) with each matrix's row 0 left out: 32 + (wire
+ * polynomials - row-0 polynomials) x 14 336 bytes.  Row 0 is defined in NTT / CRT form: number a message's row-0 polynomials k = 0, 1, ... matrix by
+ * matrix, column by column (query ciphertext c: k = c); slot z of polynomial k is ChaCha20 (RFC 8439) with key = the seed, nonce = LE32(d) || LE64(k)
+ * and block counter z >> 1; of the block's words w[0..15] with h = z & 1, the residue mod p is the little-endian 128-bit w[8h..8h+3] mod p and the
+ * residue mod b is w[8h+4..8h+7] mod b.  Domain tags d: 1 base query, 2 base public parameters, 3 SpiralPack query, 4 SpiralPack public parameters.
+ * The client takes row 0 = seed_expand(...) and a = -row 0 for the rows it computes.
+ * A QUERY'S SEED MUST BE FRESH FOR EVERY QUERY: two queries under one seed and one key share row 0, and their rows 1.. then differ by the
+ * difference of the two messages (plus noise).  The server cannot check this.
+ * *_seeded_bytes: the size of such a message (0 for parameters that get_shape / pack_get_shape refuse).
+ * seed_expand: the client's half, plain host code (no device): row-0 polynomials first_k .. first_k + npolys - 1 of `domain`, reference NTT layout
+ * [k][prime][z].
+ * set_query_seeded / set_pub_params_seeded: the server's half.  Row 0 is generated on the device into the buffers set_query / set_pub_params fill,
+ * the other rows are decoded as set_query_wire does (so graphs captured before replay the new query without a re-capture).  A wrong byte count or a
+ * coefficient above Q (named by its index among the message's coefficients after the seed) fails and leaves NO query (resp. no public parameters).
+ * Not during stream capture. */
+size_t spiral_gpu_query_seeded_bytes(const spiral_gpu_params *p);
+size_t spiral_gpu_pub_params_seeded_bytes(const spiral_gpu_params *p);
+int spiral_gpu_seed_expand(const void *seed32, uint32_t domain, uint64_t first_k, size_t npolys, uint64_t *out);
+int spiral_gpu_server_set_query_seeded(spiral_gpu_server *s, const void *msg, size_t bytes);
+int spiral_gpu_server_set_pub_params_seeded(spiral_gpu_server *s, const void *msg, size_t bytes);
 
 /* stages, asynchronous on the server stream */
 int spiral_gpu_server_expand(spiral_gpu_server *s);    /* expandImproved + reorderFromStopround      */
@@ -586,6 +608,19 @@ int spiral_gpu_pack_server_answer_batch_instances_wire(spiral_gpu_pack_server *c
                                                        spiral_gpu_pack_server *const *instances, uint32_t n_instances,
                                                        const void *const *query_wires, size_t bytes_each, uint64_t *responses,
                                                        void *wire, double *total_us);
+/* SpiralPack from the seeded form (see spiral_gpu_query_seeded_bytes above): the sizes, the public parameters as one seeded message, and answer /
+ * answer_batch / answer_batch_instances with each query a seeded message of bytes_each bytes -- otherwise exactly their _wire forms. */
+size_t spiral_gpu_pack_query_seeded_bytes(const spiral_gpu_params *p, uint32_t out_n);
+size_t spiral_gpu_pack_pub_params_seeded_bytes(const spiral_gpu_params *p, uint32_t out_n);
+int spiral_gpu_pack_server_set_pub_params_seeded(spiral_gpu_pack_server *s, const void *msg, size_t bytes);
+int spiral_gpu_pack_server_answer_seeded(spiral_gpu_pack_server *s, const void *query_msg, size_t bytes, uint64_t *response, uint64_t *packed_ct,
+                                         double stage_us[8]);
+int spiral_gpu_pack_server_answer_batch_seeded(spiral_gpu_pack_server *const *servers, uint32_t n, const void *const *query_msgs, size_t bytes_each,
+                                               uint64_t *const *responses, uint64_t *const *packed_cts, double stage_us[8]);
+int spiral_gpu_pack_server_answer_batch_instances_seeded(spiral_gpu_pack_server *const *servers, uint32_t n_clients,
+                                                         spiral_gpu_pack_server *const *instances, uint32_t n_instances,
+                                                         const void *const *query_msgs, size_t bytes_each, uint64_t *responses, void *wire,
+                                                         double *total_us);
 int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server *s, int format);
 int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server *s);
 uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server *s);

@@ -199,6 +199,17 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_answer_batch_wire": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_answer_batch_instances": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(U64P), U64P, C.c_void_p, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_answer_batch_instances_wire": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, U64P, C.c_void_p, C.POINTER(C.c_double)]),
+    "spiral_gpu_query_seeded_bytes": (C.c_size_t, [C.POINTER(Params)]),
+    "spiral_gpu_pub_params_seeded_bytes": (C.c_size_t, [C.POINTER(Params)]),
+    "spiral_gpu_pack_query_seeded_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32]),
+    "spiral_gpu_pack_pub_params_seeded_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32]),
+    "spiral_gpu_seed_expand": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_size_t, U64P]),
+    "spiral_gpu_server_set_query_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_server_set_pub_params_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_pack_server_set_pub_params_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_pack_server_answer_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, U64P, U64P, C.POINTER(C.c_double)]),
+    "spiral_gpu_pack_server_answer_batch_seeded": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
+    "spiral_gpu_pack_server_answer_batch_instances_seeded": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, U64P, C.c_void_p, C.POINTER(C.c_double)]),
 }
 
 
@@ -243,6 +254,8 @@ def check(rc: int) -> None:
 
 
 WIRE_POLY_BYTES = 7 * 2048  # one polynomial of a query / public-parameter message in its wire form (include/spiral_gpu.h)
+SEED_BYTES = 32  # the seed that opens a message in its seeded form
+SEED_QUERY, SEED_PUB_PARAMS, SEED_PACK_QUERY, SEED_PACK_PUB_PARAMS = 1, 2, 3, 4  # the seeded form's domain tags
 
 
 def wire_bytes(wire) -> np.ndarray:

@@ -45,6 +45,14 @@ Poly invert(const Poly& raw) {  // Q - a (src/poly.cpp:269)
     for (size_t i = 0; i < raw.size(); i++) out[i] = Q - raw[i];
     return out;
 }
+Poly negate_ntt(const Poly& ntt) {  // -x residue by residue, reference NTT layout [poly][2][N]
+    Poly out(ntt.size());
+    for (size_t i = 0; i < ntt.size(); i++) {
+        const uint64_t m = (i / N) % 2 == 0 ? P : B;
+        out[i] = ntt[i] == 0 ? 0 : m - ntt[i];
+    }
+    return out;
+}
 uint32_t bits_per(uint32_t dim) { return dim == 56 ? 1u : 56u / dim + 1u; }  // include/util.h:34
 // buildGadget (src/util.cpp:89-106): raw rows x cols constant polynomials
 Poly build_gadget(size_t rows, size_t cols) {
@@ -76,6 +84,20 @@ uint64_t splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 }  // namespace
+
+void Row0::begin(std::mt19937_64& rng, uint32_t d) {
+    for (int i = 0; i < 4; i++) {
+        const uint64_t x = rng();
+        for (int b = 0; b < 8; b++) seed[8 * i + b] = (uint8_t)(x >> (8 * b));
+    }
+    on = true, domain = d, k = 0;
+}
+Poly Row0::take(size_t m) {
+    Poly out(m * 2 * N);
+    ok(spiral_gpu_seed_expand(seed, domain, k, m, out.data()), "seed_expand");
+    k += m;
+    return out;
+}
 
 Poly db_item(uint64_t seed, uint64_t item, uint64_t p_db) {
     Poly pt(4 * N);
@@ -116,9 +138,18 @@ void Client::keygen() {  // src/client.cpp:21-46
 }
 
 // getRegevSample x m (src/client.cpp:147-174): column i = ( -a_i ; a_i * s + e_i )
+// --seeded: -a is the next m row-0 polynomials of the message
 Poly Client::regev_samples(size_t m) {
-    Poly a = uniform_polys(m), e = noise_polys(m);
-    Poly a_ntt = to_ntt(a), e_ntt = to_ntt(e), s_ntt = to_ntt(sr), ainv_ntt = to_ntt(invert(a));
+    Poly a_ntt, ainv_ntt;
+    if (row0.on) {
+        ainv_ntt = row0.take(m);
+        a_ntt = negate_ntt(ainv_ntt);
+    } else {
+        Poly a = uniform_polys(m);
+        a_ntt = to_ntt(a), ainv_ntt = to_ntt(invert(a));
+    }
+    Poly e = noise_polys(m);
+    Poly e_ntt = to_ntt(e), s_ntt = to_ntt(sr);
     Poly b = add(mul_by_const(s_ntt, a_ntt), e_ntt);
     Poly out(2 * m * 2 * N);
     std::copy(ainv_ntt.begin(), ainv_ntt.end(), out.begin());
@@ -128,8 +159,16 @@ Poly Client::regev_samples(size_t m) {
 
 // to_ntt(get_fresh_public_key_raw(Sp, m)) (src/client.cpp:48-68): ( -A ; Sp*A + E ), n1 x m
 Poly Client::fresh_public_key(size_t m) {
-    Poly a = uniform_polys(m), e = noise_polys(2 * m);
-    Poly a_ntt = to_ntt(a), e_ntt = to_ntt(e), sp_ntt = to_ntt(sp), ainv_ntt = to_ntt(invert(a));
+    Poly a_ntt, ainv_ntt;
+    if (row0.on) {
+        ainv_ntt = row0.take(m);
+        a_ntt = negate_ntt(ainv_ntt);
+    } else {
+        Poly a = uniform_polys(m);
+        a_ntt = to_ntt(a), ainv_ntt = to_ntt(invert(a));
+    }
+    Poly e = noise_polys(2 * m);
+    Poly e_ntt = to_ntt(e), sp_ntt = to_ntt(sp);
     Poly bp = multiply(sp_ntt, a_ntt, 2, 1, m);
     Poly b = add(e_ntt, bp);
     Poly out(3 * m * 2 * N);
@@ -159,14 +198,20 @@ void Client::gen_pub_params() {
     const uint32_t tc = p.t_conv;
     offline_bytes = 0;
     auto account = [&](size_t rows, size_t cols, size_t count) { offline_bytes += (uint64_t)count * rows * cols * N * 56 / 8; };  // add_pub_param :199
+    // --seeded: row 0 in message order W_exp_left, W_exp_right, W, V
+    const uint64_t k_right = (uint64_t)s.n_left * p.t_exp, k_w = k_right + (uint64_t)s.n_right * p.t_exp_right;
+    if (seeded) row0.begin(rng, 2);
     if (s.n_right) {  // src/spiral.cpp:2091-2092
+        row0.k = k_right;
         w_right = public_encryptions(s.n_right, p.t_exp_right);
         account(2, p.t_exp_right, s.n_right);
     }
     if (s.n_left) {
+        row0.k = 0;
         w_left = public_encryptions(s.n_left, p.t_exp);
         account(2, p.t_exp, s.n_left);
     }
+    row0.k = k_w;
     Poly s0_ntt = to_ntt(sr);
     {  // W = P + pad(s0 * G_scale) (src/spiral.cpp:2205-2219)
         size_t m = 2 * (size_t)tc;
@@ -192,6 +237,8 @@ void Client::gen_pub_params() {
     }
     if (w_left.empty()) w_left.assign(1, 0);
     if (w_right.empty()) w_right.assign(1, 0);
+    std::copy(row0.seed, row0.seed + 32, pp_seed);
+    row0.on = false;
 }
 
 Poly Client::encrypt_simple_regev(const Poly& sigma_raw) {  // src/client.cpp:176-192
@@ -202,7 +249,15 @@ Poly Client::encrypt_simple_regev(const Poly& sigma_raw) {  // src/client.cpp:17
     return c;
 }
 
-Poly Client::query(uint64_t idx_target) {
+// --seeded: ciphertext c of the query has row-0 polynomial k = c under a fresh seed
+Query Client::query(uint64_t idx_target) {
+    if (seeded) row0.begin(rng, 1);
+    Query q{query_cts(idx_target), {}};
+    std::copy(row0.seed, row0.seed + 32, q.seed.begin());
+    row0.on = false;
+    return q;
+}
+Poly Client::query_cts(uint64_t idx_target) {
     const uint64_t idx_dim0 = idx_target / s.num_per, idx_further = idx_target % s.num_per;
     const uint64_t scale_k = Q / p.p_db;  // include/values.h:93
     const uint32_t bits = bits_per(s.ell);
@@ -343,9 +398,16 @@ void PackClient::keygen() {  // keygen(S, Sp, sr, out_n), src/testing.cpp:907-91
     sp = noise_polys(out_n);
 }
 Poly PackClient::regev_samples(size_t m) {
-    Poly a = uniform_polys(m), e = noise_polys(m);
-    Poly b = add(mul_by_const(to_ntt(sr), to_ntt(a)), to_ntt(e));
-    Poly out = to_ntt(invert(a));
+    Poly a_ntt, out;  // out: -a, then b
+    if (row0.on) {
+        out = row0.take(m);
+        a_ntt = negate_ntt(out);
+    } else {
+        Poly a = uniform_polys(m);
+        a_ntt = to_ntt(a), out = to_ntt(invert(a));
+    }
+    Poly e = noise_polys(m);
+    Poly b = add(mul_by_const(to_ntt(sr), a_ntt), to_ntt(e));
     out.insert(out.end(), b.begin(), b.end());
     return out;
 }
@@ -374,22 +436,36 @@ void PackClient::gen_pub_params() {
     auto account = [&](size_t r, size_t c, size_t count) { offline_bytes += (uint64_t)count * r * c * N * 56 / 8; };
     Poly s0_ntt = to_ntt(sr), sp_ntt = to_ntt(sp);
     Poly s0g = mul_by_const(s0_ntt, to_ntt(build_gadget(1, tc)));  // 1 x t_conv
+    // --seeded: row 0 in message order W_exp_left, W_exp_right, V (expansion only), v_W
+    const bool ex = !p.direct_upload;
+    const uint64_t k_right = (uint64_t)s.n_left * p.t_exp, k_v = k_right + (uint64_t)s.n_right * p.t_exp_right, k_vw = ex ? k_v + 2ull * tc : 0;
+    if (seeded) row0.begin(rng, 4);
+    row0.k = k_vw;
     v_w.clear();
     for (uint32_t i = 0; i < out_n; i++) {  // v_W[i] = encryptMatrixArbitrary(AG_i), src/testing.cpp:918-925
-        Poly a = uniform_polys(tc), e = noise_polys((size_t)out_n * tc);
-        Poly a_ntt = to_ntt(a);
+        Poly a_ntt, w;
+        if (row0.on) {
+            w = row0.take(tc);
+            a_ntt = negate_ntt(w);
+        } else {
+            Poly a = uniform_polys(tc);
+            a_ntt = to_ntt(a), w = to_ntt(invert(a));
+        }
+        Poly e = noise_polys((size_t)out_n * tc);
         Poly b = add(to_ntt(e), multiply(sp_ntt, a_ntt, out_n, 1, tc));  // out_n x t_conv
         Poly row(b.begin() + (size_t)i * tc * 2 * N, b.begin() + (size_t)(i + 1) * tc * 2 * N);
         row = add(row, s0g);
         std::copy(row.begin(), row.end(), b.begin() + (size_t)i * tc * 2 * N);
-        Poly w = to_ntt(invert(a));
         w.insert(w.end(), b.begin(), b.end());
         v_w.insert(v_w.end(), w.begin(), w.end());
     }
     account(rows, tc, out_n);
     if (!p.direct_upload) {  // src/testing.cpp:926-949
+        row0.k = 0;
         w_left = expansion_keys(s.n_left, p.t_exp);
+        row0.k = k_right;
         w_right = expansion_keys(s.n_right, p.t_exp_right);
+        row0.k = k_v;  // (V's columns in order: column i has k = k_v + i)
         Poly s0sq = multiply(s0_ntt, s0_ntt, 1, 1, 1);
         const uint32_t bits = bits_per(tc), cols = 2 * tc;
         v.assign((size_t)2 * cols * 2 * N, 0);
@@ -407,8 +483,17 @@ void PackClient::gen_pub_params() {
     if (w_left.empty()) w_left.assign(1, 0);
     if (w_right.empty()) w_right.assign(1, 0);
     if (v.empty()) v.assign(1, 0);
+    std::copy(row0.seed, row0.seed + 32, pp_seed);
+    row0.on = false;
 }
-Poly PackClient::query(uint64_t idx_target) {
+Query PackClient::query(uint64_t idx_target) {
+    if (seeded) row0.begin(rng, 3);
+    Query q{query_cts(idx_target), {}};
+    std::copy(row0.seed, row0.seed + 32, q.seed.begin());
+    row0.on = false;
+    return q;
+}
+Poly PackClient::query_cts(uint64_t idx_target) {
     const uint64_t idx_dim0 = idx_target / s.num_per, idx_further = idx_target % s.num_per, scale_k = Q / p.p_db;
     const uint32_t bits = bits_per(s.ell);
     Poly out;
@@ -422,7 +507,10 @@ Poly PackClient::query(uint64_t idx_target) {
             const uint64_t bit = (idx_further >> i) & 1;
             for (uint32_t j = 0; j < s.ell; j++) {
                 Poly val = const_poly((1ull << (bits * j)) * bit);
+                const uint64_t k_even = s.dim0 + 2ull * (i * s.ell + j);  // (--seeded: the message order, even before odd)
+                row0.k = k_even + 1;
                 Poly c_odd = encrypt_simple_regev(val);                                                      // column 2j+1
+                row0.k = k_even;
                 Poly c_even = encrypt_simple_regev(from_ntt(multiply(s0_ntt, to_ntt(val), 1, 1, 1)));        // column 2j
                 out.insert(out.end(), c_even.begin(), c_even.end());
                 out.insert(out.end(), c_odd.begin(), c_odd.end());

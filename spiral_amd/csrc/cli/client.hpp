@@ -4,6 +4,7 @@
 // (to_ntt / multiply / add / automorph ...), so this program contains no CPU NTT; the only CPU polynomial
 // arithmetic is the final decode product modulo q' (the reference uses HEXL there, src/util.cpp:213-274).
 #pragma once
+#include <array>
 #include <cstdint>
 #include <random>
 #include <vector>
@@ -16,6 +17,23 @@ constexpr uint32_t N = 2048;
 constexpr uint64_t P = 268369921ull, B = 249561089ull, Q = P * B;
 using Poly = std::vector<uint64_t>;  // raw: N words per polynomial; NTT form: 2N words per polynomial
 
+// --seeded (include/spiral_gpu.h, spiral_gpu_query_seeded_bytes): row 0 of every matrix of a message -- the -a of its Regev samples -- is
+// spiral_gpu_seed_expand under a seed drawn from the client's RNG instead of uniform_polys.  `k` is the message's next row-0 polynomial: whoever
+// generates a matrix sets it to the matrix's place in the message first.
+struct Row0 {
+    bool on = false;
+    uint8_t seed[32] = {};
+    uint32_t domain = 0;
+    uint64_t k = 0;
+    void begin(std::mt19937_64& rng, uint32_t d);  // a fresh seed for one message of domain d
+    Poly take(size_t m);                           // the next m row-0 polynomials, NTT form
+};
+// a query as the client sends it: its ciphertexts (NTT form) and, with --seeded, the fresh seed their row 0 was expanded from
+struct Query {
+    Poly cts;
+    std::array<uint8_t, 32> seed{};
+};
+
 struct Client {
     spiral_gpu_params p;
     spiral_gpu_shape s;
@@ -26,14 +44,18 @@ struct Client {
     Poly sp;  // n0 x 1 raw: matrix-Regev secret
     Poly w_left, w_right, w, v;  // public parameters, reference NTT layout
     uint64_t offline_bytes = 0;
+    bool seeded = false;                       // --seeded: the messages' row 0 from seeds
+    Row0 row0;                                 // (while a message is generated)
+    uint8_t pp_seed[32] = {};                  // the seed of the public parameters
 
     Client(const spiral_gpu_params& params, uint64_t seed, bool nonoise_);
     void keygen();
     void gen_pub_params();
-    Poly query(uint64_t idx_target);
+    Query query(uint64_t idx_target);
     Poly decode(const uint64_t* response) const;  // -> n0 x n2 raw plaintext in [0, p_db)
 
   private:
+    Poly query_cts(uint64_t idx_target);
     uint64_t sample_noise();
     Poly noise_polys(size_t n);
     Poly uniform_polys(size_t n);
@@ -55,14 +77,18 @@ struct PackClient {
     Poly sr, sp;
     Poly w_left, w_right, v, v_w;
     uint64_t offline_bytes = 0;
+    bool seeded = false;
+    Row0 row0;
+    uint8_t pp_seed[32] = {};
 
     PackClient(const spiral_gpu_params& params, uint32_t out_n_, uint64_t seed, bool nonoise_);
     void keygen();
     void gen_pub_params();
-    Poly query(uint64_t idx_target);
+    Query query(uint64_t idx_target);
     Poly decode(const uint64_t* response) const;  // -> out_n x out_n raw plaintexts
 
   private:
+    Poly query_cts(uint64_t idx_target);
     uint64_t sample_noise();
     Poly noise_polys(size_t n);
     Poly uniform_polys(size_t n);

@@ -2,7 +2,7 @@
 // 209-265), with the server-answer path running on an MI355X through libspiral_gpu.so.
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
-//            [--wire-input]
+//            [--wire-input] [--seeded]
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -81,8 +81,59 @@ static std::vector<uint8_t> pack_pp_wire(const spiral_gpu_params& p, const spira
     return wire_of({{&c.w_left, ex ? (size_t)s.n_left * 2 * p.t_exp : 0}, {&c.w_right, ex ? (size_t)s.n_right * 2 * p.t_exp_right : 0},
                     {&c.v, ex ? (size_t)4 * p.t_conv : 0}, {&c.v_w, (size_t)out_n * (out_n + 1) * p.t_conv}});
 }
+// --seeded (implies --wire-input): the seeded form instead (include/spiral_gpu.h spiral_gpu_query_seeded_bytes): each message is the client's seed
+// followed by the wire form of its matrices without their row 0, which the client took from spiral_gpu_seed_expand (client.cpp Row0)
+static bool g_seeded = false;
+static std::vector<uint8_t> seeded_of(const uint8_t* seed, std::initializer_list<Segment> segs, std::initializer_list<uint32_t> rows,
+                                      std::initializer_list<uint32_t> cols) {
+    std::vector<const uint64_t*> sent;  // rows 1.. of every matrix, message order
+    auto r = rows.begin(), c = cols.begin();
+    for (const Segment& g : segs) {
+        for (size_t i = 0; i < g.npolys; i++)
+            if (i % ((size_t)*r * *c) >= *c) sent.push_back(g.ntt->data() + i * 2 * N);
+        ++r, ++c;
+    }
+    Poly ntt(sent.size() * 2 * N), raw(sent.size() * N);
+    for (size_t i = 0; i < sent.size(); i++) std::copy(sent[i], sent[i] + 2 * N, ntt.begin() + i * 2 * N);
+    if (!sent.empty()) GPU_OK(spiral_gpu_from_ntt(raw.data(), ntt.data(), sent.size()));
+    std::vector<uint8_t> w(32 + sent.size() * 7 * N);
+    std::copy(seed, seed + 32, w.begin());
+    GPU_OK(spiral_gpu_raw_to_wire(raw.data(), sent.size(), w.data() + 32));
+    return w;
+}
+// what a client sends: a query (with the seed its row 0 came from) and its public parameters
+static std::vector<uint8_t> query_msg(const Query& q) {
+    return g_seeded ? seeded_of(q.seed.data(), {{&q.cts, q.cts.size() / (2 * N)}}, {2}, {1}) : query_wire(q.cts);
+}
+static std::vector<uint8_t> pp_msg(const spiral_gpu_params& p, const spiral_gpu_shape& s, const Client& c) {
+    if (!g_seeded) return pp_wire(p, s, c);
+    return seeded_of(c.pp_seed, {{&c.w_left, (size_t)s.n_left * 2 * p.t_exp}, {&c.w_right, (size_t)s.n_right * 2 * p.t_exp_right}, {&c.w, (size_t)6 * p.t_conv},
+                                 {&c.v, (size_t)6 * p.t_conv}},
+                     {2, 2, 3, 3}, {p.t_exp, p.t_exp_right, 2 * p.t_conv, 2 * p.t_conv});
+}
+static std::vector<uint8_t> pack_pp_msg(const spiral_gpu_params& p, const spiral_gpu_pack_shape& s, uint32_t out_n, const PackClient& c) {
+    if (!g_seeded) return pack_pp_wire(p, s, out_n, c);
+    const bool ex = !p.direct_upload;
+    return seeded_of(c.pp_seed, {{&c.w_left, ex ? (size_t)s.n_left * 2 * p.t_exp : 0}, {&c.w_right, ex ? (size_t)s.n_right * 2 * p.t_exp_right : 0},
+                                 {&c.v, ex ? (size_t)4 * p.t_conv : 0}, {&c.v_w, (size_t)out_n * (out_n + 1) * p.t_conv}},
+                     {2, 2, 2, out_n + 1}, {p.t_exp, p.t_exp_right, 2 * p.t_conv, p.t_conv});
+}
+static int set_query_msg(spiral_gpu_server* s, const std::vector<uint8_t>& m) {
+    return g_seeded ? spiral_gpu_server_set_query_seeded(s, m.data(), m.size()) : spiral_gpu_server_set_query_wire(s, m.data(), m.size());
+}
+static int set_pp_msg(spiral_gpu_server* s, const std::vector<uint8_t>& m) {
+    return g_seeded ? spiral_gpu_server_set_pub_params_seeded(s, m.data(), m.size()) : spiral_gpu_server_set_pub_params_wire(s, m.data(), m.size());
+}
+static int pack_set_pp_msg(spiral_gpu_pack_server* s, const std::vector<uint8_t>& m) {
+    return g_seeded ? spiral_gpu_pack_server_set_pub_params_seeded(s, m.data(), m.size()) : spiral_gpu_pack_server_set_pub_params_wire(s, m.data(), m.size());
+}
 static void print_wire_bytes() {
-    if (g_wire) cout << "   Wire input, uploaded offline / online (b): " << g_wire_offline << " / " << g_wire_online << endl;
+    if (g_seeded) {  // (worded apart from the summary's "... query size (b)" lines that drivers scrape)
+        cout << "   Seeded public parameters upload (b): " << g_wire_offline << endl;
+        cout << "   Seeded query upload (b): " << g_wire_online << endl;
+    } else if (g_wire) {
+        cout << "   Wire input, uploaded offline / online (b): " << g_wire_offline << " / " << g_wire_online << endl;
+    }
 }
 // device buffers for the resident entry points the wire path drives (the host-buffer ones take NTT-form queries)
 #define HIP_CLI_OK(x)                                                                        \
@@ -104,6 +155,7 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     GPU_OK(spiral_gpu_pack_server_create(&p, out_n, 0, &srv));
     GPU_OK(spiral_gpu_pack_server_gen_db(srv, db_seed));
     PackClient cl(p, out_n, seed, nonoise);
+    cl.seeded = g_seeded;
     uint64_t t0 = now_us();
     cl.keygen();
     cl.gen_pub_params();
@@ -112,20 +164,21 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     for (uint32_t i = 0; i < p.nu2; i++) cout << (((idx_target % s.num_per) >> i) & 1) << " ";
     cout << ")" << endl;
     t0 = now_us();
-    Poly query = cl.query(idx_target);
+    const Query query = cl.query(idx_target);
     const double time_query_gen = (double)(now_us() - t0);
     Poly resp((size_t)(out_n + 1) * out_n * N);
     double us[8];
     if (g_wire) {
-        const std::vector<uint8_t> pw = pack_pp_wire(p, s, out_n, cl), qw = query_wire(query);
+        const std::vector<uint8_t> pw = pack_pp_msg(p, s, out_n, cl), qw = query_msg(query);
         g_wire_offline = pw.size(), g_wire_online = qw.size();
-        GPU_OK(spiral_gpu_pack_server_set_pub_params_wire(srv, pw.data(), pw.size()));
-        GPU_OK(spiral_gpu_pack_server_answer_wire(srv, qw.data(), qw.size(), resp.data(), nullptr, us));  // warm-up
-        GPU_OK(spiral_gpu_pack_server_answer_wire(srv, qw.data(), qw.size(), resp.data(), nullptr, us));
+        GPU_OK(pack_set_pp_msg(srv, pw));
+        auto answer = g_seeded ? spiral_gpu_pack_server_answer_seeded : spiral_gpu_pack_server_answer_wire;
+        GPU_OK(answer(srv, qw.data(), qw.size(), resp.data(), nullptr, us));  // warm-up
+        GPU_OK(answer(srv, qw.data(), qw.size(), resp.data(), nullptr, us));
     } else {
         GPU_OK(spiral_gpu_pack_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.v.data(), cl.v_w.data()));
-        GPU_OK(spiral_gpu_pack_server_answer(srv, query.data(), resp.data(), nullptr, us));  // warm-up
-        GPU_OK(spiral_gpu_pack_server_answer(srv, query.data(), resp.data(), nullptr, us));
+        GPU_OK(spiral_gpu_pack_server_answer(srv, query.cts.data(), resp.data(), nullptr, us));  // warm-up
+        GPU_OK(spiral_gpu_pack_server_answer(srv, query.cts.data(), resp.data(), nullptr, us));
     }
     // the response travels in its wire form (bit-packed on the device, include/spiral_gpu.h); the client unpacks and decodes it
     std::vector<uint8_t> wire(spiral_gpu_response_wire_bytes(&p, out_n));
@@ -149,7 +202,7 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
             inst.push_back(sv);
         }
         std::vector<uint8_t> wires((size_t)instances * wire.size());
-        const uint64_t* qp[1] = {query.data()};
+        const uint64_t* qp[1] = {query.cts.data()};
         for (int it = 0; it < 2; it++)  // a warm-up, the timed call
             GPU_OK(spiral_gpu_pack_server_answer_batch_instances(&srv, 1, inst.data(), instances, qp, nullptr, wires.data(), &item_us));
         Poly r((size_t)(out_n + 1) * out_n * N);
@@ -227,7 +280,8 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     if (batch >= 2 && batch <= 8) {
         std::vector<spiral_gpu_pack_server*> lanes{srv};
         std::vector<PackClient> clients;
-        std::vector<Poly> queries, resps(batch, Poly((size_t)(out_n + 1) * out_n * N));
+        std::vector<Query> queries;
+        std::vector<Poly> resps(batch, Poly((size_t)(out_n + 1) * out_n * N));
         std::vector<uint64_t> idxs;
         clients.reserve(batch);
         for (uint32_t b = 0; b < batch; b++) {
@@ -237,12 +291,12 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
                 lanes.push_back(lane);
             }
             clients.emplace_back(p, out_n, seed + 1 + b, nonoise);
+            clients[b].seeded = g_seeded;
             clients[b].keygen();
             clients[b].gen_pub_params();
             idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);
             if (g_wire) {
-                const std::vector<uint8_t> pw = pack_pp_wire(p, s, out_n, clients[b]);
-                GPU_OK(spiral_gpu_pack_server_set_pub_params_wire(lanes[b], pw.data(), pw.size()));
+                GPU_OK(pack_set_pp_msg(lanes[b], pack_pp_msg(p, s, out_n, clients[b])));
             } else {
                 GPU_OK(spiral_gpu_pack_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].v.data(), clients[b].v_w.data()));
             }
@@ -252,12 +306,13 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
         std::vector<uint64_t*> rp;
         std::vector<std::vector<uint8_t>> qws;
         std::vector<const void*> qwp;
-        for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].data()), rp.push_back(resps[b].data());
+        for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].cts.data()), rp.push_back(resps[b].data());
         if (g_wire)
-            for (uint32_t b = 0; b < batch; b++) qws.push_back(query_wire(queries[b]));
+            for (uint32_t b = 0; b < batch; b++) qws.push_back(query_msg(queries[b]));
         for (uint32_t b = 0; b < qws.size(); b++) qwp.push_back(qws[b].data());
         auto run = [&](uint64_t* const* r, double* u) {
-            if (g_wire) GPU_OK(spiral_gpu_pack_server_answer_batch_wire(lanes.data(), batch, qwp.data(), qws[0].size(), r, nullptr, u));
+            if (g_seeded) GPU_OK(spiral_gpu_pack_server_answer_batch_seeded(lanes.data(), batch, qwp.data(), qws[0].size(), r, nullptr, u));
+            else if (g_wire) GPU_OK(spiral_gpu_pack_server_answer_batch_wire(lanes.data(), batch, qwp.data(), qws[0].size(), r, nullptr, u));
             else GPU_OK(spiral_gpu_pack_server_answer_batch(lanes.data(), batch, qp.data(), r, nullptr, u));
         };
         double bus[8];
@@ -316,6 +371,8 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--instances") && i + 1 < argc) instances = (uint32_t)strtoul(argv[++i], nullptr, 10);
         // --wire-input (not a flag of the reference): public parameters and queries reach the server in their 7-byte wire form (include/spiral_gpu.h)
         if (!strcmp(argv[i], "--wire-input")) { cout << "Sending public parameters and queries in their wire form" << endl; g_wire = true; }
+        // --seeded (implies --wire-input): the same with every matrix's random row 0 replaced by a seed the client draws from its own generator
+        if (!strcmp(argv[i], "--seeded")) { cout << "Sending public parameters and queries in their seeded form" << endl; g_wire = g_seeded = true; }
         // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
         // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
         // --output-err F (src/spiral.cpp:1287-1291) asks the reference to dump its empirical noise statistics (analyze_err.py's
@@ -329,7 +386,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (g_wire && ((batch && (batch < 2 || batch > 8)) || (instances && (instances < 2 || instances > 16 || high_rate)))) {
-        fprintf(stderr, "spiral: --wire-input takes --batch B in 2 .. 8 and --instances F in 2 .. 16 (not with --high-rate)\n");
+        fprintf(stderr, "spiral: %s takes --batch B in 2 .. 8 and --instances F in 2 .. 16 (not with --high-rate)\n", g_seeded ? "--seeded" : "--wire-input");
         return 1;
     }
     if (idx_target >= total_n) {
@@ -379,6 +436,7 @@ int main(int argc, char** argv) {
     // ---- client: keys, public parameters, query
     double time_key_gen = 0, time_query_gen = 0, time_decoding = 0;
     Client cl(p, seed, nonoise);
+    cl.seeded = g_seeded;
     uint64_t t0 = now_us();
     cl.keygen();
     cl.gen_pub_params();
@@ -388,7 +446,7 @@ int main(int argc, char** argv) {
         cout << "stopround = " << s.stopround << endl;
     }
     t0 = now_us();
-    Poly query = cl.query(idx_target);
+    const Query query = cl.query(idx_target);
     time_query_gen = (double)(now_us() - t0);
 
     // ---- server
@@ -397,18 +455,18 @@ int main(int argc, char** argv) {
     double us[8];
     std::vector<uint8_t> qwire;  // (--wire-input) the query as sent
     if (g_wire) {
-        const std::vector<uint8_t> pw = pp_wire(p, s, cl);
-        qwire = query_wire(query);
+        const std::vector<uint8_t> pw = pp_msg(p, s, cl);
+        qwire = query_msg(query);
         g_wire_offline = pw.size(), g_wire_online = qwire.size();
-        GPU_OK(spiral_gpu_server_set_pub_params_wire(srv, pw.data(), pw.size()));
+        GPU_OK(set_pp_msg(srv, pw));
         for (int it = 0; it < 2; it++) {  // warm-up (table upload, first launches), then the answer
-            GPU_OK(spiral_gpu_server_set_query_wire(srv, qwire.data(), qwire.size()));
+            GPU_OK(set_query_msg(srv, qwire));
             GPU_OK(spiral_gpu_server_answer_resident(srv, us));
         }
     } else {
         GPU_OK(spiral_gpu_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.w.data(), cl.v.data()));
-        GPU_OK(spiral_gpu_server_answer(srv, query.data(), final_ct.data(), resp.data(), us));  // warm-up (table upload, first launches)
-        GPU_OK(spiral_gpu_server_answer(srv, query.data(), final_ct.data(), resp.data(), us));
+        GPU_OK(spiral_gpu_server_answer(srv, query.cts.data(), final_ct.data(), resp.data(), us));  // warm-up (table upload, first launches)
+        GPU_OK(spiral_gpu_server_answer(srv, query.cts.data(), final_ct.data(), resp.data(), us));
     }
     const double time_expansion_main = us[0], time_conversion = us[1], time_first_multiply = us[2], time_folding = us[3];
     cout << std::fixed << std::setprecision(0);
@@ -451,17 +509,17 @@ int main(int argc, char** argv) {
                 lanes.push_back(lane);
             }
             clients.emplace_back(p, seed + 1 + b, nonoise);
+            clients[b].seeded = g_seeded;
             clients[b].keygen();
             clients[b].gen_pub_params();
             idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);
-            Poly qb = clients[b].query(idxs[b]);
+            const Query qb = clients[b].query(idxs[b]);
             if (g_wire) {
-                const std::vector<uint8_t> pw = pp_wire(p, s, clients[b]), qw = query_wire(qb);
-                GPU_OK(spiral_gpu_server_set_pub_params_wire(lanes[b], pw.data(), pw.size()));
-                GPU_OK(spiral_gpu_server_set_query_wire(lanes[b], qw.data(), qw.size()));
+                GPU_OK(set_pp_msg(lanes[b], pp_msg(p, s, clients[b])));
+                GPU_OK(set_query_msg(lanes[b], query_msg(qb)));
             } else {
                 GPU_OK(spiral_gpu_server_set_pub_params(lanes[b], clients[b].w_left.data(), clients[b].w_right.data(), clients[b].w.data(), clients[b].v.data()));
-                GPU_OK(spiral_gpu_server_set_query(lanes[b], qb.data()));
+                GPU_OK(spiral_gpu_server_set_query(lanes[b], qb.cts.data()));
             }
         }
         return 0;
@@ -517,7 +575,7 @@ int main(int argc, char** argv) {
             void* d_resp = nullptr;
             HIP_CLI_OK(hipMalloc(&d_resp, resps.size() * sizeof(uint64_t)));
             for (int it = 0; it < 3; it++) {
-                GPU_OK(spiral_gpu_server_set_query_wire(srv, qwire.data(), qwire.size()));
+                GPU_OK(set_query_msg(srv, qwire));
                 t0 = now_us();
                 GPU_OK(spiral_gpu_server_run_query_instances(srv, inst.data(), instances, 1, d_resp, nullptr));
                 GPU_OK(spiral_gpu_server_sync(srv));
@@ -527,7 +585,7 @@ int main(int argc, char** argv) {
             HIP_CLI_OK(hipFree(d_resp));
         } else {
             for (int it = 0; it < 3; it++)  // capture, a replay, the timed replay
-                GPU_OK(spiral_gpu_server_answer_instances(srv, inst.data(), instances, query.data(), resps.data(), nullptr, &item_us));
+                GPU_OK(spiral_gpu_server_answer_instances(srv, inst.data(), instances, query.cts.data(), resps.data(), nullptr, &item_us));
         }
         cout << "Item of " << instances << " plaintexts, Is correct?:";
         for (uint32_t k = 0; k < instances; k++) {
@@ -549,18 +607,18 @@ int main(int argc, char** argv) {
         if (make_clients() || make_instances()) return 1;
         const size_t wb = wire.size();
         std::vector<uint8_t> wires((size_t)batch * instances * wb);
-        std::vector<Poly> queries;
+        std::vector<Query> queries;
         std::vector<const uint64_t*> qp;
         for (uint32_t b = 0; b < batch; b++) queries.push_back(clients[b].query(idxs[b]));
-        for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].data());
+        for (uint32_t b = 0; b < batch; b++) qp.push_back(queries[b].cts.data());
         GPU_OK(spiral_gpu_server_use_graphs(srv, 1));
         if (g_wire) {  // each client's query decoded into its lane, the item batch answered by the resident entry point, wire forms to the host
             std::vector<std::vector<uint8_t>> qws;
-            for (uint32_t b = 0; b < batch; b++) qws.push_back(query_wire(queries[b]));
+            for (uint32_t b = 0; b < batch; b++) qws.push_back(query_msg(queries[b]));
             void* d_wire = nullptr;
             HIP_CLI_OK(hipMalloc(&d_wire, wires.size()));
             for (int it = 0; it < 3; it++) {
-                for (uint32_t b = 0; b < batch; b++) GPU_OK(spiral_gpu_server_set_query_wire(lanes[b], qws[b].data(), qws[b].size()));
+                for (uint32_t b = 0; b < batch; b++) GPU_OK(set_query_msg(lanes[b], qws[b]));
                 t0 = now_us();
                 GPU_OK(spiral_gpu_server_run_query_batch_instances(lanes.data(), batch, inst.data(), instances, 1, nullptr, nullptr, d_wire));
                 GPU_OK(spiral_gpu_server_sync(srv));

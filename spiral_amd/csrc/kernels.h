@@ -264,6 +264,9 @@ constexpr bool fold_pair_exact(uint32_t ell) { return ell >= 2 && ell * get_bits
 // reference polynomial b <-> packed polynomial pk_map(b)
 void launch_ref_to_pk(const uint64_t* ref, uint64_t* pk, uint32_t npolys, IndexMap pk_map, hipStream_t s);
 void launch_pk_to_ref(const uint64_t* pk, uint64_t* ref, uint32_t npolys, IndexMap pk_map, hipStream_t s);
+// row 0 of a seeded message (seed.hip, seed_device.h): row-0 polynomials k0 .. k0 + npolys - 1 of domain `domain` under the 32-byte seed, in PK
+// form, polynomial j to pk_map(j)
+void launch_seed_rows(const uint8_t* seed, uint32_t domain, uint64_t k0, uint64_t* pk, IndexMap pk_map, uint32_t npolys, hipStream_t s);
 
 // ---- pointwise polynomial kernels (poly.hip) -------------------------------------------------------
 // out[b][r][c] = sum_m A[r][m] * B[b][m][c]  (+ addend), all PK; generic MatPoly multiply (src/poly.cpp:34)

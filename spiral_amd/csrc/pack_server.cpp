@@ -514,6 +514,36 @@ int spiral_gpu_pack_server_set_pub_params_wire(spiral_gpu_pack_server* S, const 
     return 0;
 }
 
+// the same from the seeded form: row 0 of every matrix from the message's seed (include/spiral_gpu.h)
+int spiral_gpu_pack_server_set_pub_params_seeded(spiral_gpu_pack_server* S, const void* msg, size_t bytes) {
+    if (!S) return fail("null server");
+    if (S->zombie) return fail("destroyed server");
+    HIP_OK(hipSetDevice(S->device));
+    const spiral_gpu_params& p = S->p;
+    const bool ex = !p.direct_upload;
+    const WireSegment seg[4] = {{S->w_left.p, ex ? (size_t)S->s.n_left * 2 * p.t_exp : 0, 2, p.t_exp},
+                                {S->w_right.p, ex ? (size_t)S->s.n_right * 2 * p.t_exp_right : 0, 2, p.t_exp_right},
+                                {S->v.p, ex ? (size_t)2 * 2 * p.t_conv : 0, 2, 2 * p.t_conv},
+                                {S->v_w.p, (size_t)S->out_n * (S->out_n + 1) * p.t_conv, S->out_n + 1, p.t_conv}};
+    S->have_pp = false;
+    if (ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_PACK_PUB_PARAMS, seg, 4, "set_pub_params_seeded")) return -1;
+    S->have_pp = true;
+    return 0;
+}
+
+size_t spiral_gpu_pack_query_seeded_bytes(const spiral_gpu_params* p, uint32_t out_n) {
+    spiral_gpu_pack_shape s;
+    if (!p || pack_shape_of(p, out_n, &s)) return 0;
+    return kSeedBytes + (size_t)s.n_query_cts * kWirePolyBytes;
+}
+
+size_t spiral_gpu_pack_pub_params_seeded_bytes(const spiral_gpu_params* p, uint32_t out_n) {
+    spiral_gpu_pack_shape s;
+    if (!p || pack_shape_of(p, out_n, &s)) return 0;
+    const size_t ex = p->direct_upload ? 0 : (size_t)s.n_left * p->t_exp + (size_t)s.n_right * p->t_exp_right + (size_t)2 * p->t_conv;
+    return kSeedBytes + (ex + (size_t)out_n * out_n * p->t_conv) * kWirePolyBytes;
+}
+
 size_t spiral_gpu_pack_query_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) {
     spiral_gpu_pack_shape s;
     if (!p || pack_shape_of(p, out_n, &s)) return 0;
@@ -700,6 +730,16 @@ static int pk_query_wire(spiral_gpu_pack_server* S, const void* wire, size_t byt
     const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2};
     return ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, &seg, 1, what);
 }
+// the same from the seeded form
+static int pk_query_seeded(spiral_gpu_pack_server* S, const void* msg, size_t bytes, const char* what) {
+    HIP_OK(hipSetDevice(S->device));
+    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2, 2, 1};
+    return ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_PACK_QUERY, &seg, 1, what);
+}
+// a query's bytes in the wire / seeded form (what the batch entry points check before anything is uploaded)
+static size_t pk_query_bytes(const spiral_gpu_pack_server* S, bool seeded) {
+    return seeded ? kSeedBytes + (size_t)S->s.n_query_cts * kWirePolyBytes : (size_t)S->s.n_query_cts * 2 * kWirePolyBytes;
+}
 
 // answer with the query in S->query already when query is null
 static int pk_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
@@ -717,6 +757,13 @@ int spiral_gpu_pack_server_answer_wire(spiral_gpu_pack_server* S, const void* qu
                                        double stage_us[8]) {
     if (!S || !query_wire) return fail("null argument");
     if (pk_check_answer(S) || pk_query_wire(S, query_wire, bytes, "answer_wire")) return -1;
+    return pk_answer(S, nullptr, response, packed_ct, stage_us);
+}
+
+int spiral_gpu_pack_server_answer_seeded(spiral_gpu_pack_server* S, const void* query_msg, size_t bytes, uint64_t* response, uint64_t* packed_ct,
+                                         double stage_us[8]) {
+    if (!S || !query_msg) return fail("null argument");
+    if (pk_check_answer(S) || pk_query_seeded(S, query_msg, bytes, "answer_seeded")) return -1;
     return pk_answer(S, nullptr, response, packed_ct, stage_us);
 }
 
@@ -762,21 +809,31 @@ int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server* const* servers, 
 // answer_batch from the queries' wire forms: every argument (each query's byte count included) is checked before anything is uploaded; then every
 // lane's query is decoded into its own buffer, and only when all of them decoded cleanly does the batch run -- a bad query leaves every lane's
 // previous results intact
-int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_wires, size_t bytes_each,
-                                             uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
-    if (pk_check_lanes(servers, n, false, "answer_batch_wire")) return -1;
-    if (!query_wires) return fail("answer_batch_wire: null queries");
-    const size_t want = (size_t)servers[0]->s.n_query_cts * 2 * kWirePolyBytes;
-    if (bytes_each != want) return fail("answer_batch_wire: %zu bytes per query, the wire form of a query takes %zu", bytes_each, want);
+static int pk_answer_batch_msgs(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* msgs, size_t bytes_each, bool seeded,
+                                uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8], const char* what) {
+    if (pk_check_lanes(servers, n, false, what)) return -1;
+    if (!msgs) return fail("%s: null queries", what);
+    const size_t want = pk_query_bytes(servers[0], seeded);
+    if (bytes_each != want) return fail("%s: %zu bytes per query, the %s form of a query takes %zu", what, bytes_each, seeded ? "seeded" : "wire", want);
     for (uint32_t b = 0; b < n; b++)
-        if (!query_wires[b]) return fail("answer_batch_wire: query %u is null", b);
+        if (!msgs[b]) return fail("%s: query %u is null", what, b);
     for (uint32_t b = 0; b < n; b++) {
-        char what[48];
-        snprintf(what, sizeof(what), "answer_batch_wire: query %u", b);
-        if (pk_query_wire(servers[b], query_wires[b], bytes_each, what)) return -1;
+        char w[64];
+        snprintf(w, sizeof(w), "%s: query %u", what, b);
+        if (seeded ? pk_query_seeded(servers[b], msgs[b], bytes_each, w) : pk_query_wire(servers[b], msgs[b], bytes_each, w)) return -1;
     }
     if (n == 1) return pk_answer(servers[0], nullptr, responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
     return pk_answer_batch(servers, n, nullptr, responses, packed_cts, stage_us);
+}
+
+int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_wires, size_t bytes_each,
+                                             uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
+    return pk_answer_batch_msgs(servers, n, query_wires, bytes_each, false, responses, packed_cts, stage_us, "answer_batch_wire");
+}
+
+int spiral_gpu_pack_server_answer_batch_seeded(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_msgs, size_t bytes_each,
+                                               uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
+    return pk_answer_batch_msgs(servers, n, query_msgs, bytes_each, true, responses, packed_cts, stage_us, "answer_batch_seeded");
 }
 
 // the batch after its checks; queries null: every lane's query was decoded into its buffer already
@@ -982,21 +1039,33 @@ int spiral_gpu_pack_server_answer_batch_instances(spiral_gpu_pack_server* const*
 }
 
 // from the queries' wire forms: every argument checked, then every query decoded; the call runs only when all of them decoded cleanly
-int spiral_gpu_pack_server_answer_batch_instances_wire(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
-                                                       uint32_t n_instances, const void* const* query_wires, size_t bytes_each, uint64_t* responses, void* wire,
-                                                       double* total_us) {
-    const char* what = "answer_batch_instances_wire";
-    if (pk_check_items(servers, n_clients, instances, n_instances, query_wires, responses, wire, what)) return -1;
-    const size_t want = (size_t)servers[0]->s.n_query_cts * 2 * kWirePolyBytes;
-    if (bytes_each != want) return fail("%s: %zu bytes per query, the wire form of a query takes %zu", what, bytes_each, want);
+static int pk_answer_items_msgs(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances, uint32_t n_instances,
+                                const void* const* msgs, size_t bytes_each, bool seeded, uint64_t* responses, void* wire, double* total_us, const char* what) {
+    if (pk_check_items(servers, n_clients, instances, n_instances, msgs, responses, wire, what)) return -1;
+    const size_t want = pk_query_bytes(servers[0], seeded);
+    if (bytes_each != want) return fail("%s: %zu bytes per query, the %s form of a query takes %zu", what, bytes_each, seeded ? "seeded" : "wire", want);
     for (uint32_t b = 0; b < n_clients; b++)
-        if (!query_wires[b]) return fail("%s: query %u is null", what, b);
+        if (!msgs[b]) return fail("%s: query %u is null", what, b);
     for (uint32_t b = 0; b < n_clients; b++) {
         char w[64];
         snprintf(w, sizeof(w), "%s: query %u", what, b);
-        if (pk_query_wire(servers[b], query_wires[b], bytes_each, w)) return -1;
+        if (seeded ? pk_query_seeded(servers[b], msgs[b], bytes_each, w) : pk_query_wire(servers[b], msgs[b], bytes_each, w)) return -1;
     }
     return pk_answer_items(servers, n_clients, instances, n_instances, nullptr, responses, wire, total_us);
+}
+
+int spiral_gpu_pack_server_answer_batch_instances_wire(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
+                                                       uint32_t n_instances, const void* const* query_wires, size_t bytes_each, uint64_t* responses, void* wire,
+                                                       double* total_us) {
+    return pk_answer_items_msgs(servers, n_clients, instances, n_instances, query_wires, bytes_each, false, responses, wire, total_us,
+                                "answer_batch_instances_wire");
+}
+
+int spiral_gpu_pack_server_answer_batch_instances_seeded(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
+                                                         uint32_t n_instances, const void* const* query_msgs, size_t bytes_each, uint64_t* responses,
+                                                         void* wire, double* total_us) {
+    return pk_answer_items_msgs(servers, n_clients, instances, n_instances, query_msgs, bytes_each, true, responses, wire, total_us,
+                                "answer_batch_instances_seeded");
 }
 
 // the batched first-dimension sweep alone (answer_batch's), iters times on servers[0]'s stream with the lanes' current records, timed with device

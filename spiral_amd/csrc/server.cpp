@@ -1232,6 +1232,63 @@ int spiral_gpu_server_set_query_wire(spiral_gpu_server* S, const void* wire, siz
     return 0;
 }
 
+// the same from the seeded form (include/spiral_gpu.h): row 0 of every matrix generated on the device from the message's seed, the other rows as
+// set_query_wire / set_pub_params_wire decode them
+int spiral_gpu_server_set_pub_params_seeded(spiral_gpu_server* S, const void* msg, size_t bytes) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const spiral_gpu_params& p = S->p;
+    const WireSegment seg[4] = {{S->w_left.p, (size_t)S->s.n_left * 2 * p.t_exp, 2, p.t_exp},
+                                {S->w_right.p, (size_t)S->s.n_right * 2 * p.t_exp_right, 2, p.t_exp_right},
+                                {S->w.p, (size_t)3 * 2 * p.t_conv, 3, 2 * p.t_conv},
+                                {S->v.p, (size_t)3 * 2 * p.t_conv, 3, 2 * p.t_conv}};
+    S->have_pp = false;
+    if (ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_PUB_PARAMS, seg, 4, "set_pub_params_seeded")) return -1;
+    S->have_pp = true;
+    return 0;
+}
+
+int spiral_gpu_server_set_query_seeded(spiral_gpu_server* S, const void* msg, size_t bytes) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2, 2, 1};
+    S->have_query = S->have_records = false;
+    if (ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_QUERY, &seg, 1, "set_query_seeded")) return -1;
+    S->have_query = true;
+    return 0;
+}
+
+size_t spiral_gpu_query_seeded_bytes(const spiral_gpu_params* p) {
+    spiral_gpu_shape s;
+    if (shape_of(p, &s)) return 0;
+    return kSeedBytes + (size_t)s.n_query_cts * kWirePolyBytes;
+}
+
+size_t spiral_gpu_pub_params_seeded_bytes(const spiral_gpu_params* p) {
+    spiral_gpu_shape s;
+    if (shape_of(p, &s)) return 0;
+    return kSeedBytes + ((size_t)s.n_left * p->t_exp + (size_t)s.n_right * p->t_exp_right + (size_t)8 * p->t_conv) * kWirePolyBytes;
+}
+
+// the client's half of the seeded form: row-0 polynomials first_k .. first_k + npolys - 1 of `domain` in reference NTT layout, plain host code
+// through the same definition as the device's generator (seed_device.h)
+int spiral_gpu_seed_expand(const void* seed32, uint32_t domain, uint64_t first_k, size_t npolys, uint64_t* out) {
+    if (!seed32 || (!out && npolys)) return fail("seed_expand: null argument");
+    const Seed key = seed_words((const uint8_t*)seed32);
+    for (size_t j = 0; j < npolys; j++) {
+        uint64_t* o = out + j * kRefNtt;
+        for (uint32_t c = 0; c < kN / 2; c++) {
+            uint64_t r[2];
+            seed_slot_pair(key.w, domain, first_k + j, c, r);
+            for (uint32_t h = 0; h < 2; h++) {
+                o[2 * c + h] = (uint32_t)r[h];
+                o[kN + 2 * c + h] = r[h] >> 32;
+            }
+        }
+    }
+    return 0;
+}
+
 size_t spiral_gpu_query_wire_bytes(const spiral_gpu_params* p) {
     spiral_gpu_shape s;
     if (shape_of(p, &s)) return 0;

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import WIRE_POLY_BYTES, U64P, Params, Shape, check, lib, wire_bytes
+from ._lib import SEED_BYTES, SEED_PACK_PUB_PARAMS, SEED_PACK_QUERY, SEED_PUB_PARAMS, SEED_QUERY, WIRE_POLY_BYTES, U64P, Params, Shape, check, lib, wire_bytes
 
 N = 2048
 P = 268369921
@@ -18,6 +18,8 @@ __all__ = [
     "multiply", "add", "mul_by_const", "automorph", "invert", "gadget_invert", "getRescaled", "multiplyQueryByDatabase", "multiplyQueriesByDatabase", "split_and_crt",
     "foldOneFurtherDimension", "expandImproved", "scalToMat", "regevToGSW", "time_ntt", "time_ntt_digits", "response_wire_bytes", "response_from_wire",
     "query_wire_bytes", "pub_params_wire_bytes", "pack_query_wire_bytes", "pack_pub_params_wire_bytes", "raw_to_wire", "raw_from_wire",
+    "query_seeded_bytes", "pub_params_seeded_bytes", "pack_query_seeded_bytes", "pack_pub_params_seeded_bytes", "seed_expand",
+    "SEED_BYTES", "SEED_QUERY", "SEED_PUB_PARAMS", "SEED_PACK_QUERY", "SEED_PACK_PUB_PARAMS",
     "set_option", "get_option", "options",
 ]
 
@@ -214,6 +216,37 @@ def raw_from_wire(wire) -> np.ndarray:
         raise ValueError(f"raw_from_wire: {wire.size} bytes are not whole polynomials of {WIRE_POLY_BYTES}")
     out = np.zeros((wire.size // WIRE_POLY_BYTES, N), dtype=np.uint64)
     check(lib().spiral_gpu_raw_from_wire(wire.ctypes.data_as(C.c_void_p), out.shape[0], _p(out)))
+    return out
+
+
+def query_seeded_bytes(params) -> int:
+    """size of a query's seeded form (include/spiral_gpu.h): the 32-byte seed and row 1 of each ciphertext in its wire form; 0 for refused parameters"""
+    return int(lib().spiral_gpu_query_seeded_bytes(C.byref(params)))
+
+
+def pub_params_seeded_bytes(params) -> int:
+    """size of the public parameters' seeded form (the wire message less every matrix's row 0, after a seed); 0 for refused parameters"""
+    return int(lib().spiral_gpu_pub_params_seeded_bytes(C.byref(params)))
+
+
+def pack_query_seeded_bytes(params, out_n: int) -> int:
+    """SpiralPack: size of a query's seeded form; 0 for refused parameters"""
+    return int(lib().spiral_gpu_pack_query_seeded_bytes(C.byref(params), int(out_n)))
+
+
+def pack_pub_params_seeded_bytes(params, out_n: int) -> int:
+    """SpiralPack: size of the public parameters' seeded form; 0 for refused parameters"""
+    return int(lib().spiral_gpu_pack_pub_params_seeded_bytes(C.byref(params), int(out_n)))
+
+
+def seed_expand(seed, domain: int, first_k: int, npolys: int) -> np.ndarray:
+    """the client's half of the seeded form: row-0 polynomials first_k .. first_k + npolys - 1 of `domain` (SEED_QUERY ...) under the 32-byte seed,
+    [npolys][2][2048] uint64 in the reference's NTT layout (residues mod p, then mod b); host code"""
+    seed = wire_bytes(seed)
+    if seed.size != SEED_BYTES:
+        raise ValueError(f"seed_expand: a seed is {SEED_BYTES} bytes, not {seed.size}")
+    out = np.zeros((int(npolys), 2, N), dtype=np.uint64)
+    check(lib().spiral_gpu_seed_expand(seed.ctypes.data_as(C.c_void_p), int(domain), int(first_k), int(npolys), _p(out)))
     return out
 
 

@@ -136,6 +136,21 @@ class PackServer:
         check(lib().spiral_gpu_pack_server_answer_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size, _p(resp), _p(packed) if want_packed else None, us))
         return resp, packed, dict(zip(PACK_STAGE_NAMES, list(us)))
 
+    def set_pub_params_seeded(self, msg):
+        """the public parameters as one seeded message (include/spiral_gpu.h): row 0 of every matrix from the seed"""
+        w = wire_bytes(msg)
+        check(lib().spiral_gpu_pack_server_set_pub_params_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
+    def answer_seeded(self, query_msg, want_packed: bool = True):
+        """answer with the query in its seeded form: as answer"""
+        w = wire_bytes(query_msg)
+        n = self.out_n
+        resp = np.zeros((n + 1, n, N), dtype=np.uint64)
+        packed = np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None
+        us = (C.c_double * 8)()
+        check(lib().spiral_gpu_pack_server_answer_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size, _p(resp), _p(packed) if want_packed else None, us))
+        return resp, packed, dict(zip(PACK_STAGE_NAMES, list(us)))
+
     def answer(self, query, want_packed: bool = True):
         n = self.out_n
         resp = np.zeros((n + 1, n, N), dtype=np.uint64)
@@ -220,6 +235,24 @@ def answer_batch_wire(servers, query_wires, want_packed: bool = False):
     return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
 
 
+def answer_batch_seeded(servers, query_msgs, want_packed: bool = False):
+    """answer_batch with the queries in their seeded form (all of one size); every query is checked and expanded before the batch runs"""
+    servers, hs = _lane_handles(servers, "answer_batch_seeded")
+    ws = [wire_bytes(w) for w in query_msgs]
+    if len(ws) != len(servers):
+        raise ValueError(f"answer_batch_seeded: {len(ws)} queries for {len(servers)} servers")
+    if len({w.size for w in ws}) != 1:
+        raise ValueError("answer_batch_seeded: the queries differ in size")
+    n = servers[0].out_n
+    resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
+    packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
+    arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
+    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+    us = (C.c_double * 8)()
+    check(lib().spiral_gpu_pack_server_answer_batch_seeded(hs, len(servers), wp, ws[0].size, arr(resp), arr(packed), us))
+    return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
+
+
 def time_sweep_batch(servers, iters: int = 10) -> float:
     """the batched first-dimension sweep alone (with the lanes' current queries, each answered once): average ms per pass"""
     servers, hs = _lane_handles(servers, "time_sweep_batch")
@@ -292,6 +325,22 @@ def answer_batch_instances_wire(servers, instances, query_wires, wire: bool = Fa
     wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
     return _item_call(servers, instances, wire, stats,
                       lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances_wire(hs, len(servers), ins, len(instances), wp, want, r, w, us)))
+
+
+def answer_batch_instances_seeded(servers, instances, query_msgs, wire: bool = False, stats: dict = None):
+    """answer_batch_instances with the queries in their seeded form (each spiral_gpu_pack_query_seeded_bytes long); every query is expanded before
+    the call runs"""
+    what = "answer_batch_instances_seeded"
+    servers, hs, instances, ins = _item_args(servers, instances, what)
+    ws = [wire_bytes(w) for w in query_msgs]
+    if len(ws) != len(servers):
+        raise ValueError(f"{what}: {len(ws)} queries for {len(servers)} clients")
+    want = lib().spiral_gpu_pack_query_seeded_bytes(C.byref(servers[0].params), servers[0].out_n)
+    if any(w.size != want for w in ws):
+        raise ValueError(f"{what}: the seeded form of a query takes {want} bytes, got {[w.size for w in ws]}")
+    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
+    return _item_call(servers, instances, wire, stats,
+                      lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances_seeded(hs, len(servers), ins, len(instances), wp, want, r, w, us)))
 
 
 def answer_instances(server, instances, query, wire: bool = False, stats: dict = None):

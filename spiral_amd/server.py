@@ -217,6 +217,18 @@ class Server:
         w = wire_bytes(wire)
         check(lib().spiral_gpu_server_set_query_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
 
+    def set_pub_params_seeded(self, msg):
+        """the public parameters as one seeded message (include/spiral_gpu.h): row 0 of every matrix generated on the device from the seed, the
+        other rows decoded as set_pub_params_wire does"""
+        w = wire_bytes(msg)
+        check(lib().spiral_gpu_server_set_pub_params_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
+    def set_query_seeded(self, msg):
+        """the query in its seeded form: the seed, then row 1 of each ciphertext in its wire form; into set_query's buffer.  A failure leaves no
+        query set"""
+        w = wire_bytes(msg)
+        check(lib().spiral_gpu_server_set_query_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
     # ---- stages ----
     def expand(self):
         check(lib().spiral_gpu_server_expand(self.h))
