@@ -298,25 +298,38 @@ void srv_db_loaded(spiral_gpu_server* S) {
     S->db_epoch++;
 }
 
-// the first-dimension sweep of n queries against the database image H holds: one pass on the matrix cores when the limb-plane image is given, else
-// passes of up to kSweepMaxBatch queries on the vector ALU (wide packed geometries), else one sweep per query
-int sweep_queries(const spiral_gpu_server* H, const uint64_t* limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log, hipStream_t st,
-                  uint32_t k_log = 0) {
-    const uint32_t np = H->s.num_per, jm = 2 * H->dim0_shard;
-    if (!limbs && H->db_format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;  // the one image is in limb-plane form: every sweep is the matrix-core one
+// the first-dimension sweep of n queries (records qs[b] -> accumulators acc[b]) against the packed image db of geometry (np, jm): one pass on the matrix
+// cores when the limb-plane image `limbs` is given, else passes of up to kSweepMaxBatch queries on the vector ALU (wide packed geometries), else one(b)
+// per remaining query.  g_extra: the rank-major batch layout (kernels.h launch_sweep_batch)
+template <class One>
+int sweep_queries(const uint64_t* db, const uint64_t* limbs, uint32_t np, uint32_t jm, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log,
+                  hipStream_t st, uint32_t k_log, uint32_t g_extra, One one) {
     if (limbs) {
-        const hipError_t e = launch_sweep_mfma(limbs, qs, acc, n, np, jm, g_log, st, k_log);
+        const hipError_t e = launch_sweep_mfma(limbs, qs, acc, n, np, jm, g_log, st, k_log, g_extra);
         return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
     }
     const uint32_t step = sweep_batch_ok(np, jm) ? kSweepMaxBatch : 1;
     for (uint32_t b0 = 0; b0 < n; b0 += step) {
         const uint32_t nb = n - b0 < step ? n - b0 : step;
-        if (nb == 1)
-            launch_sweep(H->db.p, qs[b0], acc[b0], np, jm, g_log, st, k_log);
-        else
-            launch_sweep_batch(H->db.p, qs + b0, acc + b0, nb, np, jm, g_log, st);
+        if (nb > 1)
+            launch_sweep_batch(db, qs + b0, acc + b0, nb, np, jm, g_log, st, g_extra);
+        else if (int rc = one(b0))
+            return rc;
     }
     return 0;
+}
+// the same where a lone query sweeps straight into its accumulators
+int sweep_queries(const uint64_t* db, const uint64_t* limbs, uint32_t np, uint32_t jm, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log,
+                  hipStream_t st, uint32_t k_log = 0) {
+    return sweep_queries(db, limbs, np, jm, qs, acc, n, g_log, st, k_log, 0, [&](uint32_t b) {
+        launch_sweep(db, qs[b], acc[b], np, jm, g_log, st, k_log);
+        return 0;
+    });
+}
+// ... of the image H holds, in whichever form it is in
+int sweep_image(const spiral_gpu_server* H, const uint64_t* limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log, hipStream_t st) {
+    if (!limbs && H->db_format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;  // the one image is in limb-plane form: every sweep is the matrix-core one
+    return sweep_queries(H->db.p, limbs, H->s.num_per, 2 * H->dim0_shard, qs, acc, n, g_log, st);
 }
 // one query's sweep (all stages, or one stage of a pipelined sweep: packed image only) of the image H holds, in whichever form it is in, with S's
 // query records into S's accumulators on S's stream (H = S's own holder, or another instance of the database: run_query_instances)
@@ -334,37 +347,31 @@ int sweep_with(spiral_gpu_server* S, const spiral_gpu_server* H, int stage) {
 }
 int sweep_one(spiral_gpu_server* S, int stage) { return sweep_with(S, holder_of(S), stage); }
 
-// The limb-plane image of the database H holds for a batched sweep of n queries on the matrix cores, or nullptr when that sweep does not apply
-// (S's threshold, geometry) -- then *rc stays 0 -- or could not be built (*rc = -1).  Built once per database load by the image's holder H, on S's
-// stream; never call this inside a capture.
-const uint64_t* limb_image(spiral_gpu_server* S, spiral_gpu_server* H, uint32_t n, int* rc) {
-    *rc = 0;
-    if (H->db_format == SPIRAL_GPU_DB_LIMBS) return H->db.p;  // (whatever the threshold says: there is no other image to sweep)
-    if (S->sweep_mfma_min == 0 || n < S->sweep_mfma_min || !sweep_mfma_ok(H->s.num_per, 2 * H->dim0_shard)) return nullptr;
+// The limb-plane image of the database H holds for a batched sweep of n queries on the matrix cores into *out, or nullptr when that sweep does not apply
+// (S's threshold, geometry); fails when it could not be built.  Built once per database load by the image's holder H, on S's stream; never call this
+// inside a capture.
+int limb_image(spiral_gpu_server* S, spiral_gpu_server* H, uint32_t n, const uint64_t** out) {
+    *out = nullptr;
+    if (H->db_format == SPIRAL_GPU_DB_LIMBS) return *out = H->db.p, 0;  // (whatever the threshold says: there is no other image to sweep)
+    if (S->sweep_mfma_min == 0 || n < S->sweep_mfma_min || !sweep_mfma_ok(H->s.num_per, 2 * H->dim0_shard)) return 0;
     if (options().one_image) {  // the one image changes form, in place
-        *rc = srv_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream);
-        return *rc ? nullptr : H->db.p;
+        if (srv_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+        return *out = H->db.p, 0;
     }
-    if (H->limbs_valid) return H->db_limbs.p;
-    if (H->limbs_refused) return nullptr;
+    if (H->limbs_valid) return *out = H->db_limbs.p, 0;
+    if (H->limbs_refused) return 0;
     if (!H->db_limbs.p && H->db_limbs.alloc(H->db.words)) {
         // the second image does not fit beside the first (databases beyond ~120 GiB on one device): the batch sweeps in passes of two on the vector ALU
         fprintf(stderr, "spiral_gpu: no memory for the limb-plane image of the database (%zu MiB): batched sweeps stay on the vector ALU\n", (size_t)(H->db.words * 8 >> 20));
         (void)hipGetLastError();
         H->limbs_refused = true;
-        return nullptr;
+        return 0;
     }
-    if (hipDeviceSynchronize() != hipSuccess) {  // whatever wrote the packed image, on whichever stream
-        *rc = fail("hipDeviceSynchronize failed");
-        return nullptr;
-    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever wrote the packed image, on whichever stream
     launch_db_limb_planes(H->db.p, H->db_limbs.p, H->s.num_per, 2 * H->dim0_shard, S->stream);
-    if (hipStreamSynchronize(S->stream) != hipSuccess) {
-        *rc = fail("building the limb-plane image failed");
-        return nullptr;
-    }
+    if (hipStreamSynchronize(S->stream) != hipSuccess) return fail("building the limb-plane image failed");
     H->limbs_valid = true;
-    return H->db_limbs.p;
+    return *out = H->db_limbs.p, 0;
 }
 
 // the fold needs the keys the forked conversion produces
@@ -374,6 +381,95 @@ int srv_join_side(spiral_gpu_server* S) {
         S->side_pending = false;
     }
     return 0;
+}
+
+// ---- calls that carry the queries of several servers (lanes): an owner and its lanes (create_lane / share_db) ----------------------------------------
+// What such a call needs of its lanes beyond sweeping one image, none listed twice (check_lanes)
+enum LaneNeeds : uint32_t {
+    NEED_QUERY = 1,     // each has its query set
+    NEED_DB = 2,        // each has a database
+    NEED_RECORDS = 4,   // each has converted its query (the sweep's records are enqueued)
+    SHARDED = 8,        // the same fold ranks and expansion shard (a batch of a sharded answer), else neither and their own accumulators
+    NO_CAPTURE = 16,    // no lane's stream is capturing
+    SWEEP_ONLY = 32,    // they share the sweep only (first_dim_batch): the image's layout must agree, not parameters or schedules
+    SHARD_LANES = SHARDED | NO_CAPTURE,
+};
+
+// Checks the lanes servers[0 .. n) of one call -- before anything is dereferenced the list (1 .. kMaxLanes servers, none null), then each lane against
+// servers[0] -- and fills their arena offsets.  Unless SWEEP_ONLY: the same parameters, device and shard, public parameters set, the default schedule.
+int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, uint32_t needs, Lanes* lanes) {
+    if (!servers || n == 0) return fail("%s: no servers", what);
+    if (n > kMaxLanes) return fail("%s: at most %u clients per batch", what, kMaxLanes);
+    for (uint32_t b = 0; b < n; b++)
+        if (!servers[b]) return fail("%s: null server %u", what, b);
+    spiral_gpu_server* S = servers[0];
+    HIP_OK(hipSetDevice(S->device));
+    const bool whole = !(needs & SWEEP_ONLY), sharded = needs & SHARDED;
+    lanes->n = n;
+    for (uint32_t b = 0; b < n; b++) {
+        spiral_gpu_server* L = servers[b];
+        if (whole && (((needs & NEED_QUERY) && !L->have_query) || !L->have_pp)) return fail("%s: server %u needs its query and public parameters set first", what, b);
+        if ((needs & NEED_DB) && !L->have_db) return fail("%s: server %u has no database", what, b);
+        if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has not converted its query (run_pre first)", what, b);
+        if (L->device != S->device || L->dim0_shard != S->dim0_shard || L->s.num_per != S->s.num_per ||
+            (whole && (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->j0 != S->j0 || L->j1 != S->j1 || L->cv.words != S->cv.words)))
+            return fail("%s: server %u differs from server 0 in parameters, device or shard", what, b);
+        if (L->db.p != S->db.p) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
+        if ((sharded || !whole) && L->fold_g_log != S->fold_g_log)
+            return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
+        if (sharded && (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank))
+            return fail("%s: server %u has another expansion shard than server 0", what, b);
+        if (whole && !sharded && (L->acc != L->acc_own.p || L->fold_g_log || L->ex_shard.g_log))
+            return fail("%s: server %u has an external accumulator, fold ranks or a sharded expansion set", what, b);
+        if (L->sweep_k_log || (whole && (L->keep_cts || L->overlap || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain)))
+            return fail("%s: server %u has keep_cts, a split or staged schedule or other fold options set", what, b);
+        for (uint32_t c = 0; c < b; c++)
+            if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (needs & NO_CAPTURE) HIP_OK(hipStreamIsCapturing(L->stream, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
+        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
+    }
+    return 0;
+}
+
+// the lanes' uploads (and whatever else their streams still hold) come before the sequence on servers[0]'s stream, and what follows on their streams
+// after it.  (Lanes on the sequence's own stream are ordered by it: the cheapest arrangement, each other stream costs ~20 us per batch.)
+int lanes_join(spiral_gpu_server* const* servers, uint32_t n) {
+    spiral_gpu_server* S = servers[0];
+    for (uint32_t b = 1; b < n; b++) {
+        if (servers[b]->stream == S->stream) continue;
+        HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
+        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev_batch, 0));
+    }
+    return 0;
+}
+int lanes_release(spiral_gpu_server* const* servers, uint32_t n) {
+    spiral_gpu_server* S = servers[0];
+    bool other = false;
+    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
+    if (other) HIP_OK(hipEventRecord(S->ev_batch, S->stream));
+    for (uint32_t b = 1; b < n; b++)
+        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev_batch, 0));
+    return 0;
+}
+
+// what a sweep or fold of servers[0 .. n) leaves: their accumulators or raw buffers overwritten (S->raw no longer the lift of S->acc)
+void mark_raw_stale(spiral_gpu_server* const* servers, uint32_t n) {
+    for (uint32_t b = 0; b < n; b++) servers[b]->raw_from_acc = false;
+}
+// ... and converting their queries before it: their records enqueued
+void mark_swept(spiral_gpu_server* const* servers, uint32_t n) {
+    for (uint32_t b = 0; b < n; b++) servers[b]->have_records = true;
+    mark_raw_stale(servers, n);
+}
+
+// each server's own query records and accumulators, as sweep_queries takes them
+void server_records(spiral_gpu_server* const* servers, uint32_t n, const uint32_t** qs, uint64_t** acc) {
+    for (uint32_t b = 0; b < n; b++) {
+        qs[b] = (const uint32_t*)servers[b]->qs.p;
+        acc[b] = servers[b]->acc;
+    }
 }
 
 int upload_ref_ntt(spiral_gpu_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) { return host::upload_ref_ntt(S->stage, S->stream, host, pk, npolys); }
@@ -709,16 +805,7 @@ int spiral_gpu_multiply_queries_by_database(uint64_t* outputs, const uint64_t* r
         acc[b] = d_acc + b * num_per * 6 * kN;
         launch_qs_from_reoriented(d_re + b * (size_t)kN * dim0 * 8, (uint32_t*)qs[b], (uint32_t)(2 * dim0), 0);
     }
-    if (mfma) {
-        const hipError_t e = launch_sweep_mfma(d_limbs, qs, acc, (uint32_t)n, (uint32_t)num_per, (uint32_t)(2 * dim0), 0, 0);
-        if (e != hipSuccess) return fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
-    } else
-        for (size_t b0 = 0; b0 < n; b0 += 2) {
-            if (n - b0 >= 2 && sweep_batch_ok((uint32_t)num_per, (uint32_t)(2 * dim0)))
-                launch_sweep_batch(d_db, qs + b0, acc + b0, 2, (uint32_t)num_per, (uint32_t)(2 * dim0), 0, 0);
-            else
-                for (size_t b = b0; b < n && b < b0 + 2; b++) launch_sweep(d_db, qs[b], acc[b], (uint32_t)num_per, (uint32_t)(2 * dim0), 0, 0);
-        }
+    if (sweep_queries(d_db, d_limbs, (uint32_t)num_per, (uint32_t)(2 * dim0), qs, acc, (uint32_t)n, 0, 0)) return -1;
     return download_pk(sc, d_acc, identity_map(), outputs, n * num_per * 6);
 }
 
@@ -1517,46 +1604,24 @@ int spiral_gpu_server_first_dim_stage(spiral_gpu_server* S, uint32_t stage) {
 // every other lane's stream is made to wait for it and it for theirs (events), so each lane's run_pre / run_post on its own stream
 // stay correctly ordered around it.  Geometries the batched kernel does not cover fall back to one sweep per lane.
 int spiral_gpu_server_first_dim_batch(spiral_gpu_server* const* servers, uint32_t n) {
-    if (!servers || n == 0) return fail("no servers");
-    for (uint32_t b = 0; b < n; b++)
-        if (!servers[b]) return fail("null server");
+    if (servers && n == 1 && servers[0]) return spiral_gpu_server_first_dim(servers[0]);
+    Lanes lanes;
+    if (check_lanes(servers, n, "first_dim_batch", NEED_DB | NEED_RECORDS | SWEEP_ONLY, &lanes)) return -1;  // a failure leaves no lane swept
     spiral_gpu_server* S0 = servers[0];
-    if (n == 1) return spiral_gpu_server_first_dim(S0);
-    if (n > kMaxLanes) return fail("at most %u queries per batched sweep", kMaxLanes);
-    HIP_OK(hipSetDevice(S0->device));
-    if (!S0->have_db) return fail("no database loaded");
     const uint32_t* qs[kMaxLanes];
     uint64_t* acc[kMaxLanes];
-    for (uint32_t b = 0; b < n; b++) {  // every lane is validated before anything is launched: a failure leaves no lane swept
-        spiral_gpu_server* S = servers[b];
-        if (!S->have_db) return fail("first_dim_batch: server %u has no database", b);
-        if (!S->have_records) return fail("first_dim_batch: server %u has not converted its query (run_pre / convert first)", b);
-        if (S->db.p != S0->db.p || S->device != S0->device || S->dim0_shard != S0->dim0_shard || S->s.num_per != S0->s.num_per || S->fold_g_log != S0->fold_g_log || S->sweep_k_log != 0)
-            return fail("first_dim_batch: server %u does not sweep the same database image with the same layout as server 0", b);
-        for (uint32_t c = 0; c < b; c++)
-            if (servers[c] == S) return fail("first_dim_batch: server %u listed twice", b);
-        qs[b] = (const uint32_t*)S->qs.p;
-        acc[b] = S->acc;
-    }
-    int rc = 0;
-    const uint64_t* limbs = limb_image(S0, holder_of(S0), n, &rc);
-    if (rc) return rc;
+    server_records(servers, n, qs, acc);
+    const uint64_t* limbs;
+    if (limb_image(S0, holder_of(S0), n, &limbs)) return -1;
     if (!limbs && !sweep_batch_ok(S0->s.num_per, 2 * S0->dim0_shard)) {  // (a packed image: limb planes always come back as `limbs`)
         for (uint32_t b = 0; b < n; b++)
             if (spiral_gpu_server_first_dim(servers[b])) return -1;
         return 0;
     }
-    for (uint32_t b = 1; b < n; b++) {  // the lanes' records must be complete
-        if (servers[b]->stream == S0->stream) continue;  // (lanes on the batch's own stream are ordered by it)
-        HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
-        HIP_OK(hipStreamWaitEvent(S0->stream, servers[b]->ev_batch, 0));
-    }
-    if (sweep_queries(holder_of(S0), limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
-    for (uint32_t b = 0; b < n; b++) servers[b]->raw_from_acc = false;
-    HIP_OK(hipEventRecord(S0->ev_batch, S0->stream));
-    for (uint32_t b = 1; b < n; b++)
-        if (servers[b]->stream != S0->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S0->ev_batch, 0));
-    return 0;
+    if (lanes_join(servers, n)) return -1;  // the lanes' records must be complete
+    if (sweep_image(holder_of(S0), limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
+    mark_raw_stale(servers, n);
+    return lanes_release(servers, n);
 }
 
 int spiral_gpu_server_lift(spiral_gpu_server* S, int reduce_first) {
@@ -1814,12 +1879,25 @@ int run_graph(spiral_gpu_server* S, GraphId id, hipStream_t st, GraphKey key, F 
     return 0;
 }
 
-// what converting and sweeping the queries of servers[0 .. n) leaves: their records enqueued, their accumulators overwritten (S->raw no longer their lift)
-void mark_swept(spiral_gpu_server* const* servers, uint32_t n) {
-    for (uint32_t b = 0; b < n; b++) {
-        servers[b]->have_records = true;
-        servers[b]->raw_from_acc = false;
-    }
+// The key of a lane call's capture: the lane count, the limb-plane image its sweep reads (or null), each lane's arena (every pointer the capture holds is
+// one of them plus a fixed offset) and the caller's buffers and flags `words`
+using Key = std::vector<uint64_t>;
+int lane_key(Key* key, spiral_gpu_server* const* servers, uint32_t n, const uint64_t* limbs, std::initializer_list<uint64_t> words) {
+    *key = {n, word(limbs)};
+    for (uint32_t b = 0; b < n; b++) key->push_back(word(servers[b]->w_left.p));
+    for (uint64_t w : words) key->push_back(w);
+    return 0;
+}
+
+// A lane call's sequence on servers[0]'s stream: the other lanes' streams joined into it, then prepare(&key) -- host work that must not run inside a
+// capture (limb_image) and the key -- then body() as servers[0]'s graph `id` (run_graph), then the lanes' streams released
+template <class P, class F>
+int run_lanes(spiral_gpu_server* const* servers, uint32_t n, GraphId id, P prepare, F body) {
+    if (lanes_join(servers, n)) return -1;
+    Key key;
+    if (int rc = prepare(&key)) return rc;
+    if (int rc = run_graph(servers[0], id, servers[0]->stream, key, body)) return rc;
+    return lanes_release(servers, n);
 }
 }  // namespace
 
@@ -1885,64 +1963,26 @@ int spiral_gpu_server_run_query(spiral_gpu_server* S) {
 namespace {
 // The pieces run_query_batch, run_query_instances and run_query_batch_instances share.
 
-// Checks the query lanes servers[0 .. n) of one launch sequence -- an owner and its lanes, same parameters, device and shard, the default schedule,
-// no server twice -- and fills their arena offsets.  need_db: each must have a database (run_query_batch sweeps servers[0]'s image).
-int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, bool need_query, bool need_db, Lanes* lanes) {
-    spiral_gpu_server* S = servers[0];
-    lanes->n = n;
-    for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_server* L = servers[b];
-        if ((need_query && !L->have_query) || !L->have_pp) return fail("%s: server %u needs its query and public parameters set first", what, b);
-        if (need_db && !L->have_db) return fail("%s: server %u has no database", what, b);
-        if (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->device != S->device || L->j0 != S->j0 || L->dim0_shard != S->dim0_shard || L->cv.words != S->cv.words)
-            return fail("%s: server %u differs from server 0 in parameters, device or shard", what, b);
-        if (L->db.p != S->db.p) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
-        if (L->acc != L->acc_own.p || L->keep_cts || L->overlap || L->fold_g_log || L->sweep_k_log || L->ex_shard.g_log || L->side_pending || L->fold_pair != S->fold_pair ||
-            L->fold_chain != S->fold_chain)
-            return fail("%s: server %u has an external accumulator, keep_cts, a split / sharded / staged schedule or other fold options set", what, b);
-        for (uint32_t c = 0; c < b; c++)
-            if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
-        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
-    }
-    return 0;
-}
-
 // Checks the instances of an item query answered by S's query (same device, shard, database geometry and plaintext modulus, each with a database)
-// and appends each one's image and epoch to the graph key
-int check_instances(const spiral_gpu_server* S, spiral_gpu_server* const* instances, uint32_t n, const char* what, std::vector<uint64_t>* key) {
+int check_instances(const spiral_gpu_server* S, spiral_gpu_server* const* instances, uint32_t n, const char* what) {
     for (uint32_t k = 0; k < n; k++) {
         const spiral_gpu_server* I = instances[k];
         if (!I) return fail("null instance %u", k);
-        const spiral_gpu_server* H = holder_of(I);
         if (!I->have_db) return fail("%s: instance %u has no database", what, k);
         if (I->device != S->device || I->j0 != S->j0 || I->dim0_shard != S->dim0_shard || I->p.nu1 != S->p.nu1 || I->p.nu2 != S->p.nu2 || I->p.p_db != S->p.p_db ||
             I->p.direct_upload != S->p.direct_upload)
             return fail("%s: instance %u differs from the query's server in device, shard, database geometry or plaintext modulus", what, k);
-        key->push_back((uint64_t)(uintptr_t)I->db.p);
-        key->push_back(H->db_epoch);
     }
     return 0;
 }
 
-// the lanes' uploads (and whatever else their streams still hold) come before the sequence on servers[0]'s stream, and what follows on their streams
-// after it.  (Lanes on the sequence's own stream are ordered by it: the cheapest arrangement, each other stream costs ~20 us per batch.)
-int lanes_join(spiral_gpu_server* const* servers, uint32_t n) {
-    spiral_gpu_server* S = servers[0];
-    for (uint32_t b = 1; b < n; b++) {
-        if (servers[b]->stream == S->stream) continue;
-        HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
-        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev_batch, 0));
+// appends to a capture's key what it bakes in of each instance: its image, the limb-plane image the sweep reads (limbs[k], when given), and the form the
+// image is in (the holder's epoch covers the form; update_db_items keeps it: captured graphs replay across updates)
+void key_instances(Key* key, spiral_gpu_server* const* instances, uint32_t n, const uint64_t* const* limbs) {
+    for (uint32_t k = 0; k < n; k++) {
+        const spiral_gpu_server* H = holder_of(instances[k]);
+        for (uint64_t w : {word(H->db.p), word(limbs ? limbs[k] : nullptr), H->db_epoch, (uint64_t)H->db_format}) key->push_back(w);
     }
-    return 0;
-}
-int lanes_release(spiral_gpu_server* const* servers, uint32_t n) {
-    spiral_gpu_server* S = servers[0];
-    bool other = false;
-    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
-    if (other) HIP_OK(hipEventRecord(S->ev_batch, S->stream));
-    for (uint32_t b = 1; b < n; b++)
-        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev_batch, 0));
-    return 0;
 }
 
 // Expansion and conversion of the queries of `lanes` (lane 0 = S): one query is expand_convert, a batch carries every lane in each launch.
@@ -1991,7 +2031,7 @@ int item_rounds(spiral_gpu_server* S, const Lanes& lanes, spiral_gpu_server* con
     lane_records(S, lanes, qs, acc);
     const size_t rw = 6 * kN, ww = wire_bytes(&S->p, 2) / 8;  // (whole words: 2048 values per polynomial)
     for (uint32_t k = 0; k < n_inst; k++) {
-        if (sweep_queries(holder_of(instances[k]), limbs ? limbs[k] : nullptr, qs, acc, lanes.n, 0, S->stream)) return -1;
+        if (sweep_image(holder_of(instances[k]), limbs ? limbs[k] : nullptr, qs, acc, lanes.n, 0, S->stream)) return -1;
         if (o.via_resp) {
             if (run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true)) return -1;
             HIP_OK(hipMemcpyAsync(o.resp + k * rw, S->resp.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
@@ -2010,6 +2050,33 @@ int item_rounds(spiral_gpu_server* S, const Lanes& lanes, spiral_gpu_server* con
     }
     return 0;
 }
+
+// The host tail of the answer_* calls of item queries: device scratch for each output the caller wants (host != null), run(device pointers) between
+// two events on S's stream, the outputs downloaded; total_us (optional): the device time between the events
+struct HostOut {
+    void* host;
+    size_t bytes;
+};
+template <class F>
+int answer_on_host(spiral_gpu_server* S, HostOut a, HostOut b, double* total_us, F run) {
+    Scratch sc;
+    const HostOut out[2] = {a, b};
+    void* d[2] = {};
+    for (int i = 0; i < 2; i++)
+        if (out[i].host && !(d[i] = sc.get((out[i].bytes + 7) / 8))) return fail("device allocation failed");
+    HIP_OK(hipEventRecord(S->ev[0], S->stream));
+    if (run(d[0], d[1])) return -1;
+    HIP_OK(hipEventRecord(S->ev[1], S->stream));
+    for (int i = 0; i < 2; i++)
+        if (out[i].host) HIP_OK(hipMemcpyAsync(out[i].host, d[i], out[i].bytes, hipMemcpyDeviceToHost, S->stream));
+    HIP_OK(hipStreamSynchronize(S->stream));
+    if (total_us) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
+        *total_us = ms * 1e3;
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -2022,34 +2089,26 @@ extern "C" {
 // The sequence runs on servers[0]'s stream (captured once per lane set into a hipGraph when servers[0] has use_graphs on); the other
 // lanes' streams are ordered before and after it with events, as in first_dim_batch.
 int spiral_gpu_server_run_query_batch(spiral_gpu_server* const* servers, uint32_t n) {
-    if (!servers || n == 0) return fail("no servers");
-    for (uint32_t b = 0; b < n; b++)
-        if (!servers[b]) return fail("null server");
-    spiral_gpu_server* S = servers[0];
-    if (n == 1) return spiral_gpu_server_run_query(S);
-    if (n > kMaxLanes) return fail("at most %u queries per batch", kMaxLanes);
-    HIP_OK(hipSetDevice(S->device));
+    if (servers && n == 1 && servers[0]) return spiral_gpu_server_run_query(servers[0]);
     Lanes lanes;
-    if (check_lanes(servers, n, "run_query_batch", true, true, &lanes)) return -1;  // every lane is validated before anything is launched
-    if (lanes_join(servers, n)) return -1;
-    int rc_l = 0;
-    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc_l);  // (not inside the capture below: it may build the image)
-    if (rc_l) return rc_l;
-    auto body = [&]() {
-        if (convert_lanes(S, lanes)) return -1;
-        const uint32_t* qs[kMaxLanes];
-        uint64_t* acc[kMaxLanes];
-        lane_records(S, lanes, qs, acc);
-        if (sweep_queries(holder_of(S), limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
-        return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true, nullptr, lanes);
-    };
-    // the capture bakes in the lanes' arenas (every pointer it holds is one of them plus a fixed offset), the image the sweep reads and its kernel
-    // (limbs or not)
-    uint64_t key[2 + kMaxLanes] = {n, word(limbs)};
-    for (uint32_t b = 0; b < n; b++) key[2 + b] = word(servers[b]->w_left.p);
-    if (int rc = run_graph(S, G_BATCH, S->stream, GraphKey(key, 2 + n), body)) return rc;
-    mark_swept(servers, n);
-    return lanes_release(servers, n);
+    if (check_lanes(servers, n, "run_query_batch", NEED_QUERY | NEED_DB, &lanes)) return -1;  // every lane is validated before anything is launched
+    spiral_gpu_server* S = servers[0];
+    const uint64_t* limbs = nullptr;
+    const int rc = run_lanes(
+        servers, n, G_BATCH,
+        [&](Key* key) {  // (limb_image: not inside the capture, it may build the image)
+            return limb_image(S, holder_of(S), n, &limbs) ? -1 : lane_key(key, servers, n, limbs, {});
+        },
+        [&]() {
+            if (convert_lanes(S, lanes)) return -1;
+            const uint32_t* qs[kMaxLanes];
+            uint64_t* acc[kMaxLanes];
+            lane_records(S, lanes, qs, acc);
+            if (sweep_image(holder_of(S), limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
+            return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true, nullptr, lanes);
+        });
+    if (!rc) mark_swept(servers, n);
+    return rc;
 }
 
 // One query against n INSTANCES of the database.  An item larger than one plaintext (configs[3]: 100 KB items, 15 360-byte plaintexts) is
@@ -2062,13 +2121,11 @@ int spiral_gpu_server_run_query_batch(spiral_gpu_server* const* servers, uint32_
 // stream, sweeps back to back; a hipGraph per (instance set, output buffers) when S has use_graphs on.
 int spiral_gpu_server_run_query_instances(spiral_gpu_server* S, spiral_gpu_server* const* instances, uint32_t n, int pre, void* responses, void* finals) {
     if (!S || !instances || n == 0 || !responses) return fail("null argument");
-    HIP_OK(hipSetDevice(S->device));
-    if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
-    if (!pre && !S->have_records) return fail("run_query_instances: the query has not been converted (run_pre first, or pass pre = 1)");
-    if (S->overlap || S->fold_g_log || S->sweep_k_log || S->ex_shard.g_log || S->keep_cts || S->acc != S->acc_own.p)
-        return fail("run_query_instances needs the default schedule on the query's server (own accumulators, no split / sharded / staged options)");
-    std::vector<uint64_t> key{(uint64_t)(uintptr_t)responses, (uint64_t)(uintptr_t)finals, (uint64_t)(pre != 0)};
-    if (check_instances(S, instances, n, "run_query_instances", &key)) return -1;
+    Lanes one;  // (S alone, on the default schedule)
+    if (check_lanes(&S, 1, "run_query_instances", NEED_QUERY | (pre ? 0 : NEED_RECORDS), &one)) return -1;
+    if (check_instances(S, instances, n, "run_query_instances")) return -1;
+    std::vector<uint64_t> key{word(responses), word(finals), pre != 0};
+    key_instances(&key, instances, n, nullptr);
     if (srv_join_side(S)) return -1;
     ItemOut o;
     o.resp = (uint64_t*)responses;
@@ -2079,8 +2136,10 @@ int spiral_gpu_server_run_query_instances(spiral_gpu_server* S, spiral_gpu_serve
         return item_rounds(S, Lanes{}, instances, nullptr, n, o);
     };
     if (int rc = run_graph(S, G_INSTANCES, S->stream, key, body)) return rc;
-    if (pre) S->have_records = true;
-    S->raw_from_acc = false;
+    if (pre)
+        mark_swept(&S, 1);
+    else
+        mark_raw_stale(&S, 1);
     return 0;
 }
 
@@ -2091,22 +2150,9 @@ int spiral_gpu_server_answer_instances(spiral_gpu_server* S, spiral_gpu_server* 
     if (!S || !instances || n == 0 || !query || !responses) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     if (spiral_gpu_server_set_query(S, query)) return -1;
-    Scratch sc;
-    uint64_t* d_resp = sc.get((size_t)n * 6 * kN);
-    uint64_t* d_fin = finals ? sc.get((size_t)n * 6 * kN) : nullptr;
-    if (!d_resp || (finals && !d_fin)) return fail("device allocation failed");
-    HIP_OK(hipEventRecord(S->ev[0], S->stream));
-    if (spiral_gpu_server_run_query_instances(S, instances, n, 1, d_resp, d_fin)) return -1;
-    HIP_OK(hipEventRecord(S->ev[1], S->stream));
-    HIP_OK(hipMemcpyAsync(responses, d_resp, (size_t)n * 6 * kPolyBytes, hipMemcpyDeviceToHost, S->stream));
-    if (finals) HIP_OK(hipMemcpyAsync(finals, d_fin, (size_t)n * 6 * kPolyBytes, hipMemcpyDeviceToHost, S->stream));
-    HIP_OK(hipStreamSynchronize(S->stream));
-    if (total_us) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
-        *total_us = ms * 1e3;
-    }
-    return 0;
+    const size_t bytes = (size_t)n * 6 * kPolyBytes;
+    return answer_on_host(S, {responses, bytes}, {finals, bytes}, total_us,
+                          [&](void* d_resp, void* d_fin) { return spiral_gpu_server_run_query_instances(S, instances, n, 1, d_resp, d_fin); });
 }
 
 }  // extern "C"
@@ -2114,22 +2160,11 @@ int spiral_gpu_server_answer_instances(spiral_gpu_server* S, spiral_gpu_server* 
 namespace {
 // every argument check of run_query_batch_instances / answer_batch_instances, before anything is uploaded or launched
 int check_batch_instances(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_server* const* instances, uint32_t n_inst, int pre, bool need_query,
-                          Lanes* lanes, std::vector<uint64_t>* key) {
+                          Lanes* lanes) {
     const char* what = "run_query_batch_instances";
-    if (!servers || n == 0 || !instances || n_inst == 0) return fail("%s: no servers or no instances", what);
-    if (n > kMaxLanes) return fail("%s: at most %u clients per batch", what, kMaxLanes);
-    for (uint32_t b = 0; b < n; b++)
-        if (!servers[b]) return fail("null server");
-    spiral_gpu_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
-    if (check_lanes(servers, n, what, need_query, false, lanes)) return -1;
-    for (uint32_t b = 0; b < n; b++) {
-        if (!pre && !servers[b]->have_records) return fail("%s: server %u has not converted its query (run_pre first, or pass pre = 1)", what, b);
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_OK(hipStreamIsCapturing(servers[b]->stream, &cs));
-        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
-    }
-    return check_instances(S, instances, n_inst, what, key);
+    if (!instances || n_inst == 0) return fail("%s: no servers or no instances", what);
+    if (check_lanes(servers, n, what, (need_query ? NEED_QUERY : 0) | (pre ? 0 : NEED_RECORDS) | NO_CAPTURE, lanes)) return -1;
+    return check_instances(servers[0], instances, n_inst, what);
 }
 }  // namespace
 
@@ -2142,76 +2177,51 @@ extern "C" {
 int spiral_gpu_server_run_query_batch_instances(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_server* const* instances, uint32_t n_inst, int pre,
                                                 void* responses, void* finals, void* wire) {
     Lanes lanes;
-    std::vector<uint64_t> checked;
     if (!responses && !wire) return fail("run_query_batch_instances: no output (responses or wire)");
-    if (check_batch_instances(servers, n, instances, n_inst, pre, true, &lanes, &checked)) return -1;
+    if (check_batch_instances(servers, n, instances, n_inst, pre, true, &lanes)) return -1;
     spiral_gpu_server* S = servers[0];
     if (srv_join_side(S)) return -1;
-    if (lanes_join(servers, n)) return -1;
-    // each instance image in the form the sweep of B queries reads, converted in place on first use (never inside the capture)
     std::vector<const uint64_t*> limbs(n_inst);
-    for (uint32_t k = 0; k < n_inst; k++) {
-        int rc = 0;
-        spiral_gpu_server* H = holder_of(instances[k]);
-        limbs[k] = limb_image(S, H, n, &rc);
-        if (rc) return rc;
-    }
-    // the capture bakes in the clients' arenas, the outputs, and each instance's image, the form it is in and the sweep kernel that reads it (the
-    // holder's epoch covers the form; update_db_items keeps it: captured graphs replay across updates)
-    std::vector<uint64_t> key{(uint64_t)n, (uint64_t)(pre != 0), (uint64_t)(uintptr_t)responses, (uint64_t)(uintptr_t)finals, (uint64_t)(uintptr_t)wire};
-    for (uint32_t b = 0; b < n; b++) key.push_back((uint64_t)(uintptr_t)servers[b]->w_left.p);
-    for (uint32_t k = 0; k < n_inst; k++) {
-        const spiral_gpu_server* H = holder_of(instances[k]);
-        key.push_back((uint64_t)(uintptr_t)H->db.p);
-        key.push_back((uint64_t)(uintptr_t)limbs[k]);
-        key.push_back(H->db_epoch);
-        key.push_back(H->db_format);
-    }
     ItemOut o;
     o.resp = (uint64_t*)responses;
     o.fin = (uint64_t*)finals;
     o.wire = (uint64_t*)wire;
-    auto body = [&]() {
-        if (pre && convert_lanes(S, lanes)) return -1;
-        return item_rounds(S, lanes, instances, limbs.data(), n_inst, o);
-    };
-    if (int rc = run_graph(S, G_BATCH_INSTANCES, S->stream, key, body)) return rc;
-    for (uint32_t b = 0; b < n; b++) {
-        if (pre) servers[b]->have_records = true;
-        servers[b]->raw_from_acc = false;
-    }
-    return lanes_release(servers, n);
+    const int rc = run_lanes(
+        servers, n, G_BATCH_INSTANCES,
+        [&](Key* key) {
+            // each instance image in the form the sweep of B queries reads, converted in place on first use (never inside the capture)
+            for (uint32_t k = 0; k < n_inst; k++)
+                if (limb_image(S, holder_of(instances[k]), n, &limbs[k])) return -1;
+            lane_key(key, servers, n, nullptr, {word(responses), word(finals), word(wire), pre != 0});
+            key_instances(key, instances, n_inst, limbs.data());
+            return 0;
+        },
+        [&]() {
+            if (pre && convert_lanes(S, lanes)) return -1;
+            return item_rounds(S, lanes, instances, limbs.data(), n_inst, o);
+        });
+    if (rc) return rc;
+    if (pre)
+        mark_swept(servers, n);
+    else
+        mark_raw_stale(servers, n);
+    return 0;
 }
 
 // the same from host buffers: upload the B queries, answer them, download the B x n_inst responses and / or wire forms; total_us: device time of the batch
 int spiral_gpu_server_answer_batch_instances(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_server* const* instances, uint32_t n_inst,
                                              const uint64_t* const* queries, uint64_t* responses, void* wire, double* total_us) {
     Lanes lanes;
-    std::vector<uint64_t> key;
     if (!queries || (!responses && !wire)) return fail("answer_batch_instances: null queries or no output (responses or wire)");
-    if (check_batch_instances(servers, n, instances, n_inst, 1, false, &lanes, &key)) return -1;
+    if (check_batch_instances(servers, n, instances, n_inst, 1, false, &lanes)) return -1;
     for (uint32_t b = 0; b < n; b++)
         if (!queries[b]) return fail("answer_batch_instances: null query %u", b);
-    spiral_gpu_server* S = servers[0];
-    const size_t slots = (size_t)n * n_inst, wb = wire_bytes(&S->p, 2);
-    Scratch sc;
-    uint64_t* d_resp = responses ? sc.get(slots * 6 * kN) : nullptr;
-    uint64_t* d_wire = wire ? sc.get(slots * wb / 8) : nullptr;
-    if ((responses && !d_resp) || (wire && !d_wire)) return fail("device allocation failed");
     for (uint32_t b = 0; b < n; b++)
         if (spiral_gpu_server_set_query(servers[b], queries[b])) return -1;
-    HIP_OK(hipEventRecord(S->ev[0], S->stream));
-    if (spiral_gpu_server_run_query_batch_instances(servers, n, instances, n_inst, 1, d_resp, nullptr, d_wire)) return -1;
-    HIP_OK(hipEventRecord(S->ev[1], S->stream));
-    if (responses) HIP_OK(hipMemcpyAsync(responses, d_resp, slots * 6 * kPolyBytes, hipMemcpyDeviceToHost, S->stream));
-    if (wire) HIP_OK(hipMemcpyAsync(wire, d_wire, slots * wb, hipMemcpyDeviceToHost, S->stream));
-    HIP_OK(hipStreamSynchronize(S->stream));
-    if (total_us) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
-        *total_us = ms * 1e3;
-    }
-    return 0;
+    const size_t slots = (size_t)n * n_inst;
+    return answer_on_host(servers[0], {responses, slots * 6 * kPolyBytes}, {wire, slots * wire_bytes(&servers[0]->p, 2)}, total_us, [&](void* d_resp, void* d_wire) {
+        return spiral_gpu_server_run_query_batch_instances(servers, n, instances, n_inst, 1, d_resp, nullptr, d_wire);
+    });
 }
 
 // The two halves of a distributed fold.  With use_graphs on they replay as hipGraphs too, keyed on the buffers the caller hands in (the
@@ -2329,56 +2339,6 @@ int spiral_gpu_server_run_unpack_gsw(spiral_gpu_server* S, const void* gathered)
 
 namespace {
 // ---- batches of a sharded answer (include/spiral_gpu.h: run_pre_sweep_batch ... fold_root_batch) ----------------------------------------------
-// Every check of a batch call of a sharded answer, before anything is launched: the lanes are an owner and its lanes (same parameters, device,
-// j-shard, image, fold ranks and expansion shard; the default schedule otherwise), none twice, no stream capturing.  check_lanes stays as it is:
-// run_query_batch keeps refusing every distributed setting.
-int check_shard_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, bool need_query, bool need_db, Lanes* lanes) {
-    if (!servers || n == 0) return fail("%s: no servers", what);
-    if (n > kMaxLanes) return fail("%s: at most %u clients per batch", what, kMaxLanes);
-    for (uint32_t b = 0; b < n; b++)
-        if (!servers[b]) return fail("%s: null server %u", what, b);
-    spiral_gpu_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
-    lanes->n = n;
-    for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_server* L = servers[b];
-        if ((need_query && !L->have_query) || !L->have_pp) return fail("%s: server %u needs its query and public parameters set first", what, b);
-        if (need_db && !L->have_db) return fail("%s: server %u has no database", what, b);
-        if (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->device != S->device || L->j0 != S->j0 || L->j1 != S->j1 || L->dim0_shard != S->dim0_shard ||
-            L->cv.words != S->cv.words)
-            return fail("%s: server %u differs from server 0 in parameters, device or j-shard", what, b);
-        if (L->db.p != S->db.p) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
-        if (L->fold_g_log != S->fold_g_log) return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
-        if (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank)
-            return fail("%s: server %u has another expansion shard than server 0", what, b);
-        if (L->keep_cts || L->overlap || L->sweep_k_log || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain)
-            return fail("%s: server %u has keep_cts, a split or staged schedule or other fold options set", what, b);
-        for (uint32_t c = 0; c < b; c++)
-            if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_OK(hipStreamIsCapturing(L->stream, &cs));
-        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
-        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
-    }
-    return 0;
-}
-
-// the graph key of a batch call: the lanes' arenas, the caller's buffers and the image the sweep reads
-std::vector<uint64_t> shard_key(spiral_gpu_server* const* servers, uint32_t n, std::initializer_list<const void*> bufs, const uint64_t* limbs = nullptr) {
-    std::vector<uint64_t> key{n, (uint64_t)(uintptr_t)limbs};
-    for (uint32_t b = 0; b < n; b++) key.push_back((uint64_t)(uintptr_t)servers[b]->w_left.p);
-    for (const void* p : bufs) key.push_back((uint64_t)(uintptr_t)p);
-    return key;
-}
-
-// body() as servers[0]'s graph `id` (run_graph), the lanes' streams ordered around it
-template <class F>
-int run_shard(spiral_gpu_server* const* servers, uint32_t n, GraphId id, const std::vector<uint64_t>& key, F body) {
-    if (lanes_join(servers, n)) return -1;
-    if (int rc = run_graph(servers[0], id, servers[0]->stream, key, body)) return rc;
-    return lanes_release(servers, n);
-}
-
 // The sweep of every lane's query over this rank's shard into the caller's rank-major buffer acc = [rank g][lane b][k < L], L = num_per / G: lane b's
 // ciphertext ii = g + G k at (g n + b) L + k.  One pass on the matrix cores where the image is in limb-plane form, else passes of two on the vector
 // ALU; a geometry neither kernel covers sweeps each query into its own accumulators and copies its G chunks into place (one strided copy).
@@ -2395,26 +2355,13 @@ int sweep_rank_major(spiral_gpu_server* S, const Lanes& lanes, const uint64_t* l
         own[b] = S->acc_own.p + lanes.off[b];  // (scratch of the fallback: whatever set_acc says, the lane's own buffer)
     }
     if (n == 1 || G == 1)  // [lane][num_per] or one query's own layout: the grouping by ii mod G of the one-query sweep
-        return sweep_queries(H, limbs, qs, acc, n, S->fold_g_log, S->stream);
-    const uint32_t g_extra = (n - 1) * L;
-    if (!limbs && H->db_format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;
-    if (limbs) {
-        const hipError_t e = launch_sweep_mfma(limbs, qs, acc, n, np, jm, S->fold_g_log, S->stream, 0, g_extra);
-        return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
-    }
-    const uint32_t step = sweep_batch_ok(np, jm) ? kSweepMaxBatch : 1;
-    for (uint32_t b0 = 0; b0 < n; b0 += step) {
-        if (n - b0 >= 2 && step == 2) {
-            launch_sweep_batch(H->db.p, qs + b0, acc + b0, 2, np, jm, S->fold_g_log, S->stream, g_extra);
-            continue;
-        }
-        for (uint32_t b = b0; b < std::min(n, b0 + step); b++) {
-            launch_sweep(H->db.p, qs[b], own[b], np, jm, S->fold_g_log, S->stream);
-            HIP_OK(hipMemcpy2DAsync(acc[b], n * chunk * sizeof(uint64_t), own[b], chunk * sizeof(uint64_t), chunk * sizeof(uint64_t), G, hipMemcpyDeviceToDevice,
-                                    S->stream));
-        }
-    }
-    return 0;
+        return sweep_image(H, limbs, qs, acc, n, S->fold_g_log, S->stream);
+    return sweep_queries(H->db.p, limbs, np, jm, qs, acc, n, S->fold_g_log, S->stream, 0, (n - 1) * L, [&](uint32_t b) {
+        launch_sweep(H->db.p, qs[b], own[b], np, jm, S->fold_g_log, S->stream);
+        HIP_OK(hipMemcpy2DAsync(acc[b], n * chunk * sizeof(uint64_t), own[b], chunk * sizeof(uint64_t), chunk * sizeof(uint64_t), G, hipMemcpyDeviceToDevice,
+                                S->stream));
+        return 0;
+    });
 }
 }  // namespace
 
@@ -2423,14 +2370,13 @@ extern "C" {
 int spiral_gpu_server_run_pre_sweep_batch(spiral_gpu_server* const* servers, uint32_t n, void* acc) {
     const char* what = "run_pre_sweep_batch";
     Lanes lanes;
-    if (check_shard_lanes(servers, n, what, true, true, &lanes)) return -1;
+    if (check_lanes(servers, n, what, SHARD_LANES | NEED_QUERY | NEED_DB, &lanes)) return -1;
     if (!acc) return fail("%s: null accumulator buffer", what);
     spiral_gpu_server* S = servers[0];
     if (S->ex_shard.g_log) return fail("%s: the expansion is sharded: run_expand_pack_batch, the all-gather, then run_unpack_convert_sweep_batch", what);
-    int rc = 0;
-    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);  // (not inside a capture: it may convert the image)
-    if (rc) return rc;
-    rc = run_shard(servers, n, G_SHARD_PRE_SWEEP, shard_key(servers, n, {acc}, limbs), [&]() {
+    const uint64_t* limbs;
+    if (limb_image(S, holder_of(S), n, &limbs)) return -1;  // (not inside a capture: it may convert the image)
+    const int rc = run_lanes(servers, n, G_SHARD_PRE_SWEEP, [&](Key* k) { return lane_key(k, servers, n, limbs, {word(acc)}); }, [&]() {
         if (convert_lanes(S, lanes)) return -1;
         return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
     });
@@ -2441,10 +2387,10 @@ int spiral_gpu_server_run_pre_sweep_batch(spiral_gpu_server* const* servers, uin
 int spiral_gpu_server_run_expand_pack_batch(spiral_gpu_server* const* servers, uint32_t n, void* bits_out) {
     const char* what = "run_expand_pack_batch";
     Lanes lanes;
-    if (check_shard_lanes(servers, n, what, true, false, &lanes)) return -1;
+    if (check_lanes(servers, n, what, SHARD_LANES | NEED_QUERY, &lanes)) return -1;
     if (!bits_out) return fail("%s: null output buffer", what);
     spiral_gpu_server* S = servers[0];
-    return run_shard(servers, n, G_SHARD_EXPAND_PACK, shard_key(servers, n, {bits_out}), [&]() {
+    return run_lanes(servers, n, G_SHARD_EXPAND_PACK, [&](Key* k) { return lane_key(k, servers, n, nullptr, {word(bits_out)}); }, [&]() {
         if (expand_lanes(S, lanes)) return -1;
         launch_gsw_bits_pack_lanes(S->cv.p, (uint64_t*)bits_out, S->ex_shard.rank, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
         return 0;
@@ -2454,13 +2400,12 @@ int spiral_gpu_server_run_expand_pack_batch(spiral_gpu_server* const* servers, u
 int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server* const* servers, uint32_t n, const void* gathered_bits, void* acc) {
     const char* what = "run_unpack_convert_sweep_batch";
     Lanes lanes;
-    if (check_shard_lanes(servers, n, what, true, true, &lanes)) return -1;
+    if (check_lanes(servers, n, what, SHARD_LANES | NEED_QUERY | NEED_DB, &lanes)) return -1;
     if (!gathered_bits || !acc) return fail("%s: null buffer", what);
     spiral_gpu_server* S = servers[0];
-    int rc = 0;
-    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);
-    if (rc) return rc;
-    rc = run_shard(servers, n, G_SHARD_UNPACK_SWEEP, shard_key(servers, n, {gathered_bits, acc}, limbs), [&]() {
+    const uint64_t* limbs;
+    if (limb_image(S, holder_of(S), n, &limbs)) return -1;
+    const int rc = run_lanes(servers, n, G_SHARD_UNPACK_SWEEP, [&](Key* k) { return lane_key(k, servers, n, limbs, {word(gathered_bits), word(acc)}); }, [&]() {
         launch_gsw_bits_unpack_lanes(S->cv.p, (const uint64_t*)gathered_bits, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
         if (convert_part(S, CONV_BOTH, S->stream, false, lanes)) return -1;
         return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
@@ -2474,12 +2419,12 @@ int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server* const* s
 int spiral_gpu_server_fold_local_batch(spiral_gpu_server* const* servers, uint32_t n, const void* chunk, void* out_cts) {
     const char* what = "fold_local_batch";
     Lanes lanes;
-    if (check_shard_lanes(servers, n, what, false, false, &lanes)) return -1;
+    if (check_lanes(servers, n, what, SHARD_LANES, &lanes)) return -1;
     if (!chunk || !out_cts) return fail("%s: null buffer", what);
     spiral_gpu_server* S = servers[0];
     const uint32_t L = S->s.num_per >> S->fold_g_log;
     const size_t ctw = 6 * kN, cw = (size_t)L * ctw;
-    const int rc = run_shard(servers, n, G_SHARD_FOLD_LOCAL, shard_key(servers, n, {chunk, out_cts}), [&]() {
+    const int rc = run_lanes(servers, n, G_SHARD_FOLD_LOCAL, [&](Key* k) { return lane_key(k, servers, n, nullptr, {word(chunk), word(out_cts)}); }, [&]() {
         for (uint32_t b = 0; b < n; b++)
             HIP_OK(hipMemcpyAsync(S->acc_own.p + lanes.off[b], (const uint64_t*)chunk + b * cw, cw * sizeof(uint64_t), hipMemcpyDeviceToDevice, S->stream));
         if (run_fold_rounds(S, L, 0, S->p.nu2 - S->fold_g_log, S->acc_own.p, true, false, nullptr, lanes)) return -1;
@@ -2487,7 +2432,7 @@ int spiral_gpu_server_fold_local_batch(spiral_gpu_server* const* servers, uint32
             HIP_OK(hipMemcpyAsync((uint64_t*)out_cts + b * ctw, S->raw.p + lanes.off[b], ctw * sizeof(uint64_t), hipMemcpyDeviceToDevice, S->stream));
         return 0;
     });
-    for (uint32_t b = 0; !rc && b < n; b++) servers[b]->raw_from_acc = false;
+    if (!rc) mark_raw_stale(servers, n);
     return rc;
 }
 
@@ -2496,12 +2441,12 @@ int spiral_gpu_server_fold_local_batch(spiral_gpu_server* const* servers, uint32
 int spiral_gpu_server_fold_root_batch(spiral_gpu_server* const* servers, uint32_t n, const void* gathered_cts, void* responses, void* wire) {
     const char* what = "fold_root_batch";
     Lanes lanes;
-    if (check_shard_lanes(servers, n, what, false, false, &lanes)) return -1;
+    if (check_lanes(servers, n, what, SHARD_LANES, &lanes)) return -1;
     if (!gathered_cts) return fail("%s: null buffer", what);
     spiral_gpu_server* S = servers[0];
     const uint32_t G = 1u << S->fold_g_log;
     const size_t ctw = 6 * kN, ww = wire_bytes(&S->p, 2) / 8;
-    const int rc = run_shard(servers, n, G_SHARD_FOLD_ROOT, shard_key(servers, n, {gathered_cts, responses, wire}), [&]() {
+    const int rc = run_lanes(servers, n, G_SHARD_FOLD_ROOT, [&](Key* k) { return lane_key(k, servers, n, nullptr, {word(gathered_cts), word(responses), word(wire)}); }, [&]() {
         for (uint32_t b = 0; b < n; b++)
             HIP_OK(hipMemcpy2DAsync(S->raw.p + lanes.off[b], ctw * sizeof(uint64_t), (const uint64_t*)gathered_cts + b * ctw, n * ctw * sizeof(uint64_t),
                                     ctw * sizeof(uint64_t), G, hipMemcpyDeviceToDevice, S->stream));
@@ -2511,7 +2456,7 @@ int spiral_gpu_server_fold_root_batch(spiral_gpu_server* const* servers, uint32_
         if (wire) launch_response_wire(S->resp.p, (uint64_t*)wire, 2 * kN, S->p.qprime_bits, 4 * kN, wire_bits_rest(&S->p), S->stream, lanes, 0, (int64_t)ww);
         return 0;
     });
-    for (uint32_t b = 0; !rc && b < n; b++) servers[b]->raw_from_acc = false;
+    if (!rc) mark_raw_stale(servers, n);
     return rc;
 }
 
@@ -2707,27 +2652,20 @@ int spiral_gpu_server_time_sweep(spiral_gpu_server* S, int iters, float* avg_ms)
 }
 
 int spiral_gpu_server_time_sweep_batch(spiral_gpu_server* const* servers, uint32_t n, int iters, float* avg_ms) {
-    if (!servers || !avg_ms || iters <= 0 || n == 0 || n > kMaxLanes) return fail("bad argument");
+    if (!avg_ms || iters <= 0) return fail("time_sweep_batch: bad argument");
+    Lanes lanes;
+    if (check_lanes(servers, n, "time_sweep_batch", NEED_DB | NEED_RECORDS | SWEEP_ONLY, &lanes)) return -1;  // (first_dim_batch's lanes)
     spiral_gpu_server* S = servers[0];
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
     const uint32_t* qs[kMaxLanes];
     uint64_t* acc[kMaxLanes];
-    for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_server* L = servers[b];
-        if (!L || !L->have_db || !L->have_records || L->db.p != S->db.p || L->device != S->device || L->dim0_shard != S->dim0_shard || L->fold_g_log != S->fold_g_log || L->sweep_k_log)
-            return fail("time_sweep_batch: server %u is not a converted lane of server 0's database image", b);
-        qs[b] = (const uint32_t*)L->qs.p;
-        acc[b] = L->acc;
-        L->raw_from_acc = false;
-    }
-    int rc = 0;
-    const uint64_t* limbs = limb_image(S, holder_of(S), n, &rc);
-    if (rc) return rc;
+    server_records(servers, n, qs, acc);
+    mark_raw_stale(servers, n);
+    const uint64_t* limbs;
+    if (limb_image(S, holder_of(S), n, &limbs)) return -1;
     HIP_OK(hipDeviceSynchronize());  // (the lanes' streams: their records are complete)
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
-        if (sweep_queries(holder_of(S), limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
+        if (sweep_image(holder_of(S), limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
     HIP_OK(hipEventRecord(S->ev[1], S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     float ms = 0;

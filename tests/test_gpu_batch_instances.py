@@ -255,6 +255,16 @@ def test_update_between_replays(sa, SV, oracle):
         assert_eq(T.clients[b].decode(r2[b, 0]), O.db_item(T.po, 830, T.idx[b]), f"client {b}: instance 0 unchanged")
     want_r, _ = T.singles(3)
     assert_eq(r2, want_r, "after the update: each client's own run_query_instances")
+    # other output buffers are baked into another capture: exactly one, with the same answers
+    resp2 = torch.zeros_like(resp)
+    for sv, q in zip(S, T.queries):
+        sv.set_query(q)
+    c1 = captures(sa)
+    sa.run_query_batch_instances(S, T.inst, resp2.data_ptr())
+    for sv in S:
+        sv.sync()
+    assert captures(sa) == c1 + 1, "new output buffers: one capture"
+    assert torch.equal(resp2, resp), "new output buffers: the same answers"
     T.close()
 
 

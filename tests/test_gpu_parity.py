@@ -1182,7 +1182,9 @@ def test_run_query_batch_equals_single_queries(sa, oracle, nu1, nu2, n, kw, grap
         qs = [cl.query(i) for cl, i in zip(clients, idxs)]
         for srv, q in zip(lanes, qs):
             srv.set_query(q)
+        c0 = captures(sa)
         sa.run_query_batch(lanes)
+        assert captures(sa) - c0 == (1 if graphs and rnd == 0 else 0), f"captures of batch round {rnd}: the same lanes replay"
         for srv in lanes:
             srv.sync()
         for b, (srv, cl, pp, q, idx) in enumerate(zip(lanes, clients, pps, qs, idxs)):
@@ -1208,7 +1210,9 @@ def test_run_query_batch_equals_single_queries(sa, oracle, nu1, nu2, n, kw, grap
         assert_eq(srv.read(SV.BUF_RESPONSE), resp, "single run_query after the batch: response")
     # a different lane set re-captures; a sub-batch answers the same
     if n >= 3:
+        c0 = captures(sa)
         sa.run_query_batch(lanes[1:])
+        assert captures(sa) - c0 == (1 if graphs else 0), "a different lane set captures once"
         for srv, (fin, resp) in zip(lanes[1:], last[1:]):
             srv.sync()
             assert_eq(srv.read(SV.BUF_FINAL), fin, "sub-batch led by another lane: final ciphertext")
