@@ -229,8 +229,8 @@ int spiral_gpu_server_fill_db_random(spiral_gpu_server *s, uint64_t seed);
 /* a second in-flight query on one database: `s` releases its own image and sweeps `owner`'s (same parameters, shard and device;
  * the owner does not reload while `s` answers; loads through `s` fail).  One handle per query lane, each on
  * its own stream: the latency-bound expansion / folding of one query runs under the HBM-bound sweep of another.
- * Lifetime: the owner counts its lanes.  spiral_gpu_server_destroy(owner) while lanes exist frees everything of the owner except the
- * image and invalidates the handle; the image itself is freed with the last lane, so a lane never sweeps freed memory. */
+ * Lifetime: the image is counted -- the owner and every lane hold a reference.  spiral_gpu_server_destroy(owner) while lanes exist destroys the
+ * owner and invalidates the handle like any other; the image itself is freed with its last reference, so a lane never sweeps freed memory. */
 int spiral_gpu_server_share_db(spiral_gpu_server *s, spiral_gpu_server *owner);
 /* the same in one step and without ever allocating a second image: a new server with `owner`'s parameters, device and shard
  * whose database IS the owner's (a query lane).  Works for images larger than half of HBM, where create + share_db cannot. */
@@ -553,8 +553,8 @@ int spiral_gpu_pack_server_read_response_wire(spiral_gpu_pack_server *s, void *o
 int spiral_gpu_pack_server_read_acc(spiral_gpu_pack_server *s, uint32_t trial, uint64_t *out);
 uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algorithmic bytes of ONE trial's sweep */
 /* Batches on the pack path, beyond the reference (one query per call).  create_lane: a new server with the owner's parameters, out_n and
- * device that sweeps the OWNER's trial images and has its own public parameters, query and intermediates (loads through a lane fail; the owner
- * counts its lanes and the images go with the last of them; trial-sharded owners have no lanes).
+ * device that sweeps the OWNER's trial images and has its own public parameters, query and intermediates (loads through a lane fail; the
+ * images are counted and go with their last reference, the owner's or a lane's; trial-sharded owners have no lanes).
  * answer_batch: n <= 8 servers -- an owner and/or its lanes, each with its own client's public parameters -- answer queries[b] each: expansion and
  * conversion per lane, ONE first-dimension pass over every trial image for all n queries, then folding, packing and the modulus switch per lane,
  * all on servers[0]'s stream; returns synchronised.  Afterwards every lane's buffers (read_acc of every trial, read_response_wire) hold exactly

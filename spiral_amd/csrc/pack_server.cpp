@@ -1,7 +1,7 @@
 // SpiralPack / SpiralStreamPack: host orchestration and C ABI (server half of testHighRate, reference
 // src/testing.cpp:1009-1081).  Kernels: pack.hip, ntt.hip (LD_PDIGIT / LD_DBGEN1), poly.hip (matmul, rescale), sweep_mfma.hip (the batched
 // first-dimension sweep of answer_batch: several lanes' queries in one pass over the trial images, from their limb-plane form).
-#include "host_common.h"
+#include "db_image.h"
 
 using namespace spiral;
 using namespace spiral::host;
@@ -15,22 +15,17 @@ struct spiral_gpu_pack_server {
     hipStream_t stream = nullptr;
     bool own_stream = true;
     DeviceTables tb;
-    bool have_db = false, have_pp = false;
+    bool have_pp = false;
     bool packed_after_front = false;  // event 6 belongs to the same answer as events 0..5
     uint32_t n_cv = 0;
-    size_t db_words = 0;  // per trial
-    DevBuf db, w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
+    DevBuf w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
     DevBuf gs_raw, gs_chat, gs_tmp, gsw, key, qs1, acc, raw, fold_d, fold_c, fold_c2, pk_ginv, pk_ct2, pk_res, pk_raw, resp, stage, wire;
     WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
     hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch / item call end, [8] ordering another call's stream in front of an item call
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
-    // query lanes (create_lane): a lane has no image of its own and sweeps its owner's; the owner counts its lanes.  Destroying an owner that
-    // still has lanes frees everything but the image and leaves a husk (zombie) that the last lane to go deletes.
-    spiral_gpu_pack_server* db_owner = nullptr;
-    uint32_t n_lanes = 0;
-    bool zombie = false;
-    uint32_t db_format = SPIRAL_GPU_DB_PACKED;  // holder only: the form db is in now (pk_db_set_format)
-    UpdateWork upd;                              // holder only: update_db_items' workspace
+    // the trial images this server sweeps (db_image.h): its own, or its owner's, of which a query lane (create_lane) holds a reference and
+    // which it never writes
+    DbImage* img = nullptr;
     DevBuf item;            // answer_batch_instances as a client: the arena of its item groups of more than one instance, kept for the next call
     uint32_t item_cap = 0;  // instances per group the arena holds
 };
@@ -63,31 +58,29 @@ int pack_shape_of(const spiral_gpu_params* p, uint32_t out_n, spiral_gpu_pack_sh
     return 0;
 }
 
-spiral_gpu_pack_server* pk_holder(spiral_gpu_pack_server* S) { return S->db_owner ? S->db_owner : S; }
+// the owner of the images S sweeps, while it lives (S itself, or a lane's owner)
+spiral_gpu_pack_server* pk_owner(const spiral_gpu_pack_server* S) { return (spiral_gpu_pack_server*)S->img->owner; }
 
-void pk_free(spiral_gpu_pack_server* S, bool keep_db = false) {
-    const DevBuf keep = S->db;
-    DevBuf* all[] = {&S->db, &S->w_left, &S->w_right, &S->v, &S->v_w, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->gs_raw, &S->gs_chat, &S->gs_tmp,
+void pk_free(spiral_gpu_pack_server* S) {
+    DbImage::drop(S->img, S);
+    DevBuf* all[] = {&S->w_left, &S->w_right, &S->v, &S->v_w, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->gs_raw, &S->gs_chat, &S->gs_tmp,
                      &S->gsw, &S->key, &S->qs1, &S->acc, &S->raw, &S->fold_d, &S->fold_c, &S->fold_c2, &S->pk_ginv, &S->pk_ct2, &S->pk_res, &S->pk_raw, &S->resp,
                      &S->stage, &S->wire, &S->item};
-    if (keep_db) S->db = DevBuf{};
     for (DevBuf* b : all) b->release();
     S->item_cap = 0;
-    S->upd.release();
     S->wire_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     if (S->stream && S->own_stream) (void)hipStreamDestroy(S->stream);
     S->stream = nullptr;
-    if (keep_db) S->db = keep;
 }
 
-int pk_alloc(spiral_gpu_pack_server* S) {
+int pk_alloc(spiral_gpu_pack_server* S, DbImage* owners) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
     const size_t ngs = (size_t)p.nu2 * s.ell, rows = S->out_n + 1;
-    S->db_words = db1_device_words(s.num_per, s.dim0);  // u64 words of one trial in the device layout
-    if (!S->db_owner && S->db.alloc(S->db_words * S->nt)) return -1;  // (a lane sweeps its owner's image)
+    S->img = owners ? owners->share() : DbImage::create(DbLayout::packed1(s.num_per, s.dim0, S->nt), S);  // (a lane sweeps its owner's images)
+    if (!S->img) return -1;
     if (S->w_left.alloc((size_t)s.n_left * 2 * p.t_exp * kN)) return -1;
     if (S->w_right.alloc((size_t)s.n_right * 2 * p.t_exp_right * kN)) return -1;
     if (S->v.alloc((size_t)2 * 2 * p.t_conv * kN)) return -1;
@@ -146,64 +139,26 @@ void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_strid
     launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st, n_inst);
 }
 
-// Converts the holder's trial images between the packed form (kernels.h; sweep1_kernel) and the limb planes (sweep_mfma.hip; the matrix-core
-// sweep) IN PLACE, as the base path's srv_db_set_format: a slot z's region of a trial is the same byte range in both forms, so the images go
-// through a staging buffer of at most 256 MiB a few slots at a time -- never a second image.  A failure once the first region has been
-// rewritten leaves the image in neither form: it is marked invalid (no database loaded) rather than left under the old tag.
-int pk_db_set_format(spiral_gpu_pack_server* H, uint32_t fmt, hipStream_t st) {
-    if (H->db_format == fmt) return 0;
-    const uint32_t np = H->s.num_per, dim0 = H->s.dim0;
-    if (!sweep1_mfma_ok(np, dim0))
-        return fail("this geometry has no limb-plane form (needs >= 128 ciphertexts per slot and a power-of-two first dimension in [128, 4096])");
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever reads or writes the image, on whichever stream
-    const size_t per_z = H->db_words / kN;
-    const uint32_t nzc = (uint32_t)std::max<size_t>(1, std::min<size_t>(kN, ((size_t)256 << 20) / (per_z * sizeof(uint64_t))));
-    DevBuf stage;
-    if (stage.alloc(per_z * nzc)) return -1;
-    hipError_t e = hipSuccess;
-    for (uint32_t t = 0; t < H->nt && e == hipSuccess; t++)
-        for (uint32_t z = 0; z < kN && e == hipSuccess; z += nzc) {
-            const uint32_t nz = std::min(nzc, kN - z);
-            uint64_t* region = H->db.p + (size_t)t * H->db_words + (size_t)z * per_z;
-            if (fmt == SPIRAL_GPU_DB_LIMBS)
-                launch_db1_limb_planes(region, stage.p, np, dim0, st, nz);
-            else
-                launch_db1_limb_unplanes(region, stage.p, np, dim0, st, nz);
-            e = hipMemcpyAsync(region, stage.p, (size_t)nz * per_z * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
-        }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    stage.release();
-    if (e != hipSuccess) {
-        H->have_db = false;
-        H->db_format = SPIRAL_GPU_DB_PACKED;
-        return fail("converting the database image failed (%s): the image is invalid, load the database again", hipGetErrorString(e));
-    }
-    H->db_format = fmt;
-    return 0;
-}
-// a loader is about to rewrite the whole image in packed form
-void pk_db_rewrite(spiral_gpu_pack_server* S) { S->db_format = SPIRAL_GPU_DB_PACKED; }
-
 // the first-dimension sweep of n servers' queries (their records) over every trial image of H into accs[b], on `st`: one pass on the matrix cores when
 // the image is in limb-plane form, else one sweep1 launch (all trials) per server
-int pk_sweep_into(const spiral_gpu_pack_server* H, spiral_gpu_pack_server* const* servers, uint64_t* const* accs, uint32_t n, hipStream_t st) {
-    const spiral_gpu_pack_shape& s = H->s;
+int pk_sweep_into(const DbImage* H, spiral_gpu_pack_server* const* servers, uint64_t* const* accs, uint32_t n, hipStream_t st) {
+    const DbLayout& s = H->lay;
     const size_t acc_stride = (size_t)s.num_per * 2 * kN;
-    if (H->db_format == SPIRAL_GPU_DB_LIMBS) {
+    if (H->format == SPIRAL_GPU_DB_LIMBS) {
         const uint32_t* qs[kMaxLanes];
         uint64_t* acc[kMaxLanes];
         for (uint32_t b = 0; b < n; b++) qs[b] = (const uint32_t*)servers[b]->qs1.p, acc[b] = accs[b];
-        const hipError_t e = launch_sweep1_mfma(H->db.p, qs, acc, n, s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
+        const hipError_t e = launch_sweep1_mfma(H->db.p, qs, acc, n, s.num_per, s.dim0, s.trials, s.trial_words, acc_stride, st);
         return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
     }
-    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, (const uint32_t*)servers[b]->qs1.p, accs[b], s.num_per, s.dim0, H->nt, H->db_words, acc_stride, st);
+    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, (const uint32_t*)servers[b]->qs1.p, accs[b], s.num_per, s.dim0, s.trials, s.trial_words, acc_stride, st);
     return 0;
 }
-// ... over servers[0]'s holder, into each server's own accumulators
+// ... over servers[0]'s images, into each server's own accumulators
 int pk_sweep(spiral_gpu_pack_server* const* servers, uint32_t n, hipStream_t st) {
     uint64_t* acc[kMaxLanes];
     for (uint32_t b = 0; b < n; b++) acc[b] = servers[b]->acc.p;
-    return pk_sweep_into(pk_holder(servers[0]), servers, acc, n, st);
+    return pk_sweep_into(servers[0]->img, servers, acc, n, st);
 }
 
 // The buffers the folding, packing and switch of one client write: its own (one instance), or one group of G instances of answer_batch_instances
@@ -286,7 +241,7 @@ int spiral_gpu_pack_server_create(const spiral_gpu_params* p, uint32_t out_n, in
 // The out_n^2 trials are independent up to the packing step (each has its own database image, sweep and folding), so N GPUs split
 // them: a server created for trials [trial0, trial1) holds only those images; fold_trials leaves their folded ciphertexts in a
 // caller-provided device buffer, one all-gather of out_n^2 x 2 polynomials collects them, pack_gathered finishes on the root.
-static int pk_create(const spiral_gpu_params* p, uint32_t out_n, int device, uint32_t trial0, uint32_t trial1, spiral_gpu_pack_server* owner,
+static int pk_create(const spiral_gpu_params* p, uint32_t out_n, int device, uint32_t trial0, uint32_t trial1, DbImage* owners,
                      spiral_gpu_pack_server** out) {
     if (!p || !out) return fail("null argument");
     spiral_gpu_pack_shape s;
@@ -301,20 +256,18 @@ static int pk_create(const spiral_gpu_params* p, uint32_t out_n, int device, uin
     S->t0 = trial0;
     S->nt = trial1 - trial0;
     S->device = device;
-    S->db_owner = owner;
     if (tables_get(device, &S->tb) != 0) {
         delete S;
         return fail("twiddle table setup failed on device %d", device);
     }
     bool ok = hipStreamCreate(&S->stream) == hipSuccess;
     for (auto& e : S->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
-    if (!ok || pk_alloc(S)) {
+    if (!ok || pk_alloc(S, owners)) {
         if (ok == false) fail("stream/event creation failed");
         pk_free(S);
         delete S;
         return -1;
     }
-    if (owner) owner->n_lanes++;
     *out = S;
     return 0;
 }
@@ -327,55 +280,40 @@ int spiral_gpu_pack_server_create_sharded(const spiral_gpu_params* p, uint32_t o
 // a query lane of `owner`: the owner's parameters, out_n and device, its own public parameters, query and intermediates, and the owner's trial images
 int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server* owner, spiral_gpu_pack_server** out) {
     if (!owner || !out) return fail("null argument");
-    if (owner->db_owner || owner->zombie) return fail("the owner does not own its database image (it is a lane)");
+    if (owner->img->owner != owner) return fail("the owner does not own its database image (it is a lane)");
     if (owner->nt != owner->s.trials) return fail("the owner holds trials [%u, %u) only: trial-sharded servers have no lanes", owner->t0, owner->t0 + owner->nt);
-    if (!owner->have_db) return fail("the owner has no database loaded");
-    return pk_create(&owner->p, owner->out_n, owner->device, 0, 0, owner, out);
+    if (!owner->img->loaded) return fail("the owner has no database loaded");
+    return pk_create(&owner->p, owner->out_n, owner->device, 0, 0, owner->img, out);
 }
 
 void spiral_gpu_pack_server_destroy(spiral_gpu_pack_server* S) {
-    if (!S || S->zombie) return;
+    if (!S) return;
     (void)hipSetDevice(S->device);
     (void)hipDeviceSynchronize();
-    if (S->n_lanes > 0) {  // lanes still sweep this server's images: keep them (only), the last lane frees them
-        pk_free(S, true);
-        S->zombie = true;
-        S->have_pp = false;
-        return;
-    }
-    spiral_gpu_pack_server* owner = S->db_owner;
-    pk_free(S);
+    pk_free(S);  // (images its lanes still sweep live on until the last of them goes)
     delete S;
-    if (owner && --owner->n_lanes == 0 && owner->zombie) {
-        owner->db.release();
-        delete owner;
-    }
 }
 
 int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server* S, int format) {
     if (!S) return fail("null server");
     if (format != SPIRAL_GPU_DB_PACKED && format != SPIRAL_GPU_DB_LIMBS) return fail("unknown database image format %d", format);
-    if (S->db_owner) return fail("this server is a lane: convert the image through its owner");
-    if (!S->have_db) return fail("no database loaded");
+    if (S->img->owner != S) return fail("this server is a lane: convert the image through its owner");
+    if (!S->img->loaded) return fail("no database loaded");
     HIP_OK(hipSetDevice(S->device));
-    return pk_db_set_format(S, (uint32_t)format, S->stream);
+    return S->img->set_format((uint32_t)format, S->stream);
 }
-int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server* S) { return S ? (int)pk_holder(S)->db_format : -1; }
-uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server* S) {
-    if (!S) return 0;
-    const spiral_gpu_pack_server* H = pk_holder(S);
-    return (uint64_t)(H->db.p ? H->db.words : 0) * 8u;
-}
+int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server* S) { return S ? (int)S->img->format : -1; }
+uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server* S) { return S ? S->img->device_bytes() : 0; }
 
 int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
-    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
-    pk_db_rewrite(S);
+    S->img->begin_rewrite();
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per, chunk = 1u << 18;
     for (uint32_t t = 0; t < S->nt; t++) {
         FwdParams fp{};
-        fp.dst = S->db.p + (size_t)t * S->db_words;
+        fp.dst = S->img->trial(t);
         fp.src_map = fp.dst_map = identity_map();
         fp.n_digits = 1;
         fp.seed = seed;
@@ -390,29 +328,29 @@ int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
         }
     }
     HIP_OK(hipStreamSynchronize(S->stream));
-    S->have_db = true;
+    S->img->finish_load();
     return 0;
 }
 
 int spiral_gpu_pack_server_load_db(spiral_gpu_pack_server* S, uint32_t trial, const uint64_t* db) {
     if (!S || !db) return fail("null argument");
-    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
     // one trial is rewritten: the others keep their words, so an image in limb-plane form goes back to the packed form first
-    if (S->db_format != SPIRAL_GPU_DB_PACKED && S->have_db && pk_db_set_format(S, SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
-    if (!S->have_db) pk_db_rewrite(S);
+    if (S->img->begin_partial(S->stream)) return -1;
     DevBuf st;
     const size_t ref_words = (size_t)kN * S->s.dim0 * S->s.num_per;
     if (st.alloc(ref_words)) return -1;
     hipError_t e = hipMemcpy(st.p, db, ref_words * sizeof(uint64_t), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        launch_db1_relayout(st.p, S->db.p + (size_t)(trial - S->t0) * S->db_words, S->s.num_per, S->s.dim0, S->stream);
+        S->img->dirty();
+        launch_db1_relayout(st.p, S->img->trial(trial - S->t0), S->s.num_per, S->s.dim0, S->stream);
         e = hipStreamSynchronize(S->stream);
     }
     st.release();
     if (e != hipSuccess) return fail("database upload failed: %s", hipGetErrorString(e));
-    S->have_db = true;
+    S->img->finish_load();
     return 0;
 }
 
@@ -420,16 +358,15 @@ int spiral_gpu_pack_server_load_db(spiral_gpu_pack_server* S, uint32_t trial, co
 int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, uint64_t first_item,
                                          uint64_t n_items) {
     if (!S) return fail("null server");
-    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
     // a partial load scatters packed words into the image: an image in limb-plane form goes back to the packed form first
-    if (S->db_format != SPIRAL_GPU_DB_PACKED && S->have_db && pk_db_set_format(S, SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
-    if (!S->have_db) pk_db_rewrite(S);
+    if (S->img->begin_partial(S->stream)) return -1;
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
     if (first_item > total || n_items > total - first_item) return fail("items outside the database");
     FwdParams fp{};
-    fp.dst = S->db.p + (size_t)(trial - S->t0) * S->db_words;
+    fp.dst = S->img->trial(trial - S->t0);
     fp.src_map = fp.dst_map = identity_map();
     fp.n_digits = 1;
     fp.p_db = S->p.p_db;
@@ -440,13 +377,14 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
     fp.coeff_bits = coeff_bits;
     if (ingest_items(items, coeff_bits, first_item, first_item, first_item + n_items, 1, S->p.p_db, S->stream,
                      [&](const uint8_t* d_items, uint32_t* d_err, uint64_t first, uint64_t n) {
+                         S->img->dirty();
                          fp.items = d_items;
                          fp.err = d_err;
                          fp.items_first = fp.item_base = first;
                          launch_ntt_forward(S->tb, fp, LD_DBGEN1, ST_DB1, (uint32_t)n, S->stream);
                      }))
         return -1;
-    S->have_db = true;
+    S->img->finish_load();
     return 0;
 }
 
@@ -454,31 +392,25 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
 int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, const uint64_t* item_ids,
                                            uint64_t n) {
     if (!S) return fail("null server");
-    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, update it through the owner");
-    if (!S->have_db) return fail("no database loaded");
+    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, update it through the owner");
+    if (!S->img->loaded) return fail("no database loaded");
     if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
     HIP_OK(hipSetDevice(S->device));
     const uint64_t np = S->s.num_per;
     if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
     std::vector<UpdateItem> sel(n);
     for (uint64_t k = 0; k < n; k++) sel[k] = UpdateItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
-    uint64_t* image = S->db.p + (size_t)(trial - S->t0) * S->db_words;
-    UpdateImage img{};
-    img.pack = 1;
-    img.num_per = S->s.num_per;
-    img.dim0 = S->s.dim0;
-    (S->db_format == SPIRAL_GPU_DB_LIMBS ? img.limbs : img.packed) = image;
-    return update_items(S->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, img);
+    return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target(trial - S->t0));
 }
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
-    if (S->db_owner) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
     HIP_OK(hipSetDevice(S->device));
-    pk_db_rewrite(S);
-    for (uint32_t t = 0; t < S->nt; t++) launch_fill_db1_random(S->db.p + (size_t)t * S->db_words, S->s.num_per, S->s.dim0, seed + S->t0 + t, S->stream);
+    S->img->begin_rewrite();
+    for (uint32_t t = 0; t < S->nt; t++) launch_fill_db1_random(S->img->trial(t), S->s.num_per, S->s.dim0, seed + S->t0 + t, S->stream);
     HIP_OK(hipStreamSynchronize(S->stream));
-    S->have_db = true;
+    S->img->finish_load();
     return 0;
 }
 
@@ -500,7 +432,6 @@ int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server* S, const uint6
 // the same from the wire form: one message W_exp_left, W_exp_right, V (expansion only), v_W; a failure leaves no public parameters
 int spiral_gpu_pack_server_set_pub_params_wire(spiral_gpu_pack_server* S, const void* wire, size_t bytes) {
     if (!S) return fail("null server");
-    if (S->zombie) return fail("destroyed server");
     HIP_OK(hipSetDevice(S->device));
     const spiral_gpu_params& p = S->p;
     const bool ex = !p.direct_upload;
@@ -517,7 +448,6 @@ int spiral_gpu_pack_server_set_pub_params_wire(spiral_gpu_pack_server* S, const 
 // the same from the seeded form: row 0 of every matrix from the message's seed (include/spiral_gpu.h)
 int spiral_gpu_pack_server_set_pub_params_seeded(spiral_gpu_pack_server* S, const void* msg, size_t bytes) {
     if (!S) return fail("null server");
-    if (S->zombie) return fail("destroyed server");
     HIP_OK(hipSetDevice(S->device));
     const spiral_gpu_params& p = S->p;
     const bool ex = !p.direct_upload;
@@ -717,9 +647,8 @@ static int pk_download(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* 
 
 // what answer and answer_wire check before anything is uploaded
 static int pk_check_answer(spiral_gpu_pack_server* S) {
-    if (S->zombie) return fail("destroyed server");
     HIP_OK(hipSetDevice(S->device));
-    if (!pk_holder(S)->have_db || !S->have_pp) return fail("database and public parameters must be set first");
+    if (!S->img->loaded || !S->have_pp) return fail("database and public parameters must be set first");
     if (S->nt != S->s.trials) return fail("this server holds trials [%u, %u) only: fold_trials + pack_gathered", S->t0, S->t0 + S->nt);
     return 0;
 }
@@ -773,15 +702,15 @@ static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bo
     if (!servers) return fail("%s: null argument", what);
     if (n == 0 || n > kMaxLanes) return fail("%s: %u servers, 1 .. %u per batch", what, n, kMaxLanes);
     for (uint32_t b = 0; b < n; b++)
-        if (!servers[b] || servers[b]->zombie) return fail("%s: server %u is null or destroyed", what, b);
-    spiral_gpu_pack_server* H = pk_holder(servers[0]);
+        if (!servers[b]) return fail("%s: server %u is null or destroyed", what, b);
+    const spiral_gpu_pack_server* H = servers[0];
     if (H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
-    if (need_db && !H->have_db) return fail("%s: no database loaded", what);
+    if (need_db && !H->img->loaded) return fail("%s: no database loaded", what);
     for (uint32_t b = 0; b < n; b++) {
         const spiral_gpu_pack_server* L = servers[b];
         for (uint32_t c = 0; c < b; c++)
             if (servers[c] == L) return fail("%s: server %u appears twice", what, b);
-        if (pk_holder(servers[b]) != H) return fail("%s: server %u does not sweep server 0's database image (create_lane)", what, b);
+        if (L->img != H->img) return fail("%s: server %u does not sweep server 0's database image (create_lane)", what, b);
         if (memcmp(&L->p, &H->p, sizeof(L->p)) != 0 || L->out_n != H->out_n || L->device != H->device || L->nt != H->nt)
             return fail("%s: server %u has other parameters than server 0", what, b);
         if (!L->have_pp) return fail("%s: server %u has no public parameters", what, b);
@@ -840,9 +769,8 @@ int spiral_gpu_pack_server_answer_batch_seeded(spiral_gpu_pack_server* const* se
 static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
                            uint64_t* const* packed_cts, double stage_us[8]) {
     spiral_gpu_pack_server* S = servers[0];
-    spiral_gpu_pack_server* H = pk_holder(S);
     HIP_OK(hipSetDevice(S->device));
-    if (H->db_format != SPIRAL_GPU_DB_LIMBS && sweep1_mfma_ok(H->s.num_per, H->s.dim0) && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+    if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     hipStream_t st = S->stream;
     for (uint32_t b = 0; b < n; b++)
         if (pk_expand_convert(servers[b], queries ? queries[b] : nullptr, st)) return -1;
@@ -889,11 +817,11 @@ static int pk_check_items(spiral_gpu_pack_server* const* servers, uint32_t n, sp
     const spiral_gpu_pack_server* S = servers[0];
     for (uint32_t k = 0; k < n_inst; k++) {
         const spiral_gpu_pack_server* I = instances[k];
-        if (!I || I->zombie) return fail("%s: instance %u is null or destroyed", what, k);
+        if (!I) return fail("%s: instance %u is null or destroyed", what, k);
         if (memcmp(&I->p, &S->p, sizeof(S->p)) != 0 || I->out_n != S->out_n || I->device != S->device)
             return fail("%s: instance %u has other parameters, out_n or device than the clients", what, k);
         if (I->nt != I->s.trials) return fail("%s: instance %u holds trials [%u, %u) only: trial-sharded servers are no instances", what, k, I->t0, I->t0 + I->nt);
-        if (!pk_holder(const_cast<spiral_gpu_pack_server*>(I))->have_db) return fail("%s: instance %u has no database loaded", what, k);
+        if (!I->img->loaded) return fail("%s: instance %u has no database loaded", what, k);
     }
     return 0;
 }
@@ -973,13 +901,11 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
     for (uint32_t b = 1; b < n; b++)
         if (join(servers[b])) return -1;
     for (uint32_t k = 0; k < n_inst; k++)
-        if (join(instances[k]) || join(pk_holder(instances[k]))) return -1;
+        if (join(instances[k]) || (pk_owner(instances[k]) && join(pk_owner(instances[k])))) return -1;  // (no owner left: nothing writes the image)
     // a batch sweeps each instance image on the matrix cores where the geometry has limb planes: converted in place on first use, as answer_batch's holder
     if (n >= 2 && sweep1_mfma_ok(S->s.num_per, S->s.dim0))
-        for (uint32_t k = 0; k < n_inst; k++) {
-            spiral_gpu_pack_server* H = pk_holder(instances[k]);
-            if (H->db_format != SPIRAL_GPU_DB_LIMBS && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, st)) return -1;
-        }
+        for (uint32_t k = 0; k < n_inst; k++)
+            if (instances[k]->img->set_format(SPIRAL_GPU_DB_LIMBS, st)) return -1;
     const uint32_t G = pk_item_group(servers, n, n_inst);
     size_t w[kPkBufs];
     pk_inst_words(S, w);
@@ -1001,7 +927,7 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
         for (uint32_t j = 0; j < g; j++) {  // one first-dimension pass per instance for all clients, into instance j's part of each group arena
             uint64_t* acc[kMaxLanes];
             for (uint32_t b = 0; b < n; b++) acc[b] = bufs[b].acc + (size_t)j * w[0];
-            if (pk_sweep_into(pk_holder(instances[k0 + j]), servers, acc, n, st)) return -1;
+            if (pk_sweep_into(instances[k0 + j]->img, servers, acc, n, st)) return -1;
         }
         for (uint32_t b = 0; b < n; b++) {  // folding, packing, switch and wire form: one sequence per client and group
             spiral_gpu_pack_server* L = servers[b];
@@ -1017,7 +943,7 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
     for (uint32_t k = 0; k < n_inst; k++) {
         spiral_gpu_pack_server* I = instances[k];
         if (I->stream != st) HIP_OK(hipStreamWaitEvent(I->stream, S->ev[7], 0));
-        if (pk_holder(I)->stream != st) HIP_OK(hipStreamWaitEvent(pk_holder(I)->stream, S->ev[7], 0));
+        if (pk_owner(I) && pk_owner(I)->stream != st) HIP_OK(hipStreamWaitEvent(pk_owner(I)->stream, S->ev[7], 0));
     }
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
@@ -1074,9 +1000,8 @@ int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server* const* serve
     if (!avg_ms || iters <= 0) return fail("time_sweep_batch: bad argument");
     if (pk_check_lanes(servers, n, true, "time_sweep_batch")) return -1;
     spiral_gpu_pack_server* S = servers[0];
-    spiral_gpu_pack_server* H = pk_holder(S);
     HIP_OK(hipSetDevice(S->device));
-    if (H->db_format != SPIRAL_GPU_DB_LIMBS && sweep1_mfma_ok(H->s.num_per, H->s.dim0) && pk_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+    if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
@@ -1116,7 +1041,7 @@ int spiral_gpu_pack_server_stage_us(spiral_gpu_pack_server* S, double stage_us[8
 int spiral_gpu_pack_server_fold_trials(spiral_gpu_pack_server* S, const uint64_t* query, void* folded_dev) {
     if (!S || !query || !folded_dev) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
-    if (!pk_holder(S)->have_db || !S->have_pp) return fail("database and public parameters must be set first");
+    if (!S->img->loaded || !S->have_pp) return fail("database and public parameters must be set first");
     if (pk_front(S, query)) return -1;
     HIP_OK(hipMemcpy2DAsync(folded_dev, 2 * kPolyBytes, S->raw.p, (size_t)S->s.num_per * 2 * kPolyBytes, 2 * kPolyBytes, S->nt, hipMemcpyDeviceToDevice,
                             S->stream));

@@ -4,7 +4,7 @@
 // there is no CPU arithmetic path -- without a device every compute entry point fails.
 #include <atomic>
 
-#include "host_common.h"
+#include "db_image.h"
 
 using namespace spiral;
 
@@ -68,23 +68,20 @@ struct spiral_gpu_server {
     uint32_t j0 = 0, j1 = 0, dim0_shard = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     DeviceTables tb;
-    bool keep_cts = false, have_db = false, have_pp = false, have_query = false;
+    bool keep_cts = false, have_pp = false, have_query = false;
     bool raw_from_acc = false;  // S->raw holds the lift of what S->acc holds now (lift ran, no sweep / write_raw / fold since): the stage fold may use the pair form
     bool have_records = false;  // the sweep's query records of the current query have been enqueued (ScalToMat ran since set_query)
     DevBuf wire;  // bit-packed response (read_response_wire)
-    bool db_shared = false;  // db.p is another server's image (share_db): never written, never freed here
-    // lifetime of a shared image: a lane points at its owner, the owner counts its lanes.  Destroying an owner that still has lanes
-    // frees everything but the image and leaves a husk (zombie) that the last lane to go deletes -- a lane never sweeps freed memory.
-    spiral_gpu_server* db_owner = nullptr;
-    uint32_t n_lanes = 0;
-    bool zombie = false;
+    // the database image this server sweeps (db_image.h): its own, or its owner's, of which it holds a reference (create_lane, share_db) and
+    // which it never writes
+    DbImage* img = nullptr;
     // expanded-ciphertext positions inside cv: first-dim j at j*pos_stride + pos_first, rest i at i*pos_stride + pos_rest
     uint32_t pos_stride = 1, pos_first = 0, pos_rest = 0, n_cv = 0;
 
     // every per-query buffer below except the lazily allocated ones (ex_raw2, ex_g2, cts_keep, stage, wire) is a piece of `arena`, carved in one
     // fixed order (srv_alloc): servers with equal parameters and shard have equal layouts, which is what run_query_batch relies on
     DevBuf arena;
-    DevBuf db, w_left, w_right, w, v, query, cv, ex_raw, ex_g, ex_raw2, ex_g2;  // (the second work set: the odd tree of a split expansion)
+    DevBuf w_left, w_right, w, v, query, cv, ex_raw, ex_g, ex_raw2, ex_g2;  // (the second work set: the odd tree of a split expansion)
     DevBuf cv_raw, cv_g, key, cts_keep;  // key: [d][3][m2]: the GSW matrices Q (src/spiral.cpp:2324) -- the fold key; Q_neg = G2 - Q (:2361-2379) is never stored (poly.hip fold_mac_two_kernel)
     uint64_t *gs_raw_p = nullptr, *gs_chat_p = nullptr;  // the Regev->GSW halves of cv_raw / cv_g
     DevBuf qs, acc_own, raw, fold_d, fold_c, fold_c2, resp, stage;
@@ -115,25 +112,16 @@ struct spiral_gpu_server {
     uint32_t fold_g_log = 0;  // distributed fold over 2^fold_g_log ranks: the sweep groups its output by ii mod G
     uint32_t sweep_k_log = 0; // pipelined sweep in 2^sweep_k_log stages (set_sweep_stages): accumulators laid out [stage][rank][ct]
     ExpandShard ex_shard{};   // sharded expansion (set_expand_shard): what this rank expands itself
-    // batched sweeps of sweep_mfma_min or more queries run on the matrix cores (sweep_mfma.hip) from a second image of the database, the "limb
-    // planes": built from db on first use by the image's holder (the owner of a shared image), as large as db, dropped when db is reloaded.
+    // batched sweeps of sweep_mfma_min or more queries run on the matrix cores (sweep_mfma.hip) from the limb planes of the database (DbImage::limb_view).
     // SPIRAL_SWEEP_MFMA=n sets the threshold (0 = never: at most kSweepMaxBatch queries per pass, on the vector ALU)
-    // With the option one_image (default) there is no second image: the holder converts its one image to limb-plane form IN PLACE the first time a
-    // batch wants it (srv_db_set_format; single queries then sweep it with sweep_mfma_kernel<1>, which ties with the vector-ALU kernel) and back
-    // when something needs the packed form (a partial reload, a staged sweep).
-    DevBuf db_limbs;
-    bool limbs_valid = false, limbs_refused = false;  // refused: the allocation failed once, do not try again
+    // With the option one_image (default) the one image is converted to limb-plane form IN PLACE the first time a batch wants it (single queries then
+    // sweep it with sweep_mfma_kernel<1>, which ties with the vector-ALU kernel) and back when something needs the packed form (a partial reload, a
+    // staged sweep); without it the limb planes are a second image, as large as the first, dropped when the database is reloaded.
     uint32_t sweep_mfma_min = 2;
-    uint32_t db_format = SPIRAL_GPU_DB_PACKED;  // holder only: the form db is in now
-    uint64_t db_epoch = 1;    // holder only: bumped when the image is reloaded or changes form -- captured sweeps of the old form must not replay
-    uint64_t epoch_seen = 0;  // the holder's epoch this server's graphs were captured under
-    UpdateWork upd;           // holder only: update_db_items' workspace
+    uint64_t epoch_seen = 0;  // the image's epoch this server's graphs were captured under
 };
 
 namespace {
-
-void lane_attach(spiral_gpu_server* lane, spiral_gpu_server* owner);
-void lane_detach(spiral_gpu_server* lane);
 
 // digits per workgroup of a fold round with n_src source polynomials: as few workgroups as keep the chip busy (every
 // workgroup repeats the inverse transform once), halved from ell until the round has about fold_blocks of them
@@ -143,19 +131,11 @@ uint32_t fold_dpb(const spiral_gpu_server* S, uint32_t n_src) {
     return dpb;
 }
 
-int srv_alloc(spiral_gpu_server* S, const spiral_gpu_server* db_owner) {
+int srv_alloc(spiral_gpu_server* S, DbImage* owners) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_shape& s = S->s;
-    const size_t nic = 2 * (size_t)s.num_per;
-    if (db_owner) {  // a query lane: the owner's image, never written or freed here
-        S->db.p = db_owner->db.p;
-        S->db.words = db_owner->db.words;
-        S->db_shared = true;
-        S->have_db = true;
-        lane_attach(S, const_cast<spiral_gpu_server*>(db_owner));
-    } else if (S->db.alloc(db_device_words((uint32_t)nic, S->dim0_shard))) {
-        return -1;
-    }
+    S->img = owners ? owners->share() : DbImage::create(DbLayout::base(s.num_per, S->dim0_shard), S);  // (a query lane: the owner's image)
+    if (!S->img) return -1;
     S->n_cv = p.direct_upload ? s.n_bits : (1u << s.g);
     const size_t ngs = (size_t)p.nu2 * s.ell;
     const size_t half = s.num_per > 1 ? s.num_per / 2 : 1;
@@ -203,20 +183,13 @@ void srv_drop_graphs(spiral_gpu_server* S) {
     }
 }
 
-void srv_free(spiral_gpu_server* S, bool keep_db = false) {
+void srv_free(spiral_gpu_server* S) {
     srv_drop_graphs(S);
-    DevBuf keep, keep_limbs;
-    if (keep_db) {
-        keep = S->db;
-        keep_limbs = S->db_limbs;
-        S->db.p = S->db_limbs.p = nullptr;
-    }
-    DevBuf* all[] = {&S->db, &S->w_left, &S->w_right, &S->w, &S->v, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->ex_raw2, &S->ex_g2, &S->cv_raw,
+    DbImage::drop(S->img, S);
+    DevBuf* all[] = {&S->w_left, &S->w_right, &S->w, &S->v, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->ex_raw2, &S->ex_g2, &S->cv_raw,
                      &S->cv_g, &S->key, &S->cts_keep, &S->qs, &S->acc_own, &S->raw, &S->fold_d, &S->fold_c, &S->fold_c2,
-                     &S->resp, &S->stage, &S->wire, &S->db_limbs, &S->arena};  // (the arena after its pieces)
-    if (S->db_shared) S->db.p = nullptr;
+                     &S->resp, &S->stage, &S->wire, &S->arena};  // (the arena after its pieces)
     for (DevBuf* b : all) b->release();
-    S->upd.release();
     S->wire_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e);
@@ -228,74 +201,15 @@ void srv_free(spiral_gpu_server* S, bool keep_db = false) {
     S->side_stream = S->own_stream = nullptr;
     S->ev_fork = S->ev_join = S->ev_batch = nullptr;
     for (auto& e : S->ev) e = nullptr;
-    if (keep_db) S->db = keep, S->db_limbs = keep_limbs;
 }
 
-// lane <-> owner bookkeeping of a shared database image
-void lane_attach(spiral_gpu_server* lane, spiral_gpu_server* owner) {
-    lane->db_owner = owner;
-    owner->n_lanes++;
-}
-void lane_detach(spiral_gpu_server* lane) {
-    spiral_gpu_server* owner = lane->db_owner;
-    if (!owner) return;
-    lane->db_owner = nullptr;
-    if (--owner->n_lanes == 0 && owner->zombie) {  // the owner was destroyed first: its image goes with its last lane
-        owner->db.release();
-        owner->db_limbs.release();
-        delete owner;
-    }
-}
-
-spiral_gpu_server* holder_of(spiral_gpu_server* S) { return S->db_owner ? S->db_owner : S; }
-const spiral_gpu_server* holder_of(const spiral_gpu_server* S) { return S->db_owner ? S->db_owner : S; }
-
-// graphs hold a sweep kernel chosen for the image's form at capture time: drop them when the holder's image has changed since
+// graphs hold a sweep kernel chosen for the image's form at capture time: drop them when the image has changed since
 void srv_check_epoch(spiral_gpu_server* S) {
-    const uint64_t e = holder_of(S)->db_epoch;
+    const uint64_t e = S->img->epoch;
     if (S->epoch_seen != e) {
         srv_drop_graphs(S);
         S->epoch_seen = e;
     }
-}
-
-// Converts the holder's database image between the packed form (common.h; the vector-ALU sweep) and the limb planes (sweep_mfma.hip; the
-// matrix-core sweep) IN PLACE: a slot z's region is the same byte range in both forms, so the image goes through a staging buffer a few slots at a
-// time -- no second image, whatever the database's size.  Offline (database load time or the first batch), never inside a capture.
-int srv_db_set_format(spiral_gpu_server* H, uint32_t fmt, hipStream_t st) {
-    if (H->db_format == fmt) return 0;
-    const uint32_t np = H->s.num_per, jm = 2 * H->dim0_shard;
-    if (!sweep_mfma_ok(np, jm)) return fail("this geometry has no limb-plane form (needs >= 64 ciphertexts per slot and a power-of-two first dimension in [64, 2048])");
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever reads or writes the image, on whichever stream
-    const size_t per_z = H->db.words / kN;
-    const uint32_t nzc = (uint32_t)std::max<size_t>(1, std::min<size_t>(kN, ((size_t)256 << 20) / (per_z * sizeof(uint64_t))));
-    DevBuf stage;
-    if (stage.alloc(per_z * nzc)) return -1;
-    hipError_t e = hipSuccess;
-    for (uint32_t z = 0; z < kN && e == hipSuccess; z += nzc) {
-        const uint32_t nz = std::min(nzc, kN - z);
-        uint64_t* region = H->db.p + (size_t)z * per_z;
-        if (fmt == SPIRAL_GPU_DB_LIMBS)
-            launch_db_limb_planes(region, stage.p, np, jm, st, nz);
-        else
-            launch_db_limb_unplanes(region, stage.p, np, jm, st, nz);
-        e = hipMemcpyAsync(region, stage.p, (size_t)nz * per_z * sizeof(uint64_t), hipMemcpyDeviceToDevice, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    stage.release();
-    if (e != hipSuccess) return fail("converting the database image failed: %s", hipGetErrorString(e));
-    H->db_format = fmt;
-    H->db_epoch++;
-    H->db_limbs.release();  // (a second image from before the option was switched on)
-    H->limbs_valid = false;
-    return 0;
-}
-// the image was (re)written in packed form by a loader
-void srv_db_loaded(spiral_gpu_server* S) {
-    S->have_db = true;
-    S->limbs_valid = false;
-    S->db_format = SPIRAL_GPU_DB_PACKED;
-    S->db_epoch++;
 }
 
 // the first-dimension sweep of n queries (records qs[b] -> accumulators acc[b]) against the packed image db of geometry (np, jm): one pass on the matrix
@@ -327,14 +241,14 @@ int sweep_queries(const uint64_t* db, const uint64_t* limbs, uint32_t np, uint32
     });
 }
 // ... of the image H holds, in whichever form it is in
-int sweep_image(const spiral_gpu_server* H, const uint64_t* limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log, hipStream_t st) {
-    if (!limbs && H->db_format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;  // the one image is in limb-plane form: every sweep is the matrix-core one
-    return sweep_queries(H->db.p, limbs, H->s.num_per, 2 * H->dim0_shard, qs, acc, n, g_log, st);
+int sweep_image(const DbImage* H, const uint64_t* limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t g_log, hipStream_t st) {
+    if (!limbs && H->format == SPIRAL_GPU_DB_LIMBS) limbs = H->db.p;  // the one image is in limb-plane form: every sweep is the matrix-core one
+    return sweep_queries(H->db.p, limbs, H->lay.num_per, 2 * H->lay.dim0, qs, acc, n, g_log, st);
 }
-// one query's sweep (all stages, or one stage of a pipelined sweep: packed image only) of the image H holds, in whichever form it is in, with S's
-// query records into S's accumulators on S's stream (H = S's own holder, or another instance of the database: run_query_instances)
-int sweep_with(spiral_gpu_server* S, const spiral_gpu_server* H, int stage) {
-    if (H->db_format == SPIRAL_GPU_DB_LIMBS) {
+// one query's sweep (all stages, or one stage of a pipelined sweep: packed image only) of the image H, in whichever form it is in, with S's
+// query records into S's accumulators on S's stream (H = S's own image, or another instance of the database: run_query_instances)
+int sweep_with(spiral_gpu_server* S, const DbImage* H, int stage) {
+    if (H->format == SPIRAL_GPU_DB_LIMBS) {
         if (stage >= 0 && S->sweep_k_log)
             return fail("a staged sweep needs the packed database image, and a batch has since converted it to limb planes: call set_sweep_stages again (or set option one_image = 0)");
         const uint32_t* qs[1] = {(const uint32_t*)S->qs.p};
@@ -345,34 +259,10 @@ int sweep_with(spiral_gpu_server* S, const spiral_gpu_server* H, int stage) {
     launch_sweep(H->db.p, (const uint32_t*)S->qs.p, S->acc, S->s.num_per, 2 * S->dim0_shard, S->fold_g_log, S->stream, S->sweep_k_log, stage);
     return 0;
 }
-int sweep_one(spiral_gpu_server* S, int stage) { return sweep_with(S, holder_of(S), stage); }
+int sweep_one(spiral_gpu_server* S, int stage) { return sweep_with(S, S->img, stage); }
 
-// The limb-plane image of the database H holds for a batched sweep of n queries on the matrix cores into *out, or nullptr when that sweep does not apply
-// (S's threshold, geometry); fails when it could not be built.  Built once per database load by the image's holder H, on S's stream; never call this
-// inside a capture.
-int limb_image(spiral_gpu_server* S, spiral_gpu_server* H, uint32_t n, const uint64_t** out) {
-    *out = nullptr;
-    if (H->db_format == SPIRAL_GPU_DB_LIMBS) return *out = H->db.p, 0;  // (whatever the threshold says: there is no other image to sweep)
-    if (S->sweep_mfma_min == 0 || n < S->sweep_mfma_min || !sweep_mfma_ok(H->s.num_per, 2 * H->dim0_shard)) return 0;
-    if (options().one_image) {  // the one image changes form, in place
-        if (srv_db_set_format(H, SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
-        return *out = H->db.p, 0;
-    }
-    if (H->limbs_valid) return *out = H->db_limbs.p, 0;
-    if (H->limbs_refused) return 0;
-    if (!H->db_limbs.p && H->db_limbs.alloc(H->db.words)) {
-        // the second image does not fit beside the first (databases beyond ~120 GiB on one device): the batch sweeps in passes of two on the vector ALU
-        fprintf(stderr, "spiral_gpu: no memory for the limb-plane image of the database (%zu MiB): batched sweeps stay on the vector ALU\n", (size_t)(H->db.words * 8 >> 20));
-        (void)hipGetLastError();
-        H->limbs_refused = true;
-        return 0;
-    }
-    if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever wrote the packed image, on whichever stream
-    launch_db_limb_planes(H->db.p, H->db_limbs.p, H->s.num_per, 2 * H->dim0_shard, S->stream);
-    if (hipStreamSynchronize(S->stream) != hipSuccess) return fail("building the limb-plane image failed");
-    H->limbs_valid = true;
-    return *out = H->db_limbs.p, 0;
-}
+// DbImage::limb_view of the image H for a batched sweep of n queries with S's threshold, on S's stream; never call this inside a capture
+int limb_image(spiral_gpu_server* S, DbImage* H, uint32_t n, const uint64_t** out) { return H->limb_view(n, S->sweep_mfma_min, S->stream, out); }
 
 // the fold needs the keys the forked conversion produces
 int srv_join_side(spiral_gpu_server* S) {
@@ -409,12 +299,12 @@ int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what,
     for (uint32_t b = 0; b < n; b++) {
         spiral_gpu_server* L = servers[b];
         if (whole && (((needs & NEED_QUERY) && !L->have_query) || !L->have_pp)) return fail("%s: server %u needs its query and public parameters set first", what, b);
-        if ((needs & NEED_DB) && !L->have_db) return fail("%s: server %u has no database", what, b);
+        if ((needs & NEED_DB) && !L->img->loaded) return fail("%s: server %u has no database", what, b);
         if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has not converted its query (run_pre first)", what, b);
         if (L->device != S->device || L->dim0_shard != S->dim0_shard || L->s.num_per != S->s.num_per ||
             (whole && (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->j0 != S->j0 || L->j1 != S->j1 || L->cv.words != S->cv.words)))
             return fail("%s: server %u differs from server 0 in parameters, device or shard", what, b);
-        if (L->db.p != S->db.p) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
+        if (L->img != S->img) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
         if ((sharded || !whole) && L->fold_g_log != S->fold_g_log)
             return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
         if (sharded && (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank))
@@ -955,7 +845,7 @@ int spiral_gpu_regev_to_gsw(uint64_t* out, const uint64_t* cv_v, const uint64_t*
 // ------------------------------------------------------------------------------------------------
 // resident server
 // ------------------------------------------------------------------------------------------------
-static int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, uint32_t j_end, const spiral_gpu_server* db_owner, spiral_gpu_server** out) {
+static int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, uint32_t j_end, DbImage* owners, spiral_gpu_server** out) {
     if (!p || !out) return fail("null argument");
     spiral_gpu_shape s;
     if (shape_of(p, &s)) return -1;
@@ -1008,8 +898,7 @@ static int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, 
             delete S;
             return fail("hipEventCreate failed");
         }
-    if (srv_alloc(S, db_owner)) {
-        lane_detach(S);
+    if (srv_alloc(S, owners)) {
         srv_free(S);
         delete S;
         return -1;
@@ -1024,23 +913,16 @@ int spiral_gpu_server_create(const spiral_gpu_params* p, int device, uint32_t j_
 
 int spiral_gpu_server_create_lane(spiral_gpu_server* owner, spiral_gpu_server** out) {
     if (!owner || !out) return fail("null argument");
-    if (owner->db_shared || owner->zombie) return fail("the owner does not own its database image");
-    if (!owner->have_db) return fail("the owner has no database loaded");
-    return srv_create(&owner->p, owner->device, owner->j0, owner->j1, owner, out);
+    if (owner->img->owner != owner) return fail("the owner does not own its database image");
+    if (!owner->img->loaded) return fail("the owner has no database loaded");
+    return srv_create(&owner->p, owner->device, owner->j0, owner->j1, owner->img, out);
 }
 
 void spiral_gpu_server_destroy(spiral_gpu_server* S) {
-    if (!S || S->zombie) return;
+    if (!S) return;
     (void)hipSetDevice(S->device);
     (void)hipDeviceSynchronize();
-    if (S->n_lanes > 0) {  // lanes still sweep this server's image: keep the image (only), the last lane frees it
-        srv_free(S, true);
-        S->zombie = true;
-        S->have_pp = S->have_query = false;
-        return;
-    }
-    lane_detach(S);
-    srv_free(S);
+    srv_free(S);  // (an image its lanes still sweep lives on until the last of them goes)
     delete S;
 }
 
@@ -1061,7 +943,7 @@ int spiral_gpu_server_use_graphs(spiral_gpu_server* S, int on) {
 
 int spiral_gpu_server_load_db(spiral_gpu_server* S, const uint64_t* database) {
     if (!S || !database) return fail("null argument");
-    if (S->db_shared) return fail("this server sweeps another server's database image (share_db): load it through the owner");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     // stage the reference-layout database one z-slab group at a time and re-lay the shard
     const size_t per_z_ref = (size_t)S->s.num_per * 2 * S->s.dim0 * 2;
@@ -1069,6 +951,7 @@ int spiral_gpu_server_load_db(spiral_gpu_server* S, const uint64_t* database) {
     const uint32_t zchunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(kN, stage_bytes / (per_z_ref * sizeof(uint64_t))));
     DevBuf st;
     if (st.alloc(per_z_ref * zchunk)) return -1;
+    S->img->begin_rewrite();
     for (uint32_t z = 0; z < kN; z += zchunk) {
         const uint32_t nz = std::min(zchunk, kN - z);
         if (hipMemcpyAsync(st.p, database + (size_t)z * per_z_ref, (size_t)nz * per_z_ref * sizeof(uint64_t), hipMemcpyHostToDevice, S->stream) !=
@@ -1076,23 +959,23 @@ int spiral_gpu_server_load_db(spiral_gpu_server* S, const uint64_t* database) {
             st.release();
             return fail("database upload failed");
         }
-        launch_db_relayout(st.p, S->db.p, S->s.num_per, S->s.dim0, S->j0, S->dim0_shard, z, nz, S->stream);
+        launch_db_relayout(st.p, S->img->db.p, S->s.num_per, S->s.dim0, S->j0, S->dim0_shard, z, nz, S->stream);
         if (hipStreamSynchronize(S->stream) != hipSuccess) {
             st.release();
             return fail("database relayout failed");
         }
     }
     st.release();
-    srv_db_loaded(S);
+    S->img->finish_load();
     return 0;
 }
 
 int spiral_gpu_server_gen_db(spiral_gpu_server* S, uint64_t seed) {
     if (!S) return fail("null server");
-    if (S->db_shared) return fail("this server sweeps another server's database image (share_db): load it through the owner");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     FwdParams fp{};
-    fp.dst = S->db.p;
+    fp.dst = S->img->db.p;
     fp.src_map = fp.dst_map = identity_map();
     fp.n_digits = 1;
     fp.seed = seed;
@@ -1102,18 +985,19 @@ int spiral_gpu_server_gen_db(spiral_gpu_server* S, uint64_t seed) {
     fp.j0 = S->j0;
     const uint64_t items = (uint64_t)S->dim0_shard * S->s.num_per, first = (uint64_t)S->j0 * S->s.num_per;
     const uint64_t chunk = 1u << 16;  // items per launch (4 polynomials each)
+    S->img->begin_rewrite();
     for (uint64_t done = 0; done < items; done += chunk) {
         fp.item_base = first + done;
         launch_ntt_forward(S->tb, fp, LD_DBGEN, ST_DB, (uint32_t)(std::min(chunk, items - done) * 4), S->stream);
     }
     HIP_OK(hipStreamSynchronize(S->stream));
-    srv_db_loaded(S);
+    S->img->finish_load();
     return 0;
 }
 
 int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items) {
     if (!S) return fail("null server");
-    if (S->db_shared) return fail("this server sweeps another server's database image (share_db): load it through the owner");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
     if (first_item > total || n_items > total - first_item) return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item,
@@ -1121,7 +1005,7 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
     // item i lives at (ii = i % num_per, j = i / num_per): this shard holds the items of j in [j0, j1)
     const uint64_t lo = std::max<uint64_t>(first_item, (uint64_t)S->j0 * S->s.num_per), hi = std::min<uint64_t>(first_item + n_items, (uint64_t)S->j1 * S->s.num_per);
     FwdParams fp{};
-    fp.dst = S->db.p;
+    fp.dst = S->img->db.p;
     fp.src_map = fp.dst_map = identity_map();
     fp.n_digits = 1;
     fp.p_db = S->p.p_db;
@@ -1130,15 +1014,16 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
     fp.j0 = S->j0;
     fp.coeff_bits = coeff_bits;
     // a partial load scatters packed words into the image: an image a batch has converted to limb planes goes back to the packed form first
-    if (S->db_format != SPIRAL_GPU_DB_PACKED && srv_db_set_format(S, SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
+    if (S->img->begin_partial(S->stream)) return -1;
     if (ingest_items(items, coeff_bits, first_item, lo, hi, 4, S->p.p_db, S->stream, [&](const uint8_t* d_items, uint32_t* d_err, uint64_t first, uint64_t n) {
+            S->img->dirty();
             fp.items = d_items;
             fp.err = d_err;
             fp.items_first = fp.item_base = first;
             launch_ntt_forward(S->tb, fp, LD_DBGEN, ST_DB, (uint32_t)(n * 4), S->stream);
         }))
         return -1;
-    srv_db_loaded(S);
+    S->img->finish_load();
     return 0;
 }
 
@@ -1146,8 +1031,8 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
 // and its form, so captured graphs replay unchanged and read the new items.
 int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, uint32_t coeff_bits, const uint64_t* item_ids, uint64_t n) {
     if (!S) return fail("null server");
-    if (S->db_shared) return fail("this server sweeps another server's database image (share_db or a lane): update it through the owner");
-    if (!S->have_db) return fail("no database loaded");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db or a lane): update it through the owner");
+    if (!S->img->loaded) return fail("no database loaded");
     HIP_OK(hipSetDevice(S->device));
     const uint64_t np = S->s.num_per;
     if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
@@ -1156,17 +1041,7 @@ int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, u
         const uint64_t j = item_ids[k] / np;
         if (j >= S->j0 && j < S->j1) sel.push_back(UpdateItem{k, (uint32_t)(j - S->j0), (uint32_t)(item_ids[k] % np)});
     }
-    UpdateImage img{};
-    img.pack = 0;
-    img.num_per = S->s.num_per;
-    img.dim0 = S->dim0_shard;
-    if (S->db_format == SPIRAL_GPU_DB_LIMBS) {
-        img.limbs = S->db.p;
-    } else {
-        img.packed = S->db.p;
-        if (S->limbs_valid) img.limbs = S->db_limbs.p;  // (option one_image = 0: the second image stays valid)
-    }
-    return update_items(S->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, img);
+    return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target());
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {
@@ -1178,8 +1053,8 @@ int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t
     uint64_t* d = sc.get(4 * kRefNtt);
     if (!d) return fail("device allocation failed");
     HIP_OK(hipStreamSynchronize(S->stream));
-    launch_db_read_item(S->db.p, d, S->s.num_per, S->dim0_shard, (uint32_t)(j - S->j0), (uint32_t)(item % S->s.num_per), S->stream,
-                        holder_of(S)->db_format == SPIRAL_GPU_DB_LIMBS);
+    launch_db_read_item(S->img->db.p, d, S->s.num_per, S->dim0_shard, (uint32_t)(j - S->j0), (uint32_t)(item % S->s.num_per), S->stream,
+                        S->img->format == SPIRAL_GPU_DB_LIMBS);
     HIP_OK(hipMemcpyAsync(out, d, 4 * kRefNtt * sizeof(uint64_t), hipMemcpyDeviceToHost, S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     return 0;
@@ -1197,7 +1072,7 @@ static int read_db_region(spiral_gpu_server* S, uint32_t z_begin, uint32_t nz, u
     hipError_t e = hipSuccess;
     for (uint32_t z = 0; z < nz && e == hipSuccess; z += zchunk) {
         const uint32_t n = std::min(zchunk, nz - z);
-        launch_db_read_slots(S->db.p, st.p, S->s.num_per, S->dim0_shard, z_begin + z, n, ii0, n_ii, S->stream, holder_of(S)->db_format == SPIRAL_GPU_DB_LIMBS);
+        launch_db_read_slots(S->img->db.p, st.p, S->s.num_per, S->dim0_shard, z_begin + z, n, ii0, n_ii, S->stream, S->img->format == SPIRAL_GPU_DB_LIMBS);
         e = hipMemcpyAsync(out + (size_t)z * per_z, st.p, (size_t)n * per_z * sizeof(uint64_t), hipMemcpyDeviceToHost, S->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(S->stream);
     }
@@ -1216,58 +1091,47 @@ int spiral_gpu_server_read_db_columns(spiral_gpu_server* S, uint32_t ii_begin, u
 int spiral_gpu_server_set_db_format(spiral_gpu_server* S, int format) {
     if (!S) return fail("null server");
     if (format != SPIRAL_GPU_DB_PACKED && format != SPIRAL_GPU_DB_LIMBS) return fail("unknown database image format %d", format);
-    if (S->db_shared) return fail("this server sweeps another server's database image: convert it through the owner");
-    if (!S->have_db) return fail("no database loaded");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image: convert it through the owner");
+    if (!S->img->loaded) return fail("no database loaded");
     HIP_OK(hipSetDevice(S->device));
-    return srv_db_set_format(S, (uint32_t)format, S->stream);
+    return S->img->set_format((uint32_t)format, S->stream);
 }
-int spiral_gpu_server_db_format(spiral_gpu_server* S) { return S ? (int)holder_of(S)->db_format : -1; }
-uint64_t spiral_gpu_server_db_device_bytes(spiral_gpu_server* S) {
-    if (!S) return 0;
-    const spiral_gpu_server* H = holder_of(S);
-    return (uint64_t)(H->db.p ? H->db.words : 0) * 8u + (uint64_t)(H->db_limbs.p ? H->db_limbs.words : 0) * 8u;
-}
+int spiral_gpu_server_db_format(spiral_gpu_server* S) { return S ? (int)S->img->format : -1; }
+uint64_t spiral_gpu_server_db_device_bytes(spiral_gpu_server* S) { return S ? S->img->device_bytes() : 0; }
 
 int spiral_gpu_server_fill_db_random(spiral_gpu_server* S, uint64_t seed) {
     if (!S) return fail("null server");
-    if (S->db_shared) return fail("this server sweeps another server's database image (share_db): load it through the owner");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
-    launch_fill_db_random(S->db.p, S->s.num_per, S->dim0_shard, seed, S->stream);
+    S->img->begin_rewrite();
+    launch_fill_db_random(S->img->db.p, S->s.num_per, S->dim0_shard, seed, S->stream);
     HIP_OK(hipStreamSynchronize(S->stream));
-    srv_db_loaded(S);
+    S->img->finish_load();
     return 0;
 }
 
-// A second in-flight query on the same database: `S` gives up its own image and sweeps `owner`'s (the image is read-only on
-// the answer path).  Same parameters, shard and device; `owner` must stay alive and must not reload its database while `S`
+// A second in-flight query on the same database: `S` gives its own image's reference back and takes one of `owner`'s (the image
+// is read-only on the answer path).  Same parameters, shard and device; `owner` must not reload its database while `S`
 // answers.  With one handle per query lane, each on its own stream, the latency-bound expansion / fold of one query runs
 // under the HBM-bound sweep of the other.
 int spiral_gpu_server_share_db(spiral_gpu_server* S, spiral_gpu_server* owner) {
     if (!S || !owner || S == owner) return fail("share_db needs two different servers");
-    if (owner->db_shared || owner->zombie) return fail("the owner does not own its database image");
+    if (owner->img->owner != owner) return fail("the owner does not own its database image");
     if (S->device != owner->device || S->j0 != owner->j0 || S->dim0_shard != owner->dim0_shard || S->p.nu1 != owner->p.nu1 || S->p.nu2 != owner->p.nu2 ||
         S->s.num_per != owner->s.num_per)
         return fail("share_db: the servers differ in device, shard or database geometry");
     // the image encodes plaintexts mod p_db (centred lift) and the lane's response switch uses ITS p_db: they must agree
     if (S->p.p_db != owner->p.p_db || S->p.direct_upload != owner->p.direct_upload)
         return fail("share_db: the servers differ in plaintext modulus or query form");
-    if (!owner->have_db) return fail("the owner has no database loaded");
+    if (!owner->img->loaded) return fail("the owner has no database loaded");
     HIP_OK(hipSetDevice(S->device));
     HIP_OK(hipStreamSynchronize(S->stream));
     srv_drop_graphs(S);  // captured sweeps hold the old image's address
-    if (S->n_lanes > 0) return fail("share_db: this server's own image is swept by %u lanes", S->n_lanes);
-    if (!S->db_shared) S->db.release();
-    S->db_limbs.release();  // (a second image of the database this server gives up)
-    S->limbs_valid = S->limbs_refused = false;
-    S->db_format = SPIRAL_GPU_DB_PACKED;
-    if (S->db_owner != owner) {
-        lane_detach(S);
-        lane_attach(S, owner);
+    if (S->img->owner == S && S->img->lanes() > 0) return fail("share_db: this server's own image is swept by %u lanes", S->img->lanes());
+    if (S->img != owner->img) {
+        DbImage::drop(S->img, S);
+        S->img = owner->img->share();
     }
-    S->db.p = owner->db.p;
-    S->db.words = owner->db.words;
-    S->db_shared = true;
-    S->have_db = true;
     return 0;
 }
 
@@ -1557,7 +1421,7 @@ int spiral_gpu_server_set_overlap(spiral_gpu_server* S, int on) {
 int spiral_gpu_server_first_dim(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     S->raw_from_acc = false;
     return sweep_one(S, -1);
 }
@@ -1576,7 +1440,7 @@ int spiral_gpu_server_set_sweep_stages(spiral_gpu_server* S, uint32_t n_stages) 
         return fail("%u sweep stages: needs the packed layout, whole 64-column blocks per stage (at most %u stages here) and a ciphertext per rank and stage", n_stages,
                     S->s.num_per / 32);
     // stage-by-stage launches exist for the packed image only: an image a batch has converted to limb planes goes back (its holder's lanes re-capture)
-    if (k_log && holder_of(S)->db_format != SPIRAL_GPU_DB_PACKED && srv_db_set_format(holder_of(S), SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
+    if (k_log && S->img->format != SPIRAL_GPU_DB_PACKED && S->img->set_format(SPIRAL_GPU_DB_PACKED, S->stream)) return -1;
     S->sweep_k_log = k_log;
     srv_drop_graphs(S);
     return 0;
@@ -1592,7 +1456,7 @@ uint32_t spiral_gpu_server_max_sweep_stages(spiral_gpu_server* S) {
 int spiral_gpu_server_first_dim_stage(spiral_gpu_server* S, uint32_t stage) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     if (stage >= (1u << S->sweep_k_log)) return fail("stage %u of %u", stage, 1u << S->sweep_k_log);
     if (S->sweep_k_log == 0) return spiral_gpu_server_first_dim(S);
     S->raw_from_acc = false;
@@ -1612,14 +1476,14 @@ int spiral_gpu_server_first_dim_batch(spiral_gpu_server* const* servers, uint32_
     uint64_t* acc[kMaxLanes];
     server_records(servers, n, qs, acc);
     const uint64_t* limbs;
-    if (limb_image(S0, holder_of(S0), n, &limbs)) return -1;
+    if (limb_image(S0, S0->img, n, &limbs)) return -1;
     if (!limbs && !sweep_batch_ok(S0->s.num_per, 2 * S0->dim0_shard)) {  // (a packed image: limb planes always come back as `limbs`)
         for (uint32_t b = 0; b < n; b++)
             if (spiral_gpu_server_first_dim(servers[b])) return -1;
         return 0;
     }
     if (lanes_join(servers, n)) return -1;  // the lanes' records must be complete
-    if (sweep_image(holder_of(S0), limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
+    if (sweep_image(S0->img, limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
     mark_raw_stale(servers, n);
     return lanes_release(servers, n);
 }
@@ -1941,7 +1805,7 @@ int spiral_gpu_server_run_query(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     if (S->overlap) {  // the split schedule is three launch groups on two streams, not one graph
         if (spiral_gpu_server_run_pre(S)) return -1;
         if (spiral_gpu_server_first_dim(S)) return -1;
@@ -1968,7 +1832,7 @@ int check_instances(const spiral_gpu_server* S, spiral_gpu_server* const* instan
     for (uint32_t k = 0; k < n; k++) {
         const spiral_gpu_server* I = instances[k];
         if (!I) return fail("null instance %u", k);
-        if (!I->have_db) return fail("%s: instance %u has no database", what, k);
+        if (!I->img->loaded) return fail("%s: instance %u has no database", what, k);
         if (I->device != S->device || I->j0 != S->j0 || I->dim0_shard != S->dim0_shard || I->p.nu1 != S->p.nu1 || I->p.nu2 != S->p.nu2 || I->p.p_db != S->p.p_db ||
             I->p.direct_upload != S->p.direct_upload)
             return fail("%s: instance %u differs from the query's server in device, shard, database geometry or plaintext modulus", what, k);
@@ -1980,8 +1844,8 @@ int check_instances(const spiral_gpu_server* S, spiral_gpu_server* const* instan
 // image is in (the holder's epoch covers the form; update_db_items keeps it: captured graphs replay across updates)
 void key_instances(Key* key, spiral_gpu_server* const* instances, uint32_t n, const uint64_t* const* limbs) {
     for (uint32_t k = 0; k < n; k++) {
-        const spiral_gpu_server* H = holder_of(instances[k]);
-        for (uint64_t w : {word(H->db.p), word(limbs ? limbs[k] : nullptr), H->db_epoch, (uint64_t)H->db_format}) key->push_back(w);
+        const DbImage* H = instances[k]->img;
+        for (uint64_t w : {word(H->db.p), word(limbs ? limbs[k] : nullptr), H->epoch, (uint64_t)H->format}) key->push_back(w);
     }
 }
 
@@ -2031,7 +1895,7 @@ int item_rounds(spiral_gpu_server* S, const Lanes& lanes, spiral_gpu_server* con
     lane_records(S, lanes, qs, acc);
     const size_t rw = 6 * kN, ww = wire_bytes(&S->p, 2) / 8;  // (whole words: 2048 values per polynomial)
     for (uint32_t k = 0; k < n_inst; k++) {
-        if (sweep_image(holder_of(instances[k]), limbs ? limbs[k] : nullptr, qs, acc, lanes.n, 0, S->stream)) return -1;
+        if (sweep_image(instances[k]->img, limbs ? limbs[k] : nullptr, qs, acc, lanes.n, 0, S->stream)) return -1;
         if (o.via_resp) {
             if (run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true)) return -1;
             HIP_OK(hipMemcpyAsync(o.resp + k * rw, S->resp.p, 6 * kPolyBytes, hipMemcpyDeviceToDevice, S->stream));
@@ -2097,14 +1961,14 @@ int spiral_gpu_server_run_query_batch(spiral_gpu_server* const* servers, uint32_
     const int rc = run_lanes(
         servers, n, G_BATCH,
         [&](Key* key) {  // (limb_image: not inside the capture, it may build the image)
-            return limb_image(S, holder_of(S), n, &limbs) ? -1 : lane_key(key, servers, n, limbs, {});
+            return limb_image(S, S->img, n, &limbs) ? -1 : lane_key(key, servers, n, limbs, {});
         },
         [&]() {
             if (convert_lanes(S, lanes)) return -1;
             const uint32_t* qs[kMaxLanes];
             uint64_t* acc[kMaxLanes];
             lane_records(S, lanes, qs, acc);
-            if (sweep_image(holder_of(S), limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
+            if (sweep_image(S->img, limbs, qs, acc, n, 0, S->stream)) return -1;  // one pass on the matrix cores where the limb-plane image exists
             return run_fold_rounds(S, S->s.num_per, 0, S->p.nu2, S->acc, false, true, nullptr, lanes);
         });
     if (!rc) mark_swept(servers, n);
@@ -2191,7 +2055,7 @@ int spiral_gpu_server_run_query_batch_instances(spiral_gpu_server* const* server
         [&](Key* key) {
             // each instance image in the form the sweep of B queries reads, converted in place on first use (never inside the capture)
             for (uint32_t k = 0; k < n_inst; k++)
-                if (limb_image(S, holder_of(instances[k]), n, &limbs[k])) return -1;
+                if (limb_image(S, instances[k]->img, n, &limbs[k])) return -1;
             lane_key(key, servers, n, nullptr, {word(responses), word(finals), word(wire), pre != 0});
             key_instances(key, instances, n_inst, limbs.data());
             return 0;
@@ -2260,7 +2124,7 @@ int spiral_gpu_server_run_pre_sweep(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     if (S->overlap) {
         if (spiral_gpu_server_run_pre(S)) return -1;
         return spiral_gpu_server_first_dim(S);
@@ -2289,7 +2153,7 @@ int spiral_gpu_server_run_expand_pack(spiral_gpu_server* S, void* bits_out) {
 int spiral_gpu_server_run_unpack_convert_sweep(spiral_gpu_server* S, const void* gathered) {
     if (!S || !gathered) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     if (int rc = run_graph(S, G_UNPACK_CONVERT_SWEEP, S->stream, {word(gathered)}, [&]() {
             if (spiral_gpu_server_gsw_bits_unpack(S, gathered)) return -1;
             if (spiral_gpu_server_convert(S)) return -1;
@@ -2307,7 +2171,7 @@ int spiral_gpu_server_run_unpack_convert_sweep(spiral_gpu_server* S, const void*
 int spiral_gpu_server_run_scal2mat_sweep(spiral_gpu_server* S) {
     if (!S) return fail("null server");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     if (int rc = run_graph(S, G_SCAL2MAT_SWEEP, S->stream, {}, [&]() {
             if (convert_scal2mat(S, S->stream)) return -1;
             return spiral_gpu_server_first_dim(S);
@@ -2343,7 +2207,7 @@ namespace {
 // ciphertext ii = g + G k at (g n + b) L + k.  One pass on the matrix cores where the image is in limb-plane form, else passes of two on the vector
 // ALU; a geometry neither kernel covers sweeps each query into its own accumulators and copies its G chunks into place (one strided copy).
 int sweep_rank_major(spiral_gpu_server* S, const Lanes& lanes, const uint64_t* limbs, uint64_t* acc_out) {
-    const spiral_gpu_server* H = holder_of(S);
+    const DbImage* H = S->img;
     const uint32_t n = lanes.n, G = 1u << S->fold_g_log, L = S->s.num_per >> S->fold_g_log, np = S->s.num_per, jm = 2 * S->dim0_shard;
     const size_t chunk = (size_t)L * 6 * kN;
     const uint32_t* qs[kMaxLanes];
@@ -2375,7 +2239,7 @@ int spiral_gpu_server_run_pre_sweep_batch(spiral_gpu_server* const* servers, uin
     spiral_gpu_server* S = servers[0];
     if (S->ex_shard.g_log) return fail("%s: the expansion is sharded: run_expand_pack_batch, the all-gather, then run_unpack_convert_sweep_batch", what);
     const uint64_t* limbs;
-    if (limb_image(S, holder_of(S), n, &limbs)) return -1;  // (not inside a capture: it may convert the image)
+    if (limb_image(S, S->img, n, &limbs)) return -1;  // (not inside a capture: it may convert the image)
     const int rc = run_lanes(servers, n, G_SHARD_PRE_SWEEP, [&](Key* k) { return lane_key(k, servers, n, limbs, {word(acc)}); }, [&]() {
         if (convert_lanes(S, lanes)) return -1;
         return sweep_rank_major(S, lanes, limbs, (uint64_t*)acc);
@@ -2404,7 +2268,7 @@ int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server* const* s
     if (!gathered_bits || !acc) return fail("%s: null buffer", what);
     spiral_gpu_server* S = servers[0];
     const uint64_t* limbs;
-    if (limb_image(S, holder_of(S), n, &limbs)) return -1;
+    if (limb_image(S, S->img, n, &limbs)) return -1;
     const int rc = run_lanes(servers, n, G_SHARD_UNPACK_SWEEP, [&](Key* k) { return lane_key(k, servers, n, limbs, {word(gathered_bits), word(acc)}); }, [&]() {
         launch_gsw_bits_unpack_lanes(S->cv.p, (const uint64_t*)gathered_bits, 1u << S->ex_shard.g_log, S->s.ell * S->p.nu2, lanes, S->stream);
         if (convert_part(S, CONV_BOTH, S->stream, false, lanes)) return -1;
@@ -2637,7 +2501,7 @@ int spiral_gpu_server_write_raw(spiral_gpu_server* S, const uint64_t* raw_cts) {
 int spiral_gpu_server_time_sweep(spiral_gpu_server* S, int iters, float* avg_ms) {
     if (!S || !avg_ms || iters <= 0) return fail("bad argument");
     HIP_OK(hipSetDevice(S->device));
-    if (!S->have_db) return fail("no database loaded");
+    if (!S->img->loaded) return fail("no database loaded");
     HIP_OK(hipSetDevice(S->device));
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
@@ -2661,11 +2525,11 @@ int spiral_gpu_server_time_sweep_batch(spiral_gpu_server* const* servers, uint32
     server_records(servers, n, qs, acc);
     mark_raw_stale(servers, n);
     const uint64_t* limbs;
-    if (limb_image(S, holder_of(S), n, &limbs)) return -1;
+    if (limb_image(S, S->img, n, &limbs)) return -1;
     HIP_OK(hipDeviceSynchronize());  // (the lanes' streams: their records are complete)
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
-        if (sweep_image(holder_of(S), limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
+        if (sweep_image(S->img, limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
     HIP_OK(hipEventRecord(S->ev[1], S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     float ms = 0;

@@ -674,7 +674,8 @@ def test_two_query_lanes_share_one_database(sa, oracle):
 
 def test_lane_created_on_the_owners_image(sa, oracle):
     """create_lane (Server(share_db_of=...)): a query lane that never allocates an image of its own; a server with another
-    plaintext modulus cannot share (its response switch would use the wrong modulus); column read-back == slot read-back"""
+    plaintext modulus cannot share (its response switch would use the wrong modulus); column read-back == slot read-back; the lanes go on
+    answering after their owner was destroyed"""
     O = oracle
     from spiral_amd import server as SV
 
@@ -707,8 +708,16 @@ def test_lane_created_on_the_owners_image(sa, oracle):
         assert_eq(owner.read_db_columns(ii0, n), slabs[:, ii0:ii0 + n], f"columns {ii0}..{ii0 + n - 1}")
     with pytest.raises(RuntimeError):
         owner.read_db_columns(7, 2)
+    lane2 = sa.Server(pg, share_db_of=owner)
+    lane2.set_pub_params(*pp)
+    owner.close()  # the lanes keep the image alive
+    for k, srv in enumerate((lane, lane2)):
+        q = cl.query(130 + k)
+        fin, resp, _ = srv.answer(q)
+        assert_eq(fin, O.answer(po, q, *pp, db), f"lane {k} after its owner was destroyed")
+        assert_eq(cl.decode(resp), O.db_item(po, 31, 130 + k), "decoded plaintext")
     lane.close()
-    owner.close()
+    lane2.close()
 
 
 @pytest.mark.parametrize("nu1,nu2,n", [(4, 5, 2), (3, 6, 3), (3, 5, 4), (5, 3, 3), (6, 6, 4), (6, 6, 7)])
