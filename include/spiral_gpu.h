@@ -237,7 +237,8 @@ int spiral_gpu_server_share_db(spiral_gpu_server *s, spiral_gpu_server *owner);
 int spiral_gpu_server_create_lane(spiral_gpu_server *owner, spiral_gpu_server **out);
 
 /* public parameters (NTT form): W_exp_left g x (n0 x t_exp), W_exp_right n_right x (n0 x t_exp_right),
- * W n1 x (n0*t_conv), V n1 x (2*t_conv)   (src/spiral.cpp:2091-2092, 2216-2227, 2279-2296) */
+ * W n1 x (n0*t_conv), V n1 x (2*t_conv)   (src/spiral.cpp:2091-2092, 2216-2227, 2279-2296).  A null pointer among those the geometry needs
+ * fails before anything is written: the previous public parameters stay. */
 int spiral_gpu_server_set_pub_params(spiral_gpu_server *s, const uint64_t *w_left, const uint64_t *w_right,
                                      const uint64_t *w, const uint64_t *v);
 /* query: n_query_cts Regev ciphertexts, n0 x 1 NTT form */
@@ -538,7 +539,8 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server *s, uint32_t tri
  * trial image's current form, on this server's stream, with the same rules for failure and ordering; any other trial fails. */
 int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server *s, uint32_t trial, const void *items, uint32_t coeff_bits,
                                            const uint64_t *item_ids, uint64_t n);
-/* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv) */
+/* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv).  A null pointer
+ * among those the geometry needs fails before anything is written: the previous public parameters stay (as for spiral_gpu_server_set_pub_params). */
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server *s, const uint64_t *w_left, const uint64_t *w_right,
                                           const uint64_t *v, const uint64_t *v_w);
 /* response: (out_n+1) x out_n raw, row 0 mod q', rows 1.. mod 4p; packed_ct (may be NULL): the (out_n+1) x out_n NTT
@@ -559,7 +561,8 @@ uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algor
  * conversion per lane, ONE first-dimension pass over every trial image for all n queries, then folding, packing and the modulus switch per lane,
  * all on servers[0]'s stream; returns synchronised.  Afterwards every lane's buffers (read_acc of every trial, read_response_wire) hold exactly
  * what its own answer would have left.  responses[b] / packed_cts[b] (or the arrays) may be NULL.  stage_us (may be NULL): [0] expansion [1]
- * conversion [3] folding [4] packing, summed over the lanes, [2] = [5] the shared sweep, [6] total, [7] n.  Every server is checked before anything
+ * conversion [3] folding [4] packing, summed over the lanes, [2] = [5] the shared sweep, [6] total, [7] n.  Every query is uploaded before the first
+ * launch, so [6] (and answer_batch_instances' total_us) is device time of the launches alone, in every form of the queries.  Every server is checked before anything
  * is launched (n in 1 .. 8, no duplicates, same image, parameters, database and public parameters present): a failing check leaves every lane's
  * previous results intact.  n = 1 is answer.
  * The shared pass runs on the matrix cores (csrc/sweep_mfma.hip, the base path's kernel with 2-row records) from the LIMBS form of the trial

@@ -54,69 +54,41 @@ static size_t bits_to_bytes(size_t bits) { return (size_t)std::llround((double)b
 // polynomials back to raw form (spiral_gpu_from_ntt) and packs them at 7 bytes per coefficient; the server decodes them on the device
 static bool g_wire = false;
 static uint64_t g_wire_offline = 0, g_wire_online = 0;  // bytes the first client actually sent
-struct Segment {
-    const Poly* ntt;
-    size_t npolys;
-};
-static std::vector<uint8_t> wire_of(std::initializer_list<Segment> segs) {
-    size_t n = 0;
-    for (const Segment& g : segs) n += g.npolys;
-    Poly raw(n * N);
-    size_t at = 0;
-    for (const Segment& g : segs) {
-        if (g.npolys) GPU_OK(spiral_gpu_from_ntt(raw.data() + at * N, g.ntt->data(), g.npolys));
-        at += g.npolys;
-    }
-    std::vector<uint8_t> w(n * 7 * N);
-    GPU_OK(spiral_gpu_raw_to_wire(raw.data(), n, w.data()));
-    return w;
-}
-static std::vector<uint8_t> query_wire(const Poly& q) { return wire_of({{&q, q.size() / (2 * N)}}); }
-static std::vector<uint8_t> pp_wire(const spiral_gpu_params& p, const spiral_gpu_shape& s, const Client& c) {
-    return wire_of({{&c.w_left, (size_t)s.n_left * 2 * p.t_exp}, {&c.w_right, (size_t)s.n_right * 2 * p.t_exp_right}, {&c.w, (size_t)6 * p.t_conv},
-                    {&c.v, (size_t)6 * p.t_conv}});
-}
-static std::vector<uint8_t> pack_pp_wire(const spiral_gpu_params& p, const spiral_gpu_pack_shape& s, uint32_t out_n, const PackClient& c) {
-    const bool ex = !p.direct_upload;
-    return wire_of({{&c.w_left, ex ? (size_t)s.n_left * 2 * p.t_exp : 0}, {&c.w_right, ex ? (size_t)s.n_right * 2 * p.t_exp_right : 0},
-                    {&c.v, ex ? (size_t)4 * p.t_conv : 0}, {&c.v_w, (size_t)out_n * (out_n + 1) * p.t_conv}});
-}
 // --seeded (implies --wire-input): the seeded form instead (include/spiral_gpu.h spiral_gpu_query_seeded_bytes): each message is the client's seed
 // followed by the wire form of its matrices without their row 0, which the client took from spiral_gpu_seed_expand (client.cpp Row0)
 static bool g_seeded = false;
-static std::vector<uint8_t> seeded_of(const uint8_t* seed, std::initializer_list<Segment> segs, std::initializer_list<uint32_t> rows,
-                                      std::initializer_list<uint32_t> cols) {
-    std::vector<const uint64_t*> sent;  // rows 1.. of every matrix, message order
-    auto r = rows.begin(), c = cols.begin();
-    for (const Segment& g : segs) {
-        for (size_t i = 0; i < g.npolys; i++)
-            if (i % ((size_t)*r * *c) >= *c) sent.push_back(g.ntt->data() + i * 2 * N);
-        ++r, ++c;
-    }
+// A message is up to four parts, each `count` matrices of [rows][cols] NTT-form polynomials back to back
+struct Part {
+    const Poly* ntt;
+    size_t count;
+    uint32_t rows, cols;
+};
+// the message of `parts`: their wire form (seed null), or the seed and then the wire form of rows 1.. of every matrix
+static std::vector<uint8_t> message_of(std::initializer_list<Part> parts, const uint8_t* seed) {
+    std::vector<const uint64_t*> sent;  // message order
+    for (const Part& g : parts)
+        for (size_t i = 0; i < g.count * g.rows * g.cols; i++)
+            if (!seed || i % ((size_t)g.rows * g.cols) >= g.cols) sent.push_back(g.ntt->data() + i * 2 * N);
     Poly ntt(sent.size() * 2 * N), raw(sent.size() * N);
     for (size_t i = 0; i < sent.size(); i++) std::copy(sent[i], sent[i] + 2 * N, ntt.begin() + i * 2 * N);
     if (!sent.empty()) GPU_OK(spiral_gpu_from_ntt(raw.data(), ntt.data(), sent.size()));
-    std::vector<uint8_t> w(32 + sent.size() * 7 * N);
-    std::copy(seed, seed + 32, w.begin());
-    GPU_OK(spiral_gpu_raw_to_wire(raw.data(), sent.size(), w.data() + 32));
+    const size_t head = seed ? 32 : 0;
+    std::vector<uint8_t> w(head + sent.size() * 7 * N);
+    if (seed) std::copy(seed, seed + 32, w.begin());
+    GPU_OK(spiral_gpu_raw_to_wire(raw.data(), sent.size(), w.data() + head));
     return w;
 }
-// what a client sends: a query (with the seed its row 0 came from) and its public parameters
-static std::vector<uint8_t> query_msg(const Query& q) {
-    return g_seeded ? seeded_of(q.seed.data(), {{&q.cts, q.cts.size() / (2 * N)}}, {2}, {1}) : query_wire(q.cts);
-}
+// what a client sends: a query (with the seed its row 0 came from) and its public parameters.  SpiralPack on a direct-upload geometry sends v_W alone
+static std::vector<uint8_t> query_msg(const Query& q) { return message_of({{&q.cts, q.cts.size() / (4 * N), 2, 1}}, g_seeded ? q.seed.data() : nullptr); }
 static std::vector<uint8_t> pp_msg(const spiral_gpu_params& p, const spiral_gpu_shape& s, const Client& c) {
-    if (!g_seeded) return pp_wire(p, s, c);
-    return seeded_of(c.pp_seed, {{&c.w_left, (size_t)s.n_left * 2 * p.t_exp}, {&c.w_right, (size_t)s.n_right * 2 * p.t_exp_right}, {&c.w, (size_t)6 * p.t_conv},
-                                 {&c.v, (size_t)6 * p.t_conv}},
-                     {2, 2, 3, 3}, {p.t_exp, p.t_exp_right, 2 * p.t_conv, 2 * p.t_conv});
+    return message_of({{&c.w_left, s.n_left, 2, p.t_exp}, {&c.w_right, s.n_right, 2, p.t_exp_right}, {&c.w, 1, 3, 2 * p.t_conv}, {&c.v, 1, 3, 2 * p.t_conv}},
+                      g_seeded ? c.pp_seed : nullptr);
 }
 static std::vector<uint8_t> pack_pp_msg(const spiral_gpu_params& p, const spiral_gpu_pack_shape& s, uint32_t out_n, const PackClient& c) {
-    if (!g_seeded) return pack_pp_wire(p, s, out_n, c);
-    const bool ex = !p.direct_upload;
-    return seeded_of(c.pp_seed, {{&c.w_left, ex ? (size_t)s.n_left * 2 * p.t_exp : 0}, {&c.w_right, ex ? (size_t)s.n_right * 2 * p.t_exp_right : 0},
-                                 {&c.v, ex ? (size_t)4 * p.t_conv : 0}, {&c.v_w, (size_t)out_n * (out_n + 1) * p.t_conv}},
-                     {2, 2, 2, out_n + 1}, {p.t_exp, p.t_exp_right, 2 * p.t_conv, p.t_conv});
+    const size_t ex = p.direct_upload ? 0 : 1;
+    return message_of({{&c.w_left, ex * s.n_left, 2, p.t_exp}, {&c.w_right, ex * s.n_right, 2, p.t_exp_right}, {&c.v, ex, 2, 2 * p.t_conv},
+                       {&c.v_w, out_n, out_n + 1, p.t_conv}},
+                      g_seeded ? c.pp_seed : nullptr);
 }
 static int set_query_msg(spiral_gpu_server* s, const std::vector<uint8_t>& m) {
     return g_seeded ? spiral_gpu_server_set_query_seeded(s, m.data(), m.size()) : spiral_gpu_server_set_query_wire(s, m.data(), m.size());

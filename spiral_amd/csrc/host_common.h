@@ -464,163 +464,6 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
     return 0;
 }
 
-// ---- query and key ingest of both servers ----------------------------------------------------------------------------------------
-// NTT form: stage a host buffer of reference NTT-form polynomials ([2][N] u64 each) through `stage` and convert to PK
-inline int upload_ref_ntt(DevBuf& stage, hipStream_t st, const uint64_t* host, uint64_t* pk, size_t npolys) {
-    if (npolys == 0) return 0;
-    if (!host) return fail("null host buffer");
-    const size_t chunk = 4096;  // polynomials per staging pass (128 MiB)
-    if (stage.words < std::min(npolys, chunk) * kRefNtt) {
-        stage.release();
-        if (stage.alloc(std::min(npolys, chunk) * kRefNtt)) return -1;
-    }
-    for (size_t done = 0; done < npolys; done += chunk) {
-        const size_t n = std::min(chunk, npolys - done);
-        HIP_OK(hipMemcpyAsync(stage.p, host + done * kRefNtt, n * kRefNtt * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        launch_ref_to_pk(stage.p, pk + done * kN, (uint32_t)n, identity_map(), st);
-        HIP_OK(hipStreamSynchronize(st));
-    }
-    return 0;
-}
-
-// Wire form (include/spiral_gpu.h): one message = the segments' polynomials back to back, 7 bytes per raw coefficient.  The bytes go up through a
-// device staging buffer a chunk at a time and each chunk is decoded + transformed straight into its PK destination by one launch (LD_WIRE); the
-// launches and copies are ordered by the stream, so the host waits once, at the end, and then reads the lowest index of a coefficient above Q.
-// The error word is tagged with the call's generation instead of being reset, and read back through a pinned word (messages of at most
-// kWireHostCheckPolys polynomials are checked on the host instead: one copy up, one launch).  On failure the destinations hold a partial message: the caller drops what they held (have_query / have_pp).
-// Seeded form (ingest_seeded): a 32-byte seed, then the wire form of every matrix without its row 0.  A segment is then a run of [rows][cols]
-// matrices; row 0 of each is generated on the device from the seed (seed.hip, one launch per segment, queued ahead of the copies), and LD_WIRE's
-// destination map steps over it.  Everything else -- staging, error word, the one synchronisation -- is the wire form's.
-struct WireSegment {
-    uint64_t* pk;   // PK destination
-    size_t npolys;
-    uint32_t rows = 1, cols = 1;  // seeded form: npolys / (rows * cols) matrices [rows][cols] back to back (rows >= 2)
-};
-struct WireIn {  // a server's ingest workspace, reused from call to call
-    DevBuf stage;                // [chunk bytes][u64 error word]
-    size_t chunk_polys = 0;
-    uint64_t* host_err = nullptr;  // pinned
-    uint32_t gen = 0;
-    void release() {
-        stage.release();
-        stage.words = 0;
-        chunk_polys = 0;
-        if (host_err) (void)hipHostFree(host_err);
-        host_err = nullptr;
-    }
-};
-constexpr size_t kWireChunkPolys = 4096;  // polynomials per staging pass (56 MiB)
-// Up to this many polynomials (a compressed query: 2) the host checks the coefficients before anything goes up -- about 1 ns per coefficient, less
-// than the readback of the device's error word, which is then skipped (a 2-polynomial set_query_wire took 34 us with the readback, set_query 28)
-constexpr size_t kWireHostCheckPolys = 4;
-inline int64_t wire_first_above_q(const uint8_t* b, size_t n) {
-    for (size_t i = 0; i < n; i++, b += kWireCoeffBytes) {
-        uint64_t v = 0;
-        memcpy(&v, b, kWireCoeffBytes);  // (little-endian host)
-        if (v > kQ) return (int64_t)i;
-    }
-    return -1;
-}
-// seed: null for the wire form; else the message's seed and `domain` its row-0 domain tag (seed_device.h), with `wire` and `bytes` the rest
-inline int ingest_message(WireIn& W, const DeviceTables& tb, hipStream_t st, const uint8_t* seed, uint32_t domain, const void* wire, size_t bytes,
-                          const WireSegment* seg, size_t nseg, const char* what) {
-    size_t npolys = 0, nrow0 = 0;  // polynomials sent, row-0 polynomials (seeded)
-    for (size_t i = 0; i < nseg; i++) {
-        if (!seed) {
-            npolys += seg[i].npolys;
-            continue;
-        }
-        const size_t mat = (size_t)seg[i].rows * seg[i].cols;
-        if (seg[i].rows < 2 || seg[i].npolys % mat) return fail("%s: segment %zu is not a run of matrices with rows >= 2", what, i);
-        npolys += seg[i].npolys - seg[i].npolys / seg[i].rows;
-        nrow0 += seg[i].npolys / seg[i].rows;
-    }
-    if (!wire) return fail("%s: null wire buffer", what);
-    if (seed && bytes != npolys * kWirePolyBytes)
-        return fail("%s: %zu bytes, the seeded form of %zu polynomials (%zu of them row 0) takes %zu", what, bytes + kSeedBytes, npolys + nrow0, nrow0,
-                    kSeedBytes + npolys * kWirePolyBytes);
-    if (bytes != npolys * kWirePolyBytes)
-        return fail("%s: %zu bytes, the wire form of %zu polynomials takes %zu", what, bytes, npolys, npolys * kWirePolyBytes);
-    if ((uint64_t)npolys * kN >= 0xffffffffull) return fail("%s: %zu polynomials exceed the coefficient index range", what, npolys);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_OK(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail("%s: the server's stream is capturing (call it outside stream capture)", what);
-    if (npolys == 0) return 0;
-    const bool host_checked = npolys <= kWireHostCheckPolys;
-    if (host_checked) {
-        const int64_t i = wire_first_above_q((const uint8_t*)wire, npolys * kN);
-        if (i >= 0) return fail("%s: coefficient %u (polynomial %u, index %u) is above Q", what, (uint32_t)i, (uint32_t)i / kN, (uint32_t)i % kN);
-    }
-    const size_t chunk = std::min(npolys, kWireChunkPolys);
-    if (W.chunk_polys < chunk || W.gen == 0xffffffffu) {  // (re)allocated: the error word starts at generation 0 (all ones)
-        W.stage.release();
-        W.chunk_polys = 0;
-        if (W.stage.alloc(chunk * kWirePolyBytes / 8 + 1)) return -1;
-        HIP_OK(hipMemset(W.stage.p + chunk * kWirePolyBytes / 8, 0xff, sizeof(uint64_t)));
-        W.chunk_polys = chunk;
-        W.gen = 0;
-    }
-    if (!W.host_err) HIP_OK(hipHostMalloc((void**)&W.host_err, sizeof(uint64_t), hipHostMallocDefault));
-    const uint32_t gen = ++W.gen;
-    uint8_t* d_wire = reinterpret_cast<uint8_t*>(W.stage.p);
-    uint64_t* d_err = W.stage.p + W.chunk_polys * kWirePolyBytes / 8;
-    if (seed) {  // row 0 first: it needs nothing from the copies, so the device generates it while the host queues them
-        size_t k = 0;
-        for (size_t i = 0; i < nseg; i++) {
-            const uint32_t r = seg[i].rows, c = seg[i].cols;
-            launch_seed_rows(seed, domain, k, seg[i].pk, IndexMap{c, r * c, 0u}, (uint32_t)(seg[i].npolys / r), st);
-            k += seg[i].npolys / r;
-        }
-    }
-    FwdParams fp{};
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
-    fp.items = d_wire;
-    fp.err = reinterpret_cast<uint32_t*>(d_err);
-    fp.seed = gen;
-    size_t first = 0;  // message index of the segment's first polynomial
-    for (size_t i = 0; i < nseg; i++) {
-        // the polynomials sent of a segment: runs of `inner` (rows 1.. of a matrix), `outer` apart in the destination, `off` after its start
-        const uint32_t r = seed ? seg[i].rows : 1u, c = seed ? seg[i].cols : 1u, inner = seed ? (r - 1u) * c : 1u, outer = r * c, off = seed ? c : 0u;
-        const size_t sent = seg[i].npolys / outer * inner;
-        if (sent == 0) continue;  // (an absent matrix: W_exp on a direct-upload geometry)
-        const size_t step = W.chunk_polys / inner * inner;  // (whole runs per chunk: a chunk's destination is one map from one base)
-        if (step == 0) return fail("%s: a matrix of %u x %u polynomials exceeds the staging chunk", what, r, c);
-        fp.dst_map = IndexMap{inner, outer, off};
-        for (size_t done = 0; done < sent; done += step) {
-            const size_t n = std::min(step, sent - done);
-            HIP_OK(hipMemcpyAsync(d_wire, (const uint8_t*)wire + (first + done) * kWirePolyBytes, n * kWirePolyBytes, hipMemcpyHostToDevice, st));
-            fp.dst = seg[i].pk + done / inner * outer * kN;
-            fp.item_base = first + done;
-            launch_ntt_forward(tb, fp, LD_WIRE, ST_PK, (uint32_t)n, st);
-        }
-        first += sent;
-    }
-    HIP_OK(hipGetLastError());
-    if (host_checked) {
-        HIP_OK(hipStreamSynchronize(st));
-        return 0;
-    }
-    HIP_OK(hipMemcpyAsync(W.host_err, d_err, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    const uint64_t err = *W.host_err;
-    if ((uint32_t)(err >> 32) == ~gen) {
-        const uint32_t i = (uint32_t)err;
-        return fail("%s: coefficient %u (polynomial %u, index %u) is above Q", what, i, i / kN, i % kN);
-    }
-    return 0;
-}
-inline int ingest_wire(WireIn& W, const DeviceTables& tb, hipStream_t st, const void* wire, size_t bytes, const WireSegment* seg, size_t nseg,
-                       const char* what) {
-    return ingest_message(W, tb, st, nullptr, 0, wire, bytes, seg, nseg, what);
-}
-inline int ingest_seeded(WireIn& W, const DeviceTables& tb, hipStream_t st, const void* msg, size_t bytes, uint32_t domain, const WireSegment* seg,
-                         size_t nseg, const char* what) {
-    if (!msg) return fail("%s: null message", what);
-    if (bytes < kSeedBytes) return fail("%s: %zu bytes, shorter than the %u-byte seed", what, bytes, kSeedBytes);
-    return ingest_message(W, tb, st, (const uint8_t*)msg, domain, (const uint8_t*)msg + kSeedBytes, bytes - kSeedBytes, seg, nseg, what);
-}
-
 // upload reference NTT-form polynomials and convert to PK / the converse
 inline uint64_t* upload_pk(Scratch& sc, const uint64_t* host_ref, size_t npolys) {
     uint64_t* d_ref = sc.upload(host_ref, npolys * kRefNtt);

@@ -2,6 +2,7 @@
 // src/testing.cpp:1009-1081).  Kernels: pack.hip, ntt.hip (LD_PDIGIT / LD_DBGEN1), poly.hip (matmul, rescale), sweep_mfma.hip (the batched
 // first-dimension sweep of answer_batch: several lanes' queries in one pass over the trial images, from their limb-plane form).
 #include "db_image.h"
+#include "message.h"
 
 using namespace spiral;
 using namespace spiral::host;
@@ -20,7 +21,7 @@ struct spiral_gpu_pack_server {
     uint32_t n_cv = 0;
     DevBuf w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
     DevBuf gs_raw, gs_chat, gs_tmp, gsw, key, qs1, acc, raw, fold_d, fold_c, fold_c2, pk_ginv, pk_ct2, pk_res, pk_raw, resp, stage, wire;
-    WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
+    WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
     hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch / item call end, [8] ordering another call's stream in front of an item call
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
     // the trial images this server sweeps (db_image.h): its own, or its owner's, of which a query lane (create_lane) holds a reference and
@@ -113,7 +114,33 @@ int pk_alloc(spiral_gpu_pack_server* S, DbImage* owners) {
     return 0;
 }
 
-int pk_upload_ref_ntt(spiral_gpu_pack_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) { return host::upload_ref_ntt(S->stage, S->stream, host, pk, npolys); }
+// The two ways client input gets into a server, in any form (message.h); both return synchronised.  A null NTT-form buffer is refused with the previous
+// message untouched; from the first write on nothing answers from half-written keys: have_pp is cleared, and set again on success.
+int pk_take_pub_params(spiral_gpu_pack_server* S, Form form, const MessageIn& in, const char* what) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const MessageLayout m = pack_pub_params_layout(S->p, S->s, S->out_n);
+    if (form == FORM_NTT && check_ntt_parts(m, in, what)) return -1;
+    uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->v.p, S->v_w.p};
+    S->have_pp = false;
+    if (ingest(form, IngestOn{S->stage, S->wire_in, S->tb, S->stream}, m, dst, in, what)) return -1;
+    S->have_pp = true;
+    return 0;
+}
+// the query into S->query, on S's own stream, before the first launch of the call that answers it (`query`: the NTT form's polynomials or the message)
+int pk_take_query(spiral_gpu_pack_server* S, Form form, const void* query, size_t bytes, const char* what) {
+    HIP_OK(hipSetDevice(S->device));
+    const MessageLayout m = pack_query_layout(S->p, S->s, S->out_n);
+    const MessageIn in = form == FORM_NTT ? MessageIn{{(const uint64_t*)query}, nullptr, 0} : MessageIn{{}, query, bytes};
+    uint64_t* const dst[kMessageParts] = {S->query.p};
+    return ingest(form, IngestOn{S->stage, S->wire_in, S->tb, S->stream}, m, dst, in, what);
+}
+// a message's bytes in the wire / seeded form for parameters SpiralPack accepts, else 0
+size_t pack_message_bytes(const spiral_gpu_params* p, uint32_t out_n, MessageLayout (*layout)(const spiral_gpu_params&, const spiral_gpu_pack_shape&, uint32_t),
+                          Form form) {
+    spiral_gpu_pack_shape s;
+    return !p || pack_shape_of(p, out_n, &s) ? 0 : message_bytes(layout(*p, s, out_n), form);
+}
 
 // pack (src/testing.cpp:198-241) on device buffers: raw cts at trial stride `ct_stride` polynomials
 // n_inst > 1: an item group, n_inst instances' trials one after another in raw_cts, ginv, ct2 and result (answer_batch_instances)
@@ -414,88 +441,34 @@ int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t se
     return 0;
 }
 
+// the public parameters in their three forms (include/spiral_gpu.h): W_exp_left, W_exp_right, V (expansion only), v_W
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server* S, const uint64_t* w_left, const uint64_t* w_right, const uint64_t* v,
                                           const uint64_t* v_w) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const spiral_gpu_params& p = S->p;
-    if (!p.direct_upload) {
-        if (pk_upload_ref_ntt(S, w_left, S->w_left.p, (size_t)S->s.n_left * 2 * p.t_exp)) return -1;
-        if (pk_upload_ref_ntt(S, w_right, S->w_right.p, (size_t)S->s.n_right * 2 * p.t_exp_right)) return -1;
-        if (pk_upload_ref_ntt(S, v, S->v.p, (size_t)2 * 2 * p.t_conv)) return -1;
-    }
-    if (pk_upload_ref_ntt(S, v_w, S->v_w.p, (size_t)S->out_n * (S->out_n + 1) * p.t_conv)) return -1;
-    S->have_pp = true;
-    return 0;
+    return pk_take_pub_params(S, FORM_NTT, MessageIn{{w_left, w_right, v, v_w}, nullptr, 0}, "set_pub_params");
 }
-
-// the same from the wire form: one message W_exp_left, W_exp_right, V (expansion only), v_W; a failure leaves no public parameters
 int spiral_gpu_pack_server_set_pub_params_wire(spiral_gpu_pack_server* S, const void* wire, size_t bytes) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const spiral_gpu_params& p = S->p;
-    const bool ex = !p.direct_upload;
-    const WireSegment seg[4] = {{S->w_left.p, ex ? (size_t)S->s.n_left * 2 * p.t_exp : 0},
-                                {S->w_right.p, ex ? (size_t)S->s.n_right * 2 * p.t_exp_right : 0},
-                                {S->v.p, ex ? (size_t)2 * 2 * p.t_conv : 0},
-                                {S->v_w.p, (size_t)S->out_n * (S->out_n + 1) * p.t_conv}};
-    S->have_pp = false;
-    if (ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, seg, 4, "set_pub_params_wire")) return -1;
-    S->have_pp = true;
-    return 0;
+    return pk_take_pub_params(S, FORM_WIRE, MessageIn{{}, wire, bytes}, "set_pub_params_wire");
 }
-
-// the same from the seeded form: row 0 of every matrix from the message's seed (include/spiral_gpu.h)
 int spiral_gpu_pack_server_set_pub_params_seeded(spiral_gpu_pack_server* S, const void* msg, size_t bytes) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const spiral_gpu_params& p = S->p;
-    const bool ex = !p.direct_upload;
-    const WireSegment seg[4] = {{S->w_left.p, ex ? (size_t)S->s.n_left * 2 * p.t_exp : 0, 2, p.t_exp},
-                                {S->w_right.p, ex ? (size_t)S->s.n_right * 2 * p.t_exp_right : 0, 2, p.t_exp_right},
-                                {S->v.p, ex ? (size_t)2 * 2 * p.t_conv : 0, 2, 2 * p.t_conv},
-                                {S->v_w.p, (size_t)S->out_n * (S->out_n + 1) * p.t_conv, S->out_n + 1, p.t_conv}};
-    S->have_pp = false;
-    if (ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_PACK_PUB_PARAMS, seg, 4, "set_pub_params_seeded")) return -1;
-    S->have_pp = true;
-    return 0;
+    return pk_take_pub_params(S, FORM_SEEDED, MessageIn{{}, msg, bytes}, "set_pub_params_seeded");
 }
 
-size_t spiral_gpu_pack_query_seeded_bytes(const spiral_gpu_params* p, uint32_t out_n) {
-    spiral_gpu_pack_shape s;
-    if (!p || pack_shape_of(p, out_n, &s)) return 0;
-    return kSeedBytes + (size_t)s.n_query_cts * kWirePolyBytes;
-}
-
-size_t spiral_gpu_pack_pub_params_seeded_bytes(const spiral_gpu_params* p, uint32_t out_n) {
-    spiral_gpu_pack_shape s;
-    if (!p || pack_shape_of(p, out_n, &s)) return 0;
-    const size_t ex = p->direct_upload ? 0 : (size_t)s.n_left * p->t_exp + (size_t)s.n_right * p->t_exp_right + (size_t)2 * p->t_conv;
-    return kSeedBytes + (ex + (size_t)out_n * out_n * p->t_conv) * kWirePolyBytes;
-}
-
-size_t spiral_gpu_pack_query_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) {
-    spiral_gpu_pack_shape s;
-    if (!p || pack_shape_of(p, out_n, &s)) return 0;
-    return (size_t)s.n_query_cts * 2 * kWirePolyBytes;
-}
-
+size_t spiral_gpu_pack_query_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) { return pack_message_bytes(p, out_n, pack_query_layout, FORM_WIRE); }
+size_t spiral_gpu_pack_query_seeded_bytes(const spiral_gpu_params* p, uint32_t out_n) { return pack_message_bytes(p, out_n, pack_query_layout, FORM_SEEDED); }
 size_t spiral_gpu_pack_pub_params_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) {
-    spiral_gpu_pack_shape s;
-    if (!p || pack_shape_of(p, out_n, &s)) return 0;
-    const size_t ex = p->direct_upload ? 0 : (size_t)s.n_left * 2 * p->t_exp + (size_t)s.n_right * 2 * p->t_exp_right + (size_t)2 * 2 * p->t_conv;
-    return (ex + (size_t)out_n * (out_n + 1) * p->t_conv) * kWirePolyBytes;
+    return pack_message_bytes(p, out_n, pack_pub_params_layout, FORM_WIRE);
+}
+size_t spiral_gpu_pack_pub_params_seeded_bytes(const spiral_gpu_params* p, uint32_t out_n) {
+    return pack_message_bytes(p, out_n, pack_pub_params_layout, FORM_SEEDED);
 }
 
 // The answer up to and including the folding, for this server's trials, in three pieces (pk_front; answer_batch puts one shared sweep between the
 // lanes' first and last pieces): the folded ciphertexts end up at the head of each trial's num_per slots of S->raw (events 0..5 bracket the stages).
-// Piece 1: query upload (none with query = null: the wire entry points decoded it into S->query), expansion and conversion -> the sweep's records qs1 and the folding keys, on `st`
-static int pk_expand_convert(spiral_gpu_pack_server* S, const uint64_t* query, hipStream_t st) {
+// Piece 1: expansion and conversion of the query in S->query (pk_take_query) -> the sweep's records qs1 and the folding keys, on `st`
+static int pk_expand_convert(spiral_gpu_pack_server* S, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
     const uint32_t ell = s.ell, ngs = p.nu2 * ell;
-    if (query && pk_upload_ref_ntt(S, query, S->query.p, (size_t)s.n_query_cts * 2)) return -1;  // (null: decoded from the wire form already)
-
     HIP_OK(hipEventRecord(S->ev[0], st));
     // ---- coefficientExpansion + reorientCiphertextsDim1 (src/testing.cpp:1009-1020)
     if (!p.direct_upload) {
@@ -610,9 +583,9 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
 
 static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) { return pk_fold_into(S, pk_own_bufs(S), S->nt, st); }
 
-static int pk_front(spiral_gpu_pack_server* S, const uint64_t* query) {
+static int pk_front(spiral_gpu_pack_server* S) {
     spiral_gpu_pack_server* one[1] = {S};
-    if (pk_expand_convert(S, query, S->stream) || pk_sweep(one, 1, S->stream)) return -1;
+    if (pk_expand_convert(S, S->stream) || pk_sweep(one, 1, S->stream)) return -1;
     return pk_fold(S, S->stream);
 }
 
@@ -645,7 +618,7 @@ static int pk_download(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* 
     return 0;
 }
 
-// what answer and answer_wire check before anything is uploaded
+// what an answer checks before its query is taken
 static int pk_check_answer(spiral_gpu_pack_server* S) {
     HIP_OK(hipSetDevice(S->device));
     if (!S->img->loaded || !S->have_pp) return fail("database and public parameters must be set first");
@@ -653,47 +626,29 @@ static int pk_check_answer(spiral_gpu_pack_server* S) {
     return 0;
 }
 
-// the query's wire form decoded into S->query on S's stream (returns synchronised)
-static int pk_query_wire(spiral_gpu_pack_server* S, const void* wire, size_t bytes, const char* what) {
-    HIP_OK(hipSetDevice(S->device));
-    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2};
-    return ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, &seg, 1, what);
-}
-// the same from the seeded form
-static int pk_query_seeded(spiral_gpu_pack_server* S, const void* msg, size_t bytes, const char* what) {
-    HIP_OK(hipSetDevice(S->device));
-    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2, 2, 1};
-    return ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_PACK_QUERY, &seg, 1, what);
-}
-// a query's bytes in the wire / seeded form (what the batch entry points check before anything is uploaded)
-static size_t pk_query_bytes(const spiral_gpu_pack_server* S, bool seeded) {
-    return seeded ? kSeedBytes + (size_t)S->s.n_query_cts * kWirePolyBytes : (size_t)S->s.n_query_cts * 2 * kWirePolyBytes;
-}
-
-// answer with the query in S->query already when query is null
-static int pk_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
-    if (pk_front(S, query) || pk_back(S, S->raw.p, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
+// the answer to the query in S->query
+static int pk_answer_taken(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
+    if (pk_front(S) || pk_back(S, S->raw.p, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
     return stage_us ? spiral_gpu_pack_server_stage_us(S, stage_us) : 0;
 }
 
-int spiral_gpu_pack_server_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
+static int pk_answer(spiral_gpu_pack_server* S, Form form, const void* query, size_t bytes, uint64_t* response, uint64_t* packed_ct, double stage_us[8],
+                     const char* what) {
     if (!S || !query) return fail("null argument");
-    if (pk_check_answer(S)) return -1;
-    return pk_answer(S, query, response, packed_ct, stage_us);
+    if (pk_check_answer(S) || pk_take_query(S, form, query, bytes, what)) return -1;
+    return pk_answer_taken(S, response, packed_ct, stage_us);
 }
 
+int spiral_gpu_pack_server_answer(spiral_gpu_pack_server* S, const uint64_t* query, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
+    return pk_answer(S, FORM_NTT, query, 0, response, packed_ct, stage_us, "answer");
+}
 int spiral_gpu_pack_server_answer_wire(spiral_gpu_pack_server* S, const void* query_wire, size_t bytes, uint64_t* response, uint64_t* packed_ct,
                                        double stage_us[8]) {
-    if (!S || !query_wire) return fail("null argument");
-    if (pk_check_answer(S) || pk_query_wire(S, query_wire, bytes, "answer_wire")) return -1;
-    return pk_answer(S, nullptr, response, packed_ct, stage_us);
+    return pk_answer(S, FORM_WIRE, query_wire, bytes, response, packed_ct, stage_us, "answer_wire");
 }
-
 int spiral_gpu_pack_server_answer_seeded(spiral_gpu_pack_server* S, const void* query_msg, size_t bytes, uint64_t* response, uint64_t* packed_ct,
                                          double stage_us[8]) {
-    if (!S || !query_msg) return fail("null argument");
-    if (pk_check_answer(S) || pk_query_seeded(S, query_msg, bytes, "answer_seeded")) return -1;
-    return pk_answer(S, nullptr, response, packed_ct, stage_us);
+    return pk_answer(S, FORM_SEEDED, query_msg, bytes, response, packed_ct, stage_us, "answer_seeded");
 }
 
 // the lanes of a batch: n in 1 .. kMaxLanes distinct servers that sweep the same images (an owner and its lanes), none trial-sharded, every one
@@ -719,61 +674,38 @@ static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bo
     return 0;
 }
 
-// Beyond the reference (one query per call): n <= kMaxLanes queries, one per server, in one launch sequence on servers[0]'s stream -- expansion and
-// conversion per lane, ONE first-dimension pass over the trial images for all of them (matrix cores, once the image is in limb-plane form: the first
-// batch on a covered geometry converts it), then folding, packing and the modulus switch per lane.  Returns synchronised.
-static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
-                           uint64_t* const* packed_cts, double stage_us[8]);
-
-int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
-                                        uint64_t* const* packed_cts, double stage_us[8]) {
-    if (pk_check_lanes(servers, n, false, "answer_batch")) return -1;
-    if (!queries) return fail("answer_batch: null queries");
+// The queries of a multi-lane call, one per server.  Every argument (in the message forms each query's byte count included) is checked before anything
+// is uploaded; then every lane's query is taken into its own buffer, and only when all of them were does anything launch -- a bad query leaves every
+// lane's previous results intact
+static int pk_take_queries(spiral_gpu_pack_server* const* servers, uint32_t n, Form form, const void* const* queries, size_t bytes_each, const char* what) {
+    if (!queries) return fail("%s: null queries", what);
+    const spiral_gpu_pack_server* S = servers[0];
+    const size_t want = message_bytes(pack_query_layout(S->p, S->s, S->out_n), form);
+    if (form != FORM_NTT && bytes_each != want)
+        return fail("%s: %zu bytes per query, the %s form of a query takes %zu", what, bytes_each, form == FORM_SEEDED ? "seeded" : "wire", want);
     for (uint32_t b = 0; b < n; b++)
-        if (!queries[b]) return fail("answer_batch: query %u is null", b);
-    if (n == 1) return spiral_gpu_pack_server_answer(servers[0], queries[0], responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
-    return pk_answer_batch(servers, n, queries, responses, packed_cts, stage_us);
-}
-
-// answer_batch from the queries' wire forms: every argument (each query's byte count included) is checked before anything is uploaded; then every
-// lane's query is decoded into its own buffer, and only when all of them decoded cleanly does the batch run -- a bad query leaves every lane's
-// previous results intact
-static int pk_answer_batch_msgs(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* msgs, size_t bytes_each, bool seeded,
-                                uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8], const char* what) {
-    if (pk_check_lanes(servers, n, false, what)) return -1;
-    if (!msgs) return fail("%s: null queries", what);
-    const size_t want = pk_query_bytes(servers[0], seeded);
-    if (bytes_each != want) return fail("%s: %zu bytes per query, the %s form of a query takes %zu", what, bytes_each, seeded ? "seeded" : "wire", want);
-    for (uint32_t b = 0; b < n; b++)
-        if (!msgs[b]) return fail("%s: query %u is null", what, b);
+        if (!queries[b]) return fail("%s: query %u is null", what, b);
     for (uint32_t b = 0; b < n; b++) {
         char w[64];
         snprintf(w, sizeof(w), "%s: query %u", what, b);
-        if (seeded ? pk_query_seeded(servers[b], msgs[b], bytes_each, w) : pk_query_wire(servers[b], msgs[b], bytes_each, w)) return -1;
+        if (pk_take_query(servers[b], form, queries[b], bytes_each, w)) return -1;
     }
-    if (n == 1) return pk_answer(servers[0], nullptr, responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
-    return pk_answer_batch(servers, n, nullptr, responses, packed_cts, stage_us);
+    return 0;
 }
 
-int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_wires, size_t bytes_each,
-                                             uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
-    return pk_answer_batch_msgs(servers, n, query_wires, bytes_each, false, responses, packed_cts, stage_us, "answer_batch_wire");
-}
-
-int spiral_gpu_pack_server_answer_batch_seeded(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_msgs, size_t bytes_each,
-                                               uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
-    return pk_answer_batch_msgs(servers, n, query_msgs, bytes_each, true, responses, packed_cts, stage_us, "answer_batch_seeded");
-}
-
-// the batch after its checks; queries null: every lane's query was decoded into its buffer already
-static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
-                           uint64_t* const* packed_cts, double stage_us[8]) {
+// Beyond the reference (one query per call): n <= kMaxLanes queries, one per server, in one launch sequence on servers[0]'s stream -- expansion and
+// conversion per lane, ONE first-dimension pass over the trial images for all of them (matrix cores, once the image is in limb-plane form: the first
+// batch on a covered geometry converts it), then folding, packing and the modulus switch per lane.  Returns synchronised.
+static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, Form form, const void* const* queries, size_t bytes_each,
+                           uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8], const char* what) {
+    if (pk_check_lanes(servers, n, false, what) || pk_take_queries(servers, n, form, queries, bytes_each, what)) return -1;
+    if (n == 1) return pk_answer_taken(servers[0], responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
     spiral_gpu_pack_server* S = servers[0];
     HIP_OK(hipSetDevice(S->device));
     if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     hipStream_t st = S->stream;
     for (uint32_t b = 0; b < n; b++)
-        if (pk_expand_convert(servers[b], queries ? queries[b] : nullptr, st)) return -1;
+        if (pk_expand_convert(servers[b], st)) return -1;
     if (pk_sweep(servers, n, st)) return -1;
     HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at servers[n - 1]'s event 2)
     for (uint32_t b = 0; b < n; b++) {
@@ -803,6 +735,19 @@ static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, c
     stage_us[6] = total * 1e3;
     stage_us[7] = n;
     return 0;
+}
+
+int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const uint64_t* const* queries, uint64_t* const* responses,
+                                        uint64_t* const* packed_cts, double stage_us[8]) {
+    return pk_answer_batch(servers, n, FORM_NTT, (const void* const*)queries, 0, responses, packed_cts, stage_us, "answer_batch");
+}
+int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_wires, size_t bytes_each,
+                                             uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
+    return pk_answer_batch(servers, n, FORM_WIRE, query_wires, bytes_each, responses, packed_cts, stage_us, "answer_batch_wire");
+}
+int spiral_gpu_pack_server_answer_batch_seeded(spiral_gpu_pack_server* const* servers, uint32_t n, const void* const* query_msgs, size_t bytes_each,
+                                               uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8]) {
+    return pk_answer_batch(servers, n, FORM_SEEDED, query_msgs, bytes_each, responses, packed_cts, stage_us, "answer_batch_seeded");
 }
 
 // ---- items of several database instances (answer_batch_instances, include/spiral_gpu.h) ----
@@ -885,9 +830,10 @@ static int pk_item_back(spiral_gpu_pack_server* L, const PkBufs& B, uint32_t g, 
     return 0;
 }
 
-// the item call after its checks; queries null: every client's query was decoded into its buffer already
-static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_pack_server* const* instances, uint32_t n_inst,
-                           const uint64_t* const* queries, uint64_t* responses, void* wire, double* total_us) {
+// the item call: every argument checked, then every query taken; the launches run only when all of them were
+static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_pack_server* const* instances, uint32_t n_inst, Form form,
+                           const void* const* queries, size_t bytes_each, uint64_t* responses, void* wire, double* total_us, const char* what) {
+    if (pk_check_items(servers, n, instances, n_inst, queries, responses, wire, what) || pk_take_queries(servers, n, form, queries, bytes_each, what)) return -1;
     spiral_gpu_pack_server* S = servers[0];
     HIP_OK(hipSetDevice(S->device));
     hipStream_t st = S->stream;
@@ -921,7 +867,7 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
         }
     }
     for (uint32_t b = 0; b < n; b++)
-        if (pk_expand_convert(servers[b], queries ? queries[b] : nullptr, st)) return -1;  // once per client, whatever the number of instances
+        if (pk_expand_convert(servers[b], st)) return -1;  // once per client, whatever the number of instances
     for (uint32_t k0 = 0; k0 < n_inst; k0 += G) {
         const uint32_t g = std::min(G, n_inst - k0);
         for (uint32_t j = 0; j < g; j++) {  // one first-dimension pass per instance for all clients, into instance j's part of each group arena
@@ -957,41 +903,20 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
 
 int spiral_gpu_pack_server_answer_batch_instances(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
                                                   uint32_t n_instances, const uint64_t* const* queries, uint64_t* responses, void* wire, double* total_us) {
-    const char* what = "answer_batch_instances";
-    if (pk_check_items(servers, n_clients, instances, n_instances, queries, responses, wire, what)) return -1;
-    for (uint32_t b = 0; b < n_clients; b++)
-        if (!queries[b]) return fail("%s: query %u is null", what, b);
-    return pk_answer_items(servers, n_clients, instances, n_instances, queries, responses, wire, total_us);
+    return pk_answer_items(servers, n_clients, instances, n_instances, FORM_NTT, (const void* const*)queries, 0, responses, wire, total_us,
+                           "answer_batch_instances");
 }
-
-// from the queries' wire forms: every argument checked, then every query decoded; the call runs only when all of them decoded cleanly
-static int pk_answer_items_msgs(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances, uint32_t n_instances,
-                                const void* const* msgs, size_t bytes_each, bool seeded, uint64_t* responses, void* wire, double* total_us, const char* what) {
-    if (pk_check_items(servers, n_clients, instances, n_instances, msgs, responses, wire, what)) return -1;
-    const size_t want = pk_query_bytes(servers[0], seeded);
-    if (bytes_each != want) return fail("%s: %zu bytes per query, the %s form of a query takes %zu", what, bytes_each, seeded ? "seeded" : "wire", want);
-    for (uint32_t b = 0; b < n_clients; b++)
-        if (!msgs[b]) return fail("%s: query %u is null", what, b);
-    for (uint32_t b = 0; b < n_clients; b++) {
-        char w[64];
-        snprintf(w, sizeof(w), "%s: query %u", what, b);
-        if (seeded ? pk_query_seeded(servers[b], msgs[b], bytes_each, w) : pk_query_wire(servers[b], msgs[b], bytes_each, w)) return -1;
-    }
-    return pk_answer_items(servers, n_clients, instances, n_instances, nullptr, responses, wire, total_us);
-}
-
 int spiral_gpu_pack_server_answer_batch_instances_wire(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
                                                        uint32_t n_instances, const void* const* query_wires, size_t bytes_each, uint64_t* responses, void* wire,
                                                        double* total_us) {
-    return pk_answer_items_msgs(servers, n_clients, instances, n_instances, query_wires, bytes_each, false, responses, wire, total_us,
-                                "answer_batch_instances_wire");
+    return pk_answer_items(servers, n_clients, instances, n_instances, FORM_WIRE, query_wires, bytes_each, responses, wire, total_us,
+                           "answer_batch_instances_wire");
 }
-
 int spiral_gpu_pack_server_answer_batch_instances_seeded(spiral_gpu_pack_server* const* servers, uint32_t n_clients, spiral_gpu_pack_server* const* instances,
                                                          uint32_t n_instances, const void* const* query_msgs, size_t bytes_each, uint64_t* responses,
                                                          void* wire, double* total_us) {
-    return pk_answer_items_msgs(servers, n_clients, instances, n_instances, query_msgs, bytes_each, true, responses, wire, total_us,
-                                "answer_batch_instances_seeded");
+    return pk_answer_items(servers, n_clients, instances, n_instances, FORM_SEEDED, query_msgs, bytes_each, responses, wire, total_us,
+                           "answer_batch_instances_seeded");
 }
 
 // the batched first-dimension sweep alone (answer_batch's), iters times on servers[0]'s stream with the lanes' current records, timed with device
@@ -1042,7 +967,7 @@ int spiral_gpu_pack_server_fold_trials(spiral_gpu_pack_server* S, const uint64_t
     if (!S || !query || !folded_dev) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     if (!S->img->loaded || !S->have_pp) return fail("database and public parameters must be set first");
-    if (pk_front(S, query)) return -1;
+    if (pk_take_query(S, FORM_NTT, query, 0, "fold_trials") || pk_front(S)) return -1;
     HIP_OK(hipMemcpy2DAsync(folded_dev, 2 * kPolyBytes, S->raw.p, (size_t)S->s.num_per * 2 * kPolyBytes, 2 * kPolyBytes, S->nt, hipMemcpyDeviceToDevice,
                             S->stream));
     return 0;

@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "db_image.h"
+#include "message.h"
 
 using namespace spiral;
 
@@ -85,7 +86,7 @@ struct spiral_gpu_server {
     DevBuf cv_raw, cv_g, key, cts_keep;  // key: [d][3][m2]: the GSW matrices Q (src/spiral.cpp:2324) -- the fold key; Q_neg = G2 - Q (:2361-2379) is never stored (poly.hip fold_mac_two_kernel)
     uint64_t *gs_raw_p = nullptr, *gs_chat_p = nullptr;  // the Regev->GSW halves of cv_raw / cv_g
     DevBuf qs, acc_own, raw, fold_d, fold_c, fold_c2, resp, stage;
-    WireIn wire_in;  // set_query_wire / set_pub_params_wire's staging (host_common.h ingest_wire)
+    WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
     uint64_t* acc = nullptr;
     hipEvent_t ev[8] = {};
     // captured launch sequences (hipGraph), used while use_graphs is on: captured on first use, re-captured when their key changes, all dropped
@@ -362,7 +363,35 @@ void server_records(spiral_gpu_server* const* servers, uint32_t n, const uint32_
     }
 }
 
-int upload_ref_ntt(spiral_gpu_server* S, const uint64_t* host, uint64_t* pk, size_t npolys) { return host::upload_ref_ntt(S->stage, S->stream, host, pk, npolys); }
+// The two ways client input gets into a server, in any form (message.h).  A null NTT-form buffer is refused with the previous message untouched; from
+// the first write on nothing answers from a half-written buffer: the flags are cleared, and set again on success.
+int take_pub_params(spiral_gpu_server* S, Form form, const MessageIn& in, const char* what) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const MessageLayout m = pub_params_layout(S->p, S->s);
+    if (form == FORM_NTT && check_ntt_parts(m, in, what)) return -1;
+    uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->w.p, S->v.p};
+    S->have_pp = false;
+    if (ingest(form, IngestOn{S->stage, S->wire_in, S->tb, S->stream}, m, dst, in, what)) return -1;
+    S->have_pp = true;
+    return 0;
+}
+int take_query(spiral_gpu_server* S, Form form, const MessageIn& in, const char* what) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    const MessageLayout m = query_layout(S->p, S->s);
+    if (form == FORM_NTT && check_ntt_parts(m, in, what)) return -1;
+    uint64_t* const dst[kMessageParts] = {S->query.p};
+    S->have_query = S->have_records = false;
+    if (ingest(form, IngestOn{S->stage, S->wire_in, S->tb, S->stream}, m, dst, in, what)) return -1;
+    S->have_query = true;
+    return 0;
+}
+// a message's bytes in the wire / seeded form for parameters the base path accepts, else 0
+size_t base_message_bytes(const spiral_gpu_params* p, MessageLayout (*layout)(const spiral_gpu_params&, const spiral_gpu_shape&), Form form) {
+    spiral_gpu_shape s;
+    return shape_of(p, &s) ? 0 : message_bytes(layout(*p, s), form);
+}
 
 int download_pk_as_ref(spiral_gpu_server* S, const uint64_t* pk, IndexMap map, uint64_t* host, size_t npolys) {
     if (npolys == 0) return 0;
@@ -1135,91 +1164,31 @@ int spiral_gpu_server_share_db(spiral_gpu_server* S, spiral_gpu_server* owner) {
     return 0;
 }
 
+// The client's two messages in their three forms (include/spiral_gpu.h).  The wire and seeded forms are decoded and transformed on the device into the
+// same buffers as the NTT form, so graphs captured on them replay the new query; any failure after the first write leaves no public parameters / no
+// query behind
 int spiral_gpu_server_set_pub_params(spiral_gpu_server* S, const uint64_t* w_left, const uint64_t* w_right, const uint64_t* w,
                                      const uint64_t* v) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const spiral_gpu_params& p = S->p;
-    if (upload_ref_ntt(S, w_left, S->w_left.p, (size_t)S->s.n_left * 2 * p.t_exp)) return -1;
-    if (upload_ref_ntt(S, w_right, S->w_right.p, (size_t)S->s.n_right * 2 * p.t_exp_right)) return -1;
-    if (upload_ref_ntt(S, w, S->w.p, (size_t)3 * 2 * p.t_conv)) return -1;
-    if (upload_ref_ntt(S, v, S->v.p, (size_t)3 * 2 * p.t_conv)) return -1;
-    S->have_pp = true;
-    return 0;
+    return take_pub_params(S, FORM_NTT, MessageIn{{w_left, w_right, w, v}, nullptr, 0}, "set_pub_params");
 }
-
-int spiral_gpu_server_set_query(spiral_gpu_server* S, const uint64_t* query) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    if (upload_ref_ntt(S, query, S->query.p, (size_t)S->s.n_query_cts * 2)) return -1;
-    S->have_query = true;
-    S->have_records = false;
-    return 0;
-}
-
-// the same from the wire form (include/spiral_gpu.h): decoded and transformed on the device into the same buffers, so graphs captured on them replay
-// the new query; any failure leaves no public parameters / no query behind
+int spiral_gpu_server_set_query(spiral_gpu_server* S, const uint64_t* query) { return take_query(S, FORM_NTT, MessageIn{{query}, nullptr, 0}, "set_query"); }
 int spiral_gpu_server_set_pub_params_wire(spiral_gpu_server* S, const void* wire, size_t bytes) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const spiral_gpu_params& p = S->p;
-    const WireSegment seg[4] = {{S->w_left.p, (size_t)S->s.n_left * 2 * p.t_exp},
-                                {S->w_right.p, (size_t)S->s.n_right * 2 * p.t_exp_right},
-                                {S->w.p, (size_t)3 * 2 * p.t_conv},
-                                {S->v.p, (size_t)3 * 2 * p.t_conv}};
-    S->have_pp = false;
-    if (ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, seg, 4, "set_pub_params_wire")) return -1;
-    S->have_pp = true;
-    return 0;
+    return take_pub_params(S, FORM_WIRE, MessageIn{{}, wire, bytes}, "set_pub_params_wire");
 }
-
 int spiral_gpu_server_set_query_wire(spiral_gpu_server* S, const void* wire, size_t bytes) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2};
-    S->have_query = S->have_records = false;
-    if (ingest_wire(S->wire_in, S->tb, S->stream, wire, bytes, &seg, 1, "set_query_wire")) return -1;
-    S->have_query = true;
-    return 0;
+    return take_query(S, FORM_WIRE, MessageIn{{}, wire, bytes}, "set_query_wire");
 }
-
-// the same from the seeded form (include/spiral_gpu.h): row 0 of every matrix generated on the device from the message's seed, the other rows as
-// set_query_wire / set_pub_params_wire decode them
 int spiral_gpu_server_set_pub_params_seeded(spiral_gpu_server* S, const void* msg, size_t bytes) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const spiral_gpu_params& p = S->p;
-    const WireSegment seg[4] = {{S->w_left.p, (size_t)S->s.n_left * 2 * p.t_exp, 2, p.t_exp},
-                                {S->w_right.p, (size_t)S->s.n_right * 2 * p.t_exp_right, 2, p.t_exp_right},
-                                {S->w.p, (size_t)3 * 2 * p.t_conv, 3, 2 * p.t_conv},
-                                {S->v.p, (size_t)3 * 2 * p.t_conv, 3, 2 * p.t_conv}};
-    S->have_pp = false;
-    if (ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_PUB_PARAMS, seg, 4, "set_pub_params_seeded")) return -1;
-    S->have_pp = true;
-    return 0;
+    return take_pub_params(S, FORM_SEEDED, MessageIn{{}, msg, bytes}, "set_pub_params_seeded");
 }
-
 int spiral_gpu_server_set_query_seeded(spiral_gpu_server* S, const void* msg, size_t bytes) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
-    const WireSegment seg{S->query.p, (size_t)S->s.n_query_cts * 2, 2, 1};
-    S->have_query = S->have_records = false;
-    if (ingest_seeded(S->wire_in, S->tb, S->stream, msg, bytes, SEED_QUERY, &seg, 1, "set_query_seeded")) return -1;
-    S->have_query = true;
-    return 0;
+    return take_query(S, FORM_SEEDED, MessageIn{{}, msg, bytes}, "set_query_seeded");
 }
 
-size_t spiral_gpu_query_seeded_bytes(const spiral_gpu_params* p) {
-    spiral_gpu_shape s;
-    if (shape_of(p, &s)) return 0;
-    return kSeedBytes + (size_t)s.n_query_cts * kWirePolyBytes;
-}
-
-size_t spiral_gpu_pub_params_seeded_bytes(const spiral_gpu_params* p) {
-    spiral_gpu_shape s;
-    if (shape_of(p, &s)) return 0;
-    return kSeedBytes + ((size_t)s.n_left * p->t_exp + (size_t)s.n_right * p->t_exp_right + (size_t)8 * p->t_conv) * kWirePolyBytes;
-}
+size_t spiral_gpu_query_wire_bytes(const spiral_gpu_params* p) { return base_message_bytes(p, query_layout, FORM_WIRE); }
+size_t spiral_gpu_query_seeded_bytes(const spiral_gpu_params* p) { return base_message_bytes(p, query_layout, FORM_SEEDED); }
+size_t spiral_gpu_pub_params_wire_bytes(const spiral_gpu_params* p) { return base_message_bytes(p, pub_params_layout, FORM_WIRE); }
+size_t spiral_gpu_pub_params_seeded_bytes(const spiral_gpu_params* p) { return base_message_bytes(p, pub_params_layout, FORM_SEEDED); }
 
 // the client's half of the seeded form: row-0 polynomials first_k .. first_k + npolys - 1 of `domain` in reference NTT layout, plain host code
 // through the same definition as the device's generator (seed_device.h)
@@ -1238,18 +1207,6 @@ int spiral_gpu_seed_expand(const void* seed32, uint32_t domain, uint64_t first_k
         }
     }
     return 0;
-}
-
-size_t spiral_gpu_query_wire_bytes(const spiral_gpu_params* p) {
-    spiral_gpu_shape s;
-    if (shape_of(p, &s)) return 0;
-    return (size_t)s.n_query_cts * 2 * kWirePolyBytes;
-}
-
-size_t spiral_gpu_pub_params_wire_bytes(const spiral_gpu_params* p) {
-    spiral_gpu_shape s;
-    if (shape_of(p, &s)) return 0;
-    return ((size_t)s.n_left * 2 * p->t_exp + (size_t)s.n_right * 2 * p->t_exp_right + (size_t)12 * p->t_conv) * kWirePolyBytes;
 }
 
 // the client's half of the wire form: plain host code, no device involved

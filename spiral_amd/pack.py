@@ -126,38 +126,31 @@ class PackServer:
         w = wire_bytes(wire)
         check(lib().spiral_gpu_pack_server_set_pub_params_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
 
-    def answer_wire(self, query_wire, want_packed: bool = True):
-        """answer with the query in its wire form: as answer"""
-        w = wire_bytes(query_wire)
-        n = self.out_n
-        resp = np.zeros((n + 1, n, N), dtype=np.uint64)
-        packed = np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None
-        us = (C.c_double * 8)()
-        check(lib().spiral_gpu_pack_server_answer_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size, _p(resp), _p(packed) if want_packed else None, us))
-        return resp, packed, dict(zip(PACK_STAGE_NAMES, list(us)))
-
     def set_pub_params_seeded(self, msg):
         """the public parameters as one seeded message (include/spiral_gpu.h): row 0 of every matrix from the seed"""
         w = wire_bytes(msg)
         check(lib().spiral_gpu_pack_server_set_pub_params_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size))
 
-    def answer_seeded(self, query_msg, want_packed: bool = True):
-        """answer with the query in its seeded form: as answer"""
-        w = wire_bytes(query_msg)
+    def _answer(self, form: str, query, want_packed: bool):
+        q = _query_arrays(form, [query])[0]
+        qargs = (_p(q),) if form == "ntt" else (q.ctypes.data_as(C.c_void_p), q.size)
         n = self.out_n
         resp = np.zeros((n + 1, n, N), dtype=np.uint64)
         packed = np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None
         us = (C.c_double * 8)()
-        check(lib().spiral_gpu_pack_server_answer_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size, _p(resp), _p(packed) if want_packed else None, us))
+        check(getattr(lib(), "spiral_gpu_pack_server_answer" + _FORMS[form])(self.h, *qargs, _p(resp), _p(packed) if want_packed else None, us))
         return resp, packed, dict(zip(PACK_STAGE_NAMES, list(us)))
 
     def answer(self, query, want_packed: bool = True):
-        n = self.out_n
-        resp = np.zeros((n + 1, n, N), dtype=np.uint64)
-        packed = np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None
-        us = (C.c_double * 8)()
-        check(lib().spiral_gpu_pack_server_answer(self.h, _p(_c(query)), _p(resp), _p(packed) if want_packed else None, us))
-        return resp, packed, dict(zip(PACK_STAGE_NAMES, list(us)))
+        return self._answer("ntt", query, want_packed)
+
+    def answer_wire(self, query_wire, want_packed: bool = True):
+        """answer with the query in its wire form: as answer"""
+        return self._answer("wire", query_wire, want_packed)
+
+    def answer_seeded(self, query_msg, want_packed: bool = True):
+        """answer with the query in its seeded form: as answer"""
+        return self._answer("seeded", query_msg, want_packed)
 
     def sweep_bytes(self) -> int:
         return int(lib().spiral_gpu_pack_server_sweep_bytes(self.h))
@@ -185,6 +178,20 @@ class PackServer:
 
 DB_PACKED, DB_LIMBS = 0, 1
 MAX_LANES = 8
+# the forms a query comes in (include/spiral_gpu.h) -> the suffix of the entry points that take it
+_FORMS = {"ntt": "", "wire": "_wire", "seeded": "_seeded"}
+
+
+def _query_arrays(form: str, queries) -> list:
+    """queries as contiguous arrays: uint64 polynomials (NTT form) or uint8 messages"""
+    return [_c(q) if form == "ntt" else wire_bytes(q) for q in queries]
+
+
+def _query_list_args(form: str, qs):
+    """what a multi-query entry point takes for its queries: the pointer array, and in the message forms the bytes of each"""
+    if form == "ntt":
+        return ((U64P * len(qs))(*[_p(q) for q in qs]),)
+    return (C.c_void_p * len(qs))(*[q.ctypes.data for q in qs]), qs[0].size
 
 
 def _lane_handles(servers, what: str):
@@ -200,57 +207,39 @@ def _lane_handles(servers, what: str):
     return servers, (C.c_void_p * len(servers))(*[s.h for s in servers])
 
 
-def answer_batch(servers, queries, want_packed: bool = False):
-    """n <= 8 queries, one per server (an owner and its lanes, create_lane), answered with ONE first-dimension pass over the trial images:
-    ([(response, packed or None) per server], stage times of the batch).  Each lane's results equal its own answer's."""
-    servers, hs = _lane_handles(servers, "answer_batch")
-    queries = list(queries)
-    if len(queries) != len(servers):
-        raise ValueError(f"answer_batch: {len(queries)} queries for {len(servers)} servers")
-    qs = [_c(q) for q in queries]
+def _answer_batch(form: str, servers, queries, want_packed: bool):
+    what = "answer_batch" + _FORMS[form]
+    servers, hs = _lane_handles(servers, what)
+    qs = list(queries) if form == "ntt" else _query_arrays(form, queries)
+    if len(qs) != len(servers):
+        raise ValueError(f"{what}: {len(qs)} queries for {len(servers)} servers")
+    if form == "ntt":
+        qs = _query_arrays(form, qs)
+    elif len({w.size for w in qs}) != 1:
+        raise ValueError(f"{what}: the queries differ in size")
     n = servers[0].out_n
     resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
     packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
     arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
     us = (C.c_double * 8)()
-    check(lib().spiral_gpu_pack_server_answer_batch(hs, len(servers), arr(qs), arr(resp), arr(packed), us))
+    check(getattr(lib(), "spiral_gpu_pack_server_" + what)(hs, len(servers), *_query_list_args(form, qs), arr(resp), arr(packed), us))
     return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
+
+
+def answer_batch(servers, queries, want_packed: bool = False):
+    """n <= 8 queries, one per server (an owner and its lanes, create_lane), answered with ONE first-dimension pass over the trial images:
+    ([(response, packed or None) per server], stage times of the batch).  Each lane's results equal its own answer's."""
+    return _answer_batch("ntt", servers, queries, want_packed)
 
 
 def answer_batch_wire(servers, query_wires, want_packed: bool = False):
     """answer_batch with the queries in their wire form (all of one size); every query is checked and decoded before the batch runs"""
-    servers, hs = _lane_handles(servers, "answer_batch_wire")
-    ws = [wire_bytes(w) for w in query_wires]
-    if len(ws) != len(servers):
-        raise ValueError(f"answer_batch_wire: {len(ws)} queries for {len(servers)} servers")
-    if len({w.size for w in ws}) != 1:
-        raise ValueError("answer_batch_wire: the queries differ in size")
-    n = servers[0].out_n
-    resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
-    packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
-    arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
-    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-    us = (C.c_double * 8)()
-    check(lib().spiral_gpu_pack_server_answer_batch_wire(hs, len(servers), wp, ws[0].size, arr(resp), arr(packed), us))
-    return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
+    return _answer_batch("wire", servers, query_wires, want_packed)
 
 
 def answer_batch_seeded(servers, query_msgs, want_packed: bool = False):
     """answer_batch with the queries in their seeded form (all of one size); every query is checked and expanded before the batch runs"""
-    servers, hs = _lane_handles(servers, "answer_batch_seeded")
-    ws = [wire_bytes(w) for w in query_msgs]
-    if len(ws) != len(servers):
-        raise ValueError(f"answer_batch_seeded: {len(ws)} queries for {len(servers)} servers")
-    if len({w.size for w in ws}) != 1:
-        raise ValueError("answer_batch_seeded: the queries differ in size")
-    n = servers[0].out_n
-    resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
-    packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
-    arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
-    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-    us = (C.c_double * 8)()
-    check(lib().spiral_gpu_pack_server_answer_batch_seeded(hs, len(servers), wp, ws[0].size, arr(resp), arr(packed), us))
-    return list(zip(resp, packed)), dict(zip(PACK_STAGE_NAMES[:7] + ["n"], list(us)))
+    return _answer_batch("seeded", servers, query_msgs, want_packed)
 
 
 def time_sweep_batch(servers, iters: int = 10) -> float:
@@ -290,57 +279,46 @@ def _item_call(servers, instances, wire: bool, stats, call):
     return (resp, wires) if wire else resp
 
 
+def _answer_batch_instances(form: str, servers, instances, queries, wire: bool, stats):
+    what = "answer_batch_instances" + _FORMS[form]
+    servers, hs, instances, ins = _item_args(servers, instances, what)
+    s0 = servers[0]
+    qs = list(queries) if form == "ntt" else _query_arrays(form, queries)
+    if len(qs) != len(servers):
+        raise ValueError(f"{what}: {len(qs)} queries for {len(servers)} clients")
+    if form == "ntt":
+        words = s0.shape.n_query_cts * 2 * 2 * N  # ([ct][row] polynomials of the reference's NTT form, two words per coefficient)
+        for q in qs:
+            if not isinstance(q, np.ndarray) or q.dtype != np.uint64:
+                raise TypeError(f"{what}: a query is a uint64 array, not {getattr(q, 'dtype', type(q).__name__)}")
+            if q.size != words:
+                raise ValueError(f"{what}: a query of {q.size} words, this geometry's takes {words}")
+        qs = _query_arrays(form, qs)
+    else:
+        want = getattr(lib(), f"spiral_gpu_pack_query_{form}_bytes")(C.byref(s0.params), s0.out_n)
+        if any(w.size != want for w in qs):
+            raise ValueError(f"{what}: the {form} form of a query takes {want} bytes, got {[w.size for w in qs]}")
+    fn, qargs = getattr(lib(), "spiral_gpu_pack_server_" + what), _query_list_args(form, qs)
+    return _item_call(servers, instances, wire, stats, lambda r, w, us: check(fn(hs, len(servers), ins, len(instances), *qargs, r, w, us)))
+
+
 def answer_batch_instances(servers, instances, queries, wire: bool = False, stats: dict = None):
     """B <= 8 clients (an owner and its lanes, each with its own public parameters) fetch an item of F = len(instances) plaintexts each: one query per
     client, F instances (PackServers holding all trial images of their own database).  Returns [B, F, out_n + 1, out_n, 2048] uint64 responses -- slot
     [q, k] equals client q's own answer against instance k -- and with wire=True also their wire forms [B, F, bytes] uint8.  stats (a dict, optional)
     receives total_us, the device time of the call.  See include/spiral_gpu.h spiral_gpu_pack_server_answer_batch_instances."""
-    what = "answer_batch_instances"
-    servers, hs, instances, ins = _item_args(servers, instances, what)
-    queries = list(queries)
-    if len(queries) != len(servers):
-        raise ValueError(f"{what}: {len(queries)} queries for {len(servers)} clients")
-    words = servers[0].shape.n_query_cts * 2 * 2 * N  # ([ct][row] polynomials of the reference's NTT form, two words per coefficient)
-    for q in queries:
-        if not isinstance(q, np.ndarray) or q.dtype != np.uint64:
-            raise TypeError(f"{what}: a query is a uint64 array, not {getattr(q, 'dtype', type(q).__name__)}")
-        if q.size != words:
-            raise ValueError(f"{what}: a query of {q.size} words, this geometry's takes {words}")
-    qs = [_c(q) for q in queries]
-    qp = (U64P * len(qs))(*[_p(q) for q in qs])
-    return _item_call(servers, instances, wire, stats,
-                      lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances(hs, len(servers), ins, len(instances), qp, r, w, us)))
+    return _answer_batch_instances("ntt", servers, instances, queries, wire, stats)
 
 
 def answer_batch_instances_wire(servers, instances, query_wires, wire: bool = False, stats: dict = None):
     """answer_batch_instances with the queries in their wire form (each spiral_gpu_pack_query_wire_bytes long); every query is decoded before the call runs"""
-    what = "answer_batch_instances_wire"
-    servers, hs, instances, ins = _item_args(servers, instances, what)
-    ws = [wire_bytes(w) for w in query_wires]
-    if len(ws) != len(servers):
-        raise ValueError(f"{what}: {len(ws)} queries for {len(servers)} clients")
-    want = lib().spiral_gpu_pack_query_wire_bytes(C.byref(servers[0].params), servers[0].out_n)
-    if any(w.size != want for w in ws):
-        raise ValueError(f"{what}: the wire form of a query takes {want} bytes, got {[w.size for w in ws]}")
-    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-    return _item_call(servers, instances, wire, stats,
-                      lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances_wire(hs, len(servers), ins, len(instances), wp, want, r, w, us)))
+    return _answer_batch_instances("wire", servers, instances, query_wires, wire, stats)
 
 
 def answer_batch_instances_seeded(servers, instances, query_msgs, wire: bool = False, stats: dict = None):
     """answer_batch_instances with the queries in their seeded form (each spiral_gpu_pack_query_seeded_bytes long); every query is expanded before
     the call runs"""
-    what = "answer_batch_instances_seeded"
-    servers, hs, instances, ins = _item_args(servers, instances, what)
-    ws = [wire_bytes(w) for w in query_msgs]
-    if len(ws) != len(servers):
-        raise ValueError(f"{what}: {len(ws)} queries for {len(servers)} clients")
-    want = lib().spiral_gpu_pack_query_seeded_bytes(C.byref(servers[0].params), servers[0].out_n)
-    if any(w.size != want for w in ws):
-        raise ValueError(f"{what}: the seeded form of a query takes {want} bytes, got {[w.size for w in ws]}")
-    wp = (C.c_void_p * len(ws))(*[w.ctypes.data for w in ws])
-    return _item_call(servers, instances, wire, stats,
-                      lambda r, w, us: check(lib().spiral_gpu_pack_server_answer_batch_instances_seeded(hs, len(servers), ins, len(instances), wp, want, r, w, us)))
+    return _answer_batch_instances("seeded", servers, instances, query_msgs, wire, stats)
 
 
 def answer_instances(server, instances, query, wire: bool = False, stats: dict = None):

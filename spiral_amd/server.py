@@ -206,28 +206,29 @@ class Server:
     def set_query(self, query):
         check(lib().spiral_gpu_server_set_query(self.h, _p(np.ascontiguousarray(query, dtype=np.uint64))))
 
+    def _set_message(self, setter: str, msg):
+        """one wire or seeded message to the entry point spiral_gpu_server_<setter>"""
+        w = wire_bytes(msg)
+        check(getattr(lib(), "spiral_gpu_server_" + setter)(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+
     def set_pub_params_wire(self, wire):
         """the public parameters as one wire message (ops.raw_to_wire of W_exp_left, W_exp_right, W, V); decoded on the device"""
-        w = wire_bytes(wire)
-        check(lib().spiral_gpu_server_set_pub_params_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+        self._set_message("set_pub_params_wire", wire)
 
     def set_query_wire(self, wire):
         """the query in its wire form (ops.raw_to_wire of the raw ciphertexts); decoded on the device into set_query's buffer.  A failure
         leaves no query set"""
-        w = wire_bytes(wire)
-        check(lib().spiral_gpu_server_set_query_wire(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+        self._set_message("set_query_wire", wire)
 
     def set_pub_params_seeded(self, msg):
         """the public parameters as one seeded message (include/spiral_gpu.h): row 0 of every matrix generated on the device from the seed, the
         other rows decoded as set_pub_params_wire does"""
-        w = wire_bytes(msg)
-        check(lib().spiral_gpu_server_set_pub_params_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+        self._set_message("set_pub_params_seeded", msg)
 
     def set_query_seeded(self, msg):
         """the query in its seeded form: the seed, then row 1 of each ciphertext in its wire form; into set_query's buffer.  A failure leaves no
         query set"""
-        w = wire_bytes(msg)
-        check(lib().spiral_gpu_server_set_query_seeded(self.h, w.ctypes.data_as(C.c_void_p), w.size))
+        self._set_message("set_query_seeded", msg)
 
     # ---- stages ----
     def expand(self):

@@ -228,7 +228,8 @@ def test_query_across_staging_chunks(sa, SV, oracle):
 
 def test_failures(sa, SV, oracle):
     """a coefficient above Q and a wrong byte count fail, naming the index; afterwards run_query fails with the existing message; the next valid
-    query is served, and a captured graph replays it without a re-capture.  Bad public parameters leave none set."""
+    query is served, and a captured graph replays it without a re-capture.  Bad public parameters leave none set; NTT-form ones with a null
+    buffer leave the previous ones."""
     O = oracle
     po, pg, cl = make(sa, O, COMPRESSED)
     wl, wr, w, v = cl.pub_params()
@@ -243,6 +244,15 @@ def test_failures(sa, SV, oracle):
         srv.run_query()
     srv.sync()
     want = srv.read(SV.BUF_RESPONSE)
+    # NTT-form public parameters with a null buffer after two valid ones: refused before anything is written, the previous keys still answer
+    U64P = C.POINTER(C.c_uint64)
+    wl2, wr2 = O.Client(po, seed=6).pub_params()[:2]
+    assert not (wl2 == wl).all()
+    assert sa.lib().spiral_gpu_server_set_pub_params(srv.h, wl2.ctypes.data_as(U64P), wr2.ctypes.data_as(U64P), None, v.ctypes.data_as(U64P)) != 0
+    assert "null" in sa.lib().spiral_gpu_last_error().decode()
+    srv.run_query()
+    srv.sync()
+    assert_eq(srv.read(SV.BUF_RESPONSE), want, "after NTT-form public parameters with a null buffer")
     n0 = captures(sa)
     # the out-of-range value written into the bytes directly (raw_to_wire refuses it)
     wbad = good.copy()
@@ -308,7 +318,7 @@ PACK_GEOMS = [
 @pytest.mark.parametrize("nu1,nu2,out_n,kw", PACK_GEOMS, ids=["pack", "streampack"])
 def test_pack_bit_identical(sa, P, oracle, nu1, nu2, out_n, kw):
     """answer_wire and answer_batch_wire (B = 1, 4) == answer / answer_batch, with set_pub_params_wire on the lanes; a bad query in a batch
-    leaves every lane's previous results intact"""
+    leaves every lane's previous results intact, and NTT-form public parameters with a null buffer the previous keys"""
     O = oracle
     po, pg = O.make_params(nu1, nu2, **kw), sa.make_params(nu1, nu2, **kw)
     s = O.pack_shape_of(po, out_n)
@@ -324,6 +334,14 @@ def test_pack_bit_identical(sa, P, oracle, nu1, nu2, out_n, kw):
     for sv, pp in zip(servers, pps):
         sv.set_pub_params(*pp)
     r0, k0, _ = owner.answer(qs[0])
+    # NTT-form public parameters with a null v_W after valid new keys: refused before anything is written, the previous keys still answer
+    U64P = C.POINTER(C.c_uint64)
+    ptr = [np.ascontiguousarray(m).ctypes.data_as(U64P) for m in pps[1][:3]]
+    assert sa.lib().spiral_gpu_pack_server_set_pub_params(owner.h, ptr[0], ptr[1], ptr[2], None) != 0
+    assert "null" in sa.lib().spiral_gpu_last_error().decode()
+    r0b, k0b, _ = owner.answer(qs[0])
+    assert_eq(r0b, r0, "answer after NTT-form public parameters with a null buffer: response")
+    assert_eq(k0b, k0, "answer after NTT-form public parameters with a null buffer: packed ciphertext")
     want1, _ = P.answer_batch(servers[:1], qs[:1], want_packed=True)
     want4, _ = P.answer_batch(servers, qs, want_packed=True)
     for sv, pp in zip(servers, pps):  # (direct upload: v_W alone -- the oracle's client draws expansion keys it does not send)
