@@ -566,12 +566,19 @@ uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algor
  * is launched (n in 1 .. 8, no duplicates, same image, parameters, database and public parameters present): a failing check leaves every lane's
  * previous results intact.  n = 1 is answer.
  * The shared pass runs on the matrix cores (csrc/sweep_mfma.hip, the base path's kernel with 2-row records) from the LIMBS form of the trial
- * images, where that form exists: >= 128 ciphertexts per slot (nu2 >= 7) and a first dimension that is a power of two in [128, 4096].  The first
- * batch on such a geometry converts the images in place (set_db_format); elsewhere the batch sweeps once per lane on the vector ALU -- same
- * results, no shared pass.  A single answer on a LIMBS image sweeps it with the one-query instance of the same kernel (bit-identical).
- * set_db_format / db_format / db_device_bytes: as spiral_gpu_server_set_db_format, for the out_n^2 trial images (on the owner, not a lane; every
- * loader leaves a correct image whatever form it finds; a conversion that fails partway leaves no database loaded).
+ * images, where that form exists (spiral_gpu_pack_has_limb_form): at least 16 ciphertexts per slot (nu2 >= 4) and a first dimension that is a power
+ * of two in [128, 4096] (nu1 = 7 .. 12), whatever out_n.  With 16, 32 or 64 ciphertexts per slot -- the large-plaintext sets, many trials of few
+ * columns -- a workgroup of the pass takes columns of several trials at once; from 128 up, of one.  The first batch on such a geometry converts the
+ * images in place (set_db_format); elsewhere (8 ciphertexts per slot or fewer, a first dimension below 128) the batch sweeps once per lane on the
+ * vector ALU -- same results, no shared pass.  A single answer on a LIMBS image sweeps it with the one-query instance of the same kernel
+ * (bit-identical).
+ * has_limb_form: 1 when a batch on this geometry shares its pass (so collecting clients into a batch pays), 0 when not, -1 (spiral_gpu_last_error)
+ * for bad parameters; a pure function of the parameters, no GPU needed.
+ * set_db_format / db_format / db_device_bytes: as spiral_gpu_server_set_db_format, for the out_n^2 trial images (on the owner, not a lane; LIMBS
+ * fails where has_limb_form is 0; a trial-sharded server converts the images of its own trials; every loader leaves a correct image whatever form
+ * it finds; a conversion that fails partway leaves no database loaded).
  * time_sweep_batch: the batched sweep alone, iters times with the lanes' current records (each answered once), average ms by device events. */
+int spiral_gpu_pack_has_limb_form(const spiral_gpu_params *p, uint32_t out_n);
 int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server *owner, spiral_gpu_pack_server **out);
 int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server *const *servers, uint32_t n, const uint64_t *const *queries,
                                         uint64_t *const *responses, uint64_t *const *packed_cts, double stage_us[8]);

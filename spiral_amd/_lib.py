@@ -180,6 +180,7 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_answer": (C.c_int, [C.c_void_p, U64P, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_read_acc": (C.c_int, [C.c_void_p, C.c_uint32, U64P]),
     "spiral_gpu_pack_server_sweep_bytes": (C.c_uint64, [C.c_void_p]),
+    "spiral_gpu_pack_has_limb_form": (C.c_int, [C.POINTER(Params), C.c_uint32]),
     "spiral_gpu_pack_server_create_lane": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "spiral_gpu_pack_server_answer_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_set_db_format": (C.c_int, [C.c_void_p, C.c_int]),

@@ -73,16 +73,19 @@ struct DbImage {
 
     // Converts the image between the packed form (common.h, kernels.h; the vector-ALU sweeps) and the limb planes (sweep_mfma.hip; the matrix-core
     // sweeps) IN PLACE: a slot z's region of a trial is the same byte range in both forms, so the image goes through a staging buffer of at most
-    // 256 MiB a few slots at a time -- no second image, whatever the database's size.  Offline (database load time or the first batch), never
-    // inside a capture.
+    // 256 MiB a few slots at a time -- no second image, whatever the database's size.  Below 64 columns a packed SpiralPack tile holds pz = 64 / num_per
+    // slots (kernels.h db1_packed_byte) and it is those pz slots that share a byte range, so the chunks are cut at multiples of pz.  Offline (database
+    // load time or the first batch), never inside a capture.
     int set_format(uint32_t fmt, hipStream_t st) {
         if (format == fmt) return 0;
         if (!lay.mfma_ok())
-            return fail(lay.pack ? "this geometry has no limb-plane form (needs >= 128 ciphertexts per slot and a power-of-two first dimension in [128, 4096])"
+            return fail(lay.pack ? "this geometry has no limb-plane form (needs 16, 32, 64 or a power of two >= 128 ciphertexts per slot and a power-of-two first "
+                                   "dimension in [128, 4096])"
                                  : "this geometry has no limb-plane form (needs >= 64 ciphertexts per slot and a power-of-two first dimension in [64, 2048])");
         if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever reads or writes the image, on whichever stream
         const size_t per_z = lay.trial_words / kN;
-        const uint32_t nzc = (uint32_t)std::max<size_t>(1, std::min<size_t>(kN, ((size_t)256 << 20) / (per_z * sizeof(uint64_t))));
+        const uint32_t pz = lay.pack && lay.num_per < 64u ? 64u / lay.num_per : 1u;
+        const uint32_t nzc = std::max(pz, (uint32_t)std::min<size_t>(kN, ((size_t)256 << 20) / (per_z * sizeof(uint64_t))) / pz * pz);
         DevBuf stage;
         if (stage.alloc(per_z * nzc)) return -1;
         const uint32_t np = lay.num_per, d = lay.pack ? lay.dim0 : 2 * lay.dim0;

@@ -229,6 +229,15 @@ int spiral_gpu_pack_get_shape(const spiral_gpu_params* p, uint32_t out_n, spiral
     return pack_shape_of(p, out_n, out);
 }
 
+int spiral_gpu_pack_has_limb_form(const spiral_gpu_params* p, uint32_t out_n) {
+    if (!p) return fail("null argument");
+    spiral_gpu_pack_shape s;
+    spiral_gpu_params q = *p;
+    q.direct_upload = 1;  // the image's form does not depend on how the query arrives: no query-size rule here
+    if (pack_shape_of(&q, out_n, &s)) return -1;
+    return sweep1_mfma_ok(s.num_per, s.dim0) ? 1 : 0;
+}
+
 int spiral_gpu_pack(uint64_t* result, uint32_t out_n, uint32_t m_conv, const uint64_t* v_ct, const uint64_t* v_W) {
     DeviceTables tb;
     if (current_tables(&tb)) return -1;

@@ -25,8 +25,11 @@
 // The B operands (query limbs) are built in LDS from the lanes' ordinary 48-byte query records by the workgroup (all its waves share z) and read
 // back with conflict-free ds_read_b128.
 // The same kernel (ROWS = 2) is the SpiralPack batch's sweep (pack_server.cpp, answer_batch): 1 x 1 plaintexts and 2-row 16-byte records, K = dim0
-// terms per column, every trial image of the server in one launch.  Coverage: sweep1_mfma_ok (>= 128 ciphertexts per slot, dim0 a power of two in
-// [128, 4096]); other pack geometries sweep once per query on the vector ALU (pack.hip).
+// terms per column, every trial image of the server in one launch.  A SpiralPack query is the same for every trial, so where a trial has fewer than
+// 128 columns (num_per = 16, 32, 64: the large-plaintext sets, few ciphertexts per slot and many trials) the eight waves of a workgroup take 16-column
+// blocks of DIFFERENT trials (the NARROW form below).  Coverage: sweep1_mfma_ok (16, 32, 64 or a power of two >= 128 ciphertexts per slot, dim0 a power
+// of two in [128, 4096], any number of trials); other pack geometries (num_per <= 8, dim0 < 128) sweep once per query on the vector ALU (pack.hip).
+// A single query may stay on a converted image: the one-query instance of this kernel sweeps it, bit-identical to sweep1_kernel.
 #include <atomic>
 #include <cstdlib>
 #include "common.h"
@@ -53,13 +56,20 @@ __device__ __forceinline__ void limbs_of_group(const uint32_t (&d)[28], uint32_t
 
 // packed image -> limb planes.  One wave per (z, block of 16 columns, piece of 128 terms); lane l = (column l & 15, term block l >> 4)
 // reads the two 112-byte groups (8 j each) that hold its 2 x 16 terms and writes its 16 bytes of each of the 2 x 7 pieces.
+// A packed tile is pw = min(64, nic) columns x pz = 64 / pw consecutive slots (kernels.h db1_packed_byte; pz = 1 from 64 columns up, where this is the
+// base image's map): column ic of slot z is lane (z % pz) pw + ic % pw of tile (z / pz) (nic / pw) + ic / pw.  Below 64 columns the unit of a
+// conversion is therefore a tile's pz slots -- the same byte range in both forms -- and both pointers must be at a multiple of pz slots.
+__device__ __forceinline__ size_t packed_lane_of(uint32_t z, uint32_t ic, uint32_t nic, uint32_t groups) {  // in uint4: the lane's first chunk of group 0
+    const uint32_t pw = min(nic, 64u), pz = 64u / pw;
+    return ((size_t)((z / pz) * (nic / pw) + ic / pw) * groups) * 7u * 64u + (z % pz) * pw + ic % pw;
+}
 __global__ __launch_bounds__(256) void db_limb_planes_kernel(const uint64_t* __restrict__ packed, uint4* __restrict__ limbs, uint32_t nic, uint32_t dim0, uint32_t nz) {
     const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * 4u + (threadIdx.x >> 6);
     const uint32_t nk2 = dim0 >> 6, nblk16 = nic >> 4;
     const uint32_t kc2 = wave % nk2, icb = (wave / nk2) % nblk16, z = wave / (nk2 * nblk16);
     if (z >= nz) return;
     const uint32_t ic = icb * 16u + (lane & 15u), kblk = lane >> 4, groups = dim0 >> 3;
-    const uint4* src = reinterpret_cast<const uint4*>(packed) + ((size_t)(z * (nic >> 6) + (ic >> 6)) * groups) * 7u * 64u + (ic & 63u);
+    const uint4* src = reinterpret_cast<const uint4*>(packed) + packed_lane_of(z, ic, nic, groups);
     uint32_t lp[3][2][4] = {}, lb[3][2][4] = {}, np[4] = {}, nb[4] = {};
 #pragma unroll
     for (uint32_t c = 0; c < 2; c++) {
@@ -124,7 +134,7 @@ __global__ __launch_bounds__(256) void db_limb_unplanes_kernel(const uint4* __re
     if (z >= nz) return;
     const uint32_t ic = icb * 16u + (lane & 15u), kblk = lane >> 4, groups = dim0 >> 3;
     const uint4* src = limbs + ((size_t)(z * nblk16 + icb) * 2u * nk2 + kc2) * 7u * 64u + lane;
-    uint4* dst = reinterpret_cast<uint4*>(packed) + ((size_t)(z * (nic >> 6) + (ic >> 6)) * groups) * 7u * 64u + (ic & 63u);
+    uint4* dst = reinterpret_cast<uint4*>(packed) + packed_lane_of(z, ic, nic, groups);
     const uint4 np4 = src[(size_t)6u * 64u], nb4 = src[((size_t)nk2 * 7u + 6u) * 64u];
     const uint32_t np[4] = {np4.x, np4.y, np4.z, np4.w}, nb[4] = {nb4.x, nb4.y, nb4.z, nb4.w};
 #pragma unroll
@@ -164,10 +174,12 @@ struct SweepLanes {
     uint64_t* acc[kMaxLanes];
 };
 // ROWS = 2 (the SpiralPack sweep) only: work items are (trial, group of 128 columns, z), the trials' images db_stride uint4 and their accumulators
-// acc_stride words apart, 2^grp_log column groups per trial
+// acc_stride words apart, 2^grp_log column groups per trial.
+// NARROW (num_per < 128): the 16-column blocks of the server are numbered row-major over (trial, block in trial), 2^grp_log blocks per trial and
+// `blocks` = trials << grp_log in all; work items are (group of 8 consecutive blocks, z) and wave wv of a workgroup takes block 8 group + wv
 struct SweepTrials {
     size_t db_stride, acc_stride;
-    uint32_t grp_log;
+    uint32_t grp_log, blocks;
 };
 
 template <typename T>
@@ -304,7 +316,10 @@ struct RecPlan {
 // dynamic LDS = 2 limb buffers x 2 NT KiB + 8 x NT x 64 x 2^zs_log result words.
 // GS (ROWS = 3, batches of a sharded answer): the accumulators are rank-major over the whole batch, [rank g][lane][k < L]; rank g's chunk of a
 // query lies tr.acc_stride = (lanes - 1) * L ciphertexts further on than in the one-query layout (sweep.hip sweep_kernel)
-template <int NT, int ROWS, bool GS = false>
+// NARROW (ROWS = 2, fewer than 128 columns per trial): a workgroup's waves own blocks of different trials (SweepTrials); they still share z, hence the
+// query limbs, the record plan and every barrier.  When `blocks` is not a multiple of 8 the last group is ragged: its surplus waves stream the last
+// block again (clamped, so every load of a trip stays unconditional and the trip straight-line), build their share of the limbs, and store nothing.
+template <int NT, int ROWS, bool GS = false, bool NARROW = false>
 __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restrict__ dbl, SweepLanes bt, uint32_t nb, uint32_t nic, uint32_t dim0, uint32_t g_log,
                                                             uint32_t ls_log, uint32_t n_work, uint32_t zs_log, SweepTrials tr) {
     extern __shared__ __attribute__((aligned(16))) uint4 bq[];
@@ -320,7 +335,10 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
     auto piece_ptr = [&](uint32_t g) -> const u32x4* {  // piece g of this workgroup's run (clamped to its last one)
         g = min(g, total - 1u);
         const uint32_t w = w0 + (g >> ppi_log), p = g & (ppi - 1u), z = w & (kN - 1u);
-        if constexpr (ROWS == 2) {
+        if constexpr (NARROW) {
+            const uint32_t blk = min((w >> kLogN) * W + wv, tr.blocks - 1u), trial = blk >> tr.grp_log, icb = blk & ((1u << tr.grp_log) - 1u);
+            return db0 + trial * tr.db_stride + ((((size_t)z * (nic >> 4) + icb) << ppi_log) + p) * (7u * 64u);
+        } else if constexpr (ROWS == 2) {
             const uint32_t grp = w >> kLogN, trial = grp >> tr.grp_log, icb = (grp & ((1u << tr.grp_log) - 1u)) * W + wv;
             return db0 + trial * tr.db_stride + ((((size_t)z * (nic >> 4) + icb) << ppi_log) + p) * (7u * 64u);
         }
@@ -410,7 +428,16 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 const uint32_t half_log = zs_log - 1u;  // 2^half_log 16-byte pieces per entry
-                if constexpr (ROWS == 2) {
+                if constexpr (NARROW) {
+                    const uint32_t blk = (w >> kLogN) * W + wv, trial = blk >> tr.grp_log, icb = blk & ((1u << tr.grp_log) - 1u);
+                    const uint32_t n_idx = blk < tr.blocks ? (NT * 64u) << half_log : 0u;  // a surplus wave of the ragged last group stores nothing
+                    for (uint32_t idx = lane; idx < n_idx; idx += 64u) {
+                        const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;
+                        const uint32_t ic = icb * 16u + (ls >> 4) * 4u + (ls & 3u), qr = t * 4u + ((ls & 15u) >> 2), q = qr >> 1, r = qr & 1u;
+                        const uint4 v = reinterpret_cast<const uint4*>(st)[idx];
+                        if (q < nb) *reinterpret_cast<uint4*>(pick_lane(bt.acc, q) + trial * tr.acc_stride + ((size_t)(2u * ic + r)) * kN + (z - zi) + 2u * part) = v;
+                    }
+                } else if constexpr (ROWS == 2) {
                     const uint32_t grp = w >> kLogN, trial = grp >> tr.grp_log, icb = (grp & ((1u << tr.grp_log) - 1u)) * W + wv;
                     for (uint32_t idx = lane; idx < (NT * 64u) << half_log; idx += 64u) {
                         const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;
@@ -463,7 +490,7 @@ void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, 
 namespace {
 
 // one launch of sweep_mfma_kernel<nt, ROWS> over n_work items (dim0: half the terms per column, as the kernel takes it)
-template <int ROWS, bool GS = false>
+template <int ROWS, bool GS = false, bool NARROW = false>
 hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint32_t nt, uint32_t nic, uint32_t dim0, uint32_t g_log, uint32_t ls_log, uint32_t n_work,
                        const SweepTrials& tr, hipStream_t s) {
     // one workgroup per CU (two per CU with half the staging measured 5 % slower); per = 8 nic / 128 items each (base path)
@@ -484,11 +511,11 @@ hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint3
         static std::atomic<uint64_t> big{0};                                                                                                       \
         const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;                                                                                        \
         if (!(big.load(std::memory_order_relaxed) & bit)) {                                                                                        \
-            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
+            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
             if (e != hipSuccess) return e;                                                                                                         \
             big.fetch_or(bit, std::memory_order_relaxed);                                                                                          \
         }                                                                                                                                          \
-        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
+        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS, NARROW>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
     } while (0)
     switch (nt) {
         case 1: SWEEP_MFMA(1); break;
@@ -531,7 +558,11 @@ hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs
 
 bool sweep1_mfma_ok(uint32_t num_per, uint32_t dim0) {
     // the base rule for nic = num_per columns and K = dim0 terms: num_per >= 128 (whole workgroups of 128 columns, a power of two), dim0 a power of two
-    // in [128, 4096] (whole pieces of 128 terms; K <= 2^12 for combine_limbs' 64-bit sums) -- and the packed trial layout (kernels.h) to convert from
+    // in [128, 4096] (whole pieces of 128 terms; K <= 2^12 for combine_limbs' 64-bit sums) -- and the packed trial layout (kernels.h) to convert from.
+    // num_per = 16, 32, 64 (whole blocks of 16 columns: the NARROW form fills its workgroups across trials), the same rule for dim0.  num_per <= 8 has
+    // no block of 16 columns: a 16-row operand would hold two trials
+    if (num_per >= 16u && num_per < 128u)
+        return (num_per & (num_per - 1u)) == 0 && dim0 >= 128u && dim0 <= 4096u && (dim0 & (dim0 - 1u)) == 0 && db1_packed(num_per, dim0);
     return (num_per & 1u) == 0 && sweep_mfma_ok(num_per / 2, dim0) && db1_packed(num_per, dim0);
 }
 void launch_db1_limb_planes(const uint64_t* packed_img, uint64_t* limbs, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz) {
@@ -543,10 +574,18 @@ void launch_db1_limb_unplanes(const uint64_t* limbs, uint64_t* packed_img, uint3
 hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* qs1, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t dim0, uint32_t trials,
                               size_t db_stride, size_t acc_stride, hipStream_t s) {
     if (n == 0 || n > kMaxLanes || trials == 0 || !sweep1_mfma_ok(num_per, dim0) || (db_stride & 1u)) return hipErrorInvalidValue;
-    uint32_t grp_log = 0;
-    while ((128u << grp_log) < num_per) grp_log++;
     const uint32_t nt = (8u * n + 15u) / 16u;
-    const SweepTrials tr{db_stride / 2u, acc_stride, grp_log};
+    uint32_t grp_log = 0;
+    if (num_per < 128u) {  // NARROW: 2^grp_log blocks of 16 columns per trial, groups of 8 blocks across trials (the last one may be ragged)
+        while ((16u << grp_log) < num_per) grp_log++;
+        if (trials > (0xFFFFFFFFu >> (grp_log + kLogN))) return hipErrorInvalidValue;
+        const uint32_t blocks = trials << grp_log;
+        const SweepTrials tr{db_stride / 2u, acc_stride, grp_log, blocks};
+        return launch_mfma<2, false, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0, kN * ((blocks + 7u) / 8u), tr,
+                                           s);
+    }
+    while ((128u << grp_log) < num_per) grp_log++;
+    const SweepTrials tr{db_stride / 2u, acc_stride, grp_log, 0};
     return launch_mfma<2>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0, (kN << grp_log) * trials, tr, s);
 }
 

@@ -27,6 +27,15 @@ def get_pack_shape(p: Params, out_n: int) -> PackShape:
     return s
 
 
+def has_limb_form(p: Params, out_n: int) -> bool:
+    """whether a batch (answer_batch, answer_batch_instances) on this geometry shares ONE matrix-core pass over the trial images: at least 16
+    ciphertexts per slot and a first dimension that is a power of two in [128, 4096].  A pure function of the parameters: no GPU needed."""
+    rc = lib().spiral_gpu_pack_has_limb_form(C.byref(p), out_n)
+    if rc < 0:
+        check(rc)
+    return bool(rc)
+
+
 def pack(out_n, m_conv, v_ct, v_W) -> np.ndarray:
     """pack (include/testing.h:36): out_n^2 raw 2x1 cts + out_n key matrices -> (out_n+1) x out_n NTT ciphertext"""
     out = np.zeros((out_n + 1, out_n, 2, N), dtype=np.uint64)

@@ -1,8 +1,11 @@
 """Batched SpiralPack answers at configs[4] (SpiralPack 2^18 x 30 KB: nu1=10, nu2=8, out_n=4, 16 trial images, ~60 GB on the device, generated
-there): for B = 1, 2, 4, 8 lanes of one owner, the time per answer_batch call, queries/s, and the batched first-dimension sweep alone (ms, algorithmic
-GB/s, fraction of the 8 TB/s HBM peak) -- beside the single-query answer on the packed image (the path bench.py --workload pack times).
+there) or, --geom pack14, at the parameter selector's spiral-pack pick (2^14 x 1 MB: nu1=10, nu2=4, out_n=12, 144 trial images of 16 ciphertexts per
+slot, 33.8 GB: the narrow form of the shared pass): for B = 1, 2, 4, 8 lanes of one owner, the time per answer_batch call, queries/s, and the batched
+first-dimension sweep alone (time_sweep_batch: ms, algorithmic GB/s, fraction of the 8 TB/s HBM peak) -- beside the single-query answer on the packed
+image (the path bench.py --workload pack times) and on the limb-plane image.  Per row the median and the min-to-max spread of the repetitions' device
+times, and the one-time in-place conversion of the image.
 
-    python tools/pack_batch.py [--reps 5] [--sizes 1,2,4,8] [--out profiles/pack_batch.json]
+    python tools/pack_batch.py [--geom config5|pack14] [--reps 5] [--sizes 1,2,4,8] [--out profiles/pack_batch.json]
 
 Prints one JSON line (and writes it to --out).  Synthetic keys and queries (uniform residues, as bench.py): timing only."""
 import argparse
@@ -16,6 +19,13 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0
+# name: (nu1, nu2, out_n, params, what it is)
+GEOMS = {
+    "config5": (10, 8, 4, dict(t_gsw=8, t_conv=4, t_exp=16, t_exp_right=56, qprime_bits=20, p_db=256),
+                "configs[4]: SpiralPack nu1=10, nu2=8, out_n=4, 16 trial images generated on the device"),
+    "pack14": (10, 4, 12, dict(t_gsw=16, t_conv=4, t_exp=56, t_exp_right=56, qprime_bits=23, p_db=1024),
+               "scheme --select 14,1000000 --variant spiral-pack (first pick): nu1=10, nu2=4, out_n=12, 144 trial images of 16 ciphertexts per slot"),
+}
 
 
 def synth(rng, sa, shape):
@@ -24,6 +34,7 @@ def synth(rng, sa, shape):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--geom", choices=sorted(GEOMS), default="config5")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="1,2,4,8")
     ap.add_argument("--out", default="")
@@ -35,8 +46,8 @@ def main():
 
     P = sys.modules["spiral_amd.pack"]
     sizes = [int(x) for x in args.sizes.split(",")]
-    out_n = 4
-    pg = sa.make_params(10, 8, t_gsw=8, t_conv=4, t_exp=16, t_exp_right=56, qprime_bits=20, p_db=256)
+    nu1, nu2, out_n, kw, what = GEOMS[args.geom]
+    pg = sa.make_params(nu1, nu2, **kw)
     shp = sa.get_pack_shape(pg, out_n)
     owner = sa.PackServer(pg, out_n)
     owner.gen_db(2024)
@@ -58,26 +69,45 @@ def main():
     single_ms = (time.perf_counter() - t0) * 1e3 / args.reps
     single_sweep_ms = float(np.mean([u["sweep_kernels_us"] for u in st])) / 1e3
     assert owner.db_format() == P.DB_PACKED
-    rows = []
+    med = lambda v: float(np.median(v))
+    spread = lambda v: [round(float(min(v)), 1), round(float(max(v)), 1)]
+    rows, convert_ms = [], None
     for b in sizes:
         lanes, q = servers[:b], qs[:b]
-        P.answer_batch(lanes, q)  # warm-up (the first batch of two or more converts the image in place)
+        if b >= 2 and owner.db_format() == P.DB_PACKED and P.has_limb_form(pg, out_n):
+            t0 = time.perf_counter()
+            owner.set_db_format(P.DB_LIMBS)  # what the first batch of two or more would do by itself: the one-time in-place conversion, timed alone
+            convert_ms = (time.perf_counter() - t0) * 1e3
+        P.answer_batch(lanes, q)  # warm-up
         stages = []
         t0 = time.perf_counter()
         for _ in range(args.reps):
             stages.append(P.answer_batch(lanes, q)[1])
         ms = (time.perf_counter() - t0) * 1e3 / args.reps
-        sw = P.time_sweep_batch(lanes, args.reps)
+        form = "limbs" if owner.db_format() == P.DB_LIMBS else "packed"  # (the form the timed batches ran on)
+        if owner.db_format() == P.DB_PACKED and P.has_limb_form(pg, out_n):  # (time_sweep_batch converts a covered image, whatever the lane count)
+            t0 = time.perf_counter()
+            owner.set_db_format(P.DB_LIMBS)
+            convert_ms = (time.perf_counter() - t0) * 1e3
+        sws = [P.time_sweep_batch(lanes, 3) for _ in range(args.reps)]
+        sw = med(sws)
         gbs = sweep_bytes / (sw * 1e-3) / 1e9
-        rows.append({"B": b, "ms_per_batch": round(ms, 3), "queries_per_s": round(b / (ms * 1e-3), 1), "sweep_ms": round(sw, 3), "sweep_algorithmic_GBps": round(gbs, 1),
-                     "sweep_frac_of_peak": round(gbs / HBM_PEAK_GBPS, 4), "image_form": "limbs" if owner.db_format() == P.DB_LIMBS else "packed",
+        dev = [s["total_us"] for s in stages]
+        rows.append({"B": b, "ms_per_batch": round(ms, 3), "queries_per_s": round(b / (ms * 1e-3), 1), "device_us_median": round(med(dev), 1), "device_us_spread": spread(dev),
+                     "device_queries_per_s": round(b / (med(dev) * 1e-6), 1), "sweep_ms": round(sw, 3), "sweep_ms_spread": [round(min(sws), 3), round(max(sws), 3)],
+                     "sweep_algorithmic_GBps": round(gbs, 1),
+                     "sweep_frac_of_peak": round(gbs / HBM_PEAK_GBPS, 4), "image_form": form, "sweep_image_form": "limbs" if owner.db_format() == P.DB_LIMBS else "packed",
                      "stages_us": {k: round(float(np.mean([s[k] for s in stages])), 1) for k in stages[0]}})
     # and the single answer again, now on the limb-plane image (the one-query instance of the batched kernel)
     t0 = time.perf_counter()
     st2 = [owner.answer(qs[0], want_packed=False)[2] for _ in range(args.reps)]
     single_limbs_ms = (time.perf_counter() - t0) * 1e3 / args.reps
-    out = {"tool": "pack_batch", "config": "configs[4]: SpiralPack nu1=10, nu2=8, out_n=4, 16 trial images generated on the device", "reps": args.reps,
-           "sweep_algorithmic_bytes": int(sweep_bytes),
+    dev1, dev2 = [u["total_us"] for u in st], [u["total_us"] for u in st2]
+    out = {"tool": "pack_batch", "config": what, "reps": args.reps, "has_limb_form": P.has_limb_form(pg, out_n),
+           "sweep_algorithmic_bytes": int(sweep_bytes), "device_db_bytes": owner.db_device_bytes(), "in_place_conversion_ms": convert_ms and round(convert_ms, 1),
+           "single_packed_device_us": {"median": round(med(dev1), 1), "spread": spread(dev1), "sweep_us_spread": spread([u["sweep_kernels_us"] for u in st])},
+           "single_limbs_device_us": {"median": round(med(dev2), 1), "spread": spread(dev2), "sweep_us_spread": spread([u["sweep_kernels_us"] for u in st2]),
+                                      "image_form": "limbs" if owner.db_format() == P.DB_LIMBS else "packed"},
            "single_packed": {"ms_per_query": round(single_ms, 3), "queries_per_s": round(1e3 / single_ms, 1), "sweep_ms": round(single_sweep_ms, 3),
                              "sweep_frac_of_peak": round(sweep_bytes / (single_sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)},
            "single_limbs": {"ms_per_query": round(single_limbs_ms, 3), "sweep_ms": round(float(np.mean([u["sweep_kernels_us"] for u in st2])) / 1e3, 3)},

@@ -1,6 +1,6 @@
 """SpiralPack items of several database instances (spiral_gpu_pack_server_answer_batch_instances) at the parameter selector's picks: per geometry one
 B = 1 item call against F separate answer calls on the same handles with the same query and against the selector's predicted_total_us; items/s at
-B = 2, 4, 8; groups of one (option pack_item_group = 1) against automatic grouping.  Every shape is warmed up first, the compared forms alternate within
+B = 2, 4, 8 (with the repetitions' spread) and the shared first-dimension pass alone; groups of one (option pack_item_group = 1) against automatic grouping.  Every shape is warmed up first, the compared forms alternate within
 the process, device-event times (the call's total_us, each answer's total_us).  Synthetic keys, queries and databases (uniform residues): timing only.
 
     python tools/pack_instances.py [--reps 5] [--geoms pack14,stream12,config5] [--out profiles/pack_instances.json]
@@ -105,7 +105,9 @@ def measure(sa, P, name, reps):
         set_group(sa, 1)
         g8.append(item(8))
         set_group(sa, 0)
-    r["batches"] = {str(B): dict(call_us=float(np.median(v)), items_per_s=B / float(np.median(v)) * 1e6) for B, v in per.items()}
+    r["batches"] = {str(B): dict(call_us=float(np.median(v)), items_per_s=B / float(np.median(v)) * 1e6, spread_call_us=[min(v), max(v)]) for B, v in per.items()}
+    # the shared first-dimension pass alone over instance 0's images (time_sweep_batch; the matrix-core pass where the geometry has limb planes)
+    r["shared_pass_ms"] = {str(B): float(np.median([P.time_sweep_batch(servers[:B], 3) for _ in range(reps)])) for B in (1, 2, 4, 8)}
     r["batches"]["8_group1_call_us"] = float(np.median(g8))
     r["b8_vs_8x_b1"] = r["batches"]["8"]["items_per_s"] / (8 * r["batches"]["1"]["items_per_s"])
     r["image_form_after"] = [i.db_format() for i in instances]
