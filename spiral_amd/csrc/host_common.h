@@ -114,13 +114,27 @@ struct DevBuf {
 struct Arena {
     uint64_t* base = nullptr;
     size_t used = 0;
+    uint64_t* take(size_t w) {
+        uint64_t* p = base ? base + used : nullptr;
+        used += (w + 31u) & ~(size_t)31u;  // 256-byte pieces
+        return p;
+    }
     void carve(DevBuf& b, size_t w) {
         b.words = w ? w : 1;
         b.carved = true;
-        b.p = base ? base + used : nullptr;
-        used += (b.words + 31u) & ~(size_t)31u;  // 256-byte pieces
+        b.p = take(b.words);
     }
 };
+// the two passes: `buf` becomes one allocation of the words `layout` takes, and holds the pieces `layout` carves
+template <class Layout>
+inline int alloc_carved(DevBuf& buf, Layout layout) {
+    Arena sizing;
+    layout(sizing);
+    if (buf.alloc(sizing.used)) return -1;
+    Arena real{buf.p};
+    layout(real);
+    return 0;
+}
 
 // scoped device scratch for the host-buffer seams
 struct Scratch {

@@ -7,6 +7,13 @@
 using namespace spiral;
 using namespace spiral::host;
 
+// The buffers the folding, packing and switch of one client write: its own (one instance), or one group of G instances of answer_batch_instances
+// (instance j's part of each buffer j x its one-instance words further on: the folding and packing launches take the group as G * n^2 trials)
+struct PkBufs {
+    uint64_t *acc, *raw, *fold_d, *fold_c, *fold_c2, *ginv, *ct2, *res, *pk_raw, *resp, *wire;
+    size_t acc_words, slot_words, wire_words;  // one instance's words of acc / of res, pk_raw and resp / of wire (whole words: 2048 values per polynomial)
+};
+
 struct spiral_gpu_pack_server {
     spiral_gpu_params p;
     spiral_gpu_pack_shape s;
@@ -19,8 +26,12 @@ struct spiral_gpu_pack_server {
     bool have_pp = false;
     bool packed_after_front = false;  // event 6 belongs to the same answer as events 0..5
     uint32_t n_cv = 0;
-    DevBuf w_left, w_right, v, v_w, query, cv, ex_raw, ex_g;
-    DevBuf gs_raw, gs_chat, gs_tmp, gsw, key, qs1, acc, raw, fold_d, fold_c, fold_c2, pk_ginv, pk_ct2, pk_res, pk_raw, resp, stage, wire;
+    // every buffer below but the lazy ones (stage, wire_in, item) is a piece of `arena`, carved in one fixed order (pk_layout): servers with equal
+    // parameters, out_n and trial range have equal layouts
+    DevBuf arena;
+    DevBuf w_left, w_right, v, v_w, query, cv, ex_raw, ex_g, gs_raw, gs_chat, gs_tmp, gsw, key, qs1;  // the client's own
+    PkBufs own{};  // what one answer writes
+    DevBuf stage;
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
     hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch / item call end, [8] ordering another call's stream in front of an item call
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
@@ -62,12 +73,20 @@ int pack_shape_of(const spiral_gpu_params* p, uint32_t out_n, spiral_gpu_pack_sh
 // the owner of the images S sweeps, while it lives (S itself, or a lane's owner)
 spiral_gpu_pack_server* pk_owner(const spiral_gpu_pack_server* S) { return (spiral_gpu_pack_server*)S->img->owner; }
 
+// what writes the trial images goes through the server that owns them: a lane refuses (verb null: set_db_format's wording)
+int pk_refuse_lane(const spiral_gpu_pack_server* S, const char* verb) {
+    if (S->img->owner == S) return 0;
+    return verb ? fail("this server is a lane: it sweeps its owner's database, %s it through the owner", verb)
+                : fail("this server is a lane: convert the image through its owner");
+}
+int pk_check_trial(const spiral_gpu_pack_server* S, uint32_t trial) {
+    if (trial >= S->t0 && trial < S->t0 + S->nt) return 0;
+    return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+}
+
 void pk_free(spiral_gpu_pack_server* S) {
     DbImage::drop(S->img, S);
-    DevBuf* all[] = {&S->w_left, &S->w_right, &S->v, &S->v_w, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->gs_raw, &S->gs_chat, &S->gs_tmp,
-                     &S->gsw, &S->key, &S->qs1, &S->acc, &S->raw, &S->fold_d, &S->fold_c, &S->fold_c2, &S->pk_ginv, &S->pk_ct2, &S->pk_res, &S->pk_raw, &S->resp,
-                     &S->stage, &S->wire, &S->item};
-    for (DevBuf* b : all) b->release();
+    for (DevBuf* b : {&S->arena, &S->stage, &S->item}) b->release();  // (what owns memory: every other buffer is a piece of the arena)
     S->item_cap = 0;
     S->wire_in.release();
     for (auto& e : S->ev)
@@ -76,41 +95,53 @@ void pk_free(spiral_gpu_pack_server* S) {
     S->stream = nullptr;
 }
 
-int pk_alloc(spiral_gpu_pack_server* S, DbImage* owners) {
+// Every device buffer of a SpiralPack server but the lazy ones, stated once, in the order it is carved from one allocation.  Two parts: the client's own
+// buffers (client: the members of S), then the per-answer buffers B for g instances, each g x its one-instance words -- the server's own with g = 1
+// (pk_alloc), the arena of an item group with g = G and no client part (pk_item_group, pk_answer_items).
+void pk_layout(spiral_gpu_pack_server* S, Arena& a, bool client, uint32_t g, PkBufs& B) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
-    const size_t ngs = (size_t)p.nu2 * s.ell, rows = S->out_n + 1;
-    S->img = owners ? owners->share() : DbImage::create(DbLayout::packed1(s.num_per, s.dim0, S->nt), S);  // (a lane sweeps its owner's images)
-    if (!S->img) return -1;
-    if (S->w_left.alloc((size_t)s.n_left * 2 * p.t_exp * kN)) return -1;
-    if (S->w_right.alloc((size_t)s.n_right * 2 * p.t_exp_right * kN)) return -1;
-    if (S->v.alloc((size_t)2 * 2 * p.t_conv * kN)) return -1;
-    if (S->v_w.alloc((size_t)S->out_n * rows * p.t_conv * kN)) return -1;
-    if (S->query.alloc((size_t)s.n_query_cts * 2 * kN)) return -1;
-    S->n_cv = p.direct_upload ? s.n_query_cts : (1u << s.g);
-    if (S->cv.alloc((size_t)S->n_cv * 2 * kN)) return -1;
-    HIP_OK(hipMemset(S->cv.p, 0, S->cv.words * sizeof(uint64_t)));
-    if (!p.direct_upload) {
-        if (S->ex_raw.alloc((size_t)S->n_cv * 2 * kN)) return -1;
-        if (S->ex_g.alloc(expand_g_polys(s.g, p.t_exp, p.t_exp_right) * kN)) return -1;
-        if (S->gs_raw.alloc(ngs * 2 * kN)) return -1;
-        if (S->gs_chat.alloc(ngs * 2 * p.t_conv * kN)) return -1;
-        if (S->gs_tmp.alloc(ngs * 2 * kN)) return -1;
+    const size_t ngs = (size_t)p.nu2 * s.ell, rows = S->out_n + 1, half = s.num_per / 2;
+    if (client) {
+        a.carve(S->w_left, (size_t)s.n_left * 2 * p.t_exp * kN);
+        a.carve(S->w_right, (size_t)s.n_right * 2 * p.t_exp_right * kN);
+        a.carve(S->v, (size_t)2 * 2 * p.t_conv * kN);
+        a.carve(S->v_w, (size_t)S->out_n * rows * p.t_conv * kN);
+        a.carve(S->query, (size_t)s.n_query_cts * 2 * kN);
+        a.carve(S->cv, (size_t)S->n_cv * 2 * kN);
+        if (!p.direct_upload) {
+            a.carve(S->ex_raw, (size_t)S->n_cv * 2 * kN);
+            a.carve(S->ex_g, expand_g_polys(s.g, p.t_exp, p.t_exp_right) * kN);
+            a.carve(S->gs_raw, ngs * 2 * kN);
+            a.carve(S->gs_chat, ngs * 2 * p.t_conv * kN);
+            a.carve(S->gs_tmp, ngs * 2 * kN);
+        }
+        a.carve(S->gsw, (size_t)p.nu2 * 2 * 2 * s.ell * kN);
+        a.carve(S->key, (size_t)p.nu2 * 2 * 4 * s.ell * kN);
+        a.carve(S->qs1, (size_t)kN * s.dim0 * 2);  // 4 u32 per (z, j)
     }
-    if (S->gsw.alloc((size_t)p.nu2 * 2 * 2 * s.ell * kN)) return -1;
-    if (S->key.alloc((size_t)p.nu2 * 2 * 4 * s.ell * kN)) return -1;
-    if (S->qs1.alloc((size_t)kN * s.dim0 * 2)) return -1;  // 4 u32 per (z, j)
-    if (S->acc.alloc((size_t)S->nt * s.num_per * 2 * kN)) return -1;
-    if (S->raw.alloc((size_t)S->nt * s.num_per * 2 * kN)) return -1;
-    const size_t half = s.num_per / 2;
-    if (S->fold_d.alloc((size_t)S->nt * half * 4 * s.ell * kN)) return -1;
-    if (S->fold_c.alloc((size_t)S->nt * half * 2 * kN)) return -1;
-    if (S->fold_c2.alloc((size_t)S->nt * half * 2 * kN)) return -1;
-    if (S->pk_ginv.alloc((size_t)s.trials * p.t_conv * kN)) return -1;
-    if (S->pk_ct2.alloc((size_t)s.trials * kN)) return -1;
-    if (S->pk_res.alloc(rows * S->out_n * kN)) return -1;
-    if (S->pk_raw.alloc(rows * S->out_n * kN)) return -1;
-    if (S->resp.alloc(rows * S->out_n * kN)) return -1;
+    B.acc_words = (size_t)S->nt * s.num_per * 2 * kN;
+    B.slot_words = rows * S->out_n * kN;
+    B.wire_words = (wire_bytes(&p, S->out_n) + 7) / 8;
+    B.acc = a.take(g * B.acc_words);
+    B.raw = a.take(g * B.acc_words);
+    B.fold_d = a.take(g * ((size_t)S->nt * half * 4 * s.ell * kN));
+    B.fold_c = a.take(g * ((size_t)S->nt * half * 2 * kN));
+    B.fold_c2 = a.take(g * ((size_t)S->nt * half * 2 * kN));
+    B.ginv = a.take(g * ((size_t)s.trials * p.t_conv * kN));
+    B.ct2 = a.take(g * ((size_t)s.trials * kN));
+    B.res = a.take(g * B.slot_words);
+    B.pk_raw = a.take(g * B.slot_words);
+    B.resp = a.take(g * B.slot_words);
+    B.wire = a.take(g * B.wire_words);
+}
+
+int pk_alloc(spiral_gpu_pack_server* S, DbImage* owners) {
+    S->img = owners ? owners->share() : DbImage::create(DbLayout::packed1(S->s.num_per, S->s.dim0, S->nt), S);  // (a lane sweeps its owner's images)
+    if (!S->img) return -1;
+    S->n_cv = S->p.direct_upload ? S->s.n_query_cts : (1u << S->s.g);
+    if (alloc_carved(S->arena, [&](Arena& a) { pk_layout(S, a, true, 1, S->own); })) return -1;
+    HIP_OK(hipMemset(S->cv.p, 0, S->cv.words * sizeof(uint64_t)));
     return 0;
 }
 
@@ -184,40 +215,8 @@ int pk_sweep_into(const DbImage* H, spiral_gpu_pack_server* const* servers, uint
 // ... over servers[0]'s images, into each server's own accumulators
 int pk_sweep(spiral_gpu_pack_server* const* servers, uint32_t n, hipStream_t st) {
     uint64_t* acc[kMaxLanes];
-    for (uint32_t b = 0; b < n; b++) acc[b] = servers[b]->acc.p;
+    for (uint32_t b = 0; b < n; b++) acc[b] = servers[b]->own.acc;
     return pk_sweep_into(servers[0]->img, servers, acc, n, st);
-}
-
-// The buffers the folding, packing and switch of one client write: its own (one instance), or one group of G instances of answer_batch_instances
-// (instance j's part of each buffer j x its one-instance size further on: the folding and packing launches take the group as G * n^2 trials)
-struct PkBufs {
-    uint64_t *acc, *raw, *fold_d, *fold_c, *fold_c2, *ginv, *ct2, *res, *pk_raw, *resp, *wire;
-};
-constexpr int kPkBufs = 11;
-PkBufs pk_own_bufs(spiral_gpu_pack_server* S) {
-    return PkBufs{S->acc.p, S->raw.p, S->fold_d.p, S->fold_c.p, S->fold_c2.p, S->pk_ginv.p, S->pk_ct2.p, S->pk_res.p, S->pk_raw.p, S->resp.p, S->wire.p};
-}
-// one instance's words of each PkBufs buffer (pk_alloc's sizes; the wire form in whole words)
-void pk_inst_words(const spiral_gpu_pack_server* S, size_t w[kPkBufs]) {
-    const spiral_gpu_pack_shape& s = S->s;
-    const size_t half = s.num_per / 2, rows = S->out_n + 1, slot = rows * S->out_n * kN;
-    const size_t v[kPkBufs] = {(size_t)S->nt * s.num_per * 2 * kN, (size_t)S->nt * s.num_per * 2 * kN, (size_t)S->nt * half * 4 * s.ell * kN,
-                               (size_t)S->nt * half * 2 * kN, (size_t)S->nt * half * 2 * kN, (size_t)s.trials * S->p.t_conv * kN, (size_t)s.trials * kN,
-                               slot, slot, slot, (wire_bytes(&S->p, S->out_n) + 7) / 8};
-    for (int i = 0; i < kPkBufs; i++) w[i] = v[i];
-}
-// the arena of a group of g instances: carved from base into *b (b null: sizing only); returns its words
-size_t pk_group_carve(const spiral_gpu_pack_server* S, uint32_t g, uint64_t* base, PkBufs* b) {
-    PkBufs sizing;
-    if (!b) b = &sizing;
-    size_t w[kPkBufs], used = 0;
-    pk_inst_words(S, w);
-    uint64_t** dst[kPkBufs] = {&b->acc, &b->raw, &b->fold_d, &b->fold_c, &b->fold_c2, &b->ginv, &b->ct2, &b->res, &b->pk_raw, &b->resp, &b->wire};
-    for (int i = 0; i < kPkBufs; i++) {
-        *dst[i] = base ? base + used : nullptr;
-        used += ((size_t)g * w[i] + 31u) & ~(size_t)31u;  // 256-byte pieces
-    }
-    return used;
 }
 
 }  // namespace
@@ -333,7 +332,7 @@ void spiral_gpu_pack_server_destroy(spiral_gpu_pack_server* S) {
 int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server* S, int format) {
     if (!S) return fail("null server");
     if (format != SPIRAL_GPU_DB_PACKED && format != SPIRAL_GPU_DB_LIMBS) return fail("unknown database image format %d", format);
-    if (S->img->owner != S) return fail("this server is a lane: convert the image through its owner");
+    if (pk_refuse_lane(S, nullptr)) return -1;
     if (!S->img->loaded) return fail("no database loaded");
     HIP_OK(hipSetDevice(S->device));
     return S->img->set_format((uint32_t)format, S->stream);
@@ -343,7 +342,7 @@ uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server* S) { ret
 
 int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
-    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (pk_refuse_lane(S, "load")) return -1;
     HIP_OK(hipSetDevice(S->device));
     S->img->begin_rewrite();
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per, chunk = 1u << 18;
@@ -370,9 +369,9 @@ int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
 
 int spiral_gpu_pack_server_load_db(spiral_gpu_pack_server* S, uint32_t trial, const uint64_t* db) {
     if (!S || !db) return fail("null argument");
-    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (pk_refuse_lane(S, "load")) return -1;
     HIP_OK(hipSetDevice(S->device));
-    if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    if (pk_check_trial(S, trial)) return -1;
     // one trial is rewritten: the others keep their words, so an image in limb-plane form goes back to the packed form first
     if (S->img->begin_partial(S->stream)) return -1;
     DevBuf st;
@@ -394,9 +393,9 @@ int spiral_gpu_pack_server_load_db(spiral_gpu_pack_server* S, uint32_t trial, co
 int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, uint64_t first_item,
                                          uint64_t n_items) {
     if (!S) return fail("null server");
-    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (pk_refuse_lane(S, "load")) return -1;
     HIP_OK(hipSetDevice(S->device));
-    if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    if (pk_check_trial(S, trial)) return -1;
     // a partial load scatters packed words into the image: an image in limb-plane form goes back to the packed form first
     if (S->img->begin_partial(S->stream)) return -1;
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
@@ -428,9 +427,9 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
 int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, const uint64_t* item_ids,
                                            uint64_t n) {
     if (!S) return fail("null server");
-    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, update it through the owner");
+    if (pk_refuse_lane(S, "update")) return -1;
     if (!S->img->loaded) return fail("no database loaded");
-    if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    if (pk_check_trial(S, trial)) return -1;
     HIP_OK(hipSetDevice(S->device));
     const uint64_t np = S->s.num_per;
     if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
@@ -441,7 +440,7 @@ int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t t
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
-    if (S->img->owner != S) return fail("this server is a lane: it sweeps its owner's database, load it through the owner");
+    if (pk_refuse_lane(S, "load")) return -1;
     HIP_OK(hipSetDevice(S->device));
     S->img->begin_rewrite();
     for (uint32_t t = 0; t < S->nt; t++) launch_fill_db1_random(S->img->trial(t), S->s.num_per, S->s.dim0, seed + S->t0 + t, S->stream);
@@ -590,7 +589,7 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
     return 0;
 }
 
-static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) { return pk_fold_into(S, pk_own_bufs(S), S->nt, st); }
+static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) { return pk_fold_into(S, S->own, S->nt, st); }
 
 static int pk_front(spiral_gpu_pack_server* S) {
     spiral_gpu_pack_server* one[1] = {S};
@@ -601,17 +600,18 @@ static int pk_front(spiral_gpu_pack_server* S) {
 // pack + modulus switch (:1064-1081) of out_n^2 folded ciphertexts at a stride of `ct_stride` ciphertexts; event 6 closes it
 static int pk_back(spiral_gpu_pack_server* S, const uint64_t* folded, uint32_t ct_stride, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
+    const PkBufs& B = S->own;
     const uint32_t rows = S->out_n + 1;
-    run_pack(S->tb, folded, ct_stride, S->v_w.p, S->pk_ginv.p, S->pk_ct2.p, S->pk_res.p, S->out_n, p.t_conv, st);
+    run_pack(S->tb, folded, ct_stride, S->v_w.p, B.ginv, B.ct2, B.res, S->out_n, p.t_conv, st);
     InvParams ip{};
-    ip.src = S->pk_res.p;
-    ip.dst = S->pk_raw.p;
+    ip.src = B.res;
+    ip.dst = B.pk_raw;
     ip.src_map = ip.dst_map = identity_map();
     launch_ntt_inverse(S->tb, ip, IST_CRT, rows * S->out_n, st);
-    launch_rescale(S->pk_raw.p, S->resp.p, S->out_n * kN, kQ, S->s.qprime, st);
-    launch_rescale(S->pk_raw.p + (size_t)S->out_n * kN, S->resp.p + (size_t)S->out_n * kN, S->out_n * S->out_n * kN, kQ, 4 * p.p_db, st);
+    launch_rescale(B.pk_raw, B.resp, S->out_n * kN, kQ, S->s.qprime, st);
+    launch_rescale(B.pk_raw + (size_t)S->out_n * kN, B.resp + (size_t)S->out_n * kN, S->out_n * S->out_n * kN, kQ, 4 * p.p_db, st);
     HIP_OK(hipEventRecord(S->ev[6], st));
-    S->packed_after_front = folded == S->raw.p;  // (a gathered buffer was filled by other servers too: no common time line)
+    S->packed_after_front = folded == B.raw;  // (a gathered buffer was filled by other servers too: no common time line)
     return 0;
 }
 
@@ -619,10 +619,10 @@ static int pk_download(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* 
     const uint32_t rows = S->out_n + 1;
     HIP_OK(hipStreamSynchronize(S->stream));
     HIP_OK(hipGetLastError());
-    if (response) HIP_OK(hipMemcpy(response, S->resp.p, (size_t)rows * S->out_n * kPolyBytes, hipMemcpyDeviceToHost));
+    if (response) HIP_OK(hipMemcpy(response, S->own.resp, (size_t)rows * S->out_n * kPolyBytes, hipMemcpyDeviceToHost));
     if (packed_ct) {
         Scratch sc;
-        if (download_pk(sc, S->pk_res.p, identity_map(), packed_ct, (size_t)rows * S->out_n)) return -1;
+        if (download_pk(sc, S->own.res, identity_map(), packed_ct, (size_t)rows * S->out_n)) return -1;
     }
     return 0;
 }
@@ -637,7 +637,7 @@ static int pk_check_answer(spiral_gpu_pack_server* S) {
 
 // the answer to the query in S->query
 static int pk_answer_taken(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
-    if (pk_front(S) || pk_back(S, S->raw.p, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
+    if (pk_front(S) || pk_back(S, S->own.raw, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
     return stage_us ? spiral_gpu_pack_server_stage_us(S, stage_us) : 0;
 }
 
@@ -719,7 +719,7 @@ static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, F
     HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at servers[n - 1]'s event 2)
     for (uint32_t b = 0; b < n; b++) {
         spiral_gpu_pack_server* L = servers[b];
-        if (pk_fold(L, st) || pk_back(L, L->raw.p, L->s.num_per, st)) return -1;
+        if (pk_fold(L, st) || pk_back(L, L->own.raw, L->s.num_per, st)) return -1;
     }
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
@@ -783,8 +783,14 @@ static int pk_check_items(spiral_gpu_pack_server* const* servers, uint32_t n, sp
 // the group size: option pack_item_group (0 = automatic: the largest G <= n_inst whose arenas, on every client, fit a quarter of the device memory free
 // now, counting what the clients' arenas already hold), never more launch rows than the folding's product takes in one grid dimension; then the
 // arenas, halving G while an allocation fails.  G = 1 needs none: the clients' own buffers.
+static size_t pk_group_words(spiral_gpu_pack_server* S, uint32_t G) {  // (the sizing pass of pk_answer_items' carve)
+    Arena a;
+    PkBufs B;
+    pk_layout(S, a, false, G, B);
+    return a.used;
+}
 static uint32_t pk_item_group(spiral_gpu_pack_server* const* servers, uint32_t n, uint32_t n_inst) {
-    const spiral_gpu_pack_server* S = servers[0];
+    spiral_gpu_pack_server* S = servers[0];
     const size_t per_group = (size_t)S->nt * (S->s.num_per / 2);  // the first fold round's ciphertexts per instance: grid rows of pack_fold_mac
     uint32_t G = options().pack_item_group ? std::min(options().pack_item_group, n_inst) : n_inst;
     G = (uint32_t)std::max<size_t>(1, std::min<size_t>(G, 65535 / std::max<size_t>(1, per_group)));
@@ -794,7 +800,7 @@ static uint32_t pk_item_group(spiral_gpu_pack_server* const* servers, uint32_t n
         (void)hipGetLastError();
         for (uint32_t b = 0; b < n; b++) held += servers[b]->item.p ? servers[b]->item.words * 8 : 0;
         const size_t budget = (free_b + held) / 4;
-        while (G > 1 && (size_t)n * pk_group_carve(S, G, nullptr, nullptr) * 8 > budget) G--;
+        while (G > 1 && (size_t)n * pk_group_words(S, G) * 8 > budget) G--;
     }
     for (; G > 1; G /= 2) {
         bool ok = true;
@@ -803,7 +809,7 @@ static uint32_t pk_item_group(spiral_gpu_pack_server* const* servers, uint32_t n
             if (L->item_cap >= G) continue;
             L->item.release();
             L->item_cap = 0;
-            const size_t words = pk_group_carve(L, G, nullptr, nullptr);
+            const size_t words = pk_group_words(L, G);
             if (hipMalloc(&L->item.p, words * 8) != hipSuccess) {
                 (void)hipGetLastError();  // (no sticky out-of-memory for the launches that follow)
                 L->item.p = nullptr;
@@ -821,20 +827,16 @@ static uint32_t pk_item_group(spiral_gpu_pack_server* const* servers, uint32_t n
 static int pk_item_back(spiral_gpu_pack_server* L, const PkBufs& B, uint32_t g, bool want_wire, hipStream_t st) {
     const spiral_gpu_params& p = L->p;
     const uint32_t rows = L->out_n + 1;
-    const int64_t slot = (int64_t)rows * L->out_n * kN;
     run_pack(L->tb, B.raw, L->s.num_per, L->v_w.p, B.ginv, B.ct2, B.res, L->out_n, p.t_conv, st, g);
     InvParams ip{};
     ip.src = B.res;
     ip.dst = B.pk_raw;
     ip.src_map = ip.dst_map = identity_map();
     launch_ntt_inverse(L->tb, ip, IST_CRT, g * rows * L->out_n, st);
-    const Slots slots{g, slot};
-    launch_rescale2_slots(B.pk_raw, B.resp, L->out_n * kN, (uint32_t)slot, kQ, L->s.qprime, 4 * p.p_db, slots, st);
-    if (want_wire) {
-        size_t w[kPkBufs];
-        pk_inst_words(L, w);
-        launch_response_wire_slots(B.resp, B.wire, L->out_n * kN, p.qprime_bits, L->out_n * L->out_n * kN, wire_bits_rest(&p), slots, (int64_t)w[kPkBufs - 1], st);
-    }
+    const Slots slots{g, (int64_t)B.slot_words};
+    launch_rescale2_slots(B.pk_raw, B.resp, L->out_n * kN, (uint32_t)B.slot_words, kQ, L->s.qprime, 4 * p.p_db, slots, st);
+    if (want_wire)
+        launch_response_wire_slots(B.resp, B.wire, L->out_n * kN, p.qprime_bits, L->out_n * L->out_n * kN, wire_bits_rest(&p), slots, (int64_t)B.wire_words, st);
     L->packed_after_front = false;
     return 0;
 }
@@ -862,26 +864,20 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
         for (uint32_t k = 0; k < n_inst; k++)
             if (instances[k]->img->set_format(SPIRAL_GPU_DB_LIMBS, st)) return -1;
     const uint32_t G = pk_item_group(servers, n, n_inst);
-    size_t w[kPkBufs];
-    pk_inst_words(S, w);
-    const size_t slot_words = w[kPkBufs - 2], wire_b = wire_bytes(&S->p, S->out_n);
-    PkBufs bufs[kMaxLanes];
+    PkBufs bufs[kMaxLanes];  // G = 1: the clients' own; else their item arenas, carved for G instances
     for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_pack_server* L = servers[b];
-        if (G == 1) {
-            if (wire && L->wire.words * 8 < wire_b && (L->wire.release(), L->wire.alloc(wire_b / 8))) return -1;
-            bufs[b] = pk_own_bufs(L);
-        } else {
-            pk_group_carve(L, G, L->item.p, &bufs[b]);
-        }
+        Arena a{servers[b]->item.p};
+        bufs[b] = servers[b]->own;
+        if (G > 1) pk_layout(servers[b], a, false, G, bufs[b]);
     }
+    const size_t slot_words = bufs[0].slot_words, wire_b = bufs[0].wire_words * 8;
     for (uint32_t b = 0; b < n; b++)
         if (pk_expand_convert(servers[b], st)) return -1;  // once per client, whatever the number of instances
     for (uint32_t k0 = 0; k0 < n_inst; k0 += G) {
         const uint32_t g = std::min(G, n_inst - k0);
         for (uint32_t j = 0; j < g; j++) {  // one first-dimension pass per instance for all clients, into instance j's part of each group arena
             uint64_t* acc[kMaxLanes];
-            for (uint32_t b = 0; b < n; b++) acc[b] = bufs[b].acc + (size_t)j * w[0];
+            for (uint32_t b = 0; b < n; b++) acc[b] = bufs[b].acc + (size_t)j * bufs[b].acc_words;
             if (pk_sweep_into(instances[k0 + j]->img, servers, acc, n, st)) return -1;
         }
         for (uint32_t b = 0; b < n; b++) {  // folding, packing, switch and wire form: one sequence per client and group
@@ -977,7 +973,7 @@ int spiral_gpu_pack_server_fold_trials(spiral_gpu_pack_server* S, const uint64_t
     HIP_OK(hipSetDevice(S->device));
     if (!S->img->loaded || !S->have_pp) return fail("database and public parameters must be set first");
     if (pk_take_query(S, FORM_NTT, query, 0, "fold_trials") || pk_front(S)) return -1;
-    HIP_OK(hipMemcpy2DAsync(folded_dev, 2 * kPolyBytes, S->raw.p, (size_t)S->s.num_per * 2 * kPolyBytes, 2 * kPolyBytes, S->nt, hipMemcpyDeviceToDevice,
+    HIP_OK(hipMemcpy2DAsync(folded_dev, 2 * kPolyBytes, S->own.raw, (size_t)S->s.num_per * 2 * kPolyBytes, 2 * kPolyBytes, S->nt, hipMemcpyDeviceToDevice,
                             S->stream));
     return 0;
 }
@@ -1009,9 +1005,8 @@ int spiral_gpu_pack_server_read_response_wire(spiral_gpu_pack_server* S, void* o
     HIP_OK(hipSetDevice(S->device));
     const size_t nbytes = wire_bytes(&S->p, S->out_n);
     if (capacity < nbytes) return fail("response buffer of %zu bytes, the wire form needs %zu", capacity, nbytes);
-    if (S->wire.words * 8 < nbytes && (S->wire.release(), S->wire.alloc(nbytes / 8))) return -1;
-    launch_response_wire(S->resp.p, S->wire.p, S->out_n * kN, S->p.qprime_bits, S->out_n * S->out_n * kN, wire_bits_rest(&S->p), S->stream);
-    HIP_OK(hipMemcpyAsync(out, S->wire.p, nbytes, hipMemcpyDeviceToHost, S->stream));
+    launch_response_wire(S->own.resp, S->own.wire, S->out_n * kN, S->p.qprime_bits, S->out_n * S->out_n * kN, wire_bits_rest(&S->p), S->stream);
+    HIP_OK(hipMemcpyAsync(out, S->own.wire, nbytes, hipMemcpyDeviceToHost, S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     return 0;
 }
@@ -1019,10 +1014,10 @@ int spiral_gpu_pack_server_read_response_wire(spiral_gpu_pack_server* S, void* o
 int spiral_gpu_pack_server_read_acc(spiral_gpu_pack_server* S, uint32_t trial, uint64_t* out) {
     if (!S || !out) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
-    if (trial < S->t0 || trial >= S->t0 + S->nt) return fail("trial %u is not one of this server's [%u, %u)", trial, S->t0, S->t0 + S->nt);
+    if (pk_check_trial(S, trial)) return -1;
     HIP_OK(hipStreamSynchronize(S->stream));
     Scratch sc;
-    return download_pk(sc, S->acc.p + (size_t)(trial - S->t0) * S->s.num_per * 2 * kN, identity_map(), out, (size_t)S->s.num_per * 2);
+    return download_pk(sc, S->own.acc + (size_t)(trial - S->t0) * S->s.num_per * 2 * kN, identity_map(), out, (size_t)S->s.num_per * 2);
 }
 
 uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server* S) {

@@ -164,12 +164,7 @@ int srv_alloc(spiral_gpu_server* S, DbImage* owners) {
         a.carve(S->fold_c2, half * 6 * kN);
         a.carve(S->resp, (size_t)6 * kN);
     };
-    Arena sizing;
-    layout(sizing);
-    if (S->arena.alloc(sizing.used)) return -1;
-    Arena real;
-    real.base = S->arena.p;
-    layout(real);
+    if (alloc_carved(S->arena, layout)) return -1;
     HIP_OK(hipMemset(S->cv.p, 0, S->cv.words * sizeof(uint64_t)));
     S->gs_raw_p = S->cv_raw.p + (size_t)S->dim0_shard * kN;
     S->gs_chat_p = S->cv_g.p + (size_t)S->dim0_shard * p.t_conv * kN;
@@ -187,10 +182,7 @@ void srv_drop_graphs(spiral_gpu_server* S) {
 void srv_free(spiral_gpu_server* S) {
     srv_drop_graphs(S);
     DbImage::drop(S->img, S);
-    DevBuf* all[] = {&S->w_left, &S->w_right, &S->w, &S->v, &S->query, &S->cv, &S->ex_raw, &S->ex_g, &S->ex_raw2, &S->ex_g2, &S->cv_raw,
-                     &S->cv_g, &S->key, &S->cts_keep, &S->qs, &S->acc_own, &S->raw, &S->fold_d, &S->fold_c, &S->fold_c2,
-                     &S->resp, &S->stage, &S->wire, &S->arena};  // (the arena after its pieces)
-    for (DevBuf* b : all) b->release();
+    for (DevBuf* b : {&S->arena, &S->ex_raw2, &S->ex_g2, &S->cts_keep, &S->stage, &S->wire}) b->release();  // (what owns memory: the rest are pieces of the arena)
     S->wire_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e);
