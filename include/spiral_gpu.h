@@ -76,7 +76,11 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *   "fwd2_min"        that threshold (default 8192 transforms per launch, all query lanes together)
  *   "db_stage_bytes"  bytes of the staging buffer of load_db / load_db_items (default 64 MiB).  Initial value: SPIRAL_DB_STAGE_BYTES.
  *   "pack_item_group" instances per group of spiral_gpu_pack_server_answer_batch_instances (default 0: automatic; g: at most g)
+ *   "pack_batch_lanes" 0 .. 8 (default 0 = never: opt-in): the smallest number of clients from which spiral_gpu_pack_server_answer_batch and
+ *                     ..._answer_batch_instances (and their _wire / _seeded forms) take the lane form -- every launch carries all clients; 0 = never.
+ *                     Read per call; same results either way
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
+ *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  * These three environment variables are the only ones the library reads. */
 int spiral_gpu_set_option(const char *name, int64_t value);
 int spiral_gpu_get_option(const char *name, int64_t *value);
@@ -557,13 +561,21 @@ uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algor
 /* Batches on the pack path, beyond the reference (one query per call).  create_lane: a new server with the owner's parameters, out_n and
  * device that sweeps the OWNER's trial images and has its own public parameters, query and intermediates (loads through a lane fail; the
  * images are counted and go with their last reference, the owner's or a lane's; trial-sharded owners have no lanes).
- * answer_batch: n <= 8 servers -- an owner and/or its lanes, each with its own client's public parameters -- answer queries[b] each: expansion and
- * conversion per lane, ONE first-dimension pass over every trial image for all n queries, then folding, packing and the modulus switch per lane,
- * all on servers[0]'s stream; returns synchronised.  Afterwards every lane's buffers (read_acc of every trial, read_response_wire) hold exactly
+ * answer_batch: n <= 8 servers -- an owner and/or its lanes, in any order, each with its own client's public parameters -- answer queries[b] each:
+ * expansion and conversion, ONE first-dimension pass over every trial image for all n queries, then folding, packing and the modulus switch, all on
+ * servers[0]'s stream (what the other servers' streams hold is ordered in front, what follows on them behind); returns synchronised.  From option
+ * "pack_batch_lanes" clients on (default 0: never, set it to 2 for every batch) this is the LANE FORM: every launch of the sequence carries all n clients in its grid -- one
+ * expansion, one conversion, the pass, one folding, one packing and switch, as many launches as one answer has; below it the stages other than the pass
+ * run per lane, one client after another.  Afterwards every lane's buffers (read_acc of every trial, read_response_wire) hold exactly
  * what its own answer would have left.  responses[b] / packed_cts[b] (or the arrays) may be NULL.  stage_us (may be NULL): [0] expansion [1]
- * conversion [3] folding [4] packing, summed over the lanes, [2] = [5] the shared sweep, [6] total, [7] n.  Every query is uploaded before the first
+ * conversion [3] folding [4] packing, summed over the lanes (lane form: the whole-batch intervals between servers[0]'s events), [2] = [5] the shared
+ * sweep, [6] total, [7] n.  The lane form records events on servers[0] only: afterwards spiral_gpu_pack_server_stage_us of servers[0] gives the batch's
+ * intervals, and of any other lane of the call it fails with a message (until that lane answers alone or as servers[0] again) -- after the per-lane form
+ * it gives that lane's own share.  The same holds for the clients of a lane-form answer_batch_instances.  Every query is uploaded before the first
  * launch, so [6] (and answer_batch_instances' total_us) is device time of the launches alone, in every form of the queries.  Every server is checked before anything
- * is launched (n in 1 .. 8, no duplicates, same image, parameters, database and public parameters present): a failing check leaves every lane's
+ * is launched (n in 1 .. 8, no duplicates, same image, parameters, database and public parameters present; and, in every multi-server SpiralPack call --
+ * answer_batch in either form, time_sweep_batch, answer_batch_instances -- that every server's buffers are laid out as servers[0]'s, which equal
+ * parameters guarantee): a failing check leaves every lane's
  * previous results intact.  n = 1 is answer.
  * The shared pass runs on the matrix cores (csrc/sweep_mfma.hip, the base path's kernel with 2-row records) from the LIMBS form of the trial
  * images, where that form exists (spiral_gpu_pack_has_limb_form): at least 16 ciphertexts per slot (nu2 >= 4) and a first dimension that is a power
@@ -598,7 +610,8 @@ int spiral_gpu_pack_server_answer_batch_wire(spiral_gpu_pack_server *const *serv
  * servers, each holding all out_n^2 trial images of its own database.  n_clients <= 8 clients -- servers[q]: an owner and its lanes (create_lane), as in
  * answer_batch, each with its own public parameters -- send one query each, and every client gets one packed response per instance: slot
  * q * n_instances + k is what answer on a server sweeping instance k's images would return for client q's public parameters and query.  Per call: the
- * expansion and conversion once per client (not per instance); per instance ONE first-dimension pass over its images for all clients (the
+ * expansion and conversion once per client (not per instance; from option "pack_batch_lanes" clients on, all clients' in one lane-aware launch
+ * sequence, as answer_batch's); per instance ONE first-dimension pass over its images for all clients (the
  * matrix-core pass of answer_batch where the geometry has limb planes: with two or more clients each instance image is converted in place on first
  * use); then per client and group of G instances ONE folding, packing, switch and wire-form sequence whose launches carry the whole group.  Option
  * "pack_item_group" sets G (0: automatic -- the largest G whose arenas fit a quarter of the free device memory; an allocation that fails halves G,

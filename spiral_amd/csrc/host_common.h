@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +21,7 @@ namespace spiral {
 namespace host {
 
 extern thread_local std::string g_err;
+extern std::atomic<uint64_t> g_pack_lane_batches;  // server.cpp: what get_option("pack_lane_batches") reads
 
 inline int fail(const char* fmt, ...) {
     char buf[512];

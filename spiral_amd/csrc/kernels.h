@@ -30,6 +30,8 @@ struct Options {
     size_t db_stage_bytes = (size_t)64 << 20;
     int one_image = 1;  // a server that batches on the matrix cores keeps ONLY the limb-plane image of its database (server.cpp)
     uint32_t pack_item_group = 0;  // pack answer_batch_instances: instances per group, 0 = automatic (pack_server.cpp)
+    uint32_t pack_batch_lanes = 0;  // SpiralPack batch calls of at least this many clients run as ONE lane-aware launch sequence, 0 = never: the default,
+                                    // until the lane form is measured against the per-lane form
 };
 Options& options();  // server.cpp; the three documented environment variables are read once, on first use
 
@@ -270,13 +272,20 @@ void launch_seed_rows(const uint8_t* seed, uint32_t domain, uint64_t k0, uint64_
 
 // ---- pointwise polynomial kernels (poly.hip) -------------------------------------------------------
 // out[b][r][c] = sum_m A[r][m] * B[b][m][c]  (+ addend), all PK; generic MatPoly multiply (src/poly.cpp:34)
-struct MatmulParams {
+struct MatmulParamsCore {
     const uint64_t* a;  // [rs][ms] polys, stride a_batch polys between batches (0 = shared)
     const uint64_t* b;  // [ms][cs] polys
     uint64_t* out;      // [rs][cs] polys
     uint32_t rs, ms, cs;
     uint32_t a_batch, b_batch, out_batch;  // strides in polynomials
 };
+template <class L>
+struct MatmulParamsT : MatmulParamsCore {
+    using Core = MatmulParamsCore;
+    using NoLanesT = MatmulParamsT<NoLanes>;
+    L lanes;  // a, b, out per query lane (the SpiralPack conversion of a batch: each client's V and digits)
+};
+using MatmulParams = MatmulParamsT<Lanes>;
 void launch_matmul(const MatmulParams& p, uint32_t batch, hipStream_t s);
 // fold product: out[i][3][2] = key[3][K] * d[i][K][2], K = 2*m2 (src/spiral.cpp:1361-1383)
 // key_stride: polynomials between the key's rows (K when the rows are K long; 2*m2 with K = m2 to take one half of [Q_neg | Q]);
@@ -470,25 +479,26 @@ __device__ __forceinline__ void db1_put_word(uint64_t* db, uint32_t z, uint32_t 
 void launch_sweep1(const uint64_t* db, const uint32_t* qs1, uint64_t* acc, uint32_t num_per, uint32_t dim0, uint32_t trials, size_t db_stride,
                    size_t acc_stride, hipStream_t s);
 // query records from the expanded cts: first-dimension ct j is cv[j * idx_factor] (reorientCiphertextsDim1, :342)
-void launch_qs1_from_cv(const uint64_t* cv, uint32_t* qs1, uint32_t dim0, uint32_t idx_factor, hipStream_t s);
+// (lanes, here and below: gridDim.z = the clients of a batch, every pointer lane 0's -- kernels.h Lanes; qs1 is shifted by the same bytes)
+void launch_qs1_from_cv(const uint64_t* cv, uint32_t* qs1, uint32_t dim0, uint32_t idx_factor, hipStream_t s, const Lanes& lanes = Lanes{});
 void launch_qs1_from_reoriented(const uint64_t* re, uint32_t* qs1, uint32_t dim0, hipStream_t s);
 // convertDb layout (:316-340) z*(num_per*dim0) + ii*dim0 + j -> device layout
 // foldCiphertextsDim1 product for `count` ciphertexts: out[b][2] = key[2][K] * d[b][K]   (src/testing.cpp:596-624)
 // key_stride: polynomials between the key's two rows (0 = K); addend (pair form: out = L + F * D'): PK ciphertexts, ciphertext b = t * np + i at
-// polynomial (t * add_stride + i) * 2 + r of `addend`
+// polynomial (t * add_stride + i) * 2 + r of `addend`.  lanes: `count` ciphertexts per lane, each lane with its own key
 void launch_pack_fold_mac(const uint64_t* key, const uint64_t* d, uint64_t* out, uint32_t K, uint32_t count, hipStream_t s, uint32_t key_stride = 0,
-                          const uint64_t* addend = nullptr, uint32_t np = 1, uint32_t add_stride = 1);
+                          const uint64_t* addend = nullptr, uint32_t np = 1, uint32_t add_stride = 1, const Lanes& lanes = Lanes{});
 void launch_db1_relayout(const uint64_t* ref, uint64_t* dev, uint32_t num_per, uint32_t dim0, hipStream_t s);
 // gsw[i][r][2j] = tmp[i*ell+j][r], gsw[i][r][2j+1] = cv[2*(i*ell+j)+1][r]   (regevToSimpleGsw, :108-139)
-void launch_pack_gsw_assemble(const uint64_t* tmp, const uint64_t* cv, uint64_t* gsw, uint32_t ell, uint32_t nu2, hipStream_t s);
-void launch_pack_gsw_from_upload(const uint64_t* query, uint64_t* gsw, uint32_t dim0, uint32_t ell, uint32_t nu2, hipStream_t s);
+void launch_pack_gsw_assemble(const uint64_t* tmp, const uint64_t* cv, uint64_t* gsw, uint32_t ell, uint32_t nu2, hipStream_t s, const Lanes& lanes = Lanes{});
+void launch_pack_gsw_from_upload(const uint64_t* query, uint64_t* gsw, uint32_t dim0, uint32_t ell, uint32_t nu2, hipStream_t s, const Lanes& lanes = Lanes{});
 // key[cur][r][0..2ell) = gadget - F, [2ell..4ell) = F with F = gsw[nu2-1-cur]   (:1027-1032, 611-618)
-void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2, hipStream_t s);
+void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2, hipStream_t s, const Lanes& lanes = Lanes{});
 // pack (:198-241): result[row][c] = sum_r sum_k W_r[row][k] * ginv[r*out_n+c][k] + (row >= 1 ? ct2[(row-1)*out_n+c] : 0)
 // n_inst > 1: n_inst such products in one launch (an item group of answer_batch_instances), instance k's ginv / ct2 / result k x (out_n^2 t_conv,
-// out_n^2, (out_n + 1) out_n) polynomials further on, the same v_w
+// out_n^2, (out_n + 1) out_n) polynomials further on, the same v_w.  lanes (n_inst = 1 only): one response per client, each with its own v_w
 void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s,
-                     uint32_t n_inst = 1);
+                     uint32_t n_inst = 1, const Lanes& lanes = Lanes{});
 // the first-dimension sweep of n = 1 .. kMaxLanes queries (records qs1[b] -> accumulators acc[b], launch_sweep1's layouts) on the matrix cores, in ONE
 // pass over `trials` trial images (db_stride / acc_stride u64 words apart) in limb-plane form (sweep_mfma.hip, ROWS = 2).  Coverage (sweep1_mfma_ok):
 // num_per 16, 32, 64 (the narrow form: a workgroup's waves take blocks of different trials) or a power of two >= 128, dim0 a power of two in

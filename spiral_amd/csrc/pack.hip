@@ -2,6 +2,9 @@
 // ciphertexts against 1 x 1 plaintexts.  The first-dimension sweep is again the HBM-bound kernel: 4 integer MADs
 // per 8-byte database word.  Several queries against one image share a pass on the matrix cores instead
 // (sweep_mfma.hip, ROWS = 2), from the limb-plane form of the image.
+#include <cstdio>
+#include <cstdlib>
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 
@@ -170,14 +173,37 @@ void launch_sweep1(const uint64_t* db, const uint32_t* qs1, uint64_t* acc, uint3
     }
 }
 
-__global__ __launch_bounds__(kTpb) void qs1_from_cv_kernel(const uint64_t* cv, uint32_t* qs, uint32_t dim0, uint32_t idx_factor) {
+// The kernels below take the clients of a batch as query lanes (kernels.h Lanes): gridDim.z = lanes.n, every pointer is lane 0's and is shifted by
+// the lane's arena offset (pack_server.cpp pk_layout: one arena per server, the same layout in each).  One client: the NoLanes instantiations.
+struct Qs1ParamsCore {
+    const uint64_t* cv;
+    uint32_t* qs;  // (u32 records in the u64-word arena: shifted by the same bytes)
+    uint32_t dim0, idx_factor;
+};
+template <class L>
+struct Qs1ParamsT : Qs1ParamsCore {
+    using Core = Qs1ParamsCore;
+    using NoLanesT = Qs1ParamsT<NoLanes>;
+    L lanes;
+};
+template <class L>
+__global__ __launch_bounds__(kTpb) void qs1_from_cv_kernel(Qs1ParamsT<L> p) {
+    {
+        const int64_t lane = p.lanes.here();
+        lane_shift(p.cv, lane);
+        lane_shift(p.qs, lane);
+    }
     const uint32_t z = blockIdx.x * kTpb + threadIdx.x, j = blockIdx.y;
-    const uint64_t* c = cv + (size_t)j * idx_factor * 2 * kN + z;
+    const uint64_t* c = p.cv + (size_t)j * p.idx_factor * 2 * kN + z;
     const uint64_t r0 = c[0], r1 = c[kN];
-    reinterpret_cast<uint4*>(qs)[(size_t)z * dim0 + j] = make_uint4(lo32(r0), lo32(r1), hi32(r0), hi32(r1));
+    reinterpret_cast<uint4*>(p.qs)[(size_t)z * p.dim0 + j] = make_uint4(lo32(r0), lo32(r1), hi32(r0), hi32(r1));
 }
-void launch_qs1_from_cv(const uint64_t* cv, uint32_t* qs1, uint32_t dim0, uint32_t idx_factor, hipStream_t s) {
-    hipLaunchKernelGGL(qs1_from_cv_kernel, dim3(kBpp, dim0), dim3(kTpb), 0, s, cv, qs1, dim0, idx_factor);
+void launch_qs1_from_cv(const uint64_t* cv, uint32_t* qs1, uint32_t dim0, uint32_t idx_factor, hipStream_t s, const Lanes& lanes) {
+    const Qs1ParamsT<Lanes> p{{cv, qs1, dim0, idx_factor}, lanes};
+    if (lanes.n > 1)
+        hipLaunchKernelGGL(qs1_from_cv_kernel<Lanes>, dim3(kBpp, dim0, lanes.n), dim3(kTpb), 0, s, p);
+    else
+        hipLaunchKernelGGL(qs1_from_cv_kernel<NoLanes>, dim3(kBpp, dim0), dim3(kTpb), 0, s, no_lanes(p));
 }
 // reference layout (z, j, m = 0, r): z*(dim0*2) + j*2 + r
 __global__ __launch_bounds__(256) void qs1_from_reoriented_kernel(const uint64_t* re, uint32_t* qs, uint32_t dim0) {
@@ -206,33 +232,99 @@ void launch_db1_relayout(const uint64_t* ref, uint64_t* dev, uint32_t num_per, u
     hipLaunchKernelGGL(db1_relayout_kernel, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, s, ref, dev, num_per, dim0);
 }
 
-__global__ __launch_bounds__(kTpb) void pack_gsw_assemble_kernel(const uint64_t* tmp, const uint64_t* cv, uint64_t* gsw, uint32_t ell) {
-    const uint32_t z = blockIdx.x * kTpb + threadIdx.x, ij = blockIdx.y, i = ij / ell, j = ij - i * ell, cols = 2 * ell;
+struct PackGswAssembleParamsCore {
+    const uint64_t* tmp;  // V * chat
+    const uint64_t* cv;   // the expanded cts
+    uint64_t* gsw;
+    uint32_t ell;
+};
+template <class L>
+struct PackGswAssembleParamsT : PackGswAssembleParamsCore {
+    using Core = PackGswAssembleParamsCore;
+    using NoLanesT = PackGswAssembleParamsT<NoLanes>;
+    L lanes;
+};
+template <class L>
+__global__ __launch_bounds__(kTpb) void pack_gsw_assemble_kernel(PackGswAssembleParamsT<L> p) {
+    {
+        const int64_t lane = p.lanes.here();
+        lane_shift(p.tmp, lane);
+        lane_shift(p.cv, lane);
+        lane_shift(p.gsw, lane);
+    }
+    const uint32_t ell = p.ell, z = blockIdx.x * kTpb + threadIdx.x, ij = blockIdx.y, i = ij / ell, j = ij - i * ell, cols = 2 * ell;
 #pragma unroll
     for (uint32_t r = 0; r < 2; r++) {
-        uint64_t* g = gsw + ((size_t)(i * 2 + r) * cols) * kN + z;
-        g[(size_t)(2 * j) * kN] = tmp[((size_t)ij * 2 + r) * kN + z];
-        g[(size_t)(2 * j + 1) * kN] = cv[((size_t)(2 * ij + 1) * 2 + r) * kN + z];
+        uint64_t* g = p.gsw + ((size_t)(i * 2 + r) * cols) * kN + z;
+        g[(size_t)(2 * j) * kN] = p.tmp[((size_t)ij * 2 + r) * kN + z];
+        g[(size_t)(2 * j + 1) * kN] = p.cv[((size_t)(2 * ij + 1) * 2 + r) * kN + z];
     }
 }
-void launch_pack_gsw_assemble(const uint64_t* tmp, const uint64_t* cv, uint64_t* gsw, uint32_t ell, uint32_t nu2, hipStream_t s) {
-    hipLaunchKernelGGL(pack_gsw_assemble_kernel, dim3(kBpp, nu2 * ell), dim3(kTpb), 0, s, tmp, cv, gsw, ell);
+void launch_pack_gsw_assemble(const uint64_t* tmp, const uint64_t* cv, uint64_t* gsw, uint32_t ell, uint32_t nu2, hipStream_t s, const Lanes& lanes) {
+    const PackGswAssembleParamsT<Lanes> p{{tmp, cv, gsw, ell}, lanes};
+    if (lanes.n > 1)
+        hipLaunchKernelGGL(pack_gsw_assemble_kernel<Lanes>, dim3(kBpp, nu2 * ell, lanes.n), dim3(kTpb), 0, s, p);
+    else
+        hipLaunchKernelGGL(pack_gsw_assemble_kernel<NoLanes>, dim3(kBpp, nu2 * ell), dim3(kTpb), 0, s, no_lanes(p));
 }
 
 // direct upload (src/testing.cpp:966-989): gsw[i][r][col] = uploaded ct (dim0 + i*2ell + col), row r
-__global__ __launch_bounds__(kTpb) void pack_gsw_from_upload_kernel(const uint64_t* query, uint64_t* gsw, uint32_t dim0, uint32_t ell) {
-    const uint32_t z = blockIdx.x * kTpb + threadIdx.x, cols = 2 * ell, ic = blockIdx.y, i = ic / cols, col = ic - i * cols;
+struct PackGswUploadParamsCore {
+    const uint64_t* query;  // the uploaded cts
+    uint64_t* gsw;
+    uint32_t dim0, ell;
+};
+template <class L>
+struct PackGswUploadParamsT : PackGswUploadParamsCore {
+    using Core = PackGswUploadParamsCore;
+    using NoLanesT = PackGswUploadParamsT<NoLanes>;
+    L lanes;
+};
+template <class L>
+__global__ __launch_bounds__(kTpb) void pack_gsw_from_upload_kernel(PackGswUploadParamsT<L> p) {
+    {
+        const int64_t lane = p.lanes.here();
+        lane_shift(p.query, lane);
+        lane_shift(p.gsw, lane);
+    }
+    const uint32_t z = blockIdx.x * kTpb + threadIdx.x, cols = 2 * p.ell, ic = blockIdx.y, i = ic / cols, col = ic - i * cols;
 #pragma unroll
-    for (uint32_t r = 0; r < 2; r++) gsw[((size_t)(i * 2 + r) * cols + col) * kN + z] = query[((size_t)(dim0 + ic) * 2 + r) * kN + z];
+    for (uint32_t r = 0; r < 2; r++) p.gsw[((size_t)(i * 2 + r) * cols + col) * kN + z] = p.query[((size_t)(p.dim0 + ic) * 2 + r) * kN + z];
 }
-void launch_pack_gsw_from_upload(const uint64_t* query, uint64_t* gsw, uint32_t dim0, uint32_t ell, uint32_t nu2, hipStream_t s) {
-    hipLaunchKernelGGL(pack_gsw_from_upload_kernel, dim3(kBpp, nu2 * 2 * ell), dim3(kTpb), 0, s, query, gsw, dim0, ell);
+void launch_pack_gsw_from_upload(const uint64_t* query, uint64_t* gsw, uint32_t dim0, uint32_t ell, uint32_t nu2, hipStream_t s, const Lanes& lanes) {
+    const PackGswUploadParamsT<Lanes> p{{query, gsw, dim0, ell}, lanes};
+    if (lanes.n > 1)
+        hipLaunchKernelGGL(pack_gsw_from_upload_kernel<Lanes>, dim3(kBpp, nu2 * 2 * ell, lanes.n), dim3(kTpb), 0, s, p);
+    else
+        hipLaunchKernelGGL(pack_gsw_from_upload_kernel<NoLanes>, dim3(kBpp, nu2 * 2 * ell), dim3(kTpb), 0, s, no_lanes(p));
 }
 
-// folding_neg = gadget + NTT(Q - INTT(F)) = gadget - F slot-wise; gadget[r][col] = 2^(bits * col/2) when col % 2 == r
-__global__ __launch_bounds__(kTpb) void pack_fold_key_kernel(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2) {
-    const uint32_t z = blockIdx.x * kTpb + threadIdx.x, cols = 2 * ell, rc = blockIdx.y, r = rc / cols, col = rc - r * cols, cur = blockIdx.z;
-    const uint64_t f = gsw[((size_t)((nu2 - 1 - cur) * 2 + r) * cols + col) * kN + z];
+// folding_neg = gadget + NTT(Q - INTT(F)) = gadget - F slot-wise; gadget[r][col] = 2^(bits * col/2) when col % 2 == r.
+// NoLanes: blockIdx.z = the round cur; Lanes: blockIdx.z = the client, and blockIdx.y = cur * 4 ell + (r, col)
+struct PackFoldKeyParamsCore {
+    const uint64_t* gsw;
+    uint64_t* key;
+    uint32_t ell, nu2;
+};
+template <class L>
+struct PackFoldKeyParamsT : PackFoldKeyParamsCore {
+    using Core = PackFoldKeyParamsCore;
+    using NoLanesT = PackFoldKeyParamsT<NoLanes>;
+    L lanes;
+};
+template <class L>
+__global__ __launch_bounds__(kTpb) void pack_fold_key_kernel(PackFoldKeyParamsT<L> p) {
+    const uint32_t ell = p.ell, nu2 = p.nu2, z = blockIdx.x * kTpb + threadIdx.x, cols = 2 * ell;
+    uint32_t rc = blockIdx.y, cur = blockIdx.z;
+    if constexpr (!std::is_same<L, NoLanes>::value) {
+        const int64_t lane = p.lanes.here();
+        lane_shift(p.gsw, lane);
+        lane_shift(p.key, lane);
+        cur = blockIdx.y / (2 * cols);
+        rc = blockIdx.y - cur * (2 * cols);
+    }
+    const uint32_t r = rc / cols, col = rc - r * cols;
+    const uint64_t f = p.gsw[((size_t)((nu2 - 1 - cur) * 2 + r) * cols + col) * kN + z];
     uint32_t gp = 0, gb = 0;
     if ((col & 1u) == r) {
         const uint32_t sh = get_bits_per(ell) * (col >> 1);
@@ -241,25 +333,50 @@ __global__ __launch_bounds__(kTpb) void pack_fold_key_kernel(const uint64_t* gsw
             gb = mod_b(1ull << sh);
         }
     }
-    uint64_t* k = key + ((size_t)(cur * 2 + r) * 2 * cols) * kN + z;
+    uint64_t* k = p.key + ((size_t)(cur * 2 + r) * 2 * cols) * kN + z;
     k[(size_t)col * kN] = pack(csub(gp + kP - lo32(f), kP), csub(gb + kB - hi32(f), kB));
     k[(size_t)(cols + col) * kN] = f;
 }
-void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2, hipStream_t s) {
-    hipLaunchKernelGGL(pack_fold_key_kernel, dim3(kBpp, 4 * ell, nu2), dim3(kTpb), 0, s, gsw, key, ell, nu2);
+void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint32_t nu2, hipStream_t s, const Lanes& lanes) {
+    const PackFoldKeyParamsT<Lanes> p{{gsw, key, ell, nu2}, lanes};
+    if (lanes.n > 1)
+        hipLaunchKernelGGL(pack_fold_key_kernel<Lanes>, dim3(kBpp, 4 * ell * nu2, lanes.n), dim3(kTpb), 0, s, p);
+    else
+        hipLaunchKernelGGL(pack_fold_key_kernel<NoLanes>, dim3(kBpp, 4 * ell, nu2), dim3(kTpb), 0, s, no_lanes(p));
 }
 
 // ITEMS: gridDim.z = the instances of one client's item group (answer_batch_instances), instance k's digits, ct2 and result k x their per-instance
-// size further on; the key matrices v_w are the client's, shared.  !ITEMS is the one-response launch.
-template <bool ITEMS>
-__global__ __launch_bounds__(kTpb) void pack_mac_kernel(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n,
-                                                        uint32_t t_conv) {
+// size further on; the key matrices v_w are the client's, shared.  !ITEMS is the one-response launch, and the only one that takes query lanes
+// (gridDim.z = the clients of a batch, each with its own v_w): blockIdx.z never means both.
+struct PackMacParamsCore {
+    const uint64_t* v_w;
+    const uint64_t* ginv;
+    const uint64_t* ct2;
+    uint64_t* result;
+    uint32_t out_n, t_conv;
+};
+template <class L>
+struct PackMacParamsT : PackMacParamsCore {
+    using Core = PackMacParamsCore;
+    using NoLanesT = PackMacParamsT<NoLanes>;
+    L lanes;
+};
+template <bool ITEMS, class L>
+__global__ __launch_bounds__(kTpb) void pack_mac_kernel(PackMacParamsT<L> p) {
+    static_assert(!ITEMS || std::is_same<L, NoLanes>::value, "an item group takes no query lanes");
+    const uint32_t out_n = p.out_n, t_conv = p.t_conv;
     const uint32_t z = blockIdx.x * kTpb + threadIdx.x, rc = blockIdx.y, row = rc / out_n, c = rc - row * out_n, rows = out_n + 1;
     if constexpr (ITEMS) {
         const size_t k = blockIdx.z, trials = (size_t)out_n * out_n;
-        ginv += k * trials * t_conv * kN;
-        ct2 += k * trials * kN;
-        result += k * rows * out_n * kN;
+        p.ginv += k * trials * t_conv * kN;
+        p.ct2 += k * trials * kN;
+        p.result += k * rows * out_n * kN;
+    } else {
+        const int64_t lane = p.lanes.here();
+        lane_shift(p.v_w, lane);
+        lane_shift(p.ginv, lane);
+        lane_shift(p.ct2, lane);
+        lane_shift(p.result, lane);
     }
     // the reference multiplies per r (t_conv <= 56 terms, one reduction, src/poly.cpp:62) and adds the out_n products mod m
     // (src/testing.cpp:225-238); a u64 holds 256 terms of < 2^56, so the sum over r is reduced whenever the next r's terms
@@ -267,8 +384,8 @@ __global__ __launch_bounds__(kTpb) void pack_mac_kernel(const uint64_t* v_w, con
     uint64_t lo = 0, hi = 0;
     uint32_t terms = 0;
     for (uint32_t r = 0; r < out_n; r++) {
-        const uint64_t* w = v_w + (((size_t)r * rows + row) * t_conv) * kN + z;
-        const uint64_t* g = ginv + ((size_t)(r * out_n + c) * t_conv) * kN + z;
+        const uint64_t* w = p.v_w + (((size_t)r * rows + row) * t_conv) * kN + z;
+        const uint64_t* g = p.ginv + ((size_t)(r * out_n + c) * t_conv) * kN + z;
         if (terms + t_conv > 255u) {  // the reduced value counts as one term
             lo = mod_p(lo);
             hi = mod_b(hi);
@@ -283,18 +400,25 @@ __global__ __launch_bounds__(kTpb) void pack_mac_kernel(const uint64_t* v_w, con
     }
     uint32_t rp = mod_p(lo), rb = mod_b(hi);
     if (row >= 1) {
-        const uint64_t x = ct2[(size_t)((row - 1) * out_n + c) * kN + z];
+        const uint64_t x = p.ct2[(size_t)((row - 1) * out_n + c) * kN + z];
         rp = csub(rp + lo32(x), kP);
         rb = csub(rb + hi32(x), kB);
     }
-    result[(size_t)rc * kN + z] = pack(rp, rb);
+    p.result[(size_t)rc * kN + z] = pack(rp, rb);
 }
 void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s,
-                     uint32_t n_inst) {
+                     uint32_t n_inst, const Lanes& lanes) {
+    const PackMacParamsT<Lanes> p{{v_w, ginv, ct2, result, out_n, t_conv}, lanes};
+    if (n_inst > 1 && lanes.n > 1) {
+        fprintf(stderr, "launch_pack_mac: an item group takes no query lanes\n");
+        abort();
+    }
     if (n_inst > 1)
-        hipLaunchKernelGGL(pack_mac_kernel<true>, dim3(kBpp, (out_n + 1) * out_n, n_inst), dim3(kTpb), 0, s, v_w, ginv, ct2, result, out_n, t_conv);
+        hipLaunchKernelGGL((pack_mac_kernel<true, NoLanes>), dim3(kBpp, (out_n + 1) * out_n, n_inst), dim3(kTpb), 0, s, no_lanes(p));
+    else if (lanes.n > 1)
+        hipLaunchKernelGGL((pack_mac_kernel<false, Lanes>), dim3(kBpp, (out_n + 1) * out_n, lanes.n), dim3(kTpb), 0, s, p);
     else
-        hipLaunchKernelGGL(pack_mac_kernel<false>, dim3(kBpp, (out_n + 1) * out_n), dim3(kTpb), 0, s, v_w, ginv, ct2, result, out_n, t_conv);
+        hipLaunchKernelGGL((pack_mac_kernel<false, NoLanes>), dim3(kBpp, (out_n + 1) * out_n), dim3(kTpb), 0, s, no_lanes(p));
 }
 
 // ---- foldCiphertextsDim1 product (src/testing.cpp:596-624): out[b][r] = sum_m key[r][m] * d[b][m], r < 2, m < K = 4*ell.
@@ -307,9 +431,11 @@ struct PackAcc {
         hi += (uint64_t)hi32(a) * hi32(b);
     }
 };
+// The kernel keeps its operands as __restrict__ kernel arguments and takes the lanes as one more argument (as rescale2_kernel does), not in a
+// parameter struct: a struct's pointers lose the arguments' noalias, which cost the one-client instantiations 3 and 5 SGPRs.
 template <uint32_t B>
-__global__ __launch_bounds__(kTpb) void pack_fold_mac_kernel(const uint64_t* __restrict__ key, const uint64_t* __restrict__ d, uint64_t* __restrict__ out,
-                                                             uint32_t K, uint32_t ks, const uint64_t* __restrict__ add, uint32_t np, uint32_t add_stride) {
+__device__ __forceinline__ void pack_fold_mac_body(const uint64_t* __restrict__ key, const uint64_t* __restrict__ d, uint64_t* __restrict__ out, uint32_t K,
+                                                   uint32_t ks, const uint64_t* __restrict__ add, uint32_t np, uint32_t add_stride) {
     __shared__ uint64_t sh[3][64][4 * B];
     const uint32_t zz = threadIdx.x & 63u, kg = threadIdx.x >> 6, z = blockIdx.x * 64u + zz, b0 = blockIdx.y * B;
     const uint64_t* dp = d + (size_t)b0 * K * kN + z;
@@ -362,14 +488,31 @@ __global__ __launch_bounds__(kTpb) void pack_fold_mac_kernel(const uint64_t* __r
             }
     }
 }
+template <uint32_t B, class L>
+__global__ __launch_bounds__(kTpb) void pack_fold_mac_kernel(const uint64_t* __restrict__ key, const uint64_t* __restrict__ d, uint64_t* __restrict__ out,
+                                                             uint32_t K, uint32_t ks, const uint64_t* __restrict__ add, uint32_t np, uint32_t add_stride, L lanes) {
+    const int64_t lane = lanes.here();
+    const uint64_t *key_l = key, *d_l = d, *add_l = add;
+    uint64_t* out_l = out;
+    lane_shift(key_l, lane);
+    lane_shift(d_l, lane);
+    lane_shift(out_l, lane);
+    lane_shift(add_l, lane);
+    pack_fold_mac_body<B>(key_l, d_l, out_l, K, ks, add_l, np, add_stride);
+}
 void launch_pack_fold_mac(const uint64_t* key, const uint64_t* d, uint64_t* out, uint32_t K, uint32_t count, hipStream_t s, uint32_t key_stride,
-                          const uint64_t* addend, uint32_t np, uint32_t add_stride) {
+                          const uint64_t* addend, uint32_t np, uint32_t add_stride, const Lanes& lanes) {
     if (count == 0) return;
     const uint32_t ks = key_stride ? key_stride : K;
-    if (count % 4 == 0 && count >= 64)
-        hipLaunchKernelGGL(pack_fold_mac_kernel<4>, dim3(kN / 64, count / 4), dim3(kTpb), 0, s, key, d, out, K, ks, addend, np, add_stride);
-    else
-        hipLaunchKernelGGL(pack_fold_mac_kernel<1>, dim3(kN / 64, count), dim3(kTpb), 0, s, key, d, out, K, ks, addend, np, add_stride);
+    const bool four = count % 4 == 0 && count >= 64;  // per lane: the lanes of a batch fold the same rounds
+    const dim3 grid(kN / 64, four ? count / 4 : count, lanes.n);
+    if (lanes.n > 1) {
+        if (four) hipLaunchKernelGGL((pack_fold_mac_kernel<4, Lanes>), grid, dim3(kTpb), 0, s, key, d, out, K, ks, addend, np, add_stride, lanes);
+        else hipLaunchKernelGGL((pack_fold_mac_kernel<1, Lanes>), grid, dim3(kTpb), 0, s, key, d, out, K, ks, addend, np, add_stride, lanes);
+    } else {
+        if (four) hipLaunchKernelGGL((pack_fold_mac_kernel<4, NoLanes>), grid, dim3(kTpb), 0, s, key, d, out, K, ks, addend, np, add_stride, NoLanes{});
+        else hipLaunchKernelGGL((pack_fold_mac_kernel<1, NoLanes>), grid, dim3(kTpb), 0, s, key, d, out, K, ks, addend, np, add_stride, NoLanes{});
+    }
 }
 
 // arbitrary valid words (benchmarks)

@@ -25,6 +25,8 @@ struct spiral_gpu_pack_server {
     DeviceTables tb;
     bool have_pp = false;
     bool packed_after_front = false;  // event 6 belongs to the same answer as events 0..5
+    bool events_elsewhere = false;    // the last call that answered this server's query recorded its stages on ANOTHER server's events (a lane-form
+                                      // batch or item call, as lane 1 .. n - 1): events 0..6 are an older call's, or were never recorded
     uint32_t n_cv = 0;
     // every buffer below but the lazy ones (stage, wire_in, item) is a piece of `arena`, carved in one fixed order (pk_layout): servers with equal
     // parameters, out_n and trial range have equal layouts
@@ -33,7 +35,8 @@ struct spiral_gpu_pack_server {
     PkBufs own{};  // what one answer writes
     DevBuf stage;
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
-    hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch / item call end, [8] ordering another call's stream in front of an item call
+    hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch sweep / item call end, [8] ordering this server's stream in front of and behind a
+                            // batch or item call that runs on another server's
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
     // the trial images this server sweeps (db_image.h): its own, or its owner's, of which a query lane (create_lane) holds a reference and
     // which it never writes
@@ -175,8 +178,9 @@ size_t pack_message_bytes(const spiral_gpu_params* p, uint32_t out_n, MessageLay
 
 // pack (src/testing.cpp:198-241) on device buffers: raw cts at trial stride `ct_stride` polynomials
 // n_inst > 1: an item group, n_inst instances' trials one after another in raw_cts, ginv, ct2 and result (answer_batch_instances)
+// lanes (n_inst = 1): the clients of a batch, every pointer lane 0's
 void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_stride_cts, const uint64_t* v_w, uint64_t* ginv, uint64_t* ct2, uint64_t* result,
-              uint32_t out_n, uint32_t t_conv, hipStream_t st, uint32_t n_inst = 1) {
+              uint32_t out_n, uint32_t t_conv, hipStream_t st, uint32_t n_inst = 1, const Lanes& lanes = Lanes{}) {
     const uint32_t trials = n_inst * out_n * out_n;
     FwdParams fp{};
     fp.src = raw_cts;
@@ -186,6 +190,7 @@ void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_strid
     fp.bits = get_bits_per(t_conv);
     fp.pmode = PM_PACK;
     fp.pk_num_per = ct_stride_cts;
+    fp.lanes = lanes;
     launch_ntt_forward(tb, fp, LD_PDIGIT, ST_PK, trials * t_conv, st);
     FwdParams fa{};
     fa.src = raw_cts;
@@ -193,30 +198,50 @@ void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_strid
     fa.src_map = IndexMap{1, 2 * ct_stride_cts, 1};
     fa.dst_map = identity_map();
     fa.n_digits = 1;
+    fa.lanes = lanes;
     launch_ntt_forward(tb, fa, LD_RAW, ST_PK, trials, st);
-    launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st, n_inst);
+    launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st, n_inst, lanes);
 }
 
-// the first-dimension sweep of n servers' queries (their records) over every trial image of H into accs[b], on `st`: one pass on the matrix cores when
-// the image is in limb-plane form, else one sweep1 launch (all trials) per server
-int pk_sweep_into(const DbImage* H, spiral_gpu_pack_server* const* servers, uint64_t* const* accs, uint32_t n, hipStream_t st) {
+// The clients of one call as query lanes (kernels.h Lanes): lane b's arena offset from servers[0]'s, in u64 words -- of either sign, the caller chooses
+// which server comes first.  pk_check_lanes has established equal parameters, out_n and trial range, hence equal layouts (pk_layout); the arenas' sizes
+// and last pieces are compared all the same, because a launch with a wrong offset writes outside its client's memory.
+int pk_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, Lanes* lanes) {
+    const spiral_gpu_pack_server* S = servers[0];
+    *lanes = Lanes{};
+    lanes->n = n;
+    for (uint32_t b = 0; b < n; b++) {
+        const spiral_gpu_pack_server* L = servers[b];
+        if (L->arena.words != S->arena.words || L->own.wire - L->w_left.p != S->own.wire - S->w_left.p || L->w_left.p != L->arena.p)
+            return fail("server %u's buffers are not laid out as server 0's", b);
+        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
+    }
+    return 0;
+}
+
+// the first-dimension sweep of n queries (their records qs[b]) over every trial image of H into accs[b], on `st`: one pass on the matrix cores when
+// the image is in limb-plane form, else one sweep1 launch (all trials) per query
+int pk_sweep_into(const DbImage* H, const uint32_t* const* qs, uint64_t* const* accs, uint32_t n, hipStream_t st) {
     const DbLayout& s = H->lay;
     const size_t acc_stride = (size_t)s.num_per * 2 * kN;
     if (H->format == SPIRAL_GPU_DB_LIMBS) {
-        const uint32_t* qs[kMaxLanes];
-        uint64_t* acc[kMaxLanes];
-        for (uint32_t b = 0; b < n; b++) qs[b] = (const uint32_t*)servers[b]->qs1.p, acc[b] = accs[b];
-        const hipError_t e = launch_sweep1_mfma(H->db.p, qs, acc, n, s.num_per, s.dim0, s.trials, s.trial_words, acc_stride, st);
+        const hipError_t e = launch_sweep1_mfma(H->db.p, qs, accs, n, s.num_per, s.dim0, s.trials, s.trial_words, acc_stride, st);
         return e == hipSuccess ? 0 : fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
     }
-    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, (const uint32_t*)servers[b]->qs1.p, accs[b], s.num_per, s.dim0, s.trials, s.trial_words, acc_stride, st);
+    for (uint32_t b = 0; b < n; b++) launch_sweep1(H->db.p, qs[b], accs[b], s.num_per, s.dim0, s.trials, s.trial_words, acc_stride, st);
     return 0;
 }
-// ... over servers[0]'s images, into each server's own accumulators
-int pk_sweep(spiral_gpu_pack_server* const* servers, uint32_t n, hipStream_t st) {
+// lane b's records of S's query lanes (S = lane 0)
+void pk_lane_records(const spiral_gpu_pack_server* S, const Lanes& lanes, const uint32_t** qs) {
+    for (uint32_t b = 0; b < lanes.n; b++) qs[b] = (const uint32_t*)(S->qs1.p + lanes.off[b]);
+}
+// piece 2 of an answer: ... over S's images, into each lane's own accumulators
+int pk_sweep(spiral_gpu_pack_server* S, const Lanes& lanes, hipStream_t st) {
+    const uint32_t* qs[kMaxLanes];
     uint64_t* acc[kMaxLanes];
-    for (uint32_t b = 0; b < n; b++) acc[b] = servers[b]->own.acc;
-    return pk_sweep_into(servers[0]->img, servers, acc, n, st);
+    pk_lane_records(S, lanes, qs);
+    for (uint32_t b = 0; b < lanes.n; b++) acc[b] = S->own.acc + lanes.off[b];
+    return pk_sweep_into(S->img, qs, acc, lanes.n, st);
 }
 
 }  // namespace
@@ -472,21 +497,26 @@ size_t spiral_gpu_pack_pub_params_seeded_bytes(const spiral_gpu_params* p, uint3
 
 // The answer up to and including the folding, for this server's trials, in three pieces (pk_front; answer_batch puts one shared sweep between the
 // lanes' first and last pieces): the folded ciphertexts end up at the head of each trial's num_per slots of S->raw (events 0..5 bracket the stages).
+// Every piece takes the query lanes of its launches (kernels.h Lanes): S is lane 0, whose buffers the launches name and whose events bracket the stages,
+// and lane b works in its own arena lanes.off[b] words further on.  Lanes{} is one client: the launches of a single answer, nothing else.
 // Piece 1: expansion and conversion of the query in S->query (pk_take_query) -> the sweep's records qs1 and the folding keys, on `st`
-static int pk_expand_convert(spiral_gpu_pack_server* S, hipStream_t st) {
+static int pk_expand_convert(spiral_gpu_pack_server* S, const Lanes& lanes, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
     const uint32_t ell = s.ell, ngs = p.nu2 * ell;
     HIP_OK(hipEventRecord(S->ev[0], st));
+    S->events_elsewhere = false;
     // ---- coefficientExpansion + reorientCiphertextsDim1 (src/testing.cpp:1009-1020)
     if (!p.direct_upload) {
         ExpandWork wk{S->ex_raw.p, S->ex_g.p};
         run_expand(S->tb, S->cv.p, s.g, p.t_exp, S->w_left.p, p.t_exp_right, S->w_right.p, ell * p.nu2, s.stopround, wk, st,
-                   s.g ? S->query.p : nullptr);
-        if (s.g == 0) HIP_OK(hipMemcpyAsync(S->cv.p, S->query.p, 2 * kPolyBytes, hipMemcpyDeviceToDevice, st));
-        launch_qs1_from_cv(S->cv.p, (uint32_t*)S->qs1.p, s.dim0, 2, st);
+                   s.g ? S->query.p : nullptr, 0, 0xffffffffu, ExpandShard{}, 3, lanes);
+        if (s.g == 0)
+            for (uint32_t b = 0; b < lanes.n; b++)
+                HIP_OK(hipMemcpyAsync(S->cv.p + lanes.off[b], S->query.p + lanes.off[b], 2 * kPolyBytes, hipMemcpyDeviceToDevice, st));
+        launch_qs1_from_cv(S->cv.p, (uint32_t*)S->qs1.p, s.dim0, 2, st, lanes);
     } else {
-        launch_qs1_from_cv(S->query.p, (uint32_t*)S->qs1.p, s.dim0, 1, st);
+        launch_qs1_from_cv(S->query.p, (uint32_t*)S->qs1.p, s.dim0, 1, st, lanes);
     }
     HIP_OK(hipEventRecord(S->ev[1], st));
     // ---- regevToSimpleGsw + the negated GSW ciphertexts (:1022-1033)
@@ -496,6 +526,7 @@ static int pk_expand_convert(spiral_gpu_pack_server* S, hipStream_t st) {
         ip.dst = S->gs_raw.p;
         ip.src_map = IndexMap{2, 4, 2};  // both rows of ct 2*ij + 1
         ip.dst_map = identity_map();
+        ip.lanes = lanes;
         launch_ntt_inverse(S->tb, ip, IST_CRT, 2 * ngs, st);
         FwdParams fp{};
         fp.src = S->gs_raw.p;
@@ -504,22 +535,23 @@ static int pk_expand_convert(spiral_gpu_pack_server* S, hipStream_t st) {
         fp.n_digits = p.t_conv;
         fp.bits = get_bits_per(p.t_conv);
         fp.pmode = PM_GSW;
+        fp.lanes = lanes;
         launch_ntt_forward(S->tb, fp, LD_PDIGIT, ST_PK, 2 * ngs * p.t_conv, st);
-        MatmulParams mp{S->v.p, S->gs_chat.p, S->gs_tmp.p, 2, 2 * p.t_conv, 1, 0, 2 * p.t_conv, 2};
+        MatmulParams mp{{S->v.p, S->gs_chat.p, S->gs_tmp.p, 2, 2 * p.t_conv, 1, 0, 2 * p.t_conv, 2}, lanes};
         launch_matmul(mp, ngs, st);
-        launch_pack_gsw_assemble(S->gs_tmp.p, S->cv.p, S->gsw.p, ell, p.nu2, st);
+        launch_pack_gsw_assemble(S->gs_tmp.p, S->cv.p, S->gsw.p, ell, p.nu2, st, lanes);
     } else {
-        launch_pack_gsw_from_upload(S->query.p, S->gsw.p, s.dim0, ell, p.nu2, st);
+        launch_pack_gsw_from_upload(S->query.p, S->gsw.p, s.dim0, ell, p.nu2, st, lanes);
     }
-    launch_pack_fold_key(S->gsw.p, S->key.p, ell, p.nu2, st);
+    launch_pack_fold_key(S->gsw.p, S->key.p, ell, p.nu2, st, lanes);
     HIP_OK(hipEventRecord(S->ev[2], st));
     S->have_records = true;
     return 0;
 }
 
 // piece 3 (piece 2 is pk_sweep: the first dimension for every trial, :1049-1051): one INTT + CRT lift (:1055-1057) and the folding, on `st`, of nt
-// trials in the buffers B (pk_fold: S's own trials in its own buffers)
-static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt, hipStream_t st) {
+// trials in the buffers B (pk_fold: S's own trials in its own buffers).  With lanes B must be S's own: a piece of the arena the offsets are taken from.
+static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt, const Lanes& lanes, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_pack_shape& s = S->s;
     const uint32_t ell = s.ell;
@@ -544,6 +576,7 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
             ip.dst = B.raw;  // [t][2 np][2], compact
             ip.src_map = IndexMap{4 * np, 2 * src_stride, 0};
             ip.dst_map = identity_map();
+            ip.lanes = lanes;
             launch_ntt_inverse(S->tb, ip, IST_CRT, nt * 4 * np, st);
             FwdParams fp{};
             fp.src = B.raw;
@@ -553,8 +586,9 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
             fp.bits = get_bits_per(ell);
             fp.fold_np = np;
             fp.lazy_out = lazy_ok(2 * ell + 1) ? 1 : 0;  // pack_fold_mac sums 2 ell products and the addend per accumulator
+            fp.lanes = lanes;
             launch_ntt_forward(S->tb, fp, LD_PDIFF, ST_PK, nt * np * 2 * ell, st);
-            launch_pack_fold_mac(S->key.p + ((size_t)cur * 2 * 4 * ell + 2 * ell) * kN, B.fold_d, out, 2 * ell, nt * np, st, 4 * ell, src, np, src_stride);
+            launch_pack_fold_mac(S->key.p + ((size_t)cur * 2 * 4 * ell + 2 * ell) * kN, B.fold_d, out, 2 * ell, nt * np, st, 4 * ell, src, np, src_stride, lanes);
             src = out;
             src_stride = np;
             continue;
@@ -569,10 +603,11 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
         cp.src_stride = src_stride;
         const uint32_t n_src = nt * 2 * np * 2;
         uint32_t dpb = ell;
-        while (dpb > 1 && n_src * ((ell + dpb - 1) / dpb) < 768u) dpb = (dpb + 1) / 2;
+        while (dpb > 1 && n_src * lanes.n * ((ell + dpb - 1) / dpb) < 768u) dpb = (dpb + 1) / 2;  // (the workgroups of all lanes)
         cp.dpb = dpb;
+        cp.lanes = lanes;
         launch_fold_chain(S->tb, cp, n_src, st);
-        launch_pack_fold_mac(S->key.p + (size_t)cur * 2 * 4 * ell * kN, B.fold_d, out, 4 * ell, nt * np, st);
+        launch_pack_fold_mac(S->key.p + (size_t)cur * 2 * 4 * ell * kN, B.fold_d, out, 4 * ell, nt * np, st, 0, nullptr, 1, 1, lanes);
         src = out;
         src_stride = np;
     }
@@ -582,6 +617,7 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
         ip.dst = B.raw;
         ip.src_map = p.nu2 ? identity_map() : IndexMap{2 * s.num_per, 2 * s.num_per, 0};
         ip.dst_map = IndexMap{2 * np, 2 * s.num_per, 0};  // the trial's surviving np cts at the head of its num_per slots
+        ip.lanes = lanes;
         launch_ntt_inverse(S->tb, ip, IST_CRT, nt * np * 2, st);
     }
     HIP_OK(hipEventRecord(S->ev[5], st));
@@ -589,27 +625,33 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
     return 0;
 }
 
-static int pk_fold(spiral_gpu_pack_server* S, hipStream_t st) { return pk_fold_into(S, S->own, S->nt, st); }
+static int pk_fold(spiral_gpu_pack_server* S, const Lanes& lanes, hipStream_t st) { return pk_fold_into(S, S->own, S->nt, lanes, st); }
 
 static int pk_front(spiral_gpu_pack_server* S) {
-    spiral_gpu_pack_server* one[1] = {S};
-    if (pk_expand_convert(S, S->stream) || pk_sweep(one, 1, S->stream)) return -1;
-    return pk_fold(S, S->stream);
+    const Lanes one{};
+    if (pk_expand_convert(S, one, S->stream) || pk_sweep(S, one, S->stream)) return -1;
+    return pk_fold(S, one, S->stream);
 }
 
-// pack + modulus switch (:1064-1081) of out_n^2 folded ciphertexts at a stride of `ct_stride` ciphertexts; event 6 closes it
-static int pk_back(spiral_gpu_pack_server* S, const uint64_t* folded, uint32_t ct_stride, hipStream_t st) {
+// pack + modulus switch (:1064-1081) of out_n^2 folded ciphertexts at a stride of `ct_stride` ciphertexts; event 6 closes it.  With lanes `folded` is
+// S's own raw buffer, and the switch is one launch_rescale2 for all of them (row 0 to q', the rest to 4p: the same words as the two launches of one client)
+static int pk_back(spiral_gpu_pack_server* S, const uint64_t* folded, uint32_t ct_stride, const Lanes& lanes, hipStream_t st) {
     const spiral_gpu_params& p = S->p;
     const PkBufs& B = S->own;
     const uint32_t rows = S->out_n + 1;
-    run_pack(S->tb, folded, ct_stride, S->v_w.p, B.ginv, B.ct2, B.res, S->out_n, p.t_conv, st);
+    run_pack(S->tb, folded, ct_stride, S->v_w.p, B.ginv, B.ct2, B.res, S->out_n, p.t_conv, st, 1, lanes);
     InvParams ip{};
     ip.src = B.res;
     ip.dst = B.pk_raw;
     ip.src_map = ip.dst_map = identity_map();
+    ip.lanes = lanes;
     launch_ntt_inverse(S->tb, ip, IST_CRT, rows * S->out_n, st);
-    launch_rescale(B.pk_raw, B.resp, S->out_n * kN, kQ, S->s.qprime, st);
-    launch_rescale(B.pk_raw + (size_t)S->out_n * kN, B.resp + (size_t)S->out_n * kN, S->out_n * S->out_n * kN, kQ, 4 * p.p_db, st);
+    if (lanes.n > 1) {
+        launch_rescale2(B.pk_raw, B.resp, S->out_n * kN, rows * S->out_n * kN, kQ, S->s.qprime, 4 * p.p_db, st, lanes);
+    } else {
+        launch_rescale(B.pk_raw, B.resp, S->out_n * kN, kQ, S->s.qprime, st);
+        launch_rescale(B.pk_raw + (size_t)S->out_n * kN, B.resp + (size_t)S->out_n * kN, S->out_n * S->out_n * kN, kQ, 4 * p.p_db, st);
+    }
     HIP_OK(hipEventRecord(S->ev[6], st));
     S->packed_after_front = folded == B.raw;  // (a gathered buffer was filled by other servers too: no common time line)
     return 0;
@@ -637,7 +679,7 @@ static int pk_check_answer(spiral_gpu_pack_server* S) {
 
 // the answer to the query in S->query
 static int pk_answer_taken(spiral_gpu_pack_server* S, uint64_t* response, uint64_t* packed_ct, double stage_us[8]) {
-    if (pk_front(S) || pk_back(S, S->own.raw, S->s.num_per, S->stream) || pk_download(S, response, packed_ct)) return -1;
+    if (pk_front(S) || pk_back(S, S->own.raw, S->s.num_per, Lanes{}, S->stream) || pk_download(S, response, packed_ct)) return -1;
     return stage_us ? spiral_gpu_pack_server_stage_us(S, stage_us) : 0;
 }
 
@@ -702,44 +744,95 @@ static int pk_take_queries(spiral_gpu_pack_server* const* servers, uint32_t n, F
     return 0;
 }
 
-// Beyond the reference (one query per call): n <= kMaxLanes queries, one per server, in one launch sequence on servers[0]'s stream -- expansion and
-// conversion per lane, ONE first-dimension pass over the trial images for all of them (matrix cores, once the image is in limb-plane form: the first
-// batch on a covered geometry converts it), then folding, packing and the modulus switch per lane.  Returns synchronised.
+// what lanes 1 .. n - 1 of a call on servers[0]'s stream still have on streams of their own comes before it (the way lanes_join / lanes_release of
+// server.cpp do it; a lane on servers[0]'s stream is ordered by it) ...
+static int pk_lanes_join(spiral_gpu_pack_server* const* servers, uint32_t n) {
+    spiral_gpu_pack_server* S = servers[0];
+    for (uint32_t b = 1; b < n; b++) {
+        if (servers[b]->stream == S->stream) continue;
+        HIP_OK(hipEventRecord(servers[b]->ev[8], servers[b]->stream));
+        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev[8], 0));
+    }
+    return 0;
+}
+// ... and what follows on their streams comes after it (event 8 of servers[0], which no join records: servers[0] is never joined to itself)
+static int pk_lanes_release(spiral_gpu_pack_server* const* servers, uint32_t n) {
+    spiral_gpu_pack_server* S = servers[0];
+    bool other = false;
+    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
+    if (other) HIP_OK(hipEventRecord(S->ev[8], S->stream));
+    for (uint32_t b = 1; b < n; b++)
+        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev[8], 0));
+    return 0;
+}
+// whether a call of n clients runs as one lane-aware launch sequence (option pack_batch_lanes, read per call; 0 = never)
+static bool pk_lane_form(uint32_t n) { return n >= 2 && options().pack_batch_lanes != 0 && n >= options().pack_batch_lanes; }
+
+// Beyond the reference (one query per call): n <= kMaxLanes queries, one per server, in one launch sequence on servers[0]'s stream, with ONE
+// first-dimension pass over the trial images for all of them (matrix cores, once the image is in limb-plane form: the first batch on a covered geometry
+// converts it).  From option pack_batch_lanes clients on (the lane form) every other launch carries all n clients too, in gridDim.z: one expansion and
+// conversion, the pass, one folding, one packing and switch; below it those run per lane, one client after another.  Either way every lane's buffers and
+// flags end up as its own answer would leave them.  Returns synchronised.
 static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, Form form, const void* const* queries, size_t bytes_each,
                            uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8], const char* what) {
     if (pk_check_lanes(servers, n, false, what) || pk_take_queries(servers, n, form, queries, bytes_each, what)) return -1;
     if (n == 1) return pk_answer_taken(servers[0], responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
     spiral_gpu_pack_server* S = servers[0];
     HIP_OK(hipSetDevice(S->device));
+    Lanes lanes;
+    if (pk_lanes(servers, n, &lanes)) return -1;
     if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     hipStream_t st = S->stream;
-    for (uint32_t b = 0; b < n; b++)
-        if (pk_expand_convert(servers[b], st)) return -1;
-    if (pk_sweep(servers, n, st)) return -1;
-    HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at servers[n - 1]'s event 2)
-    for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_pack_server* L = servers[b];
-        if (pk_fold(L, st) || pk_back(L, L->own.raw, L->s.num_per, st)) return -1;
+    const bool lane_form = pk_lane_form(n);
+    if (lane_form) {
+        if (pk_lanes_join(servers, n)) return -1;  // (the queries were taken on the lanes' own streams)
+        if (pk_expand_convert(S, lanes, st) || pk_sweep(S, lanes, st)) return -1;
+        HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at event 2)
+        if (pk_fold(S, lanes, st) || pk_back(S, S->own.raw, S->s.num_per, lanes, st) || pk_lanes_release(servers, n)) return -1;
+        for (uint32_t b = 1; b < n; b++)  // (what the pieces set on servers[0]; the stages' events are servers[0]'s alone)
+            servers[b]->have_records = true, servers[b]->packed_after_front = true, servers[b]->events_elsewhere = true;
+        g_pack_lane_batches++;
+    } else {
+        for (uint32_t b = 0; b < n; b++)
+            if (pk_expand_convert(servers[b], Lanes{}, st)) return -1;
+        if (pk_sweep(S, lanes, st)) return -1;
+        HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at servers[n - 1]'s event 2)
+        for (uint32_t b = 0; b < n; b++) {
+            spiral_gpu_pack_server* L = servers[b];
+            if (pk_fold(L, Lanes{}, st) || pk_back(L, L->own.raw, L->s.num_per, Lanes{}, st)) return -1;
+        }
     }
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     for (uint32_t b = 0; b < n; b++)
         if (pk_download(servers[b], responses ? responses[b] : nullptr, packed_cts ? packed_cts[b] : nullptr)) return -1;
     if (!stage_us) return 0;
-    // the lanes' stages ran one after another on one stream: [0], [1], [3], [4] are the sums over the lanes, [2] = [5] the one shared sweep
     for (int i = 0; i < 8; i++) stage_us[i] = 0;
-    for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_pack_server* L = servers[b];
-        float ms[4] = {};
-        HIP_OK(hipEventElapsedTime(&ms[0], L->ev[0], L->ev[1]));
-        HIP_OK(hipEventElapsedTime(&ms[1], L->ev[1], L->ev[2]));
-        HIP_OK(hipEventElapsedTime(&ms[2], L->ev[4], L->ev[5]));
-        HIP_OK(hipEventElapsedTime(&ms[3], L->ev[5], L->ev[6]));
-        stage_us[0] += ms[0] * 1e3, stage_us[1] += ms[1] * 1e3, stage_us[3] += ms[2] * 1e3, stage_us[4] += ms[3] * 1e3;
-    }
     float sw = 0, total = 0;
-    HIP_OK(hipEventElapsedTime(&sw, servers[n - 1]->ev[2], S->ev[7]));
-    HIP_OK(hipEventElapsedTime(&total, S->ev[0], servers[n - 1]->ev[6]));
+    if (lane_form) {
+        // whole-batch intervals between servers[0]'s events: the lanes' stages ran together, [2] = [5] the one shared sweep
+        float ms[4] = {};
+        HIP_OK(hipEventElapsedTime(&ms[0], S->ev[0], S->ev[1]));
+        HIP_OK(hipEventElapsedTime(&ms[1], S->ev[1], S->ev[2]));
+        HIP_OK(hipEventElapsedTime(&ms[2], S->ev[4], S->ev[5]));
+        HIP_OK(hipEventElapsedTime(&ms[3], S->ev[5], S->ev[6]));
+        stage_us[0] = ms[0] * 1e3, stage_us[1] = ms[1] * 1e3, stage_us[3] = ms[2] * 1e3, stage_us[4] = ms[3] * 1e3;
+        HIP_OK(hipEventElapsedTime(&sw, S->ev[2], S->ev[7]));
+        HIP_OK(hipEventElapsedTime(&total, S->ev[0], S->ev[6]));
+    } else {
+        // the lanes' stages ran one after another on one stream: [0], [1], [3], [4] are the sums over the lanes, [2] = [5] the one shared sweep
+        for (uint32_t b = 0; b < n; b++) {
+            spiral_gpu_pack_server* L = servers[b];
+            float ms[4] = {};
+            HIP_OK(hipEventElapsedTime(&ms[0], L->ev[0], L->ev[1]));
+            HIP_OK(hipEventElapsedTime(&ms[1], L->ev[1], L->ev[2]));
+            HIP_OK(hipEventElapsedTime(&ms[2], L->ev[4], L->ev[5]));
+            HIP_OK(hipEventElapsedTime(&ms[3], L->ev[5], L->ev[6]));
+            stage_us[0] += ms[0] * 1e3, stage_us[1] += ms[1] * 1e3, stage_us[3] += ms[2] * 1e3, stage_us[4] += ms[3] * 1e3;
+        }
+        HIP_OK(hipEventElapsedTime(&sw, servers[n - 1]->ev[2], S->ev[7]));
+        HIP_OK(hipEventElapsedTime(&total, S->ev[0], servers[n - 1]->ev[6]));
+    }
     stage_us[2] = stage_us[5] = sw * 1e3;
     stage_us[6] = total * 1e3;
     stage_us[7] = n;
@@ -871,18 +964,30 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
         if (G > 1) pk_layout(servers[b], a, false, G, bufs[b]);
     }
     const size_t slot_words = bufs[0].slot_words, wire_b = bufs[0].wire_words * 8;
-    for (uint32_t b = 0; b < n; b++)
-        if (pk_expand_convert(servers[b], st)) return -1;  // once per client, whatever the number of instances
+    Lanes lanes;
+    if (pk_lanes(servers, n, &lanes)) return -1;
+    const uint32_t* qs[kMaxLanes];
+    pk_lane_records(S, lanes, qs);
+    // expansion and conversion, once per client whatever the number of instances: one lane-aware sequence from option pack_batch_lanes clients on.  (The
+    // folding and packing below stay per client: an item group's arena is an allocation of its own, outside the arena the lane offsets are taken from.)
+    if (pk_lane_form(n)) {
+        if (pk_expand_convert(S, lanes, st)) return -1;
+        for (uint32_t b = 1; b < n; b++) servers[b]->have_records = true, servers[b]->events_elsewhere = true;
+        g_pack_lane_batches++;
+    } else {
+        for (uint32_t b = 0; b < n; b++)
+            if (pk_expand_convert(servers[b], Lanes{}, st)) return -1;
+    }
     for (uint32_t k0 = 0; k0 < n_inst; k0 += G) {
         const uint32_t g = std::min(G, n_inst - k0);
         for (uint32_t j = 0; j < g; j++) {  // one first-dimension pass per instance for all clients, into instance j's part of each group arena
             uint64_t* acc[kMaxLanes];
             for (uint32_t b = 0; b < n; b++) acc[b] = bufs[b].acc + (size_t)j * bufs[b].acc_words;
-            if (pk_sweep_into(instances[k0 + j]->img, servers, acc, n, st)) return -1;
+            if (pk_sweep_into(instances[k0 + j]->img, qs, acc, n, st)) return -1;
         }
         for (uint32_t b = 0; b < n; b++) {  // folding, packing, switch and wire form: one sequence per client and group
             spiral_gpu_pack_server* L = servers[b];
-            if (pk_fold_into(L, bufs[b], g * L->nt, st) || pk_item_back(L, bufs[b], g, wire != nullptr, st)) return -1;
+            if (pk_fold_into(L, bufs[b], g * L->nt, Lanes{}, st) || pk_item_back(L, bufs[b], g, wire != nullptr, st)) return -1;
             const size_t first = (size_t)b * n_inst + k0;
             if (responses) HIP_OK(hipMemcpyAsync(responses + first * slot_words, bufs[b].resp, g * slot_words * 8, hipMemcpyDeviceToHost, st));
             if (wire) HIP_OK(hipMemcpyAsync((uint8_t*)wire + first * wire_b, bufs[b].wire, g * wire_b, hipMemcpyDeviceToHost, st));
@@ -931,11 +1036,13 @@ int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server* const* serve
     if (pk_check_lanes(servers, n, true, "time_sweep_batch")) return -1;
     spiral_gpu_pack_server* S = servers[0];
     HIP_OK(hipSetDevice(S->device));
+    Lanes lanes;
+    if (pk_lanes(servers, n, &lanes)) return -1;
     if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
-        if (pk_sweep(servers, n, S->stream)) return -1;
+        if (pk_sweep(S, lanes, S->stream)) return -1;
     HIP_OK(hipEventRecord(S->ev[1], S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     float ms = 0;
@@ -950,6 +1057,8 @@ int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server* const* serve
 int spiral_gpu_pack_server_stage_us(spiral_gpu_pack_server* S, double stage_us[8]) {
     if (!S || !stage_us) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
+    if (S->events_elsewhere)
+        return fail("this server's last answer was a lane of a lane-form batch or item call: its stages were timed on that call's servers[0] (the call's stage_us / total_us)");
     HIP_OK(hipStreamSynchronize(S->stream));
     float ms[6] = {}, total = 0;
     for (int i = 0; i < (S->packed_after_front ? 6 : 5); i++) HIP_OK(hipEventElapsedTime(&ms[i], S->ev[i], S->ev[i + 1]));
@@ -984,7 +1093,7 @@ int spiral_gpu_pack_server_pack_gathered(spiral_gpu_pack_server* S, const void* 
     if (!S || !gathered_dev) return fail("null argument");
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_pp) return fail("public parameters must be set first");
-    if (pk_back(S, (const uint64_t*)gathered_dev, 1, S->stream)) return -1;
+    if (pk_back(S, (const uint64_t*)gathered_dev, 1, Lanes{}, S->stream)) return -1;
     return pk_download(S, response, packed_ct);
 }
 

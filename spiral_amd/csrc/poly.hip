@@ -2,6 +2,7 @@
 // One thread per NTT slot / coefficient, 256-thread workgroups, 8 workgroups per polynomial.
 // All NTT-domain outputs are canonical residues in [0, m).
 #include <cstdlib>
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 
@@ -26,9 +27,20 @@ __device__ __forceinline__ uint64_t add_pk(uint64_t a, uint64_t b) {  // canonic
 }
 
 // ---- generic MatPoly multiply (src/poly.cpp:34-78) ---------------------------------------------------
-__global__ __launch_bounds__(kTpb) void matmul_kernel(MatmulParams p) {
+// Lanes: gridDim.z = the clients of a SpiralPack batch (a, b, out per lane) and the batch index moves into blockIdx.y; NoLanes: blockIdx.z = batch
+template <class L>
+__global__ __launch_bounds__(kTpb) void matmul_kernel(MatmulParamsT<L> p) {
     const uint32_t z = blockIdx.x * kTpb + threadIdx.x;
-    const uint32_t rc = blockIdx.y, r = rc / p.cs, c = rc - r * p.cs, bt = blockIdx.z;
+    uint32_t rc = blockIdx.y, bt = blockIdx.z;
+    if constexpr (!std::is_same<L, NoLanes>::value) {
+        const int64_t lane = p.lanes.here();
+        lane_shift(p.a, lane);
+        lane_shift(p.b, lane);
+        lane_shift(p.out, lane);
+        bt = blockIdx.y / (p.rs * p.cs);
+        rc = blockIdx.y - bt * (p.rs * p.cs);
+    }
+    const uint32_t r = rc / p.cs, c = rc - r * p.cs;
     const uint64_t* a = p.a + ((size_t)bt * p.a_batch + (size_t)r * p.ms) * kN + z;
     const uint64_t* b = p.b + ((size_t)bt * p.b_batch + c) * kN + z;
     Acc2 acc;
@@ -37,7 +49,10 @@ __global__ __launch_bounds__(kTpb) void matmul_kernel(MatmulParams p) {
 }
 void launch_matmul(const MatmulParams& p, uint32_t batch, hipStream_t s) {
     if (batch == 0) return;
-    hipLaunchKernelGGL(matmul_kernel, dim3(kBpp, p.rs * p.cs, batch), dim3(kTpb), 0, s, p);
+    if (p.lanes.n > 1)
+        hipLaunchKernelGGL(matmul_kernel<Lanes>, dim3(kBpp, p.rs * p.cs * batch, p.lanes.n), dim3(kTpb), 0, s, p);
+    else
+        hipLaunchKernelGGL(matmul_kernel<NoLanes>, dim3(kBpp, p.rs * p.cs, batch), dim3(kTpb), 0, s, no_lanes(p));
 }
 
 // ---- fold product (cpu_mul_query_by_ct x2 + add, src/spiral.cpp:464-582, 1361-1383) ------------------

@@ -14,6 +14,8 @@ using namespace spiral::host;
 
 // hipGraphs the servers of this process have captured so far (get_option "graph_captures"): shows a replay is not a re-capture
 static std::atomic<uint64_t> g_captures{0};
+// SpiralPack batch calls of this process that ran as one lane-aware launch sequence (get_option "pack_lane_batches"; counted by pack_server.cpp)
+std::atomic<uint64_t> spiral::host::g_pack_lane_batches{0};
 
 // the process-wide options (kernels.h); the three documented environment variables give their initial values, once
 spiral::Options& spiral::options() {
@@ -423,6 +425,7 @@ int spiral_gpu_set_option(const char* name, int64_t value) {
     else if (n == "fwd2_min" && value >= 0) o.fwd2_min = (uint32_t)value;
     else if (n == "db_stage_bytes" && value > 0) o.db_stage_bytes = (size_t)value;
     else if (n == "pack_item_group" && value >= 0 && value <= 0xFFFFFFFFll) o.pack_item_group = (uint32_t)value;
+    else if (n == "pack_batch_lanes" && value >= 0 && value <= (int64_t)kMaxLanes) o.pack_batch_lanes = (uint32_t)value;
     else return fail("unknown option '%s' or value %lld out of range", name, (long long)value);
     return 0;
 }
@@ -439,7 +442,9 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "fwd2_min") *value = o.fwd2_min;
     else if (n == "db_stage_bytes") *value = (int64_t)o.db_stage_bytes;
     else if (n == "pack_item_group") *value = o.pack_item_group;
+    else if (n == "pack_batch_lanes") *value = o.pack_batch_lanes;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
+    else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;
 }
@@ -613,7 +618,7 @@ int spiral_gpu_multiply(uint64_t* out, const uint64_t* a, const uint64_t* b, siz
     uint64_t* db = upload_pk(sc, b, ms * cs);
     uint64_t* dout = sc.get(rs * cs * kN);
     if (!da || !db || !dout) return fail("device allocation/upload failed");
-    MatmulParams mp{da, db, dout, (uint32_t)rs, (uint32_t)ms, (uint32_t)cs, 0, 0, 0};
+    MatmulParams mp{{da, db, dout, (uint32_t)rs, (uint32_t)ms, (uint32_t)cs, 0, 0, 0}, Lanes{}};
     launch_matmul(mp, 1, 0);
     return download_pk(sc, dout, identity_map(), out, rs * cs);
 }

@@ -237,7 +237,10 @@ def _answer_batch(form: str, servers, queries, want_packed: bool):
 
 def answer_batch(servers, queries, want_packed: bool = False):
     """n <= 8 queries, one per server (an owner and its lanes, create_lane), answered with ONE first-dimension pass over the trial images:
-    ([(response, packed or None) per server], stage times of the batch).  Each lane's results equal its own answer's."""
+    ([(response, packed or None) per server], stage times of the batch).  Each lane's results equal its own answer's.  From option
+    "pack_batch_lanes" servers on (set_option; default 0 = never) the batch takes the lane form: expansion, conversion, folding, packing and switch
+    are one launch sequence that carries every client, not one client after another; get_option("pack_lane_batches") counts the calls that did.  The
+    servers may come in any order (servers[0]'s stream runs the batch); in lane form the stage times are whole-batch intervals."""
     return _answer_batch("ntt", servers, queries, want_packed)
 
 

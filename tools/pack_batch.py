@@ -3,9 +3,11 @@ there) or, --geom pack14, at the parameter selector's spiral-pack pick (2^14 x 1
 slot, 33.8 GB: the narrow form of the shared pass): for B = 1, 2, 4, 8 lanes of one owner, the time per answer_batch call, queries/s, and the batched
 first-dimension sweep alone (time_sweep_batch: ms, algorithmic GB/s, fraction of the 8 TB/s HBM peak) -- beside the single-query answer on the packed
 image (the path bench.py --workload pack times) and on the limb-plane image.  Per row the median and the min-to-max spread of the repetitions' device
-times, and the one-time in-place conversion of the image.
+times, and the one-time in-place conversion of the image.  Every row also carries the batch's stage times (median and spread per stage) and the form it
+took: option pack_batch_lanes as the library had it (--lanes sets it; null for a build that has no such option) and whether the batch ran as one
+lane-aware launch sequence (the counter pack_lane_batches moved).
 
-    python tools/pack_batch.py [--geom config5|pack14] [--reps 5] [--sizes 1,2,4,8] [--out profiles/pack_batch.json]
+    python tools/pack_batch.py [--geom config5|pack14] [--reps 5] [--sizes 1,2,4,8] [--lanes N] [--out profiles/pack_batch.json]
 
 Prints one JSON line (and writes it to --out).  Synthetic keys and queries (uniform residues, as bench.py): timing only."""
 import argparse
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--geom", choices=sorted(GEOMS), default="config5")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sizes", default="1,2,4,8")
+    ap.add_argument("--lanes", type=int, default=None, help="option pack_batch_lanes (default: the library's)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import torch
@@ -45,6 +48,15 @@ def main():
     import spiral_amd as sa
 
     P = sys.modules["spiral_amd.pack"]
+
+    def option(name):  # None: a build without the option (SPIRAL_LIB = an earlier build)
+        try:
+            return sa.get_option(name)
+        except sa.SpiralGpuError:
+            return None
+
+    if args.lanes is not None:
+        sa.set_option("pack_batch_lanes", args.lanes)
     sizes = [int(x) for x in args.sizes.split(",")]
     nu1, nu2, out_n, kw, what = GEOMS[args.geom]
     pg = sa.make_params(nu1, nu2, **kw)
@@ -80,10 +92,12 @@ def main():
             convert_ms = (time.perf_counter() - t0) * 1e3
         P.answer_batch(lanes, q)  # warm-up
         stages = []
+        counted = option("pack_lane_batches")
         t0 = time.perf_counter()
         for _ in range(args.reps):
             stages.append(P.answer_batch(lanes, q)[1])
         ms = (time.perf_counter() - t0) * 1e3 / args.reps
+        lane_form = counted is not None and option("pack_lane_batches") - counted == args.reps
         form = "limbs" if owner.db_format() == P.DB_LIMBS else "packed"  # (the form the timed batches ran on)
         if owner.db_format() == P.DB_PACKED and P.has_limb_form(pg, out_n):  # (time_sweep_batch converts a covered image, whatever the lane count)
             t0 = time.perf_counter()
@@ -97,13 +111,17 @@ def main():
                      "device_queries_per_s": round(b / (med(dev) * 1e-6), 1), "sweep_ms": round(sw, 3), "sweep_ms_spread": [round(min(sws), 3), round(max(sws), 3)],
                      "sweep_algorithmic_GBps": round(gbs, 1),
                      "sweep_frac_of_peak": round(gbs / HBM_PEAK_GBPS, 4), "image_form": form, "sweep_image_form": "limbs" if owner.db_format() == P.DB_LIMBS else "packed",
-                     "stages_us": {k: round(float(np.mean([s[k] for s in stages])), 1) for k in stages[0]}})
+                     "stages_us": {k: round(float(np.mean([s[k] for s in stages])), 1) for k in stages[0]},
+                     "stages_us_median": {k: round(med([s[k] for s in stages]), 1) for k in stages[0]},
+                     "stages_us_spread": {k: spread([s[k] for s in stages]) for k in stages[0]},
+                     "pack_batch_lanes": option("pack_batch_lanes"), "lane_form": lane_form})
     # and the single answer again, now on the limb-plane image (the one-query instance of the batched kernel)
     t0 = time.perf_counter()
     st2 = [owner.answer(qs[0], want_packed=False)[2] for _ in range(args.reps)]
     single_limbs_ms = (time.perf_counter() - t0) * 1e3 / args.reps
     dev1, dev2 = [u["total_us"] for u in st], [u["total_us"] for u in st2]
-    out = {"tool": "pack_batch", "config": what, "reps": args.reps, "has_limb_form": P.has_limb_form(pg, out_n),
+    out = {"tool": "pack_batch", "config": what, "reps": args.reps, "library": os.environ.get("SPIRAL_LIB", "product"), "pack_batch_lanes": option("pack_batch_lanes"),
+           "has_limb_form": P.has_limb_form(pg, out_n),
            "sweep_algorithmic_bytes": int(sweep_bytes), "device_db_bytes": owner.db_device_bytes(), "in_place_conversion_ms": convert_ms and round(convert_ms, 1),
            "single_packed_device_us": {"median": round(med(dev1), 1), "spread": spread(dev1), "sweep_us_spread": spread([u["sweep_kernels_us"] for u in st])},
            "single_limbs_device_us": {"median": round(med(dev2), 1), "spread": spread(dev2), "sweep_us_spread": spread([u["sweep_kernels_us"] for u in st2]),
