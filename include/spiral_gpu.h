@@ -79,6 +79,11 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *   "pack_batch_lanes" 0 .. 8 (default 0 = never: opt-in): the smallest number of clients from which spiral_gpu_pack_server_answer_batch and
  *                     ..._answer_batch_instances (and their _wire / _seeded forms) take the lane form -- every launch carries all clients; 0 = never.
  *                     Read per call; same results either way
+ *   "pack_pair_blocks" 0 (default: opt-in) or 1: with 1 a SpiralPack geometry of exactly 8 ciphertexts per slot (nu2 = 3: the small-item sets) has a
+ *                     LIMBS form too, the PAIR form of the shared pass (two adjacent trials per matrix operand).  Read where an image would TAKE that
+ *                     form -- spiral_gpu_pack_has_limb_form, ..._pack_server_set_db_format(LIMBS), the automatic conversion by a batch of two or more
+ *                     clients, time_sweep_batch -- and nowhere else: an image that is in the form is swept, updated, reloaded and converted back
+ *                     whatever the option says now.  Same results either way
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  * These three environment variables are the only ones the library reads. */
@@ -578,14 +583,15 @@ uint64_t spiral_gpu_pack_server_sweep_bytes(spiral_gpu_pack_server *s); /* algor
  * parameters guarantee): a failing check leaves every lane's
  * previous results intact.  n = 1 is answer.
  * The shared pass runs on the matrix cores (csrc/sweep_mfma.hip, the base path's kernel with 2-row records) from the LIMBS form of the trial
- * images, where that form exists (spiral_gpu_pack_has_limb_form): at least 16 ciphertexts per slot (nu2 >= 4) and a first dimension that is a power
- * of two in [128, 4096] (nu1 = 7 .. 12), whatever out_n.  With 16, 32 or 64 ciphertexts per slot -- the large-plaintext sets, many trials of few
- * columns -- a workgroup of the pass takes columns of several trials at once; from 128 up, of one.  The first batch on such a geometry converts the
- * images in place (set_db_format); elsewhere (8 ciphertexts per slot or fewer, a first dimension below 128) the batch sweeps once per lane on the
- * vector ALU -- same results, no shared pass.  A single answer on a LIMBS image sweeps it with the one-query instance of the same kernel
+ * images, where that form exists (spiral_gpu_pack_has_limb_form): at least 16 ciphertexts per slot (nu2 >= 4) -- or exactly 8 (nu2 = 3) with option
+ * "pack_pair_blocks" = 1 -- and a first dimension that is a power of two in [128, 4096] (nu1 = 7 .. 12), whatever out_n.  With 16, 32 or 64
+ * ciphertexts per slot -- the large-plaintext sets, many trials of few columns -- a workgroup of the pass takes columns of several trials at once;
+ * with 8 -- the small-item sets -- every wave of it takes the columns of two adjacent trials (the pair form); from 128 up, of one trial.  The first
+ * batch on such a geometry converts the images in place (set_db_format); elsewhere (8 ciphertexts per slot with the option at 0, 4 or fewer, a first
+ * dimension below 128) the batch sweeps once per lane on the vector ALU -- same results, no shared pass.  A single answer on a LIMBS image sweeps it with the one-query instance of the same kernel
  * (bit-identical).
  * has_limb_form: 1 when a batch on this geometry shares its pass (so collecting clients into a batch pays), 0 when not, -1 (spiral_gpu_last_error)
- * for bad parameters; a pure function of the parameters, no GPU needed.
+ * for bad parameters; a function of the parameters and of ONE option, "pack_pair_blocks" as it is when asked (8 ciphertexts per slot only), no GPU needed.
  * set_db_format / db_format / db_device_bytes: as spiral_gpu_server_set_db_format, for the out_n^2 trial images (on the owner, not a lane; LIMBS
  * fails where has_limb_form is 0; a trial-sharded server converts the images of its own trials; every loader leaves a correct image whatever form
  * it finds; a conversion that fails partway leaves no database loaded).

@@ -26,7 +26,11 @@ struct DbLayout {
     size_t trial_words;
     static DbLayout base(uint32_t num_per, uint32_t dim0_shard) { return {false, num_per, dim0_shard, 1, db_device_words(2 * num_per, dim0_shard)}; }
     static DbLayout packed1(uint32_t num_per, uint32_t dim0, uint32_t trials) { return {true, num_per, dim0, trials, db1_device_words(num_per, dim0)}; }
-    bool mfma_ok() const { return pack ? sweep1_mfma_ok(num_per, dim0) : sweep_mfma_ok(num_per, 2 * dim0); }
+    bool mfma_ok() const { return pack ? sweep1_mfma_ok(num_per, dim0) : sweep_mfma_ok(num_per, 2 * dim0); }  // the kernels can sweep the limb-plane form
+    // whether an image of this layout may TAKE the limb-plane form: at 8 ciphertexts per slot (the pair form) only with option pack_pair_blocks.  Asked
+    // where that is decided -- set_format(LIMBS), a batch's automatic conversion, has_limb_form -- and nowhere else: an image that is in the form is
+    // swept, updated, reloaded and converted back on mfma_ok alone, so switching the option off never strands one
+    bool limbs_ok() const { return mfma_ok() && (!pack || num_per != 8u || options().pack_pair_blocks != 0); }
 };
 
 struct DbImage {
@@ -78,9 +82,9 @@ struct DbImage {
     // load time or the first batch), never inside a capture.
     int set_format(uint32_t fmt, hipStream_t st) {
         if (format == fmt) return 0;
-        if (!lay.mfma_ok())
+        if (fmt == SPIRAL_GPU_DB_LIMBS ? !lay.limbs_ok() : !lay.mfma_ok())
             return fail(lay.pack ? "this geometry has no limb-plane form (needs 16, 32, 64 or a power of two >= 128 ciphertexts per slot and a power-of-two first "
-                                   "dimension in [128, 4096])"
+                                   "dimension in [128, 4096]; 8 ciphertexts per slot with option pack_pair_blocks = 1)"
                                  : "this geometry has no limb-plane form (needs >= 64 ciphertexts per slot and a power-of-two first dimension in [64, 2048])");
         if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever reads or writes the image, on whichever stream
         const size_t per_z = lay.trial_words / kN;

@@ -7,7 +7,8 @@
 // 128-term piece holds the top limbs of terms t and t + 64 (low and high nibble).  With the base path's terms k = 2 j + m that is item j and item
 // j ^ 32 of the same column; with SpiralPack's terms k = j, item j and j ^ 64.  The host groups the updated items into such partner pairs and one
 // thread writes both halves of each nibble byte it owns (keeping the old half when only one of the two items changes): no atomics, and no byte
-// is touched by two threads.
+// is touched by two threads.  A SpiralPack image of 8 columns (the pair form) has 512-byte planes of 32 half-lanes (term block, column): half-lane
+// tb 8 + column, 3584-byte pieces, one column block per slot; the partners are the same.
 #include "common.h"
 #include "kernels.h"
 
@@ -17,11 +18,11 @@ namespace {
 
 constexpr uint32_t kLimbBias = 0x808080u;  // (sweep_mfma.hip)
 
-// residue a mod m in limb form: the three limb bytes go to chunk c of the planes at `b`, the 4-bit top limb is returned
-__device__ __forceinline__ uint32_t put_limbs(uint8_t* b, uint32_t c, uint32_t a, uint32_t m) {
+// residue a mod m in limb form: the three limb bytes go to chunk c of the planes (`plane` bytes each) at `b`, the 4-bit top limb is returned
+__device__ __forceinline__ uint32_t put_limbs(uint8_t* b, uint32_t c, uint32_t a, uint32_t m, uint32_t plane) {
     const uint32_t w = (a >= (1u << 28) - kLimbBias ? a - m : a) + kLimbBias, x = w ^ kLimbBias;
 #pragma unroll
-    for (uint32_t i = 0; i < 3; i++) b[(2u * i + c) * 1024u] = (uint8_t)(x >> (8u * i));
+    for (uint32_t i = 0; i < 3; i++) b[(2u * i + c) * plane] = (uint8_t)(x >> (8u * i));
     return w >> 24;
 }
 
@@ -45,16 +46,17 @@ __global__ __launch_bounds__(256) void db_update_kernel(DbUpdateParams p) {
     const uint32_t kt = p.pack ? e.y : 2u * e.y + m, nk2 = (p.pack ? p.dim0 : 2u * p.dim0) >> 7, t = kt & 127u;  // t < 64: the high partner is t + 64
     const bool has_lo = e.z != kDbUpdateNone, has_hi = e.w != kDbUpdateNone;
     const uint64_t v_lo = has_lo ? p.enc[((size_t)e.z * polys + mc) * kN + z] : 0, v_hi = has_hi ? p.enc[((size_t)e.w * polys + mc) * kN + z] : 0;
-    const uint32_t lane = ((t >> 4) & 3u) * 16u + (col & 15u);
+    const bool c8 = p.pack && p.num_per == 8u;
+    const uint32_t plane = c8 ? 512u : 1024u, nblk = c8 ? 1u : nic >> 4, lane = c8 ? ((t >> 4) & 3u) * 8u + col : ((t >> 4) & 3u) * 16u + (col & 15u);
 #pragma unroll
     for (uint32_t pr = 0; pr < 2; pr++) {
-        const size_t piece = (((size_t)z * (nic >> 4) + (col >> 4)) * 2u + pr) * nk2 + (kt >> 7);  // 7 KiB each
-        uint8_t* b = reinterpret_cast<uint8_t*>(p.limbs) + piece * 7168u + (size_t)lane * 16u + (t & 15u);
+        const size_t piece = (((size_t)z * nblk + (col >> 4)) * 2u + pr) * nk2 + (kt >> 7);  // 7 planes each
+        uint8_t* b = reinterpret_cast<uint8_t*>(p.limbs) + piece * (7u * plane) + (size_t)lane * 16u + (t & 15u);
         const uint32_t mod = pr ? kB : kP;
-        uint32_t nib = b[6u * 1024u];
-        if (has_lo) nib = (nib & 0xF0u) | put_limbs(b, 0, pr ? hi32(v_lo) : lo32(v_lo), mod);
-        if (has_hi) nib = (nib & 0x0Fu) | (put_limbs(b, 1, pr ? hi32(v_hi) : lo32(v_hi), mod) << 4);
-        b[6u * 1024u] = (uint8_t)nib;
+        uint32_t nib = b[6u * plane];
+        if (has_lo) nib = (nib & 0xF0u) | put_limbs(b, 0, pr ? hi32(v_lo) : lo32(v_lo), mod, plane);
+        if (has_hi) nib = (nib & 0x0Fu) | (put_limbs(b, 1, pr ? hi32(v_hi) : lo32(v_hi), mod, plane) << 4);
+        b[6u * plane] = (uint8_t)nib;
     }
 }
 

@@ -32,6 +32,8 @@ struct Options {
     uint32_t pack_item_group = 0;  // pack answer_batch_instances: instances per group, 0 = automatic (pack_server.cpp)
     uint32_t pack_batch_lanes = 0;  // SpiralPack batch calls of at least this many clients run as ONE lane-aware launch sequence, 0 = never: the default,
                                     // until the lane form is measured against the per-lane form
+    int pack_pair_blocks = 0;  // 1: a SpiralPack image of 8 ciphertexts per slot may TAKE the limb-plane form (the pair form of the matrix-core sweep,
+                               // sweep_mfma.hip); read only where that is decided (db_image.h DbLayout::limbs_ok), never by what works on a converted image
 };
 Options& options();  // server.cpp; the three documented environment variables are read once, on first use
 
@@ -501,14 +503,15 @@ void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* 
                      uint32_t n_inst = 1, const Lanes& lanes = Lanes{});
 // the first-dimension sweep of n = 1 .. kMaxLanes queries (records qs1[b] -> accumulators acc[b], launch_sweep1's layouts) on the matrix cores, in ONE
 // pass over `trials` trial images (db_stride / acc_stride u64 words apart) in limb-plane form (sweep_mfma.hip, ROWS = 2).  Coverage (sweep1_mfma_ok):
-// num_per 16, 32, 64 (the narrow form: a workgroup's waves take blocks of different trials) or a power of two >= 128, dim0 a power of two in
-// [128, 4096], any trials >= 1.  Bit-identical to sweep1_kernel per query.  Returns the launch's error.
+// num_per 8 (the pair form: a wave's operand holds two adjacent trials), 16, 32, 64 (the narrow form: a workgroup's waves take blocks of different
+// trials) or a power of two >= 128, dim0 a power of two in [128, 4096], any trials >= 1.  Bit-identical to sweep1_kernel per query.  Returns the launch's
+// error.  (sweep1_mfma_ok says what the kernels can sweep; whether an 8-column image takes the form is option pack_pair_blocks, DbLayout::limbs_ok.)
 bool sweep1_mfma_ok(uint32_t num_per, uint32_t dim0);
 hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* qs1, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t dim0, uint32_t trials,
                               size_t db_stride, size_t acc_stride, hipStream_t s);
 // packed trial image <-> limb planes for nz slots z (pointers at the first of them; a slot's region, db1_device_words / kN words, is the same in both
-// forms): the base path's conversion kernels, with nic = num_per columns and dim0 terms per column.  num_per < 64: a packed tile holds 64 / num_per
-// slots, so both pointers must be at a multiple of that many slots and nz a multiple of it
+// forms): the base path's conversion kernels, with nic = num_per columns and dim0 terms per column (num_per = 8: their 8-column twins, 512-byte planes).
+// num_per < 64: a packed tile holds 64 / num_per slots, so both pointers must be at a multiple of that many slots and nz a multiple of it
 void launch_db1_limb_planes(const uint64_t* packed_img, uint64_t* limbs, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz);
 void launch_db1_limb_unplanes(const uint64_t* limbs, uint64_t* packed_img, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz);
 

@@ -259,7 +259,7 @@ int spiral_gpu_pack_has_limb_form(const spiral_gpu_params* p, uint32_t out_n) {
     spiral_gpu_params q = *p;
     q.direct_upload = 1;  // the image's form does not depend on how the query arrives: no query-size rule here
     if (pack_shape_of(&q, out_n, &s)) return -1;
-    return sweep1_mfma_ok(s.num_per, s.dim0) ? 1 : 0;
+    return DbLayout::packed1(s.num_per, s.dim0, s.trials).limbs_ok() ? 1 : 0;  // (at 8 ciphertexts per slot: option pack_pair_blocks, as read now)
 }
 
 int spiral_gpu_pack(uint64_t* result, uint32_t out_n, uint32_t m_conv, const uint64_t* v_ct, const uint64_t* v_W) {
@@ -781,7 +781,7 @@ static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, F
     HIP_OK(hipSetDevice(S->device));
     Lanes lanes;
     if (pk_lanes(servers, n, &lanes)) return -1;
-    if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+    if (S->img->lay.limbs_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     hipStream_t st = S->stream;
     const bool lane_form = pk_lane_form(n);
     if (lane_form) {
@@ -953,7 +953,7 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
     for (uint32_t k = 0; k < n_inst; k++)
         if (join(instances[k]) || (pk_owner(instances[k]) && join(pk_owner(instances[k])))) return -1;  // (no owner left: nothing writes the image)
     // a batch sweeps each instance image on the matrix cores where the geometry has limb planes: converted in place on first use, as answer_batch's holder
-    if (n >= 2 && sweep1_mfma_ok(S->s.num_per, S->s.dim0))
+    if (n >= 2 && DbLayout::packed1(S->s.num_per, S->s.dim0, S->s.trials).limbs_ok())
         for (uint32_t k = 0; k < n_inst; k++)
             if (instances[k]->img->set_format(SPIRAL_GPU_DB_LIMBS, st)) return -1;
     const uint32_t G = pk_item_group(servers, n, n_inst);
@@ -1038,7 +1038,7 @@ int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server* const* serve
     HIP_OK(hipSetDevice(S->device));
     Lanes lanes;
     if (pk_lanes(servers, n, &lanes)) return -1;
-    if (S->img->lay.mfma_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
+    if (S->img->lay.limbs_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)

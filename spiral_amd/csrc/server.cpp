@@ -426,6 +426,7 @@ int spiral_gpu_set_option(const char* name, int64_t value) {
     else if (n == "db_stage_bytes" && value > 0) o.db_stage_bytes = (size_t)value;
     else if (n == "pack_item_group" && value >= 0 && value <= 0xFFFFFFFFll) o.pack_item_group = (uint32_t)value;
     else if (n == "pack_batch_lanes" && value >= 0 && value <= (int64_t)kMaxLanes) o.pack_batch_lanes = (uint32_t)value;
+    else if (n == "pack_pair_blocks" && (value == 0 || value == 1)) o.pack_pair_blocks = (int)value;
     else return fail("unknown option '%s' or value %lld out of range", name, (long long)value);
     return 0;
 }
@@ -443,6 +444,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "db_stage_bytes") *value = (int64_t)o.db_stage_bytes;
     else if (n == "pack_item_group") *value = o.pack_item_group;
     else if (n == "pack_batch_lanes") *value = o.pack_batch_lanes;
+    else if (n == "pack_pair_blocks") *value = o.pack_pair_blocks;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else return fail("unknown option '%s'", name);

@@ -27,8 +27,10 @@
 // The same kernel (ROWS = 2) is the SpiralPack batch's sweep (pack_server.cpp, answer_batch): 1 x 1 plaintexts and 2-row 16-byte records, K = dim0
 // terms per column, every trial image of the server in one launch.  A SpiralPack query is the same for every trial, so where a trial has fewer than
 // 128 columns (num_per = 16, 32, 64: the large-plaintext sets, few ciphertexts per slot and many trials) the eight waves of a workgroup take 16-column
-// blocks of DIFFERENT trials (the NARROW form below).  Coverage: sweep1_mfma_ok (16, 32, 64 or a power of two >= 128 ciphertexts per slot, dim0 a power
-// of two in [128, 4096], any number of trials); other pack geometries (num_per <= 8, dim0 < 128) sweep once per query on the vector ALU (pack.hip).
+// blocks of DIFFERENT trials (the NARROW form below); at num_per = 8 (the small-item sets, nu2 = 3) a wave's 16 operand rows are the 8 columns of TWO
+// adjacent trials (the PAIR form below; an image takes it only with option pack_pair_blocks).  Coverage: sweep1_mfma_ok (8, 16, 32, 64 or a power of two
+// >= 128 ciphertexts per slot, dim0 a power of two in [128, 4096], any number of trials); other pack geometries (num_per <= 4, dim0 < 128) sweep once per
+// query on the vector ALU (pack.hip).
 // A single query may stay on a converted image: the one-query instance of this kernel sweeps it, bit-identical to sweep1_kernel.
 #include <atomic>
 #include <cstdlib>
@@ -106,6 +108,52 @@ __global__ __launch_bounds__(256) void db_limb_planes_kernel(const uint64_t* __r
     dst[((size_t)nk2 * 7u + 6u) * 64u] = make_uint4(nb[0], nb[1], nb[2], nb[3]);
 }
 
+// The same for nic = 8 columns (the PAIR form's image): one wave per (z, piece of 128 terms), lanes with l & 8 idle (offline: a half-idle wave is fine).
+// The planes are 512 bytes = 32 half-lanes (term block l >> 4, column l & 7) x 16 bytes, a slot's pieces [prime][piece][7 x 512 B]: 56 dim0 bytes per
+// slot as in the packed form, whose tile at 8 columns holds 8 slots -- the same byte range in both forms, so set_format's chunks apply as they stand
+__global__ __launch_bounds__(256) void db_limb_planes8_kernel(const uint64_t* __restrict__ packed, uint4* __restrict__ limbs, uint32_t nic, uint32_t dim0, uint32_t nz) {
+    constexpr uint32_t PL = 32u;  // uint4 per plane
+    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t nk2 = dim0 >> 6, kc2 = wave % nk2, z = wave / nk2;
+    if (z >= nz || (lane & 8u)) return;
+    const uint32_t ic = lane & 7u, kblk = lane >> 4, groups = dim0 >> 3;
+    const uint4* src = reinterpret_cast<const uint4*>(packed) + packed_lane_of(z, ic, nic, groups);
+    uint32_t lp[3][2][4] = {}, lb[3][2][4] = {}, np[4] = {}, nb[4] = {};
+#pragma unroll
+    for (uint32_t c = 0; c < 2; c++) {
+        const uint32_t g = kc2 * 8u + c * 4u + kblk;
+        uint32_t d[28];
+#pragma unroll
+        for (uint32_t k = 0; k < 7; k++) {
+            const uint4 v = src[((size_t)g * 7u + k) * 64u];
+            d[4 * k] = v.x, d[4 * k + 1] = v.y, d[4 * k + 2] = v.z, d[4 * k + 3] = v.w;
+        }
+        uint32_t wp[16], wb[16];
+        limbs_of_group<0>(d, wp, wb);
+#pragma unroll
+        for (uint32_t e = 0; e < 16; e++) {
+            const uint32_t xp = wp[e] ^ kLimbBias, xb = wb[e] ^ kLimbBias, sh = 8u * (e & 3u);
+#pragma unroll
+            for (uint32_t i = 0; i < 3; i++) {
+                lp[i][c][e >> 2] |= ((xp >> (8u * i)) & 0xFFu) << sh;
+                lb[i][c][e >> 2] |= ((xb >> (8u * i)) & 0xFFu) << sh;
+            }
+            np[e >> 2] |= (wp[e] >> 24) << (sh + 4u * c);
+            nb[e >> 2] |= (wb[e] >> 24) << (sh + 4u * c);
+        }
+    }
+    uint4* dst = limbs + ((size_t)z * 2u * nk2 + kc2) * 7u * PL + kblk * 8u + ic;  // prime p; prime b is nk2 pieces further
+#pragma unroll
+    for (uint32_t i = 0; i < 3; i++)
+#pragma unroll
+        for (uint32_t c = 0; c < 2; c++) {
+            dst[(size_t)(2u * i + c) * PL] = make_uint4(lp[i][c][0], lp[i][c][1], lp[i][c][2], lp[i][c][3]);
+            dst[((size_t)nk2 * 7u + 2u * i + c) * PL] = make_uint4(lb[i][c][0], lb[i][c][1], lb[i][c][2], lb[i][c][3]);
+        }
+    dst[(size_t)6u * PL] = make_uint4(np[0], np[1], np[2], np[3]);
+    dst[((size_t)nk2 * 7u + 6u) * PL] = make_uint4(nb[0], nb[1], nb[2], nb[3]);
+}
+
 // limb planes -> packed image: the inverse map, same wave and lane assignment (the two forms are bijective on residues below the moduli, so
 // packed -> limbs -> packed reproduces every byte: tests/test_gpu_parity.py::test_db_format_round_trip)
 template <int T>
@@ -168,6 +216,48 @@ __global__ __launch_bounds__(256) void db_limb_unplanes_kernel(const uint4* __re
         for (uint32_t k = 0; k < 7; k++) dst[((size_t)g * 7u + k) * 64u] = make_uint4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
     }
 }
+// the inverse map at nic = 8
+__global__ __launch_bounds__(256) void db_limb_unplanes8_kernel(const uint4* __restrict__ limbs, uint64_t* __restrict__ packed, uint32_t nic, uint32_t dim0, uint32_t nz) {
+    constexpr uint32_t PL = 32u;
+    const uint32_t lane = threadIdx.x & 63u, wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t nk2 = dim0 >> 6, kc2 = wave % nk2, z = wave / nk2;
+    if (z >= nz || (lane & 8u)) return;
+    const uint32_t ic = lane & 7u, kblk = lane >> 4, groups = dim0 >> 3;
+    const uint4* src = limbs + ((size_t)z * 2u * nk2 + kc2) * 7u * PL + kblk * 8u + ic;
+    uint4* dst = reinterpret_cast<uint4*>(packed) + packed_lane_of(z, ic, nic, groups);
+    const uint4 np4 = src[(size_t)6u * PL], nb4 = src[((size_t)nk2 * 7u + 6u) * PL];
+    const uint32_t np[4] = {np4.x, np4.y, np4.z, np4.w}, nb[4] = {nb4.x, nb4.y, nb4.z, nb4.w};
+#pragma unroll
+    for (uint32_t c = 0; c < 2; c++) {
+        uint32_t lp[3][4], lb[3][4];
+#pragma unroll
+        for (uint32_t i = 0; i < 3; i++) {
+            const uint4 vp = src[(size_t)(2u * i + c) * PL], vb = src[((size_t)nk2 * 7u + 2u * i + c) * PL];
+            lp[i][0] = vp.x, lp[i][1] = vp.y, lp[i][2] = vp.z, lp[i][3] = vp.w;
+            lb[i][0] = vb.x, lb[i][1] = vb.y, lb[i][2] = vb.z, lb[i][3] = vb.w;
+        }
+        uint32_t rp[16], rb[16];
+#pragma unroll
+        for (uint32_t e = 0; e < 16; e++) {
+            const uint32_t sh = 8u * (e & 3u);
+            uint32_t wp = 0, wb = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < 3; i++) {
+                wp |= ((lp[i][e >> 2] >> sh) & 0xFFu) << (8u * i);
+                wb |= ((lb[i][e >> 2] >> sh) & 0xFFu) << (8u * i);
+            }
+            wp = (wp ^ kLimbBias) | (((np[e >> 2] >> (sh + 4u * c)) & 0xFu) << 24);
+            wb = (wb ^ kLimbBias) | (((nb[e >> 2] >> (sh + 4u * c)) & 0xFu) << 24);
+            rp[e] = residue_of_limb_word(wp, kP);
+            rb[e] = residue_of_limb_word(wb, kB);
+        }
+        uint32_t d[28] = {};
+        group_of_limbs<0>(d, rp, rb);
+        const uint32_t g = kc2 * 8u + c * 4u + kblk;
+#pragma unroll
+        for (uint32_t k = 0; k < 7; k++) dst[((size_t)g * 7u + k) * 64u] = make_uint4(d[4 * k], d[4 * k + 1], d[4 * k + 2], d[4 * k + 3]);
+    }
+}
 
 struct SweepLanes {
     const uint32_t* qs[kMaxLanes];
@@ -177,6 +267,8 @@ struct SweepLanes {
 // acc_stride words apart, 2^grp_log column groups per trial.
 // NARROW (num_per < 128): the 16-column blocks of the server are numbered row-major over (trial, block in trial), 2^grp_log blocks per trial and
 // `blocks` = trials << grp_log in all; work items are (group of 8 consecutive blocks, z) and wave wv of a workgroup takes block 8 group + wv
+// PAIR (num_per = 8): `blocks` = trials; the trials are numbered in pair-blocks, ceil(trials / 2) of them, work items are (group of 8 consecutive
+// pair-blocks, z) and wave wv takes pair-block 8 group + wv = trials 2 blk and 2 blk + 1 (grp_log unused)
 struct SweepTrials {
     size_t db_stride, acc_stride;
     uint32_t grp_log, blocks;
@@ -319,7 +411,12 @@ struct RecPlan {
 // NARROW (ROWS = 2, fewer than 128 columns per trial): a workgroup's waves own blocks of different trials (SweepTrials); they still share z, hence the
 // query limbs, the record plan and every barrier.  When `blocks` is not a multiple of 8 the last group is ragged: its surplus waves stream the last
 // block again (clamped, so every load of a trip stays unconditional and the trip straight-line), build their share of the limbs, and store nothing.
-template <int NT, int ROWS, bool GS = false, bool NARROW = false>
+// PAIR (ROWS = 2, num_per = 8): the 16 rows of a wave's A operand are the 8 columns of two adjacent trials, each trial's image [z][prime][piece][7 x 512 B]
+// with 512 B = 32 half-lanes (term block, column) x 16 bytes (db_limb_planes8_kernel).  Lane l (operand column l & 15, term block l >> 4) reads half-lane
+// (l >> 4) 8 + (l & 7) of trial 2 blk + ((l & 15) >> 3): every load instruction is two 512-byte runs, one per trial, and as unconditional as the other
+// forms'.  Ragged ends as NARROW: a surplus wave streams the last pair-block again, the upper half of the last pair-block of an odd number of trials
+// streams the last trial again; both build limbs, meet every barrier and store nothing.
+template <int NT, int ROWS, bool GS = false, bool NARROW = false, bool PAIR = false>
 __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restrict__ dbl, SweepLanes bt, uint32_t nb, uint32_t nic, uint32_t dim0, uint32_t g_log,
                                                             uint32_t ls_log, uint32_t n_work, uint32_t zs_log, SweepTrials tr) {
     extern __shared__ __attribute__((aligned(16))) uint4 bq[];
@@ -331,11 +428,15 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
     const uint32_t per = (n_work + gridDim.x - 1u) / gridDim.x, w0 = min(blockIdx.x * per, n_work), w1 = min(w0 + per, n_work);
     if (w0 == w1) return;
     const uint32_t total = (w1 - w0) << ppi_log;
-    const u32x4* const db0 = reinterpret_cast<const u32x4*>(dbl) + lane;
+    constexpr uint32_t PL = PAIR ? 32u : 64u;  // uint4 per plane
+    const u32x4* const db0 = reinterpret_cast<const u32x4*>(dbl) + (PAIR ? (lane >> 4) * 8u + (lane & 7u) : lane);
     auto piece_ptr = [&](uint32_t g) -> const u32x4* {  // piece g of this workgroup's run (clamped to its last one)
         g = min(g, total - 1u);
         const uint32_t w = w0 + (g >> ppi_log), p = g & (ppi - 1u), z = w & (kN - 1u);
-        if constexpr (NARROW) {
+        if constexpr (PAIR) {
+            const uint32_t blk = min((w >> kLogN) * W + wv, ((tr.blocks + 1u) >> 1) - 1u), trial = min(2u * blk + ((lane >> 3) & 1u), tr.blocks - 1u);
+            return db0 + trial * tr.db_stride + ((((size_t)z) << ppi_log) + p) * (7u * PL);
+        } else if constexpr (NARROW) {
             const uint32_t blk = min((w >> kLogN) * W + wv, tr.blocks - 1u), trial = blk >> tr.grp_log, icb = blk & ((1u << tr.grp_log) - 1u);
             return db0 + trial * tr.db_stride + ((((size_t)z * (nic >> 4) + icb) << ppi_log) + p) * (7u * 64u);
         } else if constexpr (ROWS == 2) {
@@ -356,7 +457,7 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
     {
         const u32x4* src = piece_ptr(0u);
 #pragma unroll
-        for (uint32_t k = 0; k < 7; k++) d[k] = __builtin_nontemporal_load(src + k * 64u);
+        for (uint32_t k = 0; k < 7; k++) d[k] = __builtin_nontemporal_load(src + k * PL);
     }
     rec_issue(0u);
     rec.store(bq);
@@ -409,7 +510,7 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
         {
             const u32x4* src = piece_ptr(g + 1u);  // the next piece, in flight under this one's products
 #pragma unroll
-            for (uint32_t k = 0; k < 7; k++) d[k] = __builtin_nontemporal_load(src + k * 64u);
+            for (uint32_t k = 0; k < 7; k++) d[k] = __builtin_nontemporal_load(src + k * PL);
         }
         const uint32_t p_end = (g + 1u) & (ppi - 1u);
         if (p_end == nk2) {
@@ -428,7 +529,18 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 const uint32_t half_log = zs_log - 1u;  // 2^half_log 16-byte pieces per entry
-                if constexpr (NARROW) {
+                if constexpr (PAIR) {
+                    const uint32_t blk = (w >> kLogN) * W + wv;
+                    const uint32_t n_idx = 2u * blk < tr.blocks ? (NT * 64u) << half_log : 0u;  // a surplus wave of the ragged last group stores nothing
+                    for (uint32_t idx = lane; idx < n_idx; idx += 64u) {
+                        const uint32_t e = idx >> half_log, part = idx & ((1u << half_log) - 1u), t = e >> 6, ls = e & 63u;
+                        const uint32_t icl = (ls >> 4) * 4u + (ls & 3u), trial = 2u * blk + (icl >> 3), ic = icl & 7u;  // operand column -> (trial, column)
+                        const uint32_t qr = t * 4u + ((ls & 15u) >> 2), q = qr >> 1, r = qr & 1u;
+                        const uint4 v = reinterpret_cast<const uint4*>(st)[idx];
+                        if (q < nb && trial < tr.blocks)  // (nor does the upper half of the last pair-block of an odd number of trials)
+                            *reinterpret_cast<uint4*>(pick_lane(bt.acc, q) + trial * tr.acc_stride + ((size_t)(2u * ic + r)) * kN + (z - zi) + 2u * part) = v;
+                    }
+                } else if constexpr (NARROW) {
                     const uint32_t blk = (w >> kLogN) * W + wv, trial = blk >> tr.grp_log, icb = blk & ((1u << tr.grp_log) - 1u);
                     const uint32_t n_idx = blk < tr.blocks ? (NT * 64u) << half_log : 0u;  // a surplus wave of the ragged last group stores nothing
                     for (uint32_t idx = lane; idx < n_idx; idx += 64u) {
@@ -490,7 +602,7 @@ void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, 
 namespace {
 
 // one launch of sweep_mfma_kernel<nt, ROWS> over n_work items (dim0: half the terms per column, as the kernel takes it)
-template <int ROWS, bool GS = false, bool NARROW = false>
+template <int ROWS, bool GS = false, bool NARROW = false, bool PAIR = false>
 hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint32_t nt, uint32_t nic, uint32_t dim0, uint32_t g_log, uint32_t ls_log, uint32_t n_work,
                        const SweepTrials& tr, hipStream_t s) {
     // one workgroup per CU (two per CU with half the staging measured 5 % slower); per = 8 nic / 128 items each (base path)
@@ -511,11 +623,11 @@ hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint3
         static std::atomic<uint64_t> big{0};                                                                                                       \
         const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;                                                                                        \
         if (!(big.load(std::memory_order_relaxed) & bit)) {                                                                                        \
-            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS, NARROW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
+            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS, NARROW, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
             if (e != hipSuccess) return e;                                                                                                         \
             big.fetch_or(bit, std::memory_order_relaxed);                                                                                          \
         }                                                                                                                                          \
-        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS, NARROW>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
+        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS, NARROW, PAIR>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
     } while (0)
     switch (nt) {
         case 1: SWEEP_MFMA(1); break;
@@ -560,15 +672,27 @@ bool sweep1_mfma_ok(uint32_t num_per, uint32_t dim0) {
     // the base rule for nic = num_per columns and K = dim0 terms: num_per >= 128 (whole workgroups of 128 columns, a power of two), dim0 a power of two
     // in [128, 4096] (whole pieces of 128 terms; K <= 2^12 for combine_limbs' 64-bit sums) -- and the packed trial layout (kernels.h) to convert from.
     // num_per = 16, 32, 64 (whole blocks of 16 columns: the NARROW form fills its workgroups across trials), the same rule for dim0.  num_per <= 8 has
-    // no block of 16 columns: a 16-row operand would hold two trials
+    // one trial short of a block of 16 columns: the PAIR form's operand holds two trials (whether an image TAKES this form is option pack_pair_blocks,
+    // db_image.h DbLayout::limbs_ok; an image that is in it is swept, updated and converted back whatever the option says).  num_per <= 4: none
+    if (num_per == 8u) return dim0 >= 128u && dim0 <= 4096u && (dim0 & (dim0 - 1u)) == 0 && db1_packed(num_per, dim0);
     if (num_per >= 16u && num_per < 128u)
         return (num_per & (num_per - 1u)) == 0 && dim0 >= 128u && dim0 <= 4096u && (dim0 & (dim0 - 1u)) == 0 && db1_packed(num_per, dim0);
     return (num_per & 1u) == 0 && sweep_mfma_ok(num_per / 2, dim0) && db1_packed(num_per, dim0);
 }
 void launch_db1_limb_planes(const uint64_t* packed_img, uint64_t* limbs, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz) {
+    if (num_per == 8u) {  // one wave per (z, piece of 128 terms)
+        const size_t waves = (size_t)nz * (dim0 >> 7);
+        if (waves) hipLaunchKernelGGL(db_limb_planes8_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, s, packed_img, reinterpret_cast<uint4*>(limbs), 8u, dim0 / 2u, nz);
+        return;
+    }
     launch_db_limb_planes(packed_img, limbs, num_per / 2, dim0, s, nz);  // (the same image: nic = num_per columns, jm_total = dim0 terms)
 }
 void launch_db1_limb_unplanes(const uint64_t* limbs, uint64_t* packed_img, uint32_t num_per, uint32_t dim0, hipStream_t s, uint32_t nz) {
+    if (num_per == 8u) {
+        const size_t waves = (size_t)nz * (dim0 >> 7);
+        if (waves) hipLaunchKernelGGL(db_limb_unplanes8_kernel, dim3((uint32_t)((waves + 3) / 4)), dim3(256), 0, s, reinterpret_cast<const uint4*>(limbs), packed_img, 8u, dim0 / 2u, nz);
+        return;
+    }
     launch_db_limb_unplanes(limbs, packed_img, num_per / 2, dim0, s, nz);
 }
 hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* qs1, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t dim0, uint32_t trials,
@@ -576,6 +700,12 @@ hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* q
     if (n == 0 || n > kMaxLanes || trials == 0 || !sweep1_mfma_ok(num_per, dim0) || (db_stride & 1u)) return hipErrorInvalidValue;
     const uint32_t nt = (8u * n + 15u) / 16u;
     uint32_t grp_log = 0;
+    if (num_per == 8u) {  // PAIR: groups of 8 pair-blocks of two trials (the last group, and the last pair-block, may be ragged)
+        if (trials > (0xFFFFFFFFu >> kLogN)) return hipErrorInvalidValue;
+        const SweepTrials tr{db_stride / 2u, acc_stride, 0, trials};
+        return launch_mfma<2, false, false, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0,
+                                                  kN * (((trials + 1u) / 2u + 7u) / 8u), tr, s);
+    }
     if (num_per < 128u) {  // NARROW: 2^grp_log blocks of 16 columns per trial, groups of 8 blocks across trials (the last one may be ragged)
         while ((16u << grp_log) < num_per) grp_log++;
         if (trials > (0xFFFFFFFFu >> (grp_log + kLogN))) return hipErrorInvalidValue;

@@ -29,7 +29,8 @@ def get_pack_shape(p: Params, out_n: int) -> PackShape:
 
 def has_limb_form(p: Params, out_n: int) -> bool:
     """whether a batch (answer_batch, answer_batch_instances) on this geometry shares ONE matrix-core pass over the trial images: at least 16
-    ciphertexts per slot and a first dimension that is a power of two in [128, 4096].  A pure function of the parameters: no GPU needed."""
+    ciphertexts per slot -- or exactly 8 while option "pack_pair_blocks" is 1 (set_option; default 0), the pair form -- and a first dimension that is a
+    power of two in [128, 4096].  A function of the parameters and of that one option as it is now: no GPU needed."""
     rc = lib().spiral_gpu_pack_has_limb_form(C.byref(p), out_n)
     if rc < 0:
         check(rc)

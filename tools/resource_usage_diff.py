@@ -1,6 +1,6 @@
 """Condenses two `hipcc -Rpass-analysis=kernel-resource-usage` logs of one source file -- the parent commit's and this tree's -- into one line per kernel:
 `same` / `DIFF` / `GONE` for every kernel of the parent (a `NoLanes` instantiation is matched with the parent's kernel of that name without the
-argument), then the kernels only the tree has.  The logs are the compiler's stderr:
+argument; trailing template flags that are `false` are dropped from both sides), then the kernels only the tree has.  The logs are the compiler's stderr:
 
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c pack.hip -o /dev/null 2> tree_pack.rpass   (in spiral_amd/csrc)
     python tools/resource_usage_diff.py pack.hip parent_pack.rpass tree_pack.rpass [poly.hip parent_poly.rpass tree_poly.rpass ...]
@@ -27,7 +27,8 @@ def parse(path):
     names = subprocess.run(["c++filt"], input="\n".join(out), capture_output=True, text=True).stdout.split("\n")
     res = {}
     for mangled, dem in zip(out, names):
-        dem = re.sub(r"\(.*$", "", dem).replace("void ", "").replace("spiral::", "")
+        dem = re.sub(r"\(.*$", "", dem.replace("(anonymous namespace)::", "")).replace("void ", "").replace("spiral::", "")
+        dem = re.sub(r"(, false)+>$", ">", dem)  # trailing flags at their default: a template that gained one keeps its kernels' names
         res[dem] = " ".join(f"{short}={out[mangled].get(k)}" for k, short in KEYS)
     return res
 
