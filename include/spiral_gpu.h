@@ -484,6 +484,10 @@ int spiral_gpu_server_read(spiral_gpu_server *s, int which, uint64_t *out);
 int spiral_gpu_server_read_response_wire(spiral_gpu_server *s, void *out, size_t capacity);
 /* overwrite the lifted ciphertexts (raw [num_per][n1][n2][N]) -- lets a test drive fold() alone */
 int spiral_gpu_server_write_raw(spiral_gpu_server *s, const uint64_t *raw_cts);
+/* overwrite the accumulators (NTT [num_per][n1][n2][2][N], what read(SPIRAL_GPU_BUF_ACC) returns; residues below 4m as for
+ * ntt_forward) -- lets a test drive lift(), fold() and run_post() on chosen ciphertexts: with acc = to_ntt(raw), raw < Q, the lift gives
+ * raw back exactly */
+int spiral_gpu_server_write_acc(spiral_gpu_server *s, const uint64_t *acc_ref);
 
 /* measurement helper: average duration (ms) of the sweep kernel alone over `iters` launches, timed
  * with HIP events on the server stream */

@@ -2454,6 +2454,14 @@ int spiral_gpu_server_write_raw(spiral_gpu_server* S, const uint64_t* raw_cts) {
     return 0;
 }
 
+// the counterpart for the accumulators: read(SPIRAL_GPU_BUF_ACC)'s layout and index map, in the other direction
+int spiral_gpu_server_write_acc(spiral_gpu_server* S, const uint64_t* acc_ref) {
+    if (!S || !acc_ref) return fail("null argument");
+    HIP_OK(hipSetDevice(S->device));
+    S->raw_from_acc = false;
+    return upload_ref_ntt(S->stage, S->stream, acc_ref, S->acc, (size_t)S->s.num_per * 6);
+}
+
 int spiral_gpu_server_time_sweep(spiral_gpu_server* S, int iters, float* avg_ms) {
     if (!S || !avg_ms || iters <= 0) return fail("bad argument");
     HIP_OK(hipSetDevice(S->device));

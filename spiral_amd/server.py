@@ -382,6 +382,13 @@ class Server:
     def write_raw(self, raw_cts):
         check(lib().spiral_gpu_server_write_raw(self.h, _p(np.ascontiguousarray(raw_cts, dtype=np.uint64))))
 
+    def write_acc(self, acc):
+        """overwrite the accumulators with [num_per][3][2][2][N] NTT-form words, the layout read(BUF_ACC) returns"""
+        acc = np.ascontiguousarray(acc, dtype=np.uint64)
+        if acc.size != self.shape.num_per * 6 * 2 * N:
+            raise ValueError(f"write_acc: {acc.size} words, the accumulators hold {self.shape.num_per * 6 * 2 * N}")
+        check(lib().spiral_gpu_server_write_acc(self.h, _p(acc)))
+
     def time_sweep(self, iters: int = 20) -> float:
         ms = C.c_float()
         check(lib().spiral_gpu_server_time_sweep(self.h, iters, C.byref(ms)))
