@@ -86,6 +86,7 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *                     whatever the option says now.  Same results either way
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
+ *   "key_binds"       (get only) the lanes the bind_keys calls of this process have copied keys into (a lane that held them already is not counted)
  * These three environment variables are the only ones the library reads. */
 int spiral_gpu_set_option(const char *name, int64_t value);
 int spiral_gpu_get_option(const char *name, int64_t *value);
@@ -658,6 +659,51 @@ int spiral_gpu_pack_server_set_db_format(spiral_gpu_pack_server *s, int format);
 int spiral_gpu_pack_server_db_format(spiral_gpu_pack_server *s);
 uint64_t spiral_gpu_pack_server_db_device_bytes(spiral_gpu_pack_server *s);
 int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server *const *servers, uint32_t n, int iters, float *avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
+ * Key store: the public parameters of a population of clients resident on the device, bound to the lanes of a batch
+ * ------------------------------------------------------------------------------------------------
+ * A server answers for the client whose public parameters its four key buffers hold, and set_pub_params* -- an upload, the ingest, a
+ * synchronisation -- is the only other way to change them.  A key store does the ingest ONCE per client: a pool of `capacity` slots on one device, each
+ * holding one client's public parameters already in the device layout, for one parameter set (out_n = 0: the base path's W_exp_left, W_exp_right, W,
+ * V; out_n > 0: SpiralPack's W_exp_left, W_exp_right, V, v_W for that out_n).  bind_keys then makes "lane b serves the client of slot slots[b]" ONE
+ * launch for all lanes of a batch.  Two slot forms, chosen at creation:
+ *   SPIRAL_GPU_KEYS_FULL     every polynomial, the parts back to back: slot_bytes = polynomials of the message x 16 KiB.  Filled from any form.
+ *   SPIRAL_GPU_KEYS_COMPACT  the 32-byte seed of a seeded message, padded to 256 bytes, then rows 1.. of every matrix (what the seeded form sends,
+ *                            transformed), densely: slot_bytes = 256 + (polynomials - row-0 polynomials) x 16 KiB, about half of FULL for the
+ *                            published sets.  Filled from the seeded form only; put and put_wire fail.  Row 0 is regenerated by every bind.
+ * slot_bytes is a pure function of the parameters (no device needed); 0, with last_error set, for parameters get_shape / pack_get_shape refuse or
+ * an unknown form.
+ *
+ * put / put_wire / put_seeded: one client's public parameters into a slot, the arguments of set_pub_params / _wire / _seeded (SpiralPack: of the
+ * pack server's).  They run on the store's own stream and workspace and return synchronised; they first wait for every bind launched from the
+ * store that is still in flight, on whichever streams, so a put never overwrites words a bind still reads.  A put refused for its arguments alone
+ * (slot out of range, a form the store does not take, a null buffer) leaves the slot as it was; one that fails later leaves it EMPTY, never
+ * half-valid.  Every successful put gives the slot a new generation.  drop empties a slot; has returns 1 for a filled slot, else 0.  The caller
+ * owns the slot numbers: there is no eviction.
+ *
+ * bind_keys: servers[0 .. n) are the lanes of a batch -- n in 1 .. 8 distinct servers, an owner and its lanes as run_query_batch / answer_batch take
+ * them (default schedule, no shard), with the store's parameters, out_n and device; slots[b] in range and filled (two lanes may name one slot).
+ * Everything is checked before anything is launched, and a failing call changes nothing.  The launch goes on servers[0]'s stream, behind what the
+ * other lanes' streams hold and in front of what they are given next; nothing is synchronised, and it must not be called during stream capture.
+ * Afterwards each lane's key buffers hold, word for word, what its own set_pub_params* of the slot's message would have left, and the lane counts as
+ * having public parameters.  Buffer addresses do not move: a captured graph replays with the new keys.  A bind is a COPY: a later put to the slot
+ * does not reach a lane bound before it.  Each server remembers (store, slot, generation) of its last bind -- set_pub_params* forgets it -- and a
+ * lane that already holds the slot's present content is left out of the launch; option "key_binds" (get only) counts the lanes actually copied. */
+typedef struct spiral_gpu_key_store spiral_gpu_key_store;
+#define SPIRAL_GPU_KEYS_FULL 0
+#define SPIRAL_GPU_KEYS_COMPACT 1
+int spiral_gpu_key_store_create(const spiral_gpu_params *p, uint32_t out_n, int device, uint32_t capacity, int form, spiral_gpu_key_store **out);
+void spiral_gpu_key_store_destroy(spiral_gpu_key_store *store);
+size_t spiral_gpu_key_store_slot_bytes(const spiral_gpu_params *p, uint32_t out_n, int form);
+int spiral_gpu_key_store_put(spiral_gpu_key_store *store, uint32_t slot, const uint64_t *w_left, const uint64_t *w_right, const uint64_t *w_or_v,
+                             const uint64_t *v_or_vw);
+int spiral_gpu_key_store_put_wire(spiral_gpu_key_store *store, uint32_t slot, const void *wire, size_t bytes);
+int spiral_gpu_key_store_put_seeded(spiral_gpu_key_store *store, uint32_t slot, const void *msg, size_t bytes);
+int spiral_gpu_key_store_drop(spiral_gpu_key_store *store, uint32_t slot);
+int spiral_gpu_key_store_has(spiral_gpu_key_store *store, uint32_t slot);
+int spiral_gpu_server_bind_keys(spiral_gpu_server *const *servers, uint32_t n, spiral_gpu_key_store *store, const uint32_t *slots);
+int spiral_gpu_pack_server_bind_keys(spiral_gpu_pack_server *const *servers, uint32_t n, spiral_gpu_key_store *store, const uint32_t *slots);
 
 #ifdef __cplusplus
 }

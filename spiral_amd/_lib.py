@@ -212,6 +212,16 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_answer_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_answer_batch_seeded": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_answer_batch_instances_seeded": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, U64P, C.c_void_p, C.POINTER(C.c_double)]),
+    "spiral_gpu_key_store_create": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
+    "spiral_gpu_key_store_destroy": (None, [C.c_void_p]),
+    "spiral_gpu_key_store_slot_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32, C.c_int]),
+    "spiral_gpu_key_store_put": (C.c_int, [C.c_void_p, C.c_uint32, U64P, U64P, U64P, U64P]),
+    "spiral_gpu_key_store_put_wire": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_key_store_put_seeded": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_key_store_drop": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "spiral_gpu_key_store_has": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "spiral_gpu_server_bind_keys": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "spiral_gpu_pack_server_bind_keys": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
 }
 
 

@@ -2,7 +2,7 @@
 // 209-265), with the server-answer path running on an MI355X through libspiral_gpu.so.
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
-//            [--wire-input] [--seeded]
+//            [--wire-input] [--seeded] [--key-store [compact]]
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -323,6 +323,7 @@ int main(int argc, char** argv) {
     const uint64_t idx_target = strtoull(argv[3], nullptr, 10);
     bool nonoise = false, random_data = false, show_diff = false, direct_flag = false, high_rate = false;
     uint32_t batch = 0, instances = 0;
+    int key_store = -1;  // --key-store: the slot form of the store the batch's keys are bound from (-1: none)
     // as the reference (random_device, src/core.cpp:202; it labels its own generator NOT SECURE): two words of it.
     // This client is a test harness for the server path, not a hardened client.
     std::random_device rd;
@@ -345,6 +346,14 @@ int main(int argc, char** argv) {
         if (!strcmp(argv[i], "--wire-input")) { cout << "Sending public parameters and queries in their wire form" << endl; g_wire = true; }
         // --seeded (implies --wire-input): the same with every matrix's random row 0 replaced by a seed the client draws from its own generator
         if (!strcmp(argv[i], "--seeded")) { cout << "Sending public parameters and queries in their seeded form" << endl; g_wire = g_seeded = true; }
+        // --batch B --key-store [compact] (not a flag of the reference): the B clients' keys go into a key store (include/spiral_gpu.h) and the batch is
+        // answered twice more with the lanes' keys bound from it, the slot assignment rotated by one lane in between; every client is decoded and
+        // checked in both rounds.  compact: the store keeps each message's seed and rows 1.. only, so the keys travel in the seeded form (implies --seeded)
+        if (!strcmp(argv[i], "--key-store")) {
+            key_store = SPIRAL_GPU_KEYS_FULL;
+            if (i + 1 < argc && !strcmp(argv[i + 1], "compact")) key_store = SPIRAL_GPU_KEYS_COMPACT, g_wire = g_seeded = true, i++;
+            cout << "Binding the batch's keys from a key store (" << (key_store == SPIRAL_GPU_KEYS_COMPACT ? "compact" : "full") << " slots)" << endl;
+        }
         // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
         // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
         // --output-err F (src/spiral.cpp:1287-1291) asks the reference to dump its empirical noise statistics (analyze_err.py's
@@ -359,6 +368,10 @@ int main(int argc, char** argv) {
     }
     if (g_wire && ((batch && (batch < 2 || batch > 8)) || (instances && (instances < 2 || instances > 16 || high_rate)))) {
         fprintf(stderr, "spiral: %s takes --batch B in 2 .. 8 and --instances F in 2 .. 16 (not with --high-rate)\n", g_seeded ? "--seeded" : "--wire-input");
+        return 1;
+    }
+    if (key_store >= 0 && (batch < 2 || batch > 8 || instances || high_rate)) {
+        fprintf(stderr, "spiral: --key-store takes --batch B in 2 .. 8 (not with --instances or --high-rate)\n");
         return 1;
     }
     if (idx_target >= total_n) {
@@ -519,6 +532,37 @@ int main(int argc, char** argv) {
             cout << " " << (ok ? 1 : 0);
         }
         cout << endl;
+        if (key_store >= 0) {  // client c's keys into slot c, in the form they travel in; then lane b serves the client of slot (b + round) mod B
+            spiral_gpu_key_store* store = nullptr;
+            GPU_OK(spiral_gpu_key_store_create(&p, 0, 0, batch, key_store, &store));
+            for (uint32_t c = 0; c < batch; c++) {
+                const std::vector<uint8_t> m = g_wire ? pp_msg(p, s, clients[c]) : std::vector<uint8_t>();
+                if (g_seeded) GPU_OK(spiral_gpu_key_store_put_seeded(store, c, m.data(), m.size()));
+                else if (g_wire) GPU_OK(spiral_gpu_key_store_put_wire(store, c, m.data(), m.size()));
+                else GPU_OK(spiral_gpu_key_store_put(store, c, clients[c].w_left.data(), clients[c].w_right.data(), clients[c].w.data(), clients[c].v.data()));
+            }
+            cout << "Key store: " << batch << " slots of " << spiral_gpu_key_store_slot_bytes(&p, 0, key_store) << " bytes" << endl;
+            for (uint32_t round = 0; round < 2; round++) {
+                std::vector<uint32_t> slots(batch);
+                for (uint32_t b = 0; b < batch; b++) slots[b] = (b + round) % batch;
+                GPU_OK(spiral_gpu_server_bind_keys(lanes.data(), batch, store, slots.data()));
+                for (uint32_t b = 0; b < batch; b++) {
+                    const Query qb = clients[slots[b]].query(idxs[slots[b]]);
+                    if (g_wire) GPU_OK(set_query_msg(lanes[b], query_msg(qb)));
+                    else GPU_OK(spiral_gpu_server_set_query(lanes[b], qb.cts.data()));
+                }
+                GPU_OK(spiral_gpu_server_run_query_batch(lanes.data(), batch));
+                for (uint32_t b = 0; b < batch; b++) {
+                    GPU_OK(spiral_gpu_server_sync(lanes[b]));
+                    GPU_OK(spiral_gpu_server_read_response_wire(lanes[b], wire.data(), wire.size()));
+                    GPU_OK(spiral_gpu_response_from_wire(&p, 2, wire.data(), resp.data()));
+                    const bool ok = clients[slots[b]].decode(resp.data()) == db_item(db_seed, idxs[slots[b]], p.p_db);
+                    batch_corr = batch_corr && ok;
+                    cout << "Key store round " << round << ", client " << slots[b] << " on lane " << b << ", Is correct?: " << (ok ? 1 : 0) << endl;
+                }
+            }
+            spiral_gpu_key_store_destroy(store);
+        }
         GPU_OK(spiral_gpu_server_use_graphs(srv, 0));
         for (uint32_t b = 1; b < batch; b++) spiral_gpu_server_destroy(lanes[b]);
     } else if (!item_batch && batch) {

@@ -272,6 +272,30 @@ void launch_pk_to_ref(const uint64_t* pk, uint64_t* ref, uint32_t npolys, IndexM
 // form, polynomial j to pk_map(j)
 void launch_seed_rows(const uint8_t* seed, uint32_t domain, uint64_t k0, uint64_t* pk, IndexMap pk_map, uint32_t npolys, hipStream_t s);
 
+// ---- client keys from a key store into the lanes of a call (keys.hip; key_store.h) ----------------------
+// A slot of a key store holds one client's public parameters in PK form, the parts of their message layout (message.h) back to back after `head`
+// words.  KEYS_FULL: every polynomial.  KEYS_COMPACT: the words of the message's 32-byte seed open the slot, and only rows 1.. of every matrix
+// follow, densely; the bind generates row 0 from the seed, the words launch_seed_rows writes.
+enum KeyForm : int { KEYS_FULL = 0, KEYS_COMPACT = 1 };  // (= SPIRAL_GPU_KEYS_FULL / _COMPACT)
+constexpr uint32_t kKeyCompactHead = 32;  // words in front of a COMPACT slot's polynomials: the seed, padded to a 256-byte piece
+struct KeyPart {
+    uint64_t* dst;       // lane 0's buffer of the part
+    uint32_t polys;      // its polynomials in the destination: matrices of [rows][cols], back to back (0: a part the message does not have)
+    uint32_t rows, cols;
+    uint32_t src;        // the slot's polynomial index of the first one the part stores
+    uint32_t row0;       // the row-0 polynomials of the parts before it (the seeded form's k of its first)
+};
+struct KeyBindParams {
+    const uint64_t* store;  // slot 0
+    uint64_t slot_words;
+    uint32_t head;          // words of a slot in front of its polynomials
+    uint32_t domain;        // the seeded form's domain tag
+    KeyPart part[4];
+    uint32_t slot[kMaxLanes];  // lane q's slot
+    Lanes lanes;               // lane q's arena offset (gridDim.z = lanes.n)
+};
+void launch_key_bind(const KeyBindParams& p, KeyForm form, hipStream_t s);
+
 // ---- pointwise polynomial kernels (poly.hip) -------------------------------------------------------
 // out[b][r][c] = sum_m A[r][m] * B[b][m][c]  (+ addend), all PK; generic MatPoly multiply (src/poly.cpp:34)
 struct MatmulParamsCore {

@@ -2,6 +2,7 @@
 // src/testing.cpp:1009-1081).  Kernels: pack.hip, ntt.hip (LD_PDIGIT / LD_DBGEN1), poly.hip (matmul, rescale), sweep_mfma.hip (the batched
 // first-dimension sweep of answer_batch: several lanes' queries in one pass over the trial images, from their limb-plane form).
 #include "db_image.h"
+#include "key_store.h"
 #include "message.h"
 
 using namespace spiral;
@@ -35,6 +36,7 @@ struct spiral_gpu_pack_server {
     PkBufs own{};  // what one answer writes
     DevBuf stage;
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
+    KeyMemo key_memo;  // the store slot the four key buffers were last bound from (bind_keys); none once set_pub_params* has written them
     hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch sweep / item call end, [8] ordering this server's stream in front of and behind a
                             // batch or item call that runs on another server's
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
@@ -157,6 +159,7 @@ int pk_take_pub_params(spiral_gpu_pack_server* S, Form form, const MessageIn& in
     if (form == FORM_NTT && check_ntt_parts(m, in, what)) return -1;
     uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->v.p, S->v_w.p};
     S->have_pp = false;
+    S->key_memo = KeyMemo{};
     if (ingest(form, IngestOn{S->stage, S->wire_in, S->tb, S->stream}, m, dst, in, what)) return -1;
     S->have_pp = true;
     return 0;
@@ -704,7 +707,8 @@ int spiral_gpu_pack_server_answer_seeded(spiral_gpu_pack_server* S, const void* 
 
 // the lanes of a batch: n in 1 .. kMaxLanes distinct servers that sweep the same images (an owner and its lanes), none trial-sharded, every one
 // with its public parameters (and, want_records, a converted query) -- checked before anything is launched
-static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bool want_records, const char* what, bool need_db = true) {
+// (need_pp false: the call sets them, bind_keys)
+static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bool want_records, const char* what, bool need_db = true, bool need_pp = true) {
     if (!servers) return fail("%s: null argument", what);
     if (n == 0 || n > kMaxLanes) return fail("%s: %u servers, 1 .. %u per batch", what, n, kMaxLanes);
     for (uint32_t b = 0; b < n; b++)
@@ -719,7 +723,7 @@ static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bo
         if (L->img != H->img) return fail("%s: server %u does not sweep server 0's database image (create_lane)", what, b);
         if (memcmp(&L->p, &H->p, sizeof(L->p)) != 0 || L->out_n != H->out_n || L->device != H->device || L->nt != H->nt)
             return fail("%s: server %u has other parameters than server 0", what, b);
-        if (!L->have_pp) return fail("%s: server %u has no public parameters", what, b);
+        if (need_pp && !L->have_pp) return fail("%s: server %u has no public parameters", what, b);
         if (want_records && !L->have_records) return fail("%s: server %u has no converted query (answer it once first)", what, b);
     }
     return 0;
@@ -765,6 +769,35 @@ static int pk_lanes_release(spiral_gpu_pack_server* const* servers, uint32_t n) 
         if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev[8], 0));
     return 0;
 }
+// spiral_gpu_server_bind_keys for SpiralPack: the keys of slot slots[b] of a store created for this out_n into lane b's W_exp_left, W_exp_right, V and v_W,
+// all lanes in one launch on servers[0]'s stream.  Checked before anything is launched; nothing is synchronised.
+int spiral_gpu_pack_server_bind_keys(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_key_store* store, const uint32_t* slots) {
+    const char* what = "pack bind_keys";
+    if (pk_check_lanes(servers, n, false, what, false, false)) return -1;
+    spiral_gpu_pack_server* S = servers[0];
+    HIP_OK(hipSetDevice(S->device));
+    Lanes lanes;
+    if (pk_lanes(servers, n, &lanes)) return -1;
+    const KeyMemo* memo[kMaxLanes];
+    for (uint32_t b = 0; b < n; b++) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        HIP_OK(hipStreamIsCapturing(servers[b]->stream, &cs));
+        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
+        memo[b] = servers[b]->have_pp ? &servers[b]->key_memo : nullptr;
+    }
+    uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->v.p, S->v_w.p};
+    const size_t dst_words[kMessageParts] = {S->w_left.words, S->w_right.words, S->v.words, S->v_w.words};
+    KeyBindPlan plan;
+    if (key_bind_plan(store, S->p, S->out_n, S->device, lanes, slots, memo, dst_words, what, &plan)) return -1;
+    if (plan.lanes.n == 0) return 0;
+    if (pk_lanes_join(servers, n) || key_bind_launch(store, plan, dst, S->stream) || pk_lanes_release(servers, n)) return -1;
+    for (uint32_t k = 0; k < plan.lanes.n; k++) {
+        servers[plan.lane[k]]->key_memo = key_bind_memo(store, plan, k);
+        servers[plan.lane[k]]->have_pp = true;
+    }
+    return 0;
+}
+
 // whether a call of n clients runs as one lane-aware launch sequence (option pack_batch_lanes, read per call; 0 = never)
 static bool pk_lane_form(uint32_t n) { return n >= 2 && options().pack_batch_lanes != 0 && n >= options().pack_batch_lanes; }
 

@@ -14,10 +14,7 @@ namespace {
 
 __global__ __launch_bounds__(256) void seed_rows_kernel(Seed key, uint32_t domain, uint64_t k0, uint64_t* pk, IndexMap map, uint32_t j0) {
     const uint32_t j = j0 + blockIdx.y, i = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t c = ((i & 255u) << 2) | (i >> 8);  // pk_pos(2c) = (c & 3) * 512 + (c >> 2) * 2 = 2i
-    uint64_t r[2];
-    seed_slot_pair(key.w, domain, k0 + j, c, r);
-    *reinterpret_cast<ulonglong2*>(pk + (size_t)map(j) * kN + 2u * i) = make_ulonglong2(r[0], r[1]);
+    seed_store_pair(key.w, domain, k0 + j, i, [&] { return pk + (size_t)map(j) * kN; });
 }
 
 }  // namespace

@@ -73,6 +73,19 @@ __host__ __device__ inline void seed_slot_pair(const uint32_t key[8], uint32_t d
     for (int h = 0; h < 2; h++) r[h] = (uint64_t)mod128<kP>(w + 8 * h) | ((uint64_t)mod128<kB>(w + 8 * h + 4) << 32);
 }
 
+#ifdef __HIPCC__
+// The device's thread-to-word map of a row-0 polynomial (seed.hip seed_rows_kernel, keys.hip key_bind_kernel): thread i of a polynomial (0 .. 1023)
+// computes one block -- slots 2c and 2c + 1 with c = (i mod 256) * 4 + i / 256, whose PK words pk_pos(2c), pk_pos(2c + 1) are 2i and 2i + 1 -- and
+// writes them with one 16-byte store, so a wave's stores cover 1 KiB of consecutive bytes
+template <class Where>  // where(): the polynomial's first word (evaluated after the block function)
+__device__ __forceinline__ void seed_store_pair(const uint32_t key[8], uint32_t domain, uint64_t k, uint32_t i, Where where) {
+    const uint32_t c = ((i & 255u) << 2) | (i >> 8);  // pk_pos(2c) = (c & 3) * 512 + (c >> 2) * 2 = 2i
+    uint64_t r[2];
+    seed_slot_pair(key, domain, k, c, r);
+    *reinterpret_cast<ulonglong2*>(where() + 2u * i) = make_ulonglong2(r[0], r[1]);
+}
+#endif
+
 __host__ __device__ inline Seed seed_words(const uint8_t* b) {
     Seed s;
     for (int i = 0; i < 8; i++) s.w[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 | (uint32_t)b[4 * i + 3] << 24;

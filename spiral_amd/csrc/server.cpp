@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "db_image.h"
+#include "key_store.h"
 #include "message.h"
 
 using namespace spiral;
@@ -89,6 +90,7 @@ struct spiral_gpu_server {
     uint64_t *gs_raw_p = nullptr, *gs_chat_p = nullptr;  // the Regev->GSW halves of cv_raw / cv_g
     DevBuf qs, acc_own, raw, fold_d, fold_c, fold_c2, resp, stage;
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
+    KeyMemo key_memo;  // the store slot the four key buffers were last bound from (bind_keys); none once set_pub_params* has written them
     uint64_t* acc = nullptr;
     hipEvent_t ev[8] = {};
     // captured launch sequences (hipGraph), used while use_graphs is on: captured on first use, re-captured when their key changes, all dropped
@@ -277,6 +279,7 @@ enum LaneNeeds : uint32_t {
     SHARDED = 8,        // the same fold ranks and expansion shard (a batch of a sharded answer), else neither and their own accumulators
     NO_CAPTURE = 16,    // no lane's stream is capturing
     SWEEP_ONLY = 32,    // they share the sweep only (first_dim_batch): the image's layout must agree, not parameters or schedules
+    GIVES_KEYS = 64,    // the call sets the public parameters (bind_keys): they need not be set
     SHARD_LANES = SHARDED | NO_CAPTURE,
 };
 
@@ -293,7 +296,7 @@ int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what,
     lanes->n = n;
     for (uint32_t b = 0; b < n; b++) {
         spiral_gpu_server* L = servers[b];
-        if (whole && (((needs & NEED_QUERY) && !L->have_query) || !L->have_pp)) return fail("%s: server %u needs its query and public parameters set first", what, b);
+        if (whole && (((needs & NEED_QUERY) && !L->have_query) || (!L->have_pp && !(needs & GIVES_KEYS)))) return fail("%s: server %u needs its query and public parameters set first", what, b);
         if ((needs & NEED_DB) && !L->img->loaded) return fail("%s: server %u has no database", what, b);
         if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has not converted its query (run_pre first)", what, b);
         if (L->device != S->device || L->dim0_shard != S->dim0_shard || L->s.num_per != S->s.num_per ||
@@ -366,6 +369,7 @@ int take_pub_params(spiral_gpu_server* S, Form form, const MessageIn& in, const 
     if (form == FORM_NTT && check_ntt_parts(m, in, what)) return -1;
     uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->w.p, S->v.p};
     S->have_pp = false;
+    S->key_memo = KeyMemo{};
     if (ingest(form, IngestOn{S->stage, S->wire_in, S->tb, S->stream}, m, dst, in, what)) return -1;
     S->have_pp = true;
     return 0;
@@ -447,6 +451,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "pack_pair_blocks") *value = o.pack_pair_blocks;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
+    else if (n == "key_binds") *value = (int64_t)g_key_binds.load();  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;
 }
@@ -1182,6 +1187,36 @@ int spiral_gpu_server_set_pub_params_seeded(spiral_gpu_server* S, const void* ms
 }
 int spiral_gpu_server_set_query_seeded(spiral_gpu_server* S, const void* msg, size_t bytes) {
     return take_query(S, FORM_SEEDED, MessageIn{{}, msg, bytes}, "set_query_seeded");
+}
+
+// "Lane b now serves the client of slot slots[b]" for the n lanes of a batch (an owner and its lanes, as run_query_batch takes them), in one launch on
+// servers[0]'s stream (keys.hip): each lane's four key buffers then hold what its own set_pub_params* of the slot's message would have left.  Every
+// check comes before the launch, so a failing call changes nothing; a lane whose memo names the slot's present content is left out of the launch.
+// Arena addresses do not move, so captured graphs replay with the new keys.  Nothing is synchronised.
+int spiral_gpu_server_bind_keys(spiral_gpu_server* const* servers, uint32_t n, spiral_gpu_key_store* store, const uint32_t* slots) {
+    const char* what = "bind_keys";
+    Lanes lanes;
+    if (check_lanes(servers, n, what, NO_CAPTURE | GIVES_KEYS, &lanes)) return -1;
+    spiral_gpu_server* S = servers[0];
+    const KeyMemo* memo[kMaxLanes];
+    for (uint32_t b = 0; b < n; b++) {
+        const spiral_gpu_server* L = servers[b];
+        if (L->arena.words != S->arena.words || L->w_left.p != L->arena.p || L->w_right.p - L->w_left.p != S->w_right.p - S->w_left.p ||
+            L->w.p - L->w_left.p != S->w.p - S->w_left.p || L->v.p - L->w_left.p != S->v.p - S->w_left.p)
+            return fail("%s: server %u's buffers are not laid out as server 0's", what, b);
+        memo[b] = L->have_pp ? &L->key_memo : nullptr;
+    }
+    uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->w.p, S->v.p};
+    const size_t dst_words[kMessageParts] = {S->w_left.words, S->w_right.words, S->w.words, S->v.words};
+    KeyBindPlan plan;
+    if (key_bind_plan(store, S->p, 0, S->device, lanes, slots, memo, dst_words, what, &plan)) return -1;
+    if (plan.lanes.n == 0) return 0;
+    if (lanes_join(servers, n) || key_bind_launch(store, plan, dst, S->stream) || lanes_release(servers, n)) return -1;
+    for (uint32_t k = 0; k < plan.lanes.n; k++) {
+        servers[plan.lane[k]]->key_memo = key_bind_memo(store, plan, k);
+        servers[plan.lane[k]]->have_pp = true;
+    }
+    return 0;
 }
 
 size_t spiral_gpu_query_wire_bytes(const spiral_gpu_params* p) { return base_message_bytes(p, query_layout, FORM_WIRE); }

@@ -217,6 +217,15 @@ def _lane_handles(servers, what: str):
     return servers, (C.c_void_p * len(servers))(*[s.h for s in servers])
 
 
+def bind_keys(servers, store, slots):
+    """lane b (an owner PackServer and its lanes, as answer_batch takes them) now serves the client of slot slots[b] of a keys.KeyStore created with
+    their out_n: one launch on servers[0]'s stream, not synchronised; see include/spiral_gpu.h spiral_gpu_pack_server_bind_keys"""
+    from .keys import _bind
+
+    servers, _ = _lane_handles(servers, "bind_keys")
+    _bind("spiral_gpu_pack_server_bind_keys", servers, store, slots)
+
+
 def _answer_batch(form: str, servers, queries, want_packed: bool):
     what = "answer_batch" + _FORMS[form]
     servers, hs = _lane_handles(servers, what)
