@@ -84,6 +84,8 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *                     form -- spiral_gpu_pack_has_limb_form, ..._pack_server_set_db_format(LIMBS), the automatic conversion by a batch of two or more
  *                     clients, time_sweep_batch -- and nowhere else: an image that is in the form is swept, updated, reloaded and converted back
  *                     whatever the option says now.  Same results either way
+ *   "query_batch_chunk" message polynomials per lane per staging pass of spiral_gpu_server_set_query_batch for messages too large to check on the
+ *                     host (direct upload); default 512, at least 1.  Read per call; same results whatever the value
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  *   "key_binds"       (get only) the lanes the bind_keys calls of this process have copied keys into (a lane that held them already is not counted)
@@ -704,6 +706,35 @@ int spiral_gpu_key_store_drop(spiral_gpu_key_store *store, uint32_t slot);
 int spiral_gpu_key_store_has(spiral_gpu_key_store *store, uint32_t slot);
 int spiral_gpu_server_bind_keys(spiral_gpu_server *const *servers, uint32_t n, spiral_gpu_key_store *store, const uint32_t *slots);
 int spiral_gpu_pack_server_bind_keys(spiral_gpu_pack_server *const *servers, uint32_t n, spiral_gpu_key_store *store, const uint32_t *slots);
+
+/* ------------------------------------------------------------------------------------------------
+ * A batch's queries in one call, its responses in one read (base server)
+ * ------------------------------------------------------------------------------------------------
+ * set_query_wire / set_query_seeded take one lane's query and return synchronised; read_response_wire packs, copies and synchronises per lane.  These
+ * two calls do both for all lanes of a batch at once.  servers[0 .. n) are n in 1 .. 8 distinct servers, an owner and its lanes as run_query_batch
+ * takes them (the same image, parameters, device, shard and buffer layout; lanes of a sharded batch and lanes with any schedule are taken too: neither
+ * call depends on a query, on public parameters or on a schedule).  Neither may be called during stream capture.
+ *
+ * set_query_batch: msgs[b] is server b's query in `form` -- SPIRAL_GPU_FORM_WIRE: what set_query_wire takes; SPIRAL_GPU_FORM_SEEDED: what
+ * set_query_seeded takes, the 32-byte seed first -- in pageable host memory, bytes_each = spiral_gpu_query_wire_bytes / _seeded_bytes each; the
+ * buffers may be reused when the call returns.  The NTT form (0) is refused: it is no byte stream.  The lanes are not reordered: message b lands in
+ * server b.  Everything is checked before anything is written; a call refused for its arguments leaves every lane as it was.  Afterwards every
+ * lane's query buffer holds, word for word, what its own set_query_wire / set_query_seeded of its message would have left.  Buffer addresses do
+ * not move: a captured graph replays with the new queries.
+ *   Messages of at most 4 polynomials per lane (every compressed query): the host checks each coefficient while it copies the messages into a
+ *   pinned slot (a ring of two, owned by servers[0]); a coefficient above Q fails the call, naming the server and the coefficient, before anything
+ *   goes up, and every lane keeps its previous query.  Otherwise: one copy, one launch on servers[0]'s stream behind what the other lanes' streams
+ *   hold, and the call returns WITHOUT synchronising.
+ *   Larger messages (direct upload): "query_batch_chunk" message polynomials per lane per pass go through a device staging, one launch per pass for
+ *   all lanes, one synchronisation at the end.  A coefficient above Q is found on the device: the call fails, naming the server and the coefficient,
+ *   and EVERY lane of the call is left without a query (n messages x polynomials x 2048 coefficients must stay below 2^32).
+ *
+ * read_response_wire_batch: the wire forms of the n lanes' last responses in one launch, one copy and one synchronisation; lane b's
+ * spiral_gpu_response_wire_bytes(p, 2) bytes at out + b * that size, equal to what its own read_response_wire returns.  A capacity below n x that
+ * size is refused before anything is launched. */
+enum spiral_gpu_message_form { SPIRAL_GPU_FORM_WIRE = 1, SPIRAL_GPU_FORM_SEEDED = 2 };
+int spiral_gpu_server_set_query_batch(spiral_gpu_server *const *servers, uint32_t n, int form, const void *const *msgs, size_t bytes_each);
+int spiral_gpu_server_read_response_wire_batch(spiral_gpu_server *const *servers, uint32_t n, void *out, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -11,4 +11,5 @@ from .ops import *  # noqa: F401,F403
 from .pack import PackServer, fastMultiplyQueryByDatabaseDim1, get_pack_shape, pack  # noqa: F401
 from .pack import answer_batch_instances as pack_answer_batch_instances, answer_instances as pack_answer_instances  # noqa: F401
 from .server import Server, answer_batch_instances, first_dim_batch, run_query_batch, run_query_batch_instances, time_sweep_batch  # noqa: F401
+from .server import read_response_wire_batch, set_query_batch  # noqa: F401
 from .server import fold_local_batch, fold_root_batch, run_expand_pack_batch, run_pre_sweep_batch, run_unpack_convert_sweep_batch  # noqa: F401

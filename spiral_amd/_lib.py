@@ -222,6 +222,8 @@ PROTOTYPES = {
     "spiral_gpu_key_store_has": (C.c_int, [C.c_void_p, C.c_uint32]),
     "spiral_gpu_server_bind_keys": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     "spiral_gpu_pack_server_bind_keys": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "spiral_gpu_server_set_query_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.c_size_t]),
+    "spiral_gpu_server_read_response_wire_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t]),
 }
 
 
@@ -267,6 +269,7 @@ def check(rc: int) -> None:
 
 WIRE_POLY_BYTES = 7 * 2048  # one polynomial of a query / public-parameter message in its wire form (include/spiral_gpu.h)
 SEED_BYTES = 32  # the seed that opens a message in its seeded form
+FORM_NTT, FORM_WIRE, FORM_SEEDED = 0, 1, 2  # spiral_gpu_message_form (the NTT form is no message: the batch ingest refuses it by name)
 SEED_QUERY, SEED_PUB_PARAMS, SEED_PACK_QUERY, SEED_PACK_PUB_PARAMS = 1, 2, 3, 4  # the seeded form's domain tags
 
 

@@ -2,7 +2,7 @@
 // 209-265), with the server-answer path running on an MI355X through libspiral_gpu.so.
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
-//            [--wire-input] [--seeded] [--key-store [compact]]
+//            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch]
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -324,6 +324,7 @@ int main(int argc, char** argv) {
     bool nonoise = false, random_data = false, show_diff = false, direct_flag = false, high_rate = false;
     uint32_t batch = 0, instances = 0;
     int key_store = -1;  // --key-store: the slot form of the store the batch's keys are bound from (-1: none)
+    bool query_batch = false;  // --query-batch: the batch's queries in one set_query_batch call, its responses in one read
     // as the reference (random_device, src/core.cpp:202; it labels its own generator NOT SECURE): two words of it.
     // This client is a test harness for the server path, not a hardened client.
     std::random_device rd;
@@ -354,6 +355,10 @@ int main(int argc, char** argv) {
             if (i + 1 < argc && !strcmp(argv[i + 1], "compact")) key_store = SPIRAL_GPU_KEYS_COMPACT, g_wire = g_seeded = true, i++;
             cout << "Binding the batch's keys from a key store (" << (key_store == SPIRAL_GPU_KEYS_COMPACT ? "compact" : "full") << " slots)" << endl;
         }
+        // --batch B --query-batch (not a flag of the reference): after the batch, every client draws a fresh query; all of them go in through ONE
+        // spiral_gpu_server_set_query_batch call -- in the wire form, or with --seeded in the seeded form -- and all responses come back through ONE
+        // spiral_gpu_server_read_response_wire_batch; every client is decoded and checked.  With --key-store the lanes' keys are bound from the store first
+        if (!strcmp(argv[i], "--query-batch")) { cout << "Taking the batch's queries in one call and its responses in one read" << endl; query_batch = true; }
         // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
         // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
         // --output-err F (src/spiral.cpp:1287-1291) asks the reference to dump its empirical noise statistics (analyze_err.py's
@@ -366,6 +371,11 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: --batch B --instances F takes B in 2 .. 8 and F in 2 .. 16 (and no --high-rate)\n");
         return 1;
     }
+    if (query_batch && (batch < 2 || batch > 8 || instances || high_rate)) {
+        fprintf(stderr, "spiral: --query-batch takes --batch B in 2 .. 8 (not with --instances or --high-rate)\n");
+        return 1;
+    }
+    if (query_batch) g_wire = true;  // (the wire form unless --seeded chose the seeded one)
     if (g_wire && ((batch && (batch < 2 || batch > 8)) || (instances && (instances < 2 || instances > 16 || high_rate)))) {
         fprintf(stderr, "spiral: %s takes --batch B in 2 .. 8 and --instances F in 2 .. 16 (not with --high-rate)\n", g_seeded ? "--seeded" : "--wire-input");
         return 1;
@@ -532,8 +542,8 @@ int main(int argc, char** argv) {
             cout << " " << (ok ? 1 : 0);
         }
         cout << endl;
+        spiral_gpu_key_store* store = nullptr;
         if (key_store >= 0) {  // client c's keys into slot c, in the form they travel in; then lane b serves the client of slot (b + round) mod B
-            spiral_gpu_key_store* store = nullptr;
             GPU_OK(spiral_gpu_key_store_create(&p, 0, 0, batch, key_store, &store));
             for (uint32_t c = 0; c < batch; c++) {
                 const std::vector<uint8_t> m = g_wire ? pp_msg(p, s, clients[c]) : std::vector<uint8_t>();
@@ -561,8 +571,33 @@ int main(int argc, char** argv) {
                     cout << "Key store round " << round << ", client " << slots[b] << " on lane " << b << ", Is correct?: " << (ok ? 1 : 0) << endl;
                 }
             }
-            spiral_gpu_key_store_destroy(store);
         }
+        if (query_batch) {  // lane b serves client who[b]: its own, or with a key store the client two lanes on, bound from its slot
+            std::vector<uint32_t> who(batch);
+            for (uint32_t b = 0; b < batch; b++) who[b] = store ? (b + 2) % batch : b;
+            if (store) GPU_OK(spiral_gpu_server_bind_keys(lanes.data(), batch, store, who.data()));
+            std::vector<uint64_t> fresh(batch);
+            std::vector<std::vector<uint8_t>> msgs;
+            std::vector<const void*> mp;
+            for (uint32_t b = 0; b < batch; b++) {
+                fresh[b] = (idxs[who[b]] + 4099ull) % total_n;
+                msgs.push_back(query_msg(clients[who[b]].query(fresh[b])));
+            }
+            for (uint32_t b = 0; b < batch; b++) mp.push_back(msgs[b].data());
+            GPU_OK(spiral_gpu_server_set_query_batch(lanes.data(), batch, g_seeded ? SPIRAL_GPU_FORM_SEEDED : SPIRAL_GPU_FORM_WIRE, mp.data(), msgs[0].size()));
+            cout << "The batch's " << batch << " queries went in as one set_query_batch call (" << (g_seeded ? "seeded" : "wire") << " form, " << msgs[0].size()
+                 << " bytes each)" << endl;
+            GPU_OK(spiral_gpu_server_run_query_batch(lanes.data(), batch));
+            std::vector<uint8_t> wires(batch * wire.size());
+            GPU_OK(spiral_gpu_server_read_response_wire_batch(lanes.data(), batch, wires.data(), wires.size()));
+            for (uint32_t b = 0; b < batch; b++) {
+                GPU_OK(spiral_gpu_response_from_wire(&p, 2, wires.data() + b * wire.size(), resp.data()));
+                const bool ok = clients[who[b]].decode(resp.data()) == db_item(db_seed, fresh[b], p.p_db);
+                batch_corr = batch_corr && ok;
+                cout << "Query batch, client " << who[b] << " on lane " << b << ", Is correct?: " << (ok ? 1 : 0) << endl;
+            }
+        }
+        if (store) spiral_gpu_key_store_destroy(store);
         GPU_OK(spiral_gpu_server_use_graphs(srv, 0));
         for (uint32_t b = 1; b < batch; b++) spiral_gpu_server_destroy(lanes[b]);
     } else if (!item_batch && batch) {

@@ -34,6 +34,8 @@ struct Options {
                                     // until the lane form is measured against the per-lane form
     int pack_pair_blocks = 0;  // 1: a SpiralPack image of 8 ciphertexts per slot may TAKE the limb-plane form (the pair form of the matrix-core sweep,
                                // sweep_mfma.hip); read only where that is decided (db_image.h DbLayout::limbs_ok), never by what works on a converted image
+    uint32_t query_batch_chunk = 512;  // set_query_batch: message polynomials per lane per staging pass of messages too large to check on the host
+                                       // (= message.h kWireChunkPolys / kMaxLanes: all lanes together fill set_query_wire's staging), at least 1
 };
 Options& options();  // server.cpp; the three documented environment variables are read once, on first use
 
@@ -295,6 +297,29 @@ struct KeyBindParams {
     Lanes lanes;               // lane q's arena offset (gridDim.z = lanes.n)
 };
 void launch_key_bind(const KeyBindParams& p, KeyForm form, hipStream_t s);
+
+// ---- the queries of a batch's lanes from their staged messages into their query buffers (query_ingest.hip) ----------------------
+// One launch covers destination polynomials first_dst .. first_dst + n_dst - 1 of every lane's query buffer (gridDim.x = n_dst, gridDim.z = lanes).
+// The query is matrices of [rows][cols] polynomials back to back (message.h query_layout).  Lane q's staged bytes start at stage + q * lane_stride:
+// `head` bytes (the seeded form: the message's 32-byte seed), then the wire form of message polynomials first_msg .. of this pass.  QUERY_WIRE:
+// destination polynomial d is message polynomial d, decoded and transformed as LD_WIRE + ST_PK does.  QUERY_SEEDED: the message holds rows 1.. of
+// every matrix only; a row-0 destination is generated from the lane's seed (seed_device.h, the words launch_seed_rows writes).  A coefficient above
+// Q atomicMin's (~gen << 32 | (lane * msg_polys + message polynomial) * 2048 + index) into the u64 at err (wire_device.h).
+enum QueryForm : int { QUERY_WIRE = 0, QUERY_SEEDED = 1 };
+struct QueryIngestParams {
+    const uint8_t* stage;
+    uint64_t lane_stride;  // bytes, a multiple of 16
+    uint32_t head;         // bytes of a lane's staging in front of its polynomials, a multiple of 16
+    uint64_t* dst;         // lane 0's query buffer
+    uint32_t rows, cols;
+    uint32_t domain;       // the seeded form's domain tag
+    uint32_t first_dst, first_msg;
+    uint32_t msg_polys;    // polynomials a lane's whole message sends
+    uint32_t* err;
+    uint64_t gen;
+    Lanes lanes;           // lane q's arena offset
+};
+void launch_query_ingest(const DeviceTables& t, const QueryIngestParams& p, QueryForm form, uint32_t n_dst, hipStream_t s);
 
 // ---- pointwise polynomial kernels (poly.hip) -------------------------------------------------------
 // out[b][r][c] = sum_m A[r][m] * B[b][m][c]  (+ addend), all PK; generic MatPoly multiply (src/poly.cpp:34)

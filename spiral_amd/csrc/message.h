@@ -194,6 +194,53 @@ inline int ingest_message(WireIn& W, const DeviceTables& tb, hipStream_t st, con
     return 0;
 }
 
+// The workspace of the batch ingest (server.cpp spiral_gpu_server_set_query_batch), owned by the batch's servers[0] and used on its stream only:
+// the device staging [u64 error word, padded to 256 bytes][lane][head + chunk polynomials], the generation of the error word as WireIn's, and for
+// messages small enough to check on the host a ring of two pinned slots laid out as the staging, each with the event recorded behind the launch
+// that read it -- a call waits for that event before it fills the slot again, never for the stream.
+struct QueryBatchIn {
+    static constexpr size_t kErrWords = 32;
+    DevBuf stage;
+    size_t stage_bytes = 0;  // behind the error word
+    uint64_t* host_err = nullptr;  // pinned
+    uint32_t gen = 0;
+    struct Slot {
+        uint8_t* p = nullptr;  // pinned
+        size_t bytes = 0;
+        hipEvent_t ev = nullptr;
+        bool in_flight = false;
+    } ring[2];
+    uint32_t next = 0;
+    hipStream_t last_stream = nullptr;  // the staging's last user, ordered by `last` in front of a call on another stream (set_stream)
+    hipEvent_t last = nullptr;
+    uint8_t* bytes() const { return reinterpret_cast<uint8_t*>(stage.p + kErrWords); }
+    // at least `need` bytes of staging behind an error word of generation < 0xffffffff
+    int reserve(size_t need, hipStream_t st) {
+        if (stage.p && stage_bytes >= need && gen != 0xffffffffu) return 0;
+        stage.release();  // (hipFree waits for whatever still reads it)
+        stage_bytes = 0;
+        const size_t words = (need + 7) / 8;
+        if (stage.alloc(kErrWords + words)) return -1;
+        HIP_OK(hipMemsetAsync(stage.p, 0xff, kErrWords * sizeof(uint64_t), st));  // generation 0: all ones
+        stage_bytes = words * 8;
+        gen = 0;
+        return 0;
+    }
+    void release() {
+        stage.release();
+        stage_bytes = 0;
+        if (host_err) (void)hipHostFree(host_err);
+        host_err = nullptr;
+        for (Slot& s : ring) {
+            if (s.ev) (void)hipEventSynchronize(s.ev), (void)hipEventDestroy(s.ev);
+            if (s.p) (void)hipHostFree(s.p);
+            s = Slot{};
+        }
+        last = nullptr;  // (one of the slots' events)
+        last_stream = nullptr;
+    }
+};
+
 // a server's two ingest workspaces and where its ingests run
 struct IngestOn {
     DevBuf& stage;  // the NTT form's staging

@@ -8,6 +8,7 @@
 #include "digits_device.h"
 #include "kernels.h"
 #include "ntt_device.h"
+#include "wire_device.h"
 
 namespace spiral {
 
@@ -218,29 +219,8 @@ __global__ __launch_bounds__(256, 8) void ntt_forward_kernel(Tables t, FwdParams
             }
         }
     } else if constexpr (LOAD == LD_WIRE) {
-        // polynomial s of the staged message: its 14 336 bytes come into LDS with 16-byte loads (896 per polynomial, coalesced), then each
-        // thread takes its eight 56-bit coefficients from there -- one or two LDS words each
-        const uint4* src = reinterpret_cast<const uint4*>(p.items + (size_t)s * kWirePolyBytes);
-        for (uint32_t i = tid; i < kWirePolyBytes / 16u; i += 256u) {
-            const uint4 x = src[i];
-            sh[2u * i] = pack(x.x, x.y);
-            sh[2u * i + 1u] = pack(x.z, x.w);
-        }
-        __syncthreads();
-        uint32_t bad = 0xffffffffu;
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const uint32_t idx = ix_a(tid, r), bit = 56u * idx, w = bit >> 6, sft = bit & 63u;
-            uint64_t v = sh[w] >> sft;
-            if (sft > 8u) v |= sh[w + 1u] << (64u - sft);  // (the last coefficient, sft = 8, ends inside word 1791)
-            v &= (1ull << 56) - 1ull;
-            if (v > kQ) bad = min(bad, idx);
-            lo[r] = mod_p(v);
-            hi[r] = mod_b(v);
-        }
-        if (bad != 0xffffffffu)
-            atomicMin(reinterpret_cast<unsigned long long*>(p.err), (~p.seed << 32) | ((uint32_t)(p.item_base + s) * kN + bad));
-        __syncthreads();  // the transform reuses the LDS words
+        // polynomial s of the staged message (wire_device.h)
+        wire_decode8(p.items + (size_t)s * kWirePolyBytes, sh, tid, lo, hi, p.err, p.seed, (uint32_t)(p.item_base + s) * kN);
     } else if constexpr (LOAD == LD_LIMBS) {
         const uint64_t* src = p.src + (size_t)p.src_map(s) * (2 * kN);
 #pragma unroll

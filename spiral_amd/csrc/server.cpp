@@ -90,6 +90,7 @@ struct spiral_gpu_server {
     uint64_t *gs_raw_p = nullptr, *gs_chat_p = nullptr;  // the Regev->GSW halves of cv_raw / cv_g
     DevBuf qs, acc_own, raw, fold_d, fold_c, fold_c2, resp, stage;
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
+    QueryBatchIn query_batch_in;  // ... of set_query_batch, when this server is a batch's servers[0]
     KeyMemo key_memo;  // the store slot the four key buffers were last bound from (bind_keys); none once set_pub_params* has written them
     uint64_t* acc = nullptr;
     hipEvent_t ev[8] = {};
@@ -188,6 +189,7 @@ void srv_free(spiral_gpu_server* S) {
     DbImage::drop(S->img, S);
     for (DevBuf* b : {&S->arena, &S->ex_raw2, &S->ex_g2, &S->cts_keep, &S->stage, &S->wire}) b->release();  // (what owns memory: the rest are pieces of the arena)
     S->wire_in.release();
+    S->query_batch_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e);
     if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
@@ -280,6 +282,8 @@ enum LaneNeeds : uint32_t {
     NO_CAPTURE = 16,    // no lane's stream is capturing
     SWEEP_ONLY = 32,    // they share the sweep only (first_dim_batch): the image's layout must agree, not parameters or schedules
     GIVES_KEYS = 64,    // the call sets the public parameters (bind_keys): they need not be set
+    MOVES_DATA = 128,   // the call only moves messages in or responses out (set_query_batch, read_response_wire_batch): it depends on no query, no
+                        // public parameters and no schedule, so lanes of a sharded batch and lanes with other schedules are taken too
     SHARD_LANES = SHARDED | NO_CAPTURE,
 };
 
@@ -292,11 +296,11 @@ int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what,
         if (!servers[b]) return fail("%s: null server %u", what, b);
     spiral_gpu_server* S = servers[0];
     HIP_OK(hipSetDevice(S->device));
-    const bool whole = !(needs & SWEEP_ONLY), sharded = needs & SHARDED;
+    const bool whole = !(needs & SWEEP_ONLY), sharded = needs & SHARDED, moves = needs & MOVES_DATA;
     lanes->n = n;
     for (uint32_t b = 0; b < n; b++) {
         spiral_gpu_server* L = servers[b];
-        if (whole && (((needs & NEED_QUERY) && !L->have_query) || (!L->have_pp && !(needs & GIVES_KEYS)))) return fail("%s: server %u needs its query and public parameters set first", what, b);
+        if (whole && (((needs & NEED_QUERY) && !L->have_query) || (!L->have_pp && !(needs & (GIVES_KEYS | MOVES_DATA))))) return fail("%s: server %u needs its query and public parameters set first", what, b);
         if ((needs & NEED_DB) && !L->img->loaded) return fail("%s: server %u has no database", what, b);
         if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has not converted its query (run_pre first)", what, b);
         if (L->device != S->device || L->dim0_shard != S->dim0_shard || L->s.num_per != S->s.num_per ||
@@ -307,9 +311,9 @@ int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what,
             return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
         if (sharded && (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank))
             return fail("%s: server %u has another expansion shard than server 0", what, b);
-        if (whole && !sharded && (L->acc != L->acc_own.p || L->fold_g_log || L->ex_shard.g_log))
+        if (whole && !sharded && !moves && (L->acc != L->acc_own.p || L->fold_g_log || L->ex_shard.g_log))
             return fail("%s: server %u has an external accumulator, fold ranks or a sharded expansion set", what, b);
-        if (L->sweep_k_log || (whole && (L->keep_cts || L->overlap || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain)))
+        if (!moves && (L->sweep_k_log || (whole && (L->keep_cts || L->overlap || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain))))
             return fail("%s: server %u has keep_cts, a split or staged schedule or other fold options set", what, b);
         for (uint32_t c = 0; c < b; c++)
             if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
@@ -431,6 +435,7 @@ int spiral_gpu_set_option(const char* name, int64_t value) {
     else if (n == "pack_item_group" && value >= 0 && value <= 0xFFFFFFFFll) o.pack_item_group = (uint32_t)value;
     else if (n == "pack_batch_lanes" && value >= 0 && value <= (int64_t)kMaxLanes) o.pack_batch_lanes = (uint32_t)value;
     else if (n == "pack_pair_blocks" && (value == 0 || value == 1)) o.pack_pair_blocks = (int)value;
+    else if (n == "query_batch_chunk" && value >= 1 && value <= 0xFFFFFFFFll) o.query_batch_chunk = (uint32_t)value;
     else return fail("unknown option '%s' or value %lld out of range", name, (long long)value);
     return 0;
 }
@@ -449,6 +454,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "pack_item_group") *value = o.pack_item_group;
     else if (n == "pack_batch_lanes") *value = o.pack_batch_lanes;
     else if (n == "pack_pair_blocks") *value = o.pack_pair_blocks;
+    else if (n == "query_batch_chunk") *value = o.query_batch_chunk;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else if (n == "key_binds") *value = (int64_t)g_key_binds.load();  // (read only)
@@ -1216,6 +1222,155 @@ int spiral_gpu_server_bind_keys(spiral_gpu_server* const* servers, uint32_t n, s
         servers[plan.lane[k]]->key_memo = key_bind_memo(store, plan, k);
         servers[plan.lane[k]]->have_pp = true;
     }
+    return 0;
+}
+
+// The queries of the n lanes of a batch in one call: message b (wire or seeded form, pageable memory) into servers[b]'s query buffer, through ONE
+// lane-aware kernel (query_ingest.hip) on servers[0]'s stream.  Everything is checked before anything is written.  Messages the host can check
+// (at most kWireHostCheckPolys polynomials per lane: every compressed query) go up in one copy from a pinned slot and one launch, and the call
+// returns without synchronising.  Larger ones (direct upload) go through the staging [lane][chunk] a pass at a time, one launch per pass for all
+// lanes, with one synchronisation and one read of the generation-tagged error word at the end; a bad coefficient found there leaves every lane of
+// the call without a query.
+static_assert((int)FORM_NTT == 0 && (int)FORM_WIRE == SPIRAL_GPU_FORM_WIRE && (int)FORM_SEEDED == SPIRAL_GPU_FORM_SEEDED, "message.h Form is the public enum");
+static_assert(Options{}.query_batch_chunk == kWireChunkPolys / kMaxLanes, "the default pass of set_query_batch: set_query_wire's staging shared by all lanes");
+int spiral_gpu_server_set_query_batch(spiral_gpu_server* const* servers, uint32_t n, int form, const void* const* msgs, size_t bytes_each) {
+    const char* what = "set_query_batch";
+    Lanes lanes;
+    if (check_lanes(servers, n, what, NO_CAPTURE | MOVES_DATA, &lanes)) return -1;
+    spiral_gpu_server* S = servers[0];
+    if (form == FORM_NTT) return fail("%s: the NTT form is not taken (one host buffer per part: use set_query); pass the wire or the seeded form", what);
+    if (form != SPIRAL_GPU_FORM_WIRE && form != SPIRAL_GPU_FORM_SEEDED) return fail("%s: unknown message form %d", what, form);
+    const bool seeded = form == SPIRAL_GPU_FORM_SEEDED;
+    const MessageLayout m = query_layout(S->p, S->s);
+    const MessagePart& part = m.part[0];
+    const size_t npolys = message_polys(m, (Form)form), want = message_bytes(m, (Form)form);
+    if (bytes_each != want)
+        return fail("%s: %zu bytes per message, the %s form of this query takes %zu", what, bytes_each, seeded ? "seeded" : "wire", want);
+    if (seeded && part.rows < 2) return fail("%s: the query is not a run of matrices with rows >= 2", what);
+    if (!msgs) return fail("%s: null message list", what);
+    for (uint32_t b = 0; b < n; b++) {
+        if (!msgs[b]) return fail("%s: null message %u", what, b);
+        const spiral_gpu_server* L = servers[b];
+        if (L->arena.words != S->arena.words || L->w_left.p != L->arena.p || L->query.p - L->w_left.p != S->query.p - S->w_left.p)
+            return fail("%s: server %u's buffers are not laid out as server 0's", what, b);
+    }
+    // the error word's index names (lane, message polynomial, coefficient)
+    if ((uint64_t)n * npolys * kN >= 0xffffffffull) return fail("%s: %u messages of %zu polynomials exceed the coefficient index range", what, n, npolys);
+    if (npolys == 0) return 0;
+    QueryBatchIn& Q = S->query_batch_in;
+    hipStream_t st = S->stream;
+    const uint32_t head = seeded ? kSeedBytes : 0u;
+    // a pass covers whole units: one polynomial (wire), the rows 1.. of one matrix and its destinations (seeded)
+    const uint32_t unit_msg = seeded ? (part.rows - 1u) * part.cols : 1u, unit_dst = seeded ? part.rows * part.cols : 1u;
+    const size_t units = npolys / unit_msg;
+    QueryIngestParams qp{};
+    qp.head = head;
+    qp.dst = S->query.p;
+    qp.rows = part.rows;
+    qp.cols = part.cols;
+    qp.domain = m.domain;
+    qp.msg_polys = (uint32_t)npolys;
+    qp.lanes = lanes;
+    if (Q.last && Q.last_stream != st) HIP_OK(hipStreamWaitEvent(st, Q.last, 0));  // (the stream changed under a call in flight)
+
+    if (npolys <= kWireHostCheckPolys) {
+        const size_t stride = head + npolys * kWirePolyBytes;
+        QueryBatchIn::Slot& slot = Q.ring[Q.next];
+        if (slot.in_flight) HIP_OK(hipEventSynchronize(slot.ev));  // the call two back: its copy has read the slot
+        slot.in_flight = false;
+        if (slot.bytes < kMaxLanes * stride) {
+            if (slot.p) HIP_OK(hipHostFree(slot.p));
+            slot.p = nullptr;
+            HIP_OK(hipHostMalloc((void**)&slot.p, kMaxLanes * stride, hipHostMallocDefault));
+            slot.bytes = kMaxLanes * stride;
+        }
+        if (!slot.ev) HIP_OK(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+        for (uint32_t b = 0; b < n; b++) {  // checked while copied: a bad coefficient fails before anything goes up
+            const uint8_t* msg = (const uint8_t*)msgs[b];
+            const int64_t i = wire_first_above_q(msg + head, npolys * kN);
+            if (i >= 0)
+                return fail("%s: server %u: coefficient %u (polynomial %u, index %u) is above Q", what, b, (uint32_t)i, (uint32_t)i / kN, (uint32_t)i % kN);
+            memcpy(slot.p + b * stride, msg, stride);
+        }
+        if (Q.reserve(kMaxLanes * stride, st)) return -1;
+        HIP_OK(hipMemcpyAsync(Q.bytes(), slot.p, n * stride, hipMemcpyHostToDevice, st));
+        if (lanes_join(servers, n)) return -1;
+        qp.stage = Q.bytes();
+        qp.lane_stride = stride;
+        qp.err = reinterpret_cast<uint32_t*>(Q.stage.p);
+        qp.gen = ++Q.gen;  // (never read: the host has checked)
+        launch_query_ingest(S->tb, qp, seeded ? QUERY_SEEDED : QUERY_WIRE, (uint32_t)(units * unit_dst), st);
+        HIP_OK(hipGetLastError());
+        for (uint32_t b = 0; b < n; b++) {
+            servers[b]->have_query = true;
+            servers[b]->have_records = false;
+        }
+        if (lanes_release(servers, n)) return -1;
+        HIP_OK(hipEventRecord(slot.ev, st));
+        slot.in_flight = true;
+        Q.last = slot.ev;
+        Q.last_stream = st;
+        Q.next ^= 1u;
+        return 0;
+    }
+
+    const size_t chunk = std::max<size_t>(std::min<size_t>(options().query_batch_chunk, npolys), unit_msg) / unit_msg;  // units per pass
+    const size_t stride = head + chunk * unit_msg * kWirePolyBytes;
+    if (Q.reserve(kMaxLanes * stride, st)) return -1;
+    if (!Q.host_err) HIP_OK(hipHostMalloc((void**)&Q.host_err, sizeof(uint64_t), hipHostMallocDefault));
+    qp.stage = Q.bytes();
+    qp.lane_stride = stride;
+    qp.err = reinterpret_cast<uint32_t*>(Q.stage.p);
+    qp.gen = ++Q.gen;
+    for (uint32_t b = 0; b < n; b++) servers[b]->have_query = servers[b]->have_records = false;  // from the first write on nothing answers from these buffers
+    if (lanes_join(servers, n)) return -1;
+    for (size_t u0 = 0; u0 < units; u0 += chunk) {
+        const size_t nu = std::min(chunk, units - u0);
+        for (uint32_t b = 0; b < n; b++) {  // (the first pass takes the seed with it)
+            const uint8_t* msg = (const uint8_t*)msgs[b];
+            if (u0 == 0)
+                HIP_OK(hipMemcpyAsync(Q.bytes() + b * stride, msg, head + nu * unit_msg * kWirePolyBytes, hipMemcpyHostToDevice, st));
+            else
+                HIP_OK(hipMemcpyAsync(Q.bytes() + b * stride + head, msg + head + u0 * unit_msg * kWirePolyBytes, nu * unit_msg * kWirePolyBytes,
+                                      hipMemcpyHostToDevice, st));
+        }
+        qp.first_dst = (uint32_t)(u0 * unit_dst);
+        qp.first_msg = (uint32_t)(u0 * unit_msg);
+        launch_query_ingest(S->tb, qp, seeded ? QUERY_SEEDED : QUERY_WIRE, (uint32_t)(nu * unit_dst), st);
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(Q.host_err, Q.stage.p, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (lanes_release(servers, n)) return -1;
+    HIP_OK(hipStreamSynchronize(st));
+    Q.last = nullptr;
+    const uint64_t err = *Q.host_err;
+    if ((uint32_t)(err >> 32) == (uint32_t)~qp.gen) {
+        const uint32_t i = (uint32_t)err, c = i % (uint32_t)(npolys * kN);
+        return fail("%s: server %u: coefficient %u (polynomial %u, index %u) is above Q", what, i / (uint32_t)(npolys * kN), c, c / kN, c % kN);
+    }
+    for (uint32_t b = 0; b < n; b++) servers[b]->have_query = true;
+    return 0;
+}
+
+// The wire forms of the n lanes' last responses in one launch, one copy and one synchronisation: lane b's at out + b * response_wire_bytes, the
+// bytes its own read_response_wire returns
+int spiral_gpu_server_read_response_wire_batch(spiral_gpu_server* const* servers, uint32_t n, void* out, size_t capacity) {
+    const char* what = "read_response_wire_batch";
+    Lanes lanes;
+    if (check_lanes(servers, n, what, NO_CAPTURE | MOVES_DATA, &lanes)) return -1;
+    spiral_gpu_server* S = servers[0];
+    if (!out) return fail("%s: null output buffer", what);
+    const size_t nbytes = wire_bytes(&S->p, 2);
+    if (capacity < n * nbytes) return fail("%s: response buffer of %zu bytes, the wire forms of %u lanes need %zu", what, capacity, n, n * nbytes);
+    for (uint32_t b = 0; b < n; b++)
+        if (servers[b]->resp.p - servers[b]->w_left.p != S->resp.p - S->w_left.p) return fail("%s: server %u's buffers are not laid out as server 0's", what, b);
+    if (S->wire.words * 8 < n * nbytes && (S->wire.release(), S->wire.alloc(n * nbytes / 8))) return -1;
+    if (lanes_join(servers, n)) return -1;
+    launch_response_wire(S->resp.p, S->wire.p, 2 * kN, S->p.qprime_bits, 4 * kN, wire_bits_rest(&S->p), S->stream, lanes, 0, (int64_t)(nbytes / 8));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(out, S->wire.p, n * nbytes, hipMemcpyDeviceToHost, S->stream));
+    if (lanes_release(servers, n)) return -1;
+    HIP_OK(hipStreamSynchronize(S->stream));
     return 0;
 }
 

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, Params, Shape, check, lib, update_args, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, lib, update_args, wire_bytes
 
 N = 2048
 
@@ -38,6 +38,36 @@ def run_query_batch(servers):
     """the whole answer for the queries of up to eight servers sharing one image, every launch carrying all of them; see include/spiral_gpu.h"""
     arr = (C.c_void_p * len(servers))(*[s.h for s in servers])
     check(lib().spiral_gpu_server_run_query_batch(arr, len(servers)))
+
+
+MESSAGE_FORMS = {"ntt": FORM_NTT, "wire": FORM_WIRE, "seeded": FORM_SEEDED}
+
+
+def set_query_batch(servers, msgs, form="wire"):
+    """the queries of all lanes of a batch in one call: msgs[b], a wire message (form="wire": what set_query_wire takes) or a seeded one
+    (form="seeded": what set_query_seeded takes), into servers[b]'s query buffer by one lane-aware launch on servers[0]'s stream; compressed
+    queries are not synchronised.  See include/spiral_gpu.h spiral_gpu_server_set_query_batch"""
+    servers, msgs = list(servers), list(msgs)
+    if form not in MESSAGE_FORMS:
+        raise ValueError(f"set_query_batch: form {form!r}: 'wire' or 'seeded'")
+    if len(msgs) != len(servers):
+        raise ValueError(f"set_query_batch: {len(servers)} servers, {len(msgs)} messages")
+    ws = [None if m is None else wire_bytes(m) for m in msgs]
+    sizes = {w.size for w in ws if w is not None}
+    if len(sizes) > 1:
+        raise ValueError(f"set_query_batch: messages of different sizes {sorted(sizes)}")
+    ptrs = (C.c_void_p * len(ws))(*[None if w is None else w.ctypes.data for w in ws])
+    check(lib().spiral_gpu_server_set_query_batch(_lanes(servers), len(servers), MESSAGE_FORMS[form], ptrs, sizes.pop() if sizes else 0))
+
+
+def read_response_wire_batch(servers) -> np.ndarray:
+    """the wire forms of the last responses of all lanes of a batch in one launch, one copy and one synchronisation: [n][wire bytes] uint8, row b
+    what servers[b].read_response_wire() returns"""
+    servers = list(servers)
+    nb = lib().spiral_gpu_response_wire_bytes(C.byref(servers[0].params), 2) if servers and servers[0] is not None else 0
+    out = np.zeros((len(servers), nb), dtype=np.uint8)
+    check(lib().spiral_gpu_server_read_response_wire_batch(_lanes(servers), len(servers), out.ctypes.data_as(C.c_void_p), out.nbytes))
+    return out
 
 
 def _lanes(servers):
