@@ -112,12 +112,15 @@ struct DevBuf {
 };
 // One allocation holding all per-query buffers of a server in a fixed order, so that two servers with the same parameters have the
 // same internal layout and lane q's buffer X is lane 0's X + (arena_q - arena_0): what lets one launch serve several query lanes
-// (kernels.h Lanes).  Two passes over the same carve sequence: base == nullptr sizes it, then the real base hands out the pieces.
+// (kernels.h Lanes).  Two passes over the same carve sequence: base == nullptr sizes it, then the real base hands out the pieces.  `pieces` records
+// where each piece begins, in carve order: the layout itself, which lanes.h compares before it trusts that constant.
 struct Arena {
     uint64_t* base = nullptr;
     size_t used = 0;
+    std::vector<size_t> pieces;
     uint64_t* take(size_t w) {
         uint64_t* p = base ? base + used : nullptr;
+        pieces.push_back(used);
         used += (w + 31u) & ~(size_t)31u;  // 256-byte pieces
         return p;
     }
@@ -127,14 +130,15 @@ struct Arena {
         b.p = take(b.words);
     }
 };
-// the two passes: `buf` becomes one allocation of the words `layout` takes, and holds the pieces `layout` carves
+// the two passes: `buf` becomes one allocation of the words `layout` takes, and holds the pieces `layout` carves, recorded in `pieces`
 template <class Layout>
-inline int alloc_carved(DevBuf& buf, Layout layout) {
+inline int alloc_carved(DevBuf& buf, std::vector<size_t>& pieces, Layout layout) {
     Arena sizing;
     layout(sizing);
     if (buf.alloc(sizing.used)) return -1;
     Arena real{buf.p};
     layout(real);
+    pieces = std::move(real.pieces);
     return 0;
 }
 

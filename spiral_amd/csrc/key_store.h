@@ -1,8 +1,10 @@
 // The key store (include/spiral_gpu.h, spiral_gpu_key_store_*): a device pool of slots, each holding one client's public parameters already in the PK
-// layout, and what the two servers share of bind_keys -- the checks against the store, the one launch (keys.hip) and the memo of a lane's last bind.
+// layout, and bind_keys of the two servers -- the checks against the store, the one launch (keys.hip) and the memo of a lane's last bind; each server supplies
+// its lane check and its four key buffers.
 // Internal to libspiral_gpu.so.  The parts of a slot are those of the message layout (message.h pub_params_layout / pack_pub_params_layout): nothing
 // here states them again.
 #pragma once
+#include "lanes.h"
 #include "message.h"
 
 struct spiral_gpu_key_store {
@@ -56,6 +58,27 @@ int key_bind_plan(const spiral_gpu_key_store* K, const spiral_gpu_params& p, uin
 int key_bind_launch(spiral_gpu_key_store* K, const KeyBindPlan& plan, uint64_t* const dst[kMessageParts], hipStream_t st);
 // the memo lane plan.lane[k] keeps of it
 KeyMemo key_bind_memo(const spiral_gpu_key_store* K, const KeyBindPlan& plan, uint32_t k);
+
+// bind_keys of either server, behind its lane check (which gave `lanes`): the keys of slot slots[b] into lane b's four key buffers -- dst[i] and
+// dst_words[i]: servers[0]'s buffer of part i and its words -- all lanes in one launch on servers[0]'s stream.  Every check comes before the launch, so a
+// failing call changes nothing; a lane whose memo names the slot's present content is left out of the launch.  Nothing is synchronised.  A server
+// here has `p`, `have_pp` and `key_memo` beside what lanes.h asks of it.
+template <class Srv>
+static int bind_keys(Srv* const* servers, const Lanes& lanes, spiral_gpu_key_store* store, const uint32_t* slots, uint32_t out_n, uint64_t* const dst[kMessageParts],
+              const size_t dst_words[kMessageParts], const char* what) {
+    Srv* S = servers[0];
+    const KeyMemo* memo[kMaxLanes];
+    for (uint32_t b = 0; b < lanes.n; b++) memo[b] = servers[b]->have_pp ? &servers[b]->key_memo : nullptr;
+    KeyBindPlan plan;
+    if (key_bind_plan(store, S->p, out_n, S->device, lanes, slots, memo, dst_words, what, &plan)) return -1;
+    if (plan.lanes.n == 0) return 0;
+    if (lanes_join(servers, lanes.n) || key_bind_launch(store, plan, dst, S->stream) || lanes_release(servers, lanes.n)) return -1;
+    for (uint32_t k = 0; k < plan.lanes.n; k++) {
+        servers[plan.lane[k]]->key_memo = key_bind_memo(store, plan, k);
+        servers[plan.lane[k]]->have_pp = true;
+    }
+    return 0;
+}
 
 }  // namespace host
 }  // namespace spiral

@@ -15,13 +15,11 @@ struct PkBufs {
     size_t acc_words, slot_words, wire_words;  // one instance's words of acc / of res, pk_raw and resp / of wire (whole words: 2048 values per polynomial)
 };
 
-struct spiral_gpu_pack_server {
+struct spiral_gpu_pack_server : LaneHost {  // (lanes.h: device, stream, img, arena and its layout record, ev_lane)
     spiral_gpu_params p;
     spiral_gpu_pack_shape s;
     uint32_t out_n = 0;
     uint32_t t0 = 0, nt = 0;  // this server's trials [t0, t0 + nt) of the out_n^2 (all of them unless created sharded)
-    int device = 0;
-    hipStream_t stream = nullptr;
     bool own_stream = true;
     DeviceTables tb;
     bool have_pp = false;
@@ -31,18 +29,15 @@ struct spiral_gpu_pack_server {
     uint32_t n_cv = 0;
     // every buffer below but the lazy ones (stage, wire_in, item) is a piece of `arena`, carved in one fixed order (pk_layout): servers with equal
     // parameters, out_n and trial range have equal layouts
-    DevBuf arena;
     DevBuf w_left, w_right, v, v_w, query, cv, ex_raw, ex_g, gs_raw, gs_chat, gs_tmp, gsw, key, qs1;  // the client's own
     PkBufs own{};  // what one answer writes
     DevBuf stage;
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
     KeyMemo key_memo;  // the store slot the four key buffers were last bound from (bind_keys); none once set_pub_params* has written them
-    hipEvent_t ev[9] = {};  // [0..6] the stages of an answer, [7] batch sweep / item call end, [8] ordering this server's stream in front of and behind a
-                            // batch or item call that runs on another server's
+    hipEvent_t ev[8] = {};  // [0..6] the stages of an answer, [7] batch sweep / item call end (its stream is ordered around another server's call by ev_lane)
     bool have_records = false;  // qs1 holds the records of a converted query (time_sweep_batch)
-    // the trial images this server sweeps (db_image.h): its own, or its owner's, of which a query lane (create_lane) holds a reference and
+    // img, the trial images this server sweeps (db_image.h): its own, or its owner's, of which a query lane (create_lane) holds a reference and
     // which it never writes
-    DbImage* img = nullptr;
     DevBuf item;            // answer_batch_instances as a client: the arena of its item groups of more than one instance, kept for the next call
     uint32_t item_cap = 0;  // instances per group the arena holds
 };
@@ -96,6 +91,7 @@ void pk_free(spiral_gpu_pack_server* S) {
     S->wire_in.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
+    if (S->ev_lane) (void)hipEventDestroy(S->ev_lane), S->ev_lane = nullptr;
     if (S->stream && S->own_stream) (void)hipStreamDestroy(S->stream);
     S->stream = nullptr;
 }
@@ -145,7 +141,7 @@ int pk_alloc(spiral_gpu_pack_server* S, DbImage* owners) {
     S->img = owners ? owners->share() : DbImage::create(DbLayout::packed1(S->s.num_per, S->s.dim0, S->nt), S);  // (a lane sweeps its owner's images)
     if (!S->img) return -1;
     S->n_cv = S->p.direct_upload ? S->s.n_query_cts : (1u << S->s.g);
-    if (alloc_carved(S->arena, [&](Arena& a) { pk_layout(S, a, true, 1, S->own); })) return -1;
+    if (alloc_carved(S->arena, S->pieces, [&](Arena& a) { pk_layout(S, a, true, 1, S->own); })) return -1;
     HIP_OK(hipMemset(S->cv.p, 0, S->cv.words * sizeof(uint64_t)));
     return 0;
 }
@@ -204,22 +200,6 @@ void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_strid
     fa.lanes = lanes;
     launch_ntt_forward(tb, fa, LD_RAW, ST_PK, trials, st);
     launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st, n_inst, lanes);
-}
-
-// The clients of one call as query lanes (kernels.h Lanes): lane b's arena offset from servers[0]'s, in u64 words -- of either sign, the caller chooses
-// which server comes first.  pk_check_lanes has established equal parameters, out_n and trial range, hence equal layouts (pk_layout); the arenas' sizes
-// and last pieces are compared all the same, because a launch with a wrong offset writes outside its client's memory.
-int pk_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, Lanes* lanes) {
-    const spiral_gpu_pack_server* S = servers[0];
-    *lanes = Lanes{};
-    lanes->n = n;
-    for (uint32_t b = 0; b < n; b++) {
-        const spiral_gpu_pack_server* L = servers[b];
-        if (L->arena.words != S->arena.words || L->own.wire - L->w_left.p != S->own.wire - S->w_left.p || L->w_left.p != L->arena.p)
-            return fail("server %u's buffers are not laid out as server 0's", b);
-        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
-    }
-    return 0;
 }
 
 // the first-dimension sweep of n queries (their records qs[b]) over every trial image of H into accs[b], on `st`: one pass on the matrix cores when
@@ -323,7 +303,7 @@ static int pk_create(const spiral_gpu_params* p, uint32_t out_n, int device, uin
         delete S;
         return fail("twiddle table setup failed on device %d", device);
     }
-    bool ok = hipStreamCreate(&S->stream) == hipSuccess;
+    bool ok = hipStreamCreate(&S->stream) == hipSuccess && hipEventCreateWithFlags(&S->ev_lane, hipEventDisableTiming) == hipSuccess;
     for (auto& e : S->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
     if (!ok || pk_alloc(S, owners)) {
         if (ok == false) fail("stream/event creation failed");
@@ -705,28 +685,20 @@ int spiral_gpu_pack_server_answer_seeded(spiral_gpu_pack_server* S, const void* 
     return pk_answer(S, FORM_SEEDED, query_msg, bytes, response, packed_ct, stage_us, "answer_seeded");
 }
 
-// the lanes of a batch: n in 1 .. kMaxLanes distinct servers that sweep the same images (an owner and its lanes), none trial-sharded, every one
-// with its public parameters (and, want_records, a converted query) -- checked before anything is launched
-// (need_pp false: the call sets them, bind_keys)
-static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, bool want_records, const char* what, bool need_db = true, bool need_pp = true) {
-    if (!servers) return fail("%s: null argument", what);
-    if (n == 0 || n > kMaxLanes) return fail("%s: %u servers, 1 .. %u per batch", what, n, kMaxLanes);
-    for (uint32_t b = 0; b < n; b++)
-        if (!servers[b]) return fail("%s: server %u is null or destroyed", what, b);
-    const spiral_gpu_pack_server* H = servers[0];
-    if (H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
-    if (need_db && !H->img->loaded) return fail("%s: no database loaded", what);
-    for (uint32_t b = 0; b < n; b++) {
-        const spiral_gpu_pack_server* L = servers[b];
-        for (uint32_t c = 0; c < b; c++)
-            if (servers[c] == L) return fail("%s: server %u appears twice", what, b);
-        if (L->img != H->img) return fail("%s: server %u does not sweep server 0's database image (create_lane)", what, b);
+// the lanes of a batch, checked before anything is launched, and their arena offsets: the list, the image, NO_CAPTURE and the layouts in lanes.h,
+// between them SpiralPack's own rules -- none trial-sharded, the same parameters, out_n and trial range, and what `needs` names (NEED_DB,
+// NEED_RECORDS; public parameters unless the call GIVES_KEYS)
+static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, const char* what, uint32_t needs, Lanes* lanes) {
+    return check_lane_list(servers, n, what, needs, lanes, [&](uint32_t b) {
+        const spiral_gpu_pack_server *H = servers[0], *L = servers[b];
+        if (H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
+        if ((needs & NEED_DB) && !H->img->loaded) return fail("%s: no database loaded", what);
         if (memcmp(&L->p, &H->p, sizeof(L->p)) != 0 || L->out_n != H->out_n || L->device != H->device || L->nt != H->nt)
             return fail("%s: server %u has other parameters than server 0", what, b);
-        if (need_pp && !L->have_pp) return fail("%s: server %u has no public parameters", what, b);
-        if (want_records && !L->have_records) return fail("%s: server %u has no converted query (answer it once first)", what, b);
-    }
-    return 0;
+        if (!(needs & GIVES_KEYS) && !L->have_pp) return fail("%s: server %u has no public parameters", what, b);
+        if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has no converted query (answer it once first)", what, b);
+        return 0;
+    });
 }
 
 // The queries of a multi-lane call, one per server.  Every argument (in the message forms each query's byte count included) is checked before anything
@@ -748,54 +720,15 @@ static int pk_take_queries(spiral_gpu_pack_server* const* servers, uint32_t n, F
     return 0;
 }
 
-// what lanes 1 .. n - 1 of a call on servers[0]'s stream still have on streams of their own comes before it (the way lanes_join / lanes_release of
-// server.cpp do it; a lane on servers[0]'s stream is ordered by it) ...
-static int pk_lanes_join(spiral_gpu_pack_server* const* servers, uint32_t n) {
-    spiral_gpu_pack_server* S = servers[0];
-    for (uint32_t b = 1; b < n; b++) {
-        if (servers[b]->stream == S->stream) continue;
-        HIP_OK(hipEventRecord(servers[b]->ev[8], servers[b]->stream));
-        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev[8], 0));
-    }
-    return 0;
-}
-// ... and what follows on their streams comes after it (event 8 of servers[0], which no join records: servers[0] is never joined to itself)
-static int pk_lanes_release(spiral_gpu_pack_server* const* servers, uint32_t n) {
-    spiral_gpu_pack_server* S = servers[0];
-    bool other = false;
-    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
-    if (other) HIP_OK(hipEventRecord(S->ev[8], S->stream));
-    for (uint32_t b = 1; b < n; b++)
-        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev[8], 0));
-    return 0;
-}
-// spiral_gpu_server_bind_keys for SpiralPack: the keys of slot slots[b] of a store created for this out_n into lane b's W_exp_left, W_exp_right, V and v_W,
-// all lanes in one launch on servers[0]'s stream.  Checked before anything is launched; nothing is synchronised.
+// spiral_gpu_server_bind_keys for SpiralPack: the keys of slot slots[b] of a store created for this out_n into lane b's W_exp_left, W_exp_right, V and v_W
 int spiral_gpu_pack_server_bind_keys(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_key_store* store, const uint32_t* slots) {
     const char* what = "pack bind_keys";
-    if (pk_check_lanes(servers, n, false, what, false, false)) return -1;
-    spiral_gpu_pack_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
     Lanes lanes;
-    if (pk_lanes(servers, n, &lanes)) return -1;
-    const KeyMemo* memo[kMaxLanes];
-    for (uint32_t b = 0; b < n; b++) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        HIP_OK(hipStreamIsCapturing(servers[b]->stream, &cs));
-        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
-        memo[b] = servers[b]->have_pp ? &servers[b]->key_memo : nullptr;
-    }
+    if (pk_check_lanes(servers, n, what, NO_CAPTURE | GIVES_KEYS, &lanes)) return -1;
+    spiral_gpu_pack_server* S = servers[0];
     uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->v.p, S->v_w.p};
     const size_t dst_words[kMessageParts] = {S->w_left.words, S->w_right.words, S->v.words, S->v_w.words};
-    KeyBindPlan plan;
-    if (key_bind_plan(store, S->p, S->out_n, S->device, lanes, slots, memo, dst_words, what, &plan)) return -1;
-    if (plan.lanes.n == 0) return 0;
-    if (pk_lanes_join(servers, n) || key_bind_launch(store, plan, dst, S->stream) || pk_lanes_release(servers, n)) return -1;
-    for (uint32_t k = 0; k < plan.lanes.n; k++) {
-        servers[plan.lane[k]]->key_memo = key_bind_memo(store, plan, k);
-        servers[plan.lane[k]]->have_pp = true;
-    }
-    return 0;
+    return bind_keys(servers, lanes, store, slots, S->out_n, dst, dst_words, what);
 }
 
 // whether a call of n clients runs as one lane-aware launch sequence (option pack_batch_lanes, read per call; 0 = never)
@@ -808,20 +741,18 @@ static bool pk_lane_form(uint32_t n) { return n >= 2 && options().pack_batch_lan
 // flags end up as its own answer would leave them.  Returns synchronised.
 static int pk_answer_batch(spiral_gpu_pack_server* const* servers, uint32_t n, Form form, const void* const* queries, size_t bytes_each,
                            uint64_t* const* responses, uint64_t* const* packed_cts, double stage_us[8], const char* what) {
-    if (pk_check_lanes(servers, n, false, what) || pk_take_queries(servers, n, form, queries, bytes_each, what)) return -1;
+    Lanes lanes;
+    if (pk_check_lanes(servers, n, what, NEED_DB, &lanes) || pk_take_queries(servers, n, form, queries, bytes_each, what)) return -1;
     if (n == 1) return pk_answer_taken(servers[0], responses ? responses[0] : nullptr, packed_cts ? packed_cts[0] : nullptr, stage_us);
     spiral_gpu_pack_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
-    Lanes lanes;
-    if (pk_lanes(servers, n, &lanes)) return -1;
     if (S->img->lay.limbs_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     hipStream_t st = S->stream;
     const bool lane_form = pk_lane_form(n);
     if (lane_form) {
-        if (pk_lanes_join(servers, n)) return -1;  // (the queries were taken on the lanes' own streams)
+        if (lanes_join(servers, n)) return -1;  // (the queries were taken on the lanes' own streams)
         if (pk_expand_convert(S, lanes, st) || pk_sweep(S, lanes, st)) return -1;
         HIP_OK(hipEventRecord(S->ev[7], st));  // (the sweep began at event 2)
-        if (pk_fold(S, lanes, st) || pk_back(S, S->own.raw, S->s.num_per, lanes, st) || pk_lanes_release(servers, n)) return -1;
+        if (pk_fold(S, lanes, st) || pk_back(S, S->own.raw, S->s.num_per, lanes, st) || lanes_release(servers, n)) return -1;
         for (uint32_t b = 1; b < n; b++)  // (what the pieces set on servers[0]; the stages' events are servers[0]'s alone)
             servers[b]->have_records = true, servers[b]->packed_after_front = true, servers[b]->events_elsewhere = true;
         g_pack_lane_batches++;
@@ -888,12 +819,11 @@ int spiral_gpu_pack_server_answer_batch_seeded(spiral_gpu_pack_server* const* se
 // ---- items of several database instances (answer_batch_instances, include/spiral_gpu.h) ----
 // every argument check, before anything is uploaded or launched; what the clients' own image holds does not matter (it is read only as an instance)
 static int pk_check_items(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_pack_server* const* instances, uint32_t n_inst, const void* queries,
-                          const void* responses, const void* wire, const char* what) {
+                          const void* responses, const void* wire, const char* what, Lanes* lanes) {
     if (!servers || !instances || !queries) return fail("%s: null servers, instances or queries", what);
-    if (n == 0 || n > kMaxLanes) return fail("%s: %u clients, 1 .. %u per call", what, n, kMaxLanes);
     if (n_inst == 0) return fail("%s: no instances", what);
     if (!responses && !wire) return fail("%s: no output (responses or wire)", what);
-    if (pk_check_lanes(servers, n, false, what, false)) return -1;
+    if (pk_check_lanes(servers, n, what, 0, lanes)) return -1;
     const spiral_gpu_pack_server* S = servers[0];
     for (uint32_t k = 0; k < n_inst; k++) {
         const spiral_gpu_pack_server* I = instances[k];
@@ -970,21 +900,15 @@ static int pk_item_back(spiral_gpu_pack_server* L, const PkBufs& B, uint32_t g, 
 // the item call: every argument checked, then every query taken; the launches run only when all of them were
 static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_pack_server* const* instances, uint32_t n_inst, Form form,
                            const void* const* queries, size_t bytes_each, uint64_t* responses, void* wire, double* total_us, const char* what) {
-    if (pk_check_items(servers, n, instances, n_inst, queries, responses, wire, what) || pk_take_queries(servers, n, form, queries, bytes_each, what)) return -1;
+    Lanes lanes;
+    if (pk_check_items(servers, n, instances, n_inst, queries, responses, wire, what, &lanes) || pk_take_queries(servers, n, form, queries, bytes_each, what))
+        return -1;
     spiral_gpu_pack_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
     hipStream_t st = S->stream;
     // whatever the clients' and the instances' streams hold (an update_db_items on an instance's holder) comes first
-    auto join = [&](spiral_gpu_pack_server* X) -> int {
-        if (X->stream == st) return 0;
-        HIP_OK(hipEventRecord(X->ev[8], X->stream));
-        HIP_OK(hipStreamWaitEvent(st, X->ev[8], 0));
-        return 0;
-    };
-    for (uint32_t b = 1; b < n; b++)
-        if (join(servers[b])) return -1;
+    if (lanes_join(servers, n)) return -1;
     for (uint32_t k = 0; k < n_inst; k++)
-        if (join(instances[k]) || (pk_owner(instances[k]) && join(pk_owner(instances[k])))) return -1;  // (no owner left: nothing writes the image)
+        if (stream_before(instances[k], st) || (pk_owner(instances[k]) && stream_before(pk_owner(instances[k]), st))) return -1;  // (no owner left: nothing writes the image)
     // a batch sweeps each instance image on the matrix cores where the geometry has limb planes: converted in place on first use, as answer_batch's holder
     if (n >= 2 && DbLayout::packed1(S->s.num_per, S->s.dim0, S->s.trials).limbs_ok())
         for (uint32_t k = 0; k < n_inst; k++)
@@ -997,8 +921,6 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
         if (G > 1) pk_layout(servers[b], a, false, G, bufs[b]);
     }
     const size_t slot_words = bufs[0].slot_words, wire_b = bufs[0].wire_words * 8;
-    Lanes lanes;
-    if (pk_lanes(servers, n, &lanes)) return -1;
     const uint32_t* qs[kMaxLanes];
     pk_lane_records(S, lanes, qs);
     // expansion and conversion, once per client whatever the number of instances: one lane-aware sequence from option pack_batch_lanes clients on.  (The
@@ -1028,12 +950,9 @@ static int pk_answer_items(spiral_gpu_pack_server* const* servers, uint32_t n, s
     }
     HIP_OK(hipEventRecord(S->ev[7], st));
     for (uint32_t b = 1; b < n; b++)  // and what follows on the other streams comes after
-        if (servers[b]->stream != st) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev[7], 0));
-    for (uint32_t k = 0; k < n_inst; k++) {
-        spiral_gpu_pack_server* I = instances[k];
-        if (I->stream != st) HIP_OK(hipStreamWaitEvent(I->stream, S->ev[7], 0));
-        if (pk_owner(I) && pk_owner(I)->stream != st) HIP_OK(hipStreamWaitEvent(pk_owner(I)->stream, S->ev[7], 0));
-    }
+        if (stream_after(servers[b], st, S->ev[7])) return -1;
+    for (uint32_t k = 0; k < n_inst; k++)
+        if (stream_after(instances[k], st, S->ev[7]) || (pk_owner(instances[k]) && stream_after(pk_owner(instances[k]), st, S->ev[7]))) return -1;
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     if (total_us) {
@@ -1066,11 +985,9 @@ int spiral_gpu_pack_server_answer_batch_instances_seeded(spiral_gpu_pack_server*
 // events; as answer_batch, a covered geometry's image is converted to limb planes first
 int spiral_gpu_pack_server_time_sweep_batch(spiral_gpu_pack_server* const* servers, uint32_t n, int iters, float* avg_ms) {
     if (!avg_ms || iters <= 0) return fail("time_sweep_batch: bad argument");
-    if (pk_check_lanes(servers, n, true, "time_sweep_batch")) return -1;
-    spiral_gpu_pack_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
     Lanes lanes;
-    if (pk_lanes(servers, n, &lanes)) return -1;
+    if (pk_check_lanes(servers, n, "time_sweep_batch", NEED_DB | NEED_RECORDS, &lanes)) return -1;
+    spiral_gpu_pack_server* S = servers[0];
     if (S->img->lay.limbs_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, S->stream)) return -1;
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipEventRecord(S->ev[0], S->stream));

@@ -65,26 +65,23 @@ struct Captured {
     std::vector<uint64_t> key;
 };
 
-struct spiral_gpu_server {
+struct spiral_gpu_server : LaneHost {  // (lanes.h: device, stream, img, arena and its layout record, ev_lane)
     spiral_gpu_params p;
     spiral_gpu_shape s;
-    int device = 0;
     uint32_t j0 = 0, j1 = 0, dim0_shard = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipStream_t own_stream = nullptr;
     DeviceTables tb;
     bool keep_cts = false, have_pp = false, have_query = false;
     bool raw_from_acc = false;  // S->raw holds the lift of what S->acc holds now (lift ran, no sweep / write_raw / fold since): the stage fold may use the pair form
     bool have_records = false;  // the sweep's query records of the current query have been enqueued (ScalToMat ran since set_query)
     DevBuf wire;  // bit-packed response (read_response_wire)
-    // the database image this server sweeps (db_image.h): its own, or its owner's, of which it holds a reference (create_lane, share_db) and
+    // img, the database image this server sweeps (db_image.h): its own, or its owner's, of which it holds a reference (create_lane, share_db) and
     // which it never writes
-    DbImage* img = nullptr;
     // expanded-ciphertext positions inside cv: first-dim j at j*pos_stride + pos_first, rest i at i*pos_stride + pos_rest
     uint32_t pos_stride = 1, pos_first = 0, pos_rest = 0, n_cv = 0;
 
     // every per-query buffer below except the lazily allocated ones (ex_raw2, ex_g2, cts_keep, stage, wire) is a piece of `arena`, carved in one
-    // fixed order (srv_alloc): servers with equal parameters and shard have equal layouts, which is what run_query_batch relies on
-    DevBuf arena;
+    // fixed order (srv_alloc): servers with equal parameters and shard have equal layouts, which is what every multi-lane call relies on (lanes.h)
     DevBuf w_left, w_right, w, v, query, cv, ex_raw, ex_g, ex_raw2, ex_g2;  // (the second work set: the odd tree of a split expansion)
     DevBuf cv_raw, cv_g, key, cts_keep;  // key: [d][3][m2]: the GSW matrices Q (src/spiral.cpp:2324) -- the fold key; Q_neg = G2 - Q (:2361-2379) is never stored (poly.hip fold_mac_two_kernel)
     uint64_t *gs_raw_p = nullptr, *gs_chat_p = nullptr;  // the Regev->GSW halves of cv_raw / cv_g
@@ -105,7 +102,6 @@ struct spiral_gpu_server {
     bool side_pending = false;
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_batch = nullptr;  // first_dim_batch: this lane's records are ready / the shared sweep is done
     // Fold round forms.  Default: the pair form, unchained (lift launch + LD_SDIFF digit-difference launch + product with addend).
     // fold_pair = false (SPIRAL_FOLD_PAIR=0) or a gadget dimension whose digits do not recompose (!fold_pair_exact): the reference's
     // two-product form, lift chained into the digit transforms (fold_chain_kernel: a block lifts one source polynomial and transforms
@@ -169,7 +165,7 @@ int srv_alloc(spiral_gpu_server* S, DbImage* owners) {
         a.carve(S->fold_c2, half * 6 * kN);
         a.carve(S->resp, (size_t)6 * kN);
     };
-    if (alloc_carved(S->arena, layout)) return -1;
+    if (alloc_carved(S->arena, S->pieces, layout)) return -1;
     HIP_OK(hipMemset(S->cv.p, 0, S->cv.words * sizeof(uint64_t)));
     S->gs_raw_p = S->cv_raw.p + (size_t)S->dim0_shard * kN;
     S->gs_chat_p = S->cv_g.p + (size_t)S->dim0_shard * p.t_conv * kN;
@@ -194,11 +190,11 @@ void srv_free(spiral_gpu_server* S) {
         if (e) (void)hipEventDestroy(e);
     if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
     if (S->ev_join) (void)hipEventDestroy(S->ev_join);
-    if (S->ev_batch) (void)hipEventDestroy(S->ev_batch);
+    if (S->ev_lane) (void)hipEventDestroy(S->ev_lane);
     if (S->side_stream) (void)hipStreamDestroy(S->side_stream);
     if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
     S->side_stream = S->own_stream = nullptr;
-    S->ev_fork = S->ev_join = S->ev_batch = nullptr;
+    S->ev_fork = S->ev_join = S->ev_lane = nullptr;
     for (auto& e : S->ev) e = nullptr;
 }
 
@@ -273,40 +269,19 @@ int srv_join_side(spiral_gpu_server* S) {
 }
 
 // ---- calls that carry the queries of several servers (lanes): an owner and its lanes (create_lane / share_db) ----------------------------------------
-// What such a call needs of its lanes beyond sweeping one image, none listed twice (check_lanes)
-enum LaneNeeds : uint32_t {
-    NEED_QUERY = 1,     // each has its query set
-    NEED_DB = 2,        // each has a database
-    NEED_RECORDS = 4,   // each has converted its query (the sweep's records are enqueued)
-    SHARDED = 8,        // the same fold ranks and expansion shard (a batch of a sharded answer), else neither and their own accumulators
-    NO_CAPTURE = 16,    // no lane's stream is capturing
-    SWEEP_ONLY = 32,    // they share the sweep only (first_dim_batch): the image's layout must agree, not parameters or schedules
-    GIVES_KEYS = 64,    // the call sets the public parameters (bind_keys): they need not be set
-    MOVES_DATA = 128,   // the call only moves messages in or responses out (set_query_batch, read_response_wire_batch): it depends on no query, no
-                        // public parameters and no schedule, so lanes of a sharded batch and lanes with other schedules are taken too
-    SHARD_LANES = SHARDED | NO_CAPTURE,
-};
-
-// Checks the lanes servers[0 .. n) of one call -- before anything is dereferenced the list (1 .. kMaxLanes servers, none null), then each lane against
-// servers[0] -- and fills their arena offsets.  Unless SWEEP_ONLY: the same parameters, device and shard, public parameters set, the default schedule.
+// Checks the lanes servers[0 .. n) of one call and fills their arena offsets: the list, the image, NO_CAPTURE and the layouts in lanes.h, between them
+// the base server's own rules for each lane against servers[0].  Unless SWEEP_ONLY: the same parameters and shard, public parameters set, the default
+// schedule.
 int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, uint32_t needs, Lanes* lanes) {
-    if (!servers || n == 0) return fail("%s: no servers", what);
-    if (n > kMaxLanes) return fail("%s: at most %u clients per batch", what, kMaxLanes);
-    for (uint32_t b = 0; b < n; b++)
-        if (!servers[b]) return fail("%s: null server %u", what, b);
-    spiral_gpu_server* S = servers[0];
-    HIP_OK(hipSetDevice(S->device));
     const bool whole = !(needs & SWEEP_ONLY), sharded = needs & SHARDED, moves = needs & MOVES_DATA;
-    lanes->n = n;
-    for (uint32_t b = 0; b < n; b++) {
-        spiral_gpu_server* L = servers[b];
+    return check_lane_list(servers, n, what, needs, lanes, [&](uint32_t b) {
+        const spiral_gpu_server *S = servers[0], *L = servers[b];
         if (whole && (((needs & NEED_QUERY) && !L->have_query) || (!L->have_pp && !(needs & (GIVES_KEYS | MOVES_DATA))))) return fail("%s: server %u needs its query and public parameters set first", what, b);
         if ((needs & NEED_DB) && !L->img->loaded) return fail("%s: server %u has no database", what, b);
         if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has not converted its query (run_pre first)", what, b);
         if (L->device != S->device || L->dim0_shard != S->dim0_shard || L->s.num_per != S->s.num_per ||
-            (whole && (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->j0 != S->j0 || L->j1 != S->j1 || L->cv.words != S->cv.words)))
+            (whole && (memcmp(&L->p, &S->p, sizeof(S->p)) != 0 || L->j0 != S->j0 || L->j1 != S->j1)))
             return fail("%s: server %u differs from server 0 in parameters, device or shard", what, b);
-        if (L->img != S->img) return fail("%s: server %u does not sweep server 0's database image (create_lane / share_db)", what, b);
         if ((sharded || !whole) && L->fold_g_log != S->fold_g_log)
             return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
         if (sharded && (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank))
@@ -315,35 +290,8 @@ int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what,
             return fail("%s: server %u has an external accumulator, fold ranks or a sharded expansion set", what, b);
         if (!moves && (L->sweep_k_log || (whole && (L->keep_cts || L->overlap || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain))))
             return fail("%s: server %u has keep_cts, a split or staged schedule or other fold options set", what, b);
-        for (uint32_t c = 0; c < b; c++)
-            if (servers[c] == L) return fail("%s: server %u listed twice", what, b);
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (needs & NO_CAPTURE) HIP_OK(hipStreamIsCapturing(L->stream, &cs));
-        if (cs != hipStreamCaptureStatusNone) return fail("%s: server %u's stream is capturing (call it outside stream capture)", what, b);
-        lanes->off[b] = L->w_left.p - S->w_left.p;  // (the first piece of the arena)
-    }
-    return 0;
-}
-
-// the lanes' uploads (and whatever else their streams still hold) come before the sequence on servers[0]'s stream, and what follows on their streams
-// after it.  (Lanes on the sequence's own stream are ordered by it: the cheapest arrangement, each other stream costs ~20 us per batch.)
-int lanes_join(spiral_gpu_server* const* servers, uint32_t n) {
-    spiral_gpu_server* S = servers[0];
-    for (uint32_t b = 1; b < n; b++) {
-        if (servers[b]->stream == S->stream) continue;
-        HIP_OK(hipEventRecord(servers[b]->ev_batch, servers[b]->stream));
-        HIP_OK(hipStreamWaitEvent(S->stream, servers[b]->ev_batch, 0));
-    }
-    return 0;
-}
-int lanes_release(spiral_gpu_server* const* servers, uint32_t n) {
-    spiral_gpu_server* S = servers[0];
-    bool other = false;
-    for (uint32_t b = 1; b < n; b++) other |= servers[b]->stream != S->stream;
-    if (other) HIP_OK(hipEventRecord(S->ev_batch, S->stream));
-    for (uint32_t b = 1; b < n; b++)
-        if (servers[b]->stream != S->stream) HIP_OK(hipStreamWaitEvent(servers[b]->stream, S->ev_batch, 0));
-    return 0;
+        return 0;
+    });
 }
 
 // what a sweep or fold of servers[0 .. n) leaves: their accumulators or raw buffers overwritten (S->raw no longer the lift of S->acc)
@@ -926,7 +874,7 @@ static int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, 
     if (hipStreamCreateWithFlags(&S->side_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&S->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&S->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&S->ev_batch, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&S->ev_lane, hipEventDisableTiming) != hipSuccess) {
         srv_free(S);
         delete S;
         return fail("side stream setup failed");
@@ -1204,25 +1152,9 @@ int spiral_gpu_server_bind_keys(spiral_gpu_server* const* servers, uint32_t n, s
     Lanes lanes;
     if (check_lanes(servers, n, what, NO_CAPTURE | GIVES_KEYS, &lanes)) return -1;
     spiral_gpu_server* S = servers[0];
-    const KeyMemo* memo[kMaxLanes];
-    for (uint32_t b = 0; b < n; b++) {
-        const spiral_gpu_server* L = servers[b];
-        if (L->arena.words != S->arena.words || L->w_left.p != L->arena.p || L->w_right.p - L->w_left.p != S->w_right.p - S->w_left.p ||
-            L->w.p - L->w_left.p != S->w.p - S->w_left.p || L->v.p - L->w_left.p != S->v.p - S->w_left.p)
-            return fail("%s: server %u's buffers are not laid out as server 0's", what, b);
-        memo[b] = L->have_pp ? &L->key_memo : nullptr;
-    }
     uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->w.p, S->v.p};
     const size_t dst_words[kMessageParts] = {S->w_left.words, S->w_right.words, S->w.words, S->v.words};
-    KeyBindPlan plan;
-    if (key_bind_plan(store, S->p, 0, S->device, lanes, slots, memo, dst_words, what, &plan)) return -1;
-    if (plan.lanes.n == 0) return 0;
-    if (lanes_join(servers, n) || key_bind_launch(store, plan, dst, S->stream) || lanes_release(servers, n)) return -1;
-    for (uint32_t k = 0; k < plan.lanes.n; k++) {
-        servers[plan.lane[k]]->key_memo = key_bind_memo(store, plan, k);
-        servers[plan.lane[k]]->have_pp = true;
-    }
-    return 0;
+    return bind_keys(servers, lanes, store, slots, 0, dst, dst_words, what);
 }
 
 // The queries of the n lanes of a batch in one call: message b (wire or seeded form, pageable memory) into servers[b]'s query buffer, through ONE
@@ -1248,12 +1180,8 @@ int spiral_gpu_server_set_query_batch(spiral_gpu_server* const* servers, uint32_
         return fail("%s: %zu bytes per message, the %s form of this query takes %zu", what, bytes_each, seeded ? "seeded" : "wire", want);
     if (seeded && part.rows < 2) return fail("%s: the query is not a run of matrices with rows >= 2", what);
     if (!msgs) return fail("%s: null message list", what);
-    for (uint32_t b = 0; b < n; b++) {
+    for (uint32_t b = 0; b < n; b++)
         if (!msgs[b]) return fail("%s: null message %u", what, b);
-        const spiral_gpu_server* L = servers[b];
-        if (L->arena.words != S->arena.words || L->w_left.p != L->arena.p || L->query.p - L->w_left.p != S->query.p - S->w_left.p)
-            return fail("%s: server %u's buffers are not laid out as server 0's", what, b);
-    }
     // the error word's index names (lane, message polynomial, coefficient)
     if ((uint64_t)n * npolys * kN >= 0xffffffffull) return fail("%s: %u messages of %zu polynomials exceed the coefficient index range", what, n, npolys);
     if (npolys == 0) return 0;
@@ -1362,8 +1290,6 @@ int spiral_gpu_server_read_response_wire_batch(spiral_gpu_server* const* servers
     if (!out) return fail("%s: null output buffer", what);
     const size_t nbytes = wire_bytes(&S->p, 2);
     if (capacity < n * nbytes) return fail("%s: response buffer of %zu bytes, the wire forms of %u lanes need %zu", what, capacity, n, n * nbytes);
-    for (uint32_t b = 0; b < n; b++)
-        if (servers[b]->resp.p - servers[b]->w_left.p != S->resp.p - S->w_left.p) return fail("%s: server %u's buffers are not laid out as server 0's", what, b);
     if (S->wire.words * 8 < n * nbytes && (S->wire.release(), S->wire.alloc(n * nbytes / 8))) return -1;
     if (lanes_join(servers, n)) return -1;
     launch_response_wire(S->resp.p, S->wire.p, 2 * kN, S->p.qprime_bits, 4 * kN, wire_bits_rest(&S->p), S->stream, lanes, 0, (int64_t)(nbytes / 8));

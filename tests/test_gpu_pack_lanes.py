@@ -279,3 +279,53 @@ def test_items_convert_in_lane_form(sa, P, oracle, group):
             sa.set_option(k, v)
         for srv in servers[1:] + probes + instances:
             srv.close()
+
+
+@pytest.mark.parametrize("geom", [G_SMALL, G_UNCOVERED], ids=["small", "uncovered"])
+def test_mixed_streams(sa, P, oracle_mt, geom):
+    """three clients, the owner and lane 1 on one caller-made stream and lane 2 on its own: the join and release of every multi-lane call skip the
+    lanes that share servers[0]'s stream and order the other.  The batch per lane and in lane form, an item call on one instance and a lane-form
+    batch behind one bind_keys of all three lanes leave every lane's response, packed ciphertext, wire form and accumulators as its own single
+    answer does; at the covered geometry the responses are the oracle's too"""
+    import torch
+
+    st = Setup(sa, oracle_mt, geom, 3, salt=5)
+    stream = torch.cuda.Stream()  # (outlives the servers: set_stream does not give a server's own stream back)
+    store = None
+    before = sa.get_option("pack_batch_lanes")
+    try:
+        for srv in st.servers[:2]:
+            srv.set_stream(stream.cuda_stream)
+        trials = st.s.trials
+        singles = [single_of(srv, q, trials) for srv, q in zip(st.servers, st.qs)]
+        states = both_forms(sa, P, st)
+        for b in range(3):
+            assert_state_eq(states[b], singles[b], f"lane {b}: batch vs its single answer")
+        if geom is G_SMALL:
+            assert_oracle(st, states)
+        sa.set_option("pack_batch_lanes", 2)
+        counted = sa.get_option("pack_lane_batches")
+        resp, wire = P.answer_batch_instances(st.servers, st.servers[:1], st.qs, wire=True)
+        assert sa.get_option("pack_lane_batches") - counted == 1
+        for b in range(3):
+            assert_eq(resp[b, 0], singles[b][0], f"item call, client {b}: response vs its single answer")
+            assert_eq(wire[b, 0], singles[b][2], f"item call, client {b}: wire form vs its single answer's")
+        # lane b now serves client (b + 1) % 3: one bind of all three lanes, then a lane-form batch of those clients' queries
+        store = sa.KeyStore(st.pg, 3, out_n=st.out_n, form="full")
+        for c, cl in enumerate(st.clients):
+            store.put(c, *cl.pp)
+        slots = [1, 2, 0]
+        P.bind_keys(st.servers, store, slots)
+        bound = Setup.__new__(Setup)
+        bound.__dict__.update(st.__dict__)
+        bound.clients, bound.idx, bound.qs = ([x[c] for c in slots] for x in (st.clients, st.idx, st.qs))
+        got, _ = batch_with(sa, P, 2, bound.servers, bound.qs, trials, 1)
+        for b in range(3):
+            assert_state_eq(got[b], single_of(bound.servers[b], bound.qs[b], trials), f"behind bind_keys, lane {b}: batch vs its single answer")
+        if geom is G_SMALL:
+            assert_oracle(bound, got)
+    finally:
+        sa.set_option("pack_batch_lanes", before)
+        if store:
+            store.close()
+        st.close()

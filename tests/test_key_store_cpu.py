@@ -105,7 +105,7 @@ def test_bad_parameters_refused_without_a_device(sa):
     assert L.spiral_gpu_key_store_has(None, 0) == 0
     L.spiral_gpu_key_store_destroy(None)
     assert L.spiral_gpu_server_bind_keys(None, 1, None, None) != 0 and "no servers" in L.spiral_gpu_last_error().decode()
-    assert L.spiral_gpu_pack_server_bind_keys(None, 1, None, None) != 0 and "null" in L.spiral_gpu_last_error().decode()
+    assert L.spiral_gpu_pack_server_bind_keys(None, 1, None, None) != 0 and "no servers" in L.spiral_gpu_last_error().decode()
 
 
 def test_cli_parses_key_store(sa):

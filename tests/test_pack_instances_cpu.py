@@ -93,15 +93,15 @@ def test_checks_without_a_device(sa):
     assert "null" in _call(L, None, 1, ins, 1, qs, outp, None)
     assert "null" in _call(L, hs, 1, None, 1, qs, outp, None)
     assert "null" in _call(L, hs, 1, ins, 1, None, outp, None)
-    assert "1 .. 8" in _call(L, hs, 0, ins, 1, qs, outp, None)
-    assert "1 .. 8" in _call(L, hs, 9, ins, 1, qs, outp, None)
+    assert "no servers" in _call(L, hs, 0, ins, 1, qs, outp, None)
+    assert "at most 8 clients" in _call(L, hs, 9, ins, 1, qs, outp, None)
     assert "no instances" in _call(L, hs, 1, ins, 0, qs, outp, None)
     assert "no output" in _call(L, hs, 1, ins, 1, qs, None, None)
-    assert "null or destroyed" in _call(L, hs, 1, ins, 1, qs, outp, None)  # a null client handle
+    assert "null server 0" in _call(L, hs, 1, ins, 1, qs, outp, None)  # a null client handle
     wq = (C.c_void_p * 9)(*([qbuf.ctypes.data] * 9))
     assert "null" in _call_wire(L, None, 1, ins, 1, wq, 64, outp, None)
     assert "null" in _call_wire(L, hs, 1, ins, 1, None, 64, outp, None)
-    assert "1 .. 8" in _call_wire(L, hs, 9, ins, 1, wq, 64, outp, None)
+    assert "at most 8 clients" in _call_wire(L, hs, 9, ins, 1, wq, 64, outp, None)
     assert "no instances" in _call_wire(L, hs, 1, ins, 0, wq, 64, outp, None)
     assert "no output" in _call_wire(L, hs, 1, ins, 1, wq, 64, None, None)
     assert out.sum() == 0
