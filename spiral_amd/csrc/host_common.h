@@ -1,4 +1,4 @@
-// Host-side helpers shared by server.cpp and pack_server.cpp (error reporting, device buffers, the
+// Host-side helpers shared by the host units of both servers (error reporting, device buffers, the
 // coefficient-expansion driver).  Internal to libspiral_gpu.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,7 +21,7 @@ namespace spiral {
 namespace host {
 
 extern thread_local std::string g_err;
-extern std::atomic<uint64_t> g_pack_lane_batches;  // server.cpp: what get_option("pack_lane_batches") reads
+extern std::atomic<uint64_t> g_pack_lane_batches;  // primitives.cpp: what get_option("pack_lane_batches") reads
 
 inline int fail(const char* fmt, ...) {
     char buf[512];

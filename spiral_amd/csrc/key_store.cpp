@@ -1,5 +1,5 @@
 // The key store of include/spiral_gpu.h: client keys resident on the device in the PK layout, ingested once per client through the one ingest of
-// message.h, and the store's share of bind_keys (key_store.h; the servers' shares are in server.cpp and pack_server.cpp, the kernel in keys.hip).
+// message.h, and the store's share of bind_keys (key_store.h; the servers' shares are in server_lanes.cpp and pack_server.cpp, the kernel in keys.hip).
 #include "key_store.h"
 
 using namespace spiral;

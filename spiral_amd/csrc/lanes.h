@@ -1,4 +1,4 @@
-// The lane set of a multi-server call, shared by server.cpp and pack_server.cpp.  Such a call takes a list of servers -- one owner and its lanes
+// The lane set of a multi-server call, shared by server_lanes.cpp and pack_server.cpp.  Such a call takes a list of servers -- one owner and its lanes
 // (create_lane / share_db) -- and runs ONE launch sequence on servers[0]'s stream that carries all of them in gridDim.z (kernels.h Lanes).  Three
 // things hold before its first launch, each established here and nowhere else: the list is well formed and sweeps one image (check_lane_list), every
 // lane's arena is laid out as servers[0]'s, so that one word offset per lane is valid for every buffer (lanes_layout), and the lanes' own streams are
@@ -19,7 +19,14 @@ struct LaneHost {
     hipEvent_t ev_lane = nullptr;  // orders this server's stream around a call on another server's; nothing else records it, it is never timed
 };
 
-// What a call needs of its lanes beyond the list check.  Each server's own check reads the bits it knows (server.cpp check_lanes, pack_server.cpp
+// How an entry point on one server opens: a null handle is refused, the server's device is made current
+static inline int enter(const LaneHost* S) {
+    if (!S) return fail("null server");
+    HIP_OK(hipSetDevice(S->device));
+    return 0;
+}
+
+// What a call needs of its lanes beyond the list check.  Each server's own check reads the bits it knows (server_lanes.cpp check_lanes, pack_server.cpp
 // pk_check_lanes); NO_CAPTURE and SWEEP_ONLY are read here.
 enum LaneNeeds : uint32_t {
     NEED_QUERY = 1,     // each has its query set

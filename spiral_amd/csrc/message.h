@@ -194,7 +194,7 @@ inline int ingest_message(WireIn& W, const DeviceTables& tb, hipStream_t st, con
     return 0;
 }
 
-// The workspace of the batch ingest (server.cpp spiral_gpu_server_set_query_batch), owned by the batch's servers[0] and used on its stream only:
+// The workspace of the batch ingest (server_lanes.cpp spiral_gpu_server_set_query_batch), owned by the batch's servers[0] and used on its stream only:
 // the device staging [u64 error word, padded to 256 bytes][lane][head + chunk polynomials], the generation of the error word as WireIn's, and for
 // messages small enough to check on the host a ring of two pinned slots laid out as the staging, each with the event recorded behind the launch
 // that read it -- a call waits for that event before it fills the slot again, never for the stream.

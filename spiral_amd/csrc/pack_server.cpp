@@ -149,8 +149,7 @@ int pk_alloc(spiral_gpu_pack_server* S, DbImage* owners) {
 // The two ways client input gets into a server, in any form (message.h); both return synchronised.  A null NTT-form buffer is refused with the previous
 // message untouched; from the first write on nothing answers from half-written keys: have_pp is cleared, and set again on success.
 int pk_take_pub_params(spiral_gpu_pack_server* S, Form form, const MessageIn& in, const char* what) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
+    if (enter(S)) return -1;
     const MessageLayout m = pack_pub_params_layout(S->p, S->s, S->out_n);
     if (form == FORM_NTT && check_ntt_parts(m, in, what)) return -1;
     uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->v.p, S->v_w.p};
@@ -1048,8 +1047,7 @@ int spiral_gpu_pack_server_pack_gathered(spiral_gpu_pack_server* S, const void* 
 }
 
 int spiral_gpu_pack_server_set_stream(spiral_gpu_pack_server* S, void* stream) {
-    if (!S) return fail("null server");
-    HIP_OK(hipSetDevice(S->device));
+    if (enter(S)) return -1;
     HIP_OK(hipStreamSynchronize(S->stream));
     if (S->own_stream) {
         (void)hipStreamDestroy(S->stream);
