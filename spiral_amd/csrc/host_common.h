@@ -16,6 +16,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "seed_device.h"
+#include "transform_jobs.h"
 
 namespace spiral {
 namespace host {
@@ -455,16 +456,9 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
     uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
     HIP_OK(hipMemcpyAsync(d, W.host, up_bytes, hipMemcpyHostToDevice, st));
     uint64_t* enc = reinterpret_cast<uint64_t*>(d + up_bytes);
-    FwdParams fp{};
-    fp.dst = enc;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
-    fp.p_db = p_db;
-    fp.items = d + o_items;
-    fp.coeff_bits = coeff_bits;
-    fp.err = reinterpret_cast<uint32_t*>(d);
-    fp.items_first = fp.item_base = 0;
-    launch_ntt_forward(tb, fp, img.pack ? LD_DBGEN1 : LD_DBGEN, ST_PK, (uint32_t)(n * polys), st);
+    FwdJob encode = db_encode_job(img.pack ? LD_DBGEN1 : LD_DBGEN, ST_PK, enc, p_db);  // (a linear store: no geometry)
+    db_encode_staged(encode, d + o_items, coeff_bits, reinterpret_cast<uint32_t*>(d), 0, (uint32_t)(n * polys));
+    launch_job(tb, encode, st);
     DbUpdateParams up{};
     up.enc = enc;
     up.err = reinterpret_cast<const uint32_t*>(d);

@@ -180,24 +180,8 @@ size_t pack_message_bytes(const spiral_gpu_params* p, uint32_t out_n, MessageLay
 void run_pack(const DeviceTables& tb, const uint64_t* raw_cts, uint32_t ct_stride_cts, const uint64_t* v_w, uint64_t* ginv, uint64_t* ct2, uint64_t* result,
               uint32_t out_n, uint32_t t_conv, hipStream_t st, uint32_t n_inst = 1, const Lanes& lanes = Lanes{}) {
     const uint32_t trials = n_inst * out_n * out_n;
-    FwdParams fp{};
-    fp.src = raw_cts;
-    fp.dst = ginv;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = t_conv;
-    fp.bits = get_bits_per(t_conv);
-    fp.pmode = PM_PACK;
-    fp.pk_num_per = ct_stride_cts;
-    fp.lanes = lanes;
-    launch_ntt_forward(tb, fp, LD_PDIGIT, ST_PK, trials * t_conv, st);
-    FwdParams fa{};
-    fa.src = raw_cts;
-    fa.dst = ct2;
-    fa.src_map = IndexMap{1, 2 * ct_stride_cts, 1};
-    fa.dst_map = identity_map();
-    fa.n_digits = 1;
-    fa.lanes = lanes;
-    launch_ntt_forward(tb, fa, LD_RAW, ST_PK, trials, st);
+    launch_job(tb, pack_digits_job(LD_PDIGIT, raw_cts, ginv, trials, t_conv, {.pmode = PM_PACK, .pk_num_per = ct_stride_cts, .lanes = lanes}), st);
+    launch_job(tb, raw_job(raw_cts, ct2, trials, ST_PK, IndexMap{1, 2 * ct_stride_cts, 1}, lanes), st);  // row 1 of each trial's folded ct
     launch_pack_mac(v_w, ginv, ct2, result, out_n, t_conv, st, n_inst, lanes);
 }
 
@@ -354,19 +338,11 @@ int spiral_gpu_pack_server_gen_db(spiral_gpu_pack_server* S, uint64_t seed) {
     S->img->begin_rewrite();
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per, chunk = 1u << 18;
     for (uint32_t t = 0; t < S->nt; t++) {
-        FwdParams fp{};
-        fp.dst = S->img->trial(t);
-        fp.src_map = fp.dst_map = identity_map();
-        fp.n_digits = 1;
-        fp.seed = seed;
-        fp.p_db = S->p.p_db;
-        fp.num_per = S->s.num_per;
-        fp.dim0_shard = S->s.dim0;
-        fp.trial = S->t0 + t;
-        fp.total_n = total;
+        FwdJob encode = db_encode_job(LD_DBGEN1, ST_DB1, S->img->trial(t), S->p.p_db,
+                                      {.num_per = S->s.num_per, .dim0_shard = S->s.dim0, .trial = S->t0 + t, .total_n = total});
         for (uint64_t done = 0; done < total; done += chunk) {
-            fp.item_base = done;
-            launch_ntt_forward(S->tb, fp, LD_DBGEN1, ST_DB1, (uint32_t)std::min(chunk, total - done), S->stream);
+            db_encode_seeded(encode, seed, done, (uint32_t)std::min(chunk, total - done));
+            launch_job(S->tb, encode, S->stream);
         }
     }
     HIP_OK(hipStreamSynchronize(S->stream));
@@ -407,23 +383,13 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
     if (S->img->begin_partial(S->stream)) return -1;
     const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
     if (first_item > total || n_items > total - first_item) return fail("items outside the database");
-    FwdParams fp{};
-    fp.dst = S->img->trial(trial - S->t0);
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
-    fp.p_db = S->p.p_db;
-    fp.num_per = S->s.num_per;
-    fp.dim0_shard = S->s.dim0;
-    fp.trial = trial;
-    fp.total_n = total;
-    fp.coeff_bits = coeff_bits;
+    FwdJob encode = db_encode_job(LD_DBGEN1, ST_DB1, S->img->trial(trial - S->t0), S->p.p_db,
+                                  {.num_per = S->s.num_per, .dim0_shard = S->s.dim0, .trial = trial, .total_n = total});
     if (ingest_items(items, coeff_bits, first_item, first_item, first_item + n_items, 1, S->p.p_db, S->stream,
                      [&](const uint8_t* d_items, uint32_t* d_err, uint64_t first, uint64_t n) {
                          S->img->dirty();
-                         fp.items = d_items;
-                         fp.err = d_err;
-                         fp.items_first = fp.item_base = first;
-                         launch_ntt_forward(S->tb, fp, LD_DBGEN1, ST_DB1, (uint32_t)n, S->stream);
+                         db_encode_staged(encode, d_items, coeff_bits, d_err, first, (uint32_t)n);
+                         launch_job(S->tb, encode, S->stream);
                      }))
         return -1;
     S->img->finish_load();
@@ -503,22 +469,8 @@ static int pk_expand_convert(spiral_gpu_pack_server* S, const Lanes& lanes, hipS
     HIP_OK(hipEventRecord(S->ev[1], st));
     // ---- regevToSimpleGsw + the negated GSW ciphertexts (:1022-1033)
     if (!p.direct_upload) {
-        InvParams ip{};
-        ip.src = S->cv.p;
-        ip.dst = S->gs_raw.p;
-        ip.src_map = IndexMap{2, 4, 2};  // both rows of ct 2*ij + 1
-        ip.dst_map = identity_map();
-        ip.lanes = lanes;
-        launch_ntt_inverse(S->tb, ip, IST_CRT, 2 * ngs, st);
-        FwdParams fp{};
-        fp.src = S->gs_raw.p;
-        fp.dst = S->gs_chat.p;
-        fp.src_map = fp.dst_map = identity_map();
-        fp.n_digits = p.t_conv;
-        fp.bits = get_bits_per(p.t_conv);
-        fp.pmode = PM_GSW;
-        fp.lanes = lanes;
-        launch_ntt_forward(S->tb, fp, LD_PDIGIT, ST_PK, 2 * ngs * p.t_conv, st);
+        launch_job(S->tb, lift_job(S->cv.p, S->gs_raw.p, 2 * ngs, {.src_map = IndexMap{2, 4, 2}, .lanes = lanes}), st);  // both rows of ct 2*ij + 1
+        launch_job(S->tb, pack_digits_job(LD_PDIGIT, S->gs_raw.p, S->gs_chat.p, 2 * ngs, p.t_conv, {.pmode = PM_GSW, .lanes = lanes}), st);
         MatmulParams mp{{S->v.p, S->gs_chat.p, S->gs_tmp.p, 2, 2 * p.t_conv, 1, 0, 2 * p.t_conv, 2}, lanes};
         launch_matmul(mp, ngs, st);
         launch_pack_gsw_assemble(S->gs_tmp.p, S->cv.p, S->gsw.p, ell, p.nu2, st, lanes);
@@ -553,23 +505,10 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
         np /= 2;
         if (src == out) out = out == B.fold_c ? B.fold_c2 : B.fold_c;
         if (pair) {
-            InvParams ip{};
-            ip.src = src;
-            ip.dst = B.raw;  // [t][2 np][2], compact
-            ip.src_map = IndexMap{4 * np, 2 * src_stride, 0};
-            ip.dst_map = identity_map();
-            ip.lanes = lanes;
-            launch_ntt_inverse(S->tb, ip, IST_CRT, nt * 4 * np, st);
-            FwdParams fp{};
-            fp.src = B.raw;
-            fp.dst = B.fold_d;
-            fp.src_map = fp.dst_map = identity_map();
-            fp.n_digits = ell;
-            fp.bits = get_bits_per(ell);
-            fp.fold_np = np;
-            fp.lazy_out = lazy_ok(2 * ell + 1) ? 1 : 0;  // pack_fold_mac sums 2 ell products and the addend per accumulator
-            fp.lanes = lanes;
-            launch_ntt_forward(S->tb, fp, LD_PDIFF, ST_PK, nt * np * 2 * ell, st);
+            // B.raw: [t][2 np][2], compact
+            launch_job(S->tb, lift_job(src, B.raw, nt * 4 * np, {.src_map = IndexMap{4 * np, 2 * src_stride, 0}, .lanes = lanes}), st);
+            // pack_fold_mac sums 2 ell products and the addend per accumulator
+            launch_job(S->tb, pack_digits_job(LD_PDIFF, B.raw, B.fold_d, nt * np * 2, ell, {.np = np, .mac_terms = 2 * ell + 1, .lanes = lanes}), st);
             launch_pack_fold_mac(S->key.p + ((size_t)cur * 2 * 4 * ell + 2 * ell) * kN, B.fold_d, out, 2 * ell, nt * np, st, 4 * ell, src, np, src_stride, lanes);
             src = out;
             src_stride = np;
@@ -593,15 +532,9 @@ static int pk_fold_into(spiral_gpu_pack_server* S, const PkBufs& B, uint32_t nt,
         src = out;
         src_stride = np;
     }
-    {
-        InvParams ip{};
-        ip.src = src;
-        ip.dst = B.raw;
-        ip.src_map = p.nu2 ? identity_map() : IndexMap{2 * s.num_per, 2 * s.num_per, 0};
-        ip.dst_map = IndexMap{2 * np, 2 * s.num_per, 0};  // the trial's surviving np cts at the head of its num_per slots
-        ip.lanes = lanes;
-        launch_ntt_inverse(S->tb, ip, IST_CRT, nt * np * 2, st);
-    }
+    // the trial's surviving np cts to the head of its num_per slots
+    launch_job(S->tb, lift_job(src, B.raw, nt * np * 2, {.src_map = p.nu2 ? identity_map() : IndexMap{2 * s.num_per, 2 * s.num_per, 0},
+                                                      .dst_map = IndexMap{2 * np, 2 * s.num_per, 0}, .lanes = lanes}), st);
     HIP_OK(hipEventRecord(S->ev[5], st));
     S->packed_after_front = false;
     return 0;
@@ -622,12 +555,7 @@ static int pk_back(spiral_gpu_pack_server* S, const uint64_t* folded, uint32_t c
     const PkBufs& B = S->own;
     const uint32_t rows = S->out_n + 1;
     run_pack(S->tb, folded, ct_stride, S->v_w.p, B.ginv, B.ct2, B.res, S->out_n, p.t_conv, st, 1, lanes);
-    InvParams ip{};
-    ip.src = B.res;
-    ip.dst = B.pk_raw;
-    ip.src_map = ip.dst_map = identity_map();
-    ip.lanes = lanes;
-    launch_ntt_inverse(S->tb, ip, IST_CRT, rows * S->out_n, st);
+    launch_job(S->tb, lift_job(B.res, B.pk_raw, rows * S->out_n, {.lanes = lanes}), st);
     if (lanes.n > 1) {
         launch_rescale2(B.pk_raw, B.resp, S->out_n * kN, rows * S->out_n * kN, kQ, S->s.qprime, 4 * p.p_db, st, lanes);
     } else {
@@ -883,11 +811,7 @@ static int pk_item_back(spiral_gpu_pack_server* L, const PkBufs& B, uint32_t g, 
     const spiral_gpu_params& p = L->p;
     const uint32_t rows = L->out_n + 1;
     run_pack(L->tb, B.raw, L->s.num_per, L->v_w.p, B.ginv, B.ct2, B.res, L->out_n, p.t_conv, st, g);
-    InvParams ip{};
-    ip.src = B.res;
-    ip.dst = B.pk_raw;
-    ip.src_map = ip.dst_map = identity_map();
-    launch_ntt_inverse(L->tb, ip, IST_CRT, g * rows * L->out_n, st);
+    launch_job(L->tb, lift_job(B.res, B.pk_raw, g * rows * L->out_n), st);
     const Slots slots{g, (int64_t)B.slot_words};
     launch_rescale2_slots(B.pk_raw, B.resp, L->out_n * kN, (uint32_t)B.slot_words, kQ, L->s.qprime, 4 * p.p_db, slots, st);
     if (want_wire)

@@ -128,20 +128,12 @@ int spiral_gpu_to_ntt(uint64_t* out, const uint64_t* in, size_t npolys, int redu
     uint64_t* d_in = sc.upload(in, npolys * kN);
     uint64_t* d_out = sc.get(npolys * kRefNtt);
     if (!d_in || !d_out) return fail("device allocation/upload failed");
-    FwdParams fp{};
-    fp.src = d_in;
-    fp.dst = d_out;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
     if (reduce) {
-        launch_ntt_forward(tb, fp, LD_RAW, ST_REF, (uint32_t)npolys, 0);
+        launch_job(tb, raw_job(d_in, d_out, (uint32_t)npolys, ST_REF), 0);
     } else {
-        // to_ntt_no_reduce copies the raw value into both limbs (src/poly.cpp:291-309): it is digit 0 of width 32
         uint64_t* d_pk = sc.get(npolys * kN);
         if (!d_pk) return fail("device allocation failed");
-        fp.dst = d_pk;
-        fp.bits = 32;
-        launch_ntt_forward(tb, fp, LD_DIGIT, ST_PK, (uint32_t)npolys, 0);
+        launch_job(tb, raw32_job(d_in, d_pk, (uint32_t)npolys), 0);
         launch_pk_to_ref(d_pk, d_out, (uint32_t)npolys, identity_map(), 0);
     }
     HIP_OK(hipMemcpy(out, d_out, npolys * kRefNtt * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -180,21 +172,14 @@ int spiral_gpu_time_ntt(size_t npolys, int iters, float* fwd_ms, float* inv_ms) 
     HIP_OK(hipMemset(d_raw, 0x5a, npolys * kN * sizeof(uint64_t)));
     hipEvent_t e[3];
     for (auto& x : e) HIP_OK(hipEventCreate(&x));
-    FwdParams fp{};
-    fp.src = d_raw;
-    fp.dst = d_pk;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
-    InvParams ip{};
-    ip.src = d_pk;
-    ip.dst = d_raw;
-    ip.src_map = ip.dst_map = identity_map();
-    launch_ntt_forward(tb, fp, LD_RAW, ST_PK, (uint32_t)npolys, 0);  // warm
-    launch_ntt_inverse(tb, ip, IST_CRT, (uint32_t)npolys, 0);
+    const FwdJob fwd = raw_job(d_raw, d_pk, (uint32_t)npolys);
+    const InvJob inv = lift_job(d_pk, d_raw, (uint32_t)npolys);
+    launch_job(tb, fwd, 0);  // warm
+    launch_job(tb, inv, 0);
     HIP_OK(hipEventRecord(e[0], 0));
-    for (int i = 0; i < iters; i++) launch_ntt_forward(tb, fp, LD_RAW, ST_PK, (uint32_t)npolys, 0);
+    for (int i = 0; i < iters; i++) launch_job(tb, fwd, 0);
     HIP_OK(hipEventRecord(e[1], 0));
-    for (int i = 0; i < iters; i++) launch_ntt_inverse(tb, ip, IST_CRT, (uint32_t)npolys, 0);
+    for (int i = 0; i < iters; i++) launch_job(tb, inv, 0);
     HIP_OK(hipEventRecord(e[2], 0));
     HIP_OK(hipEventSynchronize(e[2]));
     HIP_OK(hipEventElapsedTime(fwd_ms, e[0], e[1]));
@@ -219,15 +204,10 @@ int spiral_gpu_time_ntt_digits(size_t npolys, uint32_t n_digits, int iters, floa
     HIP_OK(hipMemset(d_raw, 0x5a, npolys * kN * sizeof(uint64_t)));
     hipEvent_t e[2];
     for (auto& x : e) HIP_OK(hipEventCreate(&x));
-    FwdParams fp{};
-    fp.src = d_raw;
-    fp.dst = d_pk;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = n_digits;
-    fp.bits = get_bits_per(n_digits);
-    launch_ntt_forward(tb, fp, LD_DIGIT, ST_PK, (uint32_t)(npolys * n_digits), 0);  // warm
+    const FwdJob digits = gadget_digits_job(d_raw, d_pk, (uint32_t)npolys, n_digits);
+    launch_job(tb, digits, 0);  // warm
     HIP_OK(hipEventRecord(e[0], 0));
-    for (int i = 0; i < iters; i++) launch_ntt_forward(tb, fp, LD_DIGIT, ST_PK, (uint32_t)(npolys * n_digits), 0);
+    for (int i = 0; i < iters; i++) launch_job(tb, digits, 0);
     HIP_OK(hipEventRecord(e[1], 0));
     HIP_OK(hipEventSynchronize(e[1]));
     HIP_OK(hipEventElapsedTime(ms, e[0], e[1]));
@@ -357,15 +337,7 @@ int spiral_gpu_split_and_crt(uint64_t* out, const uint64_t* in, size_t num_per, 
     uint64_t* di = sc.upload(in, num_per * 6 * kN);
     uint64_t* dd = sc.get(num_per * 2 * m2 * 2 * kN);  // fold operand layout, only the low halves are filled
     if (!di || !dd) return fail("device allocation/upload failed");
-    FwdParams fp{};
-    fp.src = di;
-    fp.dst = dd;
-    fp.src_map = identity_map();
-    fp.n_digits = t_gsw;
-    fp.bits = get_bits_per(t_gsw);
-    fp.ell = t_gsw;
-    fp.fold_np = (uint32_t)num_per;  // every ct index < num_per -> low half
-    launch_ntt_forward(tb, fp, LD_SDIGIT, ST_PK, (uint32_t)(num_per * 6 * t_gsw), 0);
+    launch_job(tb, fold_digits_job(LD_SDIGIT, di, dd, (uint32_t)(num_per * 6), t_gsw, (uint32_t)num_per), 0);  // np = num_per: every ct index < num_per -> low half
     // D[i][row][c] at (i*2*m2 + row)*2 + c  ->  reference [i][row][c]
     return download_pk(sc, dd, IndexMap{2 * m2, 4 * m2, 0}, out, num_per * m2 * 2);
 }
@@ -384,21 +356,9 @@ int spiral_gpu_fold_one_further_dimension(uint64_t* cts, size_t num_per, const u
     uint64_t* d_c = sc.get(num_per * 6 * kN);
     if (!d_cts || !d_q || !d_qn || !d_key || !d_d || !d_c) return fail("device allocation/upload failed");
     launch_fold_key_from_reoriented(d_q, d_qn, d_key, m2, 0);
-    FwdParams fp{};
-    fp.src = d_cts;
-    fp.dst = d_d;
-    fp.src_map = identity_map();
-    fp.n_digits = t_gsw;
-    fp.bits = get_bits_per(t_gsw);
-    fp.ell = t_gsw;
-    fp.fold_np = (uint32_t)num_per;
-    launch_ntt_forward(tb, fp, LD_SDIGIT, ST_PK, (uint32_t)(2 * num_per * 6 * t_gsw), 0);
+    launch_job(tb, fold_digits_job(LD_SDIGIT, d_cts, d_d, (uint32_t)(2 * num_per * 6), t_gsw, (uint32_t)num_per), 0);
     launch_fold_mac(d_key, d_d, d_c, 2 * m2, (uint32_t)num_per, 0);
-    InvParams ip{};
-    ip.src = d_c;
-    ip.dst = d_cts;
-    ip.src_map = ip.dst_map = identity_map();
-    launch_ntt_inverse(tb, ip, IST_CRT, (uint32_t)(num_per * 6), 0);
+    launch_job(tb, lift_job(d_c, d_cts, (uint32_t)(num_per * 6)), 0);
     HIP_OK(hipMemcpy(cts, d_cts, num_per * 6 * kN * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -431,18 +391,8 @@ int spiral_gpu_scal_to_mat(uint64_t* out, const uint64_t* cv, const uint64_t* w,
     uint64_t* d_g = sc.get((size_t)t_conv * kN);
     uint64_t* d_out = sc.get((size_t)6 * kN);
     if (!d_cv || !d_w || !d_raw || !d_g || !d_out) return fail("device allocation/upload failed");
-    InvParams ip{};
-    ip.src = d_cv;
-    ip.dst = d_raw;
-    ip.src_map = ip.dst_map = identity_map();
-    launch_ntt_inverse(tb, ip, IST_CRT, 1, 0);
-    FwdParams fp{};
-    fp.src = d_raw;
-    fp.dst = d_g;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = t_conv;
-    fp.bits = get_bits_per(t_conv);
-    launch_ntt_forward(tb, fp, LD_DIGIT, ST_PK, t_conv, 0);
+    launch_job(tb, lift_job(d_cv, d_raw, 1), 0);
+    launch_job(tb, gadget_digits_job(d_raw, d_g, 1, t_conv), 0);
     Scal2MatParams sp{};
     sp.w = d_w;
     sp.g = d_g;
@@ -466,18 +416,8 @@ int spiral_gpu_regev_to_gsw(uint64_t* out, const uint64_t* cv_v, const uint64_t*
     uint64_t* d_chat = sc.get((size_t)ell * 2 * t_conv * kN);
     uint64_t* d_gsw = sc.get((size_t)3 * 3 * ell * kN);
     if (!d_cv || !d_w || !d_v || !d_raw || !d_chat || !d_gsw) return fail("device allocation/upload failed");
-    InvParams ip{};
-    ip.src = d_cv;
-    ip.dst = d_raw;
-    ip.src_map = ip.dst_map = identity_map();
-    launch_ntt_inverse(tb, ip, IST_CRT, 2 * ell, 0);
-    FwdParams fp{};
-    fp.src = d_raw;
-    fp.dst = d_chat;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = t_conv;
-    fp.bits = get_bits_per(t_conv);
-    launch_ntt_forward(tb, fp, LD_DIGIT, ST_PK, 2 * ell * t_conv, 0);
+    launch_job(tb, lift_job(d_cv, d_raw, 2 * ell), 0);
+    launch_job(tb, gadget_digits_job(d_raw, d_chat, 2 * ell, t_conv), 0);
     GswParams gp{};
     gp.w = d_w;
     gp.v = d_v;

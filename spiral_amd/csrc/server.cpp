@@ -291,24 +291,10 @@ int convert_part(spiral_gpu_server* S, uint32_t what, hipStream_t st, bool mark_
     const uint32_t n1 = (what & CONV_S2M) ? S->dim0_shard : 0, n2 = (what & CONV_GSW) ? 2 * ngs : 0;
     const IndexMap map1{1, 2 * ps, 2 * (S->j0 * ps + S->pos_first)};  // row 0 of ct pos(j0 + a)
     const IndexMap map2{2, 2 * ps, 2 * S->pos_rest};                   // rows 0, 1 of the nu2*ell GSW-bit cts
-    InvParams ip{};
-    ip.src = S->cv.p;
-    ip.dst = n1 ? S->cv_raw.p : S->gs_raw_p;
-    ip.src_map = n1 ? map1 : map2;
-    ip.split = (n1 && n2) ? n1 : 0;
-    ip.src_map2 = map2;
-    ip.dst_map = identity_map();
-    ip.lanes = lanes;
-    launch_ntt_inverse(S->tb, ip, IST_CRT, n1 + n2, st);
-    FwdParams fp{};
-    fp.src = ip.dst;
-    fp.dst = n1 ? S->cv_g.p : S->gs_chat_p;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = p.t_conv;
-    fp.bits = get_bits_per(p.t_conv);
-    fp.lazy_out = lazy_ok(2 * p.t_conv) ? 1 : 0;  // read only by the conversion products, which sum at most 2 * t_conv terms per accumulator
-    fp.lanes = lanes;
-    launch_ntt_forward(S->tb, fp, LD_DIGIT, ST_PK, (n1 + n2) * p.t_conv, st);
+    uint64_t* raw = n1 ? S->cv_raw.p : S->gs_raw_p;
+    launch_job(S->tb, lift_job(S->cv.p, raw, n1 + n2, {.src_map = n1 ? map1 : map2, .split = (n1 && n2) ? n1 : 0, .src_map2 = map2, .lanes = lanes}), st);
+    // read only by the conversion products, which sum at most 2 * t_conv terms per accumulator
+    launch_job(S->tb, gadget_digits_job(raw, n1 ? S->cv_g.p : S->gs_chat_p, n1 + n2, p.t_conv, 2 * p.t_conv, lanes), st);
     Scal2MatParams sp{};
     sp.w = S->w.p;
     sp.g = S->cv_g.p;
@@ -367,27 +353,11 @@ int run_fold_rounds(spiral_gpu_server* S, const FoldJob& job) {
     const uint64_t *src_pk = job.src_pk, *raw_addend = job.raw_addend;
     bool pre_reduce = job.pre_reduce;
     auto lift = [&](uint32_t npolys) {  // src_pk -> S->raw
-        InvParams ip{};
-        ip.src = src_pk;
-        ip.dst = S->raw.p;
-        ip.src_map = ip.dst_map = identity_map();
-        ip.pre_reduce = pre_reduce ? 1 : 0;
-        ip.lanes = lanes;
-        launch_ntt_inverse(S->tb, ip, IST_CRT, npolys, S->stream);
+        launch_job(S->tb, lift_job(src_pk, S->raw.p, npolys, {.pre_reduce = pre_reduce, .lanes = lanes}), S->stream);
         src_pk = nullptr;
     };
-    auto digits = [&](FwdLoad ld, uint32_t n_jobs, uint32_t lazy_out) {  // S->raw -> the round's operand S->fold_d
-        FwdParams fp{};
-        fp.src = S->raw.p;
-        fp.dst = S->fold_d.p;
-        fp.src_map = identity_map();
-        fp.n_digits = s.ell;
-        fp.bits = get_bits_per(s.ell);
-        fp.ell = s.ell;
-        fp.fold_np = np;
-        fp.lazy_out = lazy_out;
-        fp.lanes = lanes;
-        launch_ntt_forward(S->tb, fp, ld, ST_PK, n_jobs, S->stream);
+    auto digits = [&](FwdLoad ld, uint32_t n_src, uint32_t mac_terms) {  // S->raw -> the round's operand S->fold_d
+        launch_job(S->tb, fold_digits_job(ld, S->raw.p, S->fold_d.p, n_src, s.ell, np, mac_terms, lanes), S->stream);
     };
     uint64_t* out_pk = S->fold_c.p;
     for (uint32_t d = job.d0; d < job.d0 + job.rounds; d++) {
@@ -402,7 +372,7 @@ int run_fold_rounds(spiral_gpu_server* S, const FoldJob& job) {
             const uint64_t* low = from_raw ? raw_addend : src_pk;
             if (!from_raw) lift(n_src);
             raw_addend = nullptr;
-            digits(LD_SDIFF, (n_src / 2) * s.ell, lazy_ok(3 * s.ell + 1) ? 1 : 0);
+            digits(LD_SDIFF, n_src / 2, 3 * s.ell + 1);  // fold_mac sums m2 = 3 ell products and the addend per accumulator
             launch_fold_mac(key, S->fold_d.p, out_pk, s.m2, np, S->stream, s.m2, low, lanes);
         } else {
             if (src_pk && S->fold_chain) {
@@ -419,7 +389,7 @@ int run_fold_rounds(spiral_gpu_server* S, const FoldJob& job) {
                 launch_fold_chain(S->tb, cp, n_src, S->stream);
             } else {
                 if (src_pk) lift(n_src);
-                digits(LD_SDIGIT, n_src * s.ell, 0);
+                digits(LD_SDIGIT, n_src, 0);
             }
             launch_fold_mac_two(key, S->fold_d.p, out_pk, s.m2, s.ell, get_bits_per(s.ell), np, S->stream, lanes);  // the reference's two products, Q_neg derived
         }
@@ -503,21 +473,13 @@ int spiral_gpu_server_gen_db(spiral_gpu_server* S, uint64_t seed) {
     if (!S) return fail("null server");
     if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
-    FwdParams fp{};
-    fp.dst = S->img->db.p;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
-    fp.seed = seed;
-    fp.p_db = S->p.p_db;
-    fp.num_per = S->s.num_per;
-    fp.dim0_shard = S->dim0_shard;
-    fp.j0 = S->j0;
+    FwdJob encode = db_encode_job(LD_DBGEN, ST_DB, S->img->db.p, S->p.p_db, {.num_per = S->s.num_per, .dim0_shard = S->dim0_shard, .j0 = S->j0});
     const uint64_t items = (uint64_t)S->dim0_shard * S->s.num_per, first = (uint64_t)S->j0 * S->s.num_per;
     const uint64_t chunk = 1u << 16;  // items per launch (4 polynomials each)
     S->img->begin_rewrite();
     for (uint64_t done = 0; done < items; done += chunk) {
-        fp.item_base = first + done;
-        launch_ntt_forward(S->tb, fp, LD_DBGEN, ST_DB, (uint32_t)(std::min(chunk, items - done) * 4), S->stream);
+        db_encode_seeded(encode, seed, first + done, (uint32_t)(std::min(chunk, items - done) * 4));
+        launch_job(S->tb, encode, S->stream);
     }
     HIP_OK(hipStreamSynchronize(S->stream));
     S->img->finish_load();
@@ -533,23 +495,13 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
                                                                          (unsigned long long)n_items, (unsigned long long)total);
     // item i lives at (ii = i % num_per, j = i / num_per): this shard holds the items of j in [j0, j1)
     const uint64_t lo = std::max<uint64_t>(first_item, (uint64_t)S->j0 * S->s.num_per), hi = std::min<uint64_t>(first_item + n_items, (uint64_t)S->j1 * S->s.num_per);
-    FwdParams fp{};
-    fp.dst = S->img->db.p;
-    fp.src_map = fp.dst_map = identity_map();
-    fp.n_digits = 1;
-    fp.p_db = S->p.p_db;
-    fp.num_per = S->s.num_per;
-    fp.dim0_shard = S->dim0_shard;
-    fp.j0 = S->j0;
-    fp.coeff_bits = coeff_bits;
+    FwdJob encode = db_encode_job(LD_DBGEN, ST_DB, S->img->db.p, S->p.p_db, {.num_per = S->s.num_per, .dim0_shard = S->dim0_shard, .j0 = S->j0});
     // a partial load scatters packed words into the image: an image a batch has converted to limb planes goes back to the packed form first
     if (S->img->begin_partial(S->stream)) return -1;
     if (ingest_items(items, coeff_bits, first_item, lo, hi, 4, S->p.p_db, S->stream, [&](const uint8_t* d_items, uint32_t* d_err, uint64_t first, uint64_t n) {
             S->img->dirty();
-            fp.items = d_items;
-            fp.err = d_err;
-            fp.items_first = fp.item_base = first;
-            launch_ntt_forward(S->tb, fp, LD_DBGEN, ST_DB, (uint32_t)(n * 4), S->stream);
+            db_encode_staged(encode, d_items, coeff_bits, d_err, first, (uint32_t)(n * 4));
+            launch_job(S->tb, encode, S->stream);
         }))
         return -1;
     S->img->finish_load();
@@ -734,12 +686,7 @@ int spiral_gpu_server_first_dim_stage(spiral_gpu_server* S, uint32_t stage) {
 
 int spiral_gpu_server_lift(spiral_gpu_server* S, int reduce_first) {
     if (enter(S)) return -1;
-    InvParams ip{};
-    ip.src = S->acc;
-    ip.dst = S->raw.p;
-    ip.src_map = ip.dst_map = identity_map();
-    ip.pre_reduce = reduce_first ? 1 : 0;
-    launch_ntt_inverse(S->tb, ip, IST_CRT, S->s.num_per * 6, S->stream);
+    launch_job(S->tb, lift_job(S->acc, S->raw.p, S->s.num_per * 6, {.pre_reduce = reduce_first != 0}), S->stream);
     S->raw_from_acc = true;
     return 0;
 }

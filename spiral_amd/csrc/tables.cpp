@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "transform_jobs.h"
 
 namespace spiral {
 
@@ -87,13 +88,7 @@ int tables_get(int device, DeviceTables* out) {
         uint64_t* d_raw = nullptr;
         if (hipMalloc(&d_raw, raw.size() * sizeof(uint64_t)) != hipSuccess) return -1;
         if (hipMemcpy(d_raw, raw.data(), raw.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) return -1;
-        FwdParams p{};
-        p.src = d_raw;
-        p.dst = t.neg1;
-        p.src_map = identity_map();
-        p.dst_map = identity_map();
-        p.n_digits = 1;
-        launch_ntt_forward(t, p, LD_RAW, ST_PK, kLogN, 0);
+        host::launch_job(t, host::raw_job(d_raw, t.neg1, kLogN), 0);
         if (hipDeviceSynchronize() != hipSuccess) return -1;
         (void)hipFree(d_raw);
         // Shoup companions floor(w * 2^32 / m) of the same words, so that the expansion multiplies by neg1 without a division

@@ -86,6 +86,16 @@ def test_to_from_ntt(sa, oracle):
     assert_eq(sa.to_ntt_no_reduce(d), O.to_ntt(d, reduce=False), "to_ntt_no_reduce")
 
 
+def test_timing_entry_points(sa):
+    """the measurement helpers the benchmark's transform roofline calls, at the smallest sizes they accept: they launch and time something"""
+    import math
+
+    times = dict(zip(("time_ntt forward", "time_ntt inverse"), sa.time_ntt(3, 1)))
+    times["time_ntt_digits"] = sa.time_ntt_digits(3, 2, 1)
+    for what, ms in times.items():
+        assert math.isfinite(ms) and ms > 0, f"{what}: {ms} ms"
+
+
 def test_multiply_add_mul_by_const(sa, oracle):
     O = oracle
     rng = np.random.default_rng(12)
