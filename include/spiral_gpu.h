@@ -62,6 +62,11 @@ int spiral_gpu_abi_version(void);
 const char *spiral_gpu_last_error(void);
 int spiral_gpu_device_count(void);
 int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
+/* 1 when a server of these parameters on the first-dimension shard [j_begin, j_end) ((0, 0): the whole first dimension) may hold its database in the
+ * LIMBS form (spiral_gpu_server_set_db_format below), so that a batch shares one matrix-core pass over it and collecting clients into a batch pays;
+ * 0 when not; -1 (spiral_gpu_last_error) for bad parameters or a bad shard.  A function of the parameters and of ONE option, "sweep_narrow" as it
+ * is when asked (fewer than 64 ciphertexts per slot only), no GPU needed.  The SpiralPack twin is spiral_gpu_pack_has_limb_form. */
+int spiral_gpu_has_limb_form(const spiral_gpu_params *p, uint32_t j_begin, uint32_t j_end);
 
 /* Process-wide options: schedule forms that compute the same function (the reference has one form of each: its own loops).  A server takes
  * the values in force when it is created; "fwd2" and "db_stage_bytes" apply to every later call.  Unknown names fail.
@@ -84,6 +89,12 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  *                     form -- spiral_gpu_pack_has_limb_form, ..._pack_server_set_db_format(LIMBS), the automatic conversion by a batch of two or more
  *                     clients, time_sweep_batch -- and nowhere else: an image that is in the form is swept, updated, reloaded and converted back
  *                     whatever the option says now.  Same results either way
+ *   "sweep_narrow"    0 (default: opt-in) or 1: with 1 a base geometry of 8, 16 or 32 ciphertexts per slot (nu2 = 3, 4, 5: the streaming sets) has a
+ *                     LIMBS form too: workgroups of 1, 2, 4 waves per slot instead of 8 (csrc/sweep_mfma.hip), so a batch shares one pass over the
+ *                     database where it sweeps once per lane today.  Read where an image would TAKE that form -- spiral_gpu_has_limb_form,
+ *                     spiral_gpu_server_set_db_format(LIMBS), the automatic conversion by a batch, spiral_gpu_multiply_queries_by_database -- and
+ *                     nowhere else: an image that is in the form is swept, updated, read, reloaded and converted back whatever the option says now.
+ *                     Same results either way; not measured yet, hence opt-in
  *   "query_batch_chunk" message polynomials per lane per staging pass of spiral_gpu_server_set_query_batch for messages too large to check on the
  *                     host (direct upload); default 512, at least 1.  Read per call; same results whatever the value
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
@@ -229,7 +240,8 @@ int spiral_gpu_server_read_db_columns(spiral_gpu_server *s, uint32_t ii_begin, u
  * set_db_format converts the holder's image in place through a bounded staging buffer (the maps are bijective: packed -> limbs -> packed
  * reproduces every byte), so one image serves both kernels whatever the database's size; a batch converts to LIMBS by itself (option
  * "one_image"), a partial load_db_items and set_sweep_stages(K > 1) convert back.  LIMBS exists where the matrix-core sweep does (>= 64
- * ciphertexts per slot, the shard's first dimension a power of two in [64, 2048]); elsewhere set_db_format(LIMBS) fails.  Call it on the
+ * ciphertexts per slot -- or 8, 16 or 32 with option "sweep_narrow" = 1 --, the shard's first dimension a power of two in [64, 2048]:
+ * spiral_gpu_has_limb_form); elsewhere set_db_format(LIMBS) fails.  An image that is in the form stays usable when the option is switched off.  Call it on the
  * image's owner (not on a lane), outside stream capture; the lanes' captured graphs are re-captured by themselves.
  * db_device_bytes: device memory the holder of this server's image keeps for database images (one image, unless "one_image" is 0). */
 enum spiral_gpu_db_format { SPIRAL_GPU_DB_PACKED = 0, SPIRAL_GPU_DB_LIMBS = 1 };

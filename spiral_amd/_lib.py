@@ -64,6 +64,7 @@ PROTOTYPES = {
     "spiral_gpu_last_error": (C.c_char_p, []),
     "spiral_gpu_device_count": (C.c_int, []),
     "spiral_gpu_get_shape": (C.c_int, [C.POINTER(Params), C.POINTER(Shape)]),
+    "spiral_gpu_has_limb_form": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint32]),
     "spiral_gpu_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "spiral_gpu_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),
     "spiral_gpu_get_tables": (C.c_int, [U64P]),

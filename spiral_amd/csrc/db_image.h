@@ -27,10 +27,14 @@ struct DbLayout {
     static DbLayout base(uint32_t num_per, uint32_t dim0_shard) { return {false, num_per, dim0_shard, 1, db_device_words(2 * num_per, dim0_shard)}; }
     static DbLayout packed1(uint32_t num_per, uint32_t dim0, uint32_t trials) { return {true, num_per, dim0, trials, db1_device_words(num_per, dim0)}; }
     bool mfma_ok() const { return pack ? sweep1_mfma_ok(num_per, dim0) : sweep_mfma_ok(num_per, 2 * dim0); }  // the kernels can sweep the limb-plane form
-    // whether an image of this layout may TAKE the limb-plane form: at 8 ciphertexts per slot (the pair form) only with option pack_pair_blocks.  Asked
-    // where that is decided -- set_format(LIMBS), a batch's automatic conversion, has_limb_form -- and nowhere else: an image that is in the form is
-    // swept, updated, reloaded and converted back on mfma_ok alone, so switching the option off never strands one
-    bool limbs_ok() const { return mfma_ok() && (!pack || num_per != 8u || options().pack_pair_blocks != 0); }
+    // whether an image of this layout may TAKE the limb-plane form: a SpiralPack image of 8 ciphertexts per slot (the pair form) only with option
+    // pack_pair_blocks, a base image of fewer than 64 (the W forms) only with option sweep_narrow.  Asked where that is decided -- set_format(LIMBS), a
+    // batch's automatic conversion (limb_view), the stage call of primitives.cpp, has_limb_form -- and nowhere else: an image that is in the form is
+    // swept, updated, reloaded and converted back on mfma_ok alone, so switching an option off never strands one
+    bool limbs_ok() const {
+        if (!mfma_ok()) return false;
+        return pack ? num_per != 8u || options().pack_pair_blocks != 0 : num_per >= 64u || options().sweep_narrow != 0;
+    }
 };
 
 struct DbImage {
@@ -77,18 +81,20 @@ struct DbImage {
 
     // Converts the image between the packed form (common.h, kernels.h; the vector-ALU sweeps) and the limb planes (sweep_mfma.hip; the matrix-core
     // sweeps) IN PLACE: a slot z's region of a trial is the same byte range in both forms, so the image goes through a staging buffer of at most
-    // 256 MiB a few slots at a time -- no second image, whatever the database's size.  Below 64 columns a packed SpiralPack tile holds pz = 64 / num_per
-    // slots (kernels.h db1_packed_byte) and it is those pz slots that share a byte range, so the chunks are cut at multiples of pz.  Offline (database
+    // 256 MiB a few slots at a time -- no second image, whatever the database's size.  Below 64 columns a packed tile holds pz = 64 / columns
+    // slots (kernels.h db1_packed_byte: num_per columns; common.h db_tile_lane: 2 num_per columns) and it is those pz slots that share a byte range, so
+    // the chunks are cut at multiples of pz.  Offline (database
     // load time or the first batch), never inside a capture.
     int set_format(uint32_t fmt, hipStream_t st) {
         if (format == fmt) return 0;
         if (fmt == SPIRAL_GPU_DB_LIMBS ? !lay.limbs_ok() : !lay.mfma_ok())
             return fail(lay.pack ? "this geometry has no limb-plane form (needs 16, 32, 64 or a power of two >= 128 ciphertexts per slot and a power-of-two first "
                                    "dimension in [128, 4096]; 8 ciphertexts per slot with option pack_pair_blocks = 1)"
-                                 : "this geometry has no limb-plane form (needs >= 64 ciphertexts per slot and a power-of-two first dimension in [64, 2048])");
+                                 : "this geometry has no limb-plane form (needs >= 64 ciphertexts per slot and a power-of-two first dimension in [64, 2048]; 8, 16 or 32 "
+                                   "ciphertexts per slot with option sweep_narrow = 1)");
         if (hipDeviceSynchronize() != hipSuccess) return fail("hipDeviceSynchronize failed");  // whatever reads or writes the image, on whichever stream
         const size_t per_z = lay.trial_words / kN;
-        const uint32_t pz = lay.pack && lay.num_per < 64u ? 64u / lay.num_per : 1u;
+        const uint32_t nic = lay.pack ? lay.num_per : 2u * lay.num_per, pz = nic < 64u ? 64u / nic : 1u;
         const uint32_t nzc = std::max(pz, (uint32_t)std::min<size_t>(kN, ((size_t)256 << 20) / (per_z * sizeof(uint64_t))) / pz * pz);
         DevBuf stage;
         if (stage.alloc(per_z * nzc)) return -1;
@@ -142,7 +148,7 @@ struct DbImage {
     int limb_view(uint32_t n, uint32_t threshold, hipStream_t st, const uint64_t** out) {
         *out = nullptr;
         if (format == SPIRAL_GPU_DB_LIMBS) return *out = db.p, 0;  // (whatever the threshold says: there is no other image to sweep)
-        if (threshold == 0 || n < threshold || !lay.mfma_ok()) return 0;
+        if (threshold == 0 || n < threshold || !lay.limbs_ok()) return 0;  // (either way below: the one image converted, or a second one built)
         if (options().one_image) {
             if (set_format(SPIRAL_GPU_DB_LIMBS, st)) return -1;
             return *out = db.p, 0;

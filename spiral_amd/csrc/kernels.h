@@ -34,6 +34,8 @@ struct Options {
                                     // until the lane form is measured against the per-lane form
     int pack_pair_blocks = 0;  // 1: a SpiralPack image of 8 ciphertexts per slot may TAKE the limb-plane form (the pair form of the matrix-core sweep,
                                // sweep_mfma.hip); read only where that is decided (db_image.h DbLayout::limbs_ok), never by what works on a converted image
+    int sweep_narrow = 0;  // 1: a base image of 8, 16 or 32 ciphertexts per slot may TAKE the limb-plane form (the W forms of the matrix-core sweep, sweep_mfma.hip);
+                           // read only where that is decided (db_image.h DbLayout::limbs_ok), never by what works on a converted image
     uint32_t query_batch_chunk = 512;  // set_query_batch: message polynomials per lane per staging pass of messages too large to check on the host
                                        // (= message.h kWireChunkPolys / kMaxLanes: all lanes together fill set_query_wire's staging), at least 1
 };
@@ -457,8 +459,8 @@ bool sweep_batch_ok(uint32_t num_per, uint32_t jm_total);
 void launch_sweep_batch(const uint64_t* db, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
                         hipStream_t s, uint32_t g_extra = 0);
 // the same on the matrix cores for n = 1 .. kMaxLanes queries per pass (sweep_mfma.hip): needs the "limb plane" image of the database, built
-// from the packed one by launch_db_limb_planes (as many words); where sweep_mfma_ok (>= 64 ciphertexts per slot, first dimension a power of two in
-// [64, 2048]).  Returns the launch's error (the > 64 KiB LDS opt-in is per device).  k_log: the accumulators' stage layout, as launch_sweep
+// from the packed one by launch_db_limb_planes (as many words); where sweep_mfma_ok (>= 8 ciphertexts per slot, first dimension a power of two in
+// [64, 2048]; whether an image of fewer than 64 ciphertexts per slot takes the form is option sweep_narrow, DbLayout::limbs_ok).  Returns the launch's error (the > 64 KiB LDS opt-in is per device).  k_log: the accumulators' stage layout, as launch_sweep
 bool sweep_mfma_ok(uint32_t num_per, uint32_t jm_total);
 // nz slots z (both pointers at the first of them; a slot's region is db_device_words / kN words in either form, so a server converts its image IN PLACE
 // a few slots at a time through a staging buffer); launch_db_limb_unplanes is the inverse map (limb planes -> packed), bit-exact both ways

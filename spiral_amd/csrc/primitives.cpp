@@ -46,6 +46,7 @@ int spiral_gpu_set_option(const char* name, int64_t value) {
     else if (n == "pack_item_group" && value >= 0 && value <= 0xFFFFFFFFll) o.pack_item_group = (uint32_t)value;
     else if (n == "pack_batch_lanes" && value >= 0 && value <= (int64_t)kMaxLanes) o.pack_batch_lanes = (uint32_t)value;
     else if (n == "pack_pair_blocks" && (value == 0 || value == 1)) o.pack_pair_blocks = (int)value;
+    else if (n == "sweep_narrow" && (value == 0 || value == 1)) o.sweep_narrow = (int)value;
     else if (n == "query_batch_chunk" && value >= 1 && value <= 0xFFFFFFFFll) o.query_batch_chunk = (uint32_t)value;
     else return fail("unknown option '%s' or value %lld out of range", name, (long long)value);
     return 0;
@@ -65,6 +66,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "pack_item_group") *value = o.pack_item_group;
     else if (n == "pack_batch_lanes") *value = o.pack_batch_lanes;
     else if (n == "pack_pair_blocks") *value = o.pack_pair_blocks;
+    else if (n == "sweep_narrow") *value = o.sweep_narrow;
     else if (n == "query_batch_chunk") *value = o.query_batch_chunk;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
@@ -79,6 +81,16 @@ int spiral_gpu_device_count(void) {
     return n;
 }
 int spiral_gpu_get_shape(const spiral_gpu_params* p, spiral_gpu_shape* out) { return shape_of(p, out); }
+int spiral_gpu_has_limb_form(const spiral_gpu_params* p, uint32_t j_begin, uint32_t j_end) {
+    if (!p) return fail("null argument");
+    spiral_gpu_shape s;
+    spiral_gpu_params q = *p;
+    q.direct_upload = 1;  // the image's form does not depend on how the query arrives: no query-size rule here
+    if (shape_of(&q, &s)) return -1;
+    if (j_end == 0 && j_begin == 0) j_end = s.dim0;
+    if (j_begin >= j_end || j_end > s.dim0) return fail("bad first-dimension shard [%u, %u) of %u", j_begin, j_end, s.dim0);
+    return DbLayout::base(s.num_per, j_end - j_begin).limbs_ok() ? 1 : 0;  // (below 64 ciphertexts per slot: option sweep_narrow, as read now)
+}
 int spiral_gpu_get_tables(uint64_t* out) {
     if (!out) return fail("null argument");
     tables_host_rows(out);
@@ -308,7 +320,7 @@ int spiral_gpu_multiply_queries_by_database(uint64_t* outputs, const uint64_t* r
     if (n > kMaxLanes) return fail("at most %u queries per pass", kMaxLanes);
     Scratch sc;
     const size_t db_words = (size_t)kN * dim0 * num_per * 4, dev_words = db_device_words((uint32_t)(2 * num_per), (uint32_t)dim0);
-    const bool mfma = sweep_mfma_ok((uint32_t)num_per, (uint32_t)(2 * dim0));
+    const bool mfma = DbLayout::base((uint32_t)num_per, (uint32_t)dim0).limbs_ok();  // (below 64 ciphertexts per slot: option sweep_narrow)
     uint64_t* d_ref = sc.upload(database, db_words);
     uint64_t* d_db = sc.get(dev_words);
     uint64_t* d_limbs = mfma ? sc.get(dev_words) : nullptr;

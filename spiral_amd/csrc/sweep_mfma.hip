@@ -32,6 +32,8 @@
 // >= 128 ciphertexts per slot, dim0 a power of two in [128, 4096], any number of trials); other pack geometries (num_per <= 4, dim0 < 128) sweep once per
 // query on the vector ALU (pack.hip).
 // A single query may stay on a converted image: the one-query instance of this kernel sweeps it, bit-identical to sweep1_kernel.
+// Base geometries below 128 columns (32, 16, 8 ciphertexts per slot: nu2 = 5, 4, 3) take the same kernel in workgroups of W = nic / 16 = 4, 2, 1 waves, one
+// slot per work item (the W forms below; an image takes them only with option sweep_narrow).  Coverage: sweep_mfma_ok.
 #include <atomic>
 #include <cstdlib>
 #include "common.h"
@@ -416,12 +418,18 @@ struct RecPlan {
 // (l >> 4) 8 + (l & 7) of trial 2 blk + ((l & 15) >> 3): every load instruction is two 512-byte runs, one per trial, and as unconditional as the other
 // forms'.  Ragged ends as NARROW: a surplus wave streams the last pair-block again, the upper half of the last pair-block of an odd number of trials
 // streams the last trial again; both build limbs, meet every barrier and store nothing.
-template <int NT, int ROWS, bool GS = false, bool NARROW = false, bool PAIR = false>
-__global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restrict__ dbl, SweepLanes bt, uint32_t nb, uint32_t nic, uint32_t dim0, uint32_t g_log,
+// W (ROWS = 3, fewer than 128 columns per slot: nic = 64, 32, 16 -- 32, 16, 8 ciphertexts per slot): a workgroup is the W = nic / 16 = 4, 2, 1 waves of ONE slot,
+// 64 W threads, and the chip is filled by more workgroups per CU instead (launch_mfma: 2, 4, 4, each with runs of 4, 2, 2 slots so that the streams still
+// run ahead across items and the results still leave as 16-byte runs).  The body is the wide form's: the 96 nb items of a piece's records spread over
+// 64 W threads (R of them each, up to 12 at W = 1), the staging rows are W waves', and a work item is a slot.  The limbs of a piece are built once per
+// workgroup, that is once per 16 W columns: at W = 1 every wave builds its own.
+template <int NT, int ROWS, bool GS = false, bool NARROW = false, bool PAIR = false, int W = 8>
+__global__ __launch_bounds__(64 * W, W == 1 ? 1 : 2) void sweep_mfma_kernel(const uint4* __restrict__ dbl, SweepLanes bt, uint32_t nb, uint32_t nic, uint32_t dim0, uint32_t g_log,
                                                             uint32_t ls_log, uint32_t n_work, uint32_t zs_log, SweepTrials tr) {
     extern __shared__ __attribute__((aligned(16))) uint4 bq[];
-    constexpr int R = NT >= 5 ? 2 : 1;  // 96 items per query and piece over 512 threads: one each up to five queries
-    constexpr uint32_t buf_sz = 2u * NT * 64u, W = 8;
+    // 32 ROWS items per query and piece, NT tiles hold up to 4 NT / ROWS queries, over 64 W threads (W = 8: one each up to five queries, then two)
+    constexpr int R = (32 * ROWS * ((4 * NT) / ROWS) + 64 * W - 1) / (64 * W);
+    constexpr uint32_t buf_sz = 2u * NT * 64u;
     constexpr bool kZeroC = NT >= 6;
     const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t nk2 = dim0 >> 6, ppi = 2u * nk2, ppi_log = 31u - (uint32_t)__builtin_clz(ppi);  // ppi: pieces per item (both primes), a power of two
@@ -583,11 +591,13 @@ __global__ __launch_bounds__(512, 2) void sweep_mfma_kernel(const uint4* __restr
 }
 
 bool sweep_mfma_ok(uint32_t num_per, uint32_t jm_total) {
-    // whole workgroups of 128 columns, whole pieces of 128 terms; K = 2 dim0 <= 2^12 (combine_limbs' 64-bit sums); the kernel walks a work item's pieces
+    // whole workgroups of 128 columns -- or one workgroup of nic / 16 waves per slot at 64, 32 and 16 columns (the W forms; whether an image TAKES the
+    // form below 128 columns is option sweep_narrow, db_image.h DbLayout::limbs_ok; an image that is in it is swept, updated and converted back whatever
+    // the option says) --, whole pieces of 128 terms; K = 2 dim0 <= 2^12 (combine_limbs' 64-bit sums); the kernel walks a work item's pieces
     // with shifts and masks (ppi_log, nk2 - 1): the first dimension -- a shard [j0, j1) may be any range -- must be a power of two, other shards take the
-    // vector-ALU passes
+    // vector-ALU passes.  8 columns and fewer (nu2 <= 2): less than a block of 16 columns, none
     const uint32_t nic = 2 * num_per, dim0 = jm_total / 2;
-    return nic >= 128 && db_packed(nic, dim0) && (dim0 & 63u) == 0 && (dim0 & (dim0 - 1u)) == 0 && dim0 <= 2048u;
+    return nic >= 16 && db_packed(nic, dim0) && (dim0 & 63u) == 0 && (dim0 & (dim0 - 1u)) == 0 && dim0 <= 2048u;
 }
 void launch_db_limb_planes(const uint64_t* db_packed_img, uint64_t* db_limbs, uint32_t num_per, uint32_t jm_total, hipStream_t s, uint32_t nz) {
     const uint32_t nic = 2 * num_per, dim0 = jm_total / 2;
@@ -602,17 +612,20 @@ void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, 
 namespace {
 
 // one launch of sweep_mfma_kernel<nt, ROWS> over n_work items (dim0: half the terms per column, as the kernel takes it)
-template <int ROWS, bool GS = false, bool NARROW = false, bool PAIR = false>
+template <int ROWS, bool GS = false, bool NARROW = false, bool PAIR = false, int W = 8>
 hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint32_t nt, uint32_t nic, uint32_t dim0, uint32_t g_log, uint32_t ls_log, uint32_t n_work,
                        const SweepTrials& tr, hipStream_t s) {
     // one workgroup per CU (two per CU with half the staging measured 5 % slower); per = 8 nic / 128 items each (base path)
-    const uint32_t n_wg = 256u, per = n_work / n_wg;
-    // results of 2^zs_log consecutive z are staged per wave (8 x nt x 64 x 2^zs_log words) beside the two limb buffers: 8 if that fits the CU's LDS
+    // W < 8 (n_work = 2048 slots): 8 waves per CU again, in 8 / W workgroups of W waves -- but never fewer than 2 slots per workgroup, the least that
+    // leaves as 16-byte runs: 512, 1024, 1024 workgroups of 4, 2, 2 slots at W = 4, 2, 1 (W = 1: 4 waves per CU)
+    const uint32_t n_wg = W == 8 ? 256u : (W == 1 ? 1024u : 2048u / W), per = n_work / n_wg;
+    // results of 2^zs_log consecutive z are staged per wave (W x nt x 64 x 2^zs_log words) beside the two limb buffers: 8 if that fits the CU's LDS
+    // (W < 8: 2^zs_log = per, at most 72 KiB per workgroup at W = 4, 36 KiB at W = 2, 30 KiB at W = 1 -- the CU's 160 KiB hold the 2, 4, 4 of them)
     const size_t lds_b = (size_t)2u * 2u * nt * 1024u;
     uint32_t zs_log = 3;
-    while (zs_log > 1 && ((1u << zs_log) > per || lds_b + ((size_t)8u * nt * 64u * 8u << zs_log) > 160u * 1024u)) zs_log--;
-    const size_t lds = lds_b + ((size_t)8u * nt * 64u * 8u << zs_log);
-    const dim3 grid(n_wg), block(512);
+    while (zs_log > 1 && ((1u << zs_log) > per || lds_b + ((size_t)W * nt * 64u * 8u << zs_log) > 160u * 1024u)) zs_log--;
+    const size_t lds = lds_b + ((size_t)W * nt * 64u * 8u << zs_log);
+    const dim3 grid(n_wg), block(64u * W);
     // more than 64 KiB of dynamic LDS has to be asked for per kernel AND per device: a process may drive servers on several GPUs, from several
     // threads, so the opt-in is remembered per (instance, device) in an atomic bit mask (devices beyond 63 ask every time)
     int dev = 0;
@@ -623,11 +636,11 @@ hipError_t launch_mfma(const uint4* dbl, const SweepLanes& bt, uint32_t n, uint3
         static std::atomic<uint64_t> big{0};                                                                                                       \
         const uint64_t bit = dev < 64 ? 1ull << dev : 0ull;                                                                                        \
         if (!(big.load(std::memory_order_relaxed) & bit)) {                                                                                        \
-            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS, NARROW, PAIR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
+            e = hipFuncSetAttribute((const void*)sweep_mfma_kernel<NTV, ROWS, GS, NARROW, PAIR, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);        \
             if (e != hipSuccess) return e;                                                                                                         \
             big.fetch_or(bit, std::memory_order_relaxed);                                                                                          \
         }                                                                                                                                          \
-        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS, NARROW, PAIR>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
+        hipLaunchKernelGGL((sweep_mfma_kernel<NTV, ROWS, GS, NARROW, PAIR, W>), grid, block, lds, s, dbl, bt, n, nic, dim0, g_log, ls_log, n_work, zs_log, tr);     \
     } while (0)
     switch (nt) {
         case 1: SWEEP_MFMA(1); break;
@@ -660,12 +673,21 @@ hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs
     while ((1u << ls_log) < num_per) ls_log++;
     ls_log -= g_log + k_log;
     const uint32_t nt = (12u * n + 15u) / 16u;
-    if (g_extra) {  // (the rank-major batch layout: no stages)
-        SweepTrials tr{};
-        tr.acc_stride = g_extra;
-        return launch_mfma<3, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs, acc, n), n, nt, nic, dim0, g_log, ls_log, kN * (nic >> 7), tr, s);
+    if (n == 0 || n > kMaxLanes || !sweep_mfma_ok(num_per, jm_total)) return hipErrorInvalidValue;
+    const uint4* dbl = reinterpret_cast<const uint4*>(db_limbs);
+    const SweepLanes bt = sweep_lanes(qs, acc, n);
+    SweepTrials tr{};
+    tr.acc_stride = g_extra;  // (the rank-major batch layout: no stages)
+    const uint32_t n_work = nic >= 128u ? kN * (nic >> 7) : kN;  // below 128 columns a work item is a slot: its nic / 16 blocks are the workgroup's waves
+#define SWEEP_W(WV) (g_extra ? launch_mfma<3, true, false, false, WV>(dbl, bt, n, nt, nic, dim0, g_log, ls_log, n_work, tr, s) \
+                             : launch_mfma<3, false, false, false, WV>(dbl, bt, n, nt, nic, dim0, g_log, ls_log, n_work, tr, s))
+    switch (nic) {
+        case 16: return SWEEP_W(1);
+        case 32: return SWEEP_W(2);
+        case 64: return SWEEP_W(4);
+        default: return SWEEP_W(8);
     }
-    return launch_mfma<3>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs, acc, n), n, nt, nic, dim0, g_log, ls_log, kN * (nic >> 7), SweepTrials{}, s);
+#undef SWEEP_W
 }
 
 bool sweep1_mfma_ok(uint32_t num_per, uint32_t dim0) {

@@ -14,7 +14,7 @@ B = 249561089
 Q = P * B
 
 __all__ = [
-    "N", "P", "B", "Q", "make_params", "get_shape", "get_tables", "ntt_forward", "ntt_inverse", "to_ntt", "to_ntt_no_reduce", "from_ntt",
+    "N", "P", "B", "Q", "make_params", "get_shape", "has_limb_form", "get_tables", "ntt_forward", "ntt_inverse", "to_ntt", "to_ntt_no_reduce", "from_ntt",
     "multiply", "add", "mul_by_const", "automorph", "invert", "gadget_invert", "getRescaled", "multiplyQueryByDatabase", "multiplyQueriesByDatabase", "split_and_crt",
     "foldOneFurtherDimension", "expandImproved", "scalToMat", "regevToGSW", "time_ntt", "time_ntt_digits", "response_wire_bytes", "response_from_wire",
     "query_wire_bytes", "pub_params_wire_bytes", "pack_query_wire_bytes", "pack_pub_params_wire_bytes", "raw_to_wire", "raw_from_wire",
@@ -70,6 +70,17 @@ def get_shape(p: Params) -> Shape:
     s = Shape()
     check(lib().spiral_gpu_get_shape(C.byref(p), C.byref(s)))
     return s
+
+
+def has_limb_form(p: Params, j_begin: int = 0, j_end: int = 0) -> bool:
+    """whether a server of these parameters on the first-dimension shard [j_begin, j_end) ((0, 0): all of it) may hold its database as limb planes, so
+    that a batch (run_query_batch) shares ONE matrix-core pass over it: a shard that is a power of two in [64, 2048] and at least 64 ciphertexts per
+    slot -- or 8, 16 or 32 while option "sweep_narrow" is 1 (set_option; default 0).  A function of the parameters and of that one option as it is
+    now: no GPU needed."""
+    rc = lib().spiral_gpu_has_limb_form(C.byref(p), j_begin, j_end)
+    if rc < 0:
+        check(rc)
+    return bool(rc)
 
 
 def get_tables() -> np.ndarray:

@@ -1,6 +1,7 @@
 """Condenses two `hipcc -Rpass-analysis=kernel-resource-usage` logs of one source file -- the parent commit's and this tree's -- into one line per kernel:
 `same` / `DIFF` / `GONE` for every kernel of the parent (a `NoLanes` instantiation is matched with the parent's kernel of that name without the
-argument; trailing template flags that are `false` are dropped from both sides), then the kernels only the tree has.  The logs are the compiler's stderr:
+argument; trailing template flags that are `false` are dropped from both sides, and so is sweep_mfma_kernel's trailing waves-per-workgroup argument
+at its default 8), then the kernels only the tree has.  The logs are the compiler's stderr:
 
     hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c pack.hip -o /dev/null 2> tree_pack.rpass   (in spiral_amd/csrc)
     python tools/resource_usage_diff.py pack.hip parent_pack.rpass tree_pack.rpass [poly.hip parent_poly.rpass tree_poly.rpass ...]
@@ -28,6 +29,8 @@ def parse(path):
     res = {}
     for mangled, dem in zip(out, names):
         dem = re.sub(r"\(.*$", "", dem.replace("(anonymous namespace)::", "")).replace("void ", "").replace("spiral::", "")
+        if dem.startswith("sweep_mfma_kernel<"):
+            dem = re.sub(r", 8>$", ">", dem)  # W at its default: the wide form, the parent's only one
         dem = re.sub(r"(, false)+>$", ">", dem)  # trailing flags at their default: a template that gained one keeps its kernels' names
         res[dem] = " ".join(f"{short}={out[mangled].get(k)}" for k, short in KEYS)
     return res
