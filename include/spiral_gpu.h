@@ -100,6 +100,9 @@ int spiral_gpu_has_limb_form(const spiral_gpu_params *p, uint32_t j_begin, uint3
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  *   "key_binds"       (get only) the lanes the bind_keys calls of this process have copied keys into (a lane that held them already is not counted)
+ *   "mfma_sweeps"     (get only) the matrix-core sweep launches (csrc/sweep_mfma.hip) this process has made: every call, batch or stage function whose
+ *                     first-dimension pass took the limb-plane form adds one per pass; a replayed hipGraph adds nothing.  What tells the
+ *                     matrix-core form from the vector-ALU one, whose results are the same
  * These three environment variables are the only ones the library reads. */
 int spiral_gpu_set_option(const char *name, int64_t value);
 int spiral_gpu_get_option(const char *name, int64_t *value);
@@ -536,6 +539,15 @@ int spiral_gpu_pack(uint64_t *result, uint32_t out_n, uint32_t m_conv, const uin
  * reorientCiphertextsDim1's layout (:342-362); out: num_per ciphertexts base_dim x 1 NTT */
 int spiral_gpu_fast_multiply_query_by_database_dim1(uint64_t *out, const uint64_t *db, const uint64_t *v_firstdim,
                                                     size_t dim0, size_t num_per);
+/* The same for n <= 8 queries against `trials` database images in ONE pass, the way a batch of clients sweeps a server's trials (no reference
+ * counterpart): dbs = the trials' images one after the other, each in the layout above; v_firstdims = the n queries' buffers one after the other;
+ * outs = [n][trials][num_per] ciphertexts base_dim x 1 NTT, each equal to the one-query call's for that (query, trial).  Where the geometry has a
+ * limb-plane form (spiral_gpu_pack_has_limb_form: 16 ciphertexts per slot and more -- or 8 with option "pack_pair_blocks" -- and a power-of-two first
+ * dimension in [128, 4096]) the pass runs on the matrix cores (csrc/sweep_mfma.hip; "mfma_sweeps" counts it), else as one vector-ALU sweep per query.
+ * The device accumulators are followed by guard words that the call checks: a sweep that stored beyond its last trial fails the call ("wrote past
+ * the last trial").  Fails, before any device call, for n = 0 or > 8, trials = 0, an odd or zero dim0, num_per = 0. */
+int spiral_gpu_fast_multiply_queries_by_database_dim1(uint64_t *outs, const uint64_t *dbs, const uint64_t *v_firstdims, size_t n,
+                                                      size_t trials, size_t dim0, size_t num_per);
 
 /* resident server for testHighRate's server half (src/testing.cpp:1009-1081) */
 int spiral_gpu_pack_server_create(const spiral_gpu_params *p, uint32_t out_n, int device, spiral_gpu_pack_server **out);

@@ -8,7 +8,7 @@ used by the parity tests and the benchmark.  numpy uint64 arrays carry the refer
 from ._lib import PackShape, Params, Shape, SpiralGpuError, build, lib  # noqa: F401
 from .keys import KeyStore, bind_keys  # noqa: F401
 from .ops import *  # noqa: F401,F403
-from .pack import PackServer, fastMultiplyQueryByDatabaseDim1, get_pack_shape, pack  # noqa: F401
+from .pack import PackServer, fastMultiplyQueriesByDatabaseDim1, fastMultiplyQueryByDatabaseDim1, get_pack_shape, pack  # noqa: F401
 from .pack import answer_batch_instances as pack_answer_batch_instances, answer_instances as pack_answer_instances  # noqa: F401
 from .server import Server, answer_batch_instances, first_dim_batch, run_query_batch, run_query_batch_instances, time_sweep_batch  # noqa: F401
 from .server import read_response_wire_batch, set_query_batch  # noqa: F401

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+
+#include <atomic>
+
 #include "common.h"
 
 namespace spiral {
@@ -469,6 +472,9 @@ void launch_db_limb_unplanes(const uint64_t* db_limbs, uint64_t* db_packed_img, 
 // g_extra: the rank-major batch layout, as launch_sweep_batch (k_log = 0 then)
 hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
                              hipStream_t s, uint32_t k_log = 0, uint32_t g_extra = 0);
+// the launch_sweep_mfma / launch_sweep1_mfma calls of this process that returned hipSuccess (get_option "mfma_sweeps"; primitives.cpp).  Host launch calls:
+// one made under stream capture counts once, a replay of the captured graph counts nothing
+extern std::atomic<uint64_t> g_mfma_sweeps;
 // reference DB layout (src/spiral.cpp:1139-1153) -> device layout, for the j-range [j0, j0 + dim0_shard): db_ref holds the nz
 // consecutive z slabs z0 .. z0+nz-1, db_dev is the base of the shard's device database
 void launch_db_relayout(const uint64_t* db_ref, uint64_t* db_dev, uint32_t num_per, uint32_t dim0, uint32_t j0, uint32_t dim0_shard, uint32_t z0,

@@ -260,6 +260,58 @@ int spiral_gpu_fast_multiply_query_by_database_dim1(uint64_t* out, const uint64_
     return download_pk(sc, d_acc, identity_map(), out, num_per * 2);
 }
 
+// The same for n queries against `trials` images, the way a batch sweeps them: ONE matrix-core pass where the geometry has a limb-plane form (wide,
+// NARROW or, with option pack_pair_blocks, PAIR), else one vector-ALU sweep per query.  The accumulators are followed by one trial's worth of guard
+// words; everything is filled with a byte pattern first, and a guard word that changed fails the call: what a ragged group's surplus waves and the
+// empty half of an odd last pair-block must not store would land there (trial index `trials` of the last query).
+int spiral_gpu_fast_multiply_queries_by_database_dim1(uint64_t* outs, const uint64_t* dbs, const uint64_t* v_firstdims, size_t n, size_t trials, size_t dim0,
+                                                      size_t num_per) {
+    if (!outs || !dbs || !v_firstdims) return fail("null argument");
+    if (n == 0 || n > kMaxLanes) return fail("1 to %u queries per pass, not %zu", kMaxLanes, n);
+    if (trials == 0 || trials > (1u << 16)) return fail("1 to 65536 trials, not %zu", trials);
+    if (dim0 < 2 || (dim0 & 1) || dim0 > (1u << 16)) return fail("unsupported first dimension %zu (even, 2 to 65536)", dim0);
+    if (num_per == 0 || num_per > (1u << 16)) return fail("unsupported number of ciphertexts per slot %zu (1 to 65536)", num_per);
+    const uint32_t np = (uint32_t)num_per, d0 = (uint32_t)dim0, nt = (uint32_t)trials;
+    const DbLayout lay = DbLayout::packed1(np, d0, nt);
+    const bool mfma = lay.limbs_ok();  // (8 ciphertexts per slot: option pack_pair_blocks)
+    const size_t ref_words = (size_t)kN * dim0 * num_per, re_words = (size_t)kN * dim0 * 2, trial_acc = num_per * 2 * kN, query_acc = trials * trial_acc;
+    constexpr int kFill = 0xA5;  // no accumulator word: both halves are above the moduli
+    Scratch sc;
+    uint64_t* d_ref = sc.upload(dbs, trials * ref_words);
+    uint64_t* d_db = sc.get(trials * lay.trial_words);
+    uint64_t* d_limbs = mfma ? sc.get(trials * lay.trial_words) : nullptr;
+    uint64_t* d_re = sc.upload(v_firstdims, n * re_words);
+    uint64_t* d_qs = sc.get(n * re_words);
+    uint64_t* d_acc = sc.get(n * query_acc + trial_acc);
+    if (!d_ref || !d_db || (mfma && !d_limbs) || !d_re || !d_qs || !d_acc) return fail("device allocation/upload failed");
+    HIP_OK(hipMemsetAsync(d_acc, kFill, (n * query_acc + trial_acc) * sizeof(uint64_t), 0));
+    for (uint32_t t = 0; t < nt; t++) {
+        launch_db1_relayout(d_ref + t * ref_words, d_db + t * lay.trial_words, np, d0, 0);
+        if (mfma) launch_db1_limb_planes(d_db + t * lay.trial_words, d_limbs + t * lay.trial_words, np, d0, 0, kN);
+    }
+    const uint32_t* qs[kMaxLanes];
+    uint64_t* acc[kMaxLanes];
+    for (size_t b = 0; b < n; b++) {
+        qs[b] = (const uint32_t*)(d_qs + b * re_words);
+        acc[b] = d_acc + b * query_acc;
+        launch_qs1_from_reoriented(d_re + b * re_words, (uint32_t*)qs[b], d0, 0);
+    }
+    if (mfma) {
+        const hipError_t e = launch_sweep1_mfma(d_limbs, qs, acc, (uint32_t)n, np, d0, nt, lay.trial_words, trial_acc, 0);
+        if (e != hipSuccess) return fail("the matrix-core sweep could not be launched: %s", hipGetErrorString(e));
+    } else {
+        for (size_t b = 0; b < n; b++) launch_sweep1(d_db, qs[b], acc[b], np, d0, nt, lay.trial_words, trial_acc, 0);
+    }
+    HIP_OK(hipGetLastError());
+    std::vector<uint64_t> guard(trial_acc);
+    HIP_OK(hipMemcpy(guard.data(), d_acc + n * query_acc, trial_acc * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    uint64_t fill = 0;
+    memset(&fill, kFill, sizeof(fill));
+    for (size_t k = 0; k < trial_acc; k++)
+        if (guard[k] != fill) return fail("the sweep wrote past the last trial (guard word %zu)", k);
+    return download_pk(sc, d_acc, identity_map(), outs, n * trials * num_per * 2);
+}
+
 int spiral_gpu_pack_server_create(const spiral_gpu_params* p, uint32_t out_n, int device, spiral_gpu_pack_server** out) {
     return spiral_gpu_pack_server_create_sharded(p, out_n, device, 0, 0, out);
 }

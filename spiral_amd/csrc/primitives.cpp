@@ -6,6 +6,8 @@
 thread_local std::string spiral::host::g_err;
 // SpiralPack batch calls of this process that ran as one lane-aware launch sequence (get_option "pack_lane_batches"; counted by pack_server.cpp)
 std::atomic<uint64_t> spiral::host::g_pack_lane_batches{0};
+// matrix-core sweep launches of this process that were made (get_option "mfma_sweeps"; counted by the two launchers of sweep_mfma.hip)
+std::atomic<uint64_t> spiral::g_mfma_sweeps{0};
 
 // the process-wide options (kernels.h); the three documented environment variables give their initial values, once
 spiral::Options& spiral::options() {
@@ -71,6 +73,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else if (n == "key_binds") *value = (int64_t)g_key_binds.load();  // (read only)
+    else if (n == "mfma_sweeps") *value = (int64_t)g_mfma_sweeps.load(std::memory_order_relaxed);  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;
 }

@@ -306,7 +306,8 @@ __device__ __forceinline__ int64_t quad_dpp(int64_t x) {  // quad_perm exchange 
 
 // acc[i][t][e] = c_{i,l}: database limb i, query limb l = lane & 3, row (lane >> 4) * 4 + e of the column block, column n = 16 t + (lane & 15) =
 // 12 q + 4 r + l.  The result for (row e, query q, row r) is  sum_{i,l} 2^{8 (i + l)} c_{i,l}  mod M  =  sum_l U_l mod M  with
-// U_l = sum_i c_{i,l} T_{i+l},  T_w = 2^{8 w} mod M  (|U_l| < 2^56 for K <= 2^12: 64-bit MADs in lane l, no reduction); the four U_l of a quad are
+// U_l = sum_i c_{i,l} T_{i+l},  T_w = 2^{8 w} mod M  (64-bit MADs in lane l, no reduction: with every limb at the far end of its box -- |bytes| <= 128, tops <= 15
+// and 16 -- a term adds at most 2^39.3 (p) / 2^41.2 (b) to sum_l |U_l|, so K <= 2^12 terms stay below 2^53.2; tests/limb_edges.py box_bound); the four U_l of a quad are
 // summed so that lane e ends up with the sum for row e (two quad_perm exchange steps: keep the rows of my parity, then of my half), one
 // reduction mod M per lane and tile.
 template <int NT, uint32_t M>
@@ -331,7 +332,7 @@ __device__ __forceinline__ void combine_limbs(const v4i (&acc)[4][NT], uint32_t 
         const int64_t s0 = (odd ? u[1] : u[0]) + quad_dpp<0xB1>(odd ? u[0] : u[1]), s1 = (odd ? u[3] : u[2]) + quad_dpp<0xB1>(odd ? u[2] : u[3]);
         // step 2 with lane ^ 2: I keep row e = l (s0 in the low half of the quad, s1 in the high half)
         const int64_t sum = (hi ? s1 : s0) + quad_dpp<0x4E>(hi ? s0 : s1);
-        res[t] = mod_est<M>((uint64_t)(sum + (int64_t)((uint64_t)M << 30)));  // |sum| < 2^57.2 < M 2^30
+        res[t] = mod_est<M>((uint64_t)(sum + (int64_t)((uint64_t)M << 30)));  // |sum| < 2^53.2 < M 2^30: 0 < x < 2^59
     }
 }
 
@@ -664,6 +665,11 @@ SweepLanes sweep_lanes(const uint32_t* const* qs, uint64_t* const* acc, uint32_t
     return bt;
 }
 
+hipError_t counted(hipError_t e) {  // g_mfma_sweeps: the launches that were made
+    if (e == hipSuccess) g_mfma_sweeps.fetch_add(1, std::memory_order_relaxed);
+    return e;
+}
+
 }  // namespace
 
 hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs, uint64_t* const* acc, uint32_t n, uint32_t num_per, uint32_t jm_total, uint32_t g_log,
@@ -682,10 +688,10 @@ hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs
 #define SWEEP_W(WV) (g_extra ? launch_mfma<3, true, false, false, WV>(dbl, bt, n, nt, nic, dim0, g_log, ls_log, n_work, tr, s) \
                              : launch_mfma<3, false, false, false, WV>(dbl, bt, n, nt, nic, dim0, g_log, ls_log, n_work, tr, s))
     switch (nic) {
-        case 16: return SWEEP_W(1);
-        case 32: return SWEEP_W(2);
-        case 64: return SWEEP_W(4);
-        default: return SWEEP_W(8);
+        case 16: return counted(SWEEP_W(1));
+        case 32: return counted(SWEEP_W(2));
+        case 64: return counted(SWEEP_W(4));
+        default: return counted(SWEEP_W(8));
     }
 #undef SWEEP_W
 }
@@ -725,20 +731,20 @@ hipError_t launch_sweep1_mfma(const uint64_t* db_limbs, const uint32_t* const* q
     if (num_per == 8u) {  // PAIR: groups of 8 pair-blocks of two trials (the last group, and the last pair-block, may be ragged)
         if (trials > (0xFFFFFFFFu >> kLogN)) return hipErrorInvalidValue;
         const SweepTrials tr{db_stride / 2u, acc_stride, 0, trials};
-        return launch_mfma<2, false, false, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0,
-                                                  kN * (((trials + 1u) / 2u + 7u) / 8u), tr, s);
+        return counted(launch_mfma<2, false, false, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0,
+                                                          kN * (((trials + 1u) / 2u + 7u) / 8u), tr, s));
     }
     if (num_per < 128u) {  // NARROW: 2^grp_log blocks of 16 columns per trial, groups of 8 blocks across trials (the last one may be ragged)
         while ((16u << grp_log) < num_per) grp_log++;
         if (trials > (0xFFFFFFFFu >> (grp_log + kLogN))) return hipErrorInvalidValue;
         const uint32_t blocks = trials << grp_log;
         const SweepTrials tr{db_stride / 2u, acc_stride, grp_log, blocks};
-        return launch_mfma<2, false, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0, kN * ((blocks + 7u) / 8u), tr,
-                                           s);
+        return counted(launch_mfma<2, false, true>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0,
+                                                   kN * ((blocks + 7u) / 8u), tr, s));
     }
     while ((128u << grp_log) < num_per) grp_log++;
     const SweepTrials tr{db_stride / 2u, acc_stride, grp_log, 0};
-    return launch_mfma<2>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0, (kN << grp_log) * trials, tr, s);
+    return counted(launch_mfma<2>(reinterpret_cast<const uint4*>(db_limbs), sweep_lanes(qs1, acc, n), n, nt, num_per, dim0 / 2u, 0, 0, (kN << grp_log) * trials, tr, s));
 }
 
 }  // namespace spiral

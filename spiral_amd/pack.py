@@ -50,6 +50,18 @@ def fastMultiplyQueryByDatabaseDim1(db, v_firstdim, dim0, num_per) -> np.ndarray
     return out
 
 
+def fastMultiplyQueriesByDatabaseDim1(dbs, v_firstdims, dim0, num_per) -> np.ndarray:
+    """n = len(v_firstdims) <= 8 reoriented queries against the len(dbs) trial images in ONE pass (one launch on the matrix cores where the geometry
+    has a limb-plane form -- get_option("mfma_sweeps") rises by one --, else one vector-ALU sweep per query): out[b][t] is
+    fastMultiplyQueryByDatabaseDim1(dbs[t], v_firstdims[b], dim0, num_per)"""
+    n, trials = len(v_firstdims), len(dbs)
+    db = np.stack([_c(d).reshape(-1) for d in dbs]) if trials else np.zeros(1, dtype=np.uint64)
+    re = np.stack([_c(v).reshape(-1) for v in v_firstdims]) if n else np.zeros(1, dtype=np.uint64)
+    out = np.zeros((max(n, 1), max(trials, 1), num_per, 2, 2, N), dtype=np.uint64)
+    check(lib().spiral_gpu_fast_multiply_queries_by_database_dim1(_p(out), _p(db), _p(re), n, trials, dim0, num_per))
+    return out
+
+
 class PackServer:
     def __init__(self, params: Params, out_n: int, device: int = 0, trial0: int = 0, trial1: int = 0):
         """trial0, trial1: this server's share [trial0, trial1) of the out_n^2 trials (N GPUs); 0, 0 = all of them"""

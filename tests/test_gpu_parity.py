@@ -1,8 +1,14 @@
 """GPU parity tests: every seam of the C ABI against the oracle on the same seeded inputs.
 Bit-exact: the whole path is unsigned integer arithmetic (raw-domain values compared verbatim,
 NTT-domain values compared as canonical residues, SURVEY.md section 8c hazard 1)."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import limb_edges as L  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -817,16 +823,8 @@ def test_matrix_core_sweep_random_geometries_and_edge_values(sa, oracle, seed):
     nu1, nu2 = int(rng.integers(6, 8)), int(rng.integers(6, 8))
     n = int(rng.integers(1, 9))
     dim0, num_per = 1 << nu1, 1 << nu2
-    wrap = (1 << 28) - 0x808080
-    edges = {0: [0, 1, O.P - 1, O.P - 2, wrap - 1, wrap, wrap + 1, (15 << 24) - 0x808080, (14 << 24) - 0x808080 + 0xFFFFFF, 0x808080, 0x7F7F7F],
-             1: [0, 1, O.B - 1, O.B - 2, (14 << 24) - 0x808080, (13 << 24) - 0x808080 + 0xFFFFFF, 0x808080, 0x7F7F7F, 0x800000, 0x7FFFFF, 1 << 27]}
-
-    def sprinkle(a, limb_axis):  # a[..., limb, z]: replace ~3 % of the residues by edge values of their prime
-        for limb, mod in ((0, O.P), (1, O.B)):
-            view = np.moveaxis(a, limb_axis, 0)[limb]
-            mask = rng.random(view.shape) < 0.03
-            vals = np.array([v for v in edges[limb] if v < mod], dtype=np.uint64)
-            view[mask] = vals[rng.integers(0, len(vals), size=int(mask.sum()))]
+    assert (L.P, L.B) == (O.P, O.B)
+    sprinkle = lambda a, limb_axis: L.sprinkle(rng, a, limb_axis)  # the edge values and their 3 % rate: tests/limb_edges.py
 
     res = []
     for _ in range(n):
