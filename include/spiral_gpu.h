@@ -79,7 +79,7 @@ int spiral_gpu_has_limb_form(const spiral_gpu_params *p, uint32_t j_begin, uint3
  *                     packed and the limb-plane form (spiral_gpu_server_set_db_format); 0 = a second image beside the first
  *   "fwd2"            -1 (default) the two-digits-per-workgroup transform kernel from "fwd2_min" transforms per launch; 0 never; 1 always
  *   "fwd2_min"        that threshold (default 8192 transforms per launch, all query lanes together)
- *   "db_stage_bytes"  bytes of the staging buffer of load_db / load_db_items (default 64 MiB).  Initial value: SPIRAL_DB_STAGE_BYTES.
+ *   "db_stage_bytes"  bytes of the staging buffer of load_db / load_db_items / read_db_items (default 64 MiB).  Initial value: SPIRAL_DB_STAGE_BYTES.
  *   "pack_item_group" instances per group of spiral_gpu_pack_server_answer_batch_instances (default 0: automatic; g: at most g)
  *   "pack_batch_lanes" 0 .. 8 (default 0 = never: opt-in): the smallest number of clients from which spiral_gpu_pack_server_answer_batch and
  *                     ..._answer_batch_instances (and their _wire / _seeded forms) take the lane form -- every launch carries all clients; 0 = never.
@@ -100,6 +100,7 @@ int spiral_gpu_has_limb_form(const spiral_gpu_params *p, uint32_t j_begin, uint3
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  *   "key_binds"       (get only) the lanes the bind_keys calls of this process have copied keys into (a lane that held them already is not counted)
+ *   "db_export_ns"    (get only) device nanoseconds of the launches of this process's last read_db_items / read_db_items_at call, its copies excluded
  *   "mfma_sweeps"     (get only) the matrix-core sweep launches (csrc/sweep_mfma.hip) this process has made: every call, batch or stage function whose
  *                     first-dimension pass took the limb-plane form adds one per pass; a replayed hipGraph adds nothing.  What tells the
  *                     matrix-core form from the vector-ALU one, whose results are the same
@@ -227,6 +228,30 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server *s, const void *items, uin
  * previous update's launches (whose workspace it reuses) and for nothing else. */
 int spiral_gpu_server_update_db_items(spiral_gpu_server *s, const void *items, uint32_t coeff_bits, const uint64_t *item_ids,
                                       uint64_t n);
+/* bytes of n items in the bit-packed item stream of load_db_items / read_db_items: n * polys * 2048 * coeff_bits / 8, polys = 4 for a base
+ * server (out_n = 0), 1 for a SpiralPack trial (out_n >= 1).  0 and last_error for coeff_bits outside 1..64 or 2^coeff_bits < p_db.  Host only. */
+size_t spiral_gpu_db_items_bytes(const spiral_gpu_params *p, uint32_t out_n, uint32_t coeff_bits, uint64_t n_items);
+/* The database back as plaintexts: items first_item .. first_item + n_items - 1 (read_db_items) or items item_ids[0 .. n) (read_db_items_at)
+ * of the image this server references, byte for byte what load_db_items / update_db_items take.
+ * Layout: item k of the call is at byte k * polys * 256 * coeff_bits of `items` (polys = 4); polynomial (m, c) at (m*n2 + c) * 2048
+ * coefficients; coefficients coeff_bits wide in little-endian bit order, coeff_bits = 64: plain u64 words.  A polynomial is a whole number of
+ * bytes (256 * coeff_bits), written whole: no byte of a neighbouring item is read or rewritten.
+ * Undoing the lift: the ingest maps a plaintext value x < half = p_db >> 1 to x and x >= half to Q - (p_db - x).  So a lifted coefficient
+ * v < half gives x = v, v >= Q - (p_db - half) gives x = v - Q + p_db, and any other v is NOT a plaintext image (after fill_db_random or a
+ * load_db of arbitrary words): the call fails, the message says so and names the first offending item (lowest position in the call) and
+ * coefficient; the contents of `items` are then unspecified.  The image, its form, its epoch and every captured graph are untouched, always.
+ * Form: the image is read in the form it is in -- packed or plain, or limb planes (wide, and the 4-, 2- and 1-wave narrow forms) -- no
+ * conversion is needed or made.  With option one_image = 0, `db` is read in the form db_format names; a second image is ignored.
+ * Shards: a j-sharded server writes only the items of its own j-range and leaves the other items' bytes of `items` untouched, so G shards
+ * fill one buffer (the mirror of load_db_items); read_db_items_at skips ids outside the shard the same way.  Ids need not be distinct or
+ * sorted; every id must be < dim0 * num_per, which is checked before anything is launched.
+ * Who may call: any server that references a loaded image, lanes and share_db servers included (reading does not write); "no database
+ * loaded" otherwise.  Fails inside a stream capture.
+ * Ordering: enqueued on this server's stream -- an update enqueued earlier on that stream is visible -- and the call returns after that stream
+ * is synchronised and `items` is complete.  Staged through device memory in passes of option db_stage_bytes (one launch and one copy each).
+ * Before any launch: null pointers, a range outside the database, coeff_bits outside 1..64 or 2^coeff_bits < p_db (64 always passes). */
+int spiral_gpu_server_read_db_items(spiral_gpu_server *s, void *items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items);
+int spiral_gpu_server_read_db_items_at(spiral_gpu_server *s, void *items, uint32_t coeff_bits, const uint64_t *item_ids, uint64_t n);
 /* read the device database back in reference layouts (tests): plaintext `item` as its n0 x n2 NTT-form MatPoly
  * (pts_encd, :1128), or slabs z_begin .. z_begin+nz-1 of load_db's layout restricted to this server's j-range:
  * word (z, ii, c, j, m) at ((((z - z_begin)*num_per + ii)*n2 + c)*(j_end - j_begin) + (j - j_begin))*n0 + m */
@@ -579,6 +604,14 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server *s, uint32_t tri
  * trial image's current form, on this server's stream, with the same rules for failure and ordering; any other trial fails. */
 int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server *s, uint32_t trial, const void *items, uint32_t coeff_bits,
                                            const uint64_t *item_ids, uint64_t n);
+/* spiral_gpu_server_read_db_items / _at for one trial of this server's trial range: 1 x 1 plaintexts (polys = 1, item k at byte
+ * k * 256 * coeff_bits), from the trial image in its current form -- packed or plain, or limb planes in the wide, narrow and 8-column pair
+ * forms -- with the same layout, validity rule, failures and ordering; the owner or a lane may call; any other trial fails, as for the update.
+ * (A SpiralPack server holds whole trials: there is no j-shard to skip.) */
+int spiral_gpu_pack_server_read_db_items(spiral_gpu_pack_server *s, uint32_t trial, void *items, uint32_t coeff_bits, uint64_t first_item,
+                                         uint64_t n_items);
+int spiral_gpu_pack_server_read_db_items_at(spiral_gpu_pack_server *s, uint32_t trial, void *items, uint32_t coeff_bits,
+                                            const uint64_t *item_ids, uint64_t n);
 /* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv).  A null pointer
  * among those the geometry needs fails before anything is written: the previous public parameters stay (as for spiral_gpu_server_set_pub_params). */
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server *s, const uint64_t *w_left, const uint64_t *w_right,

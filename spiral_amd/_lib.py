@@ -112,6 +112,9 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_read_response_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "spiral_gpu_server_load_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_server_update_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_db_items_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32, C.c_uint32, C.c_uint64]),
+    "spiral_gpu_server_read_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_server_read_db_item": (C.c_int, [C.c_void_p, C.c_uint64, U64P]),
     "spiral_gpu_server_read_db_slots": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, U64P]),
     "spiral_gpu_server_read_db_columns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, U64P]),
@@ -179,6 +182,8 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_fill_db_random": (C.c_int, [C.c_void_p, C.c_uint64]),
     "spiral_gpu_pack_server_load_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_pack_server_update_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_pack_server_read_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_pack_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_pack_server_set_pub_params": (C.c_int, [C.c_void_p, U64P, U64P, U64P, U64P]),
     "spiral_gpu_pack_server_answer": (C.c_int, [C.c_void_p, U64P, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_read_acc": (C.c_int, [C.c_void_p, C.c_uint32, U64P]),
@@ -283,6 +288,40 @@ def wire_bytes(wire) -> np.ndarray:
     if wire.dtype != np.uint8:
         raise TypeError(f"a wire message is bytes or a uint8 array, not {wire.dtype}")
     return wire.reshape(-1)
+
+
+def db_items_bytes(params: Params, coeff_bits: int, n_items: int, out_n: int = 0) -> int:
+    """bytes of n_items plaintexts in the item stream of load_db_items / read_db_items: 4 polynomials per item of a base server (out_n = 0), one per
+    item of a SpiralPack trial (out_n >= 1); raises for a coefficient width outside 1..64 or too narrow for p_db"""
+    if not isinstance(coeff_bits, (int, np.integer)) or isinstance(coeff_bits, bool) or not 0 <= coeff_bits < 2**32:
+        raise ValueError(f"coeff_bits = {coeff_bits!r} is not in 1..64")
+    n = lib().spiral_gpu_db_items_bytes(C.byref(params), out_n, int(coeff_bits), n_items)
+    if n == 0 and n_items:
+        raise SpiralGpuError(lib().spiral_gpu_last_error().decode())
+    return n
+
+
+def read_args(params: Params, coeff_bits: int, n_items: int, out_n: int, out):
+    """the output buffer of a read_db_items call: a fresh zeroed uint8 array of n_items plaintexts, or the caller's `out` (a contiguous uint8 array of
+    exactly that size: the shards of a database fill one buffer, each its own items)"""
+    nbytes = db_items_bytes(params, coeff_bits, n_items, out_n)
+    if out is None:
+        return np.zeros(nbytes, dtype=np.uint8)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable and out.size == nbytes):
+        raise ValueError(f"out must be a writable contiguous uint8 array of {nbytes} bytes")
+    return out
+
+
+def read_ids(item_ids) -> np.ndarray:
+    """the id list of a read_db_items_at call (duplicates and any order are fine) -> uint64"""
+    ids = np.asarray(item_ids)
+    if ids.ndim != 1:
+        raise ValueError("item_ids must be a flat list of item indices")
+    if ids.size and ids.dtype.kind not in "iu":
+        raise TypeError(f"item_ids must be integers, not {ids.dtype}")
+    if ids.size and ids.dtype.kind == "i" and (ids < 0).any():
+        raise ValueError("item_ids must be non-negative")
+    return np.ascontiguousarray(ids, dtype=np.uint64)
 
 
 def update_args(items, coeff_bits: int, item_ids, polys_per_item: int):

@@ -184,6 +184,17 @@ struct DbImage {
         }
         return u;
     }
+
+    // what read_db_items reads of trial t: db in the form `format` names (a second image of option one_image = 0 is not looked at)
+    ExportImage export_source(uint32_t t = 0) const {
+        ExportImage x{};
+        x.db = db.p + (size_t)t * lay.trial_words;
+        x.pack = lay.pack;
+        x.form = format != SPIRAL_GPU_DB_LIMBS ? DBX_PACKED : lay.pack && lay.num_per == 8u ? DBX_LIMBS8 : DBX_LIMBS;
+        x.num_per = lay.num_per;
+        x.dim0 = lay.dim0;
+        return x;
+    }
 };
 
 }  // namespace host

@@ -23,6 +23,7 @@ namespace host {
 
 extern thread_local std::string g_err;
 extern std::atomic<uint64_t> g_pack_lane_batches;  // primitives.cpp: what get_option("pack_lane_batches") reads
+extern std::atomic<uint64_t> g_db_export_ns;       // primitives.cpp: what get_option("db_export_ns") reads
 
 inline int fail(const char* fmt, ...) {
     char buf[512];
@@ -475,6 +476,149 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(W.done, st));
     W.pending = true;
+    return 0;
+}
+
+// ---- items out of the image as plaintexts (read_db_items / read_db_items_at of both servers): the mirror of ingest_items ------------------------
+// the coefficient width of an exported item stream: 1 .. 64 bits, wide enough for every value below p_db (64 always is)
+inline int check_export_width(uint32_t coeff_bits, uint64_t p_db) {
+    if (coeff_bits < 1 || coeff_bits > 64) return fail("coeff_bits = %u is not in 1..64", coeff_bits);
+    if (coeff_bits < 64 && (1ull << coeff_bits) < p_db) return fail("coeff_bits = %u cannot hold values below p_db = %llu", coeff_bits, (unsigned long long)p_db);
+    return 0;
+}
+// A server's workspace, reused from call to call: one device buffer [error word][work table][staged items] and, for the _at form, a pinned bounce
+// buffer of one pass.  Per server, not per image: lanes read their owner's image on their own streams.
+struct ExportWork {
+    DevBuf dev;
+    uint8_t* host = nullptr;
+    size_t host_bytes = 0;
+    std::vector<hipEvent_t> ev;  // two per pass, around its launch: the call's device time without its copies (option "db_export_ns")
+    void release() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        ev.clear();
+        dev.release();
+        dev.words = 0;
+        if (host) (void)hipHostFree(host);
+        host = nullptr;
+        host_bytes = 0;
+    }
+};
+// the image as the export reads it: `db` in the form `form` names (kernels.h DbExportForm), dim0 = the shard's first dimension on the base path
+struct ExportImage {
+    const uint64_t* db;
+    uint32_t pack, form, num_per, dim0;
+};
+// one item of an _at call that this server holds: its position in the caller's list, j local to the image, column ii
+struct ExportItem {
+    uint64_t pos;
+    uint32_t j, ii;
+};
+// The shared body.  Range form (sel == null): the n LOCAL items first_l .. first_l + n - 1 (local item = j local * num_per + ii) go to positions
+// pos0 .. pos0 + n - 1 of `items`; table form: item sel[k] goes to position sel[k].pos.  Position k of `items` is at byte k * item_bytes; bytes of other
+// positions are not touched.  Staged in passes of option db_stage_bytes: one launch and one device-to-host copy per pass, one read of the error word at
+// the end.  Returns after `st` is synchronised.  item_of(position): the database index the failure message names.
+template <class ItemOf>
+inline int export_items(ExportWork& W, const DeviceTables& tb, hipStream_t st, void* items, uint32_t coeff_bits, uint64_t p_db, const ExportImage& img,
+                        uint64_t first_l, uint64_t n, uint64_t pos0, const std::vector<ExportItem>* sel, ItemOf item_of) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("read_db_items cannot be called while the server's stream is being captured");
+    if (check_export_width(coeff_bits, p_db)) return -1;
+    if (sel) n = sel->size();
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFFFull) return fail("at most 2^32 - 1 items per read");
+    const uint32_t polys = img.pack ? 1u : 4u;
+    const size_t item_bytes = (size_t)polys * kN * coeff_bits / 8;
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>({options().db_stage_bytes / item_bytes, (uint64_t)(1u << 18), n}));  // (tests force several passes)
+    // the work table of the _at form, in the block order of a range export (db_export.hip): band of rows, group of columns
+    std::vector<uint4> table;
+    if (sel) {
+        const uint32_t rows = img.pack ? 16u : 8u, cols = img.pack ? 8u : 4u;
+        std::vector<ExportItem> order(*sel);
+        auto key = [&](const ExportItem& e) { return ((uint64_t)(e.j / rows) << 40) | ((uint64_t)(e.ii / cols) << 20) | ((uint64_t)(e.j % rows) << 8) | (e.ii % cols); };
+        std::stable_sort(order.begin(), order.end(), [&](const ExportItem& a, const ExportItem& b) { return key(a) < key(b); });
+        table.reserve(n);
+        for (uint64_t k = 0; k < n; k++) table.push_back(make_uint4(order[k].j, order[k].ii, (uint32_t)(k % chunk), (uint32_t)order[k].pos));
+    }
+    const size_t o_table = 16, o_stage = o_table + table.size() * sizeof(uint4), dev_bytes = o_stage + chunk * item_bytes;
+    if (W.dev.words * 8 < dev_bytes) {
+        W.dev.release();
+        W.dev.words = 0;
+        if (W.dev.alloc((dev_bytes + 7) / 8)) {
+            (void)hipGetLastError();
+            W.dev.p = nullptr;
+            W.dev.words = 0;
+            return fail("no device memory for the export's staging (%zu bytes)", dev_bytes);
+        }
+    }
+    if (sel && W.host_bytes < chunk * item_bytes) {
+        if (W.host) (void)hipHostFree(W.host);
+        W.host = nullptr;
+        W.host_bytes = 0;
+        if (hipHostMalloc((void**)&W.host, chunk * item_bytes, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("no pinned host memory for the export's bounce buffer (%zu bytes)", (size_t)(chunk * item_bytes));
+        }
+        W.host_bytes = chunk * item_bytes;
+    }
+    uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
+    uint8_t* out = static_cast<uint8_t*>(items);
+    HIP_OK(hipMemsetAsync(d, 0xFF, 16, st));  // the error word: ~0 = every coefficient so far is a plaintext's
+    if (sel) HIP_OK(hipMemcpyAsync(d + o_table, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice, st));
+    DbExportParams xp{};
+    xp.db = img.db;
+    xp.out = d + o_stage;
+    xp.err = reinterpret_cast<unsigned long long*>(d);
+    xp.pack = img.pack;
+    xp.form = img.form;
+    xp.num_per = img.num_per;
+    xp.dim0 = img.dim0;
+    xp.coeff_bits = coeff_bits;
+    xp.p_db = p_db;
+    const size_t passes = (size_t)((n + chunk - 1) / chunk);
+    while (W.ev.size() < 2 * passes) {
+        hipEvent_t e = nullptr;
+        HIP_OK(hipEventCreate(&e));
+        W.ev.push_back(e);
+    }
+    for (uint64_t done = 0; done < n; done += chunk) {
+        const uint64_t cnt = std::min(chunk, n - done);
+        const size_t pass = (size_t)(done / chunk);
+        xp.n = (uint32_t)cnt;
+        if (sel) {
+            xp.table = reinterpret_cast<const uint4*>(d + o_table) + done;
+        } else {
+            xp.first = first_l + done;
+            xp.pos_base = pos0 + done;
+        }
+        HIP_OK(hipEventRecord(W.ev[2 * pass], st));
+        launch_db_export(tb, xp, st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(W.ev[2 * pass + 1], st));
+        if (sel) {  // through the bounce buffer to the items' places
+            HIP_OK(hipMemcpyAsync(W.host, xp.out, (size_t)cnt * item_bytes, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            for (uint64_t k = 0; k < cnt; k++) memcpy(out + (size_t)table[done + k].w * item_bytes, W.host + (size_t)k * item_bytes, item_bytes);
+        } else {  // (stream order keeps the next pass's launch behind this copy)
+            HIP_OK(hipMemcpyAsync(out + (size_t)(pos0 + done) * item_bytes, xp.out, (size_t)cnt * item_bytes, hipMemcpyDeviceToHost, st));
+        }
+    }
+    unsigned long long err = 0;
+    HIP_OK(hipMemcpyAsync(&err, d, sizeof(err), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    double dev_ms = 0;
+    for (size_t k = 0; k < passes; k++) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, W.ev[2 * k], W.ev[2 * k + 1]));
+        dev_ms += ms;
+    }
+    g_db_export_ns.store((uint64_t)(dev_ms * 1e6));
+    if (err != ~0ull) {
+        const uint64_t poly = err / kN, pos = poly / polys;
+        return fail("the image holds no plaintext at item %llu (polynomial %u, coefficient %u lifts to a value outside the centred range of p_db): "
+                    "not a plaintext image (fill_db_random, or a load_db of arbitrary words)",
+                    (unsigned long long)item_of(pos), (uint32_t)(poly % polys), (uint32_t)(err % kN));
+    }
     return 0;
 }
 

@@ -532,6 +532,46 @@ __device__ __forceinline__ void db1_put_word(uint64_t* db, uint32_t z, uint32_t 
         db[db1_word_index(z, j, ii, num_per, dim0)] = v;
     }
 }
+// read one word of a trial image back (the inverse of db1_put_word): the packed and the plain layout
+__device__ __forceinline__ uint64_t db1_get_word(const uint64_t* db, uint32_t z, uint32_t j, uint32_t ii, uint32_t num_per, uint32_t dim0) {
+    if (db1_packed(num_per, dim0)) {
+        const uint8_t* bytes = reinterpret_cast<const uint8_t*>(db);
+        uint64_t f = 0;
+#pragma unroll
+        for (uint32_t by = 0; by < 7; by++) f |= (uint64_t)bytes[db1_packed_byte(z, j, ii, by, num_per, dim0)] << (8u * by);
+        return (f & 0xFFFFFFFull) | ((f >> 28) << 32);
+    }
+    return db[db1_word_index(z, j, ii, num_per, dim0)];
+}
+// The same word from the limb-plane form of a trial image (sweep_mfma.hip, db_update.hip; common.h db_get_word_limbs with columns ii and terms
+// k = j): [z][16 columns][prime][piece of 128 terms][7 planes], chunk c = (j & 127) >> 6, lane = (((j & 127) >> 4) & 3) * LW + column, byte j & 15.
+// PLANE = 1024 (LW = 16: the wide and the narrow form, num_per >= 16) or 512 (LW = 8, one column block per slot: the pair form, num_per = 8).
+template <uint32_t PLANE>
+__device__ __forceinline__ uint64_t db1_get_word_planes(const uint64_t* db, uint32_t z, uint32_t j, uint32_t ii, uint32_t num_per, uint32_t dim0) {
+    constexpr uint32_t LW = PLANE / 64u;
+    const uint8_t* bytes = reinterpret_cast<const uint8_t*>(db);
+    const uint32_t nk2 = dim0 >> 7, t = j & 127u, c = t >> 6, lane = ((t >> 4) & 3u) * LW + (ii & (LW - 1u)), e = t & 15u;
+    const uint32_t nblk = PLANE == 512u ? 1u : num_per >> 4, blk = PLANE == 512u ? 0u : ii >> 4;
+    uint32_t res[2];
+#pragma unroll
+    for (uint32_t pr = 0; pr < 2; pr++) {
+        const size_t piece = (((size_t)z * nblk + blk) * 2u + pr) * nk2 + (j >> 7);  // 7 planes each
+        const uint8_t* b = bytes + piece * (7u * PLANE) + (size_t)lane * 16u + e;
+        uint32_t w = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 3; i++) w |= (uint32_t)(b[(2u * i + c) * PLANE] ^ 0x80u) << (8u * i);
+        w |= ((uint32_t)(b[6u * PLANE] >> (4u * c)) & 0xFu) << 24;
+        const int32_t a = (int32_t)w - 0x808080;
+        res[pr] = a < 0 ? (uint32_t)(a + (int32_t)(pr ? kB : kP)) : (uint32_t)a;
+    }
+    return (uint64_t)res[0] | ((uint64_t)res[1] << 32);
+}
+__device__ __forceinline__ uint64_t db1_get_word_limbs(const uint64_t* db, uint32_t z, uint32_t j, uint32_t ii, uint32_t num_per, uint32_t dim0) {
+    return db1_get_word_planes<1024u>(db, z, j, ii, num_per, dim0);
+}
+__device__ __forceinline__ uint64_t db1_get_word_limbs8(const uint64_t* db, uint32_t z, uint32_t j, uint32_t ii, uint32_t dim0) {
+    return db1_get_word_planes<512u>(db, z, j, ii, 8u, dim0);
+}
 #endif
 // fastMultiplyQueryByDatabaseDim1 (src/testing.cpp:364): acc[ii][r][z] PK; qs1 records [z][j] = {p r0, p r1, b r0, b r1}
 // `trials` databases db + t*db_stride swept in one launch into acc + t*acc_stride (strides in u64 words)
@@ -592,5 +632,32 @@ struct DbUpdateParams {
     uint32_t num_per, dim0;  // the image's geometry (dim0: the shard's first dimension on the base path)
 };
 void launch_db_update(const DbUpdateParams& p, hipStream_t s);
+
+// ---- items out of the image as plaintexts (db_export.hip) -------------------------------------------------------------------
+// The inverse of the ingest (LD_DBGEN / LD_DBGEN1 with ST_DB / ST_DB1): one workgroup per polynomial gathers its 2048 words from the image in the
+// form it is in, inverse transform + CRT lift, undoes the centred lift and bit-packs the coefficients coeff_bits wide (the item stream of
+// load_db_items).  Item k of the launch goes to out + k * polys * 256 * coeff_bits bytes, polys = 4 (base: polynomial (m, c) at m * 2 + c) or 1.
+// The work is either the n consecutive LOCAL items first .. first + n - 1 (local: j counted from the shard's first row, item = j * num_per + ii) or,
+// table != null, the n entries {j local, column ii, output slot k, position in the call} of a device table.  A coefficient that is no centred
+// lift of a value below p_db atomicMin's ((position in the call * polys + polynomial) * 2048 + coefficient) into *err (range form: position =
+// pos_base + k), which the host sets to ~0 before the first launch of a call.
+enum DbExportForm : uint32_t {
+    DBX_PACKED = 0,  // db_get_word / db1_get_word: the packed and the plain layouts
+    DBX_LIMBS = 1,   // db_get_word_limbs / db1_get_word_limbs: 1 KiB planes
+    DBX_LIMBS8 = 2,  // db1_get_word_limbs8: a SpiralPack image of 8 columns, 512-byte planes
+};
+struct DbExportParams {
+    const uint64_t* db;  // the image (SpiralPack: the trial's)
+    uint8_t* out;        // 16-byte aligned
+    unsigned long long* err;
+    const uint4* table;
+    uint64_t first, pos_base;
+    uint32_t n;
+    uint32_t pack, form;        // pack: 1 x 1 plaintexts of a trial image; form: DbExportForm
+    uint32_t num_per, dim0;     // the image's geometry (dim0: the shard's first dimension on the base path)
+    uint32_t coeff_bits;        // 1 .. 64, 2^coeff_bits >= p_db
+    uint64_t p_db;
+};
+void launch_db_export(const DeviceTables& t, const DbExportParams& p, hipStream_t s);
 
 }  // namespace spiral

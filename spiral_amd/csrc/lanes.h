@@ -17,6 +17,7 @@ struct LaneHost {
     DevBuf arena;                  // its per-query buffers, one allocation ...
     std::vector<size_t> pieces;    // ... and where each piece of it begins, in carve order (alloc_carved)
     hipEvent_t ev_lane = nullptr;  // orders this server's stream around a call on another server's; nothing else records it, it is never timed
+    ExportWork xwork;              // read_db_items' workspace (its own, also as a lane: reading does not write the image)
 };
 
 // How an entry point on one server opens: a null handle is refused, the server's device is made current

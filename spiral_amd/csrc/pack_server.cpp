@@ -89,6 +89,7 @@ void pk_free(spiral_gpu_pack_server* S) {
     for (DevBuf* b : {&S->arena, &S->stage, &S->item}) b->release();  // (what owns memory: every other buffer is a piece of the arena)
     S->item_cap = 0;
     S->wire_in.release();
+    S->xwork.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e), e = nullptr;
     if (S->ev_lane) (void)hipEventDestroy(S->ev_lane), S->ev_lane = nullptr;
@@ -461,6 +462,35 @@ int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t t
     std::vector<UpdateItem> sel(n);
     for (uint64_t k = 0; k < n; k++) sel[k] = UpdateItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
     return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target(trial - S->t0));
+}
+
+// One trial's items back as plaintexts, in the load_db_items layout, from the trial image in its current form (include/spiral_gpu.h): the owner or a
+// lane, on its own stream
+int spiral_gpu_pack_server_read_db_items(spiral_gpu_pack_server* S, uint32_t trial, void* items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items) {
+    if (enter(S)) return -1;
+    if (!items) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    if (pk_check_trial(S, trial)) return -1;
+    const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    if (check_export_width(coeff_bits, S->p.p_db)) return -1;
+    return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(trial - S->t0), first_item, n_items, 0, nullptr,
+                        [&](uint64_t pos) { return first_item + pos; });
+}
+int spiral_gpu_pack_server_read_db_items_at(spiral_gpu_pack_server* S, uint32_t trial, void* items, uint32_t coeff_bits, const uint64_t* item_ids, uint64_t n) {
+    if (enter(S)) return -1;
+    if (!items || !item_ids) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    if (pk_check_trial(S, trial)) return -1;
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    for (uint64_t k = 0; k < n; k++)
+        if (item_ids[k] >= total) return fail("item id %llu outside the database of %llu items", (unsigned long long)item_ids[k], (unsigned long long)total);
+    if (check_export_width(coeff_bits, S->p.p_db)) return -1;
+    std::vector<ExportItem> sel(n);
+    for (uint64_t k = 0; k < n; k++) sel[k] = ExportItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
+    return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(trial - S->t0), 0, 0, 0, &sel,
+                        [&](uint64_t pos) { return item_ids[pos]; });
 }
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {

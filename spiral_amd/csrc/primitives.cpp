@@ -8,6 +8,8 @@ thread_local std::string spiral::host::g_err;
 std::atomic<uint64_t> spiral::host::g_pack_lane_batches{0};
 // matrix-core sweep launches of this process that were made (get_option "mfma_sweeps"; counted by the two launchers of sweep_mfma.hip)
 std::atomic<uint64_t> spiral::g_mfma_sweeps{0};
+// device nanoseconds of the export launches of this process's last read_db_items / read_db_items_at call (get_option "db_export_ns"; host_common.h export_items)
+std::atomic<uint64_t> spiral::host::g_db_export_ns{0};
 
 // the process-wide options (kernels.h); the three documented environment variables give their initial values, once
 spiral::Options& spiral::options() {
@@ -73,6 +75,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else if (n == "key_binds") *value = (int64_t)g_key_binds.load();  // (read only)
+    else if (n == "db_export_ns") *value = (int64_t)g_db_export_ns.load();  // (read only)
     else if (n == "mfma_sweeps") *value = (int64_t)g_mfma_sweeps.load(std::memory_order_relaxed);  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;
@@ -499,6 +502,13 @@ int spiral_gpu_raw_from_wire(const void* wire, size_t npolys, uint64_t* raw) {
 size_t spiral_gpu_response_wire_bytes(const spiral_gpu_params* p, uint32_t out_n) {
     if (!p || out_n < 1 || out_n > 16 || p->qprime_bits < 1 || p->qprime_bits > 36 || p->p_db < 2 || p->p_db > (1ull << 40)) return 0;
     return wire_bytes(p, out_n);
+}
+
+// bytes of n items in the item stream of load_db_items / read_db_items (host only)
+size_t spiral_gpu_db_items_bytes(const spiral_gpu_params* p, uint32_t out_n, uint32_t coeff_bits, uint64_t n_items) {
+    if (!p) return fail("null argument"), 0;
+    if (check_export_width(coeff_bits, p->p_db)) return 0;
+    return (size_t)n_items * (out_n ? 1u : 4u) * (kN / 8u) * coeff_bits;
 }
 
 // client side of the wire form (load_modswitched_into_ct, src/client.cpp:90-110): plain host code, no device involved

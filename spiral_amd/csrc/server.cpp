@@ -71,6 +71,7 @@ void srv_free(spiral_gpu_server* S) {
     for (DevBuf* b : {&S->arena, &S->ex_raw2, &S->ex_g2, &S->cts_keep, &S->stage, &S->wire}) b->release();  // (what owns memory: the rest are pieces of the arena)
     S->wire_in.release();
     S->query_batch_in.release();
+    S->xwork.release();
     for (auto& e : S->ev)
         if (e) (void)hipEventDestroy(e);
     if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
@@ -523,6 +524,37 @@ int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, u
         if (j >= S->j0 && j < S->j1) sel.push_back(UpdateItem{k, (uint32_t)(j - S->j0), (uint32_t)(item_ids[k] % np)});
     }
     return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target());
+}
+
+// The items back as plaintexts, in the load_db_items layout, from the image in its current form (include/spiral_gpu.h): any server that references a
+// loaded image, on its own stream; a shard writes the items of its j-range and leaves the other bytes of `items` alone
+int spiral_gpu_server_read_db_items(spiral_gpu_server* S, void* items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items) {
+    if (enter(S)) return -1;
+    if (!items) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    if (check_export_width(coeff_bits, S->p.p_db)) return -1;
+    const uint64_t lo = std::max<uint64_t>(first_item, S->j0 * np), hi = std::min<uint64_t>(first_item + n_items, S->j1 * np);
+    if (lo >= hi) return 0;
+    return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), lo - S->j0 * np, hi - lo, lo - first_item, nullptr,
+                        [&](uint64_t pos) { return first_item + pos; });
+}
+int spiral_gpu_server_read_db_items_at(spiral_gpu_server* S, void* items, uint32_t coeff_bits, const uint64_t* item_ids, uint64_t n) {
+    if (enter(S)) return -1;
+    if (!items || !item_ids) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    for (uint64_t k = 0; k < n; k++)
+        if (item_ids[k] >= total) return fail("item id %llu outside the database of %llu items", (unsigned long long)item_ids[k], (unsigned long long)total);
+    if (check_export_width(coeff_bits, S->p.p_db)) return -1;
+    std::vector<ExportItem> sel;  // the ids of this shard's j-range
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t j = item_ids[k] / np;
+        if (j >= S->j0 && j < S->j1) sel.push_back(ExportItem{k, (uint32_t)(j - S->j0), (uint32_t)(item_ids[k] % np)});
+    }
+    return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), 0, 0, 0, &sel, [&](uint64_t pos) { return item_ids[pos]; });
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, PackShape, Params, check, lib, update_args, wire_bytes
+from ._lib import U64P, PackShape, Params, check, lib, read_args, read_ids, update_args, wire_bytes
 
 N = 2048
 PACK_STAGE_NAMES = ["expansion_us", "conversion_us", "first_dim_us", "folding_us", "packing_us", "sweep_kernels_us", "total_us", "reserved"]
@@ -123,6 +123,22 @@ class PackServer:
         current form, on this server's stream; see include/spiral_gpu.h spiral_gpu_pack_server_update_db_items"""
         items, ids = update_args(items, coeff_bits, item_ids, 1)
         check(lib().spiral_gpu_pack_server_update_db_items(self.h, trial, items.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
+
+    def read_db_items(self, trial: int, coeff_bits: int, first_item: int = 0, n_items=None, out=None) -> np.ndarray:
+        """items first_item .. first_item + n_items - 1 (default: to the end) of one trial back as plaintexts, uint8 bytes in load_db_items' layout,
+        read from the trial image in its current form; see include/spiral_gpu.h spiral_gpu_pack_server_read_db_items"""
+        if n_items is None:
+            n_items = self.shape.dim0 * self.shape.num_per - first_item
+        out = read_args(self.params, coeff_bits, n_items, self.out_n, out)
+        check(lib().spiral_gpu_pack_server_read_db_items(self.h, trial, out.ctypes.data_as(C.c_void_p), coeff_bits, first_item, n_items))
+        return out
+
+    def read_db_items_at(self, trial: int, coeff_bits: int, ids, out=None) -> np.ndarray:
+        """the items ids[k] of one trial (any order, duplicates allowed) back as plaintexts, plaintext k at k * 256 * coeff_bits bytes"""
+        ids = read_ids(ids)
+        out = read_args(self.params, coeff_bits, len(ids), self.out_n, out)
+        check(lib().spiral_gpu_pack_server_read_db_items_at(self.h, trial, out.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
+        return out
 
     def read_acc(self, trial: int) -> np.ndarray:
         """first-dimension accumulators of one trial of the last answer: [num_per][2][2][N] NTT form"""

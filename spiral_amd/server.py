@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, lib, update_args, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, lib, read_args, read_ids, update_args, wire_bytes
 
 N = 2048
 
@@ -179,6 +179,23 @@ class Server:
         server's stream; see include/spiral_gpu.h spiral_gpu_server_update_db_items"""
         items, ids = update_args(items, coeff_bits, item_ids, 4)
         check(lib().spiral_gpu_server_update_db_items(self.h, items.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
+
+    def read_db_items(self, coeff_bits: int, first_item: int = 0, n_items: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """items first_item .. first_item + n_items - 1 (default: to the end) back as plaintexts, uint8 bytes in load_db_items' layout, read from the
+        image in its current form; a sharded server fills in its own items only (pass the same `out` to every shard); see include/spiral_gpu.h
+        spiral_gpu_server_read_db_items"""
+        if n_items is None:
+            n_items = self.shape.dim0 * self.shape.num_per - first_item
+        out = read_args(self.params, coeff_bits, n_items, 0, out)
+        check(lib().spiral_gpu_server_read_db_items(self.h, out.ctypes.data_as(C.c_void_p), coeff_bits, first_item, n_items))
+        return out
+
+    def read_db_items_at(self, coeff_bits: int, ids, out: np.ndarray | None = None) -> np.ndarray:
+        """the items ids[k] (any order, duplicates allowed) back as plaintexts, plaintext k at k * 1024 * coeff_bits bytes; see read_db_items"""
+        ids = read_ids(ids)
+        out = read_args(self.params, coeff_bits, len(ids), 0, out)
+        check(lib().spiral_gpu_server_read_db_items_at(self.h, out.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
+        return out
 
     def read_db_item(self, item: int) -> np.ndarray:
         out = np.zeros((2, 2, 2, N), dtype=np.uint64)
