@@ -664,6 +664,39 @@ int spiral_gpu_pack_has_limb_form(const spiral_gpu_params *p, uint32_t out_n);
 int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server *owner, spiral_gpu_pack_server **out);
 int spiral_gpu_pack_server_answer_batch(spiral_gpu_pack_server *const *servers, uint32_t n, const uint64_t *const *queries,
                                         uint64_t *const *responses, uint64_t *const *packed_cts, double stage_us[8]);
+/* Batches of a TRIAL-SHARDED answer (create_sharded above): n <= 8 clients per rank, one pass over the rank's trial images for all of them, ONE
+ * all-gather, one pack on the root.  CT below = 2 x 2048 raw words, one folded ciphertext.
+ * create_shard_lane: as create_lane, of an owner that holds the trials [t0, t0 + nt) only -- the owner's parameters, out_n, device and trial range,
+ * the owner's images, its own keys, query and intermediates.  The owner must own its image and have a database loaded; loads, updates and
+ * set_db_format through the lane fail as through any lane, read_db_items* and read_acc of a trial in range work, the images go with their last
+ * reference.  Of an owner that holds every trial the result is an ordinary lane.  Shard lanes of a trial-sharded owner are taken by the two calls
+ * below and by bind_keys only (every rank holds every client's keys: the store is how a shard's lanes change clients between batches); every other
+ * multi-server call refuses them, as it refuses their owner ("trial-sharded").
+ * fold_trials_batch (every rank, before the all-gather): servers = n in 1 .. 8 distinct servers, an owner and/or its shard lanes in any order, each
+ * with its own public parameters; form = 0 (NTT-form polynomials, bytes_each ignored), SPIRAL_GPU_FORM_WIRE or SPIRAL_GPU_FORM_SEEDED (every query
+ * bytes_each long).  Every argument is checked and every query taken before anything is launched: a bad query leaves every lane as it was.  Then
+ * answer_batch's front half over the LOCAL trials: expansion and conversion (the lane form from option "pack_batch_lanes" clients on, per lane
+ * below it), with n >= 2 the in-place conversion of this shard's images where the geometry has limb planes, ONE first-dimension pass for all lanes,
+ * the folding.  Lane b's nt folded ciphertexts are left at folded_dev + (b * nt + k) * CT, k < nt -- the block [lane][k], each ciphertext what the
+ * lane's own fold_trials writes; nothing else of folded_dev is written.  The call runs on servers[0]'s stream with the other lanes' streams (and
+ * the owner's, when it is not listed) ordered around it and is ASYNCHRONOUS like fold_trials: the caller's collective follows on that stream.
+ * Not during stream capture.  Afterwards every lane's read_acc of a local trial is its own fold_trials'.  n = 1 is fold_trials.
+ * pack_gathered_batch (the root, after the all-gather): cuts[0 .. n_ranks] are the ranks' trial ranges, cuts[0] = 0 < cuts[1] < ... < cuts[n_ranks] =
+ * out_n^2.  gathered_dev (16-byte aligned) holds n_ranks blocks at a stride of block_cts ciphertexts, block r = rank r's [lane][k < cuts[r + 1] -
+ * cuts[r]]; block_cts >= n x the longest range, and the surplus of a block is padding that is never read -- unequal ranges go through an equal-size
+ * all-gather.  servers: any n lanes of one image on the root, shard lanes or ordinary (the root's own trial range plays no part), each with its own
+ * public parameters; lane b is the client that was lane b on every rank.  ONE launch regroups the blocks into every lane's trial order, then ONE
+ * lane-aware pack and switch follows: one launch more than pack_gathered, whatever n and n_ranks.  responses[b] / packed_cts[b] (or the arrays)
+ * may be NULL; wire (may be NULL): n x spiral_gpu_response_wire_bytes(p, out_n) contiguous host bytes, lane b's wire form at b x that, from one
+ * launch and one copy.  At least one of the three must be given.  Every argument is checked before anything is launched: a refused call writes
+ * nothing and leaves every lane's previous results intact.  Returns synchronised; afterwards every lane's response, packed ciphertext and
+ * read_response_wire equal its own pack_gathered on its own trial-ordered ciphertexts. */
+int spiral_gpu_pack_server_create_shard_lane(spiral_gpu_pack_server *owner, spiral_gpu_pack_server **out);
+int spiral_gpu_pack_server_fold_trials_batch(spiral_gpu_pack_server *const *servers, uint32_t n, int form, const void *const *queries,
+                                             size_t bytes_each, void *folded_dev);
+int spiral_gpu_pack_server_pack_gathered_batch(spiral_gpu_pack_server *const *servers, uint32_t n, const void *gathered_dev,
+                                               const uint32_t *cuts, uint32_t n_ranks, uint64_t block_cts, uint64_t *const *responses,
+                                               uint64_t *const *packed_cts, void *wire);
 /* SpiralPack from the wire form (see spiral_gpu_query_wire_bytes above): the sizes of a query and of the public parameters for `out_n`, the
  * public parameters as one message, and answer / answer_batch with the queries in their wire form (there is no set_query on this path).
  * answer_batch_wire checks every argument, each query's byte count included, before anything is uploaded, and runs the batch only when every

@@ -191,6 +191,12 @@ PROTOTYPES = {
     "spiral_gpu_pack_has_limb_form": (C.c_int, [C.POINTER(Params), C.c_uint32]),
     "spiral_gpu_pack_server_create_lane": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "spiral_gpu_pack_server_answer_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(U64P), C.POINTER(U64P), C.POINTER(U64P), C.POINTER(C.c_double)]),
+    "spiral_gpu_pack_server_create_shard_lane": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    # (the list of servers as an opaque pointer: tests/test_lanes_cpu.py keeps a closed table of the calls declared with POINTER(c_void_p) first; these
+    # two go through the same list check, lanes.h check_lane_list, and tests/test_pack_shard_batch_cpu.py runs that table's cases on them)
+    "spiral_gpu_pack_server_fold_trials_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p]),
+    "spiral_gpu_pack_server_pack_gathered_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64,
+                                                             C.POINTER(U64P), C.POINTER(U64P), C.c_void_p]),
     "spiral_gpu_pack_server_set_db_format": (C.c_int, [C.c_void_p, C.c_int]),
     "spiral_gpu_pack_server_db_format": (C.c_int, [C.c_void_p]),
     "spiral_gpu_pack_server_db_device_bytes": (C.c_uint64, [C.c_void_p]),

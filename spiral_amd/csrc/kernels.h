@@ -598,6 +598,20 @@ void launch_pack_fold_key(const uint64_t* gsw, uint64_t* key, uint32_t ell, uint
 // out_n^2, (out_n + 1) out_n) polynomials further on, the same v_w.  lanes (n_inst = 1 only): one response per client, each with its own v_w
 void launch_pack_mac(const uint64_t* v_w, const uint64_t* ginv, const uint64_t* ct2, uint64_t* result, uint32_t out_n, uint32_t t_conv, hipStream_t s,
                      uint32_t n_inst = 1, const Lanes& lanes = Lanes{});
+// The folded ciphertexts of a trial-sharded batch, regrouped for the pack in ONE launch (pack_gathered_batch): src holds n_ranks blocks at a stride of
+// block_cts ciphertexts (2 x 2048 raw words each), block r = [lane][k < cuts[r + 1] - cuts[r]] of the trials [cuts[r], cuts[r + 1]); lane q's trial t
+// goes to dst + lanes.off[q] + t x 2 x 2048 words -- trial order, in the lane's own arena, where run_pack's readers take it with the same lanes.  cuts[0]
+// = 0 < ... < cuts[n_ranks] = trials <= kMaxPackTrials (the host checks); the padding of a block is never read.  src is 16-byte aligned.
+constexpr uint32_t kMaxPackTrials = 256;  // out_n <= 16
+struct PackRegroupParams {
+    const uint64_t* src;
+    uint64_t* dst;
+    uint64_t block_cts;
+    uint32_t n_ranks;
+    uint32_t cuts[kMaxPackTrials + 1];
+    Lanes lanes;
+};
+void launch_pack_regroup(const PackRegroupParams& p, uint32_t trials, hipStream_t s);
 // the first-dimension sweep of n = 1 .. kMaxLanes queries (records qs1[b] -> accumulators acc[b], launch_sweep1's layouts) on the matrix cores, in ONE
 // pass over `trials` trial images (db_stride / acc_stride u64 words apart) in limb-plane form (sweep_mfma.hip, ROWS = 2).  Coverage (sweep1_mfma_ok):
 // num_per 8 (the pair form: a wave's operand holds two adjacent trials), 16, 32, 64 (the narrow form: a workgroup's waves take blocks of different

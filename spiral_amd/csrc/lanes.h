@@ -39,6 +39,7 @@ enum LaneNeeds : uint32_t {
     GIVES_KEYS = 64,    // the call sets the public parameters (bind_keys): they need not be set
     MOVES_DATA = 128,   // the call only moves messages in or responses out (set_query_batch, read_response_wire_batch): it depends on no query, no
                         // public parameters and no schedule, so lanes of a sharded batch and lanes with other schedules are taken too
+    TRIAL_SHARDS = 256, // SpiralPack: the lanes may hold a trial range only (fold_trials_batch, pack_gathered_batch, bind_keys); every other call refuses them
     SHARD_LANES = SHARDED | NO_CAPTURE,
 };
 

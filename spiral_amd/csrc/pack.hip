@@ -515,6 +515,24 @@ void launch_pack_fold_mac(const uint64_t* key, const uint64_t* d, uint64_t* out,
     }
 }
 
+// ---- the gathered blocks of a trial-sharded batch -> each lane's trial-ordered folded ciphertexts (kernels.h PackRegroupParams) ----
+// One workgroup per (trial, lane): it finds the trial's rank in the cuts (a scalar scan of the by-value table, which is only read: it stays in the
+// argument segment) and copies the 32 KiB ciphertext, 8 x 16 bytes per thread.
+__global__ __launch_bounds__(256) void pack_regroup_kernel(const PackRegroupParams p) {
+    const uint32_t t = blockIdx.x, q = blockIdx.z;
+    uint32_t r = 0;
+    while (r + 1 < p.n_ranks && t >= p.cuts[r + 1]) r++;
+    const uint32_t first = p.cuts[r], len = p.cuts[r + 1] - first;
+    const uint64_t ct = (uint64_t)r * p.block_cts + (uint64_t)q * len + (t - first);
+    const uint4* src = reinterpret_cast<const uint4*>(p.src + ct * (2u * kN));
+    uint4* dst = reinterpret_cast<uint4*>(p.dst + p.lanes.here() + (size_t)t * (2u * kN));
+#pragma unroll
+    for (uint32_t i = 0; i < 2u * kN / 2u / 256u; i++) dst[i * 256u + threadIdx.x] = src[i * 256u + threadIdx.x];
+}
+void launch_pack_regroup(const PackRegroupParams& p, uint32_t trials, hipStream_t s) {
+    hipLaunchKernelGGL(pack_regroup_kernel, dim3(trials, 1, p.lanes.n), dim3(256), 0, s, p);
+}
+
 // arbitrary valid words (benchmarks)
 __global__ __launch_bounds__(256) void fill_db1_random_kernel(uint64_t* db, uint32_t num_per, uint32_t dim0, uint64_t seed) {
     const uint64_t nwords = (uint64_t)kN * dim0 * num_per, stride = (uint64_t)gridDim.x * 256u;

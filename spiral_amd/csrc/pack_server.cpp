@@ -30,8 +30,11 @@ struct spiral_gpu_pack_server : LaneHost {  // (lanes.h: device, stream, img, ar
     // every buffer below but the lazy ones (stage, wire_in, item) is a piece of `arena`, carved in one fixed order (pk_layout): servers with equal
     // parameters, out_n and trial range have equal layouts
     DevBuf w_left, w_right, v, v_w, query, cv, ex_raw, ex_g, gs_raw, gs_chat, gs_tmp, gsw, key, qs1;  // the client's own
+    DevBuf gath;  // pack_gathered_batch: this client's out_n^2 folded ciphertexts in trial order, regrouped from the gathered blocks (a piece of the
+                  // arena like the rest, so that the pack's readers find every lane's at the lane's offset)
     PkBufs own{};  // what one answer writes
     DevBuf stage;
+    DevBuf wire_batch;  // pack_gathered_batch as servers[0]: the lanes' wire forms side by side for the one copy; grown on first use, kept
     WireIn wire_in;  // the staging of the wire and seeded forms (message.h ingest)
     KeyMemo key_memo;  // the store slot the four key buffers were last bound from (bind_keys); none once set_pub_params* has written them
     hipEvent_t ev[8] = {};  // [0..6] the stages of an answer, [7] batch sweep / item call end (its stream is ordered around another server's call by ev_lane)
@@ -86,7 +89,7 @@ int pk_check_trial(const spiral_gpu_pack_server* S, uint32_t trial) {
 
 void pk_free(spiral_gpu_pack_server* S) {
     DbImage::drop(S->img, S);
-    for (DevBuf* b : {&S->arena, &S->stage, &S->item}) b->release();  // (what owns memory: every other buffer is a piece of the arena)
+    for (DevBuf* b : {&S->arena, &S->stage, &S->item, &S->wire_batch}) b->release();  // (what owns memory: every other buffer is a piece of the arena)
     S->item_cap = 0;
     S->wire_in.release();
     S->xwork.release();
@@ -121,6 +124,7 @@ void pk_layout(spiral_gpu_pack_server* S, Arena& a, bool client, uint32_t g, PkB
         a.carve(S->gsw, (size_t)p.nu2 * 2 * 2 * s.ell * kN);
         a.carve(S->key, (size_t)p.nu2 * 2 * 4 * s.ell * kN);
         a.carve(S->qs1, (size_t)kN * s.dim0 * 2);  // 4 u32 per (z, j)
+        a.carve(S->gath, (size_t)s.trials * 2 * kN);
     }
     B.acc_words = (size_t)S->nt * s.num_per * 2 * kN;
     B.slot_words = rows * S->out_n * kN;
@@ -363,6 +367,15 @@ int spiral_gpu_pack_server_create_lane(spiral_gpu_pack_server* owner, spiral_gpu
     if (owner->nt != owner->s.trials) return fail("the owner holds trials [%u, %u) only: trial-sharded servers have no lanes", owner->t0, owner->t0 + owner->nt);
     if (!owner->img->loaded) return fail("the owner has no database loaded");
     return pk_create(&owner->p, owner->out_n, owner->device, 0, 0, owner->img, out);
+}
+
+// a lane of a server that holds the trials [t0, t0 + nt) only: as create_lane, with the owner's trial range (fold_trials_batch on every rank,
+// pack_gathered_batch on the root).  Of an owner that holds every trial it is an ordinary lane.
+int spiral_gpu_pack_server_create_shard_lane(spiral_gpu_pack_server* owner, spiral_gpu_pack_server** out) {
+    if (!owner || !out) return fail("null argument");
+    if (owner->img->owner != owner) return fail("the owner does not own its database image (it is a lane)");
+    if (!owner->img->loaded) return fail("the owner has no database loaded");
+    return pk_create(&owner->p, owner->out_n, owner->device, owner->t0, owner->t0 + owner->nt, owner->img, out);
 }
 
 void spiral_gpu_pack_server_destroy(spiral_gpu_pack_server* S) {
@@ -695,14 +708,14 @@ int spiral_gpu_pack_server_answer_seeded(spiral_gpu_pack_server* S, const void* 
 }
 
 // the lanes of a batch, checked before anything is launched, and their arena offsets: the list, the image, NO_CAPTURE and the layouts in lanes.h,
-// between them SpiralPack's own rules -- none trial-sharded, the same parameters, out_n and trial range, and what `needs` names (NEED_DB,
-// NEED_RECORDS; public parameters unless the call GIVES_KEYS)
+// between them SpiralPack's own rules -- none trial-sharded unless the call takes TRIAL_SHARDS, the same parameters, out_n and trial range, and what
+// `needs` names (NEED_DB, NEED_RECORDS; public parameters unless the call GIVES_KEYS)
 static int pk_check_lanes(spiral_gpu_pack_server* const* servers, uint32_t n, const char* what, uint32_t needs, Lanes* lanes) {
     return check_lane_list(servers, n, what, needs, lanes, [&](uint32_t b) {
         const spiral_gpu_pack_server *H = servers[0], *L = servers[b];
-        if (H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
+        if (!(needs & TRIAL_SHARDS) && H->nt != H->s.trials) return fail("%s: the image holds trials [%u, %u) only: trial-sharded servers have no batch", what, H->t0, H->t0 + H->nt);
         if ((needs & NEED_DB) && !H->img->loaded) return fail("%s: no database loaded", what);
-        if (memcmp(&L->p, &H->p, sizeof(L->p)) != 0 || L->out_n != H->out_n || L->device != H->device || L->nt != H->nt)
+        if (memcmp(&L->p, &H->p, sizeof(L->p)) != 0 || L->out_n != H->out_n || L->device != H->device || L->nt != H->nt || L->t0 != H->t0)
             return fail("%s: server %u has other parameters than server 0", what, b);
         if (!(needs & GIVES_KEYS) && !L->have_pp) return fail("%s: server %u has no public parameters", what, b);
         if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has no converted query (answer it once first)", what, b);
@@ -733,7 +746,7 @@ static int pk_take_queries(spiral_gpu_pack_server* const* servers, uint32_t n, F
 int spiral_gpu_pack_server_bind_keys(spiral_gpu_pack_server* const* servers, uint32_t n, spiral_gpu_key_store* store, const uint32_t* slots) {
     const char* what = "pack bind_keys";
     Lanes lanes;
-    if (pk_check_lanes(servers, n, what, NO_CAPTURE | GIVES_KEYS, &lanes)) return -1;
+    if (pk_check_lanes(servers, n, what, NO_CAPTURE | GIVES_KEYS | TRIAL_SHARDS, &lanes)) return -1;  // (every rank holds every client's keys)
     spiral_gpu_pack_server* S = servers[0];
     uint64_t* const dst[kMessageParts] = {S->w_left.p, S->w_right.p, S->v.p, S->v_w.p};
     const size_t dst_words[kMessageParts] = {S->w_left.words, S->w_right.words, S->v.words, S->v_w.words};
@@ -1050,6 +1063,105 @@ int spiral_gpu_pack_server_pack_gathered(spiral_gpu_pack_server* S, const void* 
     if (!S->have_pp) return fail("public parameters must be set first");
     if (pk_back(S, (const uint64_t*)gathered_dev, 1, Lanes{}, S->stream)) return -1;
     return pk_download(S, response, packed_ct);
+}
+
+// ---- batches of a trial-sharded answer (include/spiral_gpu.h): fold_trials_batch on every rank, one all-gather, pack_gathered_batch on the root ----
+// the server that may write the lanes' image, when it is none of them: its stream (an update_db_items) is ordered around the call too
+static spiral_gpu_pack_server* pk_outside_owner(spiral_gpu_pack_server* const* servers, uint32_t n) {
+    spiral_gpu_pack_server* own = pk_owner(servers[0]);
+    for (uint32_t b = 0; b < n; b++)
+        if (servers[b] == own) return nullptr;
+    return own;
+}
+
+// part 1 for n clients: answer_batch's front half over this rank's trials -- expansion and conversion (lane form or per lane), ONE sweep of the
+// local images for all lanes, the folding -- and lane b's nt folded ciphertexts to folded_dev + (b * nt + k) x 2 x 2048 words.  Asynchronous on
+// servers[0]'s stream, the other lanes' streams ordered around it.
+int spiral_gpu_pack_server_fold_trials_batch(spiral_gpu_pack_server* const* servers, uint32_t n, int form, const void* const* queries, size_t bytes_each,
+                                             void* folded_dev) {
+    const char* what = "fold_trials_batch";
+    if (!queries || !folded_dev) return fail("%s: null queries or output buffer", what);
+    if (form != FORM_NTT && form != SPIRAL_GPU_FORM_WIRE && form != SPIRAL_GPU_FORM_SEEDED) return fail("%s: unknown query form %d", what, form);
+    Lanes lanes;
+    if (pk_check_lanes(servers, n, what, NEED_DB | NO_CAPTURE | TRIAL_SHARDS, &lanes) || pk_take_queries(servers, n, (Form)form, queries, bytes_each, what))
+        return -1;
+    spiral_gpu_pack_server* S = servers[0];
+    hipStream_t st = S->stream;
+    if (n >= 2 && S->img->lay.limbs_ok() && S->img->set_format(SPIRAL_GPU_DB_LIMBS, st)) return -1;
+    spiral_gpu_pack_server* own = pk_outside_owner(servers, n);
+    if (lanes_join(servers, n) || (own && stream_before(own, st))) return -1;
+    if (n == 1) {
+        if (pk_front(S)) return -1;
+    } else if (pk_lane_form(n)) {
+        if (pk_expand_convert(S, lanes, st) || pk_sweep(S, lanes, st)) return -1;
+        HIP_OK(hipEventRecord(S->ev[7], st));
+        if (pk_fold(S, lanes, st)) return -1;
+        for (uint32_t b = 1; b < n; b++) servers[b]->have_records = true, servers[b]->packed_after_front = false, servers[b]->events_elsewhere = true;
+        g_pack_lane_batches++;
+    } else {
+        for (uint32_t b = 0; b < n; b++)
+            if (pk_expand_convert(servers[b], Lanes{}, st)) return -1;
+        if (pk_sweep(S, lanes, st)) return -1;
+        HIP_OK(hipEventRecord(S->ev[7], st));
+        for (uint32_t b = 0; b < n; b++)
+            if (pk_fold(servers[b], Lanes{}, st)) return -1;
+    }
+    const size_t ct_bytes = 2 * kPolyBytes;
+    for (uint32_t b = 0; b < n; b++)  // one strided copy per lane: the head of each trial's num_per slots
+        HIP_OK(hipMemcpy2DAsync((uint8_t*)folded_dev + (size_t)b * S->nt * ct_bytes, ct_bytes, servers[b]->own.raw, (size_t)S->s.num_per * ct_bytes, ct_bytes,
+                                S->nt, hipMemcpyDeviceToDevice, st));
+    if (lanes_release(servers, n)) return -1;
+    if (own && own->stream != st) {
+        HIP_OK(hipEventRecord(S->ev_lane, st));
+        if (stream_after(own, st, S->ev_lane)) return -1;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// part 2 for n clients, on the root: the gathered rank-major blocks (block r = [lane][k] of the trials [cuts[r], cuts[r + 1]), at a stride of
+// block_cts ciphertexts) regrouped into each lane's trial order in ONE launch, then ONE lane-aware pack and switch.  Returns synchronised.
+int spiral_gpu_pack_server_pack_gathered_batch(spiral_gpu_pack_server* const* servers, uint32_t n, const void* gathered_dev, const uint32_t* cuts,
+                                               uint32_t n_ranks, uint64_t block_cts, uint64_t* const* responses, uint64_t* const* packed_cts, void* wire) {
+    const char* what = "pack_gathered_batch";
+    if (!gathered_dev || !cuts) return fail("%s: null gathered buffer or cuts", what);
+    if (!responses && !packed_cts && !wire) return fail("%s: no output (responses, packed_cts or wire)", what);
+    Lanes lanes;
+    if (pk_check_lanes(servers, n, what, NO_CAPTURE | TRIAL_SHARDS, &lanes)) return -1;
+    spiral_gpu_pack_server* S = servers[0];
+    const uint32_t trials = S->s.trials;
+    if ((uintptr_t)gathered_dev % 16) return fail("%s: the gathered buffer must be 16-byte aligned", what);
+    if (n_ranks == 0 || n_ranks > trials) return fail("%s: %u ranks for %u trials", what, n_ranks, trials);
+    if (cuts[0] != 0 || cuts[n_ranks] != trials) return fail("%s: the cuts run from %u to %u, not from 0 to %u", what, cuts[0], cuts[n_ranks], trials);
+    uint32_t longest = 0;
+    for (uint32_t r = 0; r < n_ranks; r++) {
+        if (cuts[r + 1] <= cuts[r] || cuts[r + 1] > trials) return fail("%s: the cuts are not strictly increasing at rank %u", what, r);
+        longest = std::max(longest, cuts[r + 1] - cuts[r]);
+    }
+    if (block_cts < (uint64_t)n * longest || block_cts > ((uint64_t)1 << 32))
+        return fail("%s: blocks of %llu ciphertexts, %u lanes of up to %u trials need at least %llu", what, (unsigned long long)block_cts, n, longest,
+                    (unsigned long long)n * longest);
+    static_assert(kMaxPackTrials >= 16 * 16, "the cuts of every out_n fit the regroup launch's table");
+    const size_t nbytes = wire_bytes(&S->p, S->out_n);
+    if (wire && S->wire_batch.words * 8 < n * nbytes && (S->wire_batch.release(), S->wire_batch.alloc(n * nbytes / 8))) return -1;
+    hipStream_t st = S->stream;
+    if (lanes_join(servers, n)) return -1;
+    PackRegroupParams rp{(const uint64_t*)gathered_dev, S->gath.p, block_cts, n_ranks, {}, lanes};
+    std::copy(cuts, cuts + n_ranks + 1, rp.cuts);
+    launch_pack_regroup(rp, trials, st);
+    if (pk_back(S, S->gath.p, 1, lanes, st)) return -1;
+    for (uint32_t b = 1; b < n; b++) servers[b]->packed_after_front = false;
+    if (wire) {
+        launch_response_wire(S->own.resp, S->wire_batch.p, S->out_n * kN, S->p.qprime_bits, S->out_n * S->out_n * kN, wire_bits_rest(&S->p), st, lanes, 0,
+                             (int64_t)(nbytes / 8));
+        HIP_OK(hipMemcpyAsync(wire, S->wire_batch.p, n * nbytes, hipMemcpyDeviceToHost, st));
+    }
+    if (lanes_release(servers, n)) return -1;
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    for (uint32_t b = 0; b < n; b++)
+        if (pk_download(servers[b], responses ? responses[b] : nullptr, packed_cts ? packed_cts[b] : nullptr)) return -1;
+    return 0;
 }
 
 int spiral_gpu_pack_server_set_stream(spiral_gpu_pack_server* S, void* stream) {

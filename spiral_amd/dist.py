@@ -291,3 +291,99 @@ def answer_batch_sharded(servers, group=None, bufs=None, *, fold_ranks=None, sha
         SV.fold_root_batch(servers, bufs["gathered_cts"].data_ptr(), bufs["responses"].data_ptr(), wire_ptr)
         settle()
     return bufs
+
+
+# ---- SpiralPack batches on trial-sharded servers (include/spiral_gpu.h fold_trials_batch, pack_gathered_batch) ----------------------------------
+PACK_CT_WORDS = 2 * 2048  # one folded SpiralPack ciphertext (2 x 1 polynomials, raw words): 32 KiB
+
+
+def pack_trial_cuts(world: int, trials: int) -> list[int]:
+    """the ranks' trial ranges: rank r holds [cuts[r], cuts[r + 1]), consecutive, covering [0, trials), sizes differing by at most one (trials need not
+    divide by world; every rank holds at least one trial)"""
+    if world < 1 or world > trials:
+        raise ValueError(f"{world} ranks for {trials} trials: every rank holds at least one")
+    return [r * trials // world for r in range(world + 1)]
+
+
+def _pack_cuts(cuts) -> list[int]:
+    cuts = [int(c) for c in cuts]
+    if len(cuts) < 2 or cuts[0] != 0 or any(b <= a for a, b in zip(cuts[:-1], cuts[1:])):
+        raise ValueError(f"trial cuts {cuts}: they start at 0 and increase strictly")
+    return cuts
+
+
+def pack_batch_block_cts(n: int, cuts) -> int:
+    """ciphertexts of one rank's block of the all-gather, [lane][k]: n lanes x the LONGEST range, the same on every rank (an all-gather takes equal
+    blocks; a shorter range leaves the tail of its block as padding, which nothing reads)"""
+    cuts = _pack_cuts(cuts)
+    return _batch_n(n) * max(b - a for a, b in zip(cuts[:-1], cuts[1:]))
+
+
+def pack_batch_position(rank: int, lane: int, k: int, n: int, cuts, block_cts: int) -> int:
+    """where lane b's folded ciphertext of trial cuts[rank] + k lies in the gathered buffer (in ciphertexts): rank-major blocks at a stride of
+    block_cts, inside a block [lane][k < the rank's range]"""
+    cuts = _pack_cuts(cuts)
+    if not 0 <= rank < len(cuts) - 1:
+        raise ValueError(f"rank {rank} outside the {len(cuts) - 1} ranks of the cuts")
+    length = cuts[rank + 1] - cuts[rank]
+    if not 0 <= lane < _batch_n(n) or not 0 <= k < length:
+        raise ValueError(f"lane {lane} of {n}, trial {k} of rank {rank}'s {length}")
+    if block_cts < n * length:
+        raise ValueError(f"blocks of {block_cts} ciphertexts do not hold {n} lanes of {length} trials")
+    return rank * block_cts + lane * length + k
+
+
+def pack_batch_buffers(servers, cuts, device=None) -> dict:
+    """the two device buffers of one rank's trial-sharded batches (int64 tensors, zeroed), sized for len(servers) clients: "mine", this rank's block
+    (fold_trials_batch's output, the all-gather's input), and "gathered", the ranks' blocks.  Keep them across batches"""
+    import torch
+
+    cuts = _pack_cuts(cuts)
+    block = pack_batch_block_cts(len(servers), cuts)
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    return {"mine": torch.zeros(block * PACK_CT_WORDS, dtype=torch.int64, device=dev),
+            "gathered": torch.zeros((len(cuts) - 1) * block * PACK_CT_WORDS, dtype=torch.int64, device=dev), "block_cts": block}
+
+
+def all_gather_pack_batch(gathered, mine, group=None):
+    """the batch's one collective: every rank's block [lane][k] (padded to the common size) -> [rank][lane][k]; n x out_n^2 x 32 KiB of payload"""
+    import torch.distributed as dist
+
+    _check("all_gather_pack_batch: mine", mine)
+    _check("all_gather_pack_batch: gathered", gathered, mine.numel() * dist.get_world_size(group))
+    dist.all_gather_into_tensor(gathered, mine, group=group)
+    return gathered
+
+
+def answer_pack_batch_sharded(servers, queries, group=None, bufs=None, *, form="ntt", root=0, wire=False):
+    """One rank's whole answer of a batch of up to eight SpiralPack clients on trial-sharded servers, in order: fold_trials_batch over this rank's trials,
+    ONE all-gather of the ranks' blocks, pack_gathered_batch on `root`.  servers: this rank's owner -- created for the trials
+    pack_trial_cuts(world, out_n^2)[rank : rank + 2] -- and / or its shard lanes (create_shard_lane), lane b with client b's public parameters on every
+    rank; queries: the clients' queries, the same on every rank.  bufs: pack_batch_buffers(...) (allocated here when None; keep them across
+    batches).  Returns (bufs, out): out is pack_gathered_batch's result on the root, None elsewhere.  The servers' stream is settled before the
+    collective (which runs on torch's current stream) and the collective before the pack, as in answer_batch_sharded."""
+    import torch
+    import torch.distributed as dist
+
+    from .pack import fold_trials_batch, pack_gathered_batch  # (spiral_amd.pack is also the name of a function: take the module's own)
+
+    n = _batch_n(len(servers))
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    s0 = servers[0]
+    cuts = pack_trial_cuts(world, s0.shape.trials)
+    if (s0.trial0, s0.trial1) != (cuts[rank], cuts[rank + 1]):
+        raise ValueError(f"rank {rank} of {world} holds trials [{cuts[rank]}, {cuts[rank + 1]}), the servers [{s0.trial0}, {s0.trial1})")
+    if bufs is None:
+        bufs = pack_batch_buffers(servers, cuts)
+    block = pack_batch_block_cts(n, cuts)
+    _check("answer_pack_batch_sharded: mine", bufs["mine"], block * PACK_CT_WORDS)
+    _check("answer_pack_batch_sharded: gathered", bufs["gathered"], world * block * PACK_CT_WORDS)
+    dev = bufs["mine"].device
+    fold_trials_batch(servers, queries, bufs["mine"].data_ptr(), form=form)
+    torch.cuda.synchronize(dev)  # the servers' stream -> the collective (on torch's stream)
+    all_gather_pack_batch(bufs["gathered"], bufs["mine"], group=group)
+    torch.cuda.current_stream(dev).synchronize()  # the collective -> the servers' stream
+    out = None
+    if rank == root:
+        out = pack_gathered_batch(servers, bufs["gathered"].data_ptr(), cuts, block, wire=wire)
+    return bufs, out

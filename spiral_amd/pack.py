@@ -203,6 +203,17 @@ class PackServer:
         lane.trial0, lane.trial1 = self.trial0, self.trial1
         return lane
 
+    def create_shard_lane(self) -> "PackServer":
+        """a lane of a server that holds a trial range only: this one's parameters, out_n, device and trial range, THIS server's trial images, its own
+        public parameters, query and intermediates (fold_trials_batch on every rank, pack_gathered_batch on the root, bind_keys; loads through it
+        fail).  Of a server that holds every trial it is an ordinary lane; see include/spiral_gpu.h spiral_gpu_pack_server_create_shard_lane"""
+        h = C.c_void_p()
+        check(lib().spiral_gpu_pack_server_create_shard_lane(self.h, C.byref(h)))
+        lane = PackServer.__new__(PackServer)
+        lane.params, lane.out_n, lane.shape, lane.h = self.params, self.out_n, self.shape, h
+        lane.trial0, lane.trial1 = self.trial0, self.trial1
+        return lane
+
     def set_db_format(self, fmt: int):
         """convert the trial images in place: DB_PACKED (0) or DB_LIMBS (1, the batched matrix-core sweep's form; only where that sweep applies)"""
         check(lib().spiral_gpu_pack_server_set_db_format(self.h, int(fmt)))
@@ -290,6 +301,48 @@ def answer_batch_wire(servers, query_wires, want_packed: bool = False):
 def answer_batch_seeded(servers, query_msgs, want_packed: bool = False):
     """answer_batch with the queries in their seeded form (all of one size); every query is checked and expanded before the batch runs"""
     return _answer_batch("seeded", servers, query_msgs, want_packed)
+
+
+def fold_trials_batch(servers, queries, folded_ptr: int, form: str = "ntt"):
+    """every rank's half of a trial-sharded batch: n <= 8 queries, one per server (this rank's owner and / or its shard lanes, create_shard_lane),
+    through expansion, conversion, ONE pass over the rank's trial images and the folding; lane b's folded ciphertexts of the local trials
+    [trial0, trial1) go to the device buffer at folded_ptr + ((b * (trial1 - trial0) + k) * 2 * 2048) words.  Asynchronous on servers[0]'s stream.
+    form: "ntt" (uint64 polynomials), "wire" or "seeded" (messages of one size).  See include/spiral_gpu.h spiral_gpu_pack_server_fold_trials_batch"""
+    what = "fold_trials_batch"
+    if form not in _FORMS:
+        raise ValueError(f"{what}: form {form!r}, one of {sorted(_FORMS)}")
+    servers, hs = _lane_handles(servers, what)
+    qs = _query_arrays(form, list(queries))
+    if len(qs) != len(servers):
+        raise ValueError(f"{what}: {len(qs)} queries for {len(servers)} servers")
+    if form != "ntt" and len({w.size for w in qs}) != 1:
+        raise ValueError(f"{what}: the queries differ in size")
+    ptrs = (C.c_void_p * len(qs))(*[q.ctypes.data for q in qs])
+    code = {"ntt": 0, "wire": 1, "seeded": 2}[form]  # (spiral_gpu_message_form; 0 = the NTT form)
+    check(lib().spiral_gpu_pack_server_fold_trials_batch(hs, len(servers), code, ptrs, 0 if form == "ntt" else qs[0].size, C.c_void_p(folded_ptr)))
+
+
+def pack_gathered_batch(servers, gathered_ptr: int, cuts, block_cts: int, want_packed: bool = False, wire: bool = False):
+    """the root's half: the all-gathered blocks at gathered_ptr (block r = rank r's [lane][k] of the trials [cuts[r], cuts[r + 1]), at a stride of
+    block_cts ciphertexts) packed and switched for all n clients in one lane-aware launch sequence.  servers: n lanes of one image on the root, lane b
+    the client that was lane b on every rank.  Returns [(response, packed or None) per server], and with wire=True also their wire forms
+    [n, bytes] uint8.  See include/spiral_gpu.h spiral_gpu_pack_server_pack_gathered_batch"""
+    what = "pack_gathered_batch"
+    servers, hs = _lane_handles(servers, what)
+    cuts = [int(c) for c in cuts]
+    if len(cuts) < 2 or min(cuts) < 0 or max(cuts) >= 1 << 32:
+        raise ValueError(f"{what}: cuts {cuts}: at least two, each a uint32")
+    s0 = servers[0]
+    n = s0.out_n
+    resp = [np.zeros((n + 1, n, N), dtype=np.uint64) for _ in servers]
+    packed = [np.zeros((n + 1, n, 2, N), dtype=np.uint64) if want_packed else None for _ in servers]
+    arr = lambda xs: (U64P * len(xs))(*[_p(x) if x is not None else None for x in xs])
+    wires = np.zeros((len(servers), lib().spiral_gpu_response_wire_bytes(C.byref(s0.params), n)), dtype=np.uint8) if wire else None
+    check(lib().spiral_gpu_pack_server_pack_gathered_batch(hs, len(servers), C.c_void_p(gathered_ptr), (C.c_uint32 * len(cuts))(*cuts), len(cuts) - 1,
+                                                           int(block_cts), arr(resp), arr(packed) if want_packed else None,
+                                                           wires.ctypes.data_as(C.c_void_p) if wire else None))
+    out = list(zip(resp, packed))
+    return (out, wires) if wire else out
 
 
 def time_sweep_batch(servers, iters: int = 10) -> float:
