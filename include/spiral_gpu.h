@@ -67,6 +67,11 @@ int spiral_gpu_get_shape(const spiral_gpu_params *p, spiral_gpu_shape *out);
  * 0 when not; -1 (spiral_gpu_last_error) for bad parameters or a bad shard.  A function of the parameters and of ONE option, "sweep_narrow" as it
  * is when asked (fewer than 64 ciphertexts per slot only), no GPU needed.  The SpiralPack twin is spiral_gpu_pack_has_limb_form. */
 int spiral_gpu_has_limb_form(const spiral_gpu_params *p, uint32_t j_begin, uint32_t j_end);
+/* The same for the image of a column shard (spiral_gpu_server_create_column_shard): num_per / n_ranks ciphertexts per slot and the whole first
+ * dimension -- the answer of spiral_gpu_has_limb_form for the parameters with nu2 - log2 n_ranks, the same rule and the same option "sweep_narrow",
+ * read now.  Host only.  A rank count that gives no shard (not a power of two, fewer columns per shard than a shard needs) has no image: 0, and
+ * spiral_gpu_last_error says why; -1 for a null or invalid parameter set. */
+int spiral_gpu_column_shard_has_limb_form(const spiral_gpu_params *p, uint32_t n_ranks);
 
 /* Process-wide options: schedule forms that compute the same function (the reference has one form of each: its own loops).  A server takes
  * the values in force when it is created; "fwd2" and "db_stage_bytes" apply to every later call.  Unknown names fail.
@@ -193,6 +198,25 @@ int spiral_gpu_regev_to_gsw(uint64_t *out, const uint64_t *cv_v, const uint64_t 
  * spiral_gpu_server_acc). */
 int spiral_gpu_server_create(const spiral_gpu_params *p, int device, uint32_t j_begin, uint32_t j_end,
                              spiral_gpu_server **out);
+/* A COLUMN SHARD: rank `rank` of n_ranks = G (a power of two) holds, for ALL first-dimension indices j, the ciphertext columns ii = rank + G k,
+ * k < L = num_per / G -- the chunk the reduce-scatter of a j-sharded answer hands that rank.  Items map to (ii = i % num_per, j = i / num_per) and G
+ * divides num_per, so the shard's image is the ordinary image of L columns of the items i = rank (mod G), item i at local index i / G.  Its sweep
+ * yields finished sums for its own chunk: a sharded answer needs no accumulator reduce, only the all-gather of the folded ciphertexts (below:
+ * spiral_gpu_server_run_column_batch).  The price: every rank expands and converts the whole query.
+ * Bound: L >= 1, i.e. n_ranks <= num_per (a base server answers from one column: nu2 = 0); a larger or non-power-of-two n_ranks, or rank >= n_ranks,
+ * is refused and the message names the bound.  The fold-rank count is fixed to n_ranks (set_fold_ranks with another count fails); n_ranks = 1 gives a
+ * server whose run_column_batch followed by fold_root_batch equals run_query.  create_lane on a column shard yields a lane of the same rank.
+ * Database calls on a column shard: gen_db leaves exactly the columns rank + G k of the unsharded gen_db of that seed; load_db takes the full
+ * reference layout and keeps its columns; load_db_items takes a run of consecutive items and keeps every G-th; update_db_items writes the ids it
+ * holds and skips the rest; read_db_items / read_db_items_at fill in the shard's own items of the caller's buffer and leave every other byte alone
+ * (G shards reading into one buffer reassemble the database); fill_db_random, set_db_format, db_format, db_device_bytes as on any image.  The test
+ * readers read_db_item, read_db_slots and read_db_columns refuse a column shard by name.
+ * Answer calls: bind_keys, set_query_batch, read_response_wire_batch, fold_root(_batch) and the per-server setters and readers take a column shard;
+ * the stage calls expand, convert, first_dim(_batch) work on its L columns.  run_query, answer*, run_query_batch*, run_query_instances*,
+ * run_pre_sweep(_batch), run_expand_pack(_batch), run_unpack_convert_sweep(_batch), fold_local(_batch), lift, fold, run_post, set_expand_shard and
+ * set_sweep_stages refuse it, naming the reason; so does any multi-lane call whose servers are not all column shards of one rank and rank count, or
+ * none. */
+int spiral_gpu_server_create_column_shard(const spiral_gpu_params *p, int device, uint32_t rank, uint32_t n_ranks, spiral_gpu_server **out);
 void spiral_gpu_server_destroy(spiral_gpu_server *s);
 /* use an external HIP stream (hipStream_t as void*); NULL = the server's own stream */
 int spiral_gpu_server_set_stream(spiral_gpu_server *s, void *hip_stream);
@@ -495,6 +519,17 @@ int spiral_gpu_server_run_expand_pack_batch(spiral_gpu_server *const *servers, u
 int spiral_gpu_server_run_unpack_convert_sweep_batch(spiral_gpu_server *const *servers, uint32_t n, const void *gathered_bits, void *acc);
 int spiral_gpu_server_fold_local_batch(spiral_gpu_server *const *servers, uint32_t n, const void *chunk, void *out_cts);
 int spiral_gpu_server_fold_root_batch(spiral_gpu_server *const *servers, uint32_t n, const void *gathered_cts, void *responses, void *wire);
+/* Batches on a COLUMN-sharded database (create_column_shard): a rank's whole local share for n <= 8 clients in one call.  servers: this rank's column
+ * shard owner and its lanes, each with its client's public parameters and query.  One launch sequence: every lane's expansion and conversion (the
+ * sequence of run_pre_sweep_batch; the whole first dimension on every rank), ONE pass over the shard for all lanes straight into each lane's own
+ * accumulators (matrix cores where the image has limb planes -- converted in place on first use, as a batch does --, else the vector-ALU passes),
+ * the first nu2 - log2 G fold rounds on those L ciphertexts, and each lane's surviving ciphertext to out_cts = [lane][CT], fold_local_batch's
+ * layout.  There is no rank-major buffer, no reduce and no chunk copy.  Then, by the caller: one all-gather of out_cts into [rank][lane][CT] and
+ * fold_root_batch on the root rank (with G = 1: fold_root_batch on out_cts itself).  n = 1 is the single-query flow.  Every argument and lane is
+ * checked before anything is launched (a failing call writes nothing); not during stream capture.  Runs on servers[0]'s stream, the other lanes'
+ * streams ordered around it by events; with use_graphs on servers[0] it is one graph per (lanes, out_cts, image form), and update_db_items keeps
+ * the capture.  The counter "mfma_sweeps" grows by one per call whose pass ran on the matrix cores, launched or replayed. */
+int spiral_gpu_server_run_column_batch(spiral_gpu_server *const *servers, uint32_t n, void *out_cts);
 /* make the sweep write into caller-owned device memory (e.g. a torch tensor) */
 int spiral_gpu_server_set_acc(spiral_gpu_server *s, void *device_ptr);
 

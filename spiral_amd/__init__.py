@@ -13,3 +13,4 @@ from .pack import answer_batch_instances as pack_answer_batch_instances, answer_
 from .server import Server, answer_batch_instances, first_dim_batch, run_query_batch, run_query_batch_instances, time_sweep_batch  # noqa: F401
 from .server import read_response_wire_batch, set_query_batch  # noqa: F401
 from .server import fold_local_batch, fold_root_batch, run_expand_pack_batch, run_pre_sweep_batch, run_unpack_convert_sweep_batch  # noqa: F401
+from .server import run_column_batch  # noqa: F401

@@ -65,6 +65,7 @@ PROTOTYPES = {
     "spiral_gpu_device_count": (C.c_int, []),
     "spiral_gpu_get_shape": (C.c_int, [C.POINTER(Params), C.POINTER(Shape)]),
     "spiral_gpu_has_limb_form": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint32]),
+    "spiral_gpu_column_shard_has_limb_form": (C.c_int, [C.POINTER(Params), C.c_uint32]),
     "spiral_gpu_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "spiral_gpu_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64)]),
     "spiral_gpu_get_tables": (C.c_int, [U64P]),
@@ -89,6 +90,7 @@ PROTOTYPES = {
     "spiral_gpu_scal_to_mat": (C.c_int, [U64P, U64P, U64P, C.c_uint32]),
     "spiral_gpu_regev_to_gsw": (C.c_int, [U64P, U64P, U64P, U64P, C.c_uint32, C.c_uint32]),
     "spiral_gpu_server_create": (C.c_int, [C.POINTER(Params), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "spiral_gpu_server_create_column_shard": (C.c_int, [C.POINTER(Params), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "spiral_gpu_server_destroy": (None, [C.c_void_p]),
     "spiral_gpu_server_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_get_stream": (C.c_void_p, [C.c_void_p]),
@@ -147,6 +149,9 @@ PROTOTYPES = {
     "spiral_gpu_server_run_unpack_convert_sweep_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_fold_local_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_fold_root_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (the list of servers as an opaque pointer, as for the trial-shard calls below: tests/test_lanes_cpu.py keeps a closed table of the calls declared
+    # with POINTER(c_void_p) first; this one goes through the same list check, and tests/test_column_shard_cpu.py runs that table's cases on it)
+    "spiral_gpu_server_run_column_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "spiral_gpu_server_run_scal2mat_sweep": (C.c_int, [C.c_void_p]),
     "spiral_gpu_server_run_unpack_gsw": (C.c_int, [C.c_void_p, C.c_void_p]),
     "spiral_gpu_server_set_sweep_stages": (C.c_int, [C.c_void_p, C.c_uint32]),

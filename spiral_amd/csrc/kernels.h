@@ -185,8 +185,9 @@ struct FwdParamsCore {
     uint32_t* err;
     // LD_DBGEN / ST_DB
     uint64_t seed, p_db;
-    uint64_t item_base;                 // first item handled by this launch
+    uint64_t item_base;                 // first item (of the image) handled by this launch
     uint32_t num_per, dim0_shard, j0;   // DB geometry of this shard
+    uint32_t item_stride, item_off;     // LD_DBGEN: the image's item l is the database's item l * item_stride + item_off (transform_jobs.h DbGeometry)
 };
 template <class L>
 struct FwdParamsT : FwdParamsCore {
@@ -477,8 +478,9 @@ hipError_t launch_sweep_mfma(const uint64_t* db_limbs, const uint32_t* const* qs
 extern std::atomic<uint64_t> g_mfma_sweeps;
 // reference DB layout (src/spiral.cpp:1139-1153) -> device layout, for the j-range [j0, j0 + dim0_shard): db_ref holds the nz
 // consecutive z slabs z0 .. z0+nz-1, db_dev is the base of the shard's device database
+// (col0, col_step: the image's column ii is the reference's column col0 + col_step * ii, of col_step * num_per: a column shard's)
 void launch_db_relayout(const uint64_t* db_ref, uint64_t* db_dev, uint32_t num_per, uint32_t dim0, uint32_t j0, uint32_t dim0_shard, uint32_t z0,
-                        uint32_t nz, hipStream_t s);
+                        uint32_t nz, hipStream_t s, uint32_t col0 = 0, uint32_t col_step = 1);
 // reference reorientCiphertexts layout (z, j, m, r_pad4) u64 -> sweep query records
 void launch_qs_from_reoriented(const uint64_t* reoriented, uint32_t* qs, uint32_t jm_total, hipStream_t s);
 void launch_fill_db_random(uint64_t* db_dev, uint32_t num_per, uint32_t dim0_shard, uint64_t seed, hipStream_t s);

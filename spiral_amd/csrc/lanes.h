@@ -40,6 +40,8 @@ enum LaneNeeds : uint32_t {
     MOVES_DATA = 128,   // the call only moves messages in or responses out (set_query_batch, read_response_wire_batch): it depends on no query, no
                         // public parameters and no schedule, so lanes of a sharded batch and lanes with other schedules are taken too
     TRIAL_SHARDS = 256, // SpiralPack: the lanes may hold a trial range only (fold_trials_batch, pack_gathered_batch, bind_keys); every other call refuses them
+    COLUMN_SHARDS = 512, // the base server: the lanes may be column shards (fold_root_batch; the calls that only move data or keys always take them)
+    COLUMN_ONLY = 1024,  // ... and must be (run_column_batch)
     SHARD_LANES = SHARDED | NO_CAPTURE,
 };
 

@@ -46,8 +46,9 @@ __global__ __launch_bounds__(256, 8) void ntt_forward_kernel(Tables t, FwdParams
     uint32_t lo[8], hi[8];
 
     if constexpr (LOAD == LD_DBGEN) {
-        // block b <-> (item, polynomial mc) ; coefficient index within the item = mc*N + z
-        const uint64_t item = p.item_base + (b >> 2);
+        // block b <-> (item, polynomial mc) ; coefficient index within the item = mc*N + z.  `item` is the database's id: what the generator is
+        // keyed by and the staged stream is indexed by (the store below places the image's item)
+        const uint64_t item = (p.item_base + (b >> 2)) * p.item_stride + p.item_off;
         const uint32_t mc = b & 3u;
         const uint64_t half_p = p.p_db >> 1;
 #pragma unroll

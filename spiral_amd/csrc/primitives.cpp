@@ -97,6 +97,18 @@ int spiral_gpu_has_limb_form(const spiral_gpu_params* p, uint32_t j_begin, uint3
     if (j_begin >= j_end || j_end > s.dim0) return fail("bad first-dimension shard [%u, %u) of %u", j_begin, j_end, s.dim0);
     return DbLayout::base(s.num_per, j_end - j_begin).limbs_ok() ? 1 : 0;  // (below 64 ciphertexts per slot: option sweep_narrow, as read now)
 }
+// the twin for a column shard's image: L = num_per / n_ranks columns and the whole first dimension, the same rule read in the same place.  A rank count
+// that gives no shard (not a power of two, L below the bound) has no image and so no limb form: 0, and last_error says why
+int spiral_gpu_column_shard_has_limb_form(const spiral_gpu_params* p, uint32_t n_ranks) {
+    if (!p) return fail("null argument");
+    spiral_gpu_shape s;
+    spiral_gpu_params q = *p;
+    q.direct_upload = 1;  // (as above)
+    if (shape_of(&q, &s)) return -1;
+    const uint32_t L = column_shard_columns(s.num_per, 0, n_ranks);
+    if (!L) return 0;
+    return DbLayout::base(L, s.dim0).limbs_ok() ? 1 : 0;
+}
 int spiral_gpu_get_tables(uint64_t* out) {
     if (!out) return fail("null argument");
     tables_host_rows(out);

@@ -21,7 +21,7 @@ uint32_t fold_dpb(const spiral_gpu_server* S, uint32_t n_src) {
 int srv_alloc(spiral_gpu_server* S, DbImage* owners) {
     const spiral_gpu_params& p = S->p;
     const spiral_gpu_shape& s = S->s;
-    S->img = owners ? owners->share() : DbImage::create(DbLayout::base(s.num_per, S->dim0_shard), S);  // (a query lane: the owner's image)
+    S->img = owners ? owners->share() : DbImage::create(DbLayout::base(srv_np(S), S->dim0_shard), S);  // (a query lane: the owner's image)
     if (!S->img) return -1;
     S->n_cv = p.direct_upload ? s.n_bits : (1u << s.g);
     const size_t ngs = (size_t)p.nu2 * s.ell;
@@ -127,12 +127,13 @@ int download_pk_as_ref(spiral_gpu_server* S, const uint64_t* pk, IndexMap map, u
     return 0;
 }
 
-int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, uint32_t j_end, DbImage* owners, spiral_gpu_server** out) {
+int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, uint32_t j_end, DbImage* owners, spiral_gpu_server** out, ColumnShard col = {}) {
     if (!p || !out) return fail("null argument");
     spiral_gpu_shape s;
     if (shape_of(p, &s)) return -1;
     if (j_end == 0 && j_begin == 0) j_end = s.dim0;
     if (j_begin >= j_end || j_end > s.dim0) return fail("bad first-dimension shard [%u, %u) of %u", j_begin, j_end, s.dim0);
+    if (col.on && !column_shard_columns(s.num_per, col.rank, 1u << col.g_log)) return -1;
     HIP_OK(hipSetDevice(device));
     spiral_gpu_server* S = new spiral_gpu_server();
     S->p = *p;
@@ -141,6 +142,8 @@ int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, uint32_
     S->j0 = j_begin;
     S->j1 = j_end;
     S->dim0_shard = j_end - j_begin;
+    S->col = col;
+    if (col.on) S->fold_g_log = col.g_log;  // the last log2 G rounds are the root's (fold_root_batch): fixed for the server's life
     {  // the process-wide options as they stand now (spiral_gpu_set_option; SPIRAL_FOLD_PAIR / SPIRAL_SWEEP_MFMA give their initial values)
         const Options& o = options();
         S->fold_chain = o.fold_chain != 0;
@@ -191,6 +194,7 @@ int srv_create(const spiral_gpu_params* p, int device, uint32_t j_begin, uint32_
 
 int read_db_region(spiral_gpu_server* S, uint32_t z_begin, uint32_t nz, uint32_t ii0, uint32_t n_ii, uint64_t* out) {
     if (!S || !out) return fail("null argument");
+    if (refuse_column(S, "read_db_slots / read_db_columns (read its items with read_db_items)")) return -1;
     HIP_OK(hipSetDevice(S->device));
     if (z_begin >= kN || nz == 0 || nz > kN - z_begin) return fail("slot range out of bounds");
     if (n_ii == 0 || ii0 >= S->s.num_per || n_ii > S->s.num_per - ii0) return fail("column range out of bounds");
@@ -239,9 +243,9 @@ int sweep_one(spiral_gpu_server* S, int stage) {
             return fail("a staged sweep needs the packed database image, and a batch has since converted it to limb planes: call set_sweep_stages again (or set option one_image = 0)");
         const uint32_t* qs[1] = {(const uint32_t*)S->qs.p};
         uint64_t* acc[1] = {S->acc};
-        return sweep_mfma(H->db.p, qs, acc, 1, S->s.num_per, 2 * S->dim0_shard, S->fold_g_log, S->stream, S->sweep_k_log);
+        return sweep_mfma(H->db.p, qs, acc, 1, srv_np(S), 2 * S->dim0_shard, sweep_g_log(S), S->stream, S->sweep_k_log);
     }
-    launch_sweep(H->db.p, (const uint32_t*)S->qs.p, S->acc, S->s.num_per, 2 * S->dim0_shard, S->fold_g_log, S->stream, S->sweep_k_log, stage);
+    launch_sweep(H->db.p, (const uint32_t*)S->qs.p, S->acc, srv_np(S), 2 * S->dim0_shard, sweep_g_log(S), S->stream, S->sweep_k_log, stage);
     return 0;
 }
 
@@ -411,11 +415,19 @@ int spiral_gpu_server_create(const spiral_gpu_params* p, int device, uint32_t j_
     return srv_create(p, device, j_begin, j_end, nullptr, out);
 }
 
+int spiral_gpu_server_create_column_shard(const spiral_gpu_params* p, int device, uint32_t rank, uint32_t n_ranks, spiral_gpu_server** out) {
+    if (!p || !out) return fail("null argument");
+    spiral_gpu_shape s;
+    if (shape_of(p, &s)) return -1;
+    if (!column_shard_columns(s.num_per, rank, n_ranks)) return -1;
+    return srv_create(p, device, 0, 0, nullptr, out, ColumnShard{true, rank, ceil_log2(n_ranks)});
+}
+
 int spiral_gpu_server_create_lane(spiral_gpu_server* owner, spiral_gpu_server** out) {
     if (!owner || !out) return fail("null argument");
     if (owner->img->owner != owner) return fail("the owner does not own its database image");
     if (!owner->img->loaded) return fail("the owner has no database loaded");
-    return srv_create(&owner->p, owner->device, owner->j0, owner->j1, owner->img, out);
+    return srv_create(&owner->p, owner->device, owner->j0, owner->j1, owner->img, out, owner->col);  // (a column shard's lane is one of the same rank)
 }
 
 void spiral_gpu_server_destroy(spiral_gpu_server* S) {
@@ -459,7 +471,8 @@ int spiral_gpu_server_load_db(spiral_gpu_server* S, const uint64_t* database) {
             st.release();
             return fail("database upload failed");
         }
-        launch_db_relayout(st.p, S->img->db.p, S->s.num_per, S->s.dim0, S->j0, S->dim0_shard, z, nz, S->stream);
+        // (a column shard keeps the reference's columns rank + G k: its own num_per is L, the slab's L G)
+        launch_db_relayout(st.p, S->img->db.p, srv_np(S), S->s.dim0, S->j0, S->dim0_shard, z, nz, S->stream, S->col.rank, col_ranks(S));
         if (hipStreamSynchronize(S->stream) != hipSuccess) {
             st.release();
             return fail("database relayout failed");
@@ -474,8 +487,10 @@ int spiral_gpu_server_gen_db(spiral_gpu_server* S, uint64_t seed) {
     if (!S) return fail("null server");
     if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
-    FwdJob encode = db_encode_job(LD_DBGEN, ST_DB, S->img->db.p, S->p.p_db, {.num_per = S->s.num_per, .dim0_shard = S->dim0_shard, .j0 = S->j0});
-    const uint64_t items = (uint64_t)S->dim0_shard * S->s.num_per, first = (uint64_t)S->j0 * S->s.num_per;
+    // (a column shard: local item l is the database's item rank + G l, in an image of L columns)
+    FwdJob encode = db_encode_job(LD_DBGEN, ST_DB, S->img->db.p, S->p.p_db,
+                                  {.num_per = srv_np(S), .dim0_shard = S->dim0_shard, .j0 = S->j0, .item_stride = col_ranks(S), .item_off = S->col.rank});
+    const uint64_t items = (uint64_t)S->dim0_shard * srv_np(S), first = (uint64_t)S->j0 * srv_np(S);
     const uint64_t chunk = 1u << 16;  // items per launch (4 polynomials each)
     S->img->begin_rewrite();
     for (uint64_t done = 0; done < items; done += chunk) {
@@ -496,12 +511,17 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
                                                                          (unsigned long long)n_items, (unsigned long long)total);
     // item i lives at (ii = i % num_per, j = i / num_per): this shard holds the items of j in [j0, j1)
     const uint64_t lo = std::max<uint64_t>(first_item, (uint64_t)S->j0 * S->s.num_per), hi = std::min<uint64_t>(first_item + n_items, (uint64_t)S->j1 * S->s.num_per);
-    FwdJob encode = db_encode_job(LD_DBGEN, ST_DB, S->img->db.p, S->p.p_db, {.num_per = S->s.num_per, .dim0_shard = S->dim0_shard, .j0 = S->j0});
+    const uint64_t G = col_ranks(S), g = S->col.rank;
+    FwdJob encode = db_encode_job(LD_DBGEN, ST_DB, S->img->db.p, S->p.p_db,
+                                  {.num_per = srv_np(S), .dim0_shard = S->dim0_shard, .j0 = S->j0, .item_stride = (uint32_t)G, .item_off = (uint32_t)g});
     // a partial load scatters packed words into the image: an image a batch has converted to limb planes goes back to the packed form first
     if (S->img->begin_partial(S->stream)) return -1;
     if (ingest_items(items, coeff_bits, first_item, lo, hi, 4, S->p.p_db, S->stream, [&](const uint8_t* d_items, uint32_t* d_err, uint64_t first, uint64_t n) {
+            // a column shard keeps every G-th item of the staged run, the ids = g (mod G): local items [l0, l1), read at item stride G
+            const uint64_t l0 = (first + G - 1 - g) / G, l1 = (first + n + G - 1 - g) / G;  // (g < G: no underflow; G = 1: [first, first + n))
+            if (l0 >= l1) return;
             S->img->dirty();
-            db_encode_staged(encode, d_items, coeff_bits, d_err, first, (uint32_t)(n * 4));
+            db_encode_staged(encode, d_items, coeff_bits, d_err, first, (uint32_t)((l1 - l0) * 4), l0);
             launch_job(S->tb, encode, S->stream);
         }))
         return -1;
@@ -518,10 +538,11 @@ int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, u
     HIP_OK(hipSetDevice(S->device));
     const uint64_t np = S->s.num_per;
     if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
-    std::vector<UpdateItem> sel;  // the ids of this shard's j-range
+    std::vector<UpdateItem> sel;  // the ids of this shard's j-range (a column shard: of its columns, (j, ii) at (j, ii / G))
     for (uint64_t k = 0; k < n; k++) {
         const uint64_t j = item_ids[k] / np;
-        if (j >= S->j0 && j < S->j1) sel.push_back(UpdateItem{k, (uint32_t)(j - S->j0), (uint32_t)(item_ids[k] % np)});
+        const uint32_t ii = (uint32_t)(item_ids[k] % np);
+        if (j >= S->j0 && j < S->j1 && holds_column(S, ii)) sel.push_back(UpdateItem{k, (uint32_t)(j - S->j0), ii >> col_g_log(S)});
     }
     return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target());
 }
@@ -538,6 +559,14 @@ int spiral_gpu_server_read_db_items(spiral_gpu_server* S, void* items, uint32_t 
     if (check_export_width(coeff_bits, S->p.p_db)) return -1;
     const uint64_t lo = std::max<uint64_t>(first_item, S->j0 * np), hi = std::min<uint64_t>(first_item + n_items, S->j1 * np);
     if (lo >= hi) return 0;
+    if (S->col.on && S->col.g_log) {  // its items lie G apart in `items`: the table form, each to its own place, the bytes between left alone
+        const uint64_t G = col_ranks(S), g = S->col.rank, L = srv_np(S);
+        std::vector<ExportItem> sel;
+        sel.reserve((size_t)((hi - lo) / G + 1));
+        for (uint64_t i = lo + (g + G - lo % G) % G; i < hi; i += G) sel.push_back(ExportItem{i - first_item, (uint32_t)(i / np), (uint32_t)((i / G) % L)});
+        return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), 0, 0, 0, &sel,
+                            [&](uint64_t pos) { return first_item + pos; });
+    }
     return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), lo - S->j0 * np, hi - lo, lo - first_item, nullptr,
                         [&](uint64_t pos) { return first_item + pos; });
 }
@@ -552,13 +581,15 @@ int spiral_gpu_server_read_db_items_at(spiral_gpu_server* S, void* items, uint32
     std::vector<ExportItem> sel;  // the ids of this shard's j-range
     for (uint64_t k = 0; k < n; k++) {
         const uint64_t j = item_ids[k] / np;
-        if (j >= S->j0 && j < S->j1) sel.push_back(ExportItem{k, (uint32_t)(j - S->j0), (uint32_t)(item_ids[k] % np)});
+        const uint32_t ii = (uint32_t)(item_ids[k] % np);
+        if (j >= S->j0 && j < S->j1 && holds_column(S, ii)) sel.push_back(ExportItem{k, (uint32_t)(j - S->j0), ii >> col_g_log(S)});
     }
     return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), 0, 0, 0, &sel, [&](uint64_t pos) { return item_ids[pos]; });
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {
     if (!S || !out) return fail("null argument");
+    if (refuse_column(S, "read_db_item (read its items with read_db_items_at)")) return -1;
     HIP_OK(hipSetDevice(S->device));
     const uint64_t j = item / S->s.num_per;
     if (j < S->j0 || j >= S->j1) return fail("item %llu is not in this shard", (unsigned long long)item);
@@ -597,7 +628,7 @@ int spiral_gpu_server_fill_db_random(spiral_gpu_server* S, uint64_t seed) {
     if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db): load it through the owner");
     HIP_OK(hipSetDevice(S->device));
     S->img->begin_rewrite();
-    launch_fill_db_random(S->img->db.p, S->s.num_per, S->dim0_shard, seed, S->stream);
+    launch_fill_db_random(S->img->db.p, srv_np(S), S->dim0_shard, seed, S->stream);
     HIP_OK(hipStreamSynchronize(S->stream));
     S->img->finish_load();
     return 0;
@@ -611,8 +642,8 @@ int spiral_gpu_server_share_db(spiral_gpu_server* S, spiral_gpu_server* owner) {
     if (!S || !owner || S == owner) return fail("share_db needs two different servers");
     if (owner->img->owner != owner) return fail("the owner does not own its database image");
     if (S->device != owner->device || S->j0 != owner->j0 || S->dim0_shard != owner->dim0_shard || S->p.nu1 != owner->p.nu1 || S->p.nu2 != owner->p.nu2 ||
-        S->s.num_per != owner->s.num_per)
-        return fail("share_db: the servers differ in device, shard or database geometry");
+        S->s.num_per != owner->s.num_per || !(S->col == owner->col))
+        return fail("share_db: the servers differ in device, shard (first-dimension range, or column shard and its rank) or database geometry");
     // the image encodes plaintexts mod p_db (centred lift) and the lane's response switch uses ITS p_db: they must agree
     if (S->p.p_db != owner->p.p_db || S->p.direct_upload != owner->p.direct_upload)
         return fail("share_db: the servers differ in plaintext modulus or query form");
@@ -688,6 +719,7 @@ int spiral_gpu_server_first_dim(spiral_gpu_server* S) {
 // stage; first_dim launches all of them at once into the same layout.
 int spiral_gpu_server_set_sweep_stages(spiral_gpu_server* S, uint32_t n_stages) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "set_sweep_stages")) return -1;
     if (n_stages == 0 || (n_stages & (n_stages - 1))) return fail("sweep stages must be a power of two");
     const uint32_t k_log = ceil_log2(n_stages);
     if (!sweep_stages_ok(S->s.num_per, 2 * S->dim0_shard, S->fold_g_log, k_log))
@@ -702,6 +734,7 @@ int spiral_gpu_server_set_sweep_stages(spiral_gpu_server* S, uint32_t n_stages) 
 
 uint32_t spiral_gpu_server_max_sweep_stages(spiral_gpu_server* S) {
     if (!S) return 0;
+    if (S->col.on) return 1;
     uint32_t k = 0;
     while (k < 16 && sweep_stages_ok(S->s.num_per, 2 * S->dim0_shard, S->fold_g_log, k + 1)) k++;
     return 1u << k;
@@ -709,6 +742,7 @@ uint32_t spiral_gpu_server_max_sweep_stages(spiral_gpu_server* S) {
 
 int spiral_gpu_server_first_dim_stage(spiral_gpu_server* S, uint32_t stage) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "first_dim_stage")) return -1;
     if (!S->img->loaded) return fail("no database loaded");
     if (stage >= (1u << S->sweep_k_log)) return fail("stage %u of %u", stage, 1u << S->sweep_k_log);
     if (S->sweep_k_log == 0) return spiral_gpu_server_first_dim(S);
@@ -718,6 +752,7 @@ int spiral_gpu_server_first_dim_stage(spiral_gpu_server* S, uint32_t stage) {
 
 int spiral_gpu_server_lift(spiral_gpu_server* S, int reduce_first) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "lift")) return -1;
     launch_job(S->tb, lift_job(S->acc, S->raw.p, S->s.num_per * 6, {.pre_reduce = reduce_first != 0}), S->stream);
     S->raw_from_acc = true;
     return 0;
@@ -725,6 +760,7 @@ int spiral_gpu_server_lift(spiral_gpu_server* S, int reduce_first) {
 
 int spiral_gpu_server_fold(spiral_gpu_server* S) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "fold")) return -1;
     if (srv_join_side(S)) return -1;  // no-op inside run_post's capture: run_post joined before capturing
     return run_fold_rounds(S, {.np0 = S->s.num_per, .rounds = S->p.nu2, .raw_addend = S->raw_from_acc ? S->acc : nullptr});  // src/spiral.cpp:1622-1626
 }
@@ -732,6 +768,8 @@ int spiral_gpu_server_fold(spiral_gpu_server* S) {
 int spiral_gpu_server_set_fold_ranks(spiral_gpu_server* S, uint32_t n_ranks) {
     if (enter(S)) return -1;
     if (n_ranks == 0 || (n_ranks & (n_ranks - 1)) || n_ranks > S->s.num_per) return fail("fold ranks must be a power of two <= num_per");
+    if (S->col.on && n_ranks != col_ranks(S))
+        return fail("set_fold_ranks: this server is a column shard of %u ranks (create_column_shard): its fold-rank count is fixed to that, not %u", col_ranks(S), n_ranks);
     S->fold_g_log = ceil_log2(n_ranks);
     S->sweep_k_log = 0;  // the stage layout depends on the rank count: set_sweep_stages comes after
     srv_drop_graphs(S);
@@ -744,6 +782,7 @@ int spiral_gpu_server_set_fold_ranks(spiral_gpu_server* S, uint32_t n_ranks) {
 // before convert().  Needs the reordered layout (stopround > 0, src/spiral.cpp:2027-2036) and query compression.
 int spiral_gpu_server_set_expand_shard(spiral_gpu_server* S, uint32_t rank, uint32_t n_ranks) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "set_expand_shard")) return -1;
     srv_drop_graphs(S);
     if (n_ranks <= 1) {
         S->ex_shard = ExpandShard{};
@@ -840,6 +879,7 @@ int spiral_gpu_server_run_pre(spiral_gpu_server* S) {
 
 int spiral_gpu_server_run_query(spiral_gpu_server* S) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "run_query")) return -1;
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
     if (!S->img->loaded) return fail("no database loaded");
     if (S->overlap) {  // the split schedule is three launch groups on two streams, not one graph
@@ -860,6 +900,7 @@ int spiral_gpu_server_run_query(spiral_gpu_server* S) {
 
 int spiral_gpu_server_fold_local(spiral_gpu_server* S, const void* acc_chunk, void* out_ct) {
     if (!S || !acc_chunk || !out_ct) return fail("null argument");
+    if (refuse_column(S, "fold_local")) return -1;
     HIP_OK(hipSetDevice(S->device));
     const uint32_t L = S->s.num_per >> S->fold_g_log;
     if (srv_join_side(S)) return -1;
@@ -890,6 +931,7 @@ int spiral_gpu_server_fold_root(spiral_gpu_server* S, const void* gathered_cts) 
 // run_pre + first_dim as one group: what a rank does before the collective
 int spiral_gpu_server_run_pre_sweep(spiral_gpu_server* S) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "run_pre_sweep")) return -1;
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
     if (!S->img->loaded) return fail("no database loaded");
     if (S->overlap) {
@@ -909,6 +951,7 @@ int spiral_gpu_server_run_pre_sweep(spiral_gpu_server* S) {
 // this rank's GSW bits into bits_out; [all-gather]; run_unpack_convert_sweep = unpack of the gathered blocks + convert + sweep
 int spiral_gpu_server_run_expand_pack(spiral_gpu_server* S, void* bits_out) {
     if (!S || !bits_out) return fail("null argument");
+    if (refuse_column(S, "run_expand_pack")) return -1;
     HIP_OK(hipSetDevice(S->device));
     if (!S->have_query || !S->have_pp) return fail("query and public parameters must be set first");
     return run_graph(S, G_EXPAND_PACK, S->stream, {word(bits_out)}, [&]() {
@@ -919,6 +962,7 @@ int spiral_gpu_server_run_expand_pack(spiral_gpu_server* S, void* bits_out) {
 
 int spiral_gpu_server_run_unpack_convert_sweep(spiral_gpu_server* S, const void* gathered) {
     if (!S || !gathered) return fail("null argument");
+    if (refuse_column(S, "run_unpack_convert_sweep")) return -1;
     HIP_OK(hipSetDevice(S->device));
     if (!S->img->loaded) return fail("no database loaded");
     if (int rc = run_graph(S, G_UNPACK_CONVERT_SWEEP, S->stream, {word(gathered)}, [&]() {
@@ -966,6 +1010,7 @@ int spiral_gpu_server_run_unpack_gsw(spiral_gpu_server* S, const void* gathered)
 
 int spiral_gpu_server_run_post(spiral_gpu_server* S, int reduce_first) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "run_post")) return -1;
     if (srv_join_side(S)) return -1;
     if (int rc = run_graph(S, reduce_first ? G_POST_REDUCE : G_POST, S->stream, {}, [&]() {
             return run_fold_rounds(S, {.np0 = S->s.num_per, .rounds = S->p.nu2, .src_pk = S->acc, .pre_reduce = reduce_first != 0, .finish = true});  // lift chained into round 0, switch into the last
@@ -977,6 +1022,7 @@ int spiral_gpu_server_run_post(spiral_gpu_server* S, int reduce_first) {
 
 int spiral_gpu_server_answer_resident(spiral_gpu_server* S, double stage_us[8]) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "answer_resident")) return -1;
     hipStream_t st = S->stream;
     const bool g = S->use_graphs;
     HIP_OK(hipEventRecord(S->ev[0], st));
@@ -1030,6 +1076,7 @@ int spiral_gpu_server_answer_resident(spiral_gpu_server* S, double stage_us[8]) 
 
 int spiral_gpu_server_answer(spiral_gpu_server* S, const uint64_t* query, uint64_t* final_ct, uint64_t* response, double stage_us[8]) {
     if (enter(S)) return -1;
+    if (refuse_column(S, "answer")) return -1;
     if (spiral_gpu_server_set_query(S, query)) return -1;
     if (spiral_gpu_server_answer_resident(S, stage_us)) return -1;
     if (final_ct) HIP_OK(hipMemcpy(final_ct, S->raw.p, 6 * kPolyBytes, hipMemcpyDeviceToHost));
@@ -1136,14 +1183,14 @@ uint64_t spiral_gpu_server_sweep_device_bytes(spiral_gpu_server* S) {
     // what one launch has to move on this device: the database in its device layout (7 bytes per word when packed),
     // the query records (48 B per (z, j)) and the accumulators
     const uint64_t n = kN;
-    return (uint64_t)db_device_words(2 * S->s.num_per, S->dim0_shard) * 8 + (uint64_t)S->dim0_shard * 48 * n + (uint64_t)S->s.num_per * 6 * n * 8;
+    return (uint64_t)db_device_words(2 * srv_np(S), S->dim0_shard) * 8 + (uint64_t)S->dim0_shard * 48 * n + (uint64_t)srv_np(S) * 6 * n * 8;
 }
 
 uint64_t spiral_gpu_server_sweep_bytes(spiral_gpu_server* S) {
     if (!S) return 0;
     // SURVEY.md 8d at 8 B per packed word: database + packed query (3 rows x 2 x dim0) + output (2 limbs as u64)
     const uint64_t n = kN;
-    return (uint64_t)S->dim0_shard * S->s.num_per * 4 * n * 8 + (uint64_t)S->dim0_shard * 3 * 2 * n * 8 + (uint64_t)S->s.num_per * 6 * 2 * n * 8;
+    return (uint64_t)S->dim0_shard * srv_np(S) * 4 * n * 8 + (uint64_t)S->dim0_shard * 3 * 2 * n * 8 + (uint64_t)srv_np(S) * 6 * 2 * n * 8;
 }
 
 }  // extern "C"

@@ -8,11 +8,19 @@ namespace {
 
 // Checks the lanes servers[0 .. n) of one call and fills their arena offsets: the list, the image, NO_CAPTURE and the layouts in lanes.h, between them
 // the base server's own rules for each lane against servers[0].  Unless SWEEP_ONLY: the same parameters and shard, public parameters set, the default
-// schedule.
+// schedule.  Column shards (create_column_shard): a call takes them where its flags say so (COLUMN_SHARDS, COLUMN_ONLY, a call that only moves data or
+// keys, a sweep on each server's own pointers), every lane then one of the same rank and rank count; their arenas are laid out like a base server's of
+// the same parameters, so it is this check, not the layout comparison, that keeps the two kinds apart.
 int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what, uint32_t needs, Lanes* lanes) {
     const bool whole = !(needs & SWEEP_ONLY), sharded = needs & SHARDED, moves = needs & MOVES_DATA;
+    const bool column_ok = needs & (COLUMN_SHARDS | COLUMN_ONLY | MOVES_DATA | GIVES_KEYS | SWEEP_ONLY);
     return check_lane_list(servers, n, what, needs, lanes, [&](uint32_t b) {
         const spiral_gpu_server *S = servers[0], *L = servers[b];
+        if (L->col.on && !column_ok) return refuse_column(L, what);
+        if ((needs & COLUMN_ONLY) && !L->col.on) return fail("%s: server %u is not a column shard (create_column_shard)", what, b);
+        if (!(L->col == S->col))
+            return fail("%s: server %u is %s, server 0 %s: the lanes of a call are column shards of one rank and rank count, or none is", what, b,
+                        L->col.on ? "a column shard of another rank or rank count" : "no column shard", S->col.on ? "is a column shard" : "is none");
         if (whole && (((needs & NEED_QUERY) && !L->have_query) || (!L->have_pp && !(needs & (GIVES_KEYS | MOVES_DATA))))) return fail("%s: server %u needs its query and public parameters set first", what, b);
         if ((needs & NEED_DB) && !L->img->loaded) return fail("%s: server %u has no database", what, b);
         if ((needs & NEED_RECORDS) && !L->have_records) return fail("%s: server %u has not converted its query (run_pre first)", what, b);
@@ -23,7 +31,8 @@ int check_lanes(spiral_gpu_server* const* servers, uint32_t n, const char* what,
             return fail("%s: server %u has %u fold ranks, server 0 has %u", what, b, 1u << L->fold_g_log, 1u << S->fold_g_log);
         if (sharded && (L->ex_shard.g_log != S->ex_shard.g_log || L->ex_shard.rank != S->ex_shard.rank))
             return fail("%s: server %u has another expansion shard than server 0", what, b);
-        if (whole && !sharded && !moves && (L->acc != L->acc_own.p || L->fold_g_log || L->ex_shard.g_log))
+        // (a column shard's fold ranks are part of what it is, not a setting: bind_keys takes it)
+        if (whole && !sharded && !moves && (L->acc != L->acc_own.p || (L->fold_g_log && !L->col.on) || L->ex_shard.g_log))
             return fail("%s: server %u has an external accumulator, fold ranks or a sharded expansion set", what, b);
         if (!moves && (L->sweep_k_log || (whole && (L->keep_cts || L->overlap || L->side_pending || L->fold_pair != S->fold_pair || L->fold_chain != S->fold_chain))))
             return fail("%s: server %u has keep_cts, a split or staged schedule or other fold options set", what, b);
@@ -80,6 +89,7 @@ int check_instances(const spiral_gpu_server* S, spiral_gpu_server* const* instan
         const spiral_gpu_server* I = instances[k];
         if (!I) return fail("null instance %u", k);
         if (!I->img->loaded) return fail("%s: instance %u has no database", what, k);
+        if (I->col.on) return refuse_column(I, what);
         if (I->device != S->device || I->j0 != S->j0 || I->dim0_shard != S->dim0_shard || I->p.nu1 != S->p.nu1 || I->p.nu2 != S->p.nu2 || I->p.p_db != S->p.p_db ||
             I->p.direct_upload != S->p.direct_upload)
             return fail("%s: instance %u differs from the query's server in device, shard, database geometry or plaintext modulus", what, k);
@@ -392,13 +402,13 @@ int spiral_gpu_server_first_dim_batch(spiral_gpu_server* const* servers, uint32_
     server_records(servers, n, qs, acc);
     const uint64_t* limbs;
     if (limb_image(S0, S0->img, n, &limbs)) return -1;
-    if (!limbs && !sweep_batch_ok(S0->s.num_per, 2 * S0->dim0_shard)) {  // (a packed image: limb planes always come back as `limbs`)
+    if (!limbs && !sweep_batch_ok(srv_np(S0), 2 * S0->dim0_shard)) {  // (a packed image: limb planes always come back as `limbs`)
         for (uint32_t b = 0; b < n; b++)
             if (spiral_gpu_server_first_dim(servers[b])) return -1;
         return 0;
     }
     if (lanes_join(servers, n)) return -1;  // the lanes' records must be complete
-    if (sweep_image(S0->img, limbs, qs, acc, n, S0->fold_g_log, S0->stream)) return -1;
+    if (sweep_image(S0->img, limbs, qs, acc, n, sweep_g_log(S0), S0->stream)) return -1;
     mark_raw_stale(servers, n);
     return lanes_release(servers, n);
 }
@@ -470,6 +480,7 @@ int spiral_gpu_server_run_query_instances(spiral_gpu_server* S, spiral_gpu_serve
 int spiral_gpu_server_answer_instances(spiral_gpu_server* S, spiral_gpu_server* const* instances, uint32_t n, const uint64_t* query, uint64_t* responses,
                                        uint64_t* finals, double* total_us) {
     if (!S || !instances || n == 0 || !query || !responses) return fail("null argument");
+    if (refuse_column(S, "answer_instances")) return -1;
     HIP_OK(hipSetDevice(S->device));
     if (spiral_gpu_server_set_query(S, query)) return -1;
     const size_t bytes = (size_t)n * 6 * kPolyBytes;
@@ -605,7 +616,7 @@ int spiral_gpu_server_fold_local_batch(spiral_gpu_server* const* servers, uint32
 int spiral_gpu_server_fold_root_batch(spiral_gpu_server* const* servers, uint32_t n, const void* gathered_cts, void* responses, void* wire) {
     const char* what = "fold_root_batch";
     Lanes lanes;
-    if (check_lanes(servers, n, what, SHARD_LANES, &lanes)) return -1;
+    if (check_lanes(servers, n, what, SHARD_LANES | COLUMN_SHARDS, &lanes)) return -1;
     if (!gathered_cts) return fail("%s: null buffer", what);
     spiral_gpu_server* S = servers[0];
     const uint32_t G = 1u << S->fold_g_log;
@@ -624,6 +635,42 @@ int spiral_gpu_server_fold_root_batch(spiral_gpu_server* const* servers, uint32_
     return rc;
 }
 
+// A column shard's whole local share (include/spiral_gpu.h): every lane's expansion and conversion, ONE pass over the shard's L columns for all lanes
+// straight into each lane's own accumulators -- finished sums of its own chunk ii = rank + G k, in the order k: no rank-major buffer, nothing to reduce,
+// no chunk to copy in -- the first nu2 - log2 G fold rounds on them as they stand (canonical words: no pre_reduce), each lane's ciphertext out
+int spiral_gpu_server_run_column_batch(spiral_gpu_server* const* servers, uint32_t n, void* out_cts) {
+    const char* what = "run_column_batch";
+    Lanes lanes;
+    if (check_lanes(servers, n, what, SHARD_LANES | COLUMN_ONLY | NEED_QUERY | NEED_DB, &lanes)) return -1;
+    if (!out_cts) return fail("%s: null output buffer", what);
+    spiral_gpu_server* S = servers[0];
+    const uint32_t L = srv_np(S);
+    const size_t ctw = 6 * kN;
+    if (S->img->lay.num_per != L || S->img->lay.dim0 != S->s.dim0) return fail("%s: the image is not this column shard's", what);  // (cannot happen: share_db compares)
+    const uint64_t* limbs;
+    if (limb_image(S, S->img, n, &limbs)) return -1;  // (not inside a capture: it may convert the image)
+    const bool on_limbs = limbs || S->img->format == SPIRAL_GPU_DB_LIMBS;
+    const uint64_t launched = g_mfma_sweeps.load(std::memory_order_relaxed);
+    const int rc = run_lanes(
+        servers, n, G_COLUMN_BATCH, [&](Key* k) { return lane_key(k, servers, n, limbs, {word(out_cts), (uint64_t)S->img->format}); },
+        [&]() {
+            if (convert_lanes(S, lanes)) return -1;
+            const uint32_t* qs[kMaxLanes];
+            uint64_t* acc[kMaxLanes];
+            server_records(servers, n, qs, acc);
+            for (uint32_t b = 0; b < n; b++) acc[b] = S->acc_own.p + lanes.off[b];  // (whatever set_acc says: where the fold below reads)
+            if (sweep_image(S->img, limbs, qs, acc, n, 0, S->stream)) return -1;
+            if (run_fold_rounds(S, {.np0 = L, .rounds = S->p.nu2 - S->col.g_log, .src_pk = S->acc_own.p, .lanes = lanes})) return -1;
+            for (uint32_t b = 0; b < n; b++)
+                HIP_OK(hipMemcpyAsync((uint64_t*)out_cts + b * ctw, S->raw.p + lanes.off[b], ctw * sizeof(uint64_t), hipMemcpyDeviceToDevice, S->stream));
+            return 0;
+        });
+    // "mfma_sweeps" counts this call's pass whether it was launched or replayed: the launcher counts the first, a replay runs no host code
+    if (!rc && on_limbs && g_mfma_sweeps.load(std::memory_order_relaxed) == launched) g_mfma_sweeps.fetch_add(1, std::memory_order_relaxed);
+    if (!rc) mark_swept(servers, n);
+    return rc;
+}
+
 int spiral_gpu_server_time_sweep_batch(spiral_gpu_server* const* servers, uint32_t n, int iters, float* avg_ms) {
     if (!avg_ms || iters <= 0) return fail("time_sweep_batch: bad argument");
     Lanes lanes;
@@ -638,7 +685,7 @@ int spiral_gpu_server_time_sweep_batch(spiral_gpu_server* const* servers, uint32
     HIP_OK(hipDeviceSynchronize());  // (the lanes' streams: their records are complete)
     HIP_OK(hipEventRecord(S->ev[0], S->stream));
     for (int i = 0; i < iters; i++)
-        if (sweep_image(S->img, limbs, qs, acc, n, S->fold_g_log, S->stream)) return -1;
+        if (sweep_image(S->img, limbs, qs, acc, n, sweep_g_log(S), S->stream)) return -1;
     HIP_OK(hipEventRecord(S->ev[1], S->stream));
     HIP_OK(hipStreamSynchronize(S->stream));
     float ms = 0;

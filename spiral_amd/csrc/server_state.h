@@ -33,6 +33,7 @@ enum GraphId : int {
     G_SHARD_UNPACK_SWEEP,
     G_SHARD_FOLD_LOCAL,
     G_SHARD_FOLD_ROOT,
+    G_COLUMN_BATCH,  // run_column_batch
     G_COUNT
 };
 // a captured sequence and the words it was captured for beyond the server's own state (the caller's buffers, the lanes, the images; run_graph)
@@ -41,10 +42,20 @@ struct Captured {
     std::vector<uint64_t> key;
 };
 
+// A column shard (create_column_shard): of the num_per ciphertext columns of the database this server holds ii = rank + G k, k < L = num_per >> g_log,
+// for EVERY first-dimension index -- the base image DbLayout::base(L, dim0) of the items i = rank (mod G), local item i / G.  Its query and fold
+// geometry stay the parameters' (s.num_per, nu2); only what touches the image takes L (srv_np).
+struct ColumnShard {
+    bool on = false;
+    uint32_t rank = 0, g_log = 0;
+    bool operator==(const ColumnShard& o) const { return on == o.on && rank == o.rank && g_log == o.g_log; }
+};
+
 struct spiral_gpu_server : LaneHost {  // (lanes.h: device, stream, img, arena and its layout record, ev_lane)
     spiral_gpu_params p;
     spiral_gpu_shape s;
     uint32_t j0 = 0, j1 = 0, dim0_shard = 0;
+    ColumnShard col;  // set at creation, never changed; fold_g_log is then fixed to col.g_log
     hipStream_t own_stream = nullptr;
     DeviceTables tb;
     bool keep_cts = false, have_pp = false, have_query = false;
@@ -121,6 +132,32 @@ struct FoldJob {
 // the parts of the conversion (convert_part)
 enum ConvertWhat : uint32_t { CONV_S2M = 1, CONV_GSW = 2, CONV_BOTH = 3 };
 
+// the column count L of rank `rank` of n_ranks column shards of a database of num_per columns, or 0 and the error.  The bound: a base server answers
+// from one ciphertext column (nu2 = 0: one sweep, no fold round; the parity tests' random parameter sets draw it), so L = num_per / n_ranks >= 1
+constexpr uint32_t kMinShardColumns = 1;
+inline uint32_t column_shard_columns(uint32_t num_per, uint32_t rank, uint32_t n_ranks) {
+    if (n_ranks == 0 || (n_ranks & (n_ranks - 1))) return fail("column shards: %u ranks, the rank count must be a power of two", n_ranks), 0u;
+    if (num_per / n_ranks < kMinShardColumns)
+        return fail("column shards: %u ranks leave %u of %u ciphertext columns per shard, a shard needs at least %u", n_ranks, num_per / n_ranks, num_per,
+                    kMinShardColumns),
+               0u;
+    if (rank >= n_ranks) return fail("column shard %u of %u: no such rank", rank, n_ranks), 0u;
+    return num_per / n_ranks;
+}
+// the ciphertext columns of the image S sweeps: num_per, or a column shard's L
+inline uint32_t srv_np(const spiral_gpu_server* S) { return S->s.num_per >> (S->col.on ? S->col.g_log : 0u); }
+inline uint32_t col_g_log(const spiral_gpu_server* S) { return S->col.on ? S->col.g_log : 0u; }
+inline uint32_t col_ranks(const spiral_gpu_server* S) { return 1u << col_g_log(S); }
+inline bool holds_column(const spiral_gpu_server* S, uint32_t ii) { return (ii & (col_ranks(S) - 1u)) == (S->col.on ? S->col.rank : 0u); }
+// how a sweep of S's image groups its output: by ii mod G for the distributed fold of a j-shard; a column shard's L columns are one rank's already
+inline uint32_t sweep_g_log(const spiral_gpu_server* S) { return S->col.on ? 0u : S->fold_g_log; }
+// how a one-server entry point that has no meaning on a column shard opens
+inline int refuse_column(const spiral_gpu_server* S, const char* what) {
+    if (S && S->col.on)
+        return fail("%s: this server is a column shard (create_column_shard): it holds %u of %u ciphertext columns, so it answers through run_column_batch, "
+                    "the all-gather and fold_root_batch only", what, srv_np(S), S->s.num_per);
+    return 0;
+}
 void srv_check_epoch(spiral_gpu_server* S);  // (run_graph) drops S's graphs when its image has changed since they were captured
 int srv_join_side(spiral_gpu_server* S);
 void mark_raw_stale(spiral_gpu_server* const* servers, uint32_t n);

@@ -326,7 +326,7 @@ void launch_sweep(const uint64_t* db, const uint32_t* qs, uint64_t* acc, uint32_
 // reference layout (src/spiral.cpp:1139-1153): z*(num_per*2*dim0*2) + ii*(2*dim0*2) + c*(dim0*2) + j*2 + m.
 // `ref` holds the nz slabs z0 .. z0+nz-1 (reference slot order); `dev` is the base of the shard's device database.
 __global__ __launch_bounds__(256) void db_relayout_kernel(const uint64_t* __restrict__ ref, uint64_t* __restrict__ dev, uint32_t num_per, uint32_t dim0,
-                                                          uint32_t j0, uint32_t dim0_shard, uint32_t z0, uint32_t nz) {
+                                                          uint32_t j0, uint32_t dim0_shard, uint32_t z0, uint32_t nz, uint32_t col0, uint32_t col_step) {
     const uint32_t nic = 2 * num_per;
     const size_t o = (size_t)blockIdx.x * 256u + threadIdx.x;  // word of the shard, slab-major
     const size_t per_z = (size_t)dim0_shard * nic * 2u;
@@ -337,13 +337,15 @@ __global__ __launch_bounds__(256) void db_relayout_kernel(const uint64_t* __rest
     rem >>= 1;
     const uint32_t ic = (uint32_t)(rem % nic), jl = (uint32_t)(rem / nic);
     const uint32_t ii = ic >> 1, c = ic & 1u, j = j0 + jl;
-    const uint64_t v = ref[(size_t)zl * ((size_t)num_per * 2u * dim0 * 2u) + (size_t)ii * (2u * dim0 * 2u) + (size_t)c * (dim0 * 2u) + (size_t)j * 2u + m];
+    const uint64_t v = ref[(size_t)zl * ((size_t)num_per * col_step * 2u * dim0 * 2u) + (size_t)(col0 + col_step * ii) * (2u * dim0 * 2u) + (size_t)c * (dim0 * 2u) +
+                           (size_t)j * 2u + m];
     db_put_word(dev, pk_pos(z0 + zl), jl, ic, m, nic, dim0_shard, pack(lo32(v) % kP, hi32(v) % kB));
 }
 void launch_db_relayout(const uint64_t* db_ref, uint64_t* db_dev, uint32_t num_per, uint32_t dim0, uint32_t j0, uint32_t dim0_shard, uint32_t z0,
-                        uint32_t nz, hipStream_t s) {
+                        uint32_t nz, hipStream_t s, uint32_t col0, uint32_t col_step) {
     const size_t words = (size_t)nz * dim0_shard * 2u * num_per * 2u;
-    hipLaunchKernelGGL(db_relayout_kernel, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, s, db_ref, db_dev, num_per, dim0, j0, dim0_shard, z0, nz);
+    hipLaunchKernelGGL(db_relayout_kernel, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, s, db_ref, db_dev, num_per, dim0, j0, dim0_shard, z0, nz, col0,
+                       col_step);
 }
 
 // ---- database read-back (tests / inspection): the inverse maps of the two loaders above ----------------------------------

@@ -109,9 +109,12 @@ inline FwdJob pack_digits_job(FwdLoad load, const uint64_t* src, uint64_t* dst, 
 
 // ---- database encode: plaintext coefficients, centred lift, transform, store in a database layout or linearly (ST_PK, the in-place update) -------------
 // LD_DBGEN: 4 polynomials per item of the shard's j-range [j0, j0 + dim0_shard); LD_DBGEN1: one per item of `trial`, total_n items (dim0_shard = dim0)
+// item_stride, item_off (LD_DBGEN): the image's item l is the database's item l * item_stride + item_off -- a column shard of G ranks holds the items
+// rank (mod G) in an image of num_per / G columns (num_per here is the IMAGE's); 1, 0: the image's items are the database's
 struct DbGeometry {
     uint32_t num_per = 0, dim0_shard = 0, j0 = 0, trial = 0;
     uint64_t total_n = 0;
+    uint32_t item_stride = 1, item_off = 0;
 };
 inline FwdJob db_encode_job(FwdLoad load, FwdStore store, uint64_t* dst, uint64_t p_db, const DbGeometry& g = {}) {
     FwdJob j{{}, load, store, 0};
@@ -124,6 +127,8 @@ inline FwdJob db_encode_job(FwdLoad load, FwdStore store, uint64_t* dst, uint64_
     j.p.j0 = g.j0;
     j.p.trial = g.trial;
     j.p.total_n = g.total_n;
+    j.p.item_stride = g.item_stride;
+    j.p.item_off = g.item_off;
     return j;
 }
 // one launch of it: npolys polynomials from item `first` on, from the seeded generator ...
@@ -132,12 +137,14 @@ inline void db_encode_seeded(FwdJob& j, uint64_t seed, uint64_t first, uint32_t 
     j.p.item_base = first;
     j.nblocks = npolys;
 }
-// ... or from a staged stream of bit-packed items that starts at item `first`; *err is set when a coefficient is not below p_db
-inline void db_encode_staged(FwdJob& j, const uint8_t* items, uint32_t coeff_bits, uint32_t* err, uint64_t first, uint32_t npolys) {
+// ... or from a staged stream of bit-packed items that starts at the database's item `first`; *err is set when a coefficient is not below p_db.
+// image_first: the image's first item of the launch where that is not `first` (a strided geometry: the stream is read at item stride item_stride)
+inline void db_encode_staged(FwdJob& j, const uint8_t* items, uint32_t coeff_bits, uint32_t* err, uint64_t first, uint32_t npolys, uint64_t image_first = ~0ull) {
     j.p.items = items;
     j.p.coeff_bits = coeff_bits;
     j.p.err = err;
-    j.p.items_first = j.p.item_base = first;
+    j.p.items_first = first;
+    j.p.item_base = image_first == ~0ull ? first : image_first;
     j.nblocks = npolys;
 }
 

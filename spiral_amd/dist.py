@@ -293,6 +293,65 @@ def answer_batch_sharded(servers, group=None, bufs=None, *, fold_ranks=None, sha
     return bufs
 
 
+# ---- batches on a column-sharded database (include/spiral_gpu.h create_column_shard, run_column_batch) -----------------------------------------
+def column_batch_collective_bytes(shape, n: int, G: int) -> dict:
+    """bytes the ONE collective of a column-sharded batch step moves per rank, from the shapes alone (nothing timed): the all-gather of the locally
+    folded ciphertexts (its output, [rank][lane][CT]).  Nothing is reduced: every rank's sweep yields finished sums for its own columns"""
+    if G < 1 or (G & (G - 1)) or shape.num_per % G:
+        raise ValueError(f"{G} column shards do not divide num_per = {shape.num_per}")
+    return {"all_gather_cts_out_bytes": batch_gathered_ct_words(n, G) * 8}
+
+
+def column_batch_buffers(servers, world: int, device=None) -> dict:
+    """the device buffers of one rank's column-sharded batch steps (int64 tensors, zeroed), sized for len(servers) clients: "cts" (run_column_batch's
+    output, the all-gather's input), "gathered_cts" and "responses".  No accumulator buffer and no chunk: the sweep writes the lanes' own
+    accumulators.  Keep them across batches: the calls' hipGraphs are keyed by these pointers"""
+    import torch
+
+    n = _batch_n(len(servers))
+    dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
+    z = lambda words: torch.zeros(words, dtype=torch.int64, device=dev)
+    return {"cts": z(batch_ct_words(n)), "gathered_cts": z(batch_gathered_ct_words(n, world)), "responses": z(batch_ct_words(n))}
+
+
+def answer_batch_column_sharded(servers, group=None, bufs=None, *, root=0, wire_ptr: int = 0):
+    """One rank's whole answer of a batch of up to eight clients on a column-sharded database, in order: run_column_batch (expansion, conversion, the
+    sweep of this rank's columns and the local fold rounds), ONE all-gather of the folded ciphertexts, fold_root_batch on `root`.  servers: this rank's
+    column shard owner (Server(params, col_rank=rank, col_ranks=world)) and its lanes, each with its client's public parameters and query set.  bufs:
+    column_batch_buffers(...) (allocated here when None; keep them across batches).  Returns bufs; on the root every lane's BUF_FINAL / BUF_RESPONSE
+    hold its answer and bufs["responses"] the [lane][CT] responses (wire_ptr: optional device [lane] wire forms).  The servers' stream is settled
+    before the collective (on torch's stream) and the collective before the root's fold, as in answer_batch_sharded"""
+    import torch
+    import torch.distributed as dist
+
+    from . import server as SV
+
+    n = _batch_n(len(servers))
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    if (servers[0].col_rank, servers[0].col_ranks) != (rank, world):
+        raise ValueError(f"rank {rank} of {world} needs column shard {rank} of {world}, the servers are {servers[0].col_rank} of {servers[0].col_ranks}")
+    if bufs is None:
+        bufs = column_batch_buffers(servers, world)
+    _check("answer_batch_column_sharded: cts", bufs["cts"], batch_ct_words(n))
+    _check("answer_batch_column_sharded: gathered_cts", bufs["gathered_cts"], batch_gathered_ct_words(n, world))
+    _check("answer_batch_column_sharded: responses", bufs["responses"], batch_ct_words(n))
+
+    def settle():  # the servers' stream -> the collective (on torch's stream) -> the servers' stream
+        servers[0].sync()
+
+    def landed():
+        torch.cuda.current_stream(bufs["cts"].device).synchronize()
+
+    SV.run_column_batch(servers, bufs["cts"].data_ptr())
+    settle()
+    all_gather_batch_cts(bufs["gathered_cts"], bufs["cts"], group=group)
+    landed()
+    if rank == root:
+        SV.fold_root_batch(servers, bufs["gathered_cts"].data_ptr(), bufs["responses"].data_ptr(), wire_ptr)
+        settle()
+    return bufs
+
+
 # ---- SpiralPack batches on trial-sharded servers (include/spiral_gpu.h fold_trials_batch, pack_gathered_batch) ----------------------------------
 PACK_CT_WORDS = 2 * 2048  # one folded SpiralPack ciphertext (2 x 1 polynomials, raw words): 32 KiB
 

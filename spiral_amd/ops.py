@@ -14,7 +14,7 @@ B = 249561089
 Q = P * B
 
 __all__ = [
-    "N", "P", "B", "Q", "make_params", "get_shape", "has_limb_form", "get_tables", "ntt_forward", "ntt_inverse", "to_ntt", "to_ntt_no_reduce", "from_ntt",
+    "N", "P", "B", "Q", "make_params", "get_shape", "has_limb_form", "column_shard_has_limb_form", "get_tables", "ntt_forward", "ntt_inverse", "to_ntt", "to_ntt_no_reduce", "from_ntt",
     "multiply", "add", "mul_by_const", "automorph", "invert", "gadget_invert", "getRescaled", "multiplyQueryByDatabase", "multiplyQueriesByDatabase", "split_and_crt",
     "foldOneFurtherDimension", "expandImproved", "scalToMat", "regevToGSW", "time_ntt", "time_ntt_digits", "response_wire_bytes", "response_from_wire",
     "query_wire_bytes", "pub_params_wire_bytes", "pack_query_wire_bytes", "pack_pub_params_wire_bytes", "raw_to_wire", "raw_from_wire",
@@ -78,6 +78,16 @@ def has_limb_form(p: Params, j_begin: int = 0, j_end: int = 0) -> bool:
     slot -- or 8, 16 or 32 while option "sweep_narrow" is 1 (set_option; default 0).  A function of the parameters and of that one option as it is
     now: no GPU needed."""
     rc = lib().spiral_gpu_has_limb_form(C.byref(p), j_begin, j_end)
+    if rc < 0:
+        check(rc)
+    return bool(rc)
+
+
+def column_shard_has_limb_form(p: Params, n_ranks: int) -> bool:
+    """has_limb_form for the image of a column shard of n_ranks ranks (Server(..., col_rank=, col_ranks=)): num_per / n_ranks ciphertexts per slot and
+    the whole first dimension, i.e. has_limb_form of the parameters with nu2 - log2 n_ranks; the same rule, the same option "sweep_narrow", no GPU
+    needed.  A rank count that gives no shard (not a power of two, more ranks than columns) has no image: False, and last_error says why"""
+    rc = lib().spiral_gpu_column_shard_has_limb_form(C.byref(p), n_ranks)
     if rc < 0:
         check(rc)
     return bool(rc)

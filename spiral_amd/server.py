@@ -101,6 +101,13 @@ def fold_root_batch(servers, gathered_cts_ptr: int, responses_ptr: int = 0, wire
                                                   C.c_void_p(wire_ptr or None)))
 
 
+def run_column_batch(servers, out_cts_ptr: int):
+    """a column shard's whole local share for up to eight clients (the shard's owner and its lanes): expansion, conversion, ONE pass over the shard's
+    num_per / G columns into the lanes' own accumulators and the first nu2 - log2 G fold rounds -> [lane][6][2048] raw ciphertexts at out_cts_ptr; then
+    one all-gather and fold_root_batch on the root.  See include/spiral_gpu.h spiral_gpu_server_run_column_batch"""
+    check(lib().spiral_gpu_server_run_column_batch(_lanes(servers), len(servers), C.c_void_p(out_cts_ptr or None)))
+
+
 def run_query_batch_instances(servers, instances, responses_ptr: int = 0, finals_ptr: int = 0, wire_ptr: int = 0, pre: bool = True):
     """item queries of up to eight clients (an owner and its lanes, each with its own query) against the same database instances: one sweep per instance
     for all of them; device outputs, client q and instance k at slot q * len(instances) + k: responses / finals 6 x 2048 words, wire
@@ -131,19 +138,32 @@ def answer_batch_instances(servers, instances, queries, wire: bool = False):
 
 
 class Server:
-    def __init__(self, params: Params, device: int = 0, j_begin: int = 0, j_end: int = 0, share_db_of: "Server | None" = None):
+    def __init__(self, params: Params, device: int = 0, j_begin: int = 0, j_end: int = 0, share_db_of: "Server | None" = None, *,
+                 col_rank: "int | None" = None, col_ranks: "int | None" = None):
         """share_db_of: make this server a query lane of that one -- same parameters, device and shard, sweeping ITS database
-        image (no second image is ever allocated)"""
+        image (no second image is ever allocated).  col_rank, col_ranks (both or neither): a column shard -- the ciphertext columns
+        ii = col_rank (mod col_ranks) of the whole first dimension (include/spiral_gpu.h spiral_gpu_server_create_column_shard); a lane of a column
+        shard is one of the same rank"""
         self.params = params
         self.shape = Shape()
         check(lib().spiral_gpu_get_shape(C.byref(params), C.byref(self.shape)))
+        if (col_rank is None) != (col_ranks is None):
+            raise ValueError("a column shard takes both col_rank and col_ranks")
         h = C.c_void_p()
         if share_db_of is not None:
+            if col_rank is not None and (col_rank, col_ranks) != (share_db_of.col_rank, share_db_of.col_ranks):
+                raise ValueError(f"a lane of a server is a column shard of its owner's rank ({share_db_of.col_rank} of {share_db_of.col_ranks}) or none")
+            col_rank, col_ranks = share_db_of.col_rank, share_db_of.col_ranks
             check(lib().spiral_gpu_server_create_lane(share_db_of.h, C.byref(h)))
             self._db_owner = share_db_of  # keeps the owner alive
+        elif col_rank is not None:
+            if j_begin or j_end:
+                raise ValueError("a column shard holds the whole first dimension: no j-range")
+            check(lib().spiral_gpu_server_create_column_shard(C.byref(params), device, col_rank, col_ranks, C.byref(h)))
         else:
             check(lib().spiral_gpu_server_create(C.byref(params), device, j_begin, j_end, C.byref(h)))
         self.h = h
+        self.col_rank, self.col_ranks = col_rank, col_ranks
         self.dim0_shard = (j_end - j_begin) if (j_begin or j_end) else self.shape.dim0
 
     def close(self):
