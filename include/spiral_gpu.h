@@ -861,6 +861,74 @@ enum spiral_gpu_message_form { SPIRAL_GPU_FORM_WIRE = 1, SPIRAL_GPU_FORM_SEEDED 
 int spiral_gpu_server_set_query_batch(spiral_gpu_server *const *servers, uint32_t n, int form, const void *const *msgs, size_t bytes_each);
 int spiral_gpu_server_read_response_wire_batch(spiral_gpu_server *const *servers, uint32_t n, void *out, size_t capacity);
 
+/* ------------------------------------------------------------------------------------------------
+ * Client session: one client's secret key on the device; its public parameters, queries and decoded responses in batches
+ * ------------------------------------------------------------------------------------------------
+ * A session holds one client's secret key -- sr and the rows of Sp, 2 for base Spiral (out_n = 0) and out_n for SpiralPack, as key_store_create
+ * selects the path -- on `device`.  It generates that client's public parameters and batches of its queries there, in the forms the server ingests
+ * (reference NTT layout, 7-byte wire form, seeded form; compressed and direct-upload queries, SpiralPack and SpiralStreamPack), and decodes batches
+ * of responses: check_final's client half (src/spiral.cpp:1451-1491, src/testing.cpp:1086-1122) for n responses in ONE launch, one workgroup per
+ * output polynomial, the products Sp_r * row 0 as exact 64-bit negacyclic convolutions instead of the host client's schoolbook product mod q' on
+ * one thread.  The values are those of the command line's host client (cli/client.cpp) with the randomness below.
+ *
+ * Randomness (the one definition: spiral_amd/csrc/client_device.h).  The session is created from a 32-byte client seed K, and everything it draws is
+ * a function of K and counters through the ChaCha20 block function (RFC 8439 section 2.3).  Noise table: with C_i = sum_{j=-64}^{-64+i}
+ * exp(-pi j^2 / 6.4^2), the 64-bit thresholds T[i] = floor(2^64 C_i / C_128), i < 128 (a quotient that rounds to 1 gives 2^64 - 1), which
+ * client_noise_table returns (plain host code, no device); a 64-bit draw u gives the sample v = -64 + #{ i : T[i] <= u } in [-64, 64], raw value
+ * v mod Q.  Noise polynomial i under a noise key N and a domain tag d: coefficient z takes u = w[2 (z & 7)] + w[2 (z & 7) + 1] 2^32 of the block
+ * with key N, nonce LE32(d) || LE64(i) and block counter z >> 3.  The secret key is drawn under K itself with domain tag 16: polynomial 0 is sr,
+ * polynomials 1.. are the rows of Sp.  nonoise = 1: every sample is 0, the secret included (the command line's --nonoise).
+ * Message n -- the public parameters are message 0, queries are messages 1, 2, ... from a counter held in the session -- has the PUBLIC row-0 seed =
+ * the first 32 bytes of the block with key K, nonce LE32(17) || LE64(n), counter 0: it goes into the seeded message and expands through the seeded
+ * form's domains 1 to 4; and the SECRET noise key N_n = the first 32 bytes of the block with nonce LE32(18) || LE64(n), a derivation of its own under
+ * K, so the noise is never derivable from the public seed.  The message's noise polynomials are drawn under N_n with domain tag 19 and numbered in
+ * the order of the polynomials the seeded form transmits: matrix by matrix, rows 1.., column by column.
+ * K IS THE CLIENT'S SECRET: whoever holds it holds the key.  Two sessions from one K hold the same key and emit the same messages.
+ * A MESSAGE NUMBER MUST NEVER BE USED FOR TWO DIFFERENT QUERIES: two queries under one number share their row 0 and their noise, and their
+ * difference is the difference of their plaintexts.  A session restored from K (and set_secret) must set_counter past every number it has used, as a
+ * seeded message's seed must be fresh for every query.  set_counter(0) is refused: message 0 is the public parameters.
+ *
+ * One content, three forms.  The three forms of one message hold the same matrices: row 0 of every matrix is the expansion of the message seed
+ * (spiral_gpu_seed_expand) in every form, rows 1.. in the NTT form are the transforms of the 7-byte values, so a server that ingests any of the three
+ * ends up in the same state.  Public parameters are always message 0, whichever form and however often they are asked for; a query's form is one
+ * argument of the one call, which consumes one message number per query.
+ *
+ * pub_params: the reference NTT layout in set_pub_params' argument order and shapes -- base: W_exp_left, W_exp_right, W, V; SpiralPack: W_exp_left,
+ * W_exp_right, V, v_W -- a NULL pointer skips that matrix.  pub_params_msg: form SPIRAL_GPU_FORM_WIRE or _SEEDED, the sizes of
+ * spiral_gpu_(pack_)pub_params_wire_bytes / _seeded_bytes; a smaller capacity is refused.
+ * queries: n queries for the items idx[0 .. n), message numbers counter .. counter + n - 1, query b at out + b * bytes_each; form
+ * SPIRAL_GPU_FORM_NTT (set_query's layout, n_query_cts x 2 x 2 x 2048 words), _WIRE or _SEEDED (spiral_gpu_(pack_)query_wire_bytes / _seeded_bytes).
+ * A wrong bytes_each or an index >= 2^(nu1 + nu2) is refused before anything is written, and the counter does not move.  All n queries share one
+ * launch sequence: the noise of all of them, its transforms, one table-driven sample launch, the lift and the 7-byte encoding on the device, so only
+ * message bytes cross to the host.
+ *
+ * create: fails, with *out = NULL, for parameters get_shape / pack_get_shape refuse, for q' >= 2^31 (the decode keeps row 0 in 32-bit words) and
+ * without a device.  get_secret / set_secret: sr [2048] and Sp [rows][2048] as raw values mod Q; get_secret skips a NULL pointer; set_secret
+ * refuses, before anything is written, a coefficient outside [-64, 64] mod Q -- the exactness of the decode rests on |Sp| <= 64: every sum stays
+ * below 2048 * 64 * 2^31 < 2^48.
+ *
+ * decode: `responses` holds n in 1 .. 65535 responses, in pageable host memory, in one of two forms --
+ *   SPIRAL_GPU_RESPONSE_RAW   the switched response [(rows + 1)][cols][2048] words each, as spiral_gpu_server_read(SPIRAL_GPU_BUF_RESPONSE) and
+ *                             the answer calls return it (row 0 mod q', the other rows mod 4 p_db);
+ *   SPIRAL_GPU_RESPONSE_WIRE  the bit-packed response of read_response_wire(_batch), spiral_gpu_response_wire_bytes(p, cols) bytes apart (unpacked
+ *                             by the same launch);
+ * plaintexts: [n][2 x 2 or out_n x out_n][2048] coefficients in [0, p_db), bit for bit what the reference's check_final recovers.  One copy up, one
+ * launch, one copy down on the session's own stream; returns synchronised.  Every argument is checked before anything is copied. */
+typedef struct spiral_gpu_client spiral_gpu_client;
+enum spiral_gpu_response_form { SPIRAL_GPU_RESPONSE_RAW = 0, SPIRAL_GPU_RESPONSE_WIRE = 1 };
+#define SPIRAL_GPU_FORM_NTT 0 /* beside spiral_gpu_message_form: reference NTT-form polynomials */
+int spiral_gpu_client_noise_table(uint64_t *out128);
+int spiral_gpu_client_create(const spiral_gpu_params *p, uint32_t out_n, int device, const void *seed32, int nonoise, spiral_gpu_client **out);
+void spiral_gpu_client_destroy(spiral_gpu_client *c);
+int spiral_gpu_client_get_secret(spiral_gpu_client *c, uint64_t *sr, uint64_t *sp);
+int spiral_gpu_client_set_secret(spiral_gpu_client *c, const uint64_t *sr, const uint64_t *sp);
+int spiral_gpu_client_get_counter(spiral_gpu_client *c, uint64_t *n);
+int spiral_gpu_client_set_counter(spiral_gpu_client *c, uint64_t n);
+int spiral_gpu_client_pub_params(spiral_gpu_client *c, uint64_t *w_left, uint64_t *w_right, uint64_t *w_or_v, uint64_t *v_or_vw);
+int spiral_gpu_client_pub_params_msg(spiral_gpu_client *c, int form, void *msg, size_t capacity);
+int spiral_gpu_client_queries(spiral_gpu_client *c, const uint64_t *idx, uint32_t n, int form, void *out, size_t bytes_each);
+int spiral_gpu_client_decode(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t *plaintexts);
+
 #ifdef __cplusplus
 }
 #endif

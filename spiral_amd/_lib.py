@@ -242,6 +242,17 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_bind_keys": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]),
     "spiral_gpu_server_set_query_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.c_size_t]),
     "spiral_gpu_server_read_response_wire_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_client_noise_table": (C.c_int, [U64P]),
+    "spiral_gpu_client_create": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "spiral_gpu_client_destroy": (None, [C.c_void_p]),
+    "spiral_gpu_client_get_secret": (C.c_int, [C.c_void_p, U64P, U64P]),
+    "spiral_gpu_client_set_secret": (C.c_int, [C.c_void_p, U64P, U64P]),
+    "spiral_gpu_client_get_counter": (C.c_int, [C.c_void_p, U64P]),
+    "spiral_gpu_client_set_counter": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "spiral_gpu_client_pub_params": (C.c_int, [C.c_void_p, U64P, U64P, U64P, U64P]),
+    "spiral_gpu_client_pub_params_msg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_client_queries": (C.c_int, [C.c_void_p, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_client_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P]),
 }
 
 

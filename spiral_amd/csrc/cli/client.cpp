@@ -85,6 +85,51 @@ uint64_t splitmix64(uint64_t x) {
 }
 }  // namespace
 
+std::shared_ptr<spiral_gpu_client> open_session(const spiral_gpu_params& p, uint32_t out_n, uint64_t seed, bool nonoise) {
+    std::mt19937_64 g(seed);
+    uint8_t k[32];
+    for (int i = 0; i < 4; i++) {
+        const uint64_t x = g();
+        for (int b = 0; b < 8; b++) k[8 * i + b] = (uint8_t)(x >> (8 * b));
+    }
+    spiral_gpu_client* c = nullptr;
+    ok(spiral_gpu_client_create(&p, out_n, 0, k, nonoise ? 1 : 0, &c), "client_create");
+    return std::shared_ptr<spiral_gpu_client>(c, spiral_gpu_client_destroy);
+}
+
+namespace {
+// the session's half of gen_pub_params / query / decode, shared by both clients
+void session_pub_params(spiral_gpu_client* c, int form, size_t msg_bytes, Poly* const parts[4], const size_t polys[4], std::vector<uint8_t>& msg) {
+    if (form == SPIRAL_GPU_FORM_NTT) {
+        uint64_t* out[4];
+        for (int i = 0; i < 4; i++) {
+            parts[i]->assign(polys[i] ? polys[i] * 2 * N : 1, 0);
+            out[i] = polys[i] ? parts[i]->data() : nullptr;
+        }
+        ok(spiral_gpu_client_pub_params(c, out[0], out[1], out[2], out[3]), "client_pub_params");
+    } else {
+        msg.resize(msg_bytes);
+        ok(spiral_gpu_client_pub_params_msg(c, form, msg.data(), msg.size()), "client_pub_params_msg");
+    }
+}
+Query session_query(spiral_gpu_client* c, int form, uint64_t idx, size_t n_cts, size_t msg_bytes) {
+    Query q;
+    if (form == SPIRAL_GPU_FORM_NTT) {
+        q.cts.resize(n_cts * 4 * N);
+        ok(spiral_gpu_client_queries(c, &idx, 1, form, q.cts.data(), q.cts.size() * sizeof(uint64_t)), "client_queries");
+    } else {
+        q.msg.resize(msg_bytes);
+        ok(spiral_gpu_client_queries(c, &idx, 1, form, q.msg.data(), q.msg.size()), "client_queries");
+    }
+    return q;
+}
+Poly session_decode(spiral_gpu_client* c, const uint64_t* resp, size_t out_polys) {
+    Poly out(out_polys * N);
+    ok(spiral_gpu_client_decode(c, resp, 1, SPIRAL_GPU_RESPONSE_RAW, out.data()), "client_decode");
+    return out;
+}
+}  // namespace
+
 void Row0::begin(std::mt19937_64& rng, uint32_t d) {
     for (int i = 0; i < 4; i++) {
         const uint64_t x = rng();
@@ -105,7 +150,7 @@ Poly db_item(uint64_t seed, uint64_t item, uint64_t p_db) {
     return pt;
 }
 
-Client::Client(const spiral_gpu_params& params, uint64_t seed, bool nonoise_) : p(params), nonoise(nonoise_), rng(seed) {
+Client::Client(const spiral_gpu_params& params, uint64_t seed, bool nonoise_) : p(params), nonoise(nonoise_), rng(seed), seed0(seed) {
     ok(spiral_gpu_get_shape(&p, &s), "get_shape");
     double acc = 0;  // discrete Gaussian of width 6.4 over [-64, 64] (src/core.cpp:182-207)
     for (int i = -64; i <= 64; i++) {
@@ -133,6 +178,10 @@ Poly Client::uniform_polys(size_t n) {
 }
 
 void Client::keygen() {  // src/client.cpp:21-46
+    if (form >= 0) {
+        session = open_session(p, 0, seed0, nonoise);
+        return;
+    }
     sr = noise_polys(1);
     sp = noise_polys(2);
 }
@@ -198,6 +247,14 @@ void Client::gen_pub_params() {
     const uint32_t tc = p.t_conv;
     offline_bytes = 0;
     auto account = [&](size_t rows, size_t cols, size_t count) { offline_bytes += (uint64_t)count * rows * cols * N * 56 / 8; };  // add_pub_param :199
+    if (session) {
+        account(2, p.t_exp_right, s.n_right), account(2, p.t_exp, s.n_left), account(3, 2 * tc, p.direct_upload ? 1 : 2);
+        Poly* const parts[4] = {&w_left, &w_right, &w, &v};
+        const size_t polys[4] = {(size_t)s.n_left * 2 * p.t_exp, (size_t)s.n_right * 2 * p.t_exp_right, (size_t)6 * tc, (size_t)6 * tc};
+        session_pub_params(session.get(), form, form == SPIRAL_GPU_FORM_SEEDED ? spiral_gpu_pub_params_seeded_bytes(&p) : spiral_gpu_pub_params_wire_bytes(&p), parts,
+                           polys, pp_message);
+        return;
+    }
     // --seeded: row 0 in message order W_exp_left, W_exp_right, W, V
     const uint64_t k_right = (uint64_t)s.n_left * p.t_exp, k_w = k_right + (uint64_t)s.n_right * p.t_exp_right;
     if (seeded) row0.begin(rng, 2);
@@ -251,6 +308,8 @@ Poly Client::encrypt_simple_regev(const Poly& sigma_raw) {  // src/client.cpp:17
 
 // --seeded: ciphertext c of the query has row-0 polynomial k = c under a fresh seed
 Query Client::query(uint64_t idx_target) {
+    if (session)
+        return session_query(session.get(), form, idx_target, s.n_query_cts, form == SPIRAL_GPU_FORM_SEEDED ? spiral_gpu_query_seeded_bytes(&p) : spiral_gpu_query_wire_bytes(&p));
     if (seeded) row0.begin(rng, 1);
     Query q{query_cts(idx_target), {}};
     std::copy(row0.seed, row0.seed + 32, q.seed.begin());
@@ -307,6 +366,7 @@ Poly Client::query_cts(uint64_t idx_target) {
 
 // check_final's client half (src/spiral.cpp:1451-1491)
 Poly Client::decode(const uint64_t* resp) const {
+    if (session) return session_decode(session.get(), resp, 4);
     const uint64_t qp = s.qprime, p_db = p.p_db, q1 = 4 * p_db;
     Poly spq(2 * N), out(4 * N), prod(N);
     for (size_t i = 0; i < 2 * (size_t)N; i++) {  // to_ntt_qprime's centring (src/util.cpp:218-223)
@@ -368,7 +428,7 @@ Poly pack_db_item(uint64_t seed, uint64_t item, uint64_t total_n, uint32_t out_n
 }
 
 PackClient::PackClient(const spiral_gpu_params& params, uint32_t out_n_, uint64_t seed, bool nonoise_)
-    : p(params), out_n(out_n_), nonoise(nonoise_), rng(seed) {
+    : p(params), out_n(out_n_), nonoise(nonoise_), rng(seed), seed0(seed) {
     ok(spiral_gpu_pack_get_shape(&p, out_n, &s), "pack_get_shape");
     double acc = 0;
     for (int i = -64; i <= 64; i++) {
@@ -394,6 +454,10 @@ Poly PackClient::uniform_polys(size_t n) {
     return a;
 }
 void PackClient::keygen() {  // keygen(S, Sp, sr, out_n), src/testing.cpp:907-910
+    if (form >= 0) {
+        session = open_session(p, out_n, seed0, nonoise);
+        return;
+    }
     sr = noise_polys(1);
     sp = noise_polys(out_n);
 }
@@ -434,6 +498,17 @@ void PackClient::gen_pub_params() {
     const uint32_t tc = p.t_conv, rows = out_n + 1;
     offline_bytes = 0;
     auto account = [&](size_t r, size_t c, size_t count) { offline_bytes += (uint64_t)count * r * c * N * 56 / 8; };
+    if (session) {
+        account(rows, tc, out_n);
+        const size_t ex = p.direct_upload ? 0 : 1;
+        if (ex) account(2, p.t_exp, s.n_left), account(2, p.t_exp_right, s.n_right), account(2, 2 * tc, 1);
+        Poly* const parts[4] = {&w_left, &w_right, &v, &v_w};
+        const size_t polys[4] = {ex * s.n_left * 2 * p.t_exp, ex * s.n_right * 2 * p.t_exp_right, ex * 4 * tc, (size_t)out_n * rows * tc};
+        session_pub_params(session.get(), form,
+                           form == SPIRAL_GPU_FORM_SEEDED ? spiral_gpu_pack_pub_params_seeded_bytes(&p, out_n) : spiral_gpu_pack_pub_params_wire_bytes(&p, out_n), parts,
+                           polys, pp_message);
+        return;
+    }
     Poly s0_ntt = to_ntt(sr), sp_ntt = to_ntt(sp);
     Poly s0g = mul_by_const(s0_ntt, to_ntt(build_gadget(1, tc)));  // 1 x t_conv
     // --seeded: row 0 in message order W_exp_left, W_exp_right, V (expansion only), v_W
@@ -487,6 +562,9 @@ void PackClient::gen_pub_params() {
     row0.on = false;
 }
 Query PackClient::query(uint64_t idx_target) {
+    if (session)
+        return session_query(session.get(), form, idx_target, s.n_query_cts,
+                             form == SPIRAL_GPU_FORM_SEEDED ? spiral_gpu_pack_query_seeded_bytes(&p, out_n) : spiral_gpu_pack_query_wire_bytes(&p, out_n));
     if (seeded) row0.begin(rng, 3);
     Query q{query_cts(idx_target), {}};
     std::copy(row0.seed, row0.seed + 32, q.seed.begin());
@@ -532,6 +610,7 @@ Poly PackClient::query_cts(uint64_t idx_target) {
     return encrypt_simple_regev(sigma);
 }
 Poly PackClient::decode(const uint64_t* resp) const {  // src/testing.cpp:1086-1122
+    if (session) return session_decode(session.get(), resp, (size_t)out_n * out_n);
     const uint64_t qp = s.qprime, p_db = p.p_db, q1 = 4 * p_db;
     Poly spq((size_t)out_n * N), out((size_t)out_n * out_n * N), prod(N);
     for (size_t i = 0; i < spq.size(); i++) {

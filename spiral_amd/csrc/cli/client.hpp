@@ -6,6 +6,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <memory>
 #include <random>
 #include <vector>
 
@@ -32,7 +33,14 @@ struct Row0 {
 struct Query {
     Poly cts;
     std::array<uint8_t, 32> seed{};
+    std::vector<uint8_t> msg;  // --device-client with a message form: the query as the session emitted it (cts stays empty)
 };
+
+// --device-client: keys, queries and decoding go through a client session of the library (include/spiral_gpu.h spiral_gpu_client_*) instead of the
+// host code below.  `form` selects it, before keygen(): -1 the host client (the default), else the form the session emits its messages in --
+// SPIRAL_GPU_FORM_NTT (the public parameters land in the NTT-form members, a query in Query::cts), SPIRAL_GPU_FORM_WIRE or _SEEDED (pp_message,
+// Query::msg).  The session's 32-byte seed is drawn from mt19937_64(seed).
+std::shared_ptr<spiral_gpu_client> open_session(const spiral_gpu_params& p, uint32_t out_n, uint64_t seed, bool nonoise);
 
 struct Client {
     spiral_gpu_params p;
@@ -47,6 +55,10 @@ struct Client {
     bool seeded = false;                       // --seeded: the messages' row 0 from seeds
     Row0 row0;                                 // (while a message is generated)
     uint8_t pp_seed[32] = {};                  // the seed of the public parameters
+    int form = -1;                             // --device-client (above)
+    uint64_t seed0 = 0;
+    std::shared_ptr<spiral_gpu_client> session;
+    std::vector<uint8_t> pp_message;
 
     Client(const spiral_gpu_params& params, uint64_t seed, bool nonoise_);
     void keygen();
@@ -80,6 +92,10 @@ struct PackClient {
     bool seeded = false;
     Row0 row0;
     uint8_t pp_seed[32] = {};
+    int form = -1;  // --device-client (above)
+    uint64_t seed0 = 0;
+    std::shared_ptr<spiral_gpu_client> session;
+    std::vector<uint8_t> pp_message;
 
     PackClient(const spiral_gpu_params& params, uint32_t out_n_, uint64_t seed, bool nonoise_);
     void keygen();

@@ -2,7 +2,7 @@
 // 209-265), with the server-answer path running on an MI355X through libspiral_gpu.so.
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
-//            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch]
+//            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch] [--device-client]
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -57,6 +57,10 @@ static uint64_t g_wire_offline = 0, g_wire_online = 0;  // bytes the first clien
 // --seeded (implies --wire-input): the seeded form instead (include/spiral_gpu.h spiral_gpu_query_seeded_bytes): each message is the client's seed
 // followed by the wire form of its matrices without their row 0, which the client took from spiral_gpu_seed_expand (client.cpp Row0)
 static bool g_seeded = false;
+// --device-client: every client of the run is a client session of the library (client.hpp): its keys, its queries and its decoding run on the GPU,
+// in the form the other flags choose for the messages
+static bool g_device_client = false;
+static int client_form() { return !g_device_client ? -1 : g_seeded ? SPIRAL_GPU_FORM_SEEDED : g_wire ? SPIRAL_GPU_FORM_WIRE : SPIRAL_GPU_FORM_NTT; }
 // A message is up to four parts, each `count` matrices of [rows][cols] NTT-form polynomials back to back
 struct Part {
     const Poly* ntt;
@@ -79,12 +83,17 @@ static std::vector<uint8_t> message_of(std::initializer_list<Part> parts, const 
     return w;
 }
 // what a client sends: a query (with the seed its row 0 came from) and its public parameters.  SpiralPack on a direct-upload geometry sends v_W alone
-static std::vector<uint8_t> query_msg(const Query& q) { return message_of({{&q.cts, q.cts.size() / (4 * N), 2, 1}}, g_seeded ? q.seed.data() : nullptr); }
+static std::vector<uint8_t> query_msg(const Query& q) {
+    if (!q.msg.empty()) return q.msg;  // (--device-client: the session emitted the message)
+    return message_of({{&q.cts, q.cts.size() / (4 * N), 2, 1}}, g_seeded ? q.seed.data() : nullptr);
+}
 static std::vector<uint8_t> pp_msg(const spiral_gpu_params& p, const spiral_gpu_shape& s, const Client& c) {
+    if (!c.pp_message.empty()) return c.pp_message;
     return message_of({{&c.w_left, s.n_left, 2, p.t_exp}, {&c.w_right, s.n_right, 2, p.t_exp_right}, {&c.w, 1, 3, 2 * p.t_conv}, {&c.v, 1, 3, 2 * p.t_conv}},
                       g_seeded ? c.pp_seed : nullptr);
 }
 static std::vector<uint8_t> pack_pp_msg(const spiral_gpu_params& p, const spiral_gpu_pack_shape& s, uint32_t out_n, const PackClient& c) {
+    if (!c.pp_message.empty()) return c.pp_message;
     const size_t ex = p.direct_upload ? 0 : 1;
     return message_of({{&c.w_left, ex * s.n_left, 2, p.t_exp}, {&c.w_right, ex * s.n_right, 2, p.t_exp_right}, {&c.v, ex, 2, 2 * p.t_conv},
                        {&c.v_w, out_n, out_n + 1, p.t_conv}},
@@ -128,6 +137,7 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     GPU_OK(spiral_gpu_pack_server_gen_db(srv, db_seed));
     PackClient cl(p, out_n, seed, nonoise);
     cl.seeded = g_seeded;
+    cl.form = client_form();
     uint64_t t0 = now_us();
     cl.keygen();
     cl.gen_pub_params();
@@ -264,6 +274,7 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
             }
             clients.emplace_back(p, out_n, seed + 1 + b, nonoise);
             clients[b].seeded = g_seeded;
+            clients[b].form = client_form();
             clients[b].keygen();
             clients[b].gen_pub_params();
             idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);
@@ -358,6 +369,8 @@ int main(int argc, char** argv) {
         // --batch B --query-batch (not a flag of the reference): after the batch, every client draws a fresh query; all of them go in through ONE
         // spiral_gpu_server_set_query_batch call -- in the wire form, or with --seeded in the seeded form -- and all responses come back through ONE
         // spiral_gpu_server_read_response_wire_batch; every client is decoded and checked.  With --key-store the lanes' keys are bound from the store first
+        // --device-client (not a flag of the reference): keys, queries and decoding through client sessions on the GPU, one per client of a --batch
+        if (!strcmp(argv[i], "--device-client")) { cout << "Using client sessions on the device for keys, queries and decoding" << endl; g_device_client = true; }
         if (!strcmp(argv[i], "--query-batch")) { cout << "Taking the batch's queries in one call and its responses in one read" << endl; query_batch = true; }
         // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
         // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
@@ -432,6 +445,7 @@ int main(int argc, char** argv) {
     double time_key_gen = 0, time_query_gen = 0, time_decoding = 0;
     Client cl(p, seed, nonoise);
     cl.seeded = g_seeded;
+    cl.form = client_form();
     uint64_t t0 = now_us();
     cl.keygen();
     cl.gen_pub_params();
@@ -505,6 +519,7 @@ int main(int argc, char** argv) {
             }
             clients.emplace_back(p, seed + 1 + b, nonoise);
             clients[b].seeded = g_seeded;
+            clients[b].form = client_form();
             clients[b].keygen();
             clients[b].gen_pub_params();
             idxs.push_back((idx_target + 1 + 7919ull * b) % total_n);

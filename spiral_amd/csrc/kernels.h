@@ -676,4 +676,51 @@ struct DbExportParams {
 };
 void launch_db_export(const DeviceTables& t, const DbExportParams& p, hipStream_t s);
 
+// ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
+// noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]
+// (device memory, 8 words per key) and domain tag `domain`.  raw[b][j][2048]: the raw values mod Q, plus addend[b][j][2048] (mod Q) where addend !=
+// null -- a compressed query's e + sigma; centred (may be null): the samples themselves as 8-bit values.  table: the 128 thresholds on the device.
+// nonoise: every sample is 0
+void launch_client_noise(const uint32_t* keys, uint32_t domain, uint64_t first, const uint64_t* table, uint64_t* raw, int8_t* centred, const uint64_t* addend,
+                         uint32_t per_msg, uint32_t n_msgs, bool nonoise, hipStream_t s);
+// One column of a message's matrix: row 0 = row-0 polynomial k of the message's seed (seed_device.h), a = -row 0, and for the secret rows r = 1 ..
+// rows - 1:  b_r = a S + e + c M  pointwise in PK form, with S = secret-table polynomial s_first + (r - 1), e = transformed noise polynomial noise +
+// (r - 1) noise_stride of the message, and -- on row m_row alone, or on every row for m_row = 0, on none for kClientNoMessage -- the constant c (its
+// residues c_p, c_b) times secret-table polynomial m_idx + (r - 1) m_stride.  Row r of the column goes to polynomial dst + r dst_stride of the message.
+constexpr uint32_t kClientNoMessage = 0xFFFFFFFFu;
+struct ClientColumn {
+    uint32_t k, dst, dst_stride, rows;
+    uint32_t s_first, noise, noise_stride;
+    uint32_t m_row, m_idx, m_stride;
+    uint32_t c_p, c_b;
+};
+struct ClientSampleParams {
+    const uint32_t* seeds;        // [n_msgs][8]: the messages' public seeds
+    const ClientColumn* columns;  // [n_msgs][n_cols]
+    const uint64_t* table;        // the session's secret table, PK polynomials
+    const uint64_t* noise;        // [n_msgs][noise_polys][2048] PK
+    uint64_t* out;                // [n_msgs][msg_polys][2048] PK
+    uint32_t domain, n_cols, noise_polys, msg_polys;
+};
+void launch_client_sample(const ClientSampleParams& p, uint32_t n_msgs, hipStream_t s);
+// out = a * b pointwise, PK polynomials
+void launch_client_mul(const uint64_t* a, const uint64_t* b, uint64_t* out, uint32_t npolys, hipStream_t s);
+// raw coefficients (below Q) -> their 7-byte wire form, kWirePolyBytes per polynomial, densely
+void launch_client_wire_encode(const uint64_t* raw, uint8_t* wire, uint32_t npolys, hipStream_t s);
+// check_final's client half (src/spiral.cpp:1451-1491, src/testing.cpp:1086-1122) for n responses in ONE launch: one workgroup per output polynomial
+// (response, r, col) = round((Sp_r * row 0 [col] mod q') 4p + row (1 + r)[col] q', / 4 q') mod p_db with the reference's centring and rounding.
+// resp: n switched responses [(rows + 1)][cols][2048] words, or (wire) their bit-packed forms wire_words words apart (row 0 at w0 bits, the rest at
+// w1), followed by one word of padding; sp: the centred rows of Sp, [rows][2048]; out: [n][rows][cols][2048] coefficients in [0, p_db).
+// Exact for q' < 2^31 and |secret| <= 64: the 64-bit sums stay below 2048 * 64 * 2^31.
+struct ClientDecodeParams {
+    const int8_t* sp;
+    const uint64_t* resp;
+    uint64_t* out;
+    uint32_t rows, cols;
+    uint32_t wire, w0, w1;
+    uint64_t wire_words;
+    uint64_t qprime, p_db;
+};
+void launch_client_decode(const ClientDecodeParams& p, uint32_t n, hipStream_t s);
+
 }  // namespace spiral

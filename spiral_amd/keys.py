@@ -67,6 +67,10 @@ class KeyStore:
         w = wire_bytes(msg)
         check(lib().spiral_gpu_key_store_put_seeded(self.h, slot, w.ctypes.data_as(C.c_void_p), w.size))
 
+    def put_client(self, slot: int, client):
+        """the public parameters of a client session (spiral_amd.Client) into a slot, as their seeded message"""
+        self.put_seeded(slot, client.pub_params("seeded"))
+
     def drop(self, slot: int):
         check(lib().spiral_gpu_key_store_drop(self.h, slot))
 
