@@ -913,9 +913,40 @@ int spiral_gpu_server_read_response_wire_batch(spiral_gpu_server *const *servers
  *   SPIRAL_GPU_RESPONSE_WIRE  the bit-packed response of read_response_wire(_batch), spiral_gpu_response_wire_bytes(p, cols) bytes apart (unpacked
  *                             by the same launch);
  * plaintexts: [n][2 x 2 or out_n x out_n][2048] coefficients in [0, p_db), bit for bit what the reference's check_final recovers.  One copy up, one
- * launch, one copy down on the session's own stream; returns synchronised.  Every argument is checked before anything is copied. */
+ * launch, one copy down on the session's own stream; returns synchronised.  Every argument is checked before anything is copied.
+ *
+ * response_noise: the error e a response carries, per coefficient, and a record of it per output polynomial -- the ONE definition every layer and
+ * test uses.  A response has rows + 1 rows and cols columns (3 x 2 for base Spiral, (out_n + 1) x out_n for SpiralPack); an output polynomial is
+ * (response b, r < rows, col), k its coefficient, p = p_db.  `expected` is NULL or [n][rows][cols][2048] plaintext values m in [0, p).
+ *   Switched forms, SPIRAL_GPU_RESPONSE_RAW and _WIRE (decode's inputs).  With decode's quantities -- vf = (Sp_r * row 0 [col])[k] mod q' centred
+ *   (>= q'/2 -> - q'), vr = row (1 + r)[col][k] mod 4p centred (>= 2p -> - 4p), x = vf 4p + vr q', D = 4 q', res0 = the quotient x / D rounded half
+ *   away from zero, before its reduction mod p (decode returns res0 mod p):
+ *     without expected  e = x - D res0: the rounding residue, |e| <= D / 2, its sign at a tie what the rounding leaves (e = -D/2 for x > 0);
+ *     with expected     e = the residue of x - D m modulo p D centred into [-p D / 2, p D / 2): y in [0, p D) maps to y - p D when y >= p D / 2.
+ *   The step is D, the decoding radius D / 2.
+ *   Unswitched form, SPIRAL_GPU_RESPONSE_FINAL.  The input is the ciphertext before the modulus switch, [(rows + 1)][cols][2048] raw values mod Q
+ *   (a word is taken mod Q): what read(SPIRAL_GPU_BUF_FINAL) holds and the answer calls return as their folded ciphertexts; for SpiralPack the
+ *   inverse transform of the packed ciphertext.  v = row (1 + r)[col][k] + (Sp_r * row 0 [col])[k] mod Q (* the negacyclic product), scale_k =
+ *   floor(Q / p) (the reference's values.h:93):
+ *     with expected     e = v - scale_k m mod Q, centred (>= floor(Q / 2) -> - Q);
+ *     without expected  m0 = floor((v + floor(scale_k / 2)) / scale_k) mod p, and e is the same expression with m0 in place of m.
+ *   The step is scale_k.  This is the reference's get_diffs(from_ntt(Z), from_ntt(scaled_pt), Q_i) (src/spiral.cpp:1517-1534).
+ * stats: [n][rows][cols][6] words, per output polynomial over its 2048 coefficients
+ *     word 0     max |e|
+ *     word 1     n_wrong: 0 without expected; with expected the number of coefficients whose plaintext -- what decode returns in the switched
+ *                forms, m0 in the FINAL form -- differs from expected
+ *     words 2, 3 the sum of e, low and high word of a 128-bit two's-complement sum
+ *     words 4, 5 the sum of e^2, low and high word of an unsigned 128-bit sum
+ * errors: [n][rows][cols][2048] values e.  stats or errors may be NULL, not both.  Bounds: |e| <= p D / 2 = 2 p q' < 2^58 in the switched forms
+ * (the call refuses a session with p q' >= 2^57; every published set has p q' < 2^47) and |e| <= Q / 2 < 2^55 in the FINAL form, so |e| < 2^63
+ * and the sum of e^2 is below 2048 * 2^116 = 2^127: nothing saturates.  All of it is integer arithmetic, hence bit-reproducible and independent
+ * of the order of the reduction.  The FINAL form's products are two convolutions of decode's shape, one per 28-bit prime of Q (every sum below
+ * 2048 * 64 * 2^28 < 2^46), recombined mod Q.  n in 1 .. 65535; one copy up (two with expected), one launch on the session's stream, one copy down
+ * per output; returns synchronised.  Every argument is checked before anything is copied or written: a null session, null responses, both
+ * outputs null, an unknown form, n out of range, and an expected value >= p_db, with its position named. */
 typedef struct spiral_gpu_client spiral_gpu_client;
 enum spiral_gpu_response_form { SPIRAL_GPU_RESPONSE_RAW = 0, SPIRAL_GPU_RESPONSE_WIRE = 1 };
+enum { SPIRAL_GPU_RESPONSE_FINAL = 2 }; /* beside spiral_gpu_response_form, for response_noise alone: decode refuses it */
 #define SPIRAL_GPU_FORM_NTT 0 /* beside spiral_gpu_message_form: reference NTT-form polynomials */
 int spiral_gpu_client_noise_table(uint64_t *out128);
 int spiral_gpu_client_create(const spiral_gpu_params *p, uint32_t out_n, int device, const void *seed32, int nonoise, spiral_gpu_client **out);
@@ -928,6 +959,8 @@ int spiral_gpu_client_pub_params(spiral_gpu_client *c, uint64_t *w_left, uint64_
 int spiral_gpu_client_pub_params_msg(spiral_gpu_client *c, int form, void *msg, size_t capacity);
 int spiral_gpu_client_queries(spiral_gpu_client *c, const uint64_t *idx, uint32_t n, int form, void *out, size_t bytes_each);
 int spiral_gpu_client_decode(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t *plaintexts);
+int spiral_gpu_client_response_noise(spiral_gpu_client *c, const void *responses, uint32_t n, int form, const uint64_t *expected, uint64_t *stats,
+                                     int64_t *errors);
 
 #ifdef __cplusplus
 }

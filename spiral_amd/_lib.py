@@ -253,6 +253,7 @@ PROTOTYPES = {
     "spiral_gpu_client_pub_params_msg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_queries": (C.c_int, [C.c_void_p, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P]),
+    "spiral_gpu_client_response_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P, U64P, C.POINTER(C.c_int64)]),
 }
 
 

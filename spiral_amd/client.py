@@ -11,7 +11,10 @@ from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U6
 
 N = 2048
 RESPONSE_RAW, RESPONSE_WIRE = 0, 1  # spiral_gpu_response_form
+RESPONSE_FINAL = 2  # SPIRAL_GPU_RESPONSE_FINAL: response_noise alone
+Q = 268369921 * 249561089
 _FORMS = {"raw": RESPONSE_RAW, "wire": RESPONSE_WIRE}
+_NOISE_FORMS = {"raw": RESPONSE_RAW, "wire": RESPONSE_WIRE, "final": RESPONSE_FINAL}
 _MESSAGE_FORMS = {"ntt": FORM_NTT, "wire": FORM_WIRE, "seeded": FORM_SEEDED}
 
 
@@ -139,3 +142,79 @@ class Client:
         out = np.zeros((n, self.rows, self.cols, N), dtype=np.uint64)
         check(lib().spiral_gpu_client_decode(self.h, buf.ctypes.data_as(C.c_void_p), n, _FORMS[form], out.ctypes.data_as(U64P)))
         return out
+
+    def noise_step(self, form="raw") -> int:
+        """the step of the error's scale (include/spiral_gpu.h, response_noise): D = 4 q' for the switched forms, scale_k = Q // p_db for "final";
+        half of it is the decoding radius"""
+        if form not in _NOISE_FORMS:
+            raise ValueError(f"response form {form!r}: 'raw', 'wire' or 'final'")
+        return Q // int(self.params.p_db) if form == "final" else 4 * int(self.shape.qprime)
+
+    def response_noise(self, responses, form="raw", expected=None, errors=False) -> "ResponseNoise":
+        """the error e of n responses, per output polynomial and (errors=True) per coefficient, from one launch: the definition is
+        include/spiral_gpu.h's.  form "raw" / "wire": decode's inputs; "final": the ciphertexts before the modulus switch,
+        [n][(rows + 1)][cols][2048] raw values mod Q.  expected: None (e is the distance from the nearest plaintext) or the true plaintexts
+        [n][rows][cols][2048] below p_db (e is the distance from them, and n_wrong counts the coefficients that decode to something else)"""
+        step = self.noise_step(form)
+        if form == "wire":
+            buf = wire_bytes(responses)
+            each = self.response_wire_bytes()
+        else:
+            buf = np.ascontiguousarray(responses, dtype=np.uint64)
+            each = (self.rows + 1) * self.cols * N
+        if buf.size == 0 or buf.size % each:
+            raise ValueError(f"{buf.size} {'bytes' if form == 'wire' else 'words'} are no whole number of responses of {each}")
+        n = buf.size // each
+        shape = (n, self.rows, self.cols)
+        exp = None
+        if expected is not None:
+            exp = np.ascontiguousarray(expected, dtype=np.uint64)
+            if exp.size != n * self.rows * self.cols * N:
+                raise ValueError(f"expected holds {exp.size} values, {n} responses take {n * self.rows * self.cols * N}")
+        stats = np.zeros(shape + (6,), dtype=np.uint64)
+        err = np.zeros(shape + (N,), dtype=np.int64) if errors else None
+        check(lib().spiral_gpu_client_response_noise(self.h, buf.ctypes.data_as(C.c_void_p), n, _NOISE_FORMS[form], None if exp is None else exp.ctypes.data_as(U64P),
+                                                     stats.ctypes.data_as(U64P), None if err is None else err.ctypes.data_as(C.POINTER(C.c_int64))))
+        return ResponseNoise(stats, step, err)
+
+
+class ResponseNoise:
+    """the records of Client.response_noise: max_abs and n_wrong, uint64 [n][rows][cols]; sum and sumsq, exact Python ints in object arrays of that
+    shape; step (the decoding radius is step / 2); errors, int64 [n][rows][cols][2048] or None"""
+
+    def __init__(self, stats, step: int, errors=None):
+        stats = np.asarray(stats, dtype=np.uint64)
+        self.stats, self.step, self.errors = stats, int(step), errors
+        self.max_abs, self.n_wrong = stats[..., 0].copy(), stats[..., 1].copy()
+        words = stats.astype(object)
+        s = words[..., 2] + words[..., 3] * (1 << 64)
+        self.sum = np.where(words[..., 3] >= (1 << 63), s - (1 << 128), s)  # 128-bit two's complement
+        self.sumsq = words[..., 4] + words[..., 5] * (1 << 64)
+        self.count = N  # coefficients per record
+
+    def variance(self, pooled: bool = False):
+        """E[e^2] - E[e]^2 from the exact sums: per polynomial (a float array [n][rows][cols]), or pooled=True over all of them (one float)"""
+        from fractions import Fraction
+
+        def var(s, sq, cnt):
+            return float(Fraction(int(sq), cnt) - Fraction(int(s), cnt) ** 2)
+
+        if pooled:
+            return var(self.sum.sum(), self.sumsq.sum(), self.count * self.sum.size)
+        out = np.zeros(self.sum.shape, dtype=np.float64)
+        for i in np.ndindex(*self.sum.shape):
+            out[i] = var(self.sum[i], self.sumsq[i], self.count)
+        return out
+
+    def budget_bits(self) -> float:
+        """log2(step / 2) - log2(max(max_abs, 1)): the bits between the largest error seen and the decoding radius (negative: it decoded wrongly)"""
+        import math
+
+        return math.log2(self.step / 2) - math.log2(max(int(self.max_abs.max()), 1))
+
+    def width2(self, pooled: bool = True):
+        """2 pi variance / step^2: the squared Gaussian width parameter of the error in steps -- the unit of the noise model (scheme.py), whose
+        sigma = 6.4 is a width parameter (csrc/client_device.h's table)"""
+        import math
+
+        return 2 * math.pi * self.variance(pooled) / float(self.step) ** 2

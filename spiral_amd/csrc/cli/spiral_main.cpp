@@ -2,7 +2,7 @@
 // 209-265), with the server-answer path running on an MI355X through libspiral_gpu.so.
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
-//            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch] [--device-client]
+//            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch] [--device-client [--output-err F]]
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -116,6 +116,44 @@ static void print_wire_bytes() {
         cout << "   Wire input, uploaded offline / online (b): " << g_wire_offline << " / " << g_wire_online << endl;
     }
 }
+// --output-err F with --device-client on a one-query run (src/spiral.cpp:1517-1534): the session measures the error the answer carries against the
+// true item (include/spiral_gpu.h, spiral_gpu_client_response_noise) -- the variance of the unswitched ciphertext's errors, printed under the
+// reference's wording, the bits between the switched response's largest error and its decoding radius, and the unswitched errors appended to F,
+// space-separated, as output_diffs writes them.  final_ct: [(rows + 1)][rows][2048] raw values mod Q; wire: the response as received
+static std::string g_output_err;
+static void report_noise(spiral_gpu_client* c, const uint64_t* final_ct, const std::vector<uint8_t>& wire, const Poly& corr, size_t rows, uint64_t qprime) {
+    const size_t polys = rows * rows;
+    std::vector<uint64_t> stats(polys * 6);
+    std::vector<int64_t> errors(polys * N);
+    GPU_OK(spiral_gpu_client_response_noise(c, final_ct, 1, SPIRAL_GPU_RESPONSE_FINAL, corr.data(), stats.data(), errors.data()));
+    typedef unsigned __int128 u128;
+    u128 sumsq = 0;
+    __int128 sum = 0;
+    for (size_t i = 0; i < polys; i++) {
+        sum += (__int128)(((u128)stats[6 * i + 3] << 64) | stats[6 * i + 2]);
+        sumsq += ((u128)stats[6 * i + 5] << 64) | stats[6 * i + 4];
+    }
+    const long double count = (long double)(polys * N), mean = (long double)sum / count;
+    const long double var = (long double)sumsq / count - mean * mean;
+    const std::ios::fmtflags flags = cout.flags();
+    const std::streamsize prec = cout.precision();
+    cout << std::fixed << std::setprecision(4) << "variance of diff w/o modswitching: 2^" << (double)std::log2(var) << endl;
+    GPU_OK(spiral_gpu_client_response_noise(c, wire.data(), 1, SPIRAL_GPU_RESPONSE_WIRE, corr.data(), stats.data(), nullptr));
+    uint64_t max_abs = 1;
+    for (size_t i = 0; i < polys; i++) max_abs = std::max(max_abs, stats[6 * i]);
+    const double radius_bits = std::log2(2.0 * (double)qprime);  // step / 2 = 2 q'
+    cout << "noise budget: " << radius_bits - std::log2((double)max_abs) << " of " << radius_bits << " bits" << endl;
+    cout.flags(flags);
+    cout.precision(prec);
+    FILE* f = fopen(g_output_err.c_str(), "a");
+    if (!f) {
+        fprintf(stderr, "spiral: --output-err: cannot open %s\n", g_output_err.c_str());
+        exit(1);
+    }
+    for (int64_t e : errors) fprintf(f, "%lld ", (long long)e);
+    fclose(f);
+}
+
 // device buffers for the resident entry points the wire path drives (the host-buffer ones take NTT-form queries)
 #define HIP_CLI_OK(x)                                                                        \
     do {                                                                                     \
@@ -149,18 +187,20 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     const Query query = cl.query(idx_target);
     const double time_query_gen = (double)(now_us() - t0);
     Poly resp((size_t)(out_n + 1) * out_n * N);
+    Poly packed(g_output_err.empty() ? 0 : (size_t)(out_n + 1) * out_n * 2 * N);  // (--output-err: the packed ciphertext before the switch, NTT form)
+    uint64_t* const packed_out = packed.empty() ? nullptr : packed.data();
     double us[8];
     if (g_wire) {
         const std::vector<uint8_t> pw = pack_pp_msg(p, s, out_n, cl), qw = query_msg(query);
         g_wire_offline = pw.size(), g_wire_online = qw.size();
         GPU_OK(pack_set_pp_msg(srv, pw));
         auto answer = g_seeded ? spiral_gpu_pack_server_answer_seeded : spiral_gpu_pack_server_answer_wire;
-        GPU_OK(answer(srv, qw.data(), qw.size(), resp.data(), nullptr, us));  // warm-up
-        GPU_OK(answer(srv, qw.data(), qw.size(), resp.data(), nullptr, us));
+        GPU_OK(answer(srv, qw.data(), qw.size(), resp.data(), packed_out, us));  // warm-up
+        GPU_OK(answer(srv, qw.data(), qw.size(), resp.data(), packed_out, us));
     } else {
         GPU_OK(spiral_gpu_pack_server_set_pub_params(srv, cl.w_left.data(), cl.w_right.data(), cl.v.data(), cl.v_w.data()));
-        GPU_OK(spiral_gpu_pack_server_answer(srv, query.cts.data(), resp.data(), nullptr, us));  // warm-up
-        GPU_OK(spiral_gpu_pack_server_answer(srv, query.cts.data(), resp.data(), nullptr, us));
+        GPU_OK(spiral_gpu_pack_server_answer(srv, query.cts.data(), resp.data(), packed_out, us));  // warm-up
+        GPU_OK(spiral_gpu_pack_server_answer(srv, query.cts.data(), resp.data(), packed_out, us));
     }
     // the response travels in its wire form (bit-packed on the device, include/spiral_gpu.h); the client unpacks and decodes it
     std::vector<uint8_t> wire(spiral_gpu_response_wire_bytes(&p, out_n));
@@ -214,6 +254,11 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
                 cout << i << ": " << pt[i] << " " << corr[i] << endl;
                 shown++;
             }
+    }
+    if (!g_output_err.empty()) {
+        Poly final_ct((size_t)(out_n + 1) * out_n * N);
+        GPU_OK(spiral_gpu_from_ntt(final_ct.data(), packed.data(), (size_t)(out_n + 1) * out_n));
+        report_noise(cl.session.get(), final_ct.data(), wire, corr, out_n, s.qprime);
     }
     // print_summary_testing (src/testing.cpp:626-733)
     const size_t logp = (size_t)std::ceil(std::log2((double)p.p_db));
@@ -375,9 +420,18 @@ int main(int argc, char** argv) {
         // --batch B --instances F together: B clients -- own keys, own indices -- each fetch an item of F plaintexts in ONE call of
         // spiral_gpu_server_answer_batch_instances; every plaintext of every client is decoded from its wire form and checked
         // --output-err F (src/spiral.cpp:1287-1291) asks the reference to dump its empirical noise statistics (analyze_err.py's
-        // input): those are outside this path.  The flag and its file name are consumed so that a driver's
-        // command line parses the same way, and the file is not written.
-        if (!strcmp(argv[i], "--output-err") && i + 1 < argc) { cout << "--output-err " << argv[++i] << ": noise statistics are not produced by this build (ignored)" << endl; }
+        // input).  Here a client session measures them (report_noise above), so the flag takes --device-client; the host client has no such
+        // path: without --device-client the flag and its file name are consumed so that a driver's command line parses the same way, and the
+        // file is not written.
+        if (!strcmp(argv[i], "--output-err") && i + 1 < argc) g_output_err = argv[++i];
+    }
+    if (!g_output_err.empty() && !g_device_client) {
+        cout << "--output-err " << g_output_err << ": noise statistics are not produced by this build without --device-client (ignored)" << endl;
+        g_output_err.clear();
+    }
+    if (!g_output_err.empty() && (batch || instances || key_store >= 0 || query_batch)) {
+        fprintf(stderr, "spiral: --output-err takes --device-client on a one-query run (not with --batch, --instances, --key-store or --query-batch)\n");
+        return 1;
     }
     const bool item_batch = batch && instances;
     if (item_batch && (batch < 2 || batch > 8 || instances < 2 || instances > 16 || high_rate)) {
@@ -500,6 +554,10 @@ int main(int argc, char** argv) {
     if (show_diff)
         for (size_t i = 0; i < pt.size(); i++)
             if (pt[i] != corr[i]) cout << i << " " << corr[i] << ", " << pt[i] << endl;
+    if (!g_output_err.empty()) {
+        GPU_OK(spiral_gpu_server_read(srv, SPIRAL_GPU_BUF_FINAL, final_ct.data()));
+        report_noise(cl.session.get(), final_ct.data(), wire, corr, 2, s.qprime);
+    }
 
     // ---- --batch B: the same server, B queries of B clients in one launch sequence (include/spiral_gpu.h, spiral_gpu_server_run_query_batch)
     double batch_us = 0;

@@ -16,9 +16,14 @@
 // d = -7 .. 7, and the eight s[256 b + r] feed all 64 products of the thread, so the loop reads 23 LDS words per 64 multiply-adds; a wave's lanes
 // read consecutive words (no bank conflict), the s reads broadcast.  The WIRE form is unpacked by the same launch: a value is the bit field of its
 // position in the stream (primitives.cpp spiral_gpu_response_from_wire).
+//
+// client_response_noise_kernel: the error e of every coefficient of a response and its record per output polynomial (include/spiral_gpu.h,
+// spiral_gpu_client_response_noise).  The decode's workgroup, operands, convolution and rounding as shared device functions; the unswitched form
+// runs the convolution once per 28-bit prime; the record is reduced by wave shuffles and across the four waves through LDS.
 #include "client_device.h"
 #include "common.h"
 #include "kernels.h"
+#include "ntt_device.h"
 
 namespace spiral {
 
@@ -101,30 +106,22 @@ __global__ __launch_bounds__(kClientTpb) void client_wire_encode_kernel(const ui
     for (int w = 0; w < 7; w++) wire[7u * g + w] = (v[w] >> (8 * w)) | (v[w + 1] << (56 - 8 * w));
 }
 
-__global__ __launch_bounds__(kClientTpb) void client_decode_kernel(ClientDecodeParams p) {
-    __shared__ int32_t ext[2 * kN];
-    __shared__ int8_t s8[kN];
-    const uint32_t col = blockIdx.x, r = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
-    // the response's value (row, col, z)
-    auto value = [&](uint32_t row, uint32_t z) -> uint64_t {
-        if (!p.wire) return p.resp[(((size_t)b * (p.rows + 1u) + row) * p.cols + col) * kN + z];
-        const uint64_t* w = p.resp + (size_t)b * p.wire_words;
-        const uint32_t width = row == 0 ? p.w0 : p.w1;
-        const uint64_t idx = row == 0 ? (uint64_t)col * kN + z : ((uint64_t)(row - 1u) * p.cols + col) * kN + z;
-        const uint64_t bit = (row == 0 ? 0ull : (uint64_t)p.cols * kN * p.w0) + idx * width;
-        const uint32_t sh = (uint32_t)(bit & 63u);
-        uint64_t v = w[bit >> 6] >> sh;
-        if (sh + width > 64u) v |= w[(bit >> 6) + 1u] << (64u - sh);
-        return v & ((1ull << width) - 1ull);
-    };
-    for (uint32_t z = t; z < kN; z += kClientTpb) {
-        const int32_t a = (int32_t)(value(0, z) % p.qprime);
-        ext[kN + z] = a;
-        ext[z] = -a;
-        s8[z] = p.sp[(size_t)r * kN + z];
-    }
-    __syncthreads();
-    int64_t acc[8] = {};
+// ---- what the decode and the noise measurement share: a response's values, the LDS operands, the convolution, check_final's rounding --------------
+// the response's value (row, col, z) of response b: a word of the RAW form, or the bit field of its position in the WIRE stream
+__device__ __forceinline__ uint64_t response_value(const ClientDecodeParams& p, uint32_t b, uint32_t col, uint32_t row, uint32_t z) {
+    if (!p.wire) return p.resp[(((size_t)b * (p.rows + 1u) + row) * p.cols + col) * kN + z];
+    const uint64_t* w = p.resp + (size_t)b * p.wire_words;
+    const uint32_t width = row == 0 ? p.w0 : p.w1;
+    const uint64_t idx = row == 0 ? (uint64_t)col * kN + z : ((uint64_t)(row - 1u) * p.cols + col) * kN + z;
+    const uint64_t bit = (row == 0 ? 0ull : (uint64_t)p.cols * kN * p.w0) + idx * width;
+    const uint32_t sh = (uint32_t)(bit & 63u);
+    uint64_t v = w[bit >> 6] >> sh;
+    if (sh + width > 64u) v |= w[(bit >> 6) + 1u] << (64u - sh);
+    return v & ((1ull << width) - 1ull);
+}
+
+// acc[j] = (Sp_r * a)[t + 256 j] from the negacyclic extension of a in ext and the secret row in s8 (the loop of the header comment)
+__device__ __forceinline__ void secret_row_convolve(const int32_t* ext, const int8_t* s8, uint32_t t, int64_t (&acc)[8]) {
     for (uint32_t rr = 0; rr < 256u; rr++) {
         int32_t e[15], sv[8];
 #pragma unroll
@@ -136,20 +133,185 @@ __global__ __launch_bounds__(kClientTpb) void client_decode_kernel(ClientDecodeP
 #pragma unroll
             for (int bb = 0; bb < 8; bb++) acc[j] += (int64_t)sv[bb] * (int64_t)e[j - bb + 7];
     }
-    const int64_t qp = (int64_t)p.qprime, q1 = (int64_t)(4u * p.p_db), pdb = (int64_t)p.p_db, denom = qp * 4;
+}
+
+// check_final's x = vf 4p + vr q' of one coefficient -- vf the product mod q', centred, vr the row 1 + r value mod 4p, centred -- and its quotient by
+// D = 4 q' rounded half away from zero, before the reduction mod p
+__device__ __forceinline__ int64_t switched_round(int64_t acc, uint64_t row_value, int64_t qp, int64_t q1, int64_t& x) {
+    int64_t vf = acc % qp;
+    vf += vf < 0 ? qp : 0;
+    vf -= vf >= qp / 2 ? qp : 0;  // to_ntt_qprime's product, centred
+    int64_t vr = (int64_t)(row_value % (uint64_t)q1);
+    vr -= vr >= q1 / 2 ? q1 : 0;
+    const int64_t denom = qp * 4;
+    x = vf * q1 + vr * qp;
+    return (x + (x >= 0 ? denom / 2 : -(denom / 2))) / denom;  // round half away from zero, truncating division
+}
+
+__global__ __launch_bounds__(kClientTpb) void client_decode_kernel(ClientDecodeParams p) {
+    __shared__ int32_t ext[2 * kN];
+    __shared__ int8_t s8[kN];
+    const uint32_t col = blockIdx.x, r = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+    for (uint32_t z = t; z < kN; z += kClientTpb) {
+        const int32_t a = (int32_t)(response_value(p, b, col, 0, z) % p.qprime);
+        ext[kN + z] = a;
+        ext[z] = -a;
+        s8[z] = p.sp[(size_t)r * kN + z];
+    }
+    __syncthreads();
+    int64_t acc[8] = {};
+    secret_row_convolve(ext, s8, t, acc);
+    const int64_t qp = (int64_t)p.qprime, q1 = (int64_t)(4u * p.p_db), pdb = (int64_t)p.p_db;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const uint32_t k = t + 256u * j;
-        int64_t vf = acc[j] % qp;
-        vf += vf < 0 ? qp : 0;
-        vf -= vf >= qp / 2 ? qp : 0;  // to_ntt_qprime's product, centred
-        int64_t vr = (int64_t)(value(1u + r, k) % (uint64_t)q1);
-        vr -= vr >= q1 / 2 ? q1 : 0;
-        const int64_t x = vf * q1 + vr * qp;
-        int64_t res = (x + (x >= 0 ? denom / 2 : -(denom / 2))) / denom;  // round half away from zero, truncating division
+        int64_t x;
+        int64_t res = switched_round(acc[j], response_value(p, b, col, 1u + r, k), qp, q1, x);
         res %= pdb;
         res += res < 0 ? pdb : 0;
         p.out[(((size_t)b * p.rows + r) * p.cols + col) * kN + k] = (uint64_t)res;
+    }
+}
+
+// ---- response noise (include/spiral_gpu.h, spiral_gpu_client_response_noise: the one definition of e) ------------------------------------------
+// One workgroup per output polynomial, as the decode.  Switched forms: the decode's operands, convolution and rounding, then e from x.  FINAL form:
+// row 0 is a value mod Q of 56 bits, whose sums against the secret do not fit 64 bits; the same convolution runs once per 28-bit prime on the
+// residues of row 0 (every sum below 2048 * 64 * 2^28 < 2^46), and the two residues of the product recombine mod Q through crt_compose_lazy.
+// The record: every thread folds its eight e, a wave reduces by shuffles, the four waves meet in LDS.  128-bit sums are pairs of 64-bit words with
+// an explicit carry.
+__device__ __forceinline__ void add128(uint64_t& lo, uint64_t& hi, uint64_t alo, uint64_t ahi) {
+    lo += alo;
+    hi += ahi + (lo < alo ? 1ull : 0ull);
+}
+__device__ __forceinline__ uint64_t shfl_down64(uint64_t v, uint32_t off) {
+    return pack((uint32_t)__shfl_down((int)lo32(v), off, 64), (uint32_t)__shfl_down((int)hi32(v), off, 64));
+}
+
+template <bool FINAL>
+__global__ __launch_bounds__(kClientTpb) void client_response_noise_kernel(ClientResponseNoiseParams q) {
+    __shared__ int32_t ext[2 * kN];
+    __shared__ int8_t s8[kN];
+    __shared__ uint64_t red[kClientTpb / 64][6];
+    const ClientDecodeParams& p = q.d;
+    const uint32_t col = blockIdx.x, r = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
+    const size_t poly = ((size_t)b * p.rows + r) * p.cols + col;
+    const uint64_t* expected = q.expected ? q.expected + poly * kN : nullptr;
+    const int64_t pdb = (int64_t)p.p_db;
+    int64_t e[8];
+    uint32_t wrong = 0;
+    if constexpr (!FINAL) {
+        for (uint32_t z = t; z < kN; z += kClientTpb) {
+            const int32_t a = (int32_t)(response_value(p, b, col, 0, z) % p.qprime);
+            ext[kN + z] = a;
+            ext[z] = -a;
+            s8[z] = p.sp[(size_t)r * kN + z];
+        }
+        __syncthreads();
+        int64_t acc[8] = {};
+        secret_row_convolve(ext, s8, t, acc);
+        const int64_t qp = (int64_t)p.qprime, q1 = (int64_t)(4u * p.p_db), denom = qp * 4, span = denom * pdb;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t k = t + 256u * j;
+            int64_t x;
+            const int64_t res0 = switched_round(acc[j], response_value(p, b, col, 1u + r, k), qp, q1, x);
+            if (!expected) {
+                e[j] = x - denom * res0;
+            } else {
+                const int64_t m = (int64_t)expected[k];
+                int64_t res = res0 % pdb;
+                res += res < 0 ? pdb : 0;
+                wrong += res != m ? 1u : 0u;
+                int64_t y = (x - denom * m) % span;  // |x| <= p D and D m < p D < 2^62
+                y += y < 0 ? span : 0;
+                y -= y >= span / 2 ? span : 0;
+                e[j] = y;
+            }
+        }
+    } else {
+        uint32_t res_p[8];
+        uint64_t prod[8];
+#pragma unroll 1
+        for (int limb = 0; limb < 2; limb++) {
+            const uint32_t mod = limb == 0 ? kP : kB;
+            if (limb) __syncthreads();  // every wave is done with the first prime's operands
+            for (uint32_t z = t; z < kN; z += kClientTpb) {
+                const int32_t a = (int32_t)(response_value(p, b, col, 0, z) % kQ % mod);
+                ext[kN + z] = a;
+                ext[z] = -a;
+                if (limb == 0) s8[z] = p.sp[(size_t)r * kN + z];
+            }
+            __syncthreads();
+            int64_t acc[8] = {};
+            secret_row_convolve(ext, s8, t, acc);
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                int64_t v = acc[j] % (int64_t)mod;
+                v += v < 0 ? (int64_t)mod : 0;
+                if (limb == 0)
+                    res_p[j] = (uint32_t)v;
+                else
+                    prod[j] = crt_compose_lazy(res_p[j], (uint32_t)v);
+            }
+        }
+        const uint64_t scale = kQ / p.p_db;
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t k = t + 256u * j;
+            uint64_t v = response_value(p, b, col, 1u + r, k) % kQ + prod[j];
+            v -= v >= kQ ? kQ : 0;
+            const uint64_t m0 = (v + scale / 2) / scale % p.p_db;
+            uint64_t m = m0;
+            if (expected) {
+                m = expected[k];
+                wrong += m0 != m ? 1u : 0u;
+            }
+            const uint64_t sm = scale * m;  // below Q: m < p
+            const uint64_t d = v >= sm ? v - sm : v + kQ - sm;
+            e[j] = d >= kQ / 2 ? (int64_t)d - (int64_t)kQ : (int64_t)d;
+        }
+    }
+    if (q.errors) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) q.errors[poly * kN + t + 256u * j] = e[j];
+    }
+    if (!q.stats) return;
+    // the record of include/spiral_gpu.h: max |e|, n_wrong, the sum of e (128-bit two's complement), the sum of e^2 (128-bit unsigned)
+    uint64_t rec[6] = {0, wrong, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint64_t a = (uint64_t)(e[j] < 0 ? -e[j] : e[j]);
+        rec[0] = a > rec[0] ? a : rec[0];
+        add128(rec[2], rec[3], (uint64_t)e[j], e[j] < 0 ? ~0ull : 0ull);
+        add128(rec[4], rec[5], a * a, __umul64hi(a, a));
+    }
+    auto fold = [&](const uint64_t (&o)[6]) {
+        rec[0] = o[0] > rec[0] ? o[0] : rec[0];
+        rec[1] += o[1];
+        add128(rec[2], rec[3], o[2], o[3]);
+        add128(rec[4], rec[5], o[4], o[5]);
+    };
+#pragma unroll
+    for (uint32_t off = 32; off; off >>= 1) {
+        uint64_t o[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) o[i] = shfl_down64(rec[i], off);
+        fold(o);  // (lanes whose partner lies past the wave fold their own value in: only lane 0's result is used)
+    }
+    if ((t & 63u) == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) red[t >> 6][i] = rec[i];
+    }
+    __syncthreads();
+    if (t == 0) {
+        for (uint32_t w = 1; w < kClientTpb / 64; w++) {
+            uint64_t o[6];
+#pragma unroll
+            for (int i = 0; i < 6; i++) o[i] = red[w][i];
+            fold(o);
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) q.stats[poly * 6 + i] = rec[i];
     }
 }
 
@@ -177,6 +339,14 @@ void launch_client_wire_encode(const uint64_t* raw, uint8_t* wire, uint32_t npol
 void launch_client_decode(const ClientDecodeParams& p, uint32_t n, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(client_decode_kernel, dim3(p.cols, p.rows, n), dim3(kClientTpb), 0, s, p);
+}
+
+void launch_client_response_noise(const ClientResponseNoiseParams& p, uint32_t n, hipStream_t s) {
+    if (n == 0) return;
+    if (p.final_form)
+        hipLaunchKernelGGL(client_response_noise_kernel<true>, dim3(p.d.cols, p.d.rows, n), dim3(kClientTpb), 0, s, p);
+    else
+        hipLaunchKernelGGL(client_response_noise_kernel<false>, dim3(p.d.cols, p.d.rows, n), dim3(kClientTpb), 0, s, p);
 }
 
 }  // namespace spiral

@@ -26,6 +26,7 @@ struct spiral_gpu_client {
     DevBuf secret;   // raw values mod Q: sr, then the rows of Sp, [1 + rows][2048]
     DevBuf centred;  // the same samples as 8-bit values, [1 + rows][2048] bytes
     DevBuf in, out;  // decode's staging, grown on demand
+    DevBuf expected; // response_noise's expected plaintexts, grown on demand
     // the message half
     DeviceTables tb;
     uint64_t counter = 1;  // the next query's message number (the public parameters are message 0)
@@ -49,6 +50,7 @@ void client_free(spiral_gpu_client* c) {
     c->centred.release();
     c->in.release();
     c->out.release();
+    c->expected.release();
     for (DevBuf* b : {&c->tab, &c->keys, &c->columns, &c->sigma, &c->noise_raw, &c->noise_pk, &c->msg, &c->lifted, &c->stage}) b->release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -528,6 +530,58 @@ int spiral_gpu_client_decode(spiral_gpu_client* c, const void* responses, uint32
     launch_client_decode(dp, n, c->stream);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(plaintexts, c->out.p, n * out_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int spiral_gpu_client_response_noise(spiral_gpu_client* c, const void* responses, uint32_t n, int form, const uint64_t* expected, uint64_t* stats,
+                                     int64_t* errors) {
+    if (client_on(c, "client_response_noise")) return -1;
+    if (!responses) return fail("client_response_noise: null argument");
+    if (!stats && !errors) return fail("client_response_noise: null argument: stats and errors are both null");
+    if (form != SPIRAL_GPU_RESPONSE_RAW && form != SPIRAL_GPU_RESPONSE_WIRE && form != SPIRAL_GPU_RESPONSE_FINAL)
+        return fail("client_response_noise: unknown response form %d", form);
+    if (n == 0 || n > 65535u) return fail("client_response_noise: %u responses, a call takes 1 .. 65535", n);
+    // the sum of e^2 below 2^127: |e| <= p D / 2 = 2 p q' in the switched forms
+    if ((unsigned __int128)c->qprime * c->p.p_db >= ((unsigned __int128)1 << 57))
+        return fail("client_response_noise: q' = %llu with p_db = %llu is outside the exact range of the 128-bit sums", (unsigned long long)c->qprime,
+                    (unsigned long long)c->p.p_db);
+    const size_t polys = (size_t)n * c->rows * c->cols;
+    if (expected)
+        for (size_t i = 0; i < polys * kN; i++)
+            if (expected[i] >= c->p.p_db) {
+                const size_t poly = i / kN;
+                return fail("client_response_noise: expected value %llu of response %zu, row %zu, column %zu, coefficient %zu is not below p_db = %llu",
+                            (unsigned long long)expected[i], poly / ((size_t)c->rows * c->cols), poly / c->cols % c->rows, poly % c->cols, i % kN,
+                            (unsigned long long)c->p.p_db);
+            }
+    const bool wire = form == SPIRAL_GPU_RESPONSE_WIRE;
+    const size_t wire_each = wire_bytes(&c->p, c->cols);  // a multiple of 256 bytes
+    const size_t in_words = wire ? wire_each / 8 : (size_t)(c->rows + 1) * c->cols * kN;
+    const size_t stats_words = stats ? polys * 6 : 0, err_words = errors ? polys * kN : 0;
+    if (grow(c->in, n * in_words + 1) || grow(c->out, stats_words + err_words) || (expected && grow(c->expected, polys * kN))) return -1;
+    HIP_OK(hipMemcpyAsync(c->in.p, responses, n * in_words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->in.p + n * in_words, 0, sizeof(uint64_t), c->stream));  // (the word a wire field's window may reach into)
+    if (expected) HIP_OK(hipMemcpyAsync(c->expected.p, expected, polys * kPolyBytes, hipMemcpyHostToDevice, c->stream));
+    ClientResponseNoiseParams np{};
+    np.d.sp = centred_of(c) + kN;
+    np.d.resp = c->in.p;
+    np.d.rows = c->rows;
+    np.d.cols = c->cols;
+    np.d.wire = wire ? 1 : 0;
+    np.d.w0 = c->p.qprime_bits;
+    np.d.w1 = wire_bits_rest(&c->p);
+    np.d.wire_words = wire_each / 8;
+    np.d.qprime = c->qprime;
+    np.d.p_db = c->p.p_db;
+    np.expected = expected ? c->expected.p : nullptr;
+    np.stats = stats ? c->out.p : nullptr;
+    np.errors = errors ? reinterpret_cast<int64_t*>(c->out.p + stats_words) : nullptr;
+    np.final_form = form == SPIRAL_GPU_RESPONSE_FINAL ? 1 : 0;
+    launch_client_response_noise(np, n, c->stream);
+    HIP_OK(hipGetLastError());
+    if (stats) HIP_OK(hipMemcpyAsync(stats, c->out.p, stats_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (errors) HIP_OK(hipMemcpyAsync(errors, c->out.p + stats_words, err_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return 0;
 }

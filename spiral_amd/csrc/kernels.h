@@ -722,5 +722,17 @@ struct ClientDecodeParams {
     uint64_t qprime, p_db;
 };
 void launch_client_decode(const ClientDecodeParams& p, uint32_t n, hipStream_t s);
+// the error e of every coefficient of n responses and its record per output polynomial (include/spiral_gpu.h, spiral_gpu_client_response_noise: the
+// definition), ONE launch, one workgroup per output polynomial.  d: the decode's arguments (d.out unused); with final_form, d.resp holds n
+// unswitched ciphertexts [(rows + 1)][cols][2048] of raw values mod Q and d.wire is 0.  expected: null or [n][rows][cols][2048] values below p_db;
+// stats: null or [n][rows][cols][6] words; errors: null or [n][rows][cols][2048].  Exact under the decode's conditions and p_db q' < 2^57.
+struct ClientResponseNoiseParams {
+    ClientDecodeParams d;
+    const uint64_t* expected;
+    uint64_t* stats;
+    int64_t* errors;
+    uint32_t final_form;
+};
+void launch_client_response_noise(const ClientResponseNoiseParams& p, uint32_t n, hipStream_t s);
 
 }  // namespace spiral

@@ -153,6 +153,16 @@ def p_err_log2(p, q_prime, s_e, n=2):
     return (math.log(2) + (-math.pi * thresh ** 2) / denom + math.log(n * n * d)) * math.log(math.e, 2)
 
 
+def response_noise_model(kind, p, q_prime, t_GSW, t_conv, t_exp, t_exp_right, nu_1, nu_2, n=2):
+    """the two quantities the model computes on its way to p_err_log2, for comparison with a measured response (Client.response_noise):
+    (s_e, w2) -- s_e = noise_variance(...), the width^2 of the unswitched error in units of Q (a measured FINAL-form width2() times
+    scale_k^2 is in the same unit); w2 = s_e (p/q)^2 + (sigma^2 d / 4) (p/q')^2, the denominator of p_err_log2: the width^2 of the switched
+    error in plaintext steps, the unit of a switched form's width2()"""
+    s_e = noise_variance(kind, p, t_GSW, t_conv, t_exp, t_exp_right, nu_1, nu_2, n)
+    pr, q = float(real_p(int(p))), float(REAL_Q)
+    return s_e, float(s_e) * (pr / q) ** 2 + ((SIGMA ** 2) * POLY_LEN / 4) * (pr / float(q_prime)) ** 2  # p_err_log2's one line
+
+
 def feasible(kind, p, t_GSW, t_conv, t_exp, t_exp_right, nu_1, nu_2, n=2):
     """None when the set cannot reach 2^-40 correctness, else {"q_prime_bits", "s_e"}: simul / simul_highrate
     (generate_all_schemes.py:192-289) -- feasibility at q' = p 2^20, then the smallest q' on the reference's ladder"""
