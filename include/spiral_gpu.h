@@ -276,6 +276,61 @@ size_t spiral_gpu_db_items_bytes(const spiral_gpu_params *p, uint32_t out_n, uin
  * Before any launch: null pointers, a range outside the database, coeff_bits outside 1..64 or 2^coeff_bits < p_db (64 always passes). */
 int spiral_gpu_server_read_db_items(spiral_gpu_server *s, void *items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items);
 int spiral_gpu_server_read_db_items_at(spiral_gpu_server *s, void *items, uint32_t coeff_bits, const uint64_t *item_ids, uint64_t n);
+
+/* ---- Records: byte strings of any size S >= 1, packed into the plaintexts of a base server -------------------------------------------------
+ * The layout, stated once; every record call below, and the Python and test code, quote it.
+ *
+ * For a base parameter set:
+ *   - w = floor(log2 p_db) bits per coefficient are used.  For a power-of-two p_db this is the item stream of load_db_items at coeff_bits = log2 p_db.
+ *   - A polynomial is 256 w bytes.
+ *   - An item is item_bytes = 1024 w bytes: polynomial (m, c) at (m*2 + c) * 256 w, bits little-endian, exactly as read_db_items(w) lays it out.
+ * For a record size S >= 1 there are two cases.
+ *   - S <= item_bytes.  Then per_item = floor(item_bytes / S) and instances = 1.  Record r lives in item r / per_item and occupies bytes
+ *     [(r mod per_item) * S, + S) of that item's stream.  Records never straddle items.  They may straddle polynomials, and when 8 S is not a
+ *     multiple of w their ends fall inside a coefficient.  The item's last item_bytes - per_item * S bytes are padding.
+ *   - S > item_bytes.  Then per_item = 1 and instances = ceil(S / item_bytes) (the reference's `factor`, select_params.py; refused above 16 as
+ *     the instance calls refuse it).  Chunk f of record r is bytes [f * item_bytes, ...) of the record; it sits at byte 0 of item r of
+ *     instance f.  The tail of the last chunk is padding.
+ * In both cases capacity = 2^(nu1 + nu2) * per_item records.  (p = 256, S = 256: 32 records per 8192-byte item; p = 2^15, S = 100 000: 7
+ * instances of 15 360-byte items.)
+ * Padding: load_records writes it as zero; update_records never changes a bit outside the ranges of the records it is given.
+ * A coefficient of the image that is no plaintext value (after fill_db_random), or whose value is >= 2^w (only possible for a p_db that is no
+ * power of two), is not part of a record database: every call that would have to read it fails, the message names the first such record (lowest
+ * position in the call) and coefficient, and the failing call changes nothing.
+ * `instance` (all server calls) selects which chunk of each record this server's image holds: 0 unless instances > 1.  One call is made per
+ * instance server on the same buffer, the way shards share one. */
+typedef struct spiral_gpu_record_layout {
+    uint32_t coeff_bits; /* w */
+    uint32_t instances;
+    uint64_t per_item;
+    uint64_t item_bytes;
+    uint64_t capacity;
+} spiral_gpu_record_layout;
+/* host only, no device needed; fails for parameters get_shape refuses, S = 0, or more than 16 instances */
+int spiral_gpu_record_layout_of(const spiral_gpu_params *p, uint64_t record_bytes, spiral_gpu_record_layout *out);
+/* Records first_record .. first_record + n_records - 1 from one contiguous byte array (record k of the call at k * record_bytes), through
+ * load_db_items' ingest: the range starts and ends at a multiple of per_item.  The records are repacked into items on the host with zero
+ * padding; where per_item * S = item_bytes (and p_db is a power of two) the bytes go through unchanged.  A sharded server keeps what it holds. */
+int spiral_gpu_server_load_records(spiral_gpu_server *s, const void *records, uint64_t record_bytes, uint32_t instance, uint64_t first_record,
+                                   uint64_t n_records);
+/* Replace n records given by id, in place, in the image's CURRENT form, on the holder's stream: update_db_items' contract at a record's
+ * granularity.  Ids are distinct and below the capacity; every check runs before anything is launched; a failing call leaves the image
+ * byte-identical; no conversion and no new epoch, so graphs captured before still replay and now read the new record; a j-sharded or
+ * column-sharded server writes the records it holds and skips the rest; lanes and share_db servers are refused (update through the owner); refused
+ * inside a stream capture.  One read-modify-write launch (one workgroup per polynomial of a touched item) and update_db_items' scatter launch.
+ * Returns once `records` and `record_ids` may be reused.  Where every touched polynomial is covered whole by the call's records, nothing of the
+ * image is read and nothing is synchronised, as for update_db_items; otherwise the call waits for this server's stream (and nothing else) to learn
+ * whether the polynomials it read hold record data, and fails with the image untouched if they do not. */
+int spiral_gpu_server_update_records(spiral_gpu_server *s, const void *records, uint64_t record_bytes, uint32_t instance,
+                                     const uint64_t *record_ids, uint64_t n);
+/* The mirror of read_db_items / read_db_items_at: record k of the call to byte k * record_bytes of `records` (an instance server: its chunk of
+ * it).  Any server that references a loaded image may call them, lanes included; shards fill in the records they hold and leave the other bytes
+ * alone; ids need not be distinct; the call returns synchronised.  One workgroup per touched polynomial, and only the records' bytes are staged and
+ * copied.  A range of whole items of a layout without padding is the range export of read_db_items. */
+int spiral_gpu_server_read_records(spiral_gpu_server *s, void *records, uint64_t record_bytes, uint32_t instance, uint64_t first_record,
+                                   uint64_t n_records);
+int spiral_gpu_server_read_records_at(spiral_gpu_server *s, void *records, uint64_t record_bytes, uint32_t instance, const uint64_t *record_ids,
+                                      uint64_t n);
 /* read the device database back in reference layouts (tests): plaintext `item` as its n0 x n2 NTT-form MatPoly
  * (pts_encd, :1128), or slabs z_begin .. z_begin+nz-1 of load_db's layout restricted to this server's j-range:
  * word (z, ii, c, j, m) at ((((z - z_begin)*num_per + ii)*n2 + c)*(j_end - j_begin) + (j - j_begin))*n0 + m */
@@ -961,6 +1016,19 @@ int spiral_gpu_client_queries(spiral_gpu_client *c, const uint64_t *idx, uint32_
 int spiral_gpu_client_decode(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t *plaintexts);
 int spiral_gpu_client_response_noise(spiral_gpu_client *c, const void *responses, uint32_t n, int form, const uint64_t *expected, uint64_t *stats,
                                      int64_t *errors);
+/* Records ("Records" above; base clients, out_n = 0).
+ * record_queries: spiral_gpu_client_queries for the items the records live in (record r: item r / per_item), one query per record; one query also
+ * serves a record of several instances (the same item index in every instance server).
+ * decode_records: `responses` holds n x instances responses laid out [record][instance], in RAW or WIRE form as decode takes them (at most 65535 in
+ * all); `records` receives n x record_bytes bytes.  The result is bit for bit what decode gives, followed by packing at w bits and cutting out the
+ * record's range (chunk f of a record from response f) -- computed by one workgroup per output polynomial a record touches, which writes the record's
+ * bytes straight to the output: a record inside one polynomial costs one of the decode's four convolutions and returns record_bytes bytes instead of
+ * 64 KiB of words.  For a p_db that is no power of two the low w bits of a decoded value are packed.  Returns synchronised; every argument is checked
+ * first (null pointers, an unknown form, a record size the layout refuses, an id at or above the capacity, a SpiralPack session). */
+int spiral_gpu_client_record_queries(spiral_gpu_client *c, uint64_t record_bytes, const uint64_t *record_ids, uint32_t n, int form, void *out,
+                                     size_t bytes_each);
+int spiral_gpu_client_decode_records(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t record_bytes,
+                                     const uint64_t *record_ids, void *records);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,12 @@ class PackShape(C.Structure):
     ]
 
 
+class RecordLayout(C.Structure):
+    """spiral_gpu_record_layout: how records of one byte size lie in the plaintexts of a base parameter set (include/spiral_gpu.h "Records")"""
+
+    _fields_ = [("coeff_bits", C.c_uint32), ("instances", C.c_uint32), ("per_item", C.c_uint64), ("item_bytes", C.c_uint64), ("capacity", C.c_uint64)]
+
+
 U64P = C.POINTER(C.c_uint64)
 
 # name -> (restype, argtypes); every symbol include/spiral_gpu.h declares
@@ -117,6 +123,11 @@ PROTOTYPES = {
     "spiral_gpu_db_items_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32, C.c_uint32, C.c_uint64]),
     "spiral_gpu_server_read_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint64, C.POINTER(RecordLayout)]),
+    "spiral_gpu_server_load_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_update_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_server_read_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_read_records_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_server_read_db_item": (C.c_int, [C.c_void_p, C.c_uint64, U64P]),
     "spiral_gpu_server_read_db_slots": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, U64P]),
     "spiral_gpu_server_read_db_columns": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, U64P]),
@@ -253,6 +264,8 @@ PROTOTYPES = {
     "spiral_gpu_client_pub_params_msg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_queries": (C.c_int, [C.c_void_p, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P]),
+    "spiral_gpu_client_record_queries": (C.c_int, [C.c_void_p, C.c_uint64, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_client_decode_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, U64P, C.c_void_p]),
     "spiral_gpu_client_response_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P, U64P, C.POINTER(C.c_int64)]),
 }
 
@@ -322,6 +335,38 @@ def db_items_bytes(params: Params, coeff_bits: int, n_items: int, out_n: int = 0
     if n == 0 and n_items:
         raise SpiralGpuError(lib().spiral_gpu_last_error().decode())
     return n
+
+
+def record_layout(params: Params, record_bytes: int) -> RecordLayout:
+    """the layout of records of record_bytes bytes in the plaintexts of `params` (host only); raises for a size of 0 or one that takes more than 16
+    instances"""
+    if not isinstance(record_bytes, (int, np.integer)) or isinstance(record_bytes, bool) or not 0 <= record_bytes < 2**64:
+        raise ValueError(f"record_bytes = {record_bytes!r} is no byte count")
+    out = RecordLayout()
+    check(lib().spiral_gpu_record_layout_of(C.byref(params), int(record_bytes), C.byref(out)))
+    return out
+
+
+def record_array(records, record_bytes: int, n: int | None = None) -> np.ndarray:
+    """the records of a load_records / update_records call as one contiguous uint8 array of whole records (n of them, where n is given)"""
+    if isinstance(records, (bytes, bytearray, memoryview)):
+        records = np.frombuffer(records, dtype=np.uint8)
+    records = np.ascontiguousarray(records)
+    if records.dtype != np.uint8:
+        raise TypeError(f"records are bytes or a uint8 array, not {records.dtype}")
+    if records.size % record_bytes or (n is not None and records.size != n * record_bytes):
+        raise ValueError(f"records holds {records.size} bytes: not {'whole' if n is None else n} records of {record_bytes} bytes")
+    return records.reshape(-1)
+
+
+def record_out(record_bytes: int, n: int, out) -> np.ndarray:
+    """the output buffer of a read_records call: a fresh zeroed uint8 array [n][record_bytes], or the caller's `out` of exactly that size (shards and
+    instance servers fill one buffer)"""
+    if out is None:
+        return np.zeros((n, record_bytes), dtype=np.uint8)
+    if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable and out.size == n * record_bytes):
+        raise ValueError(f"out must be a writable contiguous uint8 array of {n * record_bytes} bytes")
+    return out
 
 
 def read_args(params: Params, coeff_bits: int, n_items: int, out_n: int, out):

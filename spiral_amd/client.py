@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U64P, check, lib, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U64P, check, lib, read_ids, record_layout, wire_bytes
 
 N = 2048
 RESPONSE_RAW, RESPONSE_WIRE = 0, 1  # spiral_gpu_response_form
@@ -141,6 +141,38 @@ class Client:
         n = buf.size // each
         out = np.zeros((n, self.rows, self.cols, N), dtype=np.uint64)
         check(lib().spiral_gpu_client_decode(self.h, buf.ctypes.data_as(C.c_void_p), n, _FORMS[form], out.ctypes.data_as(U64P)))
+        return out
+
+    # ---- records of any byte size (include/spiral_gpu.h "Records"; base clients) ----
+    def record_queries(self, record_ids, record_bytes: int, form="seeded") -> np.ndarray:
+        """queries() for the items the records live in: one query per record (it serves every instance of a record of several)"""
+        f = _message_form(form)
+        ids = read_ids(record_ids)
+        each = self._bytes["query", f]
+        out = np.zeros((ids.size, each), dtype=np.uint8)
+        check(lib().spiral_gpu_client_record_queries(self.h, record_bytes, ids.ctypes.data_as(U64P), ids.size, f, out.ctypes.data_as(C.c_void_p), each))
+        return out.view(np.uint64).reshape(ids.size, self.shape.n_query_cts, 2, 1, 2, N) if f == FORM_NTT else out
+
+    def decode_records(self, responses, record_ids, record_bytes: int, form="raw") -> np.ndarray:
+        """the records record_ids[k] as a uint8 array [n][record_bytes] from n x instances responses laid out [record][instance], in decode()'s forms:
+        bit for bit decode() followed by packing at w bits and cutting out each record's range, done per touched output polynomial on the device"""
+        if form not in _FORMS:
+            raise ValueError(f"response form {form!r}: 'raw' or 'wire'")
+        lay = record_layout(self.params, record_bytes)
+        ids = read_ids(record_ids)
+        if form == "raw":
+            buf = np.ascontiguousarray(responses, dtype=np.uint64)
+            each = (self.rows + 1) * self.cols * N
+        else:
+            buf = wire_bytes(responses)
+            each = self.response_wire_bytes()
+        if ids.size == 0 and buf.size == 0:
+            return np.zeros((0, record_bytes), dtype=np.uint8)
+        if buf.size != ids.size * lay.instances * each:
+            raise ValueError(f"{buf.size} {'words' if form == 'raw' else 'bytes'} are not the {ids.size} x {lay.instances} responses of {each} of {ids.size} records")
+        out = np.zeros((ids.size, record_bytes), dtype=np.uint8)
+        check(lib().spiral_gpu_client_decode_records(self.h, buf.ctypes.data_as(C.c_void_p), ids.size, _FORMS[form], record_bytes, ids.ctypes.data_as(U64P),
+                                                     out.ctypes.data_as(C.c_void_p)))
         return out
 
     def noise_step(self, form="raw") -> int:

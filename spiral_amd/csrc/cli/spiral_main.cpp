@@ -3,6 +3,7 @@
 //
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
 //            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch] [--device-client [--output-err F]]
+//   ./spiral <nu1> <nu2> <RECORD> a --record-bytes S [--device-client]      (a record of S bytes: run_records below)
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -369,6 +370,98 @@ static int run_high_rate(spiral_gpu_params p, uint32_t out_n, uint64_t idx_targe
     return (is_corr && batch_corr) ? 0 : 2;
 }
 
+// ---- --record-bytes S: the third argument is a RECORD id (include/spiral_gpu.h "Records") ------------------------------------------------------------
+// The database is filled through load_records -- one server per instance of the layout -- from a counter-based byte generator:
+//     byte i of record r in generation g  =  the low byte of splitmix64((0x5245434F52445300 + g) ^ (r * S + i))
+// (splitmix64 as spiral_gpu_server_gen_db's generator uses it; generation 0 is the loaded database, generation 1 what the update writes).  One query
+// for the record's item is answered -- answer_instances when the layout has several instances, the one-query flow otherwise -- and decoded: with
+// --device-client by decode_records on the session, with the host client by packing the decoded plaintexts at w bits and cutting on the host.  The
+// record is then replaced through update_records, answered again and decoded again; both results are checked against the generator.
+static uint64_t splitmix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+static void record_bytes_of(uint32_t generation, uint64_t r, uint64_t S, uint8_t* out) {
+    for (uint64_t i = 0; i < S; i++) out[i] = (uint8_t)splitmix64((0x5245434F52445300ull + generation) ^ (r * S + i));
+}
+static int run_records(const spiral_gpu_params& p, uint64_t record, uint64_t S, uint64_t seed, bool nonoise) {
+    spiral_gpu_record_layout lay;
+    GPU_OK(spiral_gpu_record_layout_of(&p, S, &lay));
+    if (record >= lay.capacity) {
+        fprintf(stderr, "spiral: record %llu out of range (%llu records of %llu bytes)\n", (unsigned long long)record, (unsigned long long)lay.capacity, (unsigned long long)S);
+        return 1;
+    }
+    spiral_gpu_shape s;
+    GPU_OK(spiral_gpu_get_shape(&p, &s));
+    cout << "Records of " << S << " bytes: " << lay.per_item << " per item of " << lay.item_bytes << " bytes, " << lay.instances << " instance(s), capacity "
+         << lay.capacity << endl;
+    const uint32_t F = lay.instances;
+    std::vector<spiral_gpu_server*> inst(F, nullptr);
+    cout << "starting generation of db" << endl;
+    const uint64_t pass = lay.per_item * 1024;  // records generated and loaded at a time
+    std::vector<uint8_t> buf;
+    for (uint32_t f = 0; f < F; f++) GPU_OK(spiral_gpu_server_create(&p, 0, 0, 0, &inst[f]));
+    for (uint64_t first = 0; first < lay.capacity; first += pass) {
+        const uint64_t n = std::min(pass, lay.capacity - first);
+        buf.resize((size_t)(n * S));
+        for (uint64_t k = 0; k < n; k++) record_bytes_of(0, first + k, S, buf.data() + k * S);
+        for (uint32_t f = 0; f < F; f++) GPU_OK(spiral_gpu_server_load_records(inst[f], buf.data(), S, f, first, n));
+    }
+    cout << "done loading/generating db." << endl;
+    Client cl(p, seed, nonoise);
+    cl.form = g_device_client ? SPIRAL_GPU_FORM_NTT : -1;
+    cl.keygen();
+    cl.gen_pub_params();
+    GPU_OK(spiral_gpu_server_set_pub_params(inst[0], cl.w_left.data(), cl.w_right.data(), cl.w.data(), cl.v.data()));
+    const uint64_t item = record / lay.per_item;
+    Poly final_ct(6 * N), resps((size_t)F * 6 * N);
+    std::vector<uint8_t> got((size_t)S), want((size_t)S);
+    bool all_ok = true;
+    for (uint32_t generation = 0; generation < 2; generation++) {
+        if (generation) {  // replace the record in place, in every instance
+            record_bytes_of(1, record, S, want.data());
+            for (uint32_t f = 0; f < F; f++) GPU_OK(spiral_gpu_server_update_records(inst[f], want.data(), S, f, &record, 1));
+        }
+        Query query = cl.query(item);
+        if (g_device_client)  // the same through the record call: one query per record, serving every instance
+            GPU_OK(spiral_gpu_client_record_queries(cl.session.get(), S, &record, 1, SPIRAL_GPU_FORM_NTT, query.cts.data(), query.cts.size() * sizeof(uint64_t)));
+        cout << "Beginning query processing..." << endl;
+        double us[8], item_us = 0;
+        if (F > 1)
+            GPU_OK(spiral_gpu_server_answer_instances(inst[0], inst.data(), F, query.cts.data(), resps.data(), nullptr, &item_us));
+        else
+            GPU_OK(spiral_gpu_server_answer(inst[0], query.cts.data(), final_ct.data(), resps.data(), us));
+        cout << "Done with query processing!" << endl;
+        if (g_device_client) {
+            GPU_OK(spiral_gpu_client_decode_records(cl.session.get(), resps.data(), 1, SPIRAL_GPU_RESPONSE_RAW, S, &record, got.data()));
+        } else {  // the plaintexts packed at w bits -- coefficient k of polynomial (m, c) at bit ((m * 2 + c) * N + k) * w -- and the record's range cut out
+            const uint32_t w = lay.coeff_bits;
+            for (uint32_t f = 0; f < F; f++) {
+                const Poly pt = cl.decode(resps.data() + (size_t)f * 6 * N);
+                const uint64_t off = F == 1 ? (record % lay.per_item) * S : 0, first = (uint64_t)f * lay.item_bytes;
+                const uint64_t len = F == 1 ? S : std::min<uint64_t>(S - first, lay.item_bytes);
+                for (uint64_t i = 0; i < len; i++) {
+                    uint32_t byte = 0;
+                    for (uint32_t b = 0; b < 8; b++) {
+                        const uint64_t bit = 8 * (off + i) + b;
+                        byte |= (uint32_t)((pt[bit / w] >> (bit % w)) & 1u) << b;
+                    }
+                    got[(F == 1 ? 0 : first) + i] = (uint8_t)byte;
+                }
+            }
+        }
+        record_bytes_of(generation, record, S, want.data());
+        const bool ok = got == want;
+        all_ok = all_ok && ok;
+        cout << "Record " << record << (generation ? " after update_records" : " as loaded") << ", correct: " << (ok ? 1 : 0) << endl;
+    }
+    cout << "Is correct?: " << (all_ok ? 1 : 0) << endl;
+    for (spiral_gpu_server* sv : inst) spiral_gpu_server_destroy(sv);
+    return all_ok ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
     if (argc < 4) {
         fprintf(stderr, "usage: %s <nu1> <nu2> <IDX_TARGET> [dbfile|a] [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--output-err F] [--seed N]\n", argv[0]);
@@ -381,6 +474,8 @@ int main(int argc, char** argv) {
     uint32_t batch = 0, instances = 0;
     int key_store = -1;  // --key-store: the slot form of the store the batch's keys are bound from (-1: none)
     bool query_batch = false;  // --query-batch: the batch's queries in one set_query_batch call, its responses in one read
+    uint64_t record_bytes = 0;  // --record-bytes S: IDX_TARGET is a record id (run_records above)
+    bool record_run = false;
     // as the reference (random_device, src/core.cpp:202; it labels its own generator NOT SECURE): two words of it.
     // This client is a test harness for the server path, not a hardened client.
     std::random_device rd;
@@ -424,6 +519,24 @@ int main(int argc, char** argv) {
         // path: without --device-client the flag and its file name are consumed so that a driver's command line parses the same way, and the
         // file is not written.
         if (!strcmp(argv[i], "--output-err") && i + 1 < argc) g_output_err = argv[++i];
+        // --record-bytes S (not a flag of the reference): IDX_TARGET names a record of S bytes; load_records, one query, decode, update_records, again
+        if (!strcmp(argv[i], "--record-bytes")) {
+            record_run = true;
+            if (i + 1 < argc) record_bytes = strtoull(argv[++i], nullptr, 10);
+        }
+    }
+    if (record_run) {
+        if (record_bytes == 0) {
+            fprintf(stderr, "spiral: --record-bytes takes a record size of at least 1 byte\n");
+            return 1;
+        }
+        if (show_diff || random_data) cout << "--record-bytes: " << (show_diff ? "--show-diff" : "--random-data") << " has no meaning in a records run (ignored)" << endl;
+        if (argc > 4 && strcmp(argv[4], "a")) cout << "--record-bytes: the database is generated, the file argument " << argv[4] << " is not read (ignored)" << endl;
+        const char* with = key_store >= 0 ? "--key-store" : query_batch ? "--query-batch" : high_rate ? "--high-rate" : instances ? "--instances" : batch ? "--batch" : nullptr;
+        if (with) {
+            fprintf(stderr, "spiral: --record-bytes does not go with %s (a one-query run of a base server; the layout chooses its own instances)\n", with);
+            return 1;
+        }
     }
     if (!g_output_err.empty() && !g_device_client) {
         cout << "--output-err " << g_output_err << ": noise statistics are not produced by this build without --device-client (ignored)" << endl;
@@ -451,7 +564,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: --key-store takes --batch B in 2 .. 8 (not with --instances or --high-rate)\n");
         return 1;
     }
-    if (idx_target >= total_n) {
+    if (!record_run && idx_target >= total_n) {
         fprintf(stderr, "spiral: IDX_TARGET %llu out of range (n = %llu)\n", (unsigned long long)idx_target, (unsigned long long)total_n);
         return 1;
     }
@@ -479,6 +592,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: no ROCm device found; this build has no CPU path\n");
         return 1;
     }
+    if (record_run) return run_records(p, idx_target, record_bytes, seed, nonoise);
     if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch, instances);
     spiral_gpu_shape s;
     GPU_OK(spiral_gpu_get_shape(&p, &s));

@@ -173,6 +173,54 @@ __global__ __launch_bounds__(kClientTpb) void client_decode_kernel(ClientDecodeP
     }
 }
 
+// The decode of the output polynomials that records touch (kernels.h ClientRecordDecodeParams): client_decode_kernel's operands, convolution and
+// rounding through the shared functions; the 2048 values then meet in LDS and the waves store the records' byte ranges of their w-bit string -- a
+// 256-byte record of an 8 KiB plaintext is one convolution and 256 bytes out, not four and 64 KiB of words.
+__global__ __launch_bounds__(kClientTpb) void client_decode_records_kernel(ClientRecordDecodeParams q) {
+    __shared__ int32_t ext[2 * kN];
+    __shared__ int8_t s8[kN];
+    __shared__ uint64_t vals[kN];
+    const ClientDecodeParams& p = q.d;
+    const uint4 e = q.entries[blockIdx.x];
+    const uint32_t b = e.x, r = e.y & 0xFFu, col = e.y >> 8, t = threadIdx.x, w = q.w;
+    for (uint32_t z = t; z < kN; z += kClientTpb) {
+        const int32_t a = (int32_t)(response_value(p, b, col, 0, z) % p.qprime);
+        ext[kN + z] = a;
+        ext[z] = -a;
+        s8[z] = p.sp[(size_t)r * kN + z];
+    }
+    __syncthreads();
+    int64_t acc[8] = {};
+    secret_row_convolve(ext, s8, t, acc);
+    const int64_t qp = (int64_t)p.qprime, q1 = (int64_t)(4u * p.p_db), pdb = (int64_t)p.p_db;
+    const uint64_t mask = (1ull << w) - 1ull;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t k = t + 256u * j;
+        int64_t x;
+        int64_t res = switched_round(acc[j], response_value(p, b, col, 1u + r, k), qp, q1, x);
+        res %= pdb;
+        res += res < 0 ? pdb : 0;
+        vals[k] = (uint64_t)res & mask;
+    }
+    __syncthreads();
+    const uint32_t lane = t & 63u, wave = t >> 6;
+    for (uint32_t s = wave; s < e.w; s += kClientTpb / 64u) {
+        const uint4 seg = q.segs[e.z + s];
+        uint8_t* dst = q.buf + (((uint64_t)seg.w << 32) | seg.z);
+        for (uint32_t i = lane; i < seg.y; i += 64u) {  // byte i of the segment: bits [8 (seg.x + i), + 8) of the string of w-bit values
+            const uint32_t bit = 8u * (seg.x + i);
+            uint32_t c = bit / w, filled = w - (bit - c * w);
+            uint64_t v = vals[c] >> (w - filled);
+            while (filled < 8u) {  // (the segment ends inside the polynomial's 2048 w bits: c + 1 < 2048 here)
+                v |= vals[++c] << filled;
+                filled += w;
+            }
+            dst[i] = (uint8_t)v;
+        }
+    }
+}
+
 // ---- response noise (include/spiral_gpu.h, spiral_gpu_client_response_noise: the one definition of e) ------------------------------------------
 // One workgroup per output polynomial, as the decode.  Switched forms: the decode's operands, convolution and rounding, then e from x.  FINAL form:
 // row 0 is a value mod Q of 56 bits, whose sums against the secret do not fit 64 bits; the same convolution runs once per 28-bit prime on the
@@ -339,6 +387,10 @@ void launch_client_wire_encode(const uint64_t* raw, uint8_t* wire, uint32_t npol
 void launch_client_decode(const ClientDecodeParams& p, uint32_t n, hipStream_t s) {
     if (n == 0) return;
     hipLaunchKernelGGL(client_decode_kernel, dim3(p.cols, p.rows, n), dim3(kClientTpb), 0, s, p);
+}
+
+void launch_client_decode_records(const ClientRecordDecodeParams& p, uint32_t n_entries, hipStream_t s) {
+    if (n_entries) hipLaunchKernelGGL(client_decode_records_kernel, dim3(n_entries), dim3(kClientTpb), 0, s, p);
 }
 
 void launch_client_response_noise(const ClientResponseNoiseParams& p, uint32_t n, hipStream_t s) {

@@ -9,6 +9,7 @@
 // the host, and the device does the rest.
 #include "client_device.h"
 #include "message.h"
+#include "records_host.h"
 
 using namespace spiral;
 using namespace spiral::host;
@@ -530,6 +531,88 @@ int spiral_gpu_client_decode(spiral_gpu_client* c, const void* responses, uint32
     launch_client_decode(dp, n, c->stream);
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(plaintexts, c->out.p, n * out_words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- records (include/spiral_gpu.h "Records"): a base client's queries for, and decode of, records of any byte size --------------------------------
+namespace {
+int client_record_layout(spiral_gpu_client* c, const char* what, uint64_t record_bytes, const uint64_t* record_ids, uint32_t n, spiral_gpu_record_layout* l) {
+    if (c->out_n) return fail("%s: records are laid out in the plaintexts of a base server, this is a SpiralPack client", what);
+    if (record_layout(&c->p, record_bytes, l)) return -1;
+    for (uint32_t k = 0; k < n; k++)
+        if (record_ids[k] >= l->capacity)
+            return fail("%s: record id %llu (position %u) outside the database of %llu records", what, (unsigned long long)record_ids[k], k, (unsigned long long)l->capacity);
+    return 0;
+}
+}  // namespace
+
+// client_queries for the items the records live in: one query per record (it also serves every instance of a record of several)
+int spiral_gpu_client_record_queries(spiral_gpu_client* c, uint64_t record_bytes, const uint64_t* record_ids, uint32_t n, int form, void* out, size_t bytes_each) {
+    if (client_on(c, "client_record_queries")) return -1;
+    if (!record_ids || !out) return fail("client_record_queries: null argument");
+    spiral_gpu_record_layout l;
+    if (client_record_layout(c, "client_record_queries", record_bytes, record_ids, n, &l)) return -1;
+    std::vector<uint64_t> items(record_ids, record_ids + n);
+    for (uint64_t& i : items) i /= l.per_item;
+    return spiral_gpu_client_queries(c, items.data(), n, form, out, bytes_each);
+}
+
+// decode, then packing at w bits and cutting out the record's range -- done per touched output polynomial on the device (client.hip)
+int spiral_gpu_client_decode_records(spiral_gpu_client* c, const void* responses, uint32_t n, int form, uint64_t record_bytes, const uint64_t* record_ids,
+                                     void* records) {
+    if (client_on(c, "client_decode_records")) return -1;
+    if (!responses || !record_ids || !records) return fail("client_decode_records: null argument");
+    if (form != SPIRAL_GPU_RESPONSE_RAW && form != SPIRAL_GPU_RESPONSE_WIRE) return fail("client_decode_records: unknown response form %d", form);
+    spiral_gpu_record_layout l;
+    if (client_record_layout(c, "client_decode_records", record_bytes, record_ids, n, &l)) return -1;
+    const uint64_t n_resp = (uint64_t)n * l.instances;
+    if (n == 0 || n_resp > 65535u) return fail("client_decode_records: %llu responses, a call takes 1 .. 65535", (unsigned long long)n_resp);
+    // response k * instances + f holds chunk f of record k: bytes [off, off + len) of its plaintext's stream, staged at the chunk's place in the record
+    std::vector<RecordPiece> pieces;
+    pieces.reserve(n_resp);
+    for (uint32_t k = 0; k < n; k++)
+        for (uint32_t f = 0; f < l.instances; f++) {
+            RecordChunk ch;
+            if (record_chunk(l, record_bytes, f, &ch)) return -1;
+            const uint32_t off = l.instances == 1 ? (uint32_t)((record_ids[k] % l.per_item) * record_bytes) : 0u;
+            pieces.push_back(RecordPiece{k, k * l.instances + f, 0u, off, (uint32_t)ch.len});
+        }
+    std::vector<uint4> entries, segs;
+    record_tables(pieces, 0, pieces.size(), l.coeff_bits, false, entries, segs, nullptr,
+                  [&](uint32_t k) { return (uint64_t)(k / l.instances) * record_bytes + (uint64_t)(k % l.instances) * l.item_bytes; });
+    for (uint4& e : entries) {  // {response, r | col << 8, first segment, segments}
+        const uint32_t mc = (e.x >> kRecordPolyShift) & 3u;
+        e = make_uint4(e.x & kRecordRowMask, (mc >> 1) | ((mc & 1u) << 8), e.z, e.w);
+    }
+    const bool wire = form == SPIRAL_GPU_RESPONSE_WIRE;
+    const size_t wire_each = wire_bytes(&c->p, c->cols);  // a multiple of 256 bytes
+    const size_t in_words = wire ? wire_each / 8 : (size_t)(c->rows + 1) * c->cols * kN;
+    const size_t o_segs = entries.size() * sizeof(uint4), o_buf = o_segs + segs.size() * sizeof(uint4), out_bytes = (size_t)n * record_bytes;
+    if (grow(c->in, n_resp * in_words + 1) || grow(c->out, (o_buf + out_bytes + 7) / 8)) return -1;
+    uint8_t* d = reinterpret_cast<uint8_t*>(c->out.p);
+    HIP_OK(hipMemcpyAsync(c->in.p, responses, n_resp * in_words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->in.p + n_resp * in_words, 0, sizeof(uint64_t), c->stream));  // (the word a wire field's window may reach into)
+    HIP_OK(hipMemcpyAsync(d, entries.data(), o_segs, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemcpyAsync(d + o_segs, segs.data(), o_buf - o_segs, hipMemcpyHostToDevice, c->stream));
+    ClientRecordDecodeParams rp{};
+    rp.d.sp = centred_of(c) + kN;
+    rp.d.resp = c->in.p;
+    rp.d.rows = c->rows;
+    rp.d.cols = c->cols;
+    rp.d.wire = wire ? 1 : 0;
+    rp.d.w0 = c->p.qprime_bits;
+    rp.d.w1 = wire_bits_rest(&c->p);
+    rp.d.wire_words = wire_each / 8;
+    rp.d.qprime = c->qprime;
+    rp.d.p_db = c->p.p_db;
+    rp.entries = reinterpret_cast<const uint4*>(d);
+    rp.segs = reinterpret_cast<const uint4*>(d + o_segs);
+    rp.buf = d + o_buf;
+    rp.w = l.coeff_bits;
+    launch_client_decode_records(rp, (uint32_t)entries.size(), c->stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(records, rp.buf, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -12,30 +12,13 @@
 // numbered band by band, column group by column group, and each XCD takes a contiguous run of jobs (ntt_forward_kernel's job-to-XCD map), so that a
 // group's workgroups are resident together on one XCD and its L2 serves the re-reads.  The grid covers whole bands; a workgroup whose item is outside
 // the launch's range returns at once.
+#include "db_plain_device.h"
 #include "kernels.h"
 #include "ntt_device.h"
 
 namespace spiral {
 
 namespace {
-
-template <uint32_t FORM, bool PACK>
-__device__ __forceinline__ uint64_t image_word(const uint64_t* db, uint32_t z, uint32_t j, uint32_t ii, uint32_t mc, uint32_t num_per, uint32_t dim0) {
-    if constexpr (PACK) {
-        if constexpr (FORM == DBX_PACKED)
-            return db1_get_word(db, z, j, ii, num_per, dim0);
-        else if constexpr (FORM == DBX_LIMBS)
-            return db1_get_word_limbs(db, z, j, ii, num_per, dim0);
-        else
-            return db1_get_word_limbs8(db, z, j, ii, dim0);
-    } else {
-        const uint32_t m = mc >> 1, ic = ii * 2u + (mc & 1u), nic = 2u * num_per;
-        if constexpr (FORM == DBX_PACKED)
-            return db_get_word(db, z, j, ic, m, nic, dim0);
-        else
-            return db_get_word_limbs(db, z, j, ic, m, nic, dim0);
-    }
-}
 
 // (6 workgroups per CU: at the transforms' bound of 8 the gather's addresses spill 12 bytes per thread; at 6 every form compiles to 61 .. 74 VGPRs, no scratch)
 template <uint32_t FORM, bool PACK>
@@ -72,15 +55,12 @@ __global__ __launch_bounds__(256, 6) void db_export_kernel(Tables t, DbExportPar
     }
     ntt_inverse_block<false>(lo, hi, sh, t.inv, tid);
     __syncthreads();  // the transform's last LDS reads
-    // ingest maps x < half to x and x >= half to Q - (p_db - x): anything between is no plaintext coefficient
-    const uint64_t half = p.p_db >> 1, top = kQ - (p.p_db - half);
     uint32_t bad = kN;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-        const uint64_t v = crt_compose_lazy(csub_min(lo[r], kP), hi[r]);
-        const bool ok = v < half || v >= top;
+        bool ok;
+        sh[ix_a(tid, r)] = unlift_coeff(crt_compose_lazy(csub_min(lo[r], kP), hi[r]), p.p_db, ok);
         if (!ok) bad = min(bad, ix_a(tid, r));
-        sh[ix_a(tid, r)] = !ok ? 0ull : v < half ? v : v - (kQ - p.p_db);
     }
     if (bad < kN) atomicMin(p.err, (unsigned long long)((pos * polys + mc) * kN + bad));
     __syncthreads();

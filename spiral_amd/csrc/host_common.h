@@ -385,25 +385,10 @@ struct UpdateImage {
     uint64_t* limbs;   // the image in limb-plane form (null: none)
     uint32_t pack, num_per, dim0;
 };
-// The shared body of update_db_items: checks the coefficients on the host, then ONE upload, ONE encode launch (the ingest transform, linear store)
-// and ONE scatter launch (db_update.hip) on `st`, and returns -- the caller's buffers are copied by then.  Nothing touches the image before every
-// check has passed; the scatter kernel also skips everything when the encode launch flags a coefficient.
-inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, const void* items, uint32_t coeff_bits, uint64_t p_db,
-                        const std::vector<UpdateItem>& sel, const UpdateImage& img) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_OK(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail("update_db_items cannot be called while the server's stream is being captured");
-    if (coeff_bits != 64 && (coeff_bits < 1 || coeff_bits > 40)) return fail("coefficient width %u not in 1..40 or 64", coeff_bits);
-    if (coeff_bits < 64 && (1ull << coeff_bits) < p_db) return fail("%u-bit coefficients cannot hold values below p_db", coeff_bits);
-    if (sel.empty()) return 0;
-    const uint32_t polys = img.pack ? 1u : 4u;
-    const size_t item_bytes = (size_t)polys * kN * coeff_bits / 8, n = sel.size();
-    const uint8_t* src = static_cast<const uint8_t*>(items);
-    for (const UpdateItem& it : sel)
-        if (!coeffs_below(src + it.src * item_bytes, (size_t)polys * kN, coeff_bits, p_db))
-            return fail("a plaintext coefficient of item %llu of the list is not below p_db", (unsigned long long)it.src);
-    // work entries: one per item for the packed form; one per partner pair (j, j ^ 32 / j ^ 64 of a column) for the limb planes
-    std::vector<uint4> put, pairs;
+// the scatter's work entries (kernels.h DbUpdateParams) for the items sel[k] = encoded item k: one per item for the packed form; one per partner pair
+// (j, j ^ 32 / j ^ 64 of a column) for the limb planes
+inline void update_entries(const std::vector<UpdateItem>& sel, const UpdateImage& img, std::vector<uint4>& put, std::vector<uint4>& pairs) {
+    const size_t n = sel.size();
     if (img.packed) {
         put.reserve(n);
         for (size_t k = 0; k < n; k++) put.push_back(make_uint4((uint32_t)k, sel[k].j, sel[k].ii, 0u));
@@ -421,10 +406,10 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
             (sel[it].j & bit ? pairs.back().w : pairs.back().z) = it;
         }
     }
-    // one buffer: [error word][put][pairs][raw items + 16 bytes of over-read room] ++ (device only) [encoded items]
-    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    const size_t o_put = 16, o_pairs = o_put + put.size() * sizeof(uint4), o_items = up16(o_pairs + pairs.size() * sizeof(uint4));
-    const size_t up_bytes = up16(o_items + n * item_bytes + 16), dev_bytes = up_bytes + n * polys * kPolyBytes;
+}
+// the workspace of an update of n items: waits for the previous update's launches (they read the buffers), then grows the pinned buffer to up_bytes and
+// the device buffer to dev_bytes
+inline int update_reserve(UpdateWork& W, size_t n, size_t up_bytes, size_t dev_bytes) {
     if (W.pending) {
         HIP_OK(hipEventSynchronize(W.done));  // the previous update's launches have consumed the buffers
         W.pending = false;
@@ -450,6 +435,32 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
             return fail("no device memory for an update of %zu items (%zu bytes)", n, dev_bytes);
         }
     }
+    return 0;
+}
+// The shared body of update_db_items: checks the coefficients on the host, then ONE upload, ONE encode launch (the ingest transform, linear store)
+// and ONE scatter launch (db_update.hip) on `st`, and returns -- the caller's buffers are copied by then.  Nothing touches the image before every
+// check has passed; the scatter kernel also skips everything when the encode launch flags a coefficient.
+inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, const void* items, uint32_t coeff_bits, uint64_t p_db,
+                        const std::vector<UpdateItem>& sel, const UpdateImage& img) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("update_db_items cannot be called while the server's stream is being captured");
+    if (coeff_bits != 64 && (coeff_bits < 1 || coeff_bits > 40)) return fail("coefficient width %u not in 1..40 or 64", coeff_bits);
+    if (coeff_bits < 64 && (1ull << coeff_bits) < p_db) return fail("%u-bit coefficients cannot hold values below p_db", coeff_bits);
+    if (sel.empty()) return 0;
+    const uint32_t polys = img.pack ? 1u : 4u;
+    const size_t item_bytes = (size_t)polys * kN * coeff_bits / 8, n = sel.size();
+    const uint8_t* src = static_cast<const uint8_t*>(items);
+    for (const UpdateItem& it : sel)
+        if (!coeffs_below(src + it.src * item_bytes, (size_t)polys * kN, coeff_bits, p_db))
+            return fail("a plaintext coefficient of item %llu of the list is not below p_db", (unsigned long long)it.src);
+    std::vector<uint4> put, pairs;
+    update_entries(sel, img, put, pairs);
+    // one buffer: [error word][put][pairs][raw items + 16 bytes of over-read room] ++ (device only) [encoded items]
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_put = 16, o_pairs = o_put + put.size() * sizeof(uint4), o_items = up16(o_pairs + pairs.size() * sizeof(uint4));
+    const size_t up_bytes = up16(o_items + n * item_bytes + 16), dev_bytes = up_bytes + n * polys * kPolyBytes;
+    if (update_reserve(W, n, up_bytes, dev_bytes)) return -1;
     memset(W.host, 0, up_bytes);
     if (!put.empty()) memcpy(W.host + o_put, put.data(), put.size() * sizeof(uint4));
     if (!pairs.empty()) memcpy(W.host + o_pairs, pairs.data(), pairs.size() * sizeof(uint4));

@@ -676,6 +676,38 @@ struct DbExportParams {
 };
 void launch_db_export(const DeviceTables& t, const DbExportParams& p, hipStream_t s);
 
+// ---- records (records.hip; the layout: include/spiral_gpu.h "Records") --------------------------------------------------------
+// Work at a record's own granularity on a base image, one workgroup per polynomial.  A record (or its chunk of one instance) is a byte range of its
+// item's stream; cut at the polynomial boundaries it is a few SEGMENTS, each a byte range of one polynomial's 256 w byte stream (w = bits per
+// coefficient) and a byte range of `buf`, the staging buffer: staged record k at k * stride.  The host builds the two tables:
+//   entries: {j local to the image (bits 0..16) | polynomial mc (24..25) | kRecordFull (bit 28), column ii, first segment, segments}: the segment count
+//            has a word of its own -- a read may name one record any number of times (ids need not be distinct), a segment each
+//   segs:    {byte offset in the polynomial's stream, bytes, byte offset in buf (low, high word)}
+// A coefficient that cannot be part of a record -- no centred lift of a value below p_db, or a value >= 2^w inside a range that is read -- atomicMin's
+// ((staged record * 4 + polynomial) * 2048 + coefficient) into *err, which the host sets to ~0 before the launch.
+// read:   the entries are the touched polynomials; each gathers its words from the image in the form it is in (db_plain_device.h), and stores the
+//         segments' bytes to buf.
+// update: entry 4 e + mc is polynomial mc of touched item e, and its 2048 encoded words go to enc + (4 e + mc) * 2048, the linear order db_update_kernel
+//         scatters from.  No segments: the image's words pass through unchanged.  kRecordFull (the segments cover the polynomial): the coefficients come
+//         from buf alone.  Otherwise gather + inverse transform + unlift, splice the segments' bits over the coefficients (a coefficient that lies
+//         partly inside a segment keeps its other bits), lift and transform forward.  An error also sets *flag, which makes db_update_kernel skip.
+constexpr uint32_t kRecordPolyShift = 24, kRecordFull = 1u << 28, kRecordRowMask = (1u << kRecordPolyShift) - 1u;
+struct RecordWorkParams {
+    const uint64_t* db;  // the image in the form `form` names (DBX_PACKED or DBX_LIMBS)
+    const uint4* entries;
+    const uint4* segs;
+    uint8_t* buf;   // read: written; update: read
+    uint64_t* enc;  // update only
+    unsigned long long* err;
+    uint32_t* flag;  // update only
+    uint32_t n_entries, form;
+    uint32_t num_per, dim0;  // the image's geometry (dim0: the shard's first dimension)
+    uint32_t w, stride;
+    uint64_t p_db;
+};
+void launch_record_read(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s);
+void launch_record_update(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s);
+
 // ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
 // noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]
 // (device memory, 8 words per key) and domain tag `domain`.  raw[b][j][2048]: the raw values mod Q, plus addend[b][j][2048] (mod Q) where addend !=
@@ -722,6 +754,18 @@ struct ClientDecodeParams {
     uint64_t qprime, p_db;
 };
 void launch_client_decode(const ClientDecodeParams& p, uint32_t n, hipStream_t s);
+// The decode at a record's granularity (include/spiral_gpu.h "Records", spiral_gpu_client_decode_records): one workgroup per output polynomial a record
+// touches, the decode's operands, convolution and rounding, then only the record's bytes of the polynomial's w-bit string go out.  d: the decode's
+// arguments (d.out unused).  entries: {response, r | col << 8, first segment, segments}; segs as for RecordWorkParams: {byte offset in the polynomial's
+// stream, bytes, byte offset in buf (low, high word)}.  A value's low w bits are packed (every value of a power-of-two p_db = 2^w).
+struct ClientRecordDecodeParams {
+    ClientDecodeParams d;
+    const uint4* entries;
+    const uint4* segs;
+    uint8_t* buf;
+    uint32_t w;
+};
+void launch_client_decode_records(const ClientRecordDecodeParams& p, uint32_t n_entries, hipStream_t s);
 // the error e of every coefficient of n responses and its record per output polynomial (include/spiral_gpu.h, spiral_gpu_client_response_noise: the
 // definition), ONE launch, one workgroup per output polynomial.  d: the decode's arguments (d.out unused); with final_form, d.resp holds n
 // unswitched ciphertexts [(rows + 1)][cols][2048] of raw values mod Q and d.wire is 0.  expected: null or [n][rows][cols][2048] values below p_db;

@@ -1,0 +1,152 @@
+// Records of any byte size on a base image (spiral_gpu_server_read_records / _read_records_at / _update_records; the layout is stated once in
+// include/spiral_gpu.h "Records", the work tables in kernels.h RecordWorkParams).  One workgroup per touched polynomial, both ways:
+//
+// read:   the export's gather + inverse transform + unlift (db_plain_device.h, shared with db_export_kernel), then only the records' byte ranges of the
+//         polynomial's 256 w byte stream are stored: a 256-byte record of an 8 KiB item costs one transform and 256 bytes.
+// update: read-modify-write of a polynomial.  Gather + inverse transform + unlift, splice the record bytes over the coefficients at bit granularity,
+//         centred lift + forward transform (ntt.hip LD_DBGEN's arithmetic), and the 2048 words go out in the linear order db_update_kernel scatters
+//         from.  The scatter -- packed words, limb planes and the partner nibbles of items j and j ^ 32 -- stays db_update.hip's: nothing of it is
+//         restated here.  It writes whole items, so the polynomials of a touched item that no record touches pass their image words through unchanged
+//         (for a limb-plane image put_limbs of db_get_word_limbs' residue gives back the bytes it was read from), and a polynomial the records cover
+//         whole skips the gather and the inverse transform.
+//
+// Splice: the segments of a polynomial are disjoint bit ranges (the host refuses duplicate ids), so a coefficient that lies inside one segment is a
+// plain LDS store, and one that two segments share, or that a segment covers in part, is cleared and set with LDS atomics on disjoint bits: the
+// waves take the segments in any order without a barrier between them.
+#include "db_plain_device.h"
+#include "kernels.h"
+#include "ntt_device.h"
+
+namespace spiral {
+
+namespace {
+
+__device__ __forceinline__ unsigned long long record_err_key(const RecordWorkParams& p, uint4 seg, uint32_t mc, uint32_t coeff) {
+    const uint64_t k = (((uint64_t)seg.w << 32) | seg.z) / p.stride;
+    return (k * 4u + mc) * kN + coeff;
+}
+
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 6) void record_read_kernel(Tables t, RecordWorkParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint4 e = p.entries[blockIdx.x];
+    const uint32_t j = e.x & kRecordRowMask, mc = (e.x >> kRecordPolyShift) & 3u, nseg = e.w, w = p.w;
+    const uint32_t bad = image_poly_plain<FORM, false>(p.db, j, e.y, mc, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+    if (bad < kN) atomicMin(p.err, record_err_key(p, p.segs[e.z], mc, bad));
+    __syncthreads();
+    for (uint32_t s = wave; s < nseg; s += 4u) {
+        const uint4 seg = p.segs[e.z + s];
+        uint8_t* dst = p.buf + (((uint64_t)seg.w << 32) | seg.z);
+        for (uint32_t i = lane; i < seg.y; i += 64u) {  // byte i of the segment: bits [8 (seg.x + i), + 8) of the string of w-bit coefficients
+            const uint32_t bit = 8u * (seg.x + i);
+            uint32_t c = bit / w, filled = w - (bit - c * w);
+            uint64_t v = sh[c];
+            if (v >> w) atomicMin(p.err, record_err_key(p, seg, mc, c));
+            uint64_t acc = v >> (w - filled);
+            while (filled < 8u) {  // (the segment ends inside the polynomial's 2048 w bits: c + 1 < 2048 here)
+                v = sh[++c];
+                if (v >> w) atomicMin(p.err, record_err_key(p, seg, mc, c));
+                acc |= v << filled;
+                filled += w;
+            }
+            dst[i] = (uint8_t)acc;
+        }
+    }
+}
+
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 4) void record_update_kernel(Tables t, RecordWorkParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint4 e = p.entries[blockIdx.x];
+    const uint32_t j = e.x & kRecordRowMask, mc = blockIdx.x & 3u, nseg = e.w, w = p.w;
+    uint64_t* dst = p.enc + (size_t)blockIdx.x * kN;
+    if (nseg == 0) {  // no record touches it: the image's words as they are
+        uint64_t v[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) v[r] = image_word<FORM, false>(p.db, pk_pos_tk(tid, r), j, e.y, mc, p.num_per, p.dim0);
+        pk_store8(dst, tid, v);
+        return;
+    }
+    const bool full = (e.x & kRecordFull) != 0;
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < 8; r++) sh[ix_a(tid, r)] = 0;
+    } else {
+        const uint32_t bad = image_poly_plain<FORM, false>(p.db, j, e.y, mc, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+        if (bad < kN) {
+            atomicMin(p.err, record_err_key(p, p.segs[e.z], mc, bad));
+            *p.flag = 1u;
+        }
+    }
+    __syncthreads();
+    unsigned long long* coeffs = reinterpret_cast<unsigned long long*>(sh);
+    for (uint32_t s = wave; s < nseg; s += 4u) {
+        const uint4 seg = p.segs[e.z + s];
+        const uint8_t* src = p.buf + (((uint64_t)seg.w << 32) | seg.z);
+        const uint32_t b0 = 8u * seg.x, b1 = b0 + 8u * seg.y;  // the segment's bits of the polynomial's string
+        for (uint32_t c = b0 / w + lane; c * w < b1; c += 64u) {
+            const uint32_t lo = max(c * w, b0), hi = min((c + 1u) * w, b1), nb = hi - lo, rel = lo - b0;  // bits [lo, hi) of coefficient c: nb <= w <= 40
+            uint64_t acc = 0;
+            for (uint32_t y = rel >> 3, k = 0; y <= (rel + nb - 1u) >> 3; y++, k++) acc |= (uint64_t)src[y] << (8u * k);  // (at most 6 bytes, all inside the segment)
+            const uint64_t mask = (1ull << nb) - 1ull, val = (acc >> (rel & 7u)) & mask;
+            if (nb == w) {
+                coeffs[c] = val;
+            } else {
+                const uint32_t sft = lo - c * w;
+                if (!full && (coeffs[c] >> w)) {  // its kept bits are no part of a record
+                    atomicMin(p.err, record_err_key(p, seg, mc, c));
+                    *p.flag = 1u;
+                }
+                atomicAnd(&coeffs[c], ~(mask << sft));
+                atomicOr(&coeffs[c], val << sft);
+            }
+        }
+    }
+    __syncthreads();
+    // the ingest's centred lift (ntt.hip LD_DBGEN): x < half -> x, x >= half -> Q - (p_db - x), as residues mod p and mod b
+    const uint64_t half = p.p_db >> 1;
+    uint32_t lo[8], hi[8];
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        uint64_t v = coeffs[ix_a(tid, r)];
+        if (v >= p.p_db) v %= p.p_db;  // (only after an error was flagged: nothing of this launch is scattered)
+        if (v >= half) {
+            const uint64_t d = p.p_db - v;
+            lo[r] = kP - mod_p(d);
+            hi[r] = kB - mod_b(d);
+        } else {
+            lo[r] = mod_p(v);
+            hi[r] = mod_b(v);
+        }
+    }
+    __syncthreads();  // every coefficient is in registers before the transform reuses the LDS words
+    ntt_forward_block<false>(lo, hi, sh, t.fwd, tid);
+    canonicalize8(lo, hi);
+    uint64_t v[8];
+    pk_pack8(lo, hi, v);
+    pk_store8(dst, tid, v);
+}
+
+}  // namespace
+
+void launch_record_read(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s) {
+    if (p.n_entries == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    if (p.form == DBX_PACKED)
+        hipLaunchKernelGGL((record_read_kernel<DBX_PACKED>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+    else
+        hipLaunchKernelGGL((record_read_kernel<DBX_LIMBS>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+}
+
+void launch_record_update(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s) {
+    if (p.n_entries == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    if (p.form == DBX_PACKED)
+        hipLaunchKernelGGL((record_update_kernel<DBX_PACKED>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+    else
+        hipLaunchKernelGGL((record_update_kernel<DBX_LIMBS>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+}
+
+}  // namespace spiral

@@ -3,6 +3,7 @@
 // process_query_fast, reference src/spiral.cpp:2040-2406, 1584-1629).  Everything is kernel launches on one HIP stream; there is no CPU
 // arithmetic path -- without a device every compute entry point fails.  The calls that carry several servers are in server_lanes.cpp, the
 // stateless host-buffer seams in primitives.cpp; what the three share is declared in server_state.h and defined here.
+#include "records_host.h"
 #include "server_state.h"
 
 // hipGraphs the servers of this process have captured so far (get_option "graph_captures"): shows a replay is not a re-capture
@@ -585,6 +586,125 @@ int spiral_gpu_server_read_db_items_at(spiral_gpu_server* S, void* items, uint32
         if (j >= S->j0 && j < S->j1 && holds_column(S, ii)) sel.push_back(ExportItem{k, (uint32_t)(j - S->j0), ii >> col_g_log(S)});
     }
     return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), 0, 0, 0, &sel, [&](uint64_t pos) { return item_ids[pos]; });
+}
+
+// ---- records (include/spiral_gpu.h "Records"; records_host.h, records.hip) ---------------------------------------------------------------------
+namespace {
+// the layout and this instance's chunk for a record call
+struct RecordCall {
+    spiral_gpu_record_layout l;
+    RecordChunk chunk;
+};
+int record_call(const spiral_gpu_server* S, uint64_t record_bytes, uint32_t instance, RecordCall* rc) {
+    if (record_layout(&S->p, record_bytes, &rc->l)) return -1;
+    return record_chunk(rc->l, record_bytes, instance, &rc->chunk);
+}
+// record r as a piece of this server's image, when the server holds its item (a j-shard: its rows; a column shard: its columns, ii at ii / G)
+bool record_piece(const spiral_gpu_server* S, const RecordCall& rc, uint64_t pos, uint64_t r, RecordPiece* pc) {
+    const uint64_t item = r / rc.l.per_item, j = item / S->s.num_per;
+    const uint32_t ii = (uint32_t)(item % S->s.num_per);
+    if (j < S->j0 || j >= S->j1 || !holds_column(S, ii)) return false;
+    *pc = RecordPiece{pos, (uint32_t)(j - S->j0), ii >> col_g_log(S), (uint32_t)((r % rc.l.per_item) * (rc.l.instances == 1 ? rc.chunk.len : 0)), (uint32_t)rc.chunk.len};
+    return true;
+}
+}  // namespace
+
+int spiral_gpu_record_layout_of(const spiral_gpu_params* p, uint64_t record_bytes, spiral_gpu_record_layout* out) { return record_layout(p, record_bytes, out); }
+
+// Through load_db_items: the records repacked into items on the host, padding zero (not a hot path); bytes that need no repacking go as they are
+int spiral_gpu_server_load_records(spiral_gpu_server* S, const void* records, uint64_t record_bytes, uint32_t instance, uint64_t first_record, uint64_t n_records) {
+    if (!S) return fail("null server");
+    RecordCall rc;
+    if (record_call(S, record_bytes, instance, &rc)) return -1;
+    if (first_record > rc.l.capacity || n_records > rc.l.capacity - first_record)
+        return fail("records [%llu, +%llu) outside the database of %llu", (unsigned long long)first_record, (unsigned long long)n_records, (unsigned long long)rc.l.capacity);
+    if (first_record % rc.l.per_item || n_records % rc.l.per_item)
+        return fail("records [%llu, +%llu) do not start and end at a multiple of the %llu records of an item", (unsigned long long)first_record,
+                    (unsigned long long)n_records, (unsigned long long)rc.l.per_item);
+    if (n_records && !records) return fail("null argument");
+    const uint32_t w = rc.l.coeff_bits, cb = (1ull << w) < S->p.p_db ? w + 1 : w;  // (load_db_items wants a width that holds every value below p_db)
+    const uint64_t first_item = first_record / rc.l.per_item, n_items = n_records / rc.l.per_item;
+    const uint8_t* src = static_cast<const uint8_t*>(records);
+    if (cb == w && rc.l.per_item * record_bytes == rc.l.item_bytes) return spiral_gpu_server_load_db_items(S, src, w, first_item, n_items);
+    const uint64_t pass = std::max<uint64_t>(1, std::min<uint64_t>(options().db_stage_bytes / (1024ull * cb), 1u << 12));  // items repacked at a time
+    std::vector<uint8_t> stream, wide;
+    for (uint64_t done = 0; done < n_items; done += pass) {
+        const uint64_t cnt = std::min(pass, n_items - done);
+        stream.assign((size_t)(cnt * rc.l.item_bytes), 0);
+        for (uint64_t i = 0; i < cnt; i++) {
+            const uint64_t r0 = (done + i) * rc.l.per_item;  // (relative to first_record)
+            if (rc.l.instances == 1)
+                memcpy(stream.data() + i * rc.l.item_bytes, src + r0 * record_bytes, (size_t)(rc.l.per_item * record_bytes));
+            else
+                memcpy(stream.data() + i * rc.l.item_bytes, src + r0 * record_bytes + rc.chunk.first, (size_t)rc.chunk.len);
+        }
+        const uint8_t* items = stream.data();
+        if (cb != w) {
+            wide.assign((size_t)(cnt * 1024ull * cb), 0);
+            widen_coeffs(stream.data(), wide.data(), (size_t)(cnt * 4 * kN), w, cb);
+            items = wide.data();
+        }
+        if (spiral_gpu_server_load_db_items(S, items, cb, first_item + done, cnt)) return -1;
+    }
+    return 0;
+}
+
+// In place, in the image's current form, on the holder's stream: update_db_items' contract at a record's granularity
+int spiral_gpu_server_update_records(spiral_gpu_server* S, const void* records, uint64_t record_bytes, uint32_t instance, const uint64_t* record_ids, uint64_t n) {
+    if (!S) return fail("null server");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db or a lane): update it through the owner");
+    RecordCall rc;
+    if (record_call(S, record_bytes, instance, &rc)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    HIP_OK(hipSetDevice(S->device));
+    if (n == 0) return 0;
+    if (!records || !record_ids) return fail("null argument");
+    if (n > (1ull << 24)) return fail("at most 2^24 records per update");
+    {
+        std::vector<uint64_t> sorted(record_ids, record_ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.back() >= rc.l.capacity)
+            return fail("record id %llu outside the database of %llu records", (unsigned long long)sorted.back(), (unsigned long long)rc.l.capacity);
+        for (uint64_t k = 1; k < n; k++)
+            if (sorted[k] == sorted[k - 1]) return fail("record id %llu given twice", (unsigned long long)sorted[k]);
+    }
+    std::vector<RecordPiece> pieces;
+    RecordPiece pc;
+    for (uint64_t k = 0; k < n; k++)
+        if (record_piece(S, rc, k, record_ids[k], &pc)) pieces.push_back(pc);
+    return update_record_pieces(S->img->upd, S->tb, S->stream, static_cast<const uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, pieces,
+                                S->img->update_target(), S->img->export_source(), [&](uint64_t pos) { return record_ids[pos]; });
+}
+
+// The records back, from the image in its current form: any server that references a loaded image, on its own stream; a shard writes the records it
+// holds and leaves the other bytes of `records` alone
+int spiral_gpu_server_read_records(spiral_gpu_server* S, void* records, uint64_t record_bytes, uint32_t instance, uint64_t first_record, uint64_t n_records) {
+    if (enter(S)) return -1;
+    RecordCall rc;
+    if (record_call(S, record_bytes, instance, &rc)) return -1;
+    if (!records) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    if (first_record > rc.l.capacity || n_records > rc.l.capacity - first_record)
+        return fail("records [%llu, +%llu) outside the database of %llu", (unsigned long long)first_record, (unsigned long long)n_records, (unsigned long long)rc.l.capacity);
+    // whole items of a layout without padding, at a width the export takes: the range export as it is
+    if (rc.l.per_item * record_bytes == rc.l.item_bytes && first_record % rc.l.per_item == 0 && n_records % rc.l.per_item == 0 && (1ull << rc.l.coeff_bits) == S->p.p_db)
+        return spiral_gpu_server_read_db_items(S, records, rc.l.coeff_bits, first_record / rc.l.per_item, n_records / rc.l.per_item);
+    return read_record_pieces(S->xwork, S->tb, S->stream, static_cast<uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, n_records,
+                              [&](uint64_t k, RecordPiece* pc) { return record_piece(S, rc, k, first_record + k, pc); }, S->img->export_source(),
+                              [&](uint64_t pos) { return first_record + pos; });
+}
+int spiral_gpu_server_read_records_at(spiral_gpu_server* S, void* records, uint64_t record_bytes, uint32_t instance, const uint64_t* record_ids, uint64_t n) {
+    if (enter(S)) return -1;
+    RecordCall rc;
+    if (record_call(S, record_bytes, instance, &rc)) return -1;
+    if (n && (!records || !record_ids)) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    for (uint64_t k = 0; k < n; k++)
+        if (record_ids[k] >= rc.l.capacity)
+            return fail("record id %llu outside the database of %llu records", (unsigned long long)record_ids[k], (unsigned long long)rc.l.capacity);
+    return read_record_pieces(S->xwork, S->tb, S->stream, static_cast<uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, n,
+                              [&](uint64_t k, RecordPiece* pc) { return record_piece(S, rc, k, record_ids[k], pc); }, S->img->export_source(),
+                              [&](uint64_t pos) { return record_ids[pos]; });
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, lib, read_args, read_ids, update_args, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
 
 N = 2048
 
@@ -215,6 +215,42 @@ class Server:
         ids = read_ids(ids)
         out = read_args(self.params, coeff_bits, len(ids), 0, out)
         check(lib().spiral_gpu_server_read_db_items_at(self.h, out.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
+        return out
+
+    # ---- records of any byte size (include/spiral_gpu.h "Records"); instance: which chunk of each record this server's image holds ----
+    def load_records(self, records, record_bytes: int, first_record: int = 0, instance: int = 0):
+        """records first_record .. (whole items' worth) from one contiguous byte array, through load_db_items' ingest, padding zero"""
+        lay = record_layout(self.params, record_bytes)
+        records = record_array(records, record_bytes)
+        check(lib().spiral_gpu_server_load_records(self.h, records.ctypes.data_as(C.c_void_p), record_bytes, instance, first_record, records.size // record_bytes))
+        return lay
+
+    def update_records(self, records, record_bytes: int, record_ids, instance: int = 0):
+        """replace the records record_ids[k] <- record k of `records` in place, in the image's current form, on this server's stream; ids distinct;
+        see include/spiral_gpu.h spiral_gpu_server_update_records"""
+        record_layout(self.params, record_bytes)
+        ids = read_ids(record_ids)
+        if np.unique(ids).size != ids.size:
+            raise ValueError("record_ids holds a duplicate id")
+        records = record_array(records, record_bytes, len(ids))
+        check(lib().spiral_gpu_server_update_records(self.h, records.ctypes.data_as(C.c_void_p), record_bytes, instance, _p(ids), len(ids)))
+
+    def read_records(self, record_bytes: int, first_record: int = 0, n_records: int | None = None, out: np.ndarray | None = None, instance: int = 0) -> np.ndarray:
+        """records first_record .. first_record + n_records - 1 (default: to the end) as a uint8 array [n][record_bytes], read from the image in its
+        current form; a shard or an instance server fills in what it holds (pass the same `out` to each)"""
+        lay = record_layout(self.params, record_bytes)
+        if n_records is None:
+            n_records = lay.capacity - first_record
+        out = record_out(record_bytes, n_records, out)
+        check(lib().spiral_gpu_server_read_records(self.h, out.ctypes.data_as(C.c_void_p), record_bytes, instance, first_record, n_records))
+        return out
+
+    def read_records_at(self, record_bytes: int, record_ids, out: np.ndarray | None = None, instance: int = 0) -> np.ndarray:
+        """the records record_ids[k] (any order, duplicates allowed) as a uint8 array [n][record_bytes]; see read_records"""
+        record_layout(self.params, record_bytes)
+        ids = read_ids(record_ids)
+        out = record_out(record_bytes, len(ids), out)
+        check(lib().spiral_gpu_server_read_records_at(self.h, out.ctypes.data_as(C.c_void_p), record_bytes, instance, _p(ids), len(ids)))
         return out
 
     def read_db_item(self, item: int) -> np.ndarray:
