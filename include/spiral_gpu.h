@@ -277,7 +277,7 @@ size_t spiral_gpu_db_items_bytes(const spiral_gpu_params *p, uint32_t out_n, uin
 int spiral_gpu_server_read_db_items(spiral_gpu_server *s, void *items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items);
 int spiral_gpu_server_read_db_items_at(spiral_gpu_server *s, void *items, uint32_t coeff_bits, const uint64_t *item_ids, uint64_t n);
 
-/* ---- Records: byte strings of any size S >= 1, packed into the plaintexts of a base server -------------------------------------------------
+/* ---- Records: byte strings of any size S >= 1, packed into the plaintexts of a base or a SpiralPack server ----------------------------------
  * The layout, stated once; every record call below, and the Python and test code, quote it.
  *
  * For a base parameter set:
@@ -298,7 +298,23 @@ int spiral_gpu_server_read_db_items_at(spiral_gpu_server *s, void *items, uint32
  * power of two), is not part of a record database: every call that would have to read it fails, the message names the first such record (lowest
  * position in the call) and coefficient, and the failing call changes nothing.
  * `instance` (all server calls) selects which chunk of each record this server's image holds: 0 unless instances > 1.  One call is made per
- * instance server on the same buffer, the way shards share one. */
+ * instance server on the same buffer, the way shards share one.
+ *
+ * SpiralPack.  For a SpiralPack parameter set with out_n >= 1 and trials = out_n^2 (the spiral_gpu_pack_server_*_records calls, and a client
+ * session created with out_n >= 1):
+ *   - w = floor(log2 p_db) bits per coefficient and 256 w bytes per polynomial, as above.
+ *   - An item is item_bytes = trials * 256 w bytes: polynomial t of item i is item i of trial t, at byte t * 256 w of the item's stream, bits
+ *     little-endian, exactly as pack_server_read_db_items(trial = t, w) lays out that one polynomial.  The stream is ordered by trial index.
+ *     In a decoded response trial t is output polynomial (r, col) = (t / out_n, t % out_n), i.e. t = r * out_n + col: polynomial t of what
+ *     spiral_gpu_client_decode returns.
+ *   - S <= item_bytes: per_item = floor(item_bytes / S) and instances = 1, record r in item r / per_item at bytes [(r mod per_item) * S, + S).
+ *     Records never straddle items; they may straddle polynomials -- here: trial images -- and end inside a coefficient; the item's tail is
+ *     padding.
+ *   - S > item_bytes: per_item = 1 and instances = ceil(S / item_bytes), refused above 16.  The instances are SpiralPack servers, as
+ *     spiral_gpu_pack_server_answer_batch_instances takes them; chunk f of record r sits at byte 0 of item r of instance f.
+ *   - capacity = 2^(nu1 + nu2) * per_item.
+ * The rules for padding and for a coefficient that is not record data are the ones above, word for word; the message names the record, the trial
+ * and the coefficient.  (p = 256, out_n = 2: 8192-byte items, as the base server's; out_n = 4: 32 768-byte items, 128 records of 256 bytes.) */
 typedef struct spiral_gpu_record_layout {
     uint32_t coeff_bits; /* w */
     uint32_t instances;
@@ -308,6 +324,8 @@ typedef struct spiral_gpu_record_layout {
 } spiral_gpu_record_layout;
 /* host only, no device needed; fails for parameters get_shape refuses, S = 0, or more than 16 instances */
 int spiral_gpu_record_layout_of(const spiral_gpu_params *p, uint64_t record_bytes, spiral_gpu_record_layout *out);
+/* the same for a SpiralPack parameter set, out_n in 1 .. 16 ("SpiralPack" above); host only */
+int spiral_gpu_pack_record_layout_of(const spiral_gpu_params *p, uint32_t out_n, uint64_t record_bytes, spiral_gpu_record_layout *out);
 /* Records first_record .. first_record + n_records - 1 from one contiguous byte array (record k of the call at k * record_bytes), through
  * load_db_items' ingest: the range starts and ends at a multiple of per_item.  The records are repacked into items on the host with zero
  * padding; where per_item * S = item_bytes (and p_db is a power of two) the bytes go through unchanged.  A sharded server keeps what it holds. */
@@ -702,6 +720,28 @@ int spiral_gpu_pack_server_read_db_items(spiral_gpu_pack_server *s, uint32_t tri
                                          uint64_t n_items);
 int spiral_gpu_pack_server_read_db_items_at(spiral_gpu_pack_server *s, uint32_t trial, void *items, uint32_t coeff_bits,
                                             const uint64_t *item_ids, uint64_t n);
+/* Records in the SpiralPack layout ("Records", SpiralPack).  The arguments and the contracts are those of spiral_gpu_server_load_records,
+ * _update_records, _read_records and _read_records_at, `instance` included; there is no `trial` argument: a record names its bytes, the layout
+ * says which trial images hold them.
+ * load_records goes through load_db_items, one ingest per trial.
+ * update_records: in place, in each trial image's CURRENT form (packed or plain, limb planes in the wide, narrow and pair forms), no conversion and
+ * no new epoch; the owner only (a lane is refused), refused inside a stream capture, every check before anything is launched, a failing call leaves
+ * every trial image byte-identical.  ONE upload, ONE read-modify-write launch (one workgroup per touched polynomial = (trial, item)) and ONE scatter
+ * launch, whatever number of trials the records touch.  It waits for this server's stream only when a polynomial had to be read (one that the
+ * call's records cover in part).
+ * read_records / _at: any server that references the image, lanes and shard lanes included; ids need not be distinct; staged in passes of option
+ * db_stage_bytes, one launch and one copy per pass; returns synchronised.
+ * A trial-sharded server (create_sharded) holds every item but only the polynomials of its trials [trial0, trial1): it writes and reads the bytes
+ * that lie in them and skips the rest, so the shards of a database fill one buffer between them, and a record that straddles two shards is updated
+ * by one call on each. */
+int spiral_gpu_pack_server_load_records(spiral_gpu_pack_server *s, const void *records, uint64_t record_bytes, uint32_t instance,
+                                        uint64_t first_record, uint64_t n_records);
+int spiral_gpu_pack_server_update_records(spiral_gpu_pack_server *s, const void *records, uint64_t record_bytes, uint32_t instance,
+                                          const uint64_t *record_ids, uint64_t n);
+int spiral_gpu_pack_server_read_records(spiral_gpu_pack_server *s, void *records, uint64_t record_bytes, uint32_t instance, uint64_t first_record,
+                                        uint64_t n_records);
+int spiral_gpu_pack_server_read_records_at(spiral_gpu_pack_server *s, void *records, uint64_t record_bytes, uint32_t instance,
+                                           const uint64_t *record_ids, uint64_t n);
 /* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv).  A null pointer
  * among those the geometry needs fails before anything is written: the previous public parameters stay (as for spiral_gpu_server_set_pub_params). */
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server *s, const uint64_t *w_left, const uint64_t *w_right,
@@ -1016,15 +1056,15 @@ int spiral_gpu_client_queries(spiral_gpu_client *c, const uint64_t *idx, uint32_
 int spiral_gpu_client_decode(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t *plaintexts);
 int spiral_gpu_client_response_noise(spiral_gpu_client *c, const void *responses, uint32_t n, int form, const uint64_t *expected, uint64_t *stats,
                                      int64_t *errors);
-/* Records ("Records" above; base clients, out_n = 0).
+/* Records ("Records" above; a session with out_n = 0 uses the base layout, one with out_n >= 1 the SpiralPack layout).
  * record_queries: spiral_gpu_client_queries for the items the records live in (record r: item r / per_item), one query per record; one query also
  * serves a record of several instances (the same item index in every instance server).
  * decode_records: `responses` holds n x instances responses laid out [record][instance], in RAW or WIRE form as decode takes them (at most 65535 in
  * all); `records` receives n x record_bytes bytes.  The result is bit for bit what decode gives, followed by packing at w bits and cutting out the
  * record's range (chunk f of a record from response f) -- computed by one workgroup per output polynomial a record touches, which writes the record's
- * bytes straight to the output: a record inside one polynomial costs one of the decode's four convolutions and returns record_bytes bytes instead of
+ * bytes straight to the output: a record inside one polynomial costs one of the decode's four (SpiralPack: out_n^2) convolutions and returns record_bytes bytes instead of
  * 64 KiB of words.  For a p_db that is no power of two the low w bits of a decoded value are packed.  Returns synchronised; every argument is checked
- * first (null pointers, an unknown form, a record size the layout refuses, an id at or above the capacity, a SpiralPack session). */
+ * first (null pointers, an unknown form, a record size the layout refuses, an id at or above the capacity). */
 int spiral_gpu_client_record_queries(spiral_gpu_client *c, uint64_t record_bytes, const uint64_t *record_ids, uint32_t n, int form, void *out,
                                      size_t bytes_each);
 int spiral_gpu_client_decode_records(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t record_bytes,

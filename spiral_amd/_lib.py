@@ -57,7 +57,8 @@ class PackShape(C.Structure):
 
 
 class RecordLayout(C.Structure):
-    """spiral_gpu_record_layout: how records of one byte size lie in the plaintexts of a base parameter set (include/spiral_gpu.h "Records")"""
+    """spiral_gpu_record_layout: how records of one byte size lie in the plaintexts of a base or a SpiralPack parameter set (include/spiral_gpu.h
+    "Records")"""
 
     _fields_ = [("coeff_bits", C.c_uint32), ("instances", C.c_uint32), ("per_item", C.c_uint64), ("item_bytes", C.c_uint64), ("capacity", C.c_uint64)]
 
@@ -124,6 +125,11 @@ PROTOTYPES = {
     "spiral_gpu_server_read_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint64, C.POINTER(RecordLayout)]),
+    "spiral_gpu_pack_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint64, C.POINTER(RecordLayout)]),
+    "spiral_gpu_pack_server_load_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_pack_server_update_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_pack_server_read_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_pack_server_read_records_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_server_load_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_server_update_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_server_read_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
@@ -337,13 +343,18 @@ def db_items_bytes(params: Params, coeff_bits: int, n_items: int, out_n: int = 0
     return n
 
 
-def record_layout(params: Params, record_bytes: int) -> RecordLayout:
-    """the layout of records of record_bytes bytes in the plaintexts of `params` (host only); raises for a size of 0 or one that takes more than 16
-    instances"""
+def record_layout(params: Params, record_bytes: int, out_n: int = 0) -> RecordLayout:
+    """the layout of records of record_bytes bytes in the plaintexts of `params` (out_n = 0: a base server's; out_n >= 1: the out_n^2 trial images of a
+    SpiralPack server's), host only; raises for a size of 0 or one that takes more than 16 instances"""
     if not isinstance(record_bytes, (int, np.integer)) or isinstance(record_bytes, bool) or not 0 <= record_bytes < 2**64:
         raise ValueError(f"record_bytes = {record_bytes!r} is no byte count")
+    if not isinstance(out_n, (int, np.integer)) or isinstance(out_n, bool) or not 0 <= out_n < 2**32:
+        raise ValueError(f"out_n = {out_n!r} is no SpiralPack dimension")
     out = RecordLayout()
-    check(lib().spiral_gpu_record_layout_of(C.byref(params), int(record_bytes), C.byref(out)))
+    if out_n:
+        check(lib().spiral_gpu_pack_record_layout_of(C.byref(params), int(out_n), int(record_bytes), C.byref(out)))
+    else:
+        check(lib().spiral_gpu_record_layout_of(C.byref(params), int(record_bytes), C.byref(out)))
     return out
 
 

@@ -143,7 +143,7 @@ class Client:
         check(lib().spiral_gpu_client_decode(self.h, buf.ctypes.data_as(C.c_void_p), n, _FORMS[form], out.ctypes.data_as(U64P)))
         return out
 
-    # ---- records of any byte size (include/spiral_gpu.h "Records"; base clients) ----
+    # ---- records of any byte size (include/spiral_gpu.h "Records"; the base layout, or SpiralPack's for a session with out_n >= 1) ----
     def record_queries(self, record_ids, record_bytes: int, form="seeded") -> np.ndarray:
         """queries() for the items the records live in: one query per record (it serves every instance of a record of several)"""
         f = _message_form(form)
@@ -158,7 +158,7 @@ class Client:
         bit for bit decode() followed by packing at w bits and cutting out each record's range, done per touched output polynomial on the device"""
         if form not in _FORMS:
             raise ValueError(f"response form {form!r}: 'raw' or 'wire'")
-        lay = record_layout(self.params, record_bytes)
+        lay = record_layout(self.params, record_bytes, self.out_n)
         ids = read_ids(record_ids)
         if form == "raw":
             buf = np.ascontiguousarray(responses, dtype=np.uint64)

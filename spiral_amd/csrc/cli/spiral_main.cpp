@@ -4,6 +4,7 @@
 //   ./spiral <nu1> <nu2> <IDX_TARGET> <dbfile|"a"> [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--seed N] [--batch B] [--instances F]
 //            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch] [--device-client [--output-err F]]
 //   ./spiral <nu1> <nu2> <RECORD> a --record-bytes S [--device-client]      (a record of S bytes: run_records below)
+//   ./spiral <nu1> <nu2> <RECORD> a --high-rate --pack-record-bytes S [--device-client]   (the same on SpiralPack servers: run_pack_records below)
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -462,6 +463,88 @@ static int run_records(const spiral_gpu_params& p, uint64_t record, uint64_t S, 
     return all_ok ? 0 : 2;
 }
 
+// ---- --high-rate --pack-record-bytes S: the records run on SpiralPack servers (include/spiral_gpu.h "Records", SpiralPack) -------------------------
+// run_records' steps and lines with out_n from OUTN: load_records per instance from the same generator, one query for the record's item -- answered by
+// answer_batch_instances when the layout has several instances -- decoded by decode_records (--device-client) or by packing the decoded item's
+// out_n^2 polynomials at w bits in trial order and cutting on the host; then update_records, and the same again.
+static int run_pack_records(const spiral_gpu_params& p, uint32_t out_n, uint64_t record, uint64_t S, uint64_t seed, bool nonoise) {
+    cout << "Using n=" << out_n << endl;
+    spiral_gpu_record_layout lay;
+    GPU_OK(spiral_gpu_pack_record_layout_of(&p, out_n, S, &lay));
+    if (record >= lay.capacity) {
+        fprintf(stderr, "spiral: record %llu out of range (%llu records of %llu bytes)\n", (unsigned long long)record, (unsigned long long)lay.capacity, (unsigned long long)S);
+        return 1;
+    }
+    cout << "Records of " << S << " bytes: " << lay.per_item << " per item of " << lay.item_bytes << " bytes, " << lay.instances << " instance(s), capacity "
+         << lay.capacity << endl;
+    const uint32_t F = lay.instances;
+    std::vector<spiral_gpu_pack_server*> inst(F, nullptr);
+    cout << "starting generation of db" << endl;
+    const uint64_t pass = lay.per_item * 256;  // records generated and loaded at a time
+    std::vector<uint8_t> buf;
+    for (uint32_t f = 0; f < F; f++) GPU_OK(spiral_gpu_pack_server_create(&p, out_n, 0, &inst[f]));
+    for (uint64_t first = 0; first < lay.capacity; first += pass) {
+        const uint64_t n = std::min(pass, lay.capacity - first);
+        buf.resize((size_t)(n * S));
+        for (uint64_t k = 0; k < n; k++) record_bytes_of(0, first + k, S, buf.data() + k * S);
+        for (uint32_t f = 0; f < F; f++) GPU_OK(spiral_gpu_pack_server_load_records(inst[f], buf.data(), S, f, first, n));
+    }
+    cout << "done loading/generating db." << endl;
+    PackClient cl(p, out_n, seed, nonoise);
+    cl.form = g_device_client ? SPIRAL_GPU_FORM_NTT : -1;
+    cl.keygen();
+    cl.gen_pub_params();
+    GPU_OK(spiral_gpu_pack_server_set_pub_params(inst[0], cl.w_left.data(), cl.w_right.data(), cl.v.data(), cl.v_w.data()));
+    const uint64_t item = record / lay.per_item;
+    const size_t resp_words = (size_t)(out_n + 1) * out_n * N;
+    Poly resps((size_t)F * resp_words);
+    std::vector<uint8_t> got((size_t)S), want((size_t)S);
+    bool all_ok = true;
+    for (uint32_t generation = 0; generation < 2; generation++) {
+        if (generation) {  // replace the record in place, in every instance
+            record_bytes_of(1, record, S, want.data());
+            for (uint32_t f = 0; f < F; f++) GPU_OK(spiral_gpu_pack_server_update_records(inst[f], want.data(), S, f, &record, 1));
+        }
+        Query query = cl.query(item);
+        if (g_device_client)  // the same through the record call: one query per record, serving every instance
+            GPU_OK(spiral_gpu_client_record_queries(cl.session.get(), S, &record, 1, SPIRAL_GPU_FORM_NTT, query.cts.data(), query.cts.size() * sizeof(uint64_t)));
+        cout << "Beginning query processing..." << endl;
+        double us[8], item_us = 0;
+        if (F > 1) {
+            const uint64_t* qp[1] = {query.cts.data()};
+            GPU_OK(spiral_gpu_pack_server_answer_batch_instances(&inst[0], 1, inst.data(), F, qp, resps.data(), nullptr, &item_us));
+        } else {
+            GPU_OK(spiral_gpu_pack_server_answer(inst[0], query.cts.data(), resps.data(), nullptr, us));
+        }
+        cout << "Done with query processing!" << endl;
+        if (g_device_client) {
+            GPU_OK(spiral_gpu_client_decode_records(cl.session.get(), resps.data(), 1, SPIRAL_GPU_RESPONSE_RAW, S, &record, got.data()));
+        } else {  // the item's polynomials packed at w bits in trial order -- coefficient k of output polynomial (r, col) at bit ((r * out_n + col) * N + k) * w
+            const uint32_t w = lay.coeff_bits;
+            for (uint32_t f = 0; f < F; f++) {
+                const Poly pt = cl.decode(resps.data() + (size_t)f * resp_words);
+                const uint64_t off = F == 1 ? (record % lay.per_item) * S : 0, first = (uint64_t)f * lay.item_bytes;
+                const uint64_t len = F == 1 ? S : std::min<uint64_t>(S - first, lay.item_bytes);
+                for (uint64_t i = 0; i < len; i++) {
+                    uint32_t byte = 0;
+                    for (uint32_t b = 0; b < 8; b++) {
+                        const uint64_t bit = 8 * (off + i) + b;
+                        byte |= (uint32_t)((pt[bit / w] >> (bit % w)) & 1u) << b;
+                    }
+                    got[(F == 1 ? 0 : first) + i] = (uint8_t)byte;
+                }
+            }
+        }
+        record_bytes_of(generation, record, S, want.data());
+        const bool ok = got == want;
+        all_ok = all_ok && ok;
+        cout << "Record " << record << (generation ? " after update_records" : " as loaded") << ", correct: " << (ok ? 1 : 0) << endl;
+    }
+    cout << "Is correct?: " << (all_ok ? 1 : 0) << endl;
+    for (spiral_gpu_pack_server* sv : inst) spiral_gpu_pack_server_destroy(sv);
+    return all_ok ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
     if (argc < 4) {
         fprintf(stderr, "usage: %s <nu1> <nu2> <IDX_TARGET> [dbfile|a] [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--output-err F] [--seed N]\n", argv[0]);
@@ -476,6 +559,8 @@ int main(int argc, char** argv) {
     bool query_batch = false;  // --query-batch: the batch's queries in one set_query_batch call, its responses in one read
     uint64_t record_bytes = 0;  // --record-bytes S: IDX_TARGET is a record id (run_records above)
     bool record_run = false;
+    uint64_t pack_record_bytes = 0;  // --high-rate --pack-record-bytes S: the same on SpiralPack servers (run_pack_records above)
+    bool pack_record_run = false;
     // as the reference (random_device, src/core.cpp:202; it labels its own generator NOT SECURE): two words of it.
     // This client is a test harness for the server path, not a hardened client.
     std::random_device rd;
@@ -524,6 +609,23 @@ int main(int argc, char** argv) {
             record_run = true;
             if (i + 1 < argc) record_bytes = strtoull(argv[++i], nullptr, 10);
         }
+        // --pack-record-bytes S with --high-rate: the records run on SpiralPack servers, OUTN as out_n
+        if (!strcmp(argv[i], "--pack-record-bytes")) {
+            pack_record_run = true;
+            if (i + 1 < argc) pack_record_bytes = strtoull(argv[++i], nullptr, 10);
+        }
+    }
+    if (pack_record_run) {
+        if (pack_record_bytes == 0) {
+            fprintf(stderr, "spiral: --pack-record-bytes takes a record size of at least 1 byte\n");
+            return 1;
+        }
+        const char* with = !high_rate ? nullptr : record_run ? "--record-bytes" : key_store >= 0 ? "--key-store" : query_batch ? "--query-batch" : instances ? "--instances" : batch ? "--batch" : g_wire ? "--wire-input / --seeded" : nullptr;
+        if (!high_rate || with) {
+            if (!high_rate) fprintf(stderr, "spiral: --pack-record-bytes takes --high-rate (records on a base server: --record-bytes)\n");
+            else fprintf(stderr, "spiral: --pack-record-bytes does not go with %s (a one-query run; the layout chooses its own instances)\n", with);
+            return 1;
+        }
     }
     if (record_run) {
         if (record_bytes == 0) {
@@ -564,7 +666,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: --key-store takes --batch B in 2 .. 8 (not with --instances or --high-rate)\n");
         return 1;
     }
-    if (!record_run && idx_target >= total_n) {
+    if (!record_run && !pack_record_run && idx_target >= total_n) {
         fprintf(stderr, "spiral: IDX_TARGET %llu out of range (n = %llu)\n", (unsigned long long)idx_target, (unsigned long long)total_n);
         return 1;
     }
@@ -593,6 +695,7 @@ int main(int argc, char** argv) {
         return 1;
     }
     if (record_run) return run_records(p, idx_target, record_bytes, seed, nonoise);
+    if (pack_record_run) return run_pack_records(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, pack_record_bytes, seed, nonoise);
     if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch, instances);
     spiral_gpu_shape s;
     GPU_OK(spiral_gpu_get_shape(&p, &s));

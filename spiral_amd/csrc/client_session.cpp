@@ -535,11 +535,10 @@ int spiral_gpu_client_decode(spiral_gpu_client* c, const void* responses, uint32
     return 0;
 }
 
-// ---- records (include/spiral_gpu.h "Records"): a base client's queries for, and decode of, records of any byte size --------------------------------
+// ---- records (include/spiral_gpu.h "Records"): a client's queries for, and decode of, records of any byte size; base and SpiralPack sessions --------------------------------
 namespace {
 int client_record_layout(spiral_gpu_client* c, const char* what, uint64_t record_bytes, const uint64_t* record_ids, uint32_t n, spiral_gpu_record_layout* l) {
-    if (c->out_n) return fail("%s: records are laid out in the plaintexts of a base server, this is a SpiralPack client", what);
-    if (record_layout(&c->p, record_bytes, l)) return -1;
+    if (record_layout(&c->p, record_bytes, l, c->out_n)) return -1;
     for (uint32_t k = 0; k < n; k++)
         if (record_ids[k] >= l->capacity)
             return fail("%s: record id %llu (position %u) outside the database of %llu records", what, (unsigned long long)record_ids[k], k, (unsigned long long)l->capacity);
@@ -579,11 +578,14 @@ int spiral_gpu_client_decode_records(spiral_gpu_client* c, const void* responses
             pieces.push_back(RecordPiece{k, k * l.instances + f, 0u, off, (uint32_t)ch.len});
         }
     std::vector<uint4> entries, segs;
-    record_tables(pieces, 0, pieces.size(), l.coeff_bits, false, entries, segs, nullptr,
-                  [&](uint32_t k) { return (uint64_t)(k / l.instances) * record_bytes + (uint64_t)(k % l.instances) * l.item_bytes; });
+    const auto staged_at = [&](uint32_t k) { return (uint64_t)(k / l.instances) * record_bytes + (uint64_t)(k % l.instances) * l.item_bytes; };
+    if (c->out_n)  // a SpiralPack item's polynomial t is the response's output polynomial (r, col) = (t / out_n, t % out_n)
+        pack_record_tables(pieces, 0, pieces.size(), l.coeff_bits, RecordTrials{c->out_n * c->out_n, 0, c->out_n * c->out_n, 0}, false, entries, segs, staged_at);
+    else
+        record_tables(pieces, 0, pieces.size(), l.coeff_bits, false, entries, segs, nullptr, staged_at);
     for (uint4& e : entries) {  // {response, r | col << 8, first segment, segments}
-        const uint32_t mc = (e.x >> kRecordPolyShift) & 3u;
-        e = make_uint4(e.x & kRecordRowMask, (mc >> 1) | ((mc & 1u) << 8), e.z, e.w);
+        const uint32_t t = c->out_n ? e.y >> kPackRecordTrialShift : (e.x >> kRecordPolyShift) & 3u;
+        e = make_uint4(e.x & kRecordRowMask, (t / c->cols) | ((t % c->cols) << 8), e.z, e.w);
     }
     const bool wire = form == SPIRAL_GPU_RESPONSE_WIRE;
     const size_t wire_each = wire_bytes(&c->p, c->cols);  // a multiple of 256 bytes

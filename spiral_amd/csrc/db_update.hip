@@ -60,11 +60,48 @@ __global__ __launch_bounds__(256) void db_update_kernel(DbUpdateParams p) {
     }
 }
 
+// The trial images of a SpiralPack server in one launch (kernels.h DbUpdateTrialsParams): block = (work entry, 256 slots), an encoded item is one
+// polynomial and its entry names the trial image it goes to.  A kernel and a body of its own: sharing the nibble loop with db_update_kernel through a
+// function changed that kernel's scalar registers (48 -> 44), and no existing kernel changes with this one.
+__global__ __launch_bounds__(256) void db_update_trials_kernel(DbUpdateTrialsParams q) {
+    const DbUpdateParams& p = q.u;
+    if (*p.err) return;
+    const uint32_t z = (blockIdx.x & 7u) * 256u + threadIdx.x, w = blockIdx.x >> 3;
+    if (w < p.n_put) {
+        const uint4 e = p.put[w];  // {encoded polynomial, j, column ii, trial}
+        db1_put_word(p.packed + (size_t)e.w * q.trial_words, z, e.y, e.z, p.num_per, p.dim0, p.enc[(size_t)e.x * kN + z]);
+        return;
+    }
+    if (w - p.n_put >= p.n_pairs) return;
+    const uint4 e = p.pairs[w - p.n_put];  // {column ii | trial << 24, j of the low partner, its encoded polynomial, the high partner's}
+    const uint32_t col = e.x & kPackRecordColMask, kt = e.y, t = kt & 127u;
+    const bool has_lo = e.z != kDbUpdateNone, has_hi = e.w != kDbUpdateNone;
+    const uint64_t v_lo = has_lo ? p.enc[(size_t)e.z * kN + z] : 0, v_hi = has_hi ? p.enc[(size_t)e.w * kN + z] : 0;
+    const bool c8 = p.num_per == 8u;
+    const uint32_t plane = c8 ? 512u : 1024u, nblk = c8 ? 1u : p.num_per >> 4, lane = c8 ? ((t >> 4) & 3u) * 8u + col : ((t >> 4) & 3u) * 16u + (col & 15u);
+    uint64_t* limbs = p.limbs + (size_t)(e.x >> kPackRecordTrialShift) * q.trial_words;
+#pragma unroll
+    for (uint32_t pr = 0; pr < 2; pr++) {
+        const size_t piece = (((size_t)z * nblk + (col >> 4)) * 2u + pr) * (p.dim0 >> 7) + (kt >> 7);  // 7 planes each
+        uint8_t* b = reinterpret_cast<uint8_t*>(limbs) + piece * (7u * plane) + (size_t)lane * 16u + (t & 15u);
+        const uint32_t mod = pr ? kB : kP;
+        uint32_t nib = b[6u * plane];
+        if (has_lo) nib = (nib & 0xF0u) | put_limbs(b, 0, pr ? hi32(v_lo) : lo32(v_lo), mod, plane);
+        if (has_hi) nib = (nib & 0x0Fu) | (put_limbs(b, 1, pr ? hi32(v_hi) : lo32(v_hi), mod, plane) << 4);
+        b[6u * plane] = (uint8_t)nib;
+    }
+}
+
 }  // namespace
 
 void launch_db_update(const DbUpdateParams& p, hipStream_t s) {
     const uint64_t blocks = ((uint64_t)p.n_put + p.n_pairs) * (p.pack ? 1u : 4u) * (kN / 256u);
     if (blocks) hipLaunchKernelGGL(db_update_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, p);
+}
+
+void launch_db_update_trials(const DbUpdateTrialsParams& p, hipStream_t s) {
+    const uint64_t blocks = ((uint64_t)p.u.n_put + p.u.n_pairs) * (kN / 256u);
+    if (blocks) hipLaunchKernelGGL(db_update_trials_kernel, dim3((uint32_t)blocks), dim3(256), 0, s, p);
 }
 
 }  // namespace spiral

@@ -648,6 +648,16 @@ struct DbUpdateParams {
     uint32_t num_per, dim0;  // the image's geometry (dim0: the shard's first dimension on the base path)
 };
 void launch_db_update(const DbUpdateParams& p, hipStream_t s);
+// The same scatter over the trial images of a SpiralPack server in ONE launch (update_records): u.pack = 1, u.packed / u.limbs are trial image 0's and
+// trial t's lies t * trial_words words further on.  An encoded item is one polynomial, and the work entries carry its trial:
+//   put:   {encoded polynomial, j, column ii, trial}
+//   pairs: {column ii | trial << kPackRecordTrialShift, j of the low partner (bit 6 clear), encoded polynomial of the low partner, of the high partner}
+constexpr uint32_t kPackRecordTrialShift = 24, kPackRecordColMask = (1u << kPackRecordTrialShift) - 1u;  // trials <= kMaxPackTrials = 2^8
+struct DbUpdateTrialsParams {
+    DbUpdateParams u;
+    uint64_t trial_words;
+};
+void launch_db_update_trials(const DbUpdateTrialsParams& p, hipStream_t s);
 
 // ---- items out of the image as plaintexts (db_export.hip) -------------------------------------------------------------------
 // The inverse of the ingest (LD_DBGEN / LD_DBGEN1 with ST_DB / ST_DB1): one workgroup per polynomial gathers its 2048 words from the image in the
@@ -707,6 +717,19 @@ struct RecordWorkParams {
 };
 void launch_record_read(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s);
 void launch_record_update(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s);
+// The same on the trial images of a SpiralPack server (include/spiral_gpu.h "Records", SpiralPack): polynomial t of an item is the item's 1 x 1 plaintext
+// in trial t, so a workgroup's polynomial is (trial, j, ii).  r.db is the first trial image the server holds (global trial `trial0`), in the form r.form
+// names (DBX_PACKED, DBX_LIMBS or DBX_LIMBS8), the next ones trial_words words apart.  The tables are RecordWorkParams' with two differences:
+//   entries: {j | kRecordFull, column ii | local trial << kPackRecordTrialShift, first segment, segments}
+//   *err:    ((staged record * trials + global trial) * 2048 + coefficient)
+// update: only touched polynomials have an entry (the scatter writes single polynomials), and entry e's words go to enc + e * 2048.
+struct PackRecordWorkParams {
+    RecordWorkParams r;
+    uint64_t trial_words;
+    uint32_t trials, trial0;
+};
+void launch_pack_record_read(const DeviceTables& t, const PackRecordWorkParams& p, hipStream_t s);
+void launch_pack_record_update(const DeviceTables& t, const PackRecordWorkParams& p, hipStream_t s);
 
 // ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
 // noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]

@@ -4,6 +4,7 @@
 #include "db_image.h"
 #include "key_store.h"
 #include "message.h"
+#include "records_host.h"
 
 using namespace spiral;
 using namespace spiral::host;
@@ -504,6 +505,128 @@ int spiral_gpu_pack_server_read_db_items_at(spiral_gpu_pack_server* S, uint32_t 
     for (uint64_t k = 0; k < n; k++) sel[k] = ExportItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
     return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(trial - S->t0), 0, 0, 0, &sel,
                         [&](uint64_t pos) { return item_ids[pos]; });
+}
+
+// ---- records (include/spiral_gpu.h "Records", SpiralPack; records_host.h, records.hip) -----------------------------------------------------------
+namespace {
+// the layout, this instance's chunk and the trial images of a record call
+struct PkRecordCall {
+    spiral_gpu_record_layout l;
+    RecordChunk chunk;
+    RecordTrials tr;
+};
+int pk_record_call(const spiral_gpu_pack_server* S, uint64_t record_bytes, uint32_t instance, PkRecordCall* rc) {
+    if (record_layout(&S->p, record_bytes, &rc->l, S->out_n)) return -1;
+    rc->tr = RecordTrials{S->s.trials, S->t0, S->nt, S->img->lay.trial_words};
+    return record_chunk(rc->l, record_bytes, instance, &rc->chunk);
+}
+// record r of the call as a piece of its item's stream (every server holds every item; which polynomials it holds, the tables decide)
+RecordPiece pk_record_piece(const spiral_gpu_pack_server* S, const PkRecordCall& rc, uint64_t pos, uint64_t r) {
+    const uint64_t item = r / rc.l.per_item;
+    return RecordPiece{pos, (uint32_t)(item / S->s.num_per), (uint32_t)(item % S->s.num_per),
+                       (uint32_t)((r % rc.l.per_item) * (rc.l.instances == 1 ? rc.chunk.len : 0)), (uint32_t)rc.chunk.len};
+}
+}  // namespace
+
+int spiral_gpu_pack_record_layout_of(const spiral_gpu_params* p, uint32_t out_n, uint64_t record_bytes, spiral_gpu_record_layout* out) {
+    if (p && out && out_n < 1) return fail("out_n out of range");
+    return record_layout(p, record_bytes, out, out_n);
+}
+
+// Through load_db_items, one call per trial this server holds: the records repacked into items on the host, padding zero (not a hot path)
+int spiral_gpu_pack_server_load_records(spiral_gpu_pack_server* S, const void* records, uint64_t record_bytes, uint32_t instance, uint64_t first_record,
+                                        uint64_t n_records) {
+    if (!S) return fail("null server");
+    PkRecordCall rc;
+    if (pk_record_call(S, record_bytes, instance, &rc)) return -1;
+    if (pk_refuse_lane(S, "load")) return -1;
+    if (first_record > rc.l.capacity || n_records > rc.l.capacity - first_record)
+        return fail("records [%llu, +%llu) outside the database of %llu", (unsigned long long)first_record, (unsigned long long)n_records, (unsigned long long)rc.l.capacity);
+    if (first_record % rc.l.per_item || n_records % rc.l.per_item)
+        return fail("records [%llu, +%llu) do not start and end at a multiple of the %llu records of an item", (unsigned long long)first_record,
+                    (unsigned long long)n_records, (unsigned long long)rc.l.per_item);
+    if (n_records && !records) return fail("null argument");
+    const uint32_t w = rc.l.coeff_bits, cb = (1ull << w) < S->p.p_db ? w + 1 : w;  // (load_db_items wants a width that holds every value below p_db)
+    const uint64_t first_item = first_record / rc.l.per_item, n_items = n_records / rc.l.per_item, poly_bytes = 256ull * w;
+    const uint64_t used = rc.l.instances == 1 ? rc.l.per_item * record_bytes : rc.chunk.len;  // bytes of an item's stream that records fill
+    const uint8_t* src = static_cast<const uint8_t*>(records);
+    const uint64_t pass = std::max<uint64_t>(1, std::min<uint64_t>(options().db_stage_bytes / (256ull * cb), 1u << 14));  // polynomials repacked at a time
+    std::vector<uint8_t> stream, wide;
+    for (uint32_t t = S->t0; t < S->t0 + S->nt; t++)
+        for (uint64_t done = 0; done < n_items; done += pass) {
+            const uint64_t cnt = std::min(pass, n_items - done);
+            stream.assign((size_t)(cnt * poly_bytes), 0);
+            const uint64_t lo = t * poly_bytes, hi = std::min(lo + poly_bytes, used);  // the bytes of an item's stream that are trial t's record bytes
+            for (uint64_t i = 0; i < cnt && lo < hi; i++) {
+                const uint64_t r0 = (done + i) * rc.l.per_item;  // (relative to first_record)
+                memcpy(stream.data() + i * poly_bytes, src + r0 * record_bytes + (rc.l.instances == 1 ? 0 : rc.chunk.first) + lo, (size_t)(hi - lo));
+            }
+            const uint8_t* items = stream.data();
+            if (cb != w) {
+                wide.assign((size_t)(cnt * 256ull * cb), 0);
+                widen_coeffs(stream.data(), wide.data(), (size_t)(cnt * kN), w, cb);
+                items = wide.data();
+            }
+            if (spiral_gpu_pack_server_load_db_items(S, t, items, cb, first_item + done, cnt)) return -1;
+        }
+    return 0;
+}
+
+// In place, in each trial image's current form, on the holder's stream: ONE upload, ONE read-modify-write launch and ONE scatter launch over every trial
+// the records touch
+int spiral_gpu_pack_server_update_records(spiral_gpu_pack_server* S, const void* records, uint64_t record_bytes, uint32_t instance, const uint64_t* record_ids,
+                                          uint64_t n) {
+    if (!S) return fail("null server");
+    if (pk_refuse_lane(S, "update")) return -1;
+    PkRecordCall rc;
+    if (pk_record_call(S, record_bytes, instance, &rc)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    HIP_OK(hipSetDevice(S->device));
+    if (n == 0) return 0;
+    if (!records || !record_ids) return fail("null argument");
+    if (n > (1ull << 24)) return fail("at most 2^24 records per update");
+    {
+        std::vector<uint64_t> sorted(record_ids, record_ids + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.back() >= rc.l.capacity)
+            return fail("record id %llu outside the database of %llu records", (unsigned long long)sorted.back(), (unsigned long long)rc.l.capacity);
+        for (uint64_t k = 1; k < n; k++)
+            if (sorted[k] == sorted[k - 1]) return fail("record id %llu given twice", (unsigned long long)sorted[k]);
+    }
+    std::vector<RecordPiece> pieces(n);
+    for (uint64_t k = 0; k < n; k++) pieces[k] = pk_record_piece(S, rc, k, record_ids[k]);
+    return update_record_pieces(S->img->upd, S->tb, S->stream, static_cast<const uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, pieces,
+                                S->img->update_target(0), S->img->export_source(0), [&](uint64_t pos) { return record_ids[pos]; }, rc.tr);
+}
+
+// The records back, from the trial images in their current form: the owner or a lane, on its own stream; a trial shard writes the bytes that lie in its
+// trials' polynomials and leaves the other bytes of `records` alone
+int spiral_gpu_pack_server_read_records(spiral_gpu_pack_server* S, void* records, uint64_t record_bytes, uint32_t instance, uint64_t first_record,
+                                        uint64_t n_records) {
+    if (enter(S)) return -1;
+    PkRecordCall rc;
+    if (pk_record_call(S, record_bytes, instance, &rc)) return -1;
+    if (!records) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    if (first_record > rc.l.capacity || n_records > rc.l.capacity - first_record)
+        return fail("records [%llu, +%llu) outside the database of %llu", (unsigned long long)first_record, (unsigned long long)n_records, (unsigned long long)rc.l.capacity);
+    return read_record_pieces(S->xwork, S->tb, S->stream, static_cast<uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, n_records,
+                              [&](uint64_t k, RecordPiece* pc) { return *pc = pk_record_piece(S, rc, k, first_record + k), true; }, S->img->export_source(0),
+                              [&](uint64_t pos) { return first_record + pos; }, rc.tr);
+}
+int spiral_gpu_pack_server_read_records_at(spiral_gpu_pack_server* S, void* records, uint64_t record_bytes, uint32_t instance, const uint64_t* record_ids,
+                                           uint64_t n) {
+    if (enter(S)) return -1;
+    PkRecordCall rc;
+    if (pk_record_call(S, record_bytes, instance, &rc)) return -1;
+    if (n && (!records || !record_ids)) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    for (uint64_t k = 0; k < n; k++)
+        if (record_ids[k] >= rc.l.capacity)
+            return fail("record id %llu outside the database of %llu records", (unsigned long long)record_ids[k], (unsigned long long)rc.l.capacity);
+    return read_record_pieces(S->xwork, S->tb, S->stream, static_cast<uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, n,
+                              [&](uint64_t k, RecordPiece* pc) { return *pc = pk_record_piece(S, rc, k, record_ids[k]), true; }, S->img->export_source(0),
+                              [&](uint64_t pos) { return record_ids[pos]; }, rc.tr);
 }
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {

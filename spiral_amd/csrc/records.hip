@@ -13,6 +13,11 @@
 // Splice: the segments of a polynomial are disjoint bit ranges (the host refuses duplicate ids), so a coefficient that lies inside one segment is a
 // plain LDS store, and one that two segments share, or that a segment covers in part, is cleared and set with LDS atomics on disjoint bits: the
 // waves take the segments in any order without a barrier between them.
+//
+// SpiralPack (spiral_gpu_pack_server_*_records): the same two bodies with PACK = true.  An item's polynomial t is its 1 x 1 plaintext in trial image t,
+// so the entry names the trial and the kernel takes the trial stride (kernels.h PackRecordWorkParams); image_word<FORM, true> reads the packed or plain
+// layout, the limb planes and the 8-column pair form.  The update has entries for touched polynomials only, and db_update_trials_kernel scatters them
+// into every touched trial image in one launch.  The base kernels keep their names, arguments and resources (profiles/pack_records_resource_usage.txt).
 #include "db_plain_device.h"
 #include "kernels.h"
 #include "ntt_device.h"
@@ -21,19 +26,36 @@ namespace spiral {
 
 namespace {
 
-__device__ __forceinline__ unsigned long long record_err_key(const RecordWorkParams& p, uint4 seg, uint32_t mc, uint32_t coeff) {
+// the error word's key of coefficient `coeff` of polynomial `poly` of the `polys` an item has, in the staged record the segment belongs to
+__device__ __forceinline__ unsigned long long record_err_key(const RecordWorkParams& p, uint4 seg, uint32_t poly, uint32_t polys, uint32_t coeff) {
     const uint64_t k = (((uint64_t)seg.w << 32) | seg.z) / p.stride;
-    return (k * 4u + mc) * kN + coeff;
+    return (k * polys + poly) * kN + coeff;
 }
 
-template <uint32_t FORM>
-__global__ __launch_bounds__(256, 6) void record_read_kernel(Tables t, RecordWorkParams p) {
-    __shared__ uint64_t sh[kLdsWords];
+// Which polynomial a workgroup has.  A base image (PACK = false): polynomial mc of the 4 of item (j, ii).  A SpiralPack server (PACK = true): the one
+// polynomial of item (j, ii) in the trial image the entry names; `poly` is the global trial, as the error word counts it.
+struct RecordPoly {
+    const uint64_t* db;
+    uint32_t j, ii, mc, poly, polys;
+};
+template <bool PACK>
+__device__ __forceinline__ RecordPoly record_poly(const RecordWorkParams& p, uint4 e, uint32_t mc, uint64_t trial_words, uint32_t trials, uint32_t trial0) {
+    if constexpr (PACK) {
+        const uint32_t tl = e.y >> kPackRecordTrialShift;
+        return RecordPoly{p.db + (size_t)tl * trial_words, e.x & kRecordRowMask, e.y & kPackRecordColMask, 0u, trial0 + tl, trials};
+    } else {
+        return RecordPoly{p.db, e.x & kRecordRowMask, e.y, mc, mc, 4u};
+    }
+}
+
+template <uint32_t FORM, bool PACK>
+__device__ __forceinline__ void record_read_body(const Tables& t, const RecordWorkParams& p, uint64_t* sh, uint64_t trial_words, uint32_t trials, uint32_t trial0) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint4 e = p.entries[blockIdx.x];
-    const uint32_t j = e.x & kRecordRowMask, mc = (e.x >> kRecordPolyShift) & 3u, nseg = e.w, w = p.w;
-    const uint32_t bad = image_poly_plain<FORM, false>(p.db, j, e.y, mc, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
-    if (bad < kN) atomicMin(p.err, record_err_key(p, p.segs[e.z], mc, bad));
+    const RecordPoly q = record_poly<PACK>(p, e, (e.x >> kRecordPolyShift) & 3u, trial_words, trials, trial0);
+    const uint32_t mc = q.poly, polys = q.polys, nseg = e.w, w = p.w;
+    const uint32_t bad = image_poly_plain<FORM, PACK>(q.db, q.j, q.ii, q.mc, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+    if (bad < kN) atomicMin(p.err, record_err_key(p, p.segs[e.z], mc, polys, bad));
     __syncthreads();
     for (uint32_t s = wave; s < nseg; s += 4u) {
         const uint4 seg = p.segs[e.z + s];
@@ -42,11 +64,11 @@ __global__ __launch_bounds__(256, 6) void record_read_kernel(Tables t, RecordWor
             const uint32_t bit = 8u * (seg.x + i);
             uint32_t c = bit / w, filled = w - (bit - c * w);
             uint64_t v = sh[c];
-            if (v >> w) atomicMin(p.err, record_err_key(p, seg, mc, c));
+            if (v >> w) atomicMin(p.err, record_err_key(p, seg, mc, polys, c));
             uint64_t acc = v >> (w - filled);
             while (filled < 8u) {  // (the segment ends inside the polynomial's 2048 w bits: c + 1 < 2048 here)
                 v = sh[++c];
-                if (v >> w) atomicMin(p.err, record_err_key(p, seg, mc, c));
+                if (v >> w) atomicMin(p.err, record_err_key(p, seg, mc, polys, c));
                 acc |= v << filled;
                 filled += w;
             }
@@ -55,17 +77,17 @@ __global__ __launch_bounds__(256, 6) void record_read_kernel(Tables t, RecordWor
     }
 }
 
-template <uint32_t FORM>
-__global__ __launch_bounds__(256, 4) void record_update_kernel(Tables t, RecordWorkParams p) {
-    __shared__ uint64_t sh[kLdsWords];
+template <uint32_t FORM, bool PACK>
+__device__ __forceinline__ void record_update_body(const Tables& t, const RecordWorkParams& p, uint64_t* sh, uint64_t trial_words, uint32_t trials, uint32_t trial0) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint4 e = p.entries[blockIdx.x];
-    const uint32_t j = e.x & kRecordRowMask, mc = blockIdx.x & 3u, nseg = e.w, w = p.w;
+    const RecordPoly q = record_poly<PACK>(p, e, blockIdx.x & 3u, trial_words, trials, trial0);
+    const uint32_t mc = q.poly, polys = q.polys, nseg = e.w, w = p.w;
     uint64_t* dst = p.enc + (size_t)blockIdx.x * kN;
-    if (nseg == 0) {  // no record touches it: the image's words as they are
+    if (nseg == 0) {  // no record touches it: the image's words as they are (a base item's other polynomials)
         uint64_t v[8];
 #pragma unroll
-        for (int r = 0; r < 8; r++) v[r] = image_word<FORM, false>(p.db, pk_pos_tk(tid, r), j, e.y, mc, p.num_per, p.dim0);
+        for (int r = 0; r < 8; r++) v[r] = image_word<FORM, PACK>(q.db, pk_pos_tk(tid, r), q.j, q.ii, q.mc, p.num_per, p.dim0);
         pk_store8(dst, tid, v);
         return;
     }
@@ -74,9 +96,9 @@ __global__ __launch_bounds__(256, 4) void record_update_kernel(Tables t, RecordW
 #pragma unroll
         for (int r = 0; r < 8; r++) sh[ix_a(tid, r)] = 0;
     } else {
-        const uint32_t bad = image_poly_plain<FORM, false>(p.db, j, e.y, mc, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+        const uint32_t bad = image_poly_plain<FORM, PACK>(q.db, q.j, q.ii, q.mc, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
         if (bad < kN) {
-            atomicMin(p.err, record_err_key(p, p.segs[e.z], mc, bad));
+            atomicMin(p.err, record_err_key(p, p.segs[e.z], mc, polys, bad));
             *p.flag = 1u;
         }
     }
@@ -96,7 +118,7 @@ __global__ __launch_bounds__(256, 4) void record_update_kernel(Tables t, RecordW
             } else {
                 const uint32_t sft = lo - c * w;
                 if (!full && (coeffs[c] >> w)) {  // its kept bits are no part of a record
-                    atomicMin(p.err, record_err_key(p, seg, mc, c));
+                    atomicMin(p.err, record_err_key(p, seg, mc, polys, c));
                     *p.flag = 1u;
                 }
                 atomicAnd(&coeffs[c], ~(mask << sft));
@@ -129,6 +151,28 @@ __global__ __launch_bounds__(256, 4) void record_update_kernel(Tables t, RecordW
     pk_store8(dst, tid, v);
 }
 
+// the kernels: the bodies above on a base image and on the trial images of a SpiralPack server
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 6) void record_read_kernel(Tables t, RecordWorkParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    record_read_body<FORM, false>(t, p, sh, 0, 4u, 0);
+}
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 4) void record_update_kernel(Tables t, RecordWorkParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    record_update_body<FORM, false>(t, p, sh, 0, 4u, 0);
+}
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 6) void pack_record_read_kernel(Tables t, PackRecordWorkParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    record_read_body<FORM, true>(t, p.r, sh, p.trial_words, p.trials, p.trial0);
+}
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 4) void pack_record_update_kernel(Tables t, PackRecordWorkParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    record_update_body<FORM, true>(t, p.r, sh, p.trial_words, p.trials, p.trial0);
+}
+
 }  // namespace
 
 void launch_record_read(const DeviceTables& t, const RecordWorkParams& p, hipStream_t s) {
@@ -147,6 +191,30 @@ void launch_record_update(const DeviceTables& t, const RecordWorkParams& p, hipS
         hipLaunchKernelGGL((record_update_kernel<DBX_PACKED>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
     else
         hipLaunchKernelGGL((record_update_kernel<DBX_LIMBS>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+}
+
+void launch_pack_record_read(const DeviceTables& t, const PackRecordWorkParams& p, hipStream_t s) {
+    if (p.r.n_entries == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    const dim3 grid(p.r.n_entries), block(256);
+    if (p.r.form == DBX_PACKED)
+        hipLaunchKernelGGL((pack_record_read_kernel<DBX_PACKED>), grid, block, 0, s, tb, p);
+    else if (p.r.form == DBX_LIMBS)
+        hipLaunchKernelGGL((pack_record_read_kernel<DBX_LIMBS>), grid, block, 0, s, tb, p);
+    else
+        hipLaunchKernelGGL((pack_record_read_kernel<DBX_LIMBS8>), grid, block, 0, s, tb, p);
+}
+
+void launch_pack_record_update(const DeviceTables& t, const PackRecordWorkParams& p, hipStream_t s) {
+    if (p.r.n_entries == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    const dim3 grid(p.r.n_entries), block(256);
+    if (p.r.form == DBX_PACKED)
+        hipLaunchKernelGGL((pack_record_update_kernel<DBX_PACKED>), grid, block, 0, s, tb, p);
+    else if (p.r.form == DBX_LIMBS)
+        hipLaunchKernelGGL((pack_record_update_kernel<DBX_LIMBS>), grid, block, 0, s, tb, p);
+    else
+        hipLaunchKernelGGL((pack_record_update_kernel<DBX_LIMBS8>), grid, block, 0, s, tb, p);
 }
 
 }  // namespace spiral

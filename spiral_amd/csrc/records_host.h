@@ -6,8 +6,11 @@
 namespace spiral {
 namespace host {
 
-inline int record_layout(const spiral_gpu_params* p, uint64_t record_bytes, spiral_gpu_record_layout* out) {
+// out_n = 0: a base parameter set (4 polynomials per item); out_n >= 1: SpiralPack, out_n^2 polynomials per item, one per trial image
+inline int record_layout(const spiral_gpu_params* p, uint64_t record_bytes, spiral_gpu_record_layout* out, uint32_t out_n = 0) {
     if (!p || !out) return fail("null argument");
+    if (out_n > 16) return fail("out_n out of range");
+    if (out_n && (p->nu1 < 1 || p->nu2 < 1)) return fail("SpiralPack needs nu1 >= 1 and nu2 >= 1");
     spiral_gpu_shape s;
     spiral_gpu_params q = *p;
     q.direct_upload = 1;  // the layout does not depend on how the query arrives: no query-size rule here
@@ -15,7 +18,7 @@ inline int record_layout(const spiral_gpu_params* p, uint64_t record_bytes, spir
     if (record_bytes < 1) return fail("a record has at least one byte");
     uint32_t w = 0;
     while ((2ull << w) <= p->p_db) w++;  // floor(log2 p_db)
-    const uint64_t item_bytes = 1024ull * w;
+    const uint64_t item_bytes = (out_n ? (uint64_t)out_n * out_n : 4ull) * 256u * w;
     spiral_gpu_record_layout l{};
     l.coeff_bits = w;
     l.item_bytes = item_bytes;
@@ -111,9 +114,81 @@ inline bool record_tables(const std::vector<RecordPiece>& pieces, size_t k0, siz
     return record_tables(pieces, k0, cnt, w, all_polys, entries, segs, items, [&](uint32_t k) { return (uint64_t)k * stride; });
 }
 
-// the failure a record kernel reports through its error word (kernels.h RecordWorkParams)
+// The trial images a SpiralPack record call works on (include/spiral_gpu.h "Records", SpiralPack): an item's polynomial t is its plaintext in trial t,
+// the server holds the global trials [t0, t0 + nt) back to back, trial_words words apart.  trials = 0: a base image.
+struct RecordTrials {
+    uint32_t trials = 0, t0 = 0, nt = 0;
+    uint64_t trial_words = 0;
+};
+// record_tables for trial images (kernels.h PackRecordWorkParams): one entry per polynomial that a piece touches AND the server holds, in (j, ii, trial)
+// order, kRecordFull (update) where the segments cover it.  Polynomials nothing touches have no entry: the scatter writes single polynomials.
+template <class BufOf>
+inline bool pack_record_tables(const std::vector<RecordPiece>& pieces, size_t k0, size_t cnt, uint32_t w, const RecordTrials& tr, bool update,
+                               std::vector<uint4>& entries, std::vector<uint4>& segs, BufOf buf_of) {
+    const uint32_t poly_bytes = 256u * w;
+    struct Touch {
+        uint64_t item;
+        uint32_t t, k;
+    };
+    std::vector<Touch> touch;
+    for (size_t k = 0; k < cnt; k++) {
+        const RecordPiece& pc = pieces[k0 + k];
+        if (pc.len == 0) continue;
+        const uint32_t ta = std::max(pc.off / poly_bytes, tr.t0), tb = std::min((pc.off + pc.len - 1u) / poly_bytes + 1u, tr.t0 + tr.nt);
+        for (uint32_t t = ta; t < tb; t++) touch.push_back(Touch{((uint64_t)pc.j << 32) | pc.ii, t, (uint32_t)k});
+    }
+    std::stable_sort(touch.begin(), touch.end(), [](const Touch& a, const Touch& b) { return a.item != b.item ? a.item < b.item : a.t < b.t; });
+    bool gathers = false;
+    for (size_t a = 0; a < touch.size();) {
+        const uint32_t t = touch[a].t, p0 = t * poly_bytes, p1 = p0 + poly_bytes, seg0 = (uint32_t)segs.size();
+        uint64_t covered = 0;
+        size_t b = a;
+        for (; b < touch.size() && touch[b].item == touch[a].item && touch[b].t == t; b++) {
+            const RecordPiece& pc = pieces[k0 + touch[b].k];
+            const uint32_t lo = std::max(pc.off, p0), hi = std::min(pc.off + pc.len, p1);
+            const uint64_t buf = buf_of(touch[b].k) + (lo - pc.off);
+            segs.push_back(make_uint4(lo - p0, hi - lo, (uint32_t)buf, (uint32_t)(buf >> 32)));
+            covered += hi - lo;
+        }
+        const bool full = update && covered == poly_bytes;
+        if (!full) gathers = true;
+        entries.push_back(make_uint4((uint32_t)(touch[a].item >> 32) | (full ? kRecordFull : 0u), (uint32_t)touch[a].item | ((t - tr.t0) << kPackRecordTrialShift), seg0,
+                                     (uint32_t)segs.size() - seg0));
+        a = b;
+    }
+    return gathers;
+}
+// the scatter's work entries (kernels.h DbUpdateTrialsParams) for the entries of pack_record_tables, entry e = encoded polynomial e
+inline void pack_update_entries(const std::vector<uint4>& entries, const UpdateImage& img, std::vector<uint4>& put, std::vector<uint4>& pairs) {
+    const size_t n = entries.size();
+    auto row = [&](size_t e) { return entries[e].x & kRecordRowMask; };
+    if (img.packed) {
+        put.reserve(n);
+        for (size_t e = 0; e < n; e++) put.push_back(make_uint4((uint32_t)e, row(e), entries[e].y & kPackRecordColMask, entries[e].y >> kPackRecordTrialShift));
+    }
+    if (img.limbs) {
+        std::vector<std::pair<uint64_t, uint32_t>> order(n);  // (column | trial, j of the low partner) -> entry
+        for (size_t e = 0; e < n; e++) order[e] = {((uint64_t)entries[e].y << 32) | (row(e) & ~64u), (uint32_t)e};
+        std::sort(order.begin(), order.end());
+        for (size_t k = 0; k < n; k++) {
+            const uint64_t key = order[k].first;
+            if (pairs.empty() || (((uint64_t)pairs.back().x << 32) | pairs.back().y) != key)
+                pairs.push_back(make_uint4((uint32_t)(key >> 32), (uint32_t)key, kDbUpdateNone, kDbUpdateNone));
+            const uint32_t e = order[k].second;
+            (row(e) & 64u ? pairs.back().w : pairs.back().z) = e;
+        }
+    }
+}
+
+// the failure a record kernel reports through its error word (kernels.h RecordWorkParams, PackRecordWorkParams)
 template <class RecordOf>
-inline int record_image_error(unsigned long long err, RecordOf record_of) {
+inline int record_image_error(unsigned long long err, RecordOf record_of, const RecordTrials& tr = RecordTrials{}) {
+    if (tr.trials) {
+        const uint64_t poly = err / kN;
+        return fail("the image holds no record data at record %llu (trial %u, coefficient %u is no plaintext value below 2^coeff_bits): not a record "
+                    "database (fill_db_random, a load_db of arbitrary words, or items loaded with larger coefficients)",
+                    (unsigned long long)record_of(poly / tr.trials), (uint32_t)(poly % tr.trials), (uint32_t)(err % kN));
+    }
     const uint64_t poly = err / kN, k = poly / 4;
     return fail("the image holds no record data at record %llu (polynomial %u, coefficient %u is no plaintext value below 2^coeff_bits): not a record "
                 "database (fill_db_random, a load_db of arbitrary words, or items loaded with larger coefficients)",
@@ -126,7 +201,8 @@ inline int record_image_error(unsigned long long err, RecordOf record_of) {
 // error word, and a coefficient that is no record data fails the call with the image untouched (the scatter skips everything).
 template <class RecordOf>
 inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream_t st, const uint8_t* records, uint64_t record_bytes, const RecordChunk& chunk,
-                                uint32_t w, uint64_t p_db, const std::vector<RecordPiece>& pieces, const UpdateImage& img, const ExportImage& src, RecordOf record_of) {
+                                uint32_t w, uint64_t p_db, const std::vector<RecordPiece>& pieces, const UpdateImage& img, const ExportImage& src, RecordOf record_of,
+                                const RecordTrials& tr = RecordTrials{}) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return fail("update_records cannot be called while the server's stream is being captured");
@@ -135,14 +211,21 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
     const size_t n = pieces.size();
     std::vector<uint4> entries, segs, put, pairs;
     std::vector<UpdateItem> items;
-    const bool gathers = record_tables(pieces, 0, n, stride, w, true, entries, segs, &items);
-    update_entries(items, img, put, pairs);
+    bool gathers;
+    if (tr.trials) {
+        gathers = pack_record_tables(pieces, 0, n, w, tr, true, entries, segs, [&](uint32_t k) { return (uint64_t)k * stride; });
+        if (entries.empty()) return 0;  // (a trial shard that holds none of the touched polynomials)
+        pack_update_entries(entries, img, put, pairs);
+    } else {
+        gathers = record_tables(pieces, 0, n, stride, w, true, entries, segs, &items);
+        update_entries(items, img, put, pairs);
+    }
     // one buffer: [flag, error word][entries][put][pairs][segments][record bytes] ++ (device only) [encoded polynomials]
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_ent = 16, o_put = o_ent + entries.size() * sizeof(uint4), o_pairs = o_put + put.size() * sizeof(uint4);
     const size_t o_segs = o_pairs + pairs.size() * sizeof(uint4), o_rec = o_segs + segs.size() * sizeof(uint4);
     const size_t up_bytes = up16(o_rec + n * stride + 16), dev_bytes = up_bytes + entries.size() * kPolyBytes;
-    if (update_reserve(W, items.size(), up_bytes, dev_bytes)) return -1;
+    if (update_reserve(W, tr.trials ? entries.size() : items.size(), up_bytes, dev_bytes)) return -1;
     memset(W.host, 0, 8);
     memset(W.host + 8, 0xFF, 8);  // the error word: ~0 = every coefficient read so far is record data
     memcpy(W.host + o_ent, entries.data(), entries.size() * sizeof(uint4));
@@ -167,7 +250,10 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
     rp.w = w;
     rp.stride = stride;
     rp.p_db = p_db;
-    launch_record_update(tb, rp, st);
+    if (tr.trials)
+        launch_pack_record_update(tb, PackRecordWorkParams{rp, tr.trial_words, tr.trials, tr.t0}, st);
+    else
+        launch_record_update(tb, rp, st);
     DbUpdateParams up{};
     up.enc = rp.enc;
     up.err = rp.flag;
@@ -177,10 +263,13 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
     up.pairs = reinterpret_cast<const uint4*>(d + o_pairs);
     up.n_put = (uint32_t)put.size();
     up.n_pairs = (uint32_t)pairs.size();
-    up.pack = 0;
+    up.pack = img.pack;
     up.num_per = img.num_per;
     up.dim0 = img.dim0;
-    launch_db_update(up, st);
+    if (tr.trials)
+        launch_db_update_trials(DbUpdateTrialsParams{up, tr.trial_words}, st);
+    else
+        launch_db_update(up, st);
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(W.done, st));
     W.pending = true;
@@ -188,7 +277,7 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
     unsigned long long err = 0;
     HIP_OK(hipMemcpyAsync(&err, d + 8, sizeof(err), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
-    if (err != ~0ull) return record_image_error(err, [&](uint64_t k) { return record_of(pieces[k].pos); });
+    if (err != ~0ull) return record_image_error(err, [&](uint64_t k) { return record_of(pieces[k].pos); }, tr);
     return 0;
 }
 
@@ -199,7 +288,7 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
 // position.  Returns after `st` is synchronised.
 template <class PieceAt, class RecordOf>
 inline int read_record_pieces(ExportWork& W, const DeviceTables& tb, hipStream_t st, uint8_t* records, uint64_t record_bytes, const RecordChunk& chunk, uint32_t w,
-                              uint64_t p_db, uint64_t n, PieceAt piece_at, const ExportImage& src, RecordOf record_of) {
+                              uint64_t p_db, uint64_t n, PieceAt piece_at, const ExportImage& src, RecordOf record_of, const RecordTrials& tr = RecordTrials{}) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return fail("read_records cannot be called while the server's stream is being captured");
@@ -219,7 +308,10 @@ inline int read_record_pieces(ExportWork& W, const DeviceTables& tb, hipStream_t
         if (cnt == 0) continue;
         entries.clear();
         segs.clear();
-        record_tables(pieces, 0, cnt, stride, w, false, entries, segs, nullptr);
+        if (tr.trials)
+            pack_record_tables(pieces, 0, cnt, w, tr, false, entries, segs, [&](uint32_t i) { return (uint64_t)i * stride; });
+        else
+            record_tables(pieces, 0, cnt, stride, w, false, entries, segs, nullptr);
         auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
         const size_t o_ent = 16, o_segs = o_ent + entries.size() * sizeof(uint4), o_stage = up16(o_segs + segs.size() * sizeof(uint4));
         const size_t dev_bytes = o_stage + cnt * stride;
@@ -260,14 +352,25 @@ inline int read_record_pieces(ExportWork& W, const DeviceTables& tb, hipStream_t
         rp.w = w;
         rp.stride = stride;
         rp.p_db = p_db;
-        launch_record_read(tb, rp, st);
+        if (tr.trials)
+            launch_pack_record_read(tb, PackRecordWorkParams{rp, tr.trial_words, tr.trials, tr.t0}, st);
+        else
+            launch_record_read(tb, rp, st);
         HIP_OK(hipGetLastError());
         unsigned long long err = ~0ull;
         HIP_OK(hipMemcpyAsync(W.host, rp.buf, cnt * stride, hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(&err, d, sizeof(err), hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        if (err != ~0ull) return record_image_error(err, [&](uint64_t i) { return record_of(pieces[i].pos); });
-        for (size_t i = 0; i < cnt; i++) memcpy(records + pieces[i].pos * record_bytes + chunk.first, W.host + i * stride, stride);
+        if (err != ~0ull) return record_image_error(err, [&](uint64_t i) { return record_of(pieces[i].pos); }, tr);
+        for (size_t i = 0; i < cnt; i++) {
+            uint64_t lo = 0, hi = stride;  // the piece's bytes this image holds: all of them, or those in the polynomials of a trial shard's trials
+            if (tr.trials) {
+                const uint64_t off = pieces[i].off, h0 = (uint64_t)tr.t0 * 256u * w, h1 = (uint64_t)(tr.t0 + tr.nt) * 256u * w;
+                lo = std::min(std::max(off, h0), off + stride) - off;
+                hi = std::max(std::min(off + stride, h1), off + lo) - off;
+            }
+            memcpy(records + pieces[i].pos * record_bytes + chunk.first + lo, W.host + i * stride + lo, (size_t)(hi - lo));
+        }
     }
     return 0;
 }

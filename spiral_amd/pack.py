@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, PackShape, Params, check, lib, read_args, read_ids, update_args, wire_bytes
+from ._lib import U64P, PackShape, Params, check, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
 
 N = 2048
 PACK_STAGE_NAMES = ["expansion_us", "conversion_us", "first_dim_us", "folding_us", "packing_us", "sweep_kernels_us", "total_us", "reserved"]
@@ -138,6 +138,42 @@ class PackServer:
         ids = read_ids(ids)
         out = read_args(self.params, coeff_bits, len(ids), self.out_n, out)
         check(lib().spiral_gpu_pack_server_read_db_items_at(self.h, trial, out.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
+        return out
+
+    # ---- records of any byte size (include/spiral_gpu.h "Records", SpiralPack): no trial argument, the layout names the trial images ----
+    def load_records(self, records, record_bytes: int, first_record: int = 0, instance: int = 0):
+        """records first_record .. (whole items' worth) from one contiguous byte array, through load_db_items' ingest of every trial, padding zero"""
+        lay = record_layout(self.params, record_bytes, self.out_n)
+        records = record_array(records, record_bytes)
+        check(lib().spiral_gpu_pack_server_load_records(self.h, records.ctypes.data_as(C.c_void_p), record_bytes, instance, first_record, records.size // record_bytes))
+        return lay
+
+    def update_records(self, records, record_bytes: int, record_ids, instance: int = 0):
+        """replace the records record_ids[k] <- record k of `records` in place, in every touched trial image's current form, on this server's stream;
+        ids distinct; see include/spiral_gpu.h spiral_gpu_pack_server_update_records"""
+        record_layout(self.params, record_bytes, self.out_n)
+        ids = read_ids(record_ids)
+        if np.unique(ids).size != ids.size:
+            raise ValueError("record_ids holds a duplicate id")
+        records = record_array(records, record_bytes, len(ids))
+        check(lib().spiral_gpu_pack_server_update_records(self.h, records.ctypes.data_as(C.c_void_p), record_bytes, instance, _p(ids), len(ids)))
+
+    def read_records(self, record_bytes: int, first_record: int = 0, n_records=None, out=None, instance: int = 0) -> np.ndarray:
+        """records first_record .. first_record + n_records - 1 (default: to the end) as a uint8 array [n][record_bytes], read from the trial images
+        in their current form; a trial shard or an instance server fills in what it holds (pass the same `out` to each)"""
+        lay = record_layout(self.params, record_bytes, self.out_n)
+        if n_records is None:
+            n_records = lay.capacity - first_record
+        out = record_out(record_bytes, n_records, out)
+        check(lib().spiral_gpu_pack_server_read_records(self.h, out.ctypes.data_as(C.c_void_p), record_bytes, instance, first_record, n_records))
+        return out
+
+    def read_records_at(self, record_bytes: int, record_ids, out=None, instance: int = 0) -> np.ndarray:
+        """the records record_ids[k] (any order, duplicates allowed) as a uint8 array [n][record_bytes]; see read_records"""
+        record_layout(self.params, record_bytes, self.out_n)
+        ids = read_ids(record_ids)
+        out = record_out(record_bytes, len(ids), out)
+        check(lib().spiral_gpu_pack_server_read_records_at(self.h, out.ctypes.data_as(C.c_void_p), record_bytes, instance, _p(ids), len(ids)))
         return out
 
     def read_acc(self, trial: int) -> np.ndarray:
