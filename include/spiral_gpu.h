@@ -106,6 +106,7 @@ int spiral_gpu_column_shard_has_limb_form(const spiral_gpu_params *p, uint32_t n
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  *   "key_binds"       (get only) the lanes the bind_keys calls of this process have copied keys into (a lane that held them already is not counted)
  *   "db_export_ns"    (get only) device nanoseconds of the launches of this process's last read_db_items / read_db_items_at call, its copies excluded
+ *   "db_fingerprint_ns" (get only) the same of its last fingerprint_items / fingerprint_items_at call
  *   "mfma_sweeps"     (get only) the matrix-core sweep launches (csrc/sweep_mfma.hip) this process has made: every call, batch or stage function whose
  *                     first-dimension pass took the limb-plane form adds one per pass; a replayed hipGraph adds nothing.  What tells the
  *                     matrix-core form from the vector-ALU one, whose results are the same
@@ -276,6 +277,50 @@ size_t spiral_gpu_db_items_bytes(const spiral_gpu_params *p, uint32_t out_n, uin
  * Before any launch: null pointers, a range outside the database, coeff_bits outside 1..64 or 2^coeff_bits < p_db (64 always passes). */
 int spiral_gpu_server_read_db_items(spiral_gpu_server *s, void *items, uint32_t coeff_bits, uint64_t first_item, uint64_t n_items);
 int spiral_gpu_server_read_db_items_at(spiral_gpu_server *s, void *items, uint32_t coeff_bits, const uint64_t *item_ids, uint64_t n);
+
+/* ---- Fingerprints: a database image compared with its source, or with another image, in 8 bytes per item or 8 bytes in all -------------------
+ * The definition, stated once; the device kernels, the host function, and the Python and test code quote it.
+ *
+ *   - P = 2^61 - 1.  Every fingerprint is returned fully reduced, in [0, P - 1].
+ *   - A key is two words: r = 2 + key[0] mod (P - 3), s = 2 + key[1] mod (P - 3), both in [2, P - 2].
+ *   - An item is `polys` polynomials of 2048 plaintext coefficients x in [0, p_db).
+ *       base server:  polys = 4, polynomial (m, c) at index q = 2 m + c -- the order of the item stream of load_db_items;
+ *       SpiralPack:   polys = trials = out_n^2, polynomial q = the item's plaintext in trial q -- the order of the record layout below.
+ *   - The item fingerprint:      f(item) = sum over q, c of x[q][c] * r^(2048 q + c + 1)  mod P.
+ *   - The combined fingerprint:  F = sum over the items i of the call of f(item i) * s^(i + 1)  mod P, i the item's DATABASE index, not its
+ *     position in the call.  Ranges add: F[a, a + n1) + F[a + n1, a + n1 + n2) = F[a, a + n1 + n2) mod P.  For a list of ids the sum runs over
+ *     the list as given: a repeated id counts as often as it is listed.
+ *   - A shard returns the partial sums over what it holds: a j-shard or column shard f = 0 for an item it does not hold and the F of its own
+ *     items; a trial shard the polynomials q of its trial range.  The partials of all shards add mod P (spiral_gpu_fingerprint_add), per item
+ *     and combined, to the unsharded values.
+ *   - The function is linear in the coefficients, so an update of some items changes F by sum of (f_new - f_old) * s^(i + 1), and every value is
+ *     an exact integer: the same bits in any order of summation.
+ *   - Collision bound.  For two DIFFERENT databases of one geometry and a key drawn uniformly AFTER both are fixed, the combined fingerprints
+ *     agree with probability at most (2048 * polys + number of items) / (P - 3) -- about 2^-37 at 2^24 items; two independent keys square the
+ *     bound.  This is a universal hash, not a cryptographic one: it gives nothing against someone who knows the key.
+ *
+ * fingerprint_items / fingerprint_items_at compute f of each item of the call into per_item[k] (uint64_t[n], or NULL) and F into *combined (or
+ * NULL; at least one of the two is given), on the device, from the image in the form it is in.  Everything else is read_db_items' contract above,
+ * word for word -- who may call, the forms read and never converted, one_image = 0, ordering (enqueued on this server's stream; returns after
+ * that stream is synchronised), refused inside a capture, the image, its form, its epoch and every captured graph untouched, the checks that
+ * come before any launch (null pointers, a range or an id outside the database, both outputs NULL), and an image that holds no plaintexts
+ * refused with the first offending item, polynomial and coefficient named, the outputs then unspecified -- except that a shard WRITES 0 for an
+ * item it does not hold.  The workspace is the server's, reused from call to call and bounded by option db_stage_bytes (8 bytes per polynomial
+ * and per item of a pass). */
+int spiral_gpu_server_fingerprint_items(spiral_gpu_server *s, const uint64_t *key, uint64_t first_item, uint64_t n_items, uint64_t *per_item,
+                                        uint64_t *combined);
+int spiral_gpu_server_fingerprint_items_at(spiral_gpu_server *s, const uint64_t *key, const uint64_t *item_ids, uint64_t n, uint64_t *per_item,
+                                           uint64_t *combined);
+/* The same function on the host, from a bit-packed item stream (coeff_bits 1..64, 2^coeff_bits >= p_db, as load_db_items takes it); needs no GPU.
+ * `items` holds, for each of n_items consecutive items from database index first_item, the polynomials poly0 .. poly0 + n_polys - 1 of an item of
+ * polys_per_item (<= 256), 256 * coeff_bits bytes each: a base item stream is (4, 0, 4), one SpiralPack trial's stream (trials, t, 1), a SpiralPack
+ * record-layout item (trials, 0, trials).  Fails on a coefficient >= p_db, which it names, on poly0 + n_polys > polys_per_item, on both outputs
+ * NULL, and on p_db outside [2, P]. */
+int spiral_gpu_fingerprint_host(const uint64_t *key, uint64_t p_db, const void *items, uint32_t coeff_bits, uint32_t polys_per_item, uint32_t poly0,
+                                uint32_t n_polys, uint64_t first_item, uint64_t n_items, uint64_t *per_item, uint64_t *combined);
+/* (a + b) mod P of two fingerprints.  An argument >= P is refused: the call returns P, which no fingerprint is, and sets last_error. */
+uint64_t spiral_gpu_fingerprint_add(uint64_t a, uint64_t b);
+#define SPIRAL_GPU_FINGERPRINT_MODULUS ((1ull << 61) - 1)
 
 /* ---- Records: byte strings of any size S >= 1, packed into the plaintexts of a base or a SpiralPack server ----------------------------------
  * The layout, stated once; every record call below, and the Python and test code, quote it.
@@ -720,6 +765,13 @@ int spiral_gpu_pack_server_read_db_items(spiral_gpu_pack_server *s, uint32_t tri
                                          uint64_t n_items);
 int spiral_gpu_pack_server_read_db_items_at(spiral_gpu_pack_server *s, uint32_t trial, void *items, uint32_t coeff_bits,
                                             const uint64_t *item_ids, uint64_t n);
+/* spiral_gpu_server_fingerprint_items / _at over this server's trial images ("Fingerprints": polys = trials, polynomial q = the item's plaintext in
+ * trial q), each read in its current form; there is no `trial` argument.  A trial-sharded server sums the polynomials of its own trial range
+ * [t0, t0 + nt) only, and the partials of all ranks add (spiral_gpu_fingerprint_add) to the whole fingerprints.  The owner or a lane may call. */
+int spiral_gpu_pack_server_fingerprint_items(spiral_gpu_pack_server *s, const uint64_t *key, uint64_t first_item, uint64_t n_items,
+                                             uint64_t *per_item, uint64_t *combined);
+int spiral_gpu_pack_server_fingerprint_items_at(spiral_gpu_pack_server *s, const uint64_t *key, const uint64_t *item_ids, uint64_t n,
+                                                uint64_t *per_item, uint64_t *combined);
 /* Records in the SpiralPack layout ("Records", SpiralPack).  The arguments and the contracts are those of spiral_gpu_server_load_records,
  * _update_records, _read_records and _read_records_at, `instance` included; there is no `trial` argument: a record names its bytes, the layout
  * says which trial images hold them.

@@ -124,6 +124,10 @@ PROTOTYPES = {
     "spiral_gpu_db_items_bytes": (C.c_size_t, [C.POINTER(Params), C.c_uint32, C.c_uint32, C.c_uint64]),
     "spiral_gpu_server_read_db_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_server_fingerprint_items": (C.c_int, [C.c_void_p, U64P, C.c_uint64, C.c_uint64, U64P, U64P]),
+    "spiral_gpu_server_fingerprint_items_at": (C.c_int, [C.c_void_p, U64P, U64P, C.c_uint64, U64P, U64P]),
+    "spiral_gpu_fingerprint_host": (C.c_int, [U64P, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, U64P, U64P]),
+    "spiral_gpu_fingerprint_add": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "spiral_gpu_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint64, C.POINTER(RecordLayout)]),
     "spiral_gpu_pack_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint64, C.POINTER(RecordLayout)]),
     "spiral_gpu_pack_server_load_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
@@ -206,6 +210,8 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_update_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_pack_server_read_db_items": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64]),
     "spiral_gpu_pack_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
+    "spiral_gpu_pack_server_fingerprint_items": (C.c_int, [C.c_void_p, U64P, C.c_uint64, C.c_uint64, U64P, U64P]),
+    "spiral_gpu_pack_server_fingerprint_items_at": (C.c_int, [C.c_void_p, U64P, U64P, C.c_uint64, U64P, U64P]),
     "spiral_gpu_pack_server_set_pub_params": (C.c_int, [C.c_void_p, U64P, U64P, U64P, U64P]),
     "spiral_gpu_pack_server_answer": (C.c_int, [C.c_void_p, U64P, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_read_acc": (C.c_int, [C.c_void_p, C.c_uint32, U64P]),
@@ -401,6 +407,82 @@ def read_ids(item_ids) -> np.ndarray:
     if ids.size and ids.dtype.kind == "i" and (ids < 0).any():
         raise ValueError("item_ids must be non-negative")
     return np.ascontiguousarray(ids, dtype=np.uint64)
+
+
+# ---- fingerprints (include/spiral_gpu.h "Fingerprints") ----
+FINGERPRINT_MODULUS = 2**61 - 1
+
+
+def _is_int(v, lo: int, hi: int) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool) and lo <= int(v) < hi
+
+
+def fingerprint_key(key):
+    """a fingerprint key, a pair of ints in [0, 2^64), as the uint64[2] the library takes"""
+    if isinstance(key, (str, bytes)) or not hasattr(key, "__len__") or len(key) != 2 or not all(_is_int(k, 0, 2**64) for k in key):
+        raise ValueError(f"a fingerprint key is a pair of ints in [0, 2^64), not {key!r}")
+    return (C.c_uint64 * 2)(int(key[0]), int(key[1]))
+
+
+def fingerprint_call(fn, head: tuple, n: int, per_item: bool):
+    """one fingerprint call of the library: fn(*head, per_item[n] or NULL, &combined) -> F, or (F, per-item uint64 array)"""
+    items = np.zeros(n, dtype=np.uint64) if per_item else None
+    combined = C.c_uint64(0)
+    check(fn(*head, items.ctypes.data_as(U64P) if per_item else None, C.byref(combined)))
+    return (int(combined.value), items) if per_item else int(combined.value)
+
+
+def fingerprint_range(first_item, n_items, total: int):
+    """the item range of a fingerprint_items call (n_items None: to the end of the database of `total` items)"""
+    if not _is_int(first_item, 0, 2**64):
+        raise ValueError(f"first_item = {first_item!r} is no item index")
+    if n_items is None:
+        n_items = max(total - int(first_item), 0)
+    if not _is_int(n_items, 0, 2**64):
+        raise ValueError(f"n_items = {n_items!r} is no item count")
+    if int(first_item) + int(n_items) > total:  # (the library's own refusal, before an output of that many words is allocated)
+        raise SpiralGpuError(f"items [{int(first_item)}, +{int(n_items)}) outside the database of {total}")
+    return int(first_item), int(n_items)
+
+
+def fingerprint_host(key, p_db: int, items, coeff_bits: int, polys_per_item: int = 4, poly0: int = 0, n_polys=None, first_item: int = 0, per_item: bool = False):
+    """the fingerprint of a bit-packed item stream, computed on the host (no GPU): `items` holds, for consecutive items from database index first_item,
+    the polynomials poly0 .. poly0 + n_polys - 1 (default: to the last) of an item of polys_per_item, coeff_bits wide as load_db_items takes them.
+    Returns F, or (F, the per-item values as a uint64 array) with per_item; see include/spiral_gpu.h "Fingerprints" """
+    k = fingerprint_key(key)
+    for name, v, lo, hi in (("p_db", p_db, 0, 2**64), ("coeff_bits", coeff_bits, 0, 2**32), ("polys_per_item", polys_per_item, 0, 2**32),
+                            ("poly0", poly0, 0, 2**32), ("first_item", first_item, 0, 2**64)):
+        if not _is_int(v, lo, hi):
+            raise ValueError(f"{name} = {v!r} is out of range")
+    if n_polys is None:
+        n_polys = max(int(polys_per_item) - int(poly0), 0)
+    if not _is_int(n_polys, 0, 2**32):
+        raise ValueError(f"n_polys = {n_polys!r} is out of range")
+    if isinstance(items, (bytes, bytearray, memoryview)):
+        items = np.frombuffer(items, dtype=np.uint8)
+    items = np.ascontiguousarray(items)
+    if items.dtype == np.uint64 and coeff_bits != 64:
+        raise TypeError("a uint64 item array holds 64-bit coefficients: pass coeff_bits = 64, or the bit-packed stream as uint8")
+    if items.dtype not in (np.uint8, np.uint64):
+        raise TypeError(f"items are bytes, a uint8 array or (coeff_bits = 64) a uint64 array, not {items.dtype}")
+    if not 1 <= int(coeff_bits) <= 64:
+        raise ValueError(f"coeff_bits = {coeff_bits!r} is not in 1..64")
+    item_bytes = int(n_polys) * 256 * int(coeff_bits)
+    if item_bytes == 0 or items.nbytes % item_bytes:
+        raise ValueError(f"items holds {items.nbytes} bytes: not whole items of {n_polys} polynomials of 2048 {coeff_bits}-bit coefficients")
+    n = items.nbytes // item_bytes
+    head = (k, int(p_db), items.ctypes.data_as(C.c_void_p), int(coeff_bits), int(polys_per_item), int(poly0), int(n_polys), int(first_item), n)
+    return fingerprint_call(lib().spiral_gpu_fingerprint_host, head, n, per_item)
+
+
+def fingerprint_add(*parts) -> int:
+    """the sum mod P = 2^61 - 1 of fingerprints (the partials of shards, or of adjoining ranges); raises for a value outside [0, P)"""
+    total = 0
+    for v in parts:
+        if not _is_int(v, 0, FINGERPRINT_MODULUS):
+            raise ValueError(f"{v!r} is no fingerprint: an int in [0, 2^61 - 1)")
+        total = int(lib().spiral_gpu_fingerprint_add(total, int(v)))
+    return total
 
 
 def update_args(items, coeff_bits: int, item_ids, polys_per_item: int):

@@ -14,6 +14,7 @@
 
 #include "../../include/spiral_gpu.h"
 #include "common.h"
+#include "fingerprint_math.h"
 #include "kernels.h"
 #include "seed_device.h"
 #include "transform_jobs.h"
@@ -24,6 +25,7 @@ namespace host {
 extern thread_local std::string g_err;
 extern std::atomic<uint64_t> g_pack_lane_batches;  // primitives.cpp: what get_option("pack_lane_batches") reads
 extern std::atomic<uint64_t> g_db_export_ns;       // primitives.cpp: what get_option("db_export_ns") reads
+extern std::atomic<uint64_t> g_db_fingerprint_ns;  // primitives.cpp: what get_option("db_fingerprint_ns") reads
 
 inline int fail(const char* fmt, ...) {
     char buf[512];
@@ -629,6 +631,171 @@ inline int export_items(ExportWork& W, const DeviceTables& tb, hipStream_t st, v
         return fail("the image holds no plaintext at item %llu (polynomial %u, coefficient %u lifts to a value outside the centred range of p_db): "
                     "not a plaintext image (fill_db_random, or a load_db of arbitrary words)",
                     (unsigned long long)item_of(pos), (uint32_t)(poly % polys), (uint32_t)(err % kN));
+    }
+    return 0;
+}
+
+// ---- content fingerprints of the image (fingerprint_items / fingerprint_items_at of both servers; include/spiral_gpu.h "Fingerprints") ----------
+// What a server holds of a fingerprint call, as the export's selection plus each item's database index.
+//   range form (sel == null): the n LOCAL items first_l .. first_l + n - 1; local item first_l + k is database item idx0 + k * stride and position
+//       pos0 + k * stride of the call (stride = the column shards G, else 1) -- affine, so nothing here grows with n;
+//   table form: item sel[k] is the call's position sel[k].pos, database item ids[sel[k].pos].
+struct FingerprintSel {
+    uint64_t first_l = 0, n = 0, idx0 = 0, stride = 1, pos0 = 0;
+    const std::vector<ExportItem>* sel = nullptr;
+    const uint64_t* ids = nullptr;
+};
+// The shared body, on the export's workspace and with its conventions (passes, error word, events).  img: the image of the first polynomial this server
+// holds; it holds npolys of an item's polynomials from poly0 on (base: 4 from 0; SpiralPack: its trial images, trial_words apart).  per_item (null: not
+// wanted) has n_call words: every one is written, 0 for an item this server does not hold.  *combined (null: not wanted): this server's partial of F.
+// One pass is two launches; a pass's per-polynomial words and item values are staged within option db_stage_bytes.  Returns after `st` is synchronised.
+inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t st, const uint64_t key[2], uint64_t p_db, const ExportImage& img,
+                             uint64_t trial_words, uint32_t npolys, uint32_t poly0, const FingerprintSel& fs, uint64_t n_call, uint64_t* per_item,
+                             uint64_t* combined) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("fingerprint_items cannot be called while the server's stream is being captured");
+    const uint64_t n = fs.sel ? fs.sel->size() : fs.n, stride = fs.sel ? 1 : fs.stride;
+    if (combined) *combined = 0;
+    if (n == 0 || npolys == 0) {
+        if (per_item) memset(per_item, 0, (size_t)n_call * 8);
+        return 0;
+    }
+    if (n > 0xFFFFFFFFull) return fail("at most 2^32 - 1 items per fingerprint call");
+    // a pass: a power of two of items (so that a power-of-two database goes through in whole passes, each of whole bands), within the staging bound
+    // and far below the launch limit of 2^31 workgroups
+    uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(options().db_stage_bytes / (8ull * (npolys + stride)), 1ull << 28));  // (tests force several passes)
+    while (chunk & (chunk - 1)) chunk &= chunk - 1;
+    chunk = std::min(chunk, n);
+    std::vector<uint4> table;
+    std::vector<uint64_t> ids;
+    if (fs.sel) {  // the export's sorted work table (export_items), and the database index of each entry
+        const uint32_t rows = img.pack ? 16u : 8u, cols = img.pack ? 8u : 4u;
+        std::vector<ExportItem> order(*fs.sel);
+        auto okey = [&](const ExportItem& e) { return ((uint64_t)(e.j / rows) << 40) | ((uint64_t)(e.ii / cols) << 20) | ((uint64_t)(e.j % rows) << 8) | (e.ii % cols); };
+        std::stable_sort(order.begin(), order.end(), [&](const ExportItem& a, const ExportItem& b) { return okey(a) < okey(b); });
+        table.reserve(n);
+        ids.reserve(n);
+        for (uint64_t k = 0; k < n; k++) {
+            table.push_back(make_uint4(order[k].j, order[k].ii, (uint32_t)(k % chunk), (uint32_t)order[k].pos));
+            ids.push_back(fs.ids[order[k].pos]);
+        }
+    }
+    // [error word][sums][weights][table][ids][a pass's polynomial words][a pass's item values]
+    const size_t o_sums = 16, o_w = o_sums + kFpSumWords * 8, o_table = o_w + kFpWeightWords * 8, o_ids = o_table + table.size() * sizeof(uint4);
+    const size_t o_part = o_ids + ids.size() * 8, o_item = o_part + (size_t)chunk * npolys * 8, item_words = (size_t)(chunk * stride);
+    const size_t dev_bytes = o_item + item_words * 8;
+    if (W.dev.words * 8 < dev_bytes) {
+        W.dev.release();
+        W.dev.words = 0;
+        if (W.dev.alloc((dev_bytes + 7) / 8)) {
+            (void)hipGetLastError();
+            W.dev.p = nullptr;
+            W.dev.words = 0;
+            return fail("no device memory for the fingerprint's staging (%zu bytes)", dev_bytes);
+        }
+    }
+    uint64_t weights[kFpWeightWords];
+    fp_build_weights(key, weights);
+    uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
+    HIP_OK(hipMemsetAsync(d, 0xFF, 16, st));  // the error word: ~0 = every coefficient so far is a plaintext's
+    HIP_OK(hipMemsetAsync(d + o_sums, 0, kFpSumWords * 8, st));
+    HIP_OK(hipMemcpyAsync(d + o_w, weights, sizeof(weights), hipMemcpyHostToDevice, st));
+    if (fs.sel) {
+        HIP_OK(hipMemcpyAsync(d + o_table, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d + o_ids, ids.data(), ids.size() * 8, hipMemcpyHostToDevice, st));
+    }
+    DbFingerprintParams fp{};
+    fp.db = img.db;
+    fp.trial_words = trial_words;
+    fp.weights = reinterpret_cast<const uint64_t*>(d + o_w);
+    fp.part = reinterpret_cast<uint64_t*>(d + o_part);
+    fp.err = reinterpret_cast<unsigned long long*>(d);
+    fp.pack = img.pack;
+    fp.form = img.form;
+    fp.num_per = img.num_per;
+    fp.dim0 = img.dim0;
+    fp.npolys = npolys;
+    fp.p_db = p_db;
+    DbFingerprintCombineParams cp{};
+    cp.part = fp.part;
+    cp.weights = fp.weights;
+    cp.item_f = per_item ? reinterpret_cast<uint64_t*>(d + o_item) : nullptr;
+    cp.out_stride = stride;
+    cp.sums = reinterpret_cast<uint64_t*>(d + o_sums);
+    cp.npolys = npolys;
+    cp.poly0 = poly0;
+    cp.idx_stride = stride;
+    const size_t passes = (size_t)((n + chunk - 1) / chunk);
+    while (W.ev.size() < 2 * passes) {
+        hipEvent_t e = nullptr;
+        HIP_OK(hipEventCreate(&e));
+        W.ev.push_back(e);
+    }
+    std::vector<uint64_t> bounce;  // table form: a pass's item values on their way to the positions of the caller's list
+    if (per_item) {
+        if (fs.sel) {
+            memset(per_item, 0, (size_t)n_call * 8);
+            bounce.resize(chunk);
+        } else {  // what lies before the first and behind the last item held
+            const uint64_t end = fs.pos0 + (n - 1) * stride + 1;
+            memset(per_item, 0, (size_t)fs.pos0 * 8);
+            memset(per_item + end, 0, (size_t)(n_call - end) * 8);
+        }
+    }
+    for (uint64_t done = 0; done < n; done += chunk) {
+        const uint64_t cnt = std::min(chunk, n - done);
+        const size_t pass = (size_t)(done / chunk);
+        fp.n = (uint32_t)cnt;
+        cp.n = cnt;
+        // a column shard's items lie `stride` apart: every pass but the last also zeroes the stride - 1 words behind its last item, up to the next pass's first
+        cp.out_words = done + cnt < n ? cnt * stride : (cnt - 1) * stride + 1;
+        if (fs.sel) {
+            fp.table = reinterpret_cast<const uint4*>(d + o_table) + done;
+            cp.ids = reinterpret_cast<const uint64_t*>(d + o_ids) + done;
+        } else {
+            fp.first = fs.first_l + done;
+            fp.pos_base = done;
+            cp.idx0 = fs.idx0 + done * stride;
+        }
+        HIP_OK(hipEventRecord(W.ev[2 * pass], st));
+        launch_db_fingerprint(tb, fp, st);
+        launch_db_fingerprint_combine(cp, st);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipEventRecord(W.ev[2 * pass + 1], st));
+        if (!per_item) continue;
+        if (fs.sel) {
+            HIP_OK(hipMemcpyAsync(bounce.data(), cp.item_f, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            for (uint64_t k = 0; k < cnt; k++) per_item[table[done + k].w] = bounce[k];
+        } else {  // (stream order keeps the next pass's launches behind this copy)
+            HIP_OK(hipMemcpyAsync(per_item + fs.pos0 + done * stride, cp.item_f, (size_t)cp.out_words * 8, hipMemcpyDeviceToHost, st));
+        }
+    }
+    struct {
+        unsigned long long err;
+        uint64_t pad, sums[kFpSumWords];
+    } back;
+    static_assert(sizeof(back) == 16 + kFpSumWords * 8, "the error word and the sums lie back to back");
+    HIP_OK(hipMemcpyAsync(&back, d, sizeof(back), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    double dev_ms = 0;
+    for (size_t k = 0; k < passes; k++) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, W.ev[2 * k], W.ev[2 * k + 1]));
+        dev_ms += ms;
+    }
+    g_db_fingerprint_ns.store((uint64_t)(dev_ms * 1e6));
+    if (back.err != ~0ull) {
+        const uint64_t poly = back.err / kN, pos = poly / npolys;  // (range form: the position among the items held)
+        return fail("the image holds no plaintext at item %llu (polynomial %u, coefficient %u lifts to a value outside the centred range of p_db): "
+                    "not a plaintext image (fill_db_random, or a load_db of arbitrary words)",
+                    (unsigned long long)(fs.sel ? fs.ids[pos] : fs.idx0 + pos * stride), poly0 + (uint32_t)(poly % npolys), (uint32_t)(back.err % kN));
+    }
+    if (combined) {
+        uint64_t F = 0;
+        for (uint32_t k = 0; k < kFpSumWords; k++) F = fp_add(F, back.sums[k]);
+        *combined = F;
     }
     return 0;
 }

@@ -686,6 +686,44 @@ struct DbExportParams {
 };
 void launch_db_export(const DeviceTables& t, const DbExportParams& p, hipStream_t s);
 
+// ---- content fingerprints of the image (db_fingerprint.hip; the definition: include/spiral_gpu.h "Fingerprints") -----------------------------
+// The export's work selection (a range of LOCAL items, or a table {j local, column ii, slot in the pass, position in the call}), gather, inverse
+// transform and error word, with one 8-byte word per polynomial in place of the item stream: part[slot * npolys + q] = sum over c of
+// x_c r^(c + 1) mod P for polynomial q of the npolys this server holds of an item -- base: npolys = 4, q = 2 m + c; SpiralPack: its nt trial images,
+// image q at db + q * trial_words.  weights: the table of fingerprint_math.h fp_build_weights.  The error word takes
+// ((position in the call * npolys + q) * 2048 + coefficient).
+struct DbFingerprintParams {
+    const uint64_t* db;
+    uint64_t trial_words;
+    const uint64_t* weights;
+    uint64_t* part;
+    unsigned long long* err;
+    const uint4* table;
+    uint64_t first, pos_base;
+    uint32_t n;
+    uint32_t pack, form;     // as DbExportParams
+    uint32_t num_per, dim0;  // the image's geometry (dim0: the shard's first dimension on the base path)
+    uint32_t npolys;
+    uint64_t p_db;
+};
+void launch_db_fingerprint(const DeviceTables& t, const DbFingerprintParams& p, hipStream_t s);
+// The pass's second launch: f of item k = sum over q of part[k * npolys + q] r^(2048 (poly0 + q)) to item_f[k * out_stride] (item_f null: not wanted;
+// the out_stride - 1 words behind it, below out_words, are zeroed: items a column shard does not hold), and f s^(i + 1) -- i = ids[k], or
+// idx0 + k * idx_stride with ids null -- summed into sums[0 .. kFpSumWords), which ACCUMULATE from pass to pass.
+constexpr uint32_t kFpSumWords = 256;
+struct DbFingerprintCombineParams {
+    const uint64_t* part;
+    const uint64_t* weights;
+    const uint64_t* ids;
+    uint64_t idx0, idx_stride;
+    uint64_t* item_f;
+    uint64_t out_stride, out_words;
+    uint64_t* sums;
+    uint64_t n;
+    uint32_t npolys, poly0;
+};
+void launch_db_fingerprint_combine(const DbFingerprintCombineParams& p, hipStream_t s);
+
 // ---- records (records.hip; the layout: include/spiral_gpu.h "Records") --------------------------------------------------------
 // Work at a record's own granularity on a base image, one workgroup per polynomial.  A record (or its chunk of one instance) is a byte range of its
 // item's stream; cut at the polynomial boundaries it is a few SEGMENTS, each a byte range of one polynomial's 256 w byte stream (w = bits per

@@ -507,6 +507,45 @@ int spiral_gpu_pack_server_read_db_items_at(spiral_gpu_pack_server* S, uint32_t 
                         [&](uint64_t pos) { return item_ids[pos]; });
 }
 
+// The content fingerprint of items over this server's trial images, each in its current form (include/spiral_gpu.h "Fingerprints"): polynomial q of an
+// item is its plaintext in trial q, and a trial shard sums the q of its own range [t0, t0 + nt)
+namespace {
+static int pk_fingerprint_enter(spiral_gpu_pack_server* S, const uint64_t* key, const uint64_t* per_item, const uint64_t* combined) {
+    if (enter(S)) return -1;
+    if (!key) return fail("null argument");
+    if (!per_item && !combined) return fail("per_item and combined are both null: nothing to compute");
+    if (!S->img->loaded) return fail("no database loaded");
+    return 0;
+}
+}  // namespace
+int spiral_gpu_pack_server_fingerprint_items(spiral_gpu_pack_server* S, const uint64_t* key, uint64_t first_item, uint64_t n_items, uint64_t* per_item,
+                                             uint64_t* combined) {
+    if (pk_fingerprint_enter(S, key, per_item, combined)) return -1;
+    const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    FingerprintSel fs;
+    fs.first_l = fs.idx0 = first_item;
+    fs.n = n_items;
+    return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(0), S->img->lay.trial_words, S->nt, S->t0, fs, n_items, per_item,
+                             combined);
+}
+int spiral_gpu_pack_server_fingerprint_items_at(spiral_gpu_pack_server* S, const uint64_t* key, const uint64_t* item_ids, uint64_t n, uint64_t* per_item,
+                                                uint64_t* combined) {
+    if (pk_fingerprint_enter(S, key, per_item, combined)) return -1;
+    if (!item_ids) return fail("null argument");
+    if (n > 0xFFFFFFFFull) return fail("at most 2^32 - 1 items per fingerprint call");
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    for (uint64_t k = 0; k < n; k++)
+        if (item_ids[k] >= total) return fail("item id %llu outside the database of %llu items", (unsigned long long)item_ids[k], (unsigned long long)total);
+    std::vector<ExportItem> sel(n);
+    for (uint64_t k = 0; k < n; k++) sel[k] = ExportItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
+    FingerprintSel fs;
+    fs.sel = &sel;
+    fs.ids = item_ids;
+    return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(0), S->img->lay.trial_words, S->nt, S->t0, fs, n, per_item, combined);
+}
+
 // ---- records (include/spiral_gpu.h "Records", SpiralPack; records_host.h, records.hip) -----------------------------------------------------------
 namespace {
 // the layout, this instance's chunk and the trial images of a record call

@@ -10,6 +10,8 @@ std::atomic<uint64_t> spiral::host::g_pack_lane_batches{0};
 std::atomic<uint64_t> spiral::g_mfma_sweeps{0};
 // device nanoseconds of the export launches of this process's last read_db_items / read_db_items_at call (get_option "db_export_ns"; host_common.h export_items)
 std::atomic<uint64_t> spiral::host::g_db_export_ns{0};
+// the same of its last fingerprint_items / fingerprint_items_at call (get_option "db_fingerprint_ns"; host_common.h fingerprint_items)
+std::atomic<uint64_t> spiral::host::g_db_fingerprint_ns{0};
 
 // the process-wide options (kernels.h); the three documented environment variables give their initial values, once
 spiral::Options& spiral::options() {
@@ -76,6 +78,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else if (n == "key_binds") *value = (int64_t)g_key_binds.load();  // (read only)
     else if (n == "db_export_ns") *value = (int64_t)g_db_export_ns.load();  // (read only)
+    else if (n == "db_fingerprint_ns") *value = (int64_t)g_db_fingerprint_ns.load();  // (read only)
     else if (n == "mfma_sweeps") *value = (int64_t)g_mfma_sweeps.load(std::memory_order_relaxed);  // (read only)
     else return fail("unknown option '%s'", name);
     return 0;
@@ -521,6 +524,51 @@ size_t spiral_gpu_db_items_bytes(const spiral_gpu_params* p, uint32_t out_n, uin
     if (!p) return fail("null argument"), 0;
     if (check_export_width(coeff_bits, p->p_db)) return 0;
     return (size_t)n_items * (out_n ? 1u : 4u) * (kN / 8u) * coeff_bits;
+}
+
+// ---- fingerprints on the host (include/spiral_gpu.h "Fingerprints"): the function the device computes, from a bit-packed item stream -------------
+int spiral_gpu_fingerprint_host(const uint64_t* key, uint64_t p_db, const void* items, uint32_t coeff_bits, uint32_t polys_per_item, uint32_t poly0,
+                                uint32_t n_polys, uint64_t first_item, uint64_t n_items, uint64_t* per_item, uint64_t* combined) {
+    if (!key || (!items && n_items && n_polys)) return fail("null argument");
+    if (!per_item && !combined) return fail("per_item and combined are both null: nothing to compute");
+    if (p_db < 2 || p_db > kFpP) return fail("p_db = %llu is not in [2, 2^61 - 1]", (unsigned long long)p_db);
+    if (check_export_width(coeff_bits, p_db)) return -1;
+    if (polys_per_item < 1 || polys_per_item > kFpMaxPolys) return fail("polys_per_item = %u is not in 1..%u", polys_per_item, kFpMaxPolys);
+    if (poly0 > polys_per_item || n_polys > polys_per_item - poly0)
+        return fail("polynomials [%u, +%u) outside an item of %u", poly0, n_polys, polys_per_item);
+    if (first_item > ~0ull - n_items) return fail("items [%llu, +%llu) overflow the index", (unsigned long long)first_item, (unsigned long long)n_items);
+    std::vector<uint64_t> w(kFpWeightWords);
+    fp_build_weights(key, w.data());
+    const size_t poly_bytes = (size_t)(kN / 8u) * coeff_bits;
+    const uint64_t mask = coeff_bits == 64 ? ~0ull : (1ull << coeff_bits) - 1;
+    const uint8_t* b = static_cast<const uint8_t*>(items);
+    uint64_t F = 0;
+    for (uint64_t k = 0; k < n_items; k++) {
+        uint64_t f = 0;
+        for (uint32_t q = 0; q < n_polys; q++, b += poly_bytes) {
+            uint64_t acc = 0;
+            size_t bit = 0;
+            for (uint32_t c = 0; c < kN; c++, bit += coeff_bits) {
+                unsigned __int128 raw = 0;  // up to 64 + 7 bits from a byte boundary, inside the polynomial's own bytes
+                const size_t first = bit / 8;
+                for (size_t u = 0; u < 9 && first + u < poly_bytes; u++) raw |= (unsigned __int128)b[first + u] << (8 * u);
+                const uint64_t x = (uint64_t)(raw >> (bit % 8)) & mask;
+                if (x >= p_db)
+                    return fail("coefficient %u of polynomial %u of item %llu is %llu: not below p_db = %llu", c, poly0 + q, (unsigned long long)(first_item + k),
+                                (unsigned long long)x, (unsigned long long)p_db);
+                acc = fp_add(acc, fp_mul(x, w[c]));
+            }
+            f = fp_add(f, fp_mul(acc, w[kFpW_Poly + poly0 + q]));
+        }
+        if (per_item) per_item[k] = f;
+        F = fp_add(F, fp_mul(f, fp_pow_s(w.data() + kFpW_S, first_item + k + 1)));
+    }
+    if (combined) *combined = F;
+    return 0;
+}
+uint64_t spiral_gpu_fingerprint_add(uint64_t a, uint64_t b) {
+    if (a >= kFpP || b >= kFpP) return fail("a fingerprint is below 2^61 - 1: %llu is none", (unsigned long long)(a >= kFpP ? a : b)), kFpP;
+    return fp_add(a, b);
 }
 
 // client side of the wire form (load_modswitched_into_ct, src/client.cpp:90-110): plain host code, no device involved

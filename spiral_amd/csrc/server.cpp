@@ -588,6 +588,58 @@ int spiral_gpu_server_read_db_items_at(spiral_gpu_server* S, void* items, uint32
     return export_items(S->xwork, S->tb, S->stream, items, coeff_bits, S->p.p_db, S->img->export_source(), 0, 0, 0, &sel, [&](uint64_t pos) { return item_ids[pos]; });
 }
 
+// The content fingerprint of items of the image this server references, computed from the image in its current form (include/spiral_gpu.h
+// "Fingerprints"): read_db_items' contract with 8 bytes per item, or 8 bytes in all, in place of the item stream.  A shard returns its partial sums.
+namespace {
+static int fingerprint_enter(spiral_gpu_server* S, const uint64_t* key, const uint64_t* per_item, const uint64_t* combined) {
+    if (enter(S)) return -1;
+    if (!key) return fail("null argument");
+    if (!per_item && !combined) return fail("per_item and combined are both null: nothing to compute");
+    if (!S->img->loaded) return fail("no database loaded");
+    return 0;
+}
+}  // namespace
+int spiral_gpu_server_fingerprint_items(spiral_gpu_server* S, const uint64_t* key, uint64_t first_item, uint64_t n_items, uint64_t* per_item, uint64_t* combined) {
+    if (fingerprint_enter(S, key, per_item, combined)) return -1;
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    // database item i of column shard g of G is local item i / G of the shard's columns (read_db_items' map: j = i / np, column (i / G) % L, np = L G),
+    // so the items this server holds of a range are a range of local items, G apart in the database
+    const uint64_t G = col_ranks(S), g = S->col.on ? S->col.rank : 0u, L = srv_np(S);
+    const uint64_t lo = std::max<uint64_t>(first_item, S->j0 * np), hi = std::min<uint64_t>(first_item + n_items, S->j1 * np);
+    FingerprintSel fs;
+    if (lo < hi) {
+        const uint64_t u0 = (lo + G - 1 - g) / G, u1 = (hi + G - 1 - g) / G;  // i = u G + g in [lo, hi)
+        if (u0 < u1) {
+            fs.first_l = u0 - S->j0 * L;
+            fs.n = u1 - u0;
+            fs.idx0 = u0 * G + g;
+            fs.stride = G;
+            fs.pos0 = fs.idx0 - first_item;
+        }
+    }
+    return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(), 0, 4, 0, fs, n_items, per_item, combined);
+}
+int spiral_gpu_server_fingerprint_items_at(spiral_gpu_server* S, const uint64_t* key, const uint64_t* item_ids, uint64_t n, uint64_t* per_item, uint64_t* combined) {
+    if (fingerprint_enter(S, key, per_item, combined)) return -1;
+    if (!item_ids) return fail("null argument");
+    if (n > 0xFFFFFFFFull) return fail("at most 2^32 - 1 items per fingerprint call");
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    for (uint64_t k = 0; k < n; k++)
+        if (item_ids[k] >= total) return fail("item id %llu outside the database of %llu items", (unsigned long long)item_ids[k], (unsigned long long)total);
+    std::vector<ExportItem> sel;  // the ids this shard holds, as read_db_items_at
+    for (uint64_t k = 0; k < n; k++) {
+        const uint64_t j = item_ids[k] / np;
+        const uint32_t ii = (uint32_t)(item_ids[k] % np);
+        if (j >= S->j0 && j < S->j1 && holds_column(S, ii)) sel.push_back(ExportItem{k, (uint32_t)(j - S->j0), ii >> col_g_log(S)});
+    }
+    FingerprintSel fs;
+    fs.sel = &sel;
+    fs.ids = item_ids;
+    return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(), 0, 4, 0, fs, n, per_item, combined);
+}
+
 // ---- records (include/spiral_gpu.h "Records"; records_host.h, records.hip) ---------------------------------------------------------------------
 namespace {
 // the layout and this instance's chunk for a record call

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, fingerprint_call, fingerprint_key, fingerprint_range, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
 
 N = 2048
 
@@ -216,6 +216,22 @@ class Server:
         out = read_args(self.params, coeff_bits, len(ids), 0, out)
         check(lib().spiral_gpu_server_read_db_items_at(self.h, out.ctypes.data_as(C.c_void_p), coeff_bits, _p(ids), len(ids)))
         return out
+
+    # ---- content fingerprints (include/spiral_gpu.h "Fingerprints"): computed on the device from the image in its current form ----
+    def fingerprint_items(self, key, first_item: int = 0, n_items=None, per_item: bool = False):
+        """the combined fingerprint F of items first_item .. first_item + n_items - 1 (default: to the end) under `key`, a pair of ints in [0, 2^64);
+        with per_item, (F, the item fingerprints as a uint64 array).  A shard returns its partial sums (0 for an item it does not hold): add the
+        shards' values with spiral_amd.fingerprint_add"""
+        k = fingerprint_key(key)
+        first_item, n_items = fingerprint_range(first_item, n_items, self.shape.dim0 * self.shape.num_per)
+        return fingerprint_call(lib().spiral_gpu_server_fingerprint_items, (self.h, k, first_item, n_items), n_items, per_item)
+
+    def fingerprint_items_at(self, key, ids):
+        """(F, the item fingerprints as a uint64 array) of the items ids[k] (any order; a repeated id counts as often as it is listed); see
+        fingerprint_items"""
+        k = fingerprint_key(key)
+        ids = read_ids(ids)
+        return fingerprint_call(lib().spiral_gpu_server_fingerprint_items_at, (self.h, k, _p(ids), len(ids)), len(ids), True)
 
     # ---- records of any byte size (include/spiral_gpu.h "Records"); instance: which chunk of each record this server's image holds ----
     def load_records(self, records, record_bytes: int, first_record: int = 0, instance: int = 0):
