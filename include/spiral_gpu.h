@@ -322,6 +322,48 @@ int spiral_gpu_fingerprint_host(const uint64_t *key, uint64_t p_db, const void *
 uint64_t spiral_gpu_fingerprint_add(uint64_t a, uint64_t b);
 #define SPIRAL_GPU_FINGERPRINT_MODULUS ((1ull << 61) - 1)
 
+/* Tracked.  With P, r, s, q, c, x as above:
+ *   - the polynomial sum  g(i, q) = sum over c of x[q][c] * r^(c + 1)  mod P  (the word the fingerprint's first launch computes per polynomial),
+ *   - f(i) = sum over q of g(i, q) * r^(2048 q),   F = sum over the database indices i of f(i) * s^(i + 1).
+ * The tracked state belongs to the image's holder: the key; g for every (local item, polynomial) the server holds, 8 bytes each, resident on the
+ * device (4 words per item on a base server, one per held trial on SpiralPack); and F over what the server holds, as accumulator words on the
+ * device that the host adds.  A j-shard, column shard or trial shard keeps its partial F; partials add (spiral_gpu_fingerprint_add).
+ *
+ * fingerprint_track(key, poly_sums): poly_sums NULL computes the table and F from the image in its current form (fingerprint_items' passes and
+ *   contract; an image without plaintexts is refused with that call's message and tracking stays off).  poly_sums given adopts a table --
+ *   uint64_t[local items][polynomials held], local items in ascending database index, q ascending -- WITHOUT reading the image: every word must
+ *   be below P, else the call is refused.  Owner only (a lane or share_db server is refused); refused inside a capture; tracking again replaces
+ *   the state.  fingerprint_untrack frees it.
+ * Kept current: update_db_items and update_records of a tracked image also replace the table words of the polynomials they write and add
+ *   (g_new - g_old) * r^(2048 q) * s^(i + 1) to F, in launches of their own behind the scatter on the holder's stream, from the plaintexts the call
+ *   brought -- the image is not read, and no synchronisation is added.  A record call replaces only the polynomials a record touches.  A call that
+ *   fails leaves image, table, F and the update count as they were.  set_db_format and a batch's automatic conversion keep the state (the table does
+ *   not depend on the form).  gen_db, load_db, load_db_items, load_records and fill_db_random END tracking: keeping partial loads current is out of
+ *   scope, track again after them.  With tracking off every call does what it did, with the same kernels.
+ * fingerprint_tracked: synchronises this server's stream and returns the key, F (8 bytes: a 2 KiB copy added on the host) and the number of table
+ *   words replaced since track (a host counter); any out pointer may be NULL; any server that references the image may call; fails when the image
+ *   is not tracked.
+ * fingerprint_tracked_polys: the table's words of database items [first_item, + n_items) into poly_sums[n_items][polynomials held]; a j-shard or
+ *   column shard writes 0 for an item it does not hold, as fingerprint_items does, so the shards' outputs add to the unsharded table.
+ * fingerprint_scrub: recomputes g of the range from the image in its current form (fingerprint_items' kernels, passes and contract: who may call,
+ *   forms, ordering, refused in a capture, nothing converted, a coefficient that is no plaintext value fails the call naming item and coefficient)
+ *   and compares each word with the table on the device: *n_bad = the polynomials that differ, and with n_bad > 0 the lowest (database item,
+ *   polynomial) to *first_bad_item, *first_bad_poly (else untouched; either may be NULL).  Sixteen bytes come back.
+ * Measured at 2^15 items of 8 KiB on one MI355X (profiles/db_track.json; tracked / untracked, device ms, packed image): update_db_items of 1 item
+ *   0.039 / 0.031, of 4096 items 4.89 / 4.86; update_records of 1 record 0.076 / 0.068, of 4096 records 2.66 / 2.64; fingerprint_tracked 0.037 ms per
+ *   call against 5.88 ms for fingerprint_items of the image; track and scrub of the whole image 6.14 and 6.13 ms against 5.82 ms. */
+int spiral_gpu_server_fingerprint_track(spiral_gpu_server *s, const uint64_t *key, const uint64_t *poly_sums);
+int spiral_gpu_server_fingerprint_untrack(spiral_gpu_server *s);
+int spiral_gpu_server_fingerprint_tracked(spiral_gpu_server *s, uint64_t *key_out, uint64_t *combined, uint64_t *n_updates);
+int spiral_gpu_server_fingerprint_tracked_polys(spiral_gpu_server *s, uint64_t first_item, uint64_t n_items, uint64_t *poly_sums);
+int spiral_gpu_server_fingerprint_scrub(spiral_gpu_server *s, uint64_t first_item, uint64_t n_items, uint64_t *n_bad, uint64_t *first_bad_item,
+                                        uint32_t *first_bad_poly);
+/* f and F from a table of g, on the host (no GPU): poly_sums[k * n_polys + q] = g(first_item + k, poly0 + q) of an item of polys_per_item
+ * polynomials -- an exported table yields every value the other calls return.  (g itself from plaintexts: spiral_gpu_fingerprint_host with
+ * polys_per_item = 1 on a stream of single polynomials.)  Fails on a word >= P, on both outputs NULL and on poly0 + n_polys > polys_per_item. */
+int spiral_gpu_fingerprint_of_polys(const uint64_t *key, const uint64_t *poly_sums, uint32_t polys_per_item, uint32_t poly0, uint32_t n_polys,
+                                    uint64_t first_item, uint64_t n_items, uint64_t *per_item, uint64_t *combined);
+
 /* ---- Records: byte strings of any size S >= 1, packed into the plaintexts of a base or a SpiralPack server ----------------------------------
  * The layout, stated once; every record call below, and the Python and test code, quote it.
  *
@@ -772,6 +814,14 @@ int spiral_gpu_pack_server_fingerprint_items(spiral_gpu_pack_server *s, const ui
                                              uint64_t *per_item, uint64_t *combined);
 int spiral_gpu_pack_server_fingerprint_items_at(spiral_gpu_pack_server *s, const uint64_t *key, const uint64_t *item_ids, uint64_t n,
                                                 uint64_t *per_item, uint64_t *combined);
+/* The tracked fingerprint ("Fingerprints", Tracked) over this server's trial images: the table holds nt words per item, q = t0 .. t0 + nt - 1; a trial
+ * shard's weights start at r^(2048 t0) and its F is a partial.  update_db_items of any trial and update_records keep it current. */
+int spiral_gpu_pack_server_fingerprint_track(spiral_gpu_pack_server *s, const uint64_t *key, const uint64_t *poly_sums);
+int spiral_gpu_pack_server_fingerprint_untrack(spiral_gpu_pack_server *s);
+int spiral_gpu_pack_server_fingerprint_tracked(spiral_gpu_pack_server *s, uint64_t *key_out, uint64_t *combined, uint64_t *n_updates);
+int spiral_gpu_pack_server_fingerprint_tracked_polys(spiral_gpu_pack_server *s, uint64_t first_item, uint64_t n_items, uint64_t *poly_sums);
+int spiral_gpu_pack_server_fingerprint_scrub(spiral_gpu_pack_server *s, uint64_t first_item, uint64_t n_items, uint64_t *n_bad,
+                                             uint64_t *first_bad_item, uint32_t *first_bad_poly);
 /* Records in the SpiralPack layout ("Records", SpiralPack).  The arguments and the contracts are those of spiral_gpu_server_load_records,
  * _update_records, _read_records and _read_records_at, `instance` included; there is no `trial` argument: a record names its bytes, the layout
  * says which trial images hold them.

@@ -6,7 +6,7 @@ interface for that path (names and argument meaning of src/spiral.cpp / src/poly
 used by the parity tests and the benchmark.  numpy uint64 arrays carry the reference layouts.
 """
 from ._lib import PackShape, Params, RecordLayout, Shape, SpiralGpuError, build, db_items_bytes, lib, record_layout  # noqa: F401
-from ._lib import FINGERPRINT_MODULUS, fingerprint_add, fingerprint_host  # noqa: F401
+from ._lib import FINGERPRINT_MODULUS, fingerprint_add, fingerprint_host, fingerprint_of_polys  # noqa: F401
 from .client import Client, ResponseNoise, client_noise_table  # noqa: F401
 from .keys import KeyStore, bind_keys  # noqa: F401
 from .ops import *  # noqa: F401,F403

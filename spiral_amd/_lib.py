@@ -128,6 +128,12 @@ PROTOTYPES = {
     "spiral_gpu_server_fingerprint_items_at": (C.c_int, [C.c_void_p, U64P, U64P, C.c_uint64, U64P, U64P]),
     "spiral_gpu_fingerprint_host": (C.c_int, [U64P, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, U64P, U64P]),
     "spiral_gpu_fingerprint_add": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_fingerprint_track": (C.c_int, [C.c_void_p, U64P, U64P]),
+    "spiral_gpu_server_fingerprint_untrack": (C.c_int, [C.c_void_p]),
+    "spiral_gpu_server_fingerprint_tracked": (C.c_int, [C.c_void_p, U64P, U64P, U64P]),
+    "spiral_gpu_server_fingerprint_tracked_polys": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, U64P]),
+    "spiral_gpu_server_fingerprint_scrub": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, U64P, U64P, C.POINTER(C.c_uint32)]),
+    "spiral_gpu_fingerprint_of_polys": (C.c_int, [U64P, U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, U64P, U64P]),
     "spiral_gpu_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint64, C.POINTER(RecordLayout)]),
     "spiral_gpu_pack_record_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint64, C.POINTER(RecordLayout)]),
     "spiral_gpu_pack_server_load_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64]),
@@ -212,6 +218,11 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_read_db_items_at": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, U64P, C.c_uint64]),
     "spiral_gpu_pack_server_fingerprint_items": (C.c_int, [C.c_void_p, U64P, C.c_uint64, C.c_uint64, U64P, U64P]),
     "spiral_gpu_pack_server_fingerprint_items_at": (C.c_int, [C.c_void_p, U64P, U64P, C.c_uint64, U64P, U64P]),
+    "spiral_gpu_pack_server_fingerprint_track": (C.c_int, [C.c_void_p, U64P, U64P]),
+    "spiral_gpu_pack_server_fingerprint_untrack": (C.c_int, [C.c_void_p]),
+    "spiral_gpu_pack_server_fingerprint_tracked": (C.c_int, [C.c_void_p, U64P, U64P, U64P]),
+    "spiral_gpu_pack_server_fingerprint_tracked_polys": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, U64P]),
+    "spiral_gpu_pack_server_fingerprint_scrub": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, U64P, U64P, C.POINTER(C.c_uint32)]),
     "spiral_gpu_pack_server_set_pub_params": (C.c_int, [C.c_void_p, U64P, U64P, U64P, U64P]),
     "spiral_gpu_pack_server_answer": (C.c_int, [C.c_void_p, U64P, U64P, U64P, C.POINTER(C.c_double)]),
     "spiral_gpu_pack_server_read_acc": (C.c_int, [C.c_void_p, C.c_uint32, U64P]),
@@ -483,6 +494,84 @@ def fingerprint_add(*parts) -> int:
             raise ValueError(f"{v!r} is no fingerprint: an int in [0, 2^61 - 1)")
         total = int(lib().spiral_gpu_fingerprint_add(total, int(v)))
     return total
+
+
+def fingerprint_of_polys(key, poly_sums, polys_per_item: int = 4, poly0: int = 0, n_polys=None, first_item: int = 0, per_item: bool = False):
+    """f and F from a table of polynomial sums g, on the host (no GPU): poly_sums[k][q] = g(first_item + k, poly0 + q) for the polynomials poly0 ..
+    poly0 + n_polys - 1 (default: to the last) of an item of polys_per_item.  Returns F, or (F, the per-item values as a uint64 array) with per_item;
+    see include/spiral_gpu.h "Fingerprints", Tracked"""
+    k = fingerprint_key(key)
+    for name, v, hi in (("polys_per_item", polys_per_item, 2**32), ("poly0", poly0, 2**32), ("first_item", first_item, 2**64)):
+        if not _is_int(v, 0, hi):
+            raise ValueError(f"{name} = {v!r} is out of range")
+    if n_polys is None:
+        n_polys = max(int(polys_per_item) - int(poly0), 0)
+    if not _is_int(n_polys, 0, 2**32):
+        raise ValueError(f"n_polys = {n_polys!r} is out of range")
+    g = np.ascontiguousarray(poly_sums)
+    if g.dtype != np.uint64:
+        raise TypeError(f"polynomial sums are a uint64 array, not {g.dtype}")
+    if int(n_polys) == 0 or g.size % int(n_polys):
+        raise ValueError(f"poly_sums holds {g.size} words: not whole items of {n_polys} polynomials")
+    n = g.size // int(n_polys)
+    head = (k, g.ctypes.data_as(U64P), int(polys_per_item), int(poly0), int(n_polys), int(first_item), n)
+    return fingerprint_call(lib().spiral_gpu_fingerprint_of_polys, head, n, per_item)
+
+
+class TrackedFingerprint:
+    """the tracked-fingerprint calls of Server and PackServer (include/spiral_gpu.h "Fingerprints", Tracked).  The class says which library calls are
+    its own (_fp_prefix) and what its table holds (_fp_table: local items, polynomials held of an item, items of the database)"""
+
+    def _fp(self, name: str):
+        return getattr(lib(), f"{self._fp_prefix}_fingerprint_{name}")
+
+    def fingerprint_track(self, key, poly_sums=None):
+        """start tracking under `key`: the table of polynomial sums and F computed from the image in its current form, or, with poly_sums (a uint64
+        array, [local item][polynomial held], as fingerprint_tracked_polys of an unsharded or equally sharded server returns it), adopted without
+        reading the image.  The update calls keep both current; every loader ends tracking.  Owner only"""
+        k = fingerprint_key(key)
+        if poly_sums is None:
+            check(self._fp("track")(self.h, k, None))
+            return
+        g = np.ascontiguousarray(poly_sums)
+        items, polys, _ = self._fp_table()
+        if g.dtype != np.uint64 or g.size != items * polys:
+            raise ValueError(f"poly_sums must be {items} x {polys} uint64 words (local items x polynomials held), not {g.size} of {g.dtype}")
+        check(self._fp("track")(self.h, k, g.ctypes.data_as(U64P)))
+
+    def fingerprint_untrack(self):
+        check(self._fp("untrack")(self.h))
+
+    def fingerprint_tracked(self):
+        """(F, n_updates): the tracked combined fingerprint of what this server holds after everything enqueued on its stream, and the number of
+        polynomials whose table word the update calls have replaced since fingerprint_track.  Raises when the image is not tracked"""
+        F, n = C.c_uint64(0), C.c_uint64(0)
+        check(self._fp("tracked")(self.h, None, C.byref(F), C.byref(n)))
+        return int(F.value), int(n.value)
+
+    def fingerprint_tracked_key(self):
+        """the key the image is tracked under, as a pair of ints"""
+        k = (C.c_uint64 * 2)()
+        check(self._fp("tracked")(self.h, k, None, None))
+        return int(k[0]), int(k[1])
+
+    def fingerprint_tracked_polys(self, first_item: int = 0, n_items=None) -> np.ndarray:
+        """the table's words g of database items first_item .. (default: to the end) as a uint64 array [item][polynomial held]; a j-shard or column
+        shard returns 0 for an item it does not hold, so the shards' arrays add to the unsharded table"""
+        _, polys, total = self._fp_table()
+        first_item, n_items = fingerprint_range(first_item, n_items, total)
+        out = np.zeros((n_items, polys), dtype=np.uint64)
+        check(self._fp("tracked_polys")(self.h, first_item, n_items, out.ctypes.data_as(U64P)))
+        return out
+
+    def fingerprint_scrub(self, first_item: int = 0, n_items=None):
+        """recompute the polynomial sums of a range from the image in its current form and compare them with the table on the device:
+        (n_bad, first_bad) with first_bad = None, or the lowest (database item, polynomial) that differs"""
+        _, _, total = self._fp_table()
+        first_item, n_items = fingerprint_range(first_item, n_items, total)
+        n_bad, item, poly = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        check(self._fp("scrub")(self.h, first_item, n_items, C.byref(n_bad), C.byref(item), C.byref(poly)))
+        return int(n_bad.value), ((int(item.value), int(poly.value)) if n_bad.value else None)
 
 
 def update_args(items, coeff_bits: int, item_ids, polys_per_item: int):

@@ -18,15 +18,6 @@ namespace spiral {
 
 namespace {
 
-// the sum of `v` over the workgroup's 256 threads, valid in thread 0; sh: 4 words of LDS nobody reads any more
-__device__ __forceinline__ uint64_t fp_block_sum(uint64_t v, uint64_t* sh, uint32_t tid) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fp_add(v, (uint64_t)__shfl_xor((unsigned long long)v, off));  // across the wave of 64
-    if ((tid & 63u) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    return fp_add(fp_add(sh[0], sh[1]), fp_add(sh[2], sh[3]));  // across the four waves
-}
-
 // (launch bounds as db_export_kernel's: the same gather and transform; the weights take the place of the packing loop)
 template <uint32_t FORM, bool PACK>
 __global__ __launch_bounds__(256, 6) void db_fingerprint_kernel(Tables t, DbFingerprintParams p) {

@@ -13,6 +13,8 @@
 //     that says so.  A partial loader calls dirty() where its first write is enqueued: if it fails before that, an image that was loaded still
 //     is; if it fails after, the image is not loaded.
 //   - update_target: where update_db_items writes, every valid form of the image (no conversion, no new epoch).
+// `trk`, while on, holds the fingerprint table of the database `db` holds, whatever its form: the update calls move it with the image, set_format leaves it
+// alone, and dirty() -- every loader's first write -- ends it.
 #pragma once
 #include "host_common.h"
 
@@ -46,6 +48,7 @@ struct DbImage {
     bool loaded = false;
     uint64_t epoch = 1;  // bumped when the image is reloaded or changes form -- captured sweeps of the old form must not replay
     UpdateWork upd;      // update_db_items' workspace
+    FpTrack trk;         // the tracked fingerprint (include/spiral_gpu.h "Fingerprints", Tracked): kept by the update calls, ended by every loader (dirty)
     const void* owner = nullptr;  // the server that may write the image; null once it is destroyed or has given the image up
     uint32_t refs = 1;
 
@@ -67,6 +70,7 @@ struct DbImage {
         if (img->owner == who) {
             img->owner = nullptr;
             img->upd.release();
+            img->trk.release();  // (nobody is left to keep it current)
         }
         if (--img->refs == 0) {
             img->db.release();
@@ -124,7 +128,10 @@ struct DbImage {
     }
 
     // the loaders' bracket (see the invariant above)
-    void dirty() { loaded = limbs_valid = false; }
+    void dirty() {
+        loaded = limbs_valid = false;
+        trk.release();  // a loader's writes are not followed: tracking ends
+    }
     void begin_rewrite() {
         dirty();
         format = SPIRAL_GPU_DB_PACKED;

@@ -1,5 +1,5 @@
 // Arithmetic modulo P = 2^61 - 1 of the database fingerprints (include/spiral_gpu.h "Fingerprints"), stated once for the device kernels
-// (db_fingerprint.hip) and the host function (spiral_gpu_fingerprint_host), so that the two cannot drift.  Every argument and every result is
+// (db_fingerprint.hip, db_track.hip, the TRACK record kernels) and the host functions (spiral_gpu_fingerprint_host, _of_polys), so that they cannot drift.  Every argument and every result is
 // canonical, in [0, P - 1], unless a comment says otherwise.
 #pragma once
 #include <cstdint>
@@ -65,5 +65,16 @@ FP_HD uint64_t fp_pow_s(const uint64_t* sq, uint64_t e) {
         if (e & 1u) r = fp_mul(r, sq[k]);
     return r;
 }
+
+#if defined(__HIPCC__)
+// the sum of `v` over the workgroup's 256 threads, valid in thread 0; sh: 4 words of LDS nobody reads any more
+__device__ __forceinline__ uint64_t fp_block_sum(uint64_t v, uint64_t* sh, uint32_t tid) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fp_add(v, (uint64_t)__shfl_xor((unsigned long long)v, off));  // across the wave of 64
+    if ((tid & 63u) == 0) sh[tid >> 6] = v;
+    __syncthreads();
+    return fp_add(fp_add(sh[0], sh[1]), fp_add(sh[2], sh[3]));  // across the four waves
+}
+#endif
 
 }  // namespace spiral

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -319,6 +320,51 @@ inline int ingest_items(const void* items, uint32_t coeff_bits, uint64_t first, 
     return 0;
 }
 
+// ---- tracked fingerprints (include/spiral_gpu.h "Fingerprints", Tracked) -------------------------------------------------------------------------
+// The state an image's holder keeps between fingerprint_track and untrack (or the next loader): the key, its weight table and the accumulator words
+// of F on the device ([sums][weights] in `aux`), and the table of polynomial sums, word (local item) * npolys + q.
+struct FpTrack {
+    bool on = false;
+    uint64_t key[2] = {0, 0};
+    DevBuf table, aux;
+    uint32_t npolys = 0;     // polynomials held of an item
+    uint64_t n_updates = 0;  // table words replaced since track
+    uint64_t* sums() const { return aux.p; }
+    const uint64_t* weights() const { return aux.p + kFpSumWords; }
+    void release() {
+        table.release();
+        aux.release();
+        on = false;
+        n_updates = 0;
+    }
+    // room for `items` x `npolys` words and the weights of `key` on the device (uploaded on `st`); not `on` yet
+    int reserve(const uint64_t k[2], uint64_t n_items, uint32_t polys, hipStream_t st) {
+        release();
+        if (table.alloc((size_t)n_items * polys) || aux.alloc(kFpSumWords + kFpWeightWords)) {
+            (void)hipGetLastError();
+            release();
+            return fail("no device memory for the tracked fingerprint table (%llu bytes)", (unsigned long long)(n_items * polys * 8));
+        }
+        std::vector<uint64_t> w(kFpSumWords + kFpWeightWords, 0);
+        fp_build_weights(k, w.data() + kFpSumWords);
+        HIP_OK(hipMemcpyAsync(aux.p, w.data(), w.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));  // (w goes out of scope)
+        key[0] = k[0], key[1] = k[1];
+        npolys = polys;
+        return 0;
+    }
+};
+// What an update call needs to keep a tracked image's table and F current: polynomial m of the call's item (j local, column ii local) is table word
+// (j * num_per + ii) * t->npolys + q0 + m and polynomial poly0 + q0 + m of database item db_index(j, ii).  Null where the image is not tracked.
+struct FpTrackCtx {
+    FpTrack* t = nullptr;
+    uint32_t q0 = 0, poly0 = 0;
+    std::function<uint64_t(uint32_t, uint32_t)> db_index;
+    uint64_t entry_y(uint32_t j, uint32_t ii, uint32_t num_per, uint32_t m) const {
+        return ((((uint64_t)j * num_per + ii) * t->npolys + q0 + m) << 8) | (poly0 + q0 + m);
+    }
+};
+
 // ---- in-place item updates (update_db_items of both servers) ---------------------------------------------------------------------
 // The image holder's workspace, reused from call to call: a pinned host buffer holding what goes up (error word, work entries, the raw items) and
 // one device buffer holding the same plus the encoded items.  `done` is recorded on the holder's stream after an update's launches: the next
@@ -443,7 +489,7 @@ inline int update_reserve(UpdateWork& W, size_t n, size_t up_bytes, size_t dev_b
 // and ONE scatter launch (db_update.hip) on `st`, and returns -- the caller's buffers are copied by then.  Nothing touches the image before every
 // check has passed; the scatter kernel also skips everything when the encode launch flags a coefficient.
 inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, const void* items, uint32_t coeff_bits, uint64_t p_db,
-                        const std::vector<UpdateItem>& sel, const UpdateImage& img) {
+                        const std::vector<UpdateItem>& sel, const UpdateImage& img, const FpTrackCtx* trk = nullptr) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return fail("update_db_items cannot be called while the server's stream is being captured");
@@ -459,11 +505,18 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
     std::vector<uint4> put, pairs;
     update_entries(sel, img, put, pairs);
     // one buffer: [error word][put][pairs][raw items + 16 bytes of over-read room] ++ (device only) [encoded items]
+    // a tracked image: [..][raw items + 16][apply entries] ++ (device only) [encoded items][new polynomial sums]
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_put = 16, o_pairs = o_put + put.size() * sizeof(uint4), o_items = up16(o_pairs + pairs.size() * sizeof(uint4));
-    const size_t up_bytes = up16(o_items + n * item_bytes + 16), dev_bytes = up_bytes + n * polys * kPolyBytes;
+    const size_t o_app = up16(o_items + n * item_bytes + 16), n_app = trk ? n * polys : 0;
+    const size_t up_bytes = o_app + n_app * sizeof(ulonglong2), o_gnew = up_bytes + n * polys * kPolyBytes, dev_bytes = o_gnew + n_app * 8;
     if (update_reserve(W, n, up_bytes, dev_bytes)) return -1;
     memset(W.host, 0, up_bytes);
+    if (trk) {
+        ulonglong2* app = reinterpret_cast<ulonglong2*>(W.host + o_app);
+        for (size_t k = 0; k < n; k++)
+            for (uint32_t m = 0; m < polys; m++) app[k * polys + m] = make_ulonglong2(trk->db_index(sel[k].j, sel[k].ii), trk->entry_y(sel[k].j, sel[k].ii, img.num_per, m));
+    }
     if (!put.empty()) memcpy(W.host + o_put, put.data(), put.size() * sizeof(uint4));
     if (!pairs.empty()) memcpy(W.host + o_pairs, pairs.data(), pairs.size() * sizeof(uint4));
     for (size_t k = 0; k < n; k++) memcpy(W.host + o_items + k * item_bytes, src + sel[k].src * item_bytes, item_bytes);
@@ -486,6 +539,26 @@ inline int update_items(UpdateWork& W, const DeviceTables& tb, hipStream_t st, c
     up.num_per = img.num_per;
     up.dim0 = img.dim0;
     launch_db_update(up, st);
+    if (trk) {  // the table and F follow, from the staged stream: the image is not read
+        FpStreamParams sp{};
+        sp.items = d + o_items;
+        sp.weights = trk->t->weights();
+        sp.gnew = reinterpret_cast<uint64_t*>(d + o_gnew);
+        sp.err = up.err;
+        sp.n_polys = (uint32_t)n_app;
+        sp.coeff_bits = coeff_bits;
+        launch_fingerprint_stream(sp, st);
+        FpApplyParams ap{};
+        ap.entries = reinterpret_cast<const ulonglong2*>(d + o_app);
+        ap.gnew = sp.gnew;
+        ap.table = trk->t->table.p;
+        ap.weights = sp.weights;
+        ap.sums = trk->t->sums();
+        ap.err = up.err;
+        ap.n = (uint32_t)n_app;
+        launch_fingerprint_apply(ap, st);
+        trk->t->n_updates += n_app;  // (every check has passed on the host: the launches above do apply)
+    }
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(W.done, st));
     W.pending = true;
@@ -645,13 +718,23 @@ struct FingerprintSel {
     const std::vector<ExportItem>* sel = nullptr;
     const uint64_t* ids = nullptr;
 };
+// A range-form call on behalf of a tracked table (word (local item) * npolys + q, pointers at local item 0):
+//   store:   fingerprint_track -- the first launch stores a pass's words straight into the table, and the call's accumulator words go to `sums`;
+//   compare: fingerprint_scrub -- a compare launch per pass in place of the combine, the count and the lowest (item * 256 + polynomial) to n_bad, first_bad.
+struct FingerprintTable {
+    uint64_t* store = nullptr;
+    uint64_t* sums = nullptr;
+    const uint64_t* compare = nullptr;
+    uint64_t n_bad = 0, first_bad = ~0ull;
+};
 // The shared body, on the export's workspace and with its conventions (passes, error word, events).  img: the image of the first polynomial this server
 // holds; it holds npolys of an item's polynomials from poly0 on (base: 4 from 0; SpiralPack: its trial images, trial_words apart).  per_item (null: not
 // wanted) has n_call words: every one is written, 0 for an item this server does not hold.  *combined (null: not wanted): this server's partial of F.
 // One pass is two launches; a pass's per-polynomial words and item values are staged within option db_stage_bytes.  Returns after `st` is synchronised.
+// ft (range form only; null: none): the call serves a tracked table -- FingerprintTable above.
 inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t st, const uint64_t key[2], uint64_t p_db, const ExportImage& img,
                              uint64_t trial_words, uint32_t npolys, uint32_t poly0, const FingerprintSel& fs, uint64_t n_call, uint64_t* per_item,
-                             uint64_t* combined) {
+                             uint64_t* combined, FingerprintTable* ft = nullptr) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return fail("fingerprint_items cannot be called while the server's stream is being captured");
@@ -681,10 +764,10 @@ inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t 
             ids.push_back(fs.ids[order[k].pos]);
         }
     }
-    // [error word][sums][weights][table][ids][a pass's polynomial words][a pass's item values]
+    // [error word][sums][weights][table][ids][a pass's polynomial words][a pass's item values][a scrub's two words]
     const size_t o_sums = 16, o_w = o_sums + kFpSumWords * 8, o_table = o_w + kFpWeightWords * 8, o_ids = o_table + table.size() * sizeof(uint4);
     const size_t o_part = o_ids + ids.size() * 8, o_item = o_part + (size_t)chunk * npolys * 8, item_words = (size_t)(chunk * stride);
-    const size_t dev_bytes = o_item + item_words * 8;
+    const size_t o_scrub = o_item + item_words * 8, dev_bytes = o_scrub + 16;
     if (W.dev.words * 8 < dev_bytes) {
         W.dev.release();
         W.dev.words = 0;
@@ -701,6 +784,10 @@ inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t 
     HIP_OK(hipMemsetAsync(d, 0xFF, 16, st));  // the error word: ~0 = every coefficient so far is a plaintext's
     HIP_OK(hipMemsetAsync(d + o_sums, 0, kFpSumWords * 8, st));
     HIP_OK(hipMemcpyAsync(d + o_w, weights, sizeof(weights), hipMemcpyHostToDevice, st));
+    if (ft && ft->compare) {
+        HIP_OK(hipMemsetAsync(d + o_scrub, 0, 8, st));
+        HIP_OK(hipMemsetAsync(d + o_scrub + 8, 0xFF, 8, st));
+    }
     if (fs.sel) {
         HIP_OK(hipMemcpyAsync(d + o_table, table.data(), table.size() * sizeof(uint4), hipMemcpyHostToDevice, st));
         HIP_OK(hipMemcpyAsync(d + o_ids, ids.data(), ids.size() * 8, hipMemcpyHostToDevice, st));
@@ -758,9 +845,23 @@ inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t 
             fp.pos_base = done;
             cp.idx0 = fs.idx0 + done * stride;
         }
+        if (ft && ft->store) cp.part = fp.part = ft->store + (size_t)(fs.first_l + done) * npolys;
         HIP_OK(hipEventRecord(W.ev[2 * pass], st));
         launch_db_fingerprint(tb, fp, st);
-        launch_db_fingerprint_combine(cp, st);
+        if (ft && ft->compare) {
+            FpCompareParams mp{};
+            mp.part = fp.part;
+            mp.table = ft->compare + (size_t)(fs.first_l + done) * npolys;
+            mp.out = reinterpret_cast<unsigned long long*>(d + o_scrub);
+            mp.n_words = cnt * npolys;
+            mp.idx0 = cp.idx0;
+            mp.idx_stride = stride;
+            mp.npolys = npolys;
+            mp.poly0 = poly0;
+            launch_fingerprint_compare(mp, st);
+        } else {
+            launch_db_fingerprint_combine(cp, st);
+        }
         HIP_OK(hipGetLastError());
         HIP_OK(hipEventRecord(W.ev[2 * pass + 1], st));
         if (!per_item) continue;
@@ -778,7 +879,11 @@ inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t 
     } back;
     static_assert(sizeof(back) == 16 + kFpSumWords * 8, "the error word and the sums lie back to back");
     HIP_OK(hipMemcpyAsync(&back, d, sizeof(back), hipMemcpyDeviceToHost, st));
+    uint64_t scrub[2] = {0, ~0ull};
+    if (ft && ft->compare) HIP_OK(hipMemcpyAsync(scrub, d + o_scrub, 16, hipMemcpyDeviceToHost, st));
+    if (ft && ft->sums) HIP_OK(hipMemcpyAsync(ft->sums, d + o_sums, kFpSumWords * 8, hipMemcpyDeviceToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
+    if (ft) ft->n_bad = scrub[0], ft->first_bad = scrub[1];
     double dev_ms = 0;
     for (size_t k = 0; k < passes; k++) {
         float ms = 0;
@@ -796,6 +901,120 @@ inline int fingerprint_items(ExportWork& W, const DeviceTables& tb, hipStream_t 
         uint64_t F = 0;
         for (uint32_t k = 0; k < kFpSumWords; k++) F = fp_add(F, back.sums[k]);
         *combined = F;
+    }
+    return 0;
+}
+
+// ---- tracked fingerprints: the calls' shared bodies (both servers; include/spiral_gpu.h "Fingerprints", Tracked) ----------------------------------
+// The server's local items are database items idx0 + l * stride, l = 0 .. n_local - 1 (fingerprint_items' affine map), and it holds npolys polynomials of
+// each from poly0 on.
+struct FpTrackGeom {
+    uint64_t n_local, idx0, stride;
+    uint32_t npolys, poly0;
+};
+// fingerprint_track: the table and F from the image in its current form (poly_sums null: fingerprint_items' passes, the first launch storing into the
+// table), or from an adopted table (one upload and the combine launch; the image is not read).  On failure tracking is off.
+inline int fingerprint_track(FpTrack& T, ExportWork& W, const DeviceTables& tb, hipStream_t st, const uint64_t key[2], uint64_t p_db, const ExportImage& img,
+                             uint64_t trial_words, const FpTrackGeom& g, const uint64_t* poly_sums) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("fingerprint_track cannot be called while the server's stream is being captured");
+    const uint64_t words = g.n_local * g.npolys;
+    if (poly_sums)
+        for (uint64_t k = 0; k < words; k++)
+            if (poly_sums[k] >= kFpP)
+                return fail("word %llu of the polynomial sums is %llu: not below 2^61 - 1", (unsigned long long)k, (unsigned long long)poly_sums[k]);
+    T.release();
+    if (T.reserve(key, g.n_local, g.npolys, st)) {
+        T.release();
+        return -1;
+    }
+    if (!poly_sums) {
+        FingerprintSel fs;
+        fs.n = g.n_local;
+        fs.idx0 = g.idx0;
+        fs.stride = g.stride;
+        FingerprintTable ft;
+        ft.store = T.table.p;
+        ft.sums = T.sums();
+        uint64_t F = 0;
+        if (fingerprint_items(W, tb, st, key, p_db, img, trial_words, g.npolys, g.poly0, fs, 0, nullptr, &F, &ft)) {
+            T.release();
+            return -1;
+        }
+    } else {
+        DbFingerprintCombineParams cp{};
+        cp.part = T.table.p;
+        cp.weights = T.weights();
+        cp.idx0 = g.idx0;
+        cp.idx_stride = g.stride;
+        cp.out_stride = 1;
+        cp.sums = T.sums();
+        cp.n = g.n_local;
+        cp.npolys = g.npolys;
+        cp.poly0 = g.poly0;
+        hipError_t e = hipMemcpyAsync(T.table.p, poly_sums, (size_t)words * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            launch_db_fingerprint_combine(cp, st);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            T.release();
+            return fail("adopting the polynomial sums failed: %s", hipGetErrorString(e));
+        }
+    }
+    T.on = true;
+    return 0;
+}
+inline int fingerprint_not_tracked() { return fail("the image's fingerprint is not tracked (fingerprint_track; a loader ends tracking)"); }
+// fingerprint_tracked: F as the sum of the accumulator words, after `st`
+inline int fingerprint_tracked(const FpTrack& T, hipStream_t st, uint64_t* key_out, uint64_t* combined, uint64_t* n_updates) {
+    if (!T.on) return fingerprint_not_tracked();
+    uint64_t sums[kFpSumWords];
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipMemcpyAsync(sums, T.sums(), sizeof(sums), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    uint64_t F = 0;
+    for (uint32_t k = 0; k < kFpSumWords; k++) F = fp_add(F, sums[k]);
+    if (key_out) key_out[0] = T.key[0], key_out[1] = T.key[1];
+    if (combined) *combined = F;
+    if (n_updates) *n_updates = T.n_updates;
+    return 0;
+}
+// fingerprint_tracked_polys: the table's words of the n local items from first_l on, to items pos0, pos0 + stride, .. of the call's n_call; every other
+// word of poly_sums[n_call][npolys] is 0
+inline int fingerprint_tracked_polys(const FpTrack& T, hipStream_t st, uint64_t first_l, uint64_t n, uint64_t pos0, uint64_t stride, uint64_t n_call,
+                                     uint64_t* poly_sums) {
+    if (!T.on) return fingerprint_not_tracked();
+    if (!poly_sums) return fail("null argument");
+    const uint32_t np = T.npolys;
+    HIP_OK(hipStreamSynchronize(st));
+    if (stride == 1) {
+        memset(poly_sums, 0, (size_t)pos0 * np * 8);
+        memset(poly_sums + (pos0 + n) * np, 0, (size_t)(n_call - pos0 - n) * np * 8);
+        if (n) HIP_OK(hipMemcpyAsync(poly_sums + pos0 * np, T.table.p + first_l * np, (size_t)n * np * 8, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        return 0;
+    }
+    std::vector<uint64_t> tmp((size_t)n * np);
+    if (n) HIP_OK(hipMemcpyAsync(tmp.data(), T.table.p + first_l * np, tmp.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    memset(poly_sums, 0, (size_t)n_call * np * 8);
+    for (uint64_t k = 0; k < n; k++) memcpy(poly_sums + (pos0 + k * stride) * np, tmp.data() + k * np, (size_t)np * 8);
+    return 0;
+}
+// fingerprint_scrub: fingerprint_items' range form with the compare launch; *n_bad mismatching polynomials, the lowest (database item, polynomial) where any
+inline int fingerprint_scrub(const FpTrack& T, ExportWork& W, const DeviceTables& tb, hipStream_t st, uint64_t p_db, const ExportImage& img, uint64_t trial_words,
+                             uint32_t poly0, const FingerprintSel& fs, uint64_t* n_bad, uint64_t* first_bad_item, uint32_t* first_bad_poly) {
+    if (!T.on) return fingerprint_not_tracked();
+    FingerprintTable ft;
+    ft.compare = T.table.p;
+    if (fingerprint_items(W, tb, st, T.key, p_db, img, trial_words, T.npolys, poly0, fs, 0, nullptr, nullptr, &ft)) return -1;
+    if (n_bad) *n_bad = ft.n_bad;
+    if (ft.n_bad) {
+        if (first_bad_item) *first_bad_item = ft.first_bad / kFpMaxPolys;
+        if (first_bad_poly) *first_bad_poly = (uint32_t)(ft.first_bad % kFpMaxPolys);
     }
     return 0;
 }

@@ -724,6 +724,46 @@ struct DbFingerprintCombineParams {
 };
 void launch_db_fingerprint_combine(const DbFingerprintCombineParams& p, hipStream_t s);
 
+// ---- tracked fingerprints (db_track.hip; include/spiral_gpu.h "Fingerprints", Tracked) ------------------------------------------------------
+// The resident table holds g(i, q) = sum over c of x_c r^(c + 1) mod P, the word db_fingerprint_kernel stores, for every (local item, polynomial held):
+// word (local item) * npolys + q.  An in-place update computes the new words without reading the image, then replaces them and moves F by the difference.
+// All three kernels below return at once when *err != 0 (the update's error word or flag, as db_update_kernel).
+//
+// g of polynomial k of a staged raw item stream (update_db_items' `d + o_items`): gnew[k] from the 2048 coeff_bits-wide coefficients at
+// k * 2048 on (common.h packed_coeff: widths 1..40 and 64; the staging buffer's 16 bytes of over-read room).  One workgroup per polynomial.
+struct FpStreamParams {
+    const uint8_t* items;
+    const uint64_t* weights;  // fingerprint_math.h fp_build_weights
+    uint64_t* gnew;
+    const uint32_t* err;
+    uint32_t n_polys, coeff_bits;
+};
+void launch_fingerprint_stream(const FpStreamParams& p, hipStream_t s);
+// Entry k = {database index i of the item (kFpApplySkip: nothing to do, a polynomial no record touches), table word << 8 | polynomial q of the item}:
+// delta = (gnew[k] - table[word]) r^(2048 q) s^(i + 1), table[word] = gnew[k], and the workgroup's sum of deltas is ADDED to sums[blockIdx.x]
+// (db_fingerprint_combine_kernel's pattern: launches on one stream are ordered).  No two entries of a launch name the same word.
+constexpr uint64_t kFpApplySkip = ~0ull;
+struct FpApplyParams {
+    const ulonglong2* entries;
+    const uint64_t* gnew;
+    uint64_t* table;
+    const uint64_t* weights;
+    uint64_t* sums;
+    const uint32_t* err;
+    uint32_t n;
+};
+void launch_fingerprint_apply(const FpApplyParams& p, hipStream_t s);
+// A scrub pass: word w of the n_words recomputed words `part` (item k = w / npolys of the pass, polynomial q = w % npolys) against table[w]; a mismatch
+// adds 1 to out[0] and atomicMin's (database index idx0 + k idx_stride) * 256 + poly0 + q into out[1], which the host sets to 0 and ~0 before a call.
+struct FpCompareParams {
+    const uint64_t* part;
+    const uint64_t* table;
+    unsigned long long* out;
+    uint64_t n_words, idx0, idx_stride;
+    uint32_t npolys, poly0;
+};
+void launch_fingerprint_compare(const FpCompareParams& p, hipStream_t s);
+
 // ---- records (records.hip; the layout: include/spiral_gpu.h "Records") --------------------------------------------------------
 // Work at a record's own granularity on a base image, one workgroup per polynomial.  A record (or its chunk of one instance) is a byte range of its
 // item's stream; cut at the polynomial boundaries it is a few SEGMENTS, each a byte range of one polynomial's 256 w byte stream (w = bits per
@@ -768,6 +808,15 @@ struct PackRecordWorkParams {
 };
 void launch_pack_record_read(const DeviceTables& t, const PackRecordWorkParams& p, hipStream_t s);
 void launch_pack_record_update(const DeviceTables& t, const PackRecordWorkParams& p, hipStream_t s);
+// The update launches on an image whose fingerprint is tracked (the TRACK instantiations; launched on such an image only): the same work, and entry e
+// with segments also stores gnew[e] = sum over c of x_c r^(c + 1) mod P of the coefficients it holds after the splice (an entry without segments
+// stores nothing: its table word stays).  weights: fingerprint_math.h fp_build_weights.
+struct RecordTrackParams {
+    const uint64_t* weights;
+    uint64_t* gnew;
+};
+void launch_record_update_tracked(const DeviceTables& t, const RecordWorkParams& p, const RecordTrackParams& k, hipStream_t s);
+void launch_pack_record_update_tracked(const DeviceTables& t, const PackRecordWorkParams& p, const RecordTrackParams& k, hipStream_t s);
 
 // ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
 // noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]

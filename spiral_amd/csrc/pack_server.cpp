@@ -464,6 +464,18 @@ int spiral_gpu_pack_server_load_db_items(spiral_gpu_pack_server* S, uint32_t tri
 }
 
 // In place, in the trial image's current form, on the holder's stream (include/spiral_gpu.h; the base path's update_db_items with 1 x 1 plaintexts)
+namespace {
+// what the update calls need to keep a tracked image's fingerprint current (t null: not tracked): the polynomial of local trial q0 + m of item (j, ii),
+// database item j num_per + ii, is polynomial t0 + q0 + m of that item
+void pk_track_ctx(const spiral_gpu_pack_server* S, uint32_t q0, FpTrackCtx& c) {
+    if (!S->img->trk.on) return;
+    c.t = &S->img->trk;
+    c.q0 = q0;
+    c.poly0 = S->t0;
+    const uint64_t np = S->s.num_per;
+    c.db_index = [=](uint32_t j, uint32_t ii) { return j * np + ii; };
+}
+}  // namespace
 int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t trial, const void* items, uint32_t coeff_bits, const uint64_t* item_ids,
                                            uint64_t n) {
     if (!S) return fail("null server");
@@ -475,7 +487,9 @@ int spiral_gpu_pack_server_update_db_items(spiral_gpu_pack_server* S, uint32_t t
     if (check_update_ids(items, item_ids, n, (uint64_t)S->s.dim0 * np)) return -1;
     std::vector<UpdateItem> sel(n);
     for (uint64_t k = 0; k < n; k++) sel[k] = UpdateItem{k, (uint32_t)(item_ids[k] / np), (uint32_t)(item_ids[k] % np)};
-    return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target(trial - S->t0));
+    FpTrackCtx trk;
+    pk_track_ctx(S, trial - S->t0, trk);
+    return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target(trial - S->t0), trk.t ? &trk : nullptr);
 }
 
 // One trial's items back as plaintexts, in the load_db_items layout, from the trial image in its current form (include/spiral_gpu.h): the owner or a
@@ -544,6 +558,52 @@ int spiral_gpu_pack_server_fingerprint_items_at(spiral_gpu_pack_server* S, const
     fs.sel = &sel;
     fs.ids = item_ids;
     return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(0), S->img->lay.trial_words, S->nt, S->t0, fs, n, per_item, combined);
+}
+
+// ---- tracked fingerprints (include/spiral_gpu.h "Fingerprints", Tracked; host_common.h): over this server's trial images, polynomial q = trial q --
+namespace {
+int pk_fingerprint_check_range(const spiral_gpu_pack_server* S, uint64_t first_item, uint64_t n_items) {
+    const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    return 0;
+}
+}  // namespace
+int spiral_gpu_pack_server_fingerprint_track(spiral_gpu_pack_server* S, const uint64_t* key, const uint64_t* poly_sums) {
+    if (enter(S)) return -1;
+    if (!key) return fail("null argument");
+    if (pk_refuse_lane(S, "track")) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    const FpTrackGeom geom{(uint64_t)S->s.dim0 * S->s.num_per, 0, 1, S->nt, S->t0};
+    return fingerprint_track(S->img->trk, S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(0), S->img->lay.trial_words, geom, poly_sums);
+}
+int spiral_gpu_pack_server_fingerprint_untrack(spiral_gpu_pack_server* S) {
+    if (enter(S)) return -1;
+    if (pk_refuse_lane(S, "untrack")) return -1;
+    HIP_OK(hipStreamSynchronize(S->stream));  // (an update's apply launch may still write the table)
+    S->img->trk.release();
+    return 0;
+}
+int spiral_gpu_pack_server_fingerprint_tracked(spiral_gpu_pack_server* S, uint64_t* key_out, uint64_t* combined, uint64_t* n_updates) {
+    if (enter(S)) return -1;
+    return fingerprint_tracked(S->img->trk, S->stream, key_out, combined, n_updates);
+}
+int spiral_gpu_pack_server_fingerprint_tracked_polys(spiral_gpu_pack_server* S, uint64_t first_item, uint64_t n_items, uint64_t* poly_sums) {
+    if (enter(S)) return -1;
+    if (pk_fingerprint_check_range(S, first_item, n_items)) return -1;
+    return fingerprint_tracked_polys(S->img->trk, S->stream, first_item, n_items, 0, 1, n_items, poly_sums);
+}
+int spiral_gpu_pack_server_fingerprint_scrub(spiral_gpu_pack_server* S, uint64_t first_item, uint64_t n_items, uint64_t* n_bad, uint64_t* first_bad_item,
+                                             uint32_t* first_bad_poly) {
+    if (enter(S)) return -1;
+    if (!n_bad) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    if (pk_fingerprint_check_range(S, first_item, n_items)) return -1;
+    FingerprintSel fs;
+    fs.first_l = fs.idx0 = first_item;
+    fs.n = n_items;
+    return fingerprint_scrub(S->img->trk, S->xwork, S->tb, S->stream, S->p.p_db, S->img->export_source(0), S->img->lay.trial_words, S->t0, fs, n_bad, first_bad_item,
+                             first_bad_poly);
 }
 
 // ---- records (include/spiral_gpu.h "Records", SpiralPack; records_host.h, records.hip) -----------------------------------------------------------
@@ -634,8 +694,10 @@ int spiral_gpu_pack_server_update_records(spiral_gpu_pack_server* S, const void*
     }
     std::vector<RecordPiece> pieces(n);
     for (uint64_t k = 0; k < n; k++) pieces[k] = pk_record_piece(S, rc, k, record_ids[k]);
+    FpTrackCtx trk;
+    pk_track_ctx(S, 0, trk);
     return update_record_pieces(S->img->upd, S->tb, S->stream, static_cast<const uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, pieces,
-                                S->img->update_target(0), S->img->export_source(0), [&](uint64_t pos) { return record_ids[pos]; }, rc.tr);
+                                S->img->update_target(0), S->img->export_source(0), [&](uint64_t pos) { return record_ids[pos]; }, rc.tr, trk.t ? &trk : nullptr);
 }
 
 // The records back, from the trial images in their current form: the owner or a lane, on its own stream; a trial shard writes the bytes that lie in its

@@ -566,6 +566,32 @@ int spiral_gpu_fingerprint_host(const uint64_t* key, uint64_t p_db, const void* 
     if (combined) *combined = F;
     return 0;
 }
+// f and F from a table of polynomial sums g (include/spiral_gpu.h "Fingerprints", Tracked): poly_sums[k * n_polys + q] = g(first_item + k, poly0 + q)
+int spiral_gpu_fingerprint_of_polys(const uint64_t* key, const uint64_t* poly_sums, uint32_t polys_per_item, uint32_t poly0, uint32_t n_polys, uint64_t first_item,
+                                    uint64_t n_items, uint64_t* per_item, uint64_t* combined) {
+    if (!key || (!poly_sums && n_items && n_polys)) return fail("null argument");
+    if (!per_item && !combined) return fail("per_item and combined are both null: nothing to compute");
+    if (polys_per_item < 1 || polys_per_item > kFpMaxPolys) return fail("polys_per_item = %u is not in 1..%u", polys_per_item, kFpMaxPolys);
+    if (poly0 > polys_per_item || n_polys > polys_per_item - poly0)
+        return fail("polynomials [%u, +%u) outside an item of %u", poly0, n_polys, polys_per_item);
+    if (first_item > ~0ull - n_items) return fail("items [%llu, +%llu) overflow the index", (unsigned long long)first_item, (unsigned long long)n_items);
+    std::vector<uint64_t> w(kFpWeightWords);
+    fp_build_weights(key, w.data());
+    uint64_t F = 0;
+    for (uint64_t k = 0; k < n_items; k++) {
+        uint64_t f = 0;
+        for (uint32_t q = 0; q < n_polys; q++) {
+            const uint64_t g = poly_sums[k * n_polys + q];
+            if (g >= kFpP)
+                return fail("the sum of polynomial %u of item %llu is %llu: not below 2^61 - 1", poly0 + q, (unsigned long long)(first_item + k), (unsigned long long)g);
+            f = fp_add(f, fp_mul(g, w[kFpW_Poly + poly0 + q]));
+        }
+        if (per_item) per_item[k] = f;
+        F = fp_add(F, fp_mul(f, fp_pow_s(w.data() + kFpW_S, first_item + k + 1)));
+    }
+    if (combined) *combined = F;
+    return 0;
+}
 uint64_t spiral_gpu_fingerprint_add(uint64_t a, uint64_t b) {
     if (a >= kFpP || b >= kFpP) return fail("a fingerprint is below 2^61 - 1: %llu is none", (unsigned long long)(a >= kFpP ? a : b)), kFpP;
     return fp_add(a, b);

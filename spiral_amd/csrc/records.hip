@@ -19,6 +19,7 @@
 // layout, the limb planes and the 8-column pair form.  The update has entries for touched polynomials only, and db_update_trials_kernel scatters them
 // into every touched trial image in one launch.  The base kernels keep their names, arguments and resources (profiles/pack_records_resource_usage.txt).
 #include "db_plain_device.h"
+#include "fingerprint_math.h"
 #include "kernels.h"
 #include "ntt_device.h"
 
@@ -77,8 +78,11 @@ __device__ __forceinline__ void record_read_body(const Tables& t, const RecordWo
     }
 }
 
-template <uint32_t FORM, bool PACK>
-__device__ __forceinline__ void record_update_body(const Tables& t, const RecordWorkParams& p, uint64_t* sh, uint64_t trial_words, uint32_t trials, uint32_t trial0) {
+// TRACK (the image's fingerprint is tracked, include/spiral_gpu.h "Fingerprints"): an entry with segments also stores its polynomial sum
+// k->gnew[entry] = sum over c of x_c r^(c + 1) mod P, from the coefficients it holds after the splice; k is not looked at otherwise
+template <uint32_t FORM, bool PACK, bool TRACK = false>
+__device__ __forceinline__ void record_update_body(const Tables& t, const RecordWorkParams& p, uint64_t* sh, uint64_t trial_words, uint32_t trials, uint32_t trial0,
+                                                   const RecordTrackParams* k = nullptr) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint4 e = p.entries[blockIdx.x];
     const RecordPoly q = record_poly<PACK>(p, e, blockIdx.x & 3u, trial_words, trials, trial0);
@@ -130,10 +134,12 @@ __device__ __forceinline__ void record_update_body(const Tables& t, const Record
     // the ingest's centred lift (ntt.hip LD_DBGEN): x < half -> x, x >= half -> Q - (p_db - x), as residues mod p and mod b
     const uint64_t half = p.p_db >> 1;
     uint32_t lo[8], hi[8];
+    [[maybe_unused]] uint64_t fp_acc = 0;  // TRACK: 8 canonical terms, each below 2^61
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         uint64_t v = coeffs[ix_a(tid, r)];
         if (v >= p.p_db) v %= p.p_db;  // (only after an error was flagged: nothing of this launch is scattered)
+        if constexpr (TRACK) fp_acc += fp_mul(v, k->weights[ix_a(tid, r)]);
         if (v >= half) {
             const uint64_t d = p.p_db - v;
             lo[r] = kP - mod_p(d);
@@ -144,6 +150,11 @@ __device__ __forceinline__ void record_update_body(const Tables& t, const Record
         }
     }
     __syncthreads();  // every coefficient is in registers before the transform reuses the LDS words
+    if constexpr (TRACK) {
+        const uint64_t sum = fp_block_sum(fp_reduce(fp_acc), sh, tid);
+        if (tid == 0) k->gnew[blockIdx.x] = sum;
+        __syncthreads();  // the sum's four LDS words are read before the transform writes them
+    }
     ntt_forward_block<false>(lo, hi, sh, t.fwd, tid);
     canonicalize8(lo, hi);
     uint64_t v[8];
@@ -171,6 +182,17 @@ template <uint32_t FORM>
 __global__ __launch_bounds__(256, 4) void pack_record_update_kernel(Tables t, PackRecordWorkParams p) {
     __shared__ uint64_t sh[kLdsWords];
     record_update_body<FORM, true>(t, p.r, sh, p.trial_words, p.trials, p.trial0);
+}
+// the update kernels on an image whose fingerprint is tracked (kernels.h RecordTrackParams): kernels of their own, so that the two above keep their resources
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 4) void record_update_tracked_kernel(Tables t, RecordWorkParams p, RecordTrackParams k) {
+    __shared__ uint64_t sh[kLdsWords];
+    record_update_body<FORM, false, true>(t, p, sh, 0, 4u, 0, &k);
+}
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 4) void pack_record_update_tracked_kernel(Tables t, PackRecordWorkParams p, RecordTrackParams k) {
+    __shared__ uint64_t sh[kLdsWords];
+    record_update_body<FORM, true, true>(t, p.r, sh, p.trial_words, p.trials, p.trial0, &k);
 }
 
 }  // namespace
@@ -215,6 +237,27 @@ void launch_pack_record_update(const DeviceTables& t, const PackRecordWorkParams
         hipLaunchKernelGGL((pack_record_update_kernel<DBX_LIMBS>), grid, block, 0, s, tb, p);
     else
         hipLaunchKernelGGL((pack_record_update_kernel<DBX_LIMBS8>), grid, block, 0, s, tb, p);
+}
+
+void launch_record_update_tracked(const DeviceTables& t, const RecordWorkParams& p, const RecordTrackParams& k, hipStream_t s) {
+    if (p.n_entries == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    if (p.form == DBX_PACKED)
+        hipLaunchKernelGGL((record_update_tracked_kernel<DBX_PACKED>), dim3(p.n_entries), dim3(256), 0, s, tb, p, k);
+    else
+        hipLaunchKernelGGL((record_update_tracked_kernel<DBX_LIMBS>), dim3(p.n_entries), dim3(256), 0, s, tb, p, k);
+}
+
+void launch_pack_record_update_tracked(const DeviceTables& t, const PackRecordWorkParams& p, const RecordTrackParams& k, hipStream_t s) {
+    if (p.r.n_entries == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    const dim3 grid(p.r.n_entries), block(256);
+    if (p.r.form == DBX_PACKED)
+        hipLaunchKernelGGL((pack_record_update_tracked_kernel<DBX_PACKED>), grid, block, 0, s, tb, p, k);
+    else if (p.r.form == DBX_LIMBS)
+        hipLaunchKernelGGL((pack_record_update_tracked_kernel<DBX_LIMBS>), grid, block, 0, s, tb, p, k);
+    else
+        hipLaunchKernelGGL((pack_record_update_tracked_kernel<DBX_LIMBS8>), grid, block, 0, s, tb, p, k);
 }
 
 }  // namespace spiral

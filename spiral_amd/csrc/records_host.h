@@ -202,7 +202,7 @@ inline int record_image_error(unsigned long long err, RecordOf record_of, const 
 template <class RecordOf>
 inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream_t st, const uint8_t* records, uint64_t record_bytes, const RecordChunk& chunk,
                                 uint32_t w, uint64_t p_db, const std::vector<RecordPiece>& pieces, const UpdateImage& img, const ExportImage& src, RecordOf record_of,
-                                const RecordTrials& tr = RecordTrials{}) {
+                                const RecordTrials& tr = RecordTrials{}, const FpTrackCtx* trk = nullptr) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_OK(hipStreamIsCapturing(st, &cap));
     if (cap != hipStreamCaptureStatusNone) return fail("update_records cannot be called while the server's stream is being captured");
@@ -221,11 +221,25 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
         update_entries(items, img, put, pairs);
     }
     // one buffer: [flag, error word][entries][put][pairs][segments][record bytes] ++ (device only) [encoded polynomials]
+    // a tracked image: [..][record bytes][apply entries] ++ (device only) [encoded polynomials][new polynomial sums]
     auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
     const size_t o_ent = 16, o_put = o_ent + entries.size() * sizeof(uint4), o_pairs = o_put + put.size() * sizeof(uint4);
     const size_t o_segs = o_pairs + pairs.size() * sizeof(uint4), o_rec = o_segs + segs.size() * sizeof(uint4);
-    const size_t up_bytes = up16(o_rec + n * stride + 16), dev_bytes = up_bytes + entries.size() * kPolyBytes;
+    const size_t o_app = up16(o_rec + n * stride + 16), n_app = trk ? entries.size() : 0;
+    const size_t up_bytes = o_app + n_app * sizeof(ulonglong2), o_gnew = up_bytes + entries.size() * kPolyBytes, dev_bytes = o_gnew + n_app * 8;
     if (update_reserve(W, tr.trials ? entries.size() : items.size(), up_bytes, dev_bytes)) return -1;
+    uint64_t n_touched = 0;  // table words this call replaces: the entries with segments
+    if (trk) {
+        ulonglong2* app = reinterpret_cast<ulonglong2*>(W.host + o_app);
+        for (size_t e = 0; e < n_app; e++) {
+            // (base: entry 4 k + mc is polynomial mc of touched item k; SpiralPack: the entry names row, column and local trial, one polynomial per trial)
+            const uint32_t j = tr.trials ? entries[e].x & kRecordRowMask : items[e / 4].j, ii = tr.trials ? entries[e].y & kPackRecordColMask : items[e / 4].ii;
+            const uint32_t m = tr.trials ? entries[e].y >> kPackRecordTrialShift : (uint32_t)(e & 3u);
+            const bool skip = entries[e].w == 0;
+            app[e] = make_ulonglong2(skip ? kFpApplySkip : trk->db_index(j, ii), trk->entry_y(j, ii, img.num_per, m));
+            n_touched += skip ? 0 : 1;
+        }
+    }
     memset(W.host, 0, 8);
     memset(W.host + 8, 0xFF, 8);  // the error word: ~0 = every coefficient read so far is record data
     memcpy(W.host + o_ent, entries.data(), entries.size() * sizeof(uint4));
@@ -250,10 +264,12 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
     rp.w = w;
     rp.stride = stride;
     rp.p_db = p_db;
+    const RecordTrackParams tk{trk ? trk->t->weights() : nullptr, reinterpret_cast<uint64_t*>(d + o_gnew)};
     if (tr.trials)
-        launch_pack_record_update(tb, PackRecordWorkParams{rp, tr.trial_words, tr.trials, tr.t0}, st);
+        trk ? launch_pack_record_update_tracked(tb, PackRecordWorkParams{rp, tr.trial_words, tr.trials, tr.t0}, tk, st)
+            : launch_pack_record_update(tb, PackRecordWorkParams{rp, tr.trial_words, tr.trials, tr.t0}, st);
     else
-        launch_record_update(tb, rp, st);
+        trk ? launch_record_update_tracked(tb, rp, tk, st) : launch_record_update(tb, rp, st);
     DbUpdateParams up{};
     up.enc = rp.enc;
     up.err = rp.flag;
@@ -270,14 +286,27 @@ inline int update_record_pieces(UpdateWork& W, const DeviceTables& tb, hipStream
         launch_db_update_trials(DbUpdateTrialsParams{up, tr.trial_words}, st);
     else
         launch_db_update(up, st);
+    if (trk) {  // the table and F follow the scatter, from the sums the read-modify-write launch stored; the flag that stops the scatter stops this too
+        FpApplyParams ap{};
+        ap.entries = reinterpret_cast<const ulonglong2*>(d + o_app);
+        ap.gnew = tk.gnew;
+        ap.table = trk->t->table.p;
+        ap.weights = tk.weights;
+        ap.sums = trk->t->sums();
+        ap.err = rp.flag;
+        ap.n = (uint32_t)n_app;
+        launch_fingerprint_apply(ap, st);
+    }
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(W.done, st));
     W.pending = true;
-    if (!gathers) return 0;
-    unsigned long long err = 0;
-    HIP_OK(hipMemcpyAsync(&err, d + 8, sizeof(err), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    if (err != ~0ull) return record_image_error(err, [&](uint64_t k) { return record_of(pieces[k].pos); }, tr);
+    if (gathers) {
+        unsigned long long err = 0;
+        HIP_OK(hipMemcpyAsync(&err, d + 8, sizeof(err), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (err != ~0ull) return record_image_error(err, [&](uint64_t k) { return record_of(pieces[k].pos); }, tr);
+    }
+    if (trk) trk->t->n_updates += n_touched;
     return 0;
 }
 

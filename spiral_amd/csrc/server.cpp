@@ -532,6 +532,16 @@ int spiral_gpu_server_load_db_items(spiral_gpu_server* S, const void* items, uin
 
 // In place, in the image's current form, on the holder's stream (include/spiral_gpu.h): no conversion, no new epoch -- the image keeps its address
 // and its form, so captured graphs replay unchanged and read the new items.
+namespace {
+// what the update calls need to keep a tracked image's fingerprint current (t null: not tracked): local item (j, ii) is database item
+// ((j0 + j) L + ii) G + g -- fingerprint_items' map
+void track_ctx(const spiral_gpu_server* S, FpTrackCtx& c) {
+    if (!S->img->trk.on) return;
+    c.t = &S->img->trk;
+    const uint64_t G = col_ranks(S), g = S->col.on ? S->col.rank : 0u, L = srv_np(S), j0 = S->j0;
+    c.db_index = [=](uint32_t j, uint32_t ii) { return ((j0 + j) * L + ii) * G + g; };
+}
+}  // namespace
 int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, uint32_t coeff_bits, const uint64_t* item_ids, uint64_t n) {
     if (!S) return fail("null server");
     if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db or a lane): update it through the owner");
@@ -545,7 +555,9 @@ int spiral_gpu_server_update_db_items(spiral_gpu_server* S, const void* items, u
         const uint32_t ii = (uint32_t)(item_ids[k] % np);
         if (j >= S->j0 && j < S->j1 && holds_column(S, ii)) sel.push_back(UpdateItem{k, (uint32_t)(j - S->j0), ii >> col_g_log(S)});
     }
-    return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target());
+    FpTrackCtx trk;
+    track_ctx(S, trk);
+    return update_items(S->img->upd, S->tb, S->stream, items, coeff_bits, S->p.p_db, sel, S->img->update_target(), trk.t ? &trk : nullptr);
 }
 
 // The items back as plaintexts, in the load_db_items layout, from the image in its current form (include/spiral_gpu.h): any server that references a
@@ -599,16 +611,13 @@ static int fingerprint_enter(spiral_gpu_server* S, const uint64_t* key, const ui
     return 0;
 }
 }  // namespace
-int spiral_gpu_server_fingerprint_items(spiral_gpu_server* S, const uint64_t* key, uint64_t first_item, uint64_t n_items, uint64_t* per_item, uint64_t* combined) {
-    if (fingerprint_enter(S, key, per_item, combined)) return -1;
-    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
-    if (first_item > total || n_items > total - first_item)
-        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+namespace {
+// what this server holds of the database items [first_item, + n_items), as fingerprint_items' range form
+void fingerprint_range_sel(const spiral_gpu_server* S, uint64_t first_item, uint64_t n_items, FingerprintSel& fs) {
     // database item i of column shard g of G is local item i / G of the shard's columns (read_db_items' map: j = i / np, column (i / G) % L, np = L G),
     // so the items this server holds of a range are a range of local items, G apart in the database
-    const uint64_t G = col_ranks(S), g = S->col.on ? S->col.rank : 0u, L = srv_np(S);
+    const uint64_t np = S->s.num_per, G = col_ranks(S), g = S->col.on ? S->col.rank : 0u, L = srv_np(S);
     const uint64_t lo = std::max<uint64_t>(first_item, S->j0 * np), hi = std::min<uint64_t>(first_item + n_items, S->j1 * np);
-    FingerprintSel fs;
     if (lo < hi) {
         const uint64_t u0 = (lo + G - 1 - g) / G, u1 = (hi + G - 1 - g) / G;  // i = u G + g in [lo, hi)
         if (u0 < u1) {
@@ -619,6 +628,21 @@ int spiral_gpu_server_fingerprint_items(spiral_gpu_server* S, const uint64_t* ke
             fs.pos0 = fs.idx0 - first_item;
         }
     }
+}
+int fingerprint_check_range(const spiral_gpu_server* S, uint64_t first_item, uint64_t n_items) {
+    const uint64_t total = (uint64_t)S->s.dim0 * S->s.num_per;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    return 0;
+}
+}  // namespace
+int spiral_gpu_server_fingerprint_items(spiral_gpu_server* S, const uint64_t* key, uint64_t first_item, uint64_t n_items, uint64_t* per_item, uint64_t* combined) {
+    if (fingerprint_enter(S, key, per_item, combined)) return -1;
+    const uint64_t np = S->s.num_per, total = (uint64_t)S->s.dim0 * np;
+    if (first_item > total || n_items > total - first_item)
+        return fail("items [%llu, +%llu) outside the database of %llu", (unsigned long long)first_item, (unsigned long long)n_items, (unsigned long long)total);
+    FingerprintSel fs;
+    fingerprint_range_sel(S, first_item, n_items, fs);
     return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(), 0, 4, 0, fs, n_items, per_item, combined);
 }
 int spiral_gpu_server_fingerprint_items_at(spiral_gpu_server* S, const uint64_t* key, const uint64_t* item_ids, uint64_t n, uint64_t* per_item, uint64_t* combined) {
@@ -638,6 +662,44 @@ int spiral_gpu_server_fingerprint_items_at(spiral_gpu_server* S, const uint64_t*
     fs.sel = &sel;
     fs.ids = item_ids;
     return fingerprint_items(S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(), 0, 4, 0, fs, n, per_item, combined);
+}
+
+// ---- tracked fingerprints (include/spiral_gpu.h "Fingerprints", Tracked; host_common.h) -----------------------------------------------------------
+int spiral_gpu_server_fingerprint_track(spiral_gpu_server* S, const uint64_t* key, const uint64_t* poly_sums) {
+    if (enter(S)) return -1;
+    if (!key) return fail("null argument");
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db or a lane): track its fingerprint through the owner");
+    if (!S->img->loaded) return fail("no database loaded");
+    const uint64_t G = col_ranks(S), g = S->col.on ? S->col.rank : 0u, L = srv_np(S);
+    const FpTrackGeom geom{(uint64_t)S->dim0_shard * L, (uint64_t)S->j0 * L * G + g, G, 4u, 0u};
+    return fingerprint_track(S->img->trk, S->xwork, S->tb, S->stream, key, S->p.p_db, S->img->export_source(), 0, geom, poly_sums);
+}
+int spiral_gpu_server_fingerprint_untrack(spiral_gpu_server* S) {
+    if (enter(S)) return -1;
+    if (S->img->owner != S) return fail("this server sweeps another server's database image (share_db or a lane): untrack through the owner");
+    HIP_OK(hipStreamSynchronize(S->stream));  // (an update's apply launch may still write the table)
+    S->img->trk.release();
+    return 0;
+}
+int spiral_gpu_server_fingerprint_tracked(spiral_gpu_server* S, uint64_t* key_out, uint64_t* combined, uint64_t* n_updates) {
+    if (enter(S)) return -1;
+    return fingerprint_tracked(S->img->trk, S->stream, key_out, combined, n_updates);
+}
+int spiral_gpu_server_fingerprint_tracked_polys(spiral_gpu_server* S, uint64_t first_item, uint64_t n_items, uint64_t* poly_sums) {
+    if (enter(S)) return -1;
+    if (fingerprint_check_range(S, first_item, n_items)) return -1;
+    FingerprintSel fs;
+    fingerprint_range_sel(S, first_item, n_items, fs);
+    return fingerprint_tracked_polys(S->img->trk, S->stream, fs.first_l, fs.n, fs.pos0, fs.stride, n_items, poly_sums);
+}
+int spiral_gpu_server_fingerprint_scrub(spiral_gpu_server* S, uint64_t first_item, uint64_t n_items, uint64_t* n_bad, uint64_t* first_bad_item, uint32_t* first_bad_poly) {
+    if (enter(S)) return -1;
+    if (!n_bad) return fail("null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    if (fingerprint_check_range(S, first_item, n_items)) return -1;
+    FingerprintSel fs;
+    fingerprint_range_sel(S, first_item, n_items, fs);
+    return fingerprint_scrub(S->img->trk, S->xwork, S->tb, S->stream, S->p.p_db, S->img->export_source(), 0, 0, fs, n_bad, first_bad_item, first_bad_poly);
 }
 
 // ---- records (include/spiral_gpu.h "Records"; records_host.h, records.hip) ---------------------------------------------------------------------
@@ -724,8 +786,11 @@ int spiral_gpu_server_update_records(spiral_gpu_server* S, const void* records, 
     RecordPiece pc;
     for (uint64_t k = 0; k < n; k++)
         if (record_piece(S, rc, k, record_ids[k], &pc)) pieces.push_back(pc);
+    FpTrackCtx trk;
+    track_ctx(S, trk);
     return update_record_pieces(S->img->upd, S->tb, S->stream, static_cast<const uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, pieces,
-                                S->img->update_target(), S->img->export_source(), [&](uint64_t pos) { return record_ids[pos]; });
+                                S->img->update_target(), S->img->export_source(), [&](uint64_t pos) { return record_ids[pos]; }, RecordTrials{},
+                                trk.t ? &trk : nullptr);
 }
 
 // The records back, from the image in its current form: any server that references a loaded image, on its own stream; a shard writes the records it

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, check, fingerprint_call, fingerprint_key, fingerprint_range, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, TrackedFingerprint, check, fingerprint_call, fingerprint_key, fingerprint_range, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
 
 N = 2048
 
@@ -137,7 +137,7 @@ def answer_batch_instances(servers, instances, queries, wire: bool = False):
     return out, us.value
 
 
-class Server:
+class Server(TrackedFingerprint):
     def __init__(self, params: Params, device: int = 0, j_begin: int = 0, j_end: int = 0, share_db_of: "Server | None" = None, *,
                  col_rank: "int | None" = None, col_ranks: "int | None" = None):
         """share_db_of: make this server a query lane of that one -- same parameters, device and shard, sweeping ITS database
@@ -232,6 +232,13 @@ class Server:
         k = fingerprint_key(key)
         ids = read_ids(ids)
         return fingerprint_call(lib().spiral_gpu_server_fingerprint_items_at, (self.h, k, _p(ids), len(ids)), len(ids), True)
+
+    # ---- tracked fingerprints: fingerprint_track, _untrack, _tracked, _tracked_polys, _scrub (_lib.TrackedFingerprint) ----
+    _fp_prefix = "spiral_gpu_server"
+
+    def _fp_table(self):
+        total = self.shape.dim0 * self.shape.num_per
+        return self.dim0_shard * (self.shape.num_per // (self.col_ranks or 1)), 4, total
 
     # ---- records of any byte size (include/spiral_gpu.h "Records"); instance: which chunk of each record this server's image holds ----
     def load_records(self, records, record_bytes: int, first_record: int = 0, instance: int = 0):
