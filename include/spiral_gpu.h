@@ -436,6 +436,63 @@ int spiral_gpu_server_read_records(spiral_gpu_server *s, void *records, uint64_t
                                    uint64_t n_records);
 int spiral_gpu_server_read_records_at(spiral_gpu_server *s, void *records, uint64_t record_bytes, uint32_t instance, const uint64_t *record_ids,
                                       uint64_t n);
+/* ---- Keyed records: put, get and delete by key; bucketised two-choice hashing over the items of a base server -------------------------------
+ * The definition, stated once; the C++ (csrc/kv_host.h), the Python and the tests' restatement quote it.  Base parameter sets only (a SpiralPack
+ * session or server is refused), one instance, an unsharded image.
+ *
+ * Layout.  w, item_bytes = 1024 w and the item stream are those of "Records".  A bucket is an item: bucket b is item b, in the item order of
+ * load_db_items.  For a value size V >= 1, slots = floor(item_bytes / (8 + V)), and the bucket's stream is
+ *     [slots x 8-byte tags, little-endian u64][slots x V value bytes][padding]:
+ * the tag of slot s at byte 8 s, its value at byte 8 slots + s V.  Refused: slots = 0; slots > 256; a header that does not lie inside polynomial 0
+ * (8 slots > 256 w) -- a probe therefore reads one polynomial per bucket; fewer than 2 buckets.  Tag 0 means "empty": an image of all-zero
+ * plaintexts is an empty table.  capacity = 2^(nu1 + nu2) * slots.
+ *
+ * Hash.  SipHash-2-4 (c = 2, d = 4, 64-bit output) under the 16-byte table key: k0 = LE64(bytes 0..7), k1 = LE64(bytes 8..15).
+ *     tag = SipHash(k0, k1; key), a result of 0 replaced by 1;   u = SipHash(k0, k1 XOR 0xA5; key);   nb = 2^(nu1 + nu2);
+ *     b1 = (u & 0xffffffff) mod nb;   b2 = (u >> 32) mod nb, and b2 = b1 XOR 1 where that equals b1.
+ * Two keys with equal tags that share a candidate bucket are ONE key to this store.  For a table key drawn after the key set is fixed the chance
+ * of that is at most 2 slots / 2^64 per pair of keys.  The hash runs on the host: the client needs the bucket numbers there to make its queries.
+ *
+ * Placement.  Keys are placed in the order of the call.  (1) If the tag is present in b1 or b2 (b1 is looked at first), that slot is overwritten.
+ * (2) Otherwise the bucket with fewer used slots takes it; a tie goes to b1.  (3) Within the bucket, the lowest free slot.  (4) Both full: the call
+ * fails.
+ *
+ * A coefficient of a probed header that is no plaintext value below 2^w fails the call as a record call fails, naming the first such bucket. */
+typedef struct spiral_gpu_kv_layout {
+    uint32_t coeff_bits; /* w */
+    uint32_t slots;
+    uint64_t value_bytes;
+    uint64_t item_bytes;
+    uint64_t buckets;  /* nb */
+    uint64_t capacity; /* nb * slots */
+} spiral_gpu_kv_layout;
+/* host only, no device needed */
+int spiral_gpu_kv_layout_of(const spiral_gpu_params *p, uint64_t value_bytes, spiral_gpu_kv_layout *out);
+/* host only: the definition's tag, b1 and b2 of one key of key_bytes >= 0 bytes (key may be NULL for 0 bytes) */
+int spiral_gpu_kv_hash(const spiral_gpu_params *p, const void *table_key16, const void *key, uint64_t key_bytes, uint64_t *tag, uint64_t *b1,
+                       uint64_t *b2);
+/* A fresh table from n keys (`keys` is [n][key_bytes], `values` [n][value_bytes]): placement from empty on the host, the item stream built there
+ * with every unused byte zero, then load_db_items' ingest of the whole image.  Fails before touching the image where a key cannot be placed or two
+ * keys have equal tags (both named by position). */
+int spiral_gpu_server_kv_load(spiral_gpu_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, const void *values,
+                              uint64_t value_bytes, uint64_t n);
+/* put: arguments are checked first (two keys of one call with equal tags are refused by position); ONE probe launch (one workgroup per distinct
+ * candidate bucket: it reads polynomial 0 from the image in its current form and returns 32 bytes of occupancy per bucket and 4 bytes per (key,
+ * candidate), not the headers) and one wait on this server's stream; the host applies the placement rule; a key with both buckets full fails the
+ * call naming the first such key, and nothing is written; otherwise tag and value of every key go through update_records' read-modify-write and
+ * scatter: in place, in the current form, no epoch, tracked fingerprints kept current.  Owner only; refused inside a capture; refused on a j-shard or
+ * a column shard (both candidates of a key must be probed in one place).
+ * delete: the same probe; tag and value bytes of each found slot are written as zero; an absent key is not an error; *n_deleted (may be NULL)
+ * counts the keys found.
+ * get: the probe, then the found slots' values through read_records' path; found[k] is 0 (absent), 1 or 2 (the candidate that holds it); a missing
+ * key's bytes of `values` are left alone.  Any server that references the image may call it, lanes included. */
+int spiral_gpu_server_kv_put(spiral_gpu_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, const void *values,
+                             uint64_t value_bytes, uint64_t n);
+int spiral_gpu_server_kv_delete(spiral_gpu_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, uint64_t value_bytes, uint64_t n,
+                                uint64_t *n_deleted);
+int spiral_gpu_server_kv_get(spiral_gpu_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, void *values, uint64_t value_bytes,
+                             uint64_t n, uint8_t *found);
+
 /* read the device database back in reference layouts (tests): plaintext `item` as its n0 x n2 NTT-form MatPoly
  * (pts_encd, :1128), or slabs z_begin .. z_begin+nz-1 of load_db's layout restricted to this server's j-range:
  * word (z, ii, c, j, m) at ((((z - z_begin)*num_per + ii)*n2 + c)*(j_end - j_begin) + (j - j_begin))*n0 + m */
@@ -1171,6 +1228,18 @@ int spiral_gpu_client_record_queries(spiral_gpu_client *c, uint64_t record_bytes
                                      size_t bytes_each);
 int spiral_gpu_client_decode_records(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t record_bytes,
                                      const uint64_t *record_ids, void *records);
+/* Keyed records ("Keyed records" above; base sessions only, out_n = 0).
+ * kv_queries: spiral_gpu_client_queries for the items b1, b2 of each key: 2 n queries laid out [key][candidate], under 2 n message numbers.  BOTH
+ * are always made, whichever bucket holds the key and whether or not it is present: what a server sees does not depend on the table's content.
+ * kv_decode: `responses` holds the 2 n responses laid out [key][candidate], in RAW or WIRE form as decode takes them (2 n <= 65535).  One launch,
+ * one workgroup per response: it decodes output polynomial 0 as decode does, packs the header at w bits, looks for the key's tag (computed on the
+ * host) and, on a hit, decodes only the output polynomials the slot's value bytes touch.  Candidate 1 wins over candidate 2.  found[k] is 0, 1 or
+ * 2; values receives n x value_bytes bytes, those of an absent key zero.  n x value_bytes + n bytes come back, not 2 n plaintexts.  The values
+ * and found are bit for bit what decode, the header scan and the value cut of the definition give. */
+int spiral_gpu_client_kv_queries(spiral_gpu_client *c, const void *table_key16, const void *keys, uint64_t key_bytes, uint32_t n, int form, void *out,
+                                 size_t bytes_each);
+int spiral_gpu_client_kv_decode(spiral_gpu_client *c, const void *table_key16, const void *keys, uint64_t key_bytes, const void *responses, uint32_t n,
+                                int form, uint64_t value_bytes, void *values, uint8_t *found);
 
 #ifdef __cplusplus
 }

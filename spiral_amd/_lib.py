@@ -63,6 +63,14 @@ class RecordLayout(C.Structure):
     _fields_ = [("coeff_bits", C.c_uint32), ("instances", C.c_uint32), ("per_item", C.c_uint64), ("item_bytes", C.c_uint64), ("capacity", C.c_uint64)]
 
 
+class KvLayout(C.Structure):
+    """spiral_gpu_kv_layout: how keyed records of one value size lie in the buckets (items) of a base parameter set (include/spiral_gpu.h "Keyed
+    records")"""
+
+    _fields_ = [("coeff_bits", C.c_uint32), ("slots", C.c_uint32), ("value_bytes", C.c_uint64), ("item_bytes", C.c_uint64), ("buckets", C.c_uint64),
+                ("capacity", C.c_uint64)]
+
+
 U64P = C.POINTER(C.c_uint64)
 
 # name -> (restype, argtypes); every symbol include/spiral_gpu.h declares
@@ -287,6 +295,14 @@ PROTOTYPES = {
     "spiral_gpu_client_pub_params_msg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_queries": (C.c_int, [C.c_void_p, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P]),
+    "spiral_gpu_kv_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint64, C.POINTER(KvLayout)]),
+    "spiral_gpu_kv_hash": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64, U64P, U64P, U64P]),
+    "spiral_gpu_server_kv_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_kv_put": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_server_kv_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, U64P]),
+    "spiral_gpu_server_kv_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "spiral_gpu_client_kv_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "spiral_gpu_client_kv_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
     "spiral_gpu_client_record_queries": (C.c_int, [C.c_void_p, C.c_uint64, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_decode_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, U64P, C.c_void_p]),
     "spiral_gpu_client_response_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, U64P, U64P, C.POINTER(C.c_int64)]),
@@ -373,6 +389,50 @@ def record_layout(params: Params, record_bytes: int, out_n: int = 0) -> RecordLa
     else:
         check(lib().spiral_gpu_record_layout_of(C.byref(params), int(record_bytes), C.byref(out)))
     return out
+
+
+# ---- keyed records (include/spiral_gpu.h "Keyed records") ----
+def kv_layout(params: Params, value_bytes: int, out_n: int = 0) -> KvLayout:
+    """the layout of keyed records with values of value_bytes bytes in the buckets of `params`, host only; raises for a value size the definition
+    refuses (slots = 0, slots > 256, a header beyond polynomial 0), for fewer than 2 buckets and for a SpiralPack parameter set (out_n >= 1)"""
+    if not isinstance(value_bytes, (int, np.integer)) or isinstance(value_bytes, bool) or not 0 <= value_bytes < 2**64:
+        raise ValueError(f"value_bytes = {value_bytes!r} is no byte count")
+    if out_n:
+        raise SpiralGpuError(f"keyed records are defined for base parameter sets only (out_n = 0), not for a SpiralPack set with out_n = {out_n}")
+    out = KvLayout()
+    check(lib().spiral_gpu_kv_layout_of(C.byref(params), int(value_bytes), C.byref(out)))
+    return out
+
+
+def kv_table_key(table_key) -> np.ndarray:
+    """the 16-byte table key as a uint8 array"""
+    key = np.frombuffer(bytes(table_key), dtype=np.uint8) if isinstance(table_key, (bytes, bytearray, memoryview)) else np.ascontiguousarray(table_key)
+    if key.dtype != np.uint8 or key.size != 16:
+        raise ValueError("the table key is 16 bytes (bytes or a uint8 array)")
+    return np.ascontiguousarray(key.reshape(16))
+
+
+def kv_keys(keys) -> np.ndarray:
+    """the keys of a call as one contiguous uint8 array [n][key_bytes]: a 2-D uint8 array, or a list of bytes of equal length"""
+    if isinstance(keys, np.ndarray):
+        if keys.dtype != np.uint8 or keys.ndim != 2:
+            raise TypeError("keys are a 2-D uint8 array [n][key_bytes] or a list of bytes of equal length")
+        return np.ascontiguousarray(keys)
+    keys = [bytes(k) for k in keys]
+    if len({len(k) for k in keys}) > 1:
+        raise ValueError("the keys of one call have one length")
+    width = len(keys[0]) if keys else 0
+    return np.frombuffer(b"".join(keys), dtype=np.uint8).reshape(len(keys), width).copy()
+
+
+def kv_hash(params: Params, table_key, key) -> tuple[int, int, int]:
+    """(tag, b1, b2) of one key under the 16-byte table key: the definition's SipHash-2-4 values, host only"""
+    tk = kv_table_key(table_key)
+    kb = np.frombuffer(bytes(key), dtype=np.uint8)
+    tag, b1, b2 = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    check(lib().spiral_gpu_kv_hash(C.byref(params), tk.ctypes.data_as(C.c_void_p), kb.ctypes.data_as(C.c_void_p) if kb.size else None, kb.size, C.byref(tag),
+                                   C.byref(b1), C.byref(b2)))
+    return tag.value, b1.value, b2.value
 
 
 def record_array(records, record_bytes: int, n: int | None = None) -> np.ndarray:

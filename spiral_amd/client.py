@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U64P, check, lib, read_ids, record_layout, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U64P, check, kv_keys, kv_layout, kv_table_key, lib, read_ids, record_layout, wire_bytes
 
 N = 2048
 RESPONSE_RAW, RESPONSE_WIRE = 0, 1  # spiral_gpu_response_form
@@ -174,6 +174,41 @@ class Client:
         check(lib().spiral_gpu_client_decode_records(self.h, buf.ctypes.data_as(C.c_void_p), ids.size, _FORMS[form], record_bytes, ids.ctypes.data_as(U64P),
                                                      out.ctypes.data_as(C.c_void_p)))
         return out
+
+    # ---- keyed records (include/spiral_gpu.h "Keyed records"; base sessions only) ----
+    def kv_queries(self, table_key, keys, form="seeded") -> np.ndarray:
+        """queries() for both candidate buckets of every key, laid out [key][candidate] under 2 n message numbers; both are always made"""
+        f = _message_form(form)
+        if self.out_n:
+            kv_layout(self.params, 1, self.out_n)  # (raises: base sessions only)
+        tk, keys = kv_table_key(table_key), kv_keys(keys)
+        n, each = keys.shape[0], self._bytes["query", f]
+        out = np.zeros((2 * n, each), dtype=np.uint8)
+        check(lib().spiral_gpu_client_kv_queries(self.h, tk.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p) if keys.size else None, keys.shape[1], n, f,
+                                                 out.ctypes.data_as(C.c_void_p), each))
+        return out.view(np.uint64).reshape(2 * n, self.shape.n_query_cts, 2, 1, 2, N) if f == FORM_NTT else out
+
+    def kv_decode(self, table_key, keys, responses, value_bytes: int, form="raw"):
+        """(values uint8 [n][value_bytes], found uint8 [n]) from the 2 n responses laid out [key][candidate], in decode()'s forms: found[k] is 0
+        (absent: its value bytes are zero), 1 or 2; one launch finds the tag in the headers and decodes only what the found value touches"""
+        if form not in _FORMS:
+            raise ValueError(f"response form {form!r}: 'raw' or 'wire'")
+        kv_layout(self.params, value_bytes, self.out_n)
+        tk, keys = kv_table_key(table_key), kv_keys(keys)
+        n = keys.shape[0]
+        if form == "raw":
+            buf = np.ascontiguousarray(responses, dtype=np.uint64)
+            each = (self.rows + 1) * self.cols * N
+        else:
+            buf = wire_bytes(responses)
+            each = self.response_wire_bytes()
+        if buf.size != 2 * n * each:
+            raise ValueError(f"{buf.size} {'words' if form == 'raw' else 'bytes'} are not the 2 x {n} responses of {each} of {n} keys")
+        values, found = np.zeros((n, value_bytes), dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        check(lib().spiral_gpu_client_kv_decode(self.h, tk.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p) if keys.size else None, keys.shape[1],
+                                                buf.ctypes.data_as(C.c_void_p), n, _FORMS[form], value_bytes, values.ctypes.data_as(C.c_void_p),
+                                                found.ctypes.data_as(C.c_void_p)))
+        return values, found
 
     def noise_step(self, form="raw") -> int:
         """the step of the error's scale (include/spiral_gpu.h, response_noise): D = 4 q' for the switched forms, scale_k = Q // p_db for "final";

@@ -221,6 +221,93 @@ __global__ __launch_bounds__(kClientTpb) void client_decode_records_kernel(Clien
     }
 }
 
+// ---- keyed records: the client's find (include/spiral_gpu.h "Keyed records"; kernels.h ClientKvFindParams) ---------------------------------------
+// output polynomial (r, col) of response b into vals, masked to w bits: client_decode_records_kernel's steps through the shared functions.  Opens with
+// a barrier (the tiles' previous readers are done) and closes with one (vals is complete).
+__device__ __forceinline__ void kv_decode_poly(const ClientDecodeParams& p, uint32_t b, uint32_t r, uint32_t col, uint32_t w, int32_t* ext, int8_t* s8, uint64_t* vals,
+                                               uint32_t t) {
+    __syncthreads();
+    for (uint32_t z = t; z < kN; z += kClientTpb) {
+        const int32_t a = (int32_t)(response_value(p, b, col, 0, z) % p.qprime);
+        ext[kN + z] = a;
+        ext[z] = -a;
+        s8[z] = p.sp[(size_t)r * kN + z];
+    }
+    __syncthreads();
+    int64_t acc[8] = {};
+    secret_row_convolve(ext, s8, t, acc);
+    const int64_t qp = (int64_t)p.qprime, q1 = (int64_t)(4u * p.p_db), pdb = (int64_t)p.p_db;
+    const uint64_t mask = (1ull << w) - 1ull;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t k = t + 256u * j;
+        int64_t x;
+        int64_t res = switched_round(acc[j], response_value(p, b, col, 1u + r, k), qp, q1, x);
+        res %= pdb;
+        res += res < 0 ? pdb : 0;
+        vals[k] = (uint64_t)res & mask;
+    }
+    __syncthreads();
+}
+
+// Workgroup b = 2 k + candidate.  Polynomial 0 holds the header (the layout refuses one that does not), and the found slot's value bytes may start in it:
+// the polynomials the value touches are taken in ascending order, so polynomial 0's tile is read before a later polynomial reuses it.
+__global__ __launch_bounds__(kClientTpb) void client_kv_find_kernel(ClientKvFindParams q) {
+    __shared__ int32_t ext[2 * kN];
+    __shared__ int8_t s8[kN];
+    __shared__ uint64_t vals[kN];
+    __shared__ uint32_t hit_slot, arrived;
+    const ClientDecodeParams& p = q.d;
+    const uint32_t b = blockIdx.x, key = b >> 1, t = threadIdx.x, w = q.w, V = q.value_bytes, poly_bytes = 256u * w;
+    if (t == 0) hit_slot = 0xFFFFFFFFu;
+    kv_decode_poly(p, b, 0u, 0u, w, ext, s8, vals, t);
+    if (t < q.slots) {  // tag t: bits [64 t, + 64) of the string of w-bit values
+        const uint32_t bit = 64u * t;
+        uint32_t c = bit / w, off = bit - c * w;
+        uint64_t tag = 0;
+        for (uint32_t got = 0; got < 64u; c++) {
+            const uint32_t take = min(w - off, 64u - got);
+            tag |= ((vals[c] >> off) & ((1ull << take) - 1ull)) << got;
+            got += take;
+            off = 0;
+        }
+        if (tag == q.tags[key]) atomicMin(&hit_slot, t);
+    }
+    __syncthreads();
+    const uint32_t slot = hit_slot;
+    if (slot != 0xFFFFFFFFu) {
+        const uint32_t v0 = 8u * q.slots + slot * V, v1 = v0 + V;  // the value's bytes of the item's stream
+        for (uint32_t poly = v0 / poly_bytes; poly * poly_bytes < v1; poly++) {
+            if (poly != 0) kv_decode_poly(p, b, poly / p.cols, poly % p.cols, w, ext, s8, vals, t);
+            const uint32_t lo = max(v0, poly * poly_bytes), hi = min(v1, (poly + 1u) * poly_bytes);
+            for (uint32_t i = lo + t; i < hi; i += kClientTpb) {  // byte i of the item: bits [8 (i - poly * poly_bytes), + 8) of the polynomial's string
+                const uint32_t bit = 8u * (i - poly * poly_bytes);
+                uint32_t c = bit / w, filled = w - (bit - c * w);
+                uint64_t v = vals[c] >> (w - filled);
+                while (filled < 8u) {  // (the byte ends inside the polynomial's 2048 w bits: c + 1 < 2048 here)
+                    v |= vals[++c] << filled;
+                    filled += w;
+                }
+                q.stage[(size_t)b * V + (i - v0)] = (uint8_t)v;
+            }
+        }
+    }
+    // the second of the key's two workgroups to get here settles it: every thread's staged bytes are visible to the device before thread 0 counts
+    __threadfence();
+    __syncthreads();
+    if (t == 0) {
+        q.hit[b] = slot != 0xFFFFFFFFu ? 1u : 0u;
+        __threadfence();
+        arrived = atomicAdd(&q.arrive[key], 1u);
+    }
+    __syncthreads();
+    if (arrived != 1u) return;
+    __threadfence();
+    const uint32_t win = q.hit[2u * key] ? 0u : q.hit[2u * key + 1u] ? 1u : 2u;  // candidate 1 wins
+    for (uint32_t i = t; i < V; i += kClientTpb) q.values[(size_t)key * V + i] = win < 2u ? q.stage[(size_t)(2u * key + win) * V + i] : (uint8_t)0;
+    if (t == 0) q.found[key] = win < 2u ? (uint8_t)(win + 1u) : (uint8_t)0;
+}
+
 // ---- response noise (include/spiral_gpu.h, spiral_gpu_client_response_noise: the one definition of e) ------------------------------------------
 // One workgroup per output polynomial, as the decode.  Switched forms: the decode's operands, convolution and rounding, then e from x.  FINAL form:
 // row 0 is a value mod Q of 56 bits, whose sums against the secret do not fit 64 bits; the same convolution runs once per 28-bit prime on the
@@ -391,6 +478,11 @@ void launch_client_decode(const ClientDecodeParams& p, uint32_t n, hipStream_t s
 
 void launch_client_decode_records(const ClientRecordDecodeParams& p, uint32_t n_entries, hipStream_t s) {
     if (n_entries) hipLaunchKernelGGL(client_decode_records_kernel, dim3(n_entries), dim3(kClientTpb), 0, s, p);
+}
+
+void launch_client_kv_find(const ClientKvFindParams& p, uint32_t n_keys, hipStream_t s) {
+    if (n_keys == 0) return;
+    hipLaunchKernelGGL(client_kv_find_kernel, dim3(2u * n_keys), dim3(kClientTpb), 0, s, p);
 }
 
 void launch_client_response_noise(const ClientResponseNoiseParams& p, uint32_t n, hipStream_t s) {

@@ -9,6 +9,7 @@
 // the host, and the device does the rest.
 #include "client_device.h"
 #include "message.h"
+#include "kv_host.h"
 #include "records_host.h"
 
 using namespace spiral;
@@ -616,6 +617,76 @@ int spiral_gpu_client_decode_records(spiral_gpu_client* c, const void* responses
     HIP_OK(hipGetLastError());
     HIP_OK(hipMemcpyAsync(records, rp.buf, out_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_OK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+// ---- keyed records (include/spiral_gpu.h "Keyed records"; kv_host.h): queries for both candidate buckets of each key, and the find on the device -----
+// queries for items b1, b2 of every key, [key][candidate]: both are always made
+int spiral_gpu_client_kv_queries(spiral_gpu_client* c, const void* table_key16, const void* keys, uint64_t key_bytes, uint32_t n, int form, void* out, size_t bytes_each) {
+    if (client_on(c, "client_kv_queries")) return -1;
+    if (!out) return fail("client_kv_queries: null argument");
+    if (n == 0 || n > 32767u) return fail("client_kv_queries: %u keys, a call takes 1 .. 32767", n);
+    uint64_t nb;
+    if (kv_buckets(&c->p, c->out_n, &nb)) return -1;
+    std::vector<KvKey> hk;
+    if (kv_hash_keys("client_kv_queries", nb, table_key16, keys, key_bytes, n, false, hk)) return -1;
+    std::vector<uint64_t> items(2 * (size_t)n);
+    for (uint32_t k = 0; k < n; k++) items[2 * k] = hk[k].b[0], items[2 * k + 1] = hk[k].b[1];
+    return spiral_gpu_client_queries(c, items.data(), 2 * n, form, out, bytes_each);
+}
+
+int spiral_gpu_client_kv_decode(spiral_gpu_client* c, const void* table_key16, const void* keys, uint64_t key_bytes, const void* responses, uint32_t n, int form,
+                                uint64_t value_bytes, void* values, uint8_t* found) {
+    if (client_on(c, "client_kv_decode")) return -1;
+    if (!responses || !values || !found) return fail("client_kv_decode: null argument");
+    if (form != SPIRAL_GPU_RESPONSE_RAW && form != SPIRAL_GPU_RESPONSE_WIRE) return fail("client_kv_decode: unknown response form %d", form);
+    if (n == 0 || n > 32767u) return fail("client_kv_decode: %u keys (two responses each), a call takes 1 .. 32767", n);
+    spiral_gpu_kv_layout l;
+    if (kv_layout(&c->p, value_bytes, &l, c->out_n)) return -1;
+    std::vector<KvKey> hk;
+    if (kv_hash_keys("client_kv_decode", l.buckets, table_key16, keys, key_bytes, n, false, hk)) return -1;
+    std::vector<uint64_t> tags(n);
+    for (uint32_t k = 0; k < n; k++) tags[k] = hk[k].tag;
+    const bool wire = form == SPIRAL_GPU_RESPONSE_WIRE;
+    const size_t wire_each = wire_bytes(&c->p, c->cols);  // a multiple of 256 bytes
+    const size_t in_words = wire ? wire_each / 8 : (size_t)(c->rows + 1) * c->cols * kN, n_resp = 2 * (size_t)n, V = (size_t)value_bytes;
+    // one buffer: [tags][arrival counters][hit flags][staged values, per response] ++ what comes back: [values][found]
+    auto up8 = [](size_t b) { return (b + 7) & ~(size_t)7; };
+    const size_t o_arr = (size_t)n * 8, o_hit = o_arr + up8((size_t)n * 4), o_stage = o_hit + n_resp * 4, o_val = up8(o_stage + n_resp * V), o_found = o_val + (size_t)n * V;
+    const size_t total = o_found + n;
+    if (grow(c->in, n_resp * in_words + 1) || grow(c->out, (total + 7) / 8)) return -1;
+    uint8_t* d = reinterpret_cast<uint8_t*>(c->out.p);
+    HIP_OK(hipMemcpyAsync(c->in.p, responses, n_resp * in_words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(c->in.p + n_resp * in_words, 0, sizeof(uint64_t), c->stream));  // (the word a wire field's window may reach into)
+    HIP_OK(hipMemcpyAsync(d, tags.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_OK(hipMemsetAsync(d + o_arr, 0, o_hit - o_arr, c->stream));
+    ClientKvFindParams fp{};
+    fp.d.sp = centred_of(c) + kN;
+    fp.d.resp = c->in.p;
+    fp.d.rows = c->rows;
+    fp.d.cols = c->cols;
+    fp.d.wire = wire ? 1 : 0;
+    fp.d.w0 = c->p.qprime_bits;
+    fp.d.w1 = wire_bits_rest(&c->p);
+    fp.d.wire_words = wire_each / 8;
+    fp.d.qprime = c->qprime;
+    fp.d.p_db = c->p.p_db;
+    fp.tags = reinterpret_cast<const uint64_t*>(d);
+    fp.arrive = reinterpret_cast<uint32_t*>(d + o_arr);
+    fp.hit = reinterpret_cast<uint32_t*>(d + o_hit);
+    fp.stage = d + o_stage;
+    fp.values = d + o_val;
+    fp.found = d + o_found;
+    fp.w = l.coeff_bits;
+    fp.slots = l.slots;
+    fp.value_bytes = (uint32_t)value_bytes;
+    launch_client_kv_find(fp, n, c->stream);
+    HIP_OK(hipGetLastError());
+    std::vector<uint8_t> back((size_t)n * V + n);
+    HIP_OK(hipMemcpyAsync(back.data(), d + o_val, back.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_OK(hipStreamSynchronize(c->stream));
+    memcpy(values, back.data(), (size_t)n * V);
+    memcpy(found, back.data() + (size_t)n * V, n);
     return 0;
 }
 

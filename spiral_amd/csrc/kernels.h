@@ -818,6 +818,27 @@ struct RecordTrackParams {
 void launch_record_update_tracked(const DeviceTables& t, const RecordWorkParams& p, const RecordTrackParams& k, hipStream_t s);
 void launch_pack_record_update_tracked(const DeviceTables& t, const PackRecordWorkParams& p, const RecordTrackParams& k, hipStream_t s);
 
+// ---- keyed records: the server's probe (kv.hip; the definition: include/spiral_gpu.h "Keyed records") ------------------------------------------
+// One workgroup per distinct candidate bucket of a call: polynomial 0 of the bucket's item from the image in the form it is in (db_plain_device.h),
+// the header's `slots` 8-byte tags packed at w bits in LDS, then
+//   occ[4 e .. 4 e + 3]: entry e's occupancy bitmap, bit s set where tag s is not 0;
+//   slot_out[lookup.y]:  for each of the entry's lookups {tag, output index}, the lowest slot that holds the tag, or 0xFFFFFFFF.
+// entries: {j local to the image, column ii, first lookup, lookups}, in ascending bucket order.  A coefficient that is no plaintext value, or a header
+// coefficient >= 2^w, atomicMin's (entry * 2048 + coefficient) into *err, which the host sets to ~0 before the launch.
+struct KvProbeParams {
+    const uint64_t* db;  // the image in the form `form` names (DBX_PACKED or DBX_LIMBS)
+    const uint4* entries;
+    const ulonglong2* lookups;
+    uint64_t* occ;
+    uint32_t* slot_out;
+    unsigned long long* err;
+    uint32_t n_entries, form;
+    uint32_t num_per, dim0;  // the image's geometry (dim0: the shard's first dimension)
+    uint32_t w, slots;
+    uint64_t p_db;
+};
+void launch_kv_probe(const DeviceTables& t, const KvProbeParams& p, hipStream_t s);
+
 // ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
 // noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]
 // (device memory, 8 words per key) and domain tag `domain`.  raw[b][j][2048]: the raw values mod Q, plus addend[b][j][2048] (mod Q) where addend !=
@@ -876,6 +897,22 @@ struct ClientRecordDecodeParams {
     uint32_t w;
 };
 void launch_client_decode_records(const ClientRecordDecodeParams& p, uint32_t n_entries, hipStream_t s);
+// The client's find of keyed records (include/spiral_gpu.h "Keyed records", spiral_gpu_client_kv_decode): ONE launch, workgroup b = 2 k + candidate
+// per response.  It decodes output polynomial 0 with the decode's operands, convolution and rounding, packs the header's tags at w bits and looks
+// for tags[k]; on a hit it decodes the output polynomials the slot's value bytes touch and stages the V bytes at stage + b * V.  The second of a key's
+// two workgroups to finish (arrive[k], zeroed by the host) settles the key: found[k] = 0, 1 or 2 -- candidate 1 wins -- and the winner's bytes, or
+// zeros, to values + k * V.  d: the decode's arguments (d.out unused).
+struct ClientKvFindParams {
+    ClientDecodeParams d;
+    const uint64_t* tags;  // [n]
+    uint8_t* stage;        // [2 n][V]
+    uint32_t* hit;         // [2 n]: 1 where the response holds the tag
+    uint32_t* arrive;      // [n], zero before the launch
+    uint8_t* values;       // [n][V]
+    uint8_t* found;        // [n]
+    uint32_t w, slots, value_bytes;
+};
+void launch_client_kv_find(const ClientKvFindParams& p, uint32_t n_keys, hipStream_t s);
 // the error e of every coefficient of n responses and its record per output polynomial (include/spiral_gpu.h, spiral_gpu_client_response_noise: the
 // definition), ONE launch, one workgroup per output polynomial.  d: the decode's arguments (d.out unused); with final_form, d.resp holds n
 // unswitched ciphertexts [(rows + 1)][cols][2048] of raw values mod Q and d.wire is 0.  expected: null or [n][rows][cols][2048] values below p_db;

@@ -1,0 +1,234 @@
+// Keyed records on the host side: the definition of include/spiral_gpu.h "Keyed records" as code -- layout, SipHash-2-4, candidate buckets, the
+// placement rule -- and the probe's tables (kv.hip does the device work).  What is written or read afterwards goes through records_host.h's
+// update_record_pieces and read_record_pieces unchanged.  Internal to libspiral_gpu.so.
+#pragma once
+#include <array>
+
+#include "records_host.h"
+
+namespace spiral {
+namespace host {
+
+// the buckets of a parameter set, nb = 2^(nu1 + nu2) (r: the record layout they come from); the hash needs no more than this
+inline int kv_buckets(const spiral_gpu_params* p, uint32_t out_n, uint64_t* nb, spiral_gpu_record_layout* r = nullptr) {
+    if (!p) return fail("null argument");
+    if (out_n) return fail("keyed records are defined for base parameter sets only (out_n = 0), not for a SpiralPack set with out_n = %u", out_n);
+    spiral_gpu_record_layout l;
+    if (record_layout(p, 1, &l)) return -1;
+    *nb = l.capacity / l.per_item;
+    if (*nb < 2) return fail("a keyed table needs at least 2 buckets (nu1 + nu2 >= 1)");
+    if (r) *r = l;
+    return 0;
+}
+
+inline int kv_layout(const spiral_gpu_params* p, uint64_t value_bytes, spiral_gpu_kv_layout* out, uint32_t out_n = 0) {
+    if (!p || !out) return fail("null argument");
+    spiral_gpu_record_layout r;
+    uint64_t nb;
+    if (kv_buckets(p, out_n, &nb, &r)) return -1;
+    if (value_bytes < 1) return fail("a value has at least one byte");
+    if (value_bytes > r.item_bytes) return fail("a value of %llu bytes and its tag do not fit a %llu-byte bucket (slots = 0)", (unsigned long long)value_bytes, (unsigned long long)r.item_bytes);
+    const uint64_t slots = r.item_bytes / (8 + value_bytes);
+    if (slots == 0) return fail("a value of %llu bytes and its tag do not fit a %llu-byte bucket (slots = 0)", (unsigned long long)value_bytes, (unsigned long long)r.item_bytes);
+    if (slots > 256) return fail("a value of %llu bytes gives %llu slots per bucket: at most 256", (unsigned long long)value_bytes, (unsigned long long)slots);
+    if (8 * slots > 256ull * r.coeff_bits)
+        return fail("the %llu tags of a bucket take %llu bytes: the header does not lie inside polynomial 0 (%u bytes)", (unsigned long long)slots,
+                    (unsigned long long)(8 * slots), 256u * r.coeff_bits);
+    spiral_gpu_kv_layout l{};
+    l.coeff_bits = r.coeff_bits;
+    l.slots = (uint32_t)slots;
+    l.value_bytes = value_bytes;
+    l.item_bytes = r.item_bytes;
+    l.buckets = nb;
+    l.capacity = nb * slots;
+    *out = l;
+    return 0;
+}
+
+// SipHash-2-4, 64-bit output (the public algorithm)
+inline uint64_t siphash24(uint64_t k0, uint64_t k1, const uint8_t* m, uint64_t len) {
+    uint64_t v0 = k0 ^ 0x736f6d6570736575ull, v1 = k1 ^ 0x646f72616e646f6dull, v2 = k0 ^ 0x6c7967656e657261ull, v3 = k1 ^ 0x7465646279746573ull;
+    auto rotl = [](uint64_t x, int b) { return (x << b) | (x >> (64 - b)); };
+    auto round = [&] {
+        v0 += v1, v1 = rotl(v1, 13), v1 ^= v0, v0 = rotl(v0, 32);
+        v2 += v3, v3 = rotl(v3, 16), v3 ^= v2;
+        v0 += v3, v3 = rotl(v3, 21), v3 ^= v0;
+        v2 += v1, v1 = rotl(v1, 17), v1 ^= v2, v2 = rotl(v2, 32);
+    };
+    uint64_t i = 0;
+    for (; i + 8 <= len; i += 8) {
+        uint64_t w = 0;
+        for (int b = 0; b < 8; b++) w |= (uint64_t)m[i + b] << (8 * b);
+        v3 ^= w;
+        round(), round();
+        v0 ^= w;
+    }
+    uint64_t last = len << 56;
+    for (int b = 0; i + b < len; b++) last |= (uint64_t)m[i + b] << (8 * b);
+    v3 ^= last;
+    round(), round();
+    v0 ^= last;
+    v2 ^= 0xff;
+    round(), round(), round(), round();
+    return v0 ^ v1 ^ v2 ^ v3;
+}
+
+struct KvKey {
+    uint64_t tag, b[2];
+};
+inline KvKey kv_hash(uint64_t nb, const uint8_t* table_key16, const uint8_t* key, uint64_t key_bytes) {
+    uint64_t k0 = 0, k1 = 0;
+    for (int b = 0; b < 8; b++) k0 |= (uint64_t)table_key16[b] << (8 * b), k1 |= (uint64_t)table_key16[8 + b] << (8 * b);
+    KvKey h;
+    h.tag = siphash24(k0, k1, key, key_bytes);
+    if (h.tag == 0) h.tag = 1;
+    const uint64_t u = siphash24(k0, k1 ^ 0xA5ull, key, key_bytes);
+    h.b[0] = (u & 0xffffffffull) % nb;
+    h.b[1] = (u >> 32) % nb;
+    if (h.b[1] == h.b[0]) h.b[1] = h.b[0] ^ 1ull;
+    return h;
+}
+// the n keys of a call, [n][key_bytes]; two equal tags are refused by position
+inline int kv_hash_keys(const char* what, uint64_t nb, const void* table_key16, const void* keys, uint64_t key_bytes, uint64_t n, bool distinct,
+                        std::vector<KvKey>& out) {
+    if (!table_key16 || (n && key_bytes && !keys)) return fail("%s: null argument", what);
+    if (n > (1ull << 24)) return fail("%s: at most 2^24 keys per call", what);
+    out.resize((size_t)n);
+    static const uint8_t none = 0;
+    for (uint64_t k = 0; k < n; k++)
+        out[k] = kv_hash(nb, static_cast<const uint8_t*>(table_key16), key_bytes ? static_cast<const uint8_t*>(keys) + k * key_bytes : &none, key_bytes);
+    if (distinct && n > 1) {
+        std::vector<std::pair<uint64_t, uint64_t>> byt((size_t)n);
+        for (uint64_t k = 0; k < n; k++) byt[k] = {out[k].tag, k};
+        std::sort(byt.begin(), byt.end());
+        uint64_t best = ~0ull, other = 0;  // the lowest position that repeats an earlier tag
+        for (uint64_t i = 1; i < n; i++)
+            if (byt[i].first == byt[i - 1].first && byt[i].second < best) best = byt[i].second, other = byt[i - 1].second;
+        if (best != ~0ull)
+            return fail("%s: keys %llu and %llu have equal tags (the same key given twice, or a 64-bit collision: one key to this store)", what,
+                        (unsigned long long)other, (unsigned long long)best);
+    }
+    return 0;
+}
+
+// The occupancy of the buckets a call touches, and the rule that places a key ("Placement"): bitmaps[i] belongs to bucket ids[i], ids ascending.
+struct KvTable {
+    uint32_t slots = 0;
+    std::vector<uint64_t> ids;
+    std::vector<std::array<uint64_t, 4>> occ;
+    size_t at(uint64_t bucket) const { return (size_t)(std::lower_bound(ids.begin(), ids.end(), bucket) - ids.begin()); }
+    static uint32_t used(const std::array<uint64_t, 4>& o) { return (uint32_t)(__builtin_popcountll(o[0]) + __builtin_popcountll(o[1]) + __builtin_popcountll(o[2]) + __builtin_popcountll(o[3])); }
+    // a new key's (candidate, slot), or false when both buckets are full; marks the slot used
+    bool place(const KvKey& h, uint32_t* cand, uint32_t* slot) {
+        const size_t i1 = at(h.b[0]), i2 = at(h.b[1]);
+        const uint32_t u1 = used(occ[i1]), u2 = used(occ[i2]);
+        if (u1 >= slots && u2 >= slots) return false;
+        *cand = u2 < u1 ? 1u : 0u;
+        std::array<uint64_t, 4>& o = occ[*cand ? i2 : i1];
+        for (uint32_t s = 0; s < slots; s++)
+            if (!((o[s >> 6] >> (s & 63u)) & 1ull)) {
+                o[s >> 6] |= 1ull << (s & 63u);
+                *slot = s;
+                return true;
+            }
+        return false;
+    }
+};
+
+// where a key of a call ends up or was found: candidate 1 or 2 (0: nowhere) and the slot
+struct KvSlot {
+    uint32_t cand = 0, slot = 0;
+};
+
+constexpr uint32_t kKvNoSlot = 0xFFFFFFFFu;
+
+// The probe: ONE launch over the distinct candidate buckets of `keys` (ascending; one workgroup each) on `st`, then one wait.  table receives the buckets'
+// occupancy, found[k] the (candidate, slot) that holds key k's tag -- candidate 1 first -- or cand = 0.  32 bytes per bucket and 4 per (key, candidate) come back.
+inline int kv_probe(const char* what, ExportWork& W, const DeviceTables& tb, hipStream_t st, const ExportImage& src, const spiral_gpu_kv_layout& l, uint64_t p_db,
+                    const std::vector<KvKey>& keys, KvTable& table, std::vector<KvSlot>& found) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("%s cannot be called while the server's stream is being captured", what);
+    const size_t n = keys.size();
+    found.assign(n, KvSlot{});
+    table.slots = l.slots;
+    table.ids.clear();
+    table.occ.clear();
+    if (n == 0) return 0;
+    struct Want {
+        uint64_t bucket, tag;
+        uint32_t out;
+    };
+    std::vector<Want> want(2 * n);
+    for (size_t k = 0; k < n; k++)
+        for (uint32_t c = 0; c < 2; c++) want[2 * k + c] = Want{keys[k].b[c], keys[k].tag, (uint32_t)(2 * k + c)};
+    std::stable_sort(want.begin(), want.end(), [](const Want& a, const Want& b) { return a.bucket < b.bucket; });
+    std::vector<uint4> entries;
+    std::vector<ulonglong2> lookups(2 * n);
+    for (size_t a = 0; a < want.size();) {
+        size_t b = a;
+        for (; b < want.size() && want[b].bucket == want[a].bucket; b++) lookups[b] = make_ulonglong2(want[b].tag, want[b].out);
+        table.ids.push_back(want[a].bucket);
+        entries.push_back(make_uint4((uint32_t)(want[a].bucket / src.num_per), (uint32_t)(want[a].bucket % src.num_per), (uint32_t)a, (uint32_t)(b - a)));
+        a = b;
+    }
+    const size_t nbk = entries.size();
+    // one buffer: [error word][entries][lookups] ++ (device writes) [occupancy 4 x u64 per bucket][slot per (key, candidate)]
+    const size_t o_ent = 16, o_look = o_ent + nbk * sizeof(uint4), o_occ = o_look + lookups.size() * sizeof(ulonglong2), o_slot = o_occ + nbk * 32;
+    const size_t dev_bytes = o_slot + 2 * n * sizeof(uint32_t), back = dev_bytes - o_occ;
+    if (W.dev.words * 8 < dev_bytes) {
+        W.dev.release();
+        W.dev.words = 0;
+        if (W.dev.alloc((dev_bytes + 7) / 8)) {
+            (void)hipGetLastError();
+            W.dev.p = nullptr;
+            W.dev.words = 0;
+            return fail("no device memory for the probe's tables (%zu bytes)", dev_bytes);
+        }
+    }
+    uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
+    HIP_OK(hipMemsetAsync(d, 0xFF, 16, st));  // the error word: ~0 = every coefficient read so far is a plaintext value
+    HIP_OK(hipMemcpyAsync(d + o_ent, entries.data(), nbk * sizeof(uint4), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d + o_look, lookups.data(), lookups.size() * sizeof(ulonglong2), hipMemcpyHostToDevice, st));
+    KvProbeParams kp{};
+    kp.db = src.db;
+    kp.entries = reinterpret_cast<const uint4*>(d + o_ent);
+    kp.lookups = reinterpret_cast<const ulonglong2*>(d + o_look);
+    kp.occ = reinterpret_cast<uint64_t*>(d + o_occ);
+    kp.slot_out = reinterpret_cast<uint32_t*>(d + o_slot);
+    kp.err = reinterpret_cast<unsigned long long*>(d);
+    kp.n_entries = (uint32_t)nbk;
+    kp.form = src.form;
+    kp.num_per = src.num_per;
+    kp.dim0 = src.dim0;
+    kp.w = l.coeff_bits;
+    kp.slots = l.slots;
+    kp.p_db = p_db;
+    launch_kv_probe(tb, kp, st);
+    HIP_OK(hipGetLastError());
+    std::vector<uint8_t> host(back);
+    unsigned long long err = ~0ull;
+    HIP_OK(hipMemcpyAsync(host.data(), d + o_occ, back, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&err, d, sizeof(err), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (err != ~0ull)
+        return fail("%s: the image holds no keyed table at bucket %llu (polynomial 0, coefficient %u is no plaintext value below 2^coeff_bits): not a record "
+                    "database (fill_db_random, a load_db of arbitrary words, or items loaded with larger coefficients)",
+                    what, (unsigned long long)table.ids[(size_t)(err / kN)], (uint32_t)(err % kN));
+    table.occ.resize(nbk);
+    memcpy(table.occ.data(), host.data(), nbk * 32);
+    const uint32_t* slot = reinterpret_cast<const uint32_t*>(host.data() + nbk * 32);
+    for (size_t k = 0; k < n; k++)
+        for (uint32_t c = 0; c < 2 && !found[k].cand; c++)
+            if (slot[2 * k + c] != kKvNoSlot) found[k] = KvSlot{c + 1, slot[2 * k + c]};
+    return 0;
+}
+
+// tag and value of a key in slot `slot` of image item (j, ii) as two pieces staged at 2 k and 2 k + 1, `stride` = max(8, V) bytes apart
+inline void kv_pieces(const spiral_gpu_kv_layout& l, uint64_t k, uint32_t j, uint32_t ii, uint32_t slot, std::vector<RecordPiece>& pieces) {
+    pieces.push_back(RecordPiece{2 * k, j, ii, 8u * slot, 8u});
+    pieces.push_back(RecordPiece{2 * k + 1, j, ii, (uint32_t)(8u * l.slots + slot * l.value_bytes), (uint32_t)l.value_bytes});
+}
+
+}  // namespace host
+}  // namespace spiral

@@ -3,6 +3,7 @@
 // process_query_fast, reference src/spiral.cpp:2040-2406, 1584-1629).  Everything is kernel launches on one HIP stream; there is no CPU
 // arithmetic path -- without a device every compute entry point fails.  The calls that carry several servers are in server_lanes.cpp, the
 // stateless host-buffer seams in primitives.cpp; what the three share is declared in server_state.h and defined here.
+#include "kv_host.h"
 #include "records_host.h"
 #include "server_state.h"
 
@@ -822,6 +823,156 @@ int spiral_gpu_server_read_records_at(spiral_gpu_server* S, void* records, uint6
     return read_record_pieces(S->xwork, S->tb, S->stream, static_cast<uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, n,
                               [&](uint64_t k, RecordPiece* pc) { return record_piece(S, rc, k, record_ids[k], pc); }, S->img->export_source(),
                               [&](uint64_t pos) { return record_ids[pos]; });
+}
+
+// ---- keyed records (include/spiral_gpu.h "Keyed records"; kv_host.h, kv.hip) --------------------------------------------------------------------
+namespace {
+// how every keyed call opens: the layout, and an unsharded image (both candidates of a key are probed in one place)
+int kv_call(const spiral_gpu_server* S, const char* what, uint64_t value_bytes, spiral_gpu_kv_layout* l) {
+    if (kv_layout(&S->p, value_bytes, l)) return -1;
+    if (S->col.on) return fail("%s: this server is a column shard: keyed records need the whole image in one place (both candidate buckets of a key are probed together)", what);
+    if (S->j0 != 0 || S->j1 != S->s.dim0) return fail("%s: this server is a j-shard (rows [%u, %u) of %u): keyed records need the whole image in one place (both candidate buckets of a key are probed together)", what, S->j0, S->j1, S->s.dim0);
+    return 0;
+}
+// n whole items of the record layout's stream (w bits per coefficient) through load_db_items, widened by a bit where p_db is no power of two
+int load_item_stream(spiral_gpu_server* S, const uint8_t* stream, uint32_t w, uint64_t item_bytes, uint64_t first_item, uint64_t n_items) {
+    const uint32_t cb = (1ull << w) < S->p.p_db ? w + 1 : w;  // (load_db_items wants a width that holds every value below p_db)
+    if (cb == w) return spiral_gpu_server_load_db_items(S, stream, w, first_item, n_items);
+    const uint64_t pass = std::max<uint64_t>(1, std::min<uint64_t>(options().db_stage_bytes / (1024ull * cb), 1u << 12));  // items widened at a time
+    std::vector<uint8_t> wide;
+    for (uint64_t done = 0; done < n_items; done += pass) {
+        const uint64_t cnt = std::min(pass, n_items - done);
+        wide.assign((size_t)(cnt * 1024ull * cb), 0);
+        widen_coeffs(stream + done * item_bytes, wide.data(), (size_t)(cnt * 4 * kN), w, cb);
+        if (spiral_gpu_server_load_db_items(S, wide.data(), cb, first_item + done, cnt)) return -1;
+    }
+    return 0;
+}
+// put, and delete (tag and value bytes of the found slots become zero)
+int kv_write(spiral_gpu_server* S, const char* what, bool put, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values, uint64_t value_bytes,
+             uint64_t n, uint64_t* n_deleted) {
+    if (!S) return fail("null server");
+    if (S->img->owner != S) return fail("%s: this server sweeps another server's database image (share_db or a lane): update it through the owner", what);
+    spiral_gpu_kv_layout l;
+    if (kv_call(S, what, value_bytes, &l)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    HIP_OK(hipSetDevice(S->device));
+    std::vector<KvKey> hk;
+    if (kv_hash_keys(what, l.buckets, table_key16, keys, key_bytes, n, true, hk)) return -1;
+    if (n_deleted) *n_deleted = 0;
+    if (n == 0) return 0;
+    KvTable table;
+    std::vector<KvSlot> at;
+    if (kv_probe(what, S->xwork, S->tb, S->stream, S->img->export_source(), l, S->p.p_db, hk, table, at)) return -1;
+    if (put)
+        for (uint64_t k = 0; k < n; k++) {
+            if (at[k].cand) continue;  // present: that slot is overwritten
+            uint32_t cand, slot;
+            if (!table.place(hk[k], &cand, &slot))
+                return fail("%s: key %llu cannot be placed: its buckets %llu and %llu are both full (%u slots each); nothing was written", what, (unsigned long long)k,
+                            (unsigned long long)hk[k].b[0], (unsigned long long)hk[k].b[1], l.slots);
+            at[k] = KvSlot{cand + 1, slot};
+        }
+    const uint64_t stride = std::max<uint64_t>(8, value_bytes);
+    std::vector<uint64_t> key_of;  // written key -> its position in the call
+    for (uint64_t k = 0; k < n; k++)
+        if (at[k].cand) key_of.push_back(k);
+    const size_t m = key_of.size();
+    if (m == 0) return 0;
+    std::vector<RecordPiece> pieces;
+    pieces.reserve(2 * m);
+    std::vector<uint8_t> stage(2 * m * (size_t)stride, 0);  // [tag, value] per written key, `stride` bytes each; a delete writes zeros
+    for (size_t i = 0; i < m; i++) {
+        const uint64_t k = key_of[i], bucket = hk[k].b[at[k].cand - 1];
+        kv_pieces(l, i, (uint32_t)(bucket / S->s.num_per), (uint32_t)(bucket % S->s.num_per), at[k].slot, pieces);
+        if (put) {
+            for (int b = 0; b < 8; b++) stage[2 * i * (size_t)stride + b] = (uint8_t)(hk[k].tag >> (8 * b));
+            memcpy(&stage[(2 * i + 1) * (size_t)stride], static_cast<const uint8_t*>(values) + k * value_bytes, (size_t)value_bytes);
+        }
+    }
+    FpTrackCtx trk;
+    track_ctx(S, trk);
+    if (update_record_pieces(S->img->upd, S->tb, S->stream, stage.data(), stride, RecordChunk{0, stride}, l.coeff_bits, S->p.p_db, pieces, S->img->update_target(),
+                             S->img->export_source(), [&](uint64_t pos) { return key_of[(size_t)(pos / 2)]; }, RecordTrials{}, trk.t ? &trk : nullptr))
+        return -1;
+    if (n_deleted) *n_deleted = m;
+    return 0;
+}
+}  // namespace
+
+int spiral_gpu_kv_layout_of(const spiral_gpu_params* p, uint64_t value_bytes, spiral_gpu_kv_layout* out) { return kv_layout(p, value_bytes, out); }
+
+int spiral_gpu_kv_hash(const spiral_gpu_params* p, const void* table_key16, const void* key, uint64_t key_bytes, uint64_t* tag, uint64_t* b1, uint64_t* b2) {
+    if (!p || !table_key16 || !tag || !b1 || !b2 || (key_bytes && !key)) return fail("kv_hash: null argument");
+    uint64_t nb;
+    if (kv_buckets(p, 0, &nb)) return -1;
+    static const uint8_t none = 0;
+    const KvKey h = kv_hash(nb, static_cast<const uint8_t*>(table_key16), key_bytes ? static_cast<const uint8_t*>(key) : &none, key_bytes);
+    *tag = h.tag;
+    *b1 = h.b[0];
+    *b2 = h.b[1];
+    return 0;
+}
+
+// A fresh table: placement from empty and the item stream on the host, then load_db_items' ingest of the whole image (not a hot path)
+int spiral_gpu_server_kv_load(spiral_gpu_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values, uint64_t value_bytes, uint64_t n) {
+    if (!S) return fail("null server");
+    if (S->img->owner != S) return fail("kv_load: this server sweeps another server's database image (share_db): load it through the owner");
+    spiral_gpu_kv_layout l;
+    if (kv_call(S, "kv_load", value_bytes, &l)) return -1;
+    if (n && !values) return fail("kv_load: null argument");
+    std::vector<KvKey> hk;
+    if (kv_hash_keys("kv_load", l.buckets, table_key16, keys, key_bytes, n, true, hk)) return -1;
+    KvTable table;
+    table.slots = l.slots;
+    table.ids.resize((size_t)l.buckets);
+    for (uint64_t b = 0; b < l.buckets; b++) table.ids[b] = b;
+    table.occ.assign((size_t)l.buckets, std::array<uint64_t, 4>{});
+    std::vector<uint8_t> stream((size_t)(l.buckets * l.item_bytes), 0);
+    for (uint64_t k = 0; k < n; k++) {
+        uint32_t cand, slot;
+        if (!table.place(hk[k], &cand, &slot))
+            return fail("kv_load: key %llu cannot be placed: its buckets %llu and %llu are both full (%u slots each); the image was not touched", (unsigned long long)k,
+                        (unsigned long long)hk[k].b[0], (unsigned long long)hk[k].b[1], l.slots);
+        uint8_t* item = stream.data() + hk[k].b[cand] * l.item_bytes;
+        for (int b = 0; b < 8; b++) item[8u * slot + b] = (uint8_t)(hk[k].tag >> (8 * b));
+        memcpy(item + 8u * l.slots + slot * value_bytes, static_cast<const uint8_t*>(values) + k * value_bytes, (size_t)value_bytes);
+    }
+    return load_item_stream(S, stream.data(), l.coeff_bits, l.item_bytes, 0, l.buckets);
+}
+
+int spiral_gpu_server_kv_put(spiral_gpu_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values, uint64_t value_bytes, uint64_t n) {
+    if (n && !values) return fail("kv_put: null argument");
+    return kv_write(S, "kv_put", true, table_key16, keys, key_bytes, values, value_bytes, n, nullptr);
+}
+
+int spiral_gpu_server_kv_delete(spiral_gpu_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, uint64_t value_bytes, uint64_t n, uint64_t* n_deleted) {
+    return kv_write(S, "kv_delete", false, table_key16, keys, key_bytes, nullptr, value_bytes, n, n_deleted);
+}
+
+// The probe, then the found slots' values through read_records' path; any server that references the image, on its own stream
+int spiral_gpu_server_kv_get(spiral_gpu_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, void* values, uint64_t value_bytes, uint64_t n,
+                             uint8_t* found) {
+    if (enter(S)) return -1;
+    spiral_gpu_kv_layout l;
+    if (kv_call(S, "kv_get", value_bytes, &l)) return -1;
+    if (n && (!values || !found)) return fail("kv_get: null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    std::vector<KvKey> hk;
+    if (kv_hash_keys("kv_get", l.buckets, table_key16, keys, key_bytes, n, false, hk)) return -1;
+    KvTable table;
+    std::vector<KvSlot> at;
+    if (kv_probe("kv_get", S->xwork, S->tb, S->stream, S->img->export_source(), l, S->p.p_db, hk, table, at)) return -1;
+    for (uint64_t k = 0; k < n; k++) found[k] = (uint8_t)at[k].cand;
+    return read_record_pieces(
+        S->xwork, S->tb, S->stream, static_cast<uint8_t*>(values), value_bytes, RecordChunk{0, value_bytes}, l.coeff_bits, S->p.p_db, n,
+        [&](uint64_t k, RecordPiece* pc) {
+            if (!at[k].cand) return false;
+            const uint64_t bucket = hk[k].b[at[k].cand - 1];
+            *pc = RecordPiece{k, (uint32_t)(bucket / S->s.num_per), (uint32_t)(bucket % S->s.num_per), (uint32_t)(8u * l.slots + at[k].slot * value_bytes), (uint32_t)value_bytes};
+            return true;
+        },
+        S->img->export_source(), [&](uint64_t pos) { return pos; });
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {
