@@ -436,9 +436,9 @@ int spiral_gpu_server_read_records(spiral_gpu_server *s, void *records, uint64_t
                                    uint64_t n_records);
 int spiral_gpu_server_read_records_at(spiral_gpu_server *s, void *records, uint64_t record_bytes, uint32_t instance, const uint64_t *record_ids,
                                       uint64_t n);
-/* ---- Keyed records: put, get and delete by key; bucketised two-choice hashing over the items of a base server -------------------------------
- * The definition, stated once; the C++ (csrc/kv_host.h), the Python and the tests' restatement quote it.  Base parameter sets only (a SpiralPack
- * session or server is refused), one instance, an unsharded image.
+/* ---- Keyed records: put, get and delete by key; bucketised two-choice hashing over the items of a base or a SpiralPack server ----------------
+ * The definition, stated once; the C++ (csrc/kv_host.h), the Python and the tests' restatement quote it.  Base parameter sets first, then
+ * "SpiralPack" below; one instance, an unsharded image.
  *
  * Layout.  w, item_bytes = 1024 w and the item stream are those of "Records".  A bucket is an item: bucket b is item b, in the item order of
  * load_db_items.  For a value size V >= 1, slots = floor(item_bytes / (8 + V)), and the bucket's stream is
@@ -457,7 +457,19 @@ int spiral_gpu_server_read_records_at(spiral_gpu_server *s, void *records, uint6
  * (2) Otherwise the bucket with fewer used slots takes it; a tie goes to b1.  (3) Within the bucket, the lowest free slot.  (4) Both full: the call
  * fails.
  *
- * A coefficient of a probed header that is no plaintext value below 2^w fails the call as a record call fails, naming the first such bucket. */
+ * A coefficient of a probed header that is no plaintext value below 2^w fails the call as a record call fails, naming the first such bucket.
+ *
+ * SpiralPack.  For a SpiralPack parameter set with out_n >= 1 (the spiral_gpu_pack_server_kv_* calls, and a client session created with
+ * out_n >= 1):
+ *   - w, item_bytes = out_n^2 * 256 w and the item stream are those of "Records", SpiralPack: polynomial t of bucket b is item b of trial image t.
+ *   - A bucket is an item, and nb = 2^(nu1 + nu2).
+ *   - slots = floor(item_bytes / (8 + V)), and the bucket's stream is [slots x 8-byte tags][slots x V value bytes][padding], exactly as above.
+ *   - Refused, as above: slots = 0; slots > 256; nb < 2; 8 slots > 256 w -- the header lies inside polynomial 0, which is trial 0, so a probe still
+ *     reads one polynomial per bucket.  A value may span several polynomials, i.e. trial images.
+ *   - Hash and placement are the ones above, word for word.
+ *   (p = 256, out_n = 2, V = 248: 32 slots, as the base server's; p = 256, out_n = 4, V = 4088: 8 slots of a 32 768-byte bucket.)
+ * Out of scope, each refused by name: trial-sharded servers (create_sharded with fewer than all trials, and their shard lanes); values larger
+ * than an item (instances). */
 typedef struct spiral_gpu_kv_layout {
     uint32_t coeff_bits; /* w */
     uint32_t slots;
@@ -492,6 +504,21 @@ int spiral_gpu_server_kv_delete(spiral_gpu_server *s, const void *table_key16, c
                                 uint64_t *n_deleted);
 int spiral_gpu_server_kv_get(spiral_gpu_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, void *values, uint64_t value_bytes,
                              uint64_t n, uint8_t *found);
+/* Table occupancy (a base server here, a SpiralPack server: spiral_gpu_pack_server_kv_stats): how full buckets [first_bucket, first_bucket + n_buckets) of a keyed table with values of value_bytes bytes are, computed where
+ * the image lives.  ONE launch (one per 2^23 buckets of the range, so that a grid stays below 2^32 threads): the probe's gather, inverse transform and header packing of polynomial 0 per bucket -- the bucket's place comes
+ * from the block index, no table is uploaded -- then one integer atomic add per bucket into a histogram, so the result is exact whatever the
+ * order; 257 words come back, not the headers, and used, full_buckets and max_used are derived from them on the host.  Any server that references
+ * the image may call it, lanes included, on its own stream; the call returns synchronised.  Refused inside a capture, on a j-shard, a column shard
+ * and a trial shard, and for a range that is not inside [0, nb]; n_buckets = 0 returns zeros (and `slots`).  A bucket whose polynomial 0 holds a
+ * coefficient that is no plaintext value below 2^w fails the call, naming the lowest such bucket. */
+typedef struct spiral_gpu_kv_stats {
+    uint64_t buckets;      /* n_buckets looked at */
+    uint64_t used;         /* slots whose tag is not 0 */
+    uint64_t full_buckets; /* buckets with used == slots */
+    uint32_t max_used, slots;
+    uint64_t hist[257]; /* hist[u] = buckets with exactly u used slots; entries above `slots` are 0 */
+} spiral_gpu_kv_stats;
+int spiral_gpu_server_kv_stats(spiral_gpu_server *s, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_stats *out);
 
 /* read the device database back in reference layouts (tests): plaintext `item` as its n0 x n2 NTT-form MatPoly
  * (pts_encd, :1128), or slabs z_begin .. z_begin+nz-1 of load_db's layout restricted to this server's j-range:
@@ -901,6 +928,30 @@ int spiral_gpu_pack_server_read_records(spiral_gpu_pack_server *s, void *records
                                         uint64_t n_records);
 int spiral_gpu_pack_server_read_records_at(spiral_gpu_pack_server *s, void *records, uint64_t record_bytes, uint32_t instance,
                                            const uint64_t *record_ids, uint64_t n);
+/* Keyed records for a SpiralPack parameter set and server ("Keyed records", SpiralPack), out_n in 1 .. 16.  layout_of and hash are host only.  The
+ * server calls take the base calls' arguments and keep their contracts: load, put and delete are the owner's (a lane refuses); get and stats work
+ * on any server that references the image, lanes included, on its own stream; refused inside a capture; a failing call leaves every trial image
+ * byte-identical; the images keep their current form (packed or plain, limb planes, the pair form), no epoch, no re-captured graph; tracked
+ * fingerprints stay current; a key whose two buckets are full fails the call with the base server's message.  The probe reads polynomial 0 of a
+ * bucket from trial image 0; tag and value go through pack_server_update_records' path -- a put that touches many trials is still one upload, one
+ * read-modify-write launch and one scatter launch -- and pack_server_read_records' path.  load places every key on the host first (a key that
+ * cannot be placed fails the call before anything else is built), then builds the item stream a pass of at most 2^14 buckets at a time -- host
+ * memory beyond the caller's keys and values is that pass (512 MiB at 32 KiB buckets) and 24 bytes per key, not the table -- and loads polynomial t
+ * of each bucket into trial t through pack_server_load_db_items.  A server that holds fewer than all trials (create_sharded, create_shard_lane) refuses every
+ * call by name. */
+int spiral_gpu_pack_kv_layout_of(const spiral_gpu_params *p, uint32_t out_n, uint64_t value_bytes, spiral_gpu_kv_layout *out);
+int spiral_gpu_pack_kv_hash(const spiral_gpu_params *p, uint32_t out_n, const void *table_key16, const void *key, uint64_t key_bytes, uint64_t *tag,
+                            uint64_t *b1, uint64_t *b2);
+int spiral_gpu_pack_server_kv_load(spiral_gpu_pack_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, const void *values,
+                                   uint64_t value_bytes, uint64_t n);
+int spiral_gpu_pack_server_kv_put(spiral_gpu_pack_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, const void *values,
+                                  uint64_t value_bytes, uint64_t n);
+int spiral_gpu_pack_server_kv_delete(spiral_gpu_pack_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, uint64_t value_bytes,
+                                     uint64_t n, uint64_t *n_deleted);
+int spiral_gpu_pack_server_kv_get(spiral_gpu_pack_server *s, const void *table_key16, const void *keys, uint64_t key_bytes, void *values,
+                                  uint64_t value_bytes, uint64_t n, uint8_t *found);
+int spiral_gpu_pack_server_kv_stats(spiral_gpu_pack_server *s, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets,
+                                    spiral_gpu_kv_stats *out);
 /* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv).  A null pointer
  * among those the geometry needs fails before anything is written: the previous public parameters stay (as for spiral_gpu_server_set_pub_params). */
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server *s, const uint64_t *w_left, const uint64_t *w_right,
@@ -1228,7 +1279,8 @@ int spiral_gpu_client_record_queries(spiral_gpu_client *c, uint64_t record_bytes
                                      size_t bytes_each);
 int spiral_gpu_client_decode_records(spiral_gpu_client *c, const void *responses, uint32_t n, int form, uint64_t record_bytes,
                                      const uint64_t *record_ids, void *records);
-/* Keyed records ("Keyed records" above; base sessions only, out_n = 0).
+/* Keyed records ("Keyed records" above; a base session, or one created with out_n >= 1, whose responses are SpiralPack responses: the header is in
+ * output polynomial (0, 0), polynomial t of a value at (t / out_n, t % out_n), up to out_n^2 of them, taken in ascending order).
  * kv_queries: spiral_gpu_client_queries for the items b1, b2 of each key: 2 n queries laid out [key][candidate], under 2 n message numbers.  BOTH
  * are always made, whichever bucket holds the key and whether or not it is present: what a server sees does not depend on the table's content.
  * kv_decode: `responses` holds the 2 n responses laid out [key][candidate], in RAW or WIRE form as decode takes them (2 n <= 65535).  One launch,

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -69,6 +70,13 @@ class KvLayout(C.Structure):
 
     _fields_ = [("coeff_bits", C.c_uint32), ("slots", C.c_uint32), ("value_bytes", C.c_uint64), ("item_bytes", C.c_uint64), ("buckets", C.c_uint64),
                 ("capacity", C.c_uint64)]
+
+
+class KvStatsStruct(C.Structure):
+    """spiral_gpu_kv_stats (include/spiral_gpu.h, spiral_gpu_server_kv_stats)"""
+
+    _fields_ = [("buckets", C.c_uint64), ("used", C.c_uint64), ("full_buckets", C.c_uint64), ("max_used", C.c_uint32), ("slots", C.c_uint32),
+                ("hist", C.c_uint64 * 257)]
 
 
 U64P = C.POINTER(C.c_uint64)
@@ -301,6 +309,14 @@ PROTOTYPES = {
     "spiral_gpu_server_kv_put": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]),
     "spiral_gpu_server_kv_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, U64P]),
     "spiral_gpu_server_kv_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "spiral_gpu_server_kv_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(KvStatsStruct)]),
+    "spiral_gpu_pack_kv_layout_of": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_uint64, C.POINTER(KvLayout)]),
+    "spiral_gpu_pack_kv_hash": (C.c_int, [C.POINTER(Params), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, U64P, U64P, U64P]),
+    "spiral_gpu_pack_server_kv_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_pack_server_kv_put": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "spiral_gpu_pack_server_kv_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, U64P]),
+    "spiral_gpu_pack_server_kv_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "spiral_gpu_pack_server_kv_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(KvStatsStruct)]),
     "spiral_gpu_client_kv_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_kv_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
     "spiral_gpu_client_record_queries": (C.c_int, [C.c_void_p, C.c_uint64, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
@@ -394,14 +410,34 @@ def record_layout(params: Params, record_bytes: int, out_n: int = 0) -> RecordLa
 # ---- keyed records (include/spiral_gpu.h "Keyed records") ----
 def kv_layout(params: Params, value_bytes: int, out_n: int = 0) -> KvLayout:
     """the layout of keyed records with values of value_bytes bytes in the buckets of `params`, host only; raises for a value size the definition
-    refuses (slots = 0, slots > 256, a header beyond polynomial 0), for fewer than 2 buckets and for a SpiralPack parameter set (out_n >= 1)"""
+    refuses (slots = 0, slots > 256, a header beyond polynomial 0) and for fewer than 2 buckets.  This is the layout of a BASE parameter set (buckets
+    of 4 polynomials), as spiral_gpu_kv_layout_of: out_n >= 1 is refused by name -- a SpiralPack set has pack_kv_layout, as the C ABI has
+    spiral_gpu_pack_kv_layout_of"""
     if not isinstance(value_bytes, (int, np.integer)) or isinstance(value_bytes, bool) or not 0 <= value_bytes < 2**64:
         raise ValueError(f"value_bytes = {value_bytes!r} is no byte count")
     if out_n:
-        raise SpiralGpuError(f"keyed records are defined for base parameter sets only (out_n = 0), not for a SpiralPack set with out_n = {out_n}")
+        raise SpiralGpuError(f"kv_layout is the layout of base parameter sets only (out_n = 0); for a SpiralPack set with out_n = {out_n} call "
+                             f"pack_kv_layout(params, out_n, value_bytes)")
     out = KvLayout()
     check(lib().spiral_gpu_kv_layout_of(C.byref(params), int(value_bytes), C.byref(out)))
     return out
+
+
+def pack_kv_layout(params: Params, out_n: int, value_bytes: int) -> KvLayout:
+    """kv_layout for a SpiralPack parameter set with out_n in 1 .. 16: a bucket is an item of out_n^2 polynomials, one per trial image (include/spiral_gpu.h
+    "Keyed records", SpiralPack), host only; the same refusals"""
+    if not isinstance(value_bytes, (int, np.integer)) or isinstance(value_bytes, bool) or not 0 <= value_bytes < 2**64:
+        raise ValueError(f"value_bytes = {value_bytes!r} is no byte count")
+    if not isinstance(out_n, (int, np.integer)) or isinstance(out_n, bool) or not 0 <= out_n < 2**32:
+        raise ValueError(f"out_n = {out_n!r} is no SpiralPack dimension")
+    out = KvLayout()
+    check(lib().spiral_gpu_pack_kv_layout_of(C.byref(params), int(out_n), int(value_bytes), C.byref(out)))
+    return out
+
+
+def kv_layout_for(params: Params, value_bytes: int, out_n: int) -> KvLayout:
+    """the layout a server or session with this out_n uses (0: base)"""
+    return pack_kv_layout(params, out_n, value_bytes) if out_n else kv_layout(params, value_bytes)
 
 
 def kv_table_key(table_key) -> np.ndarray:
@@ -425,14 +461,94 @@ def kv_keys(keys) -> np.ndarray:
     return np.frombuffer(b"".join(keys), dtype=np.uint8).reshape(len(keys), width).copy()
 
 
-def kv_hash(params: Params, table_key, key) -> tuple[int, int, int]:
-    """(tag, b1, b2) of one key under the 16-byte table key: the definition's SipHash-2-4 values, host only"""
+def kv_hash(params: Params, table_key, key, out_n: int = 0) -> tuple[int, int, int]:
+    """(tag, b1, b2) of one key under the 16-byte table key: the definition's SipHash-2-4 values, host only (out_n >= 1: a SpiralPack set, spiral_gpu_pack_kv_hash; the values depend
+    on nu1 + nu2 alone)"""
     tk = kv_table_key(table_key)
     kb = np.frombuffer(bytes(key), dtype=np.uint8)
     tag, b1, b2 = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    check(lib().spiral_gpu_kv_hash(C.byref(params), tk.ctypes.data_as(C.c_void_p), kb.ctypes.data_as(C.c_void_p) if kb.size else None, kb.size, C.byref(tag),
-                                   C.byref(b1), C.byref(b2)))
+    args = (tk.ctypes.data_as(C.c_void_p), kb.ctypes.data_as(C.c_void_p) if kb.size else None, kb.size, C.byref(tag), C.byref(b1), C.byref(b2))
+    if out_n:
+        check(lib().spiral_gpu_pack_kv_hash(C.byref(params), int(out_n), *args))
+    else:
+        check(lib().spiral_gpu_kv_hash(C.byref(params), *args))
     return tag.value, b1.value, b2.value
+
+
+@dataclass(frozen=True)
+class KvStats:
+    """the occupancy of a range of buckets of a keyed table (include/spiral_gpu.h, spiral_gpu_server_kv_stats): hist[u] = buckets with exactly u used
+    slots, u = 0 .. slots"""
+
+    buckets: int
+    used: int
+    full_buckets: int
+    max_used: int
+    slots: int
+    hist: tuple
+
+    def load(self) -> float:
+        """used / (buckets * slots); 0.0 for an empty range"""
+        return self.used / (self.buckets * self.slots) if self.buckets else 0.0
+
+
+class KeyedRecords:
+    """the keyed-record calls of Server and PackServer (include/spiral_gpu.h "Keyed records"): a bucket is an item, a key hashes to two candidate
+    buckets.  The class says which library calls are its own (_kv_prefix); out_n (PackServer) selects the SpiralPack layout"""
+
+    def _kv(self, name: str):
+        return getattr(lib(), f"{self._kv_prefix}_kv_{name}")
+
+    def _kv_args(self, table_key, keys, values=None, value_bytes=None):
+        tk, keys = kv_table_key(table_key), kv_keys(keys)
+        if values is not None:
+            values = np.ascontiguousarray(values)
+            if values.dtype != np.uint8 or values.ndim != 2 or values.shape[0] != keys.shape[0]:
+                raise ValueError(f"values are a uint8 array [n][value_bytes] with one row per key ({keys.shape[0]})")
+            value_bytes = values.shape[1]
+        kv_layout_for(self.params, value_bytes, getattr(self, "out_n", 0))
+        kp = keys.ctypes.data_as(C.c_void_p) if keys.size else None
+        return tk, keys, kp, values, int(value_bytes)
+
+    def kv_load(self, table_key, keys, values):
+        """a fresh keyed table from keys [n][key_bytes] and values [n][value_bytes]: placed from empty on the host, loaded through load_db_items (a
+        SpiralPack server: every trial image)"""
+        tk, keys, kp, values, vb = self._kv_args(table_key, keys, values)
+        check(self._kv("load")(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], values.ctypes.data_as(C.c_void_p), vb, keys.shape[0]))
+        return self
+
+    def kv_put(self, table_key, keys, values):
+        """insert or overwrite keys in place, in the image's current form: one probe launch, the placement rule on the host, update_records' write;
+        fails with nothing written where a key's two buckets are full; see include/spiral_gpu.h spiral_gpu_server_kv_put"""
+        tk, keys, kp, values, vb = self._kv_args(table_key, keys, values)
+        check(self._kv("put")(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], values.ctypes.data_as(C.c_void_p), vb, keys.shape[0]))
+
+    def kv_delete(self, table_key, keys, value_bytes: int) -> int:
+        """zero tag and value of every key that is present; returns how many were (an absent key is not an error)"""
+        tk, keys, kp, _, vb = self._kv_args(table_key, keys, None, value_bytes)
+        n = C.c_uint64()
+        check(self._kv("delete")(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], vb, keys.shape[0], C.byref(n)))
+        return n.value
+
+    def kv_get(self, table_key, keys, value_bytes: int, out: np.ndarray | None = None):
+        """(values uint8 [n][value_bytes], found uint8 [n]): found[k] is 0 (absent), 1 or 2 (the candidate bucket that holds the key); the bytes of an
+        absent key are left as they are in `out` (zero in a fresh array).  Any server that references the image, lanes included"""
+        tk, keys, kp, _, vb = self._kv_args(table_key, keys, None, value_bytes)
+        out = record_out(vb, keys.shape[0], out)
+        found = np.zeros(keys.shape[0], dtype=np.uint8)
+        check(self._kv("get")(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], out.ctypes.data_as(C.c_void_p), vb, keys.shape[0],
+                              found.ctypes.data_as(C.c_void_p)))
+        return out.reshape(keys.shape[0], vb), found
+
+    def kv_stats(self, value_bytes: int, first_bucket: int = 0, n_buckets: int | None = None) -> KvStats:
+        """how full buckets [first_bucket, first_bucket + n_buckets) are (n_buckets None: to the table's end): one launch, a histogram of used slots
+        per bucket comes back, not the headers.  Any server that references the image, lanes included"""
+        lay = kv_layout_for(self.params, value_bytes, getattr(self, "out_n", 0))
+        if n_buckets is None:
+            n_buckets = max(lay.buckets - first_bucket, 0)
+        out = KvStatsStruct()
+        check(self._kv("stats")(self.h, int(value_bytes), int(first_bucket), int(n_buckets), C.byref(out)))
+        return KvStats(int(out.buckets), int(out.used), int(out.full_buckets), int(out.max_used), int(out.slots), tuple(int(x) for x in out.hist))
 
 
 def record_array(records, record_bytes: int, n: int | None = None) -> np.ndarray:

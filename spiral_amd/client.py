@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U64P, check, kv_keys, kv_layout, kv_table_key, lib, read_ids, record_layout, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, PackShape, Params, Shape, U64P, check, kv_keys, kv_layout_for, kv_table_key, lib, read_ids, record_layout, wire_bytes
 
 N = 2048
 RESPONSE_RAW, RESPONSE_WIRE = 0, 1  # spiral_gpu_response_form
@@ -175,12 +175,10 @@ class Client:
                                                      out.ctypes.data_as(C.c_void_p)))
         return out
 
-    # ---- keyed records (include/spiral_gpu.h "Keyed records"; base sessions only) ----
+    # ---- keyed records (include/spiral_gpu.h "Keyed records"; a base session, or a SpiralPack session created with out_n >= 1) ----
     def kv_queries(self, table_key, keys, form="seeded") -> np.ndarray:
         """queries() for both candidate buckets of every key, laid out [key][candidate] under 2 n message numbers; both are always made"""
         f = _message_form(form)
-        if self.out_n:
-            kv_layout(self.params, 1, self.out_n)  # (raises: base sessions only)
         tk, keys = kv_table_key(table_key), kv_keys(keys)
         n, each = keys.shape[0], self._bytes["query", f]
         out = np.zeros((2 * n, each), dtype=np.uint8)
@@ -193,7 +191,7 @@ class Client:
         (absent: its value bytes are zero), 1 or 2; one launch finds the tag in the headers and decodes only what the found value touches"""
         if form not in _FORMS:
             raise ValueError(f"response form {form!r}: 'raw' or 'wire'")
-        kv_layout(self.params, value_bytes, self.out_n)
+        kv_layout_for(self.params, value_bytes, self.out_n)
         tk, keys = kv_table_key(table_key), kv_keys(keys)
         n = keys.shape[0]
         if form == "raw":

@@ -5,6 +5,7 @@
 //            [--wire-input] [--seeded] [--key-store [compact]] [--query-batch] [--device-client [--output-err F]]
 //   ./spiral <nu1> <nu2> <RECORD> a --record-bytes S [--device-client]      (a record of S bytes: run_records below)
 //   ./spiral <nu1> <nu2> <RECORD> a --high-rate --pack-record-bytes S [--device-client]   (the same on SpiralPack servers: run_pack_records below)
+//   ./spiral <nu1> <nu2> <KEY NUMBER> a --kv-value-bytes V --device-client [--high-rate]   (a keyed table of V-byte values: run_kv below)
 //
 // The reference fixes its scheme parameters at compile time (-DTEXP ... -DOUTN, include/values.h:78-93,
 // select_params.py:337); here the same nine values are read at run time from the environment variables or
@@ -545,6 +546,124 @@ static int run_pack_records(const spiral_gpu_params& p, uint32_t out_n, uint64_t
     return all_ok ? 0 : 2;
 }
 
+// ---- --kv-value-bytes V --device-client [--high-rate]: the third argument is a KEY number (include/spiral_gpu.h "Keyed records") ---------------------
+// Keys are "key-%08d", the table key is the bytes 00 .. 0f, and the value of key k in generation g is record_bytes_of(g, k, V) -- the record runs'
+// generator.  One run: kv_load of keys 0 .. n - 1 with n = half of the capacity -- or, where the placement rule refuses that many (buckets of two or
+// three slots overflow early), the longest prefix it accepts, found by bisection over kv_load calls, which fail before they touch the image --; key
+// number K is looked up privately (kv_queries, two answers, kv_decode) and compared with the generator, or, for K >= n, must not be found; it is
+// written by kv_put in generation 1 and looked up again; one key that was never stored is looked up; kv_stats reports the table's load.  On a base
+// server, or with --high-rate on a SpiralPack server with OUTN as out_n.
+static int run_kv(const spiral_gpu_params& p, uint32_t out_n, uint64_t key_no, uint64_t V, uint64_t seed, bool nonoise) {
+    if (out_n) cout << "Using n=" << out_n << endl;
+    spiral_gpu_kv_layout lay;
+    GPU_OK(out_n ? spiral_gpu_pack_kv_layout_of(&p, out_n, V, &lay) : spiral_gpu_kv_layout_of(&p, V, &lay));
+    if (key_no >= 50000000ull) {
+        fprintf(stderr, "spiral: key number %llu out of range (below 50000000: keys are \"key-%%08d\")\n", (unsigned long long)key_no);
+        return 1;
+    }
+    cout << "Keyed records of " << V << "-byte values: " << lay.slots << " slots per bucket of " << lay.item_bytes << " bytes, " << lay.buckets << " buckets, capacity "
+         << lay.capacity << endl;
+    uint8_t tk[16];
+    for (int b = 0; b < 16; b++) tk[b] = (uint8_t)b;
+    constexpr uint64_t KB = 12;  // bytes of a key
+    auto key_of = [](uint64_t k, uint8_t* out) {
+        char text[32];
+        snprintf(text, sizeof(text), "key-%08llu", (unsigned long long)k);
+        memcpy(out, text, KB);
+    };
+    spiral_gpu_server* base = nullptr;
+    spiral_gpu_pack_server* pack = nullptr;
+    if (out_n)
+        GPU_OK(spiral_gpu_pack_server_create(&p, out_n, 0, &pack));
+    else
+        GPU_OK(spiral_gpu_server_create(&p, 0, 0, 0, &base));
+    cout << "starting generation of db" << endl;
+    const uint64_t half = lay.capacity / 2;
+    std::vector<uint8_t> keys((size_t)(half * KB)), vals((size_t)(half * V));
+    for (uint64_t k = 0; k < half; k++) key_of(k, keys.data() + k * KB), record_bytes_of(0, k, V, vals.data() + k * V);
+    auto load = [&](uint64_t n) { return out_n ? spiral_gpu_pack_server_kv_load(pack, tk, keys.data(), KB, vals.data(), V, n) : spiral_gpu_server_kv_load(base, tk, keys.data(), KB, vals.data(), V, n); };
+    uint64_t n_loaded = half;
+    if (load(half)) {  // the longest prefix the placement rule accepts: [lo places, hi does not)
+        uint64_t lo = 0, hi = half;
+        while (hi - lo > 1) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            (load(mid) ? hi : lo) = mid;
+        }
+        n_loaded = lo;
+        GPU_OK(load(n_loaded));
+    }
+    cout << "done loading/generating db: " << n_loaded << " keys (half of the capacity: " << half << ")" << endl;
+    // a session for either kind of client; the servers take its public parameters in the NTT form
+    std::shared_ptr<spiral_gpu_client> session;
+    size_t query_words;
+    if (out_n) {
+        PackClient cl(p, out_n, seed, nonoise);
+        cl.form = SPIRAL_GPU_FORM_NTT;
+        cl.keygen();
+        cl.gen_pub_params();
+        GPU_OK(spiral_gpu_pack_server_set_pub_params(pack, cl.w_left.data(), cl.w_right.data(), cl.v.data(), cl.v_w.data()));
+        session = cl.session;
+        query_words = cl.query(0).cts.size();
+    } else {
+        Client cl(p, seed, nonoise);
+        cl.form = SPIRAL_GPU_FORM_NTT;
+        cl.keygen();
+        cl.gen_pub_params();
+        GPU_OK(spiral_gpu_server_set_pub_params(base, cl.w_left.data(), cl.w_right.data(), cl.w.data(), cl.v.data()));
+        session = cl.session;
+        query_words = cl.query(0).cts.size();
+    }
+    const size_t resp_words = out_n ? (size_t)(out_n + 1) * out_n * N : 6 * N;
+    Poly queries(2 * query_words), resps(2 * resp_words), final_ct(6 * N);
+    std::vector<uint8_t> got((size_t)V), want((size_t)V);
+    // one private lookup: both candidates' queries, two answers, the find on the device
+    auto lookup = [&](const uint8_t* key, uint8_t* found) -> int {
+        GPU_OK(spiral_gpu_client_kv_queries(session.get(), tk, key, KB, 1, SPIRAL_GPU_FORM_NTT, queries.data(), query_words * sizeof(uint64_t)));
+        cout << "Beginning query processing..." << endl;
+        double us[8];
+        for (int c = 0; c < 2; c++) {
+            if (out_n)
+                GPU_OK(spiral_gpu_pack_server_answer(pack, queries.data() + c * query_words, resps.data() + c * resp_words, nullptr, us));
+            else
+                GPU_OK(spiral_gpu_server_answer(base, queries.data() + c * query_words, final_ct.data(), resps.data() + c * resp_words, us));
+        }
+        cout << "Done with query processing!" << endl;
+        GPU_OK(spiral_gpu_client_kv_decode(session.get(), tk, key, KB, resps.data(), 1, SPIRAL_GPU_RESPONSE_RAW, V, got.data(), found));
+        return 0;
+    };
+    uint8_t key[KB], found = 0;
+    key_of(key_no, key);
+    const std::string name((const char*)key, KB);
+    bool all_ok = true;
+    for (uint32_t generation = 0; generation < 2; generation++) {
+        if (generation) {  // insert or overwrite, in place
+            record_bytes_of(1, key_no, V, want.data());
+            GPU_OK(out_n ? spiral_gpu_pack_server_kv_put(pack, tk, key, KB, want.data(), V, 1) : spiral_gpu_server_kv_put(base, tk, key, KB, want.data(), V, 1));
+        }
+        if (lookup(key, &found)) return 1;
+        const bool stored = generation || key_no < n_loaded;
+        record_bytes_of(generation, key_no, V, want.data());
+        if (!stored) std::fill(want.begin(), want.end(), (uint8_t)0);  // (an absent key's value bytes are zero)
+        const bool ok = (found != 0) == stored && got == want;
+        all_ok = all_ok && ok;
+        cout << "Key " << name << (generation ? " after kv_put" : " as loaded") << ", found: " << (int)found << ", correct: " << (ok ? 1 : 0) << endl;
+    }
+    key_of(50000000ull + key_no, key);  // (never loaded, never put)
+    if (lookup(key, &found)) return 1;
+    all_ok = all_ok && found == 0;
+    cout << "Absent key, found: " << (int)found << endl;
+    spiral_gpu_kv_stats st;
+    GPU_OK(out_n ? spiral_gpu_pack_server_kv_stats(pack, V, 0, lay.buckets, &st) : spiral_gpu_server_kv_stats(base, V, 0, lay.buckets, &st));
+    const uint64_t stored_now = n_loaded + (key_no < n_loaded ? 0 : 1);
+    all_ok = all_ok && st.used == stored_now;
+    cout << "Table load (kv_stats): " << st.used << " of " << lay.capacity << " slots used, load " << (double)st.used / (double)lay.capacity << ", fullest bucket "
+         << st.max_used << " of " << st.slots << ", full buckets " << st.full_buckets << endl;
+    cout << "Is correct?: " << (all_ok ? 1 : 0) << endl;
+    if (pack) spiral_gpu_pack_server_destroy(pack);
+    if (base) spiral_gpu_server_destroy(base);
+    return all_ok ? 0 : 2;
+}
+
 int main(int argc, char** argv) {
     if (argc < 4) {
         fprintf(stderr, "usage: %s <nu1> <nu2> <IDX_TARGET> [dbfile|a] [--random-data] [--direct-upload] [--nonoise] [--show-diff] [--output-err F] [--seed N]\n", argv[0]);
@@ -561,6 +680,8 @@ int main(int argc, char** argv) {
     bool record_run = false;
     uint64_t pack_record_bytes = 0;  // --high-rate --pack-record-bytes S: the same on SpiralPack servers (run_pack_records above)
     bool pack_record_run = false;
+    uint64_t kv_value_bytes = 0;  // --kv-value-bytes V --device-client [--high-rate]: IDX_TARGET is a key number (run_kv above)
+    bool kv_run = false;
     // as the reference (random_device, src/core.cpp:202; it labels its own generator NOT SECURE): two words of it.
     // This client is a test harness for the server path, not a hardened client.
     std::random_device rd;
@@ -614,6 +735,27 @@ int main(int argc, char** argv) {
             pack_record_run = true;
             if (i + 1 < argc) pack_record_bytes = strtoull(argv[++i], nullptr, 10);
         }
+        // --kv-value-bytes V with --device-client (and --high-rate for a SpiralPack server): IDX_TARGET names key number K of a keyed table (run_kv above)
+        if (!strcmp(argv[i], "--kv-value-bytes")) {
+            kv_run = true;
+            if (i + 1 < argc) kv_value_bytes = strtoull(argv[++i], nullptr, 10);
+        }
+    }
+    if (kv_run) {
+        if (kv_value_bytes == 0) {
+            fprintf(stderr, "spiral: --kv-value-bytes takes a value size of at least 1 byte\n");
+            return 1;
+        }
+        if (!g_device_client) {
+            fprintf(stderr, "spiral: --kv-value-bytes takes --device-client (the lookup's queries and its find run in a client session on the device)\n");
+            return 1;
+        }
+        const char* with = record_run ? "--record-bytes" : pack_record_run ? "--pack-record-bytes" : key_store >= 0 ? "--key-store" : query_batch ? "--query-batch"
+                           : instances ? "--instances" : batch ? "--batch" : g_wire ? "--wire-input / --seeded" : !g_output_err.empty() ? "--output-err" : nullptr;
+        if (with) {
+            fprintf(stderr, "spiral: --kv-value-bytes does not go with %s (a run of its own: load, private lookups of one key, kv_put, kv_stats)\n", with);
+            return 1;
+        }
     }
     if (pack_record_run) {
         if (pack_record_bytes == 0) {
@@ -666,7 +808,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: --key-store takes --batch B in 2 .. 8 (not with --instances or --high-rate)\n");
         return 1;
     }
-    if (!record_run && !pack_record_run && idx_target >= total_n) {
+    if (!record_run && !pack_record_run && !kv_run && idx_target >= total_n) {
         fprintf(stderr, "spiral: IDX_TARGET %llu out of range (n = %llu)\n", (unsigned long long)idx_target, (unsigned long long)total_n);
         return 1;
     }
@@ -694,6 +836,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: no ROCm device found; this build has no CPU path\n");
         return 1;
     }
+    if (kv_run) return run_kv(p, high_rate ? (uint32_t)param(argc, argv, "OUTN", 2) : 0u, idx_target, kv_value_bytes, seed, nonoise);
     if (record_run) return run_records(p, idx_target, record_bytes, seed, nonoise);
     if (pack_record_run) return run_pack_records(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, pack_record_bytes, seed, nonoise);
     if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch, instances);

@@ -621,6 +621,9 @@ int spiral_gpu_client_decode_records(spiral_gpu_client* c, const void* responses
 }
 
 // ---- keyed records (include/spiral_gpu.h "Keyed records"; kv_host.h): queries for both candidate buckets of each key, and the find on the device -----
+// A SpiralPack session (out_n >= 1) takes the same two calls: a bucket is an item of out_n^2 polynomials, the header is in output polynomial (0, 0) and
+// the find walks the value's polynomials t as (t / out_n, t % out_n).  The find's byte offsets are 32-bit: 8 slots + slot V < item_bytes <= 16^2 * 256 *
+// 40 bytes < 2^22, and the stage of 2 n V bytes is indexed in size_t.
 // queries for items b1, b2 of every key, [key][candidate]: both are always made
 int spiral_gpu_client_kv_queries(spiral_gpu_client* c, const void* table_key16, const void* keys, uint64_t key_bytes, uint32_t n, int form, void* out, size_t bytes_each) {
     if (client_on(c, "client_kv_queries")) return -1;

@@ -837,7 +837,22 @@ struct KvProbeParams {
     uint32_t w, slots;
     uint64_t p_db;
 };
-void launch_kv_probe(const DeviceTables& t, const KvProbeParams& p, hipStream_t s);
+// pack: the image is trial image 0 of a SpiralPack server (polynomial 0 of a bucket is its item there), in the form DBX_PACKED, DBX_LIMBS or DBX_LIMBS8
+void launch_kv_probe(const DeviceTables& t, const KvProbeParams& p, bool pack, hipStream_t s);
+// Table occupancy (include/spiral_gpu.h spiral_gpu_server_kv_stats): the probe's work on buckets [first_bucket, + n_buckets) -- bucket b is image item
+// (b / num_per, b % num_per), so no table is uploaded -- and one atomic add per bucket: hist[u] += 1 for a bucket with u used slots (tags that are
+// not 0).  hist: 257 words, zero before the launch.  *err as for the probe, with the BUCKET in the entry's place: (bucket * 2048 + coefficient).
+struct KvStatsParams {
+    const uint64_t* db;  // as KvProbeParams
+    unsigned long long* hist;
+    unsigned long long* err;
+    uint32_t first_bucket, n_buckets;  // one workgroup per bucket
+    uint32_t form;
+    uint32_t num_per, dim0;
+    uint32_t w, slots;
+    uint64_t p_db;
+};
+void launch_kv_stats(const DeviceTables& t, const KvStatsParams& p, bool pack, hipStream_t s);
 
 // ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
 // noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]

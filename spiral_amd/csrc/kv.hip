@@ -3,6 +3,14 @@
 // transform + unlift of polynomial 0 (db_plain_device.h), the header's tags packed at w bits in LDS, then 32 bytes of occupancy per bucket and 4 bytes
 // per (key, candidate) go out -- the host never sees the headers.  The launch bounds are the export's and the record kernels' (256, 6): at the
 // transforms' (256, 8) the getters' addresses spill.
+//
+// SpiralPack (spiral_gpu_pack_server_kv_*): the same body with PACK = true.  Polynomial 0 of a bucket is the bucket's item in trial image 0, so the
+// launch takes trial 0's image and image_poly_plain<FORM, true> reads the packed or plain layout, the limb planes and the 8-column pair form.  The base
+// kernels keep their names, arguments and resources (profiles/pack_kv_resource_usage.txt).
+//
+// Table occupancy (spiral_gpu_server_kv_stats / spiral_gpu_pack_server_kv_stats; kernels.h KvStatsParams): the probe's gather, transform and header
+// packing over a range of buckets, whose (j, ii) come from the block index -- no table goes up -- and ONE integer atomic add per bucket into a
+// histogram of used slots, 257 words that come back instead of the headers.
 #include "db_plain_device.h"
 #include "kernels.h"
 #include "ntt_device.h"
@@ -13,29 +21,33 @@ namespace {
 
 constexpr uint32_t kKvNoSlot = 0xFFFFFFFFu;
 
-template <uint32_t FORM>
-__global__ __launch_bounds__(256, 6) void kv_probe_kernel(Tables t, KvProbeParams p) {
-    __shared__ uint64_t sh[kLdsWords];
-    __shared__ uint64_t tags[256];
-    const uint32_t tid = threadIdx.x, w = p.w;
-    const uint4 e = p.entries[blockIdx.x];
-    const uint32_t bad = image_poly_plain<FORM, false>(p.db, e.x, e.y, 0u, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
-    if (bad < kN) atomicMin(p.err, (unsigned long long)blockIdx.x * kN + bad);
-    __syncthreads();
-    // tag s: bits [64 s, + 64) of the string of w-bit coefficients; w need not divide 64 (the header lies inside the polynomial: c < 2048)
+// tag `tid` of the header whose coefficients lie in sh: bits [64 tid, + 64) of the string of w-bit coefficients; w need not divide 64 (the header lies
+// inside the polynomial: c < 2048).  0 for tid >= slots.  A header coefficient >= 2^w atomicMin's (err_base + coefficient) into *err.
+__device__ __forceinline__ uint64_t kv_header_tag(const uint64_t* sh, uint32_t tid, uint32_t slots, uint32_t w, unsigned long long* err, unsigned long long err_base) {
     uint64_t tag = 0;
-    if (tid < p.slots) {
+    if (tid < slots) {
         const uint32_t bit = 64u * tid;
         uint32_t c = bit / w, off = bit - c * w;
         for (uint32_t got = 0; got < 64u; c++) {
             const uint64_t v = sh[c];
-            if (v >> w) atomicMin(p.err, (unsigned long long)blockIdx.x * kN + c);
+            if (v >> w) atomicMin(err, err_base + c);
             const uint32_t take = min(w - off, 64u - got);  // <= w <= 40
             tag |= ((v >> off) & ((1ull << take) - 1ull)) << got;
             got += take;
             off = 0;
         }
     }
+    return tag;
+}
+
+template <uint32_t FORM, bool PACK>
+__device__ __forceinline__ void kv_probe_body(const Tables& t, const KvProbeParams& p, uint64_t* sh, uint64_t* tags) {
+    const uint32_t tid = threadIdx.x, w = p.w;
+    const uint4 e = p.entries[blockIdx.x];
+    const uint32_t bad = image_poly_plain<FORM, PACK>(p.db, e.x, e.y, 0u, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+    if (bad < kN) atomicMin(p.err, (unsigned long long)blockIdx.x * kN + bad);
+    __syncthreads();
+    const uint64_t tag = kv_header_tag(sh, tid, p.slots, w, p.err, (unsigned long long)blockIdx.x * kN);
     tags[tid] = tag;
     const unsigned long long used = __ballot(tag != 0);
     if ((tid & 63u) == 0) p.occ[(size_t)blockIdx.x * 4u + (tid >> 6)] = used;
@@ -52,15 +64,81 @@ __global__ __launch_bounds__(256, 6) void kv_probe_kernel(Tables t, KvProbeParam
     }
 }
 
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 6) void kv_probe_kernel(Tables t, KvProbeParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    __shared__ uint64_t tags[256];
+    kv_probe_body<FORM, false>(t, p, sh, tags);
+}
+template <uint32_t FORM>
+__global__ __launch_bounds__(256, 6) void pack_kv_probe_kernel(Tables t, KvProbeParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    __shared__ uint64_t tags[256];
+    kv_probe_body<FORM, true>(t, p, sh, tags);
+}
+
+// Workgroup g has bucket first_bucket + g (the host checks the range against nb < 2^31): image item (bucket / num_per, bucket % num_per).  The adds are
+// integer, so the histogram is exact whatever the order the workgroups finish in.  (One bucket per workgroup: a loop over a stride of buckets keeps the
+// probe's addresses live across iterations and spills at these launch bounds.)
+template <uint32_t FORM, bool PACK>
+__global__ __launch_bounds__(256, 6) void kv_stats_kernel(Tables t, KvStatsParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    __shared__ uint32_t used[4];
+    const uint32_t tid = threadIdx.x, bucket = p.first_bucket + blockIdx.x;
+    const uint32_t bad = image_poly_plain<FORM, PACK>(p.db, bucket / p.num_per, bucket % p.num_per, 0u, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+    if (bad < kN) atomicMin(p.err, (unsigned long long)bucket * kN + bad);
+    __syncthreads();
+    const uint64_t tag = kv_header_tag(sh, tid, p.slots, p.w, p.err, (unsigned long long)bucket * kN);
+    const unsigned long long ballot = __ballot(tag != 0);
+    if ((tid & 63u) == 0) used[tid >> 6] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    if (tid == 0) atomicAdd(&p.hist[used[0] + used[1] + used[2] + used[3]], 1ull);
+}
+
+template <uint32_t FORM, bool PACK>
+void launch_kv_stats_form(const Tables& tb, const KvStatsParams& p, hipStream_t s) {
+    constexpr uint32_t kMaxGrid = 1u << 23;  // workgroups per launch: grid x block stays below 2^32 threads, whatever the range
+    for (uint32_t done = 0; done < p.n_buckets; done += kMaxGrid) {
+        KvStatsParams q = p;
+        q.first_bucket = p.first_bucket + done;
+        q.n_buckets = std::min(kMaxGrid, p.n_buckets - done);
+        hipLaunchKernelGGL((kv_stats_kernel<FORM, PACK>), dim3(q.n_buckets), dim3(256), 0, s, tb, q);
+    }
+}
+
 }  // namespace
 
-void launch_kv_probe(const DeviceTables& t, const KvProbeParams& p, hipStream_t s) {
+void launch_kv_probe(const DeviceTables& t, const KvProbeParams& p, bool pack, hipStream_t s) {
     if (p.n_entries == 0) return;
     const Tables tb{t.fwd, t.inv};
-    if (p.form == DBX_PACKED)
-        hipLaunchKernelGGL((kv_probe_kernel<DBX_PACKED>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+    const dim3 grid(p.n_entries), block(256);
+    if (!pack) {
+        if (p.form == DBX_PACKED)
+            hipLaunchKernelGGL((kv_probe_kernel<DBX_PACKED>), grid, block, 0, s, tb, p);
+        else
+            hipLaunchKernelGGL((kv_probe_kernel<DBX_LIMBS>), grid, block, 0, s, tb, p);
+    } else if (p.form == DBX_PACKED)
+        hipLaunchKernelGGL((pack_kv_probe_kernel<DBX_PACKED>), grid, block, 0, s, tb, p);
+    else if (p.form == DBX_LIMBS)
+        hipLaunchKernelGGL((pack_kv_probe_kernel<DBX_LIMBS>), grid, block, 0, s, tb, p);
     else
-        hipLaunchKernelGGL((kv_probe_kernel<DBX_LIMBS>), dim3(p.n_entries), dim3(256), 0, s, tb, p);
+        hipLaunchKernelGGL((pack_kv_probe_kernel<DBX_LIMBS8>), grid, block, 0, s, tb, p);
+}
+
+void launch_kv_stats(const DeviceTables& t, const KvStatsParams& p, bool pack, hipStream_t s) {
+    if (p.n_buckets == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    if (!pack) {
+        if (p.form == DBX_PACKED)
+            launch_kv_stats_form<DBX_PACKED, false>(tb, p, s);
+        else
+            launch_kv_stats_form<DBX_LIMBS, false>(tb, p, s);
+    } else if (p.form == DBX_PACKED)
+        launch_kv_stats_form<DBX_PACKED, true>(tb, p, s);
+    else if (p.form == DBX_LIMBS)
+        launch_kv_stats_form<DBX_LIMBS, true>(tb, p, s);
+    else
+        launch_kv_stats_form<DBX_LIMBS8, true>(tb, p, s);
 }
 
 }  // namespace spiral

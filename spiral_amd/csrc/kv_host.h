@@ -9,12 +9,12 @@
 namespace spiral {
 namespace host {
 
-// the buckets of a parameter set, nb = 2^(nu1 + nu2) (r: the record layout they come from); the hash needs no more than this
+// the buckets of a parameter set, nb = 2^(nu1 + nu2) (r: the record layout they come from); the hash needs no more than this.  out_n = 0: a base
+// parameter set; out_n >= 1: SpiralPack, a bucket is an item of out_n^2 polynomials, one per trial image
 inline int kv_buckets(const spiral_gpu_params* p, uint32_t out_n, uint64_t* nb, spiral_gpu_record_layout* r = nullptr) {
     if (!p) return fail("null argument");
-    if (out_n) return fail("keyed records are defined for base parameter sets only (out_n = 0), not for a SpiralPack set with out_n = %u", out_n);
     spiral_gpu_record_layout l;
-    if (record_layout(p, 1, &l)) return -1;
+    if (record_layout(p, 1, &l, out_n)) return -1;
     *nb = l.capacity / l.per_item;
     if (*nb < 2) return fail("a keyed table needs at least 2 buckets (nu1 + nu2 >= 1)");
     if (r) *r = l;
@@ -142,7 +142,8 @@ struct KvSlot {
 
 constexpr uint32_t kKvNoSlot = 0xFFFFFFFFu;
 
-// The probe: ONE launch over the distinct candidate buckets of `keys` (ascending; one workgroup each) on `st`, then one wait.  table receives the buckets'
+// The probe: ONE launch over the distinct candidate buckets of `keys` (ascending; one workgroup each) on `st`, then one wait.  src: the image that holds
+// polynomial 0 of every bucket (a SpiralPack server: trial image 0).  table receives the buckets'
 // occupancy, found[k] the (candidate, slot) that holds key k's tag -- candidate 1 first -- or cand = 0.  32 bytes per bucket and 4 per (key, candidate) come back.
 inline int kv_probe(const char* what, ExportWork& W, const DeviceTables& tb, hipStream_t st, const ExportImage& src, const spiral_gpu_kv_layout& l, uint64_t p_db,
                     const std::vector<KvKey>& keys, KvTable& table, std::vector<KvSlot>& found) {
@@ -204,7 +205,7 @@ inline int kv_probe(const char* what, ExportWork& W, const DeviceTables& tb, hip
     kp.w = l.coeff_bits;
     kp.slots = l.slots;
     kp.p_db = p_db;
-    launch_kv_probe(tb, kp, st);
+    launch_kv_probe(tb, kp, src.pack != 0, st);
     HIP_OK(hipGetLastError());
     std::vector<uint8_t> host(back);
     unsigned long long err = ~0ull;
@@ -228,6 +229,152 @@ inline int kv_probe(const char* what, ExportWork& W, const DeviceTables& tb, hip
 inline void kv_pieces(const spiral_gpu_kv_layout& l, uint64_t k, uint32_t j, uint32_t ii, uint32_t slot, std::vector<RecordPiece>& pieces) {
     pieces.push_back(RecordPiece{2 * k, j, ii, 8u * slot, 8u});
     pieces.push_back(RecordPiece{2 * k + 1, j, ii, (uint32_t)(8u * l.slots + slot * l.value_bytes), (uint32_t)l.value_bytes});
+}
+
+// The image a keyed call works on, as either server states it: a base server's image, or the trial images of a SpiralPack server (tr.trials != 0; src
+// and dst name trial 0, where polynomial 0 of every bucket lies)
+struct KvImage {
+    ExportWork& xwork;
+    UpdateWork& upd;
+    const DeviceTables& tb;
+    hipStream_t st;
+    ExportImage src;
+    UpdateImage dst;
+    RecordTrials tr;
+    const FpTrackCtx* trk;  // null: the image's fingerprint is not tracked
+    uint32_t num_per;
+    uint64_t p_db;
+};
+
+// put, and delete (tag and value bytes of the found slots become zero), after the server's own checks: the probe, the placement rule over the host's copy
+// of the occupancy, then tag and value of every written key as two pieces through update_record_pieces.  ONE copy of the rule and of its failure message
+// for both servers.
+inline int kv_write(const KvImage& I, const char* what, bool put, const spiral_gpu_kv_layout& l, const void* table_key16, const void* keys, uint64_t key_bytes,
+                    const void* values, uint64_t n, uint64_t* n_deleted) {
+    const uint64_t value_bytes = l.value_bytes;
+    std::vector<KvKey> hk;
+    if (kv_hash_keys(what, l.buckets, table_key16, keys, key_bytes, n, true, hk)) return -1;
+    if (n_deleted) *n_deleted = 0;
+    if (n == 0) return 0;
+    KvTable table;
+    std::vector<KvSlot> at;
+    if (kv_probe(what, I.xwork, I.tb, I.st, I.src, l, I.p_db, hk, table, at)) return -1;
+    if (put)
+        for (uint64_t k = 0; k < n; k++) {
+            if (at[k].cand) continue;  // present: that slot is overwritten
+            uint32_t cand, slot;
+            if (!table.place(hk[k], &cand, &slot))
+                return fail("%s: key %llu cannot be placed: its buckets %llu and %llu are both full (%u slots each); nothing was written", what, (unsigned long long)k,
+                            (unsigned long long)hk[k].b[0], (unsigned long long)hk[k].b[1], l.slots);
+            at[k] = KvSlot{cand + 1, slot};
+        }
+    const uint64_t stride = std::max<uint64_t>(8, value_bytes);
+    std::vector<uint64_t> key_of;  // written key -> its position in the call
+    for (uint64_t k = 0; k < n; k++)
+        if (at[k].cand) key_of.push_back(k);
+    const size_t m = key_of.size();
+    if (m == 0) return 0;
+    std::vector<RecordPiece> pieces;
+    pieces.reserve(2 * m);
+    std::vector<uint8_t> stage(2 * m * (size_t)stride, 0);  // [tag, value] per written key, `stride` bytes each; a delete writes zeros
+    for (size_t i = 0; i < m; i++) {
+        const uint64_t k = key_of[i], bucket = hk[k].b[at[k].cand - 1];
+        kv_pieces(l, i, (uint32_t)(bucket / I.num_per), (uint32_t)(bucket % I.num_per), at[k].slot, pieces);
+        if (put) {
+            for (int b = 0; b < 8; b++) stage[2 * i * (size_t)stride + b] = (uint8_t)(hk[k].tag >> (8 * b));
+            memcpy(&stage[(2 * i + 1) * (size_t)stride], static_cast<const uint8_t*>(values) + k * value_bytes, (size_t)value_bytes);
+        }
+    }
+    if (update_record_pieces(I.upd, I.tb, I.st, stage.data(), stride, RecordChunk{0, stride}, l.coeff_bits, I.p_db, pieces, I.dst, I.src,
+                             [&](uint64_t pos) { return key_of[(size_t)(pos / 2)]; }, I.tr, I.trk))
+        return -1;
+    if (n_deleted) *n_deleted = m;
+    return 0;
+}
+
+// get, after the server's own checks: the probe, then the found slots' values through read_record_pieces; a missing key's bytes are left alone
+inline int kv_get(const KvImage& I, const spiral_gpu_kv_layout& l, const void* table_key16, const void* keys, uint64_t key_bytes, void* values, uint64_t n,
+                  uint8_t* found) {
+    const uint64_t value_bytes = l.value_bytes;
+    std::vector<KvKey> hk;
+    if (kv_hash_keys("kv_get", l.buckets, table_key16, keys, key_bytes, n, false, hk)) return -1;
+    KvTable table;
+    std::vector<KvSlot> at;
+    if (kv_probe("kv_get", I.xwork, I.tb, I.st, I.src, l, I.p_db, hk, table, at)) return -1;
+    for (uint64_t k = 0; k < n; k++) found[k] = (uint8_t)at[k].cand;
+    return read_record_pieces(
+        I.xwork, I.tb, I.st, static_cast<uint8_t*>(values), value_bytes, RecordChunk{0, value_bytes}, l.coeff_bits, I.p_db, n,
+        [&](uint64_t k, RecordPiece* pc) {
+            if (!at[k].cand) return false;
+            const uint64_t bucket = hk[k].b[at[k].cand - 1];
+            *pc = RecordPiece{k, (uint32_t)(bucket / I.num_per), (uint32_t)(bucket % I.num_per), (uint32_t)(8u * l.slots + at[k].slot * value_bytes), (uint32_t)value_bytes};
+            return true;
+        },
+        I.src, [&](uint64_t pos) { return pos; }, I.tr);
+}
+
+// Table occupancy (include/spiral_gpu.h spiral_gpu_server_kv_stats): ONE launch over buckets [first, first + n) on `st`, the histogram's 257 words back,
+// one wait; used, full_buckets and max_used are derived from the histogram here.  src as for kv_probe.
+inline int kv_stats(ExportWork& W, const DeviceTables& tb, hipStream_t st, const ExportImage& src, const spiral_gpu_kv_layout& l, uint64_t p_db, uint64_t first, uint64_t n,
+                    spiral_gpu_kv_stats* out) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("kv_stats cannot be called while the server's stream is being captured");
+    if (first > l.buckets || n > l.buckets - first)
+        return fail("kv_stats: buckets [%llu, +%llu) outside the table of %llu", (unsigned long long)first, (unsigned long long)n, (unsigned long long)l.buckets);
+    if (l.buckets > 0x7FFFFFFFull) return fail("kv_stats: a table of %llu buckets, at most 2^31 - 1", (unsigned long long)l.buckets);
+    spiral_gpu_kv_stats s{};
+    s.buckets = n;
+    s.slots = l.slots;
+    if (n == 0) {
+        *out = s;
+        return 0;
+    }
+    // one buffer: [error word, padding][histogram, 257 words]
+    const size_t o_hist = 16, dev_bytes = o_hist + 257 * 8;
+    if (W.dev.words * 8 < dev_bytes) {
+        W.dev.release();
+        W.dev.words = 0;
+        if (W.dev.alloc((dev_bytes + 7) / 8)) {
+            (void)hipGetLastError();
+            W.dev.p = nullptr;
+            W.dev.words = 0;
+            return fail("no device memory for the histogram (%zu bytes)", dev_bytes);
+        }
+    }
+    uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
+    HIP_OK(hipMemsetAsync(d, 0xFF, 16, st));  // the error word: ~0 = every coefficient read so far is a plaintext value
+    HIP_OK(hipMemsetAsync(d + o_hist, 0, 257 * 8, st));
+    KvStatsParams sp{};
+    sp.db = src.db;
+    sp.hist = reinterpret_cast<unsigned long long*>(d + o_hist);
+    sp.err = reinterpret_cast<unsigned long long*>(d);
+    sp.first_bucket = (uint32_t)first;
+    sp.n_buckets = (uint32_t)n;
+    sp.form = src.form;
+    sp.num_per = src.num_per;
+    sp.dim0 = src.dim0;
+    sp.w = l.coeff_bits;
+    sp.slots = l.slots;
+    sp.p_db = p_db;
+    launch_kv_stats(tb, sp, src.pack != 0, st);
+    HIP_OK(hipGetLastError());
+    unsigned long long err = ~0ull;
+    HIP_OK(hipMemcpyAsync(s.hist, d + o_hist, 257 * 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&err, d, sizeof(err), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (err != ~0ull)
+        return fail("kv_stats: the image holds no keyed table at bucket %llu (polynomial 0, coefficient %u is no plaintext value below 2^coeff_bits): not a record "
+                    "database (fill_db_random, a load_db of arbitrary words, or items loaded with larger coefficients)",
+                    (unsigned long long)(err / kN), (uint32_t)(err % kN));
+    for (uint32_t u = 0; u <= l.slots; u++) {
+        if (!s.hist[u]) continue;
+        s.used += (uint64_t)u * s.hist[u];
+        s.max_used = u;
+    }
+    s.full_buckets = s.hist[l.slots];
+    *out = s;
+    return 0;
 }
 
 }  // namespace host

@@ -3,8 +3,8 @@
 // first-dimension sweep of answer_batch: several lanes' queries in one pass over the trial images, from their limb-plane form).
 #include "db_image.h"
 #include "key_store.h"
+#include "kv_host.h"
 #include "message.h"
-#include "records_host.h"
 
 using namespace spiral;
 using namespace spiral::host;
@@ -728,6 +728,145 @@ int spiral_gpu_pack_server_read_records_at(spiral_gpu_pack_server* S, void* reco
     return read_record_pieces(S->xwork, S->tb, S->stream, static_cast<uint8_t*>(records), record_bytes, rc.chunk, rc.l.coeff_bits, S->p.p_db, n,
                               [&](uint64_t k, RecordPiece* pc) { return *pc = pk_record_piece(S, rc, k, record_ids[k]), true; }, S->img->export_source(0),
                               [&](uint64_t pos) { return record_ids[pos]; }, rc.tr);
+}
+
+// ---- keyed records (include/spiral_gpu.h "Keyed records", SpiralPack; kv_host.h, kv.hip) ----------------------------------------------------------
+namespace {
+// how every keyed call opens: the layout, and a server that holds every trial image (a value's bytes span trials; the header is in trial 0)
+int pk_kv_call(const spiral_gpu_pack_server* S, const char* what, uint64_t value_bytes, spiral_gpu_kv_layout* l) {
+    if (kv_layout(&S->p, value_bytes, l, S->out_n)) return -1;
+    if (S->nt != S->s.trials)
+        return fail("%s: this server is a trial shard (trials [%u, %u) of %u): keyed records need every trial image in one place (a bucket's header is in "
+                    "trial 0, its values span the trials)",
+                    what, S->t0, S->t0 + S->nt, S->s.trials);
+    return 0;
+}
+// the trial images as the shared keyed bodies take them (kv_host.h KvImage): src and dst name trial 0; trk: the caller's, filled by pk_track_ctx
+extern "C++" KvImage pk_kv_image(spiral_gpu_pack_server* S, const FpTrackCtx& trk) {
+    return KvImage{S->xwork, S->img->upd, S->tb, S->stream, S->img->export_source(0), S->img->update_target(0), RecordTrials{S->s.trials, S->t0, S->nt, S->img->lay.trial_words},
+                   trk.t ? &trk : nullptr, S->s.num_per, S->p.p_db};
+}
+// put, and delete: the owner's checks, then kv_host.h kv_write
+int pk_kv_write(spiral_gpu_pack_server* S, const char* what, bool put, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values,
+                uint64_t value_bytes, uint64_t n, uint64_t* n_deleted) {
+    if (!S) return fail("null server");
+    if (S->img->owner != S) return fail("%s: this server is a lane: it sweeps its owner's database, update it through the owner", what);
+    spiral_gpu_kv_layout l;
+    if (pk_kv_call(S, what, value_bytes, &l)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    HIP_OK(hipSetDevice(S->device));
+    FpTrackCtx trk;
+    pk_track_ctx(S, 0, trk);
+    return kv_write(pk_kv_image(S, trk), what, put, l, table_key16, keys, key_bytes, values, n, n_deleted);
+}
+}  // namespace
+
+int spiral_gpu_pack_kv_layout_of(const spiral_gpu_params* p, uint32_t out_n, uint64_t value_bytes, spiral_gpu_kv_layout* out) {
+    if (p && out && out_n < 1) return fail("out_n out of range");
+    return kv_layout(p, value_bytes, out, out_n);
+}
+
+int spiral_gpu_pack_kv_hash(const spiral_gpu_params* p, uint32_t out_n, const void* table_key16, const void* key, uint64_t key_bytes, uint64_t* tag, uint64_t* b1,
+                            uint64_t* b2) {
+    if (!p || !table_key16 || !tag || !b1 || !b2 || (key_bytes && !key)) return fail("kv_hash: null argument");
+    if (out_n < 1) return fail("out_n out of range");
+    uint64_t nb;
+    if (kv_buckets(p, out_n, &nb)) return -1;
+    static const uint8_t none = 0;
+    const KvKey h = kv_hash(nb, static_cast<const uint8_t*>(table_key16), key_bytes ? static_cast<const uint8_t*>(key) : &none, key_bytes);
+    *tag = h.tag;
+    *b1 = h.b[0];
+    *b2 = h.b[1];
+    return 0;
+}
+
+// A fresh table: placement from empty on the host, then the item stream built a pass of buckets at a time and every trial image loaded through
+// load_db_items' ingest, polynomial t of each bucket to trial t (not a hot path)
+int spiral_gpu_pack_server_kv_load(spiral_gpu_pack_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values, uint64_t value_bytes,
+                                   uint64_t n) {
+    if (!S) return fail("null server");
+    if (S->img->owner != S) return fail("kv_load: this server is a lane: it sweeps its owner's database, load it through the owner");
+    spiral_gpu_kv_layout l;
+    if (pk_kv_call(S, "kv_load", value_bytes, &l)) return -1;
+    if (n && !values) return fail("kv_load: null argument");
+    std::vector<KvKey> hk;
+    if (kv_hash_keys("kv_load", l.buckets, table_key16, keys, key_bytes, n, true, hk)) return -1;
+    KvTable table;
+    table.slots = l.slots;
+    table.ids.resize((size_t)l.buckets);
+    for (uint64_t b = 0; b < l.buckets; b++) table.ids[b] = b;
+    table.occ.assign((size_t)l.buckets, std::array<uint64_t, 4>{});
+    // placement first: a key that cannot be placed fails the call before the stream is built.  where[k] = bucket << 8 | slot
+    std::vector<std::pair<uint64_t, uint64_t>> where((size_t)n);  // (bucket << 8 | slot, key), sorted by bucket below
+    for (uint64_t k = 0; k < n; k++) {
+        uint32_t cand, slot;
+        if (!table.place(hk[k], &cand, &slot))
+            return fail("kv_load: key %llu cannot be placed: its buckets %llu and %llu are both full (%u slots each); the image was not touched", (unsigned long long)k,
+                        (unsigned long long)hk[k].b[0], (unsigned long long)hk[k].b[1], l.slots);
+        where[k] = {(hk[k].b[cand] << 8) | slot, k};
+    }
+    std::sort(where.begin(), where.end());
+    // the item stream a pass of buckets at a time (at most 2^14 buckets: 512 MiB at 32 KiB buckets, not the whole table), polynomial t of each to trial t
+    const uint32_t w = l.coeff_bits, cb = (1ull << w) < S->p.p_db ? w + 1 : w;  // (load_db_items wants a width that holds every value below p_db)
+    const uint64_t poly_bytes = 256ull * w;
+    const uint64_t pass = std::max<uint64_t>(1, std::min<uint64_t>(options().db_stage_bytes / (256ull * cb), 1u << 14));  // buckets built and repacked at a time
+    std::vector<uint8_t> stream, polys, wide;
+    size_t next = 0;
+    for (uint64_t done = 0; done < l.buckets; done += pass) {
+        const uint64_t cnt = std::min(pass, l.buckets - done);
+        stream.assign((size_t)(cnt * l.item_bytes), 0);
+        for (; next < where.size() && (where[next].first >> 8) < done + cnt; next++) {
+            const uint64_t k = where[next].second, slot = where[next].first & 0xFFu;
+            uint8_t* item = stream.data() + ((where[next].first >> 8) - done) * l.item_bytes;
+            for (int b = 0; b < 8; b++) item[8u * slot + b] = (uint8_t)(hk[k].tag >> (8 * b));
+            memcpy(item + 8u * l.slots + slot * value_bytes, static_cast<const uint8_t*>(values) + k * value_bytes, (size_t)value_bytes);
+        }
+        for (uint32_t t = 0; t < S->s.trials; t++) {
+            polys.resize((size_t)(cnt * poly_bytes));
+            for (uint64_t i = 0; i < cnt; i++) memcpy(polys.data() + i * poly_bytes, stream.data() + i * l.item_bytes + t * poly_bytes, (size_t)poly_bytes);
+            const uint8_t* items = polys.data();
+            if (cb != w) {
+                wide.assign((size_t)(cnt * 256ull * cb), 0);
+                widen_coeffs(polys.data(), wide.data(), (size_t)(cnt * kN), w, cb);
+                items = wide.data();
+            }
+            if (spiral_gpu_pack_server_load_db_items(S, t, items, cb, done, cnt)) return -1;
+        }
+    }
+    return 0;
+}
+
+int spiral_gpu_pack_server_kv_put(spiral_gpu_pack_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values, uint64_t value_bytes,
+                                  uint64_t n) {
+    if (n && !values) return fail("kv_put: null argument");
+    return pk_kv_write(S, "kv_put", true, table_key16, keys, key_bytes, values, value_bytes, n, nullptr);
+}
+
+int spiral_gpu_pack_server_kv_delete(spiral_gpu_pack_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, uint64_t value_bytes, uint64_t n,
+                                     uint64_t* n_deleted) {
+    return pk_kv_write(S, "kv_delete", false, table_key16, keys, key_bytes, nullptr, value_bytes, n, n_deleted);
+}
+
+// The probe, then the found slots' values through read_records' path; the owner or a lane, on its own stream
+int spiral_gpu_pack_server_kv_get(spiral_gpu_pack_server* S, const void* table_key16, const void* keys, uint64_t key_bytes, void* values, uint64_t value_bytes, uint64_t n,
+                                  uint8_t* found) {
+    if (enter(S)) return -1;
+    spiral_gpu_kv_layout l;
+    if (pk_kv_call(S, "kv_get", value_bytes, &l)) return -1;
+    if (n && (!values || !found)) return fail("kv_get: null argument");
+    if (!S->img->loaded) return fail("no database loaded");
+    FpTrackCtx none;
+    return kv_get(pk_kv_image(S, none), l, table_key16, keys, key_bytes, values, n, found);
+}
+
+// Table occupancy: one launch over the range's buckets in trial image 0, 257 words back (kv_host.h kv_stats); the owner or a lane, on its own stream
+int spiral_gpu_pack_server_kv_stats(spiral_gpu_pack_server* S, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_stats* out) {
+    if (enter(S)) return -1;
+    if (!out) return fail("kv_stats: null argument");
+    spiral_gpu_kv_layout l;
+    if (pk_kv_call(S, "kv_stats", value_bytes, &l)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    return kv_stats(S->xwork, S->tb, S->stream, S->img->export_source(0), l, S->p.p_db, first_bucket, n_buckets, out);
 }
 
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {

@@ -848,7 +848,11 @@ int load_item_stream(spiral_gpu_server* S, const uint8_t* stream, uint32_t w, ui
     }
     return 0;
 }
-// put, and delete (tag and value bytes of the found slots become zero)
+// the image as the shared keyed bodies take it (kv_host.h KvImage); trk: the caller's, filled by track_ctx
+extern "C++" KvImage kv_image(spiral_gpu_server* S, const FpTrackCtx& trk) {
+    return KvImage{S->xwork, S->img->upd, S->tb, S->stream, S->img->export_source(), S->img->update_target(), RecordTrials{}, trk.t ? &trk : nullptr, S->s.num_per, S->p.p_db};
+}
+// put, and delete: the owner's checks, then kv_host.h kv_write
 int kv_write(spiral_gpu_server* S, const char* what, bool put, const void* table_key16, const void* keys, uint64_t key_bytes, const void* values, uint64_t value_bytes,
              uint64_t n, uint64_t* n_deleted) {
     if (!S) return fail("null server");
@@ -857,46 +861,9 @@ int kv_write(spiral_gpu_server* S, const char* what, bool put, const void* table
     if (kv_call(S, what, value_bytes, &l)) return -1;
     if (!S->img->loaded) return fail("no database loaded");
     HIP_OK(hipSetDevice(S->device));
-    std::vector<KvKey> hk;
-    if (kv_hash_keys(what, l.buckets, table_key16, keys, key_bytes, n, true, hk)) return -1;
-    if (n_deleted) *n_deleted = 0;
-    if (n == 0) return 0;
-    KvTable table;
-    std::vector<KvSlot> at;
-    if (kv_probe(what, S->xwork, S->tb, S->stream, S->img->export_source(), l, S->p.p_db, hk, table, at)) return -1;
-    if (put)
-        for (uint64_t k = 0; k < n; k++) {
-            if (at[k].cand) continue;  // present: that slot is overwritten
-            uint32_t cand, slot;
-            if (!table.place(hk[k], &cand, &slot))
-                return fail("%s: key %llu cannot be placed: its buckets %llu and %llu are both full (%u slots each); nothing was written", what, (unsigned long long)k,
-                            (unsigned long long)hk[k].b[0], (unsigned long long)hk[k].b[1], l.slots);
-            at[k] = KvSlot{cand + 1, slot};
-        }
-    const uint64_t stride = std::max<uint64_t>(8, value_bytes);
-    std::vector<uint64_t> key_of;  // written key -> its position in the call
-    for (uint64_t k = 0; k < n; k++)
-        if (at[k].cand) key_of.push_back(k);
-    const size_t m = key_of.size();
-    if (m == 0) return 0;
-    std::vector<RecordPiece> pieces;
-    pieces.reserve(2 * m);
-    std::vector<uint8_t> stage(2 * m * (size_t)stride, 0);  // [tag, value] per written key, `stride` bytes each; a delete writes zeros
-    for (size_t i = 0; i < m; i++) {
-        const uint64_t k = key_of[i], bucket = hk[k].b[at[k].cand - 1];
-        kv_pieces(l, i, (uint32_t)(bucket / S->s.num_per), (uint32_t)(bucket % S->s.num_per), at[k].slot, pieces);
-        if (put) {
-            for (int b = 0; b < 8; b++) stage[2 * i * (size_t)stride + b] = (uint8_t)(hk[k].tag >> (8 * b));
-            memcpy(&stage[(2 * i + 1) * (size_t)stride], static_cast<const uint8_t*>(values) + k * value_bytes, (size_t)value_bytes);
-        }
-    }
     FpTrackCtx trk;
     track_ctx(S, trk);
-    if (update_record_pieces(S->img->upd, S->tb, S->stream, stage.data(), stride, RecordChunk{0, stride}, l.coeff_bits, S->p.p_db, pieces, S->img->update_target(),
-                             S->img->export_source(), [&](uint64_t pos) { return key_of[(size_t)(pos / 2)]; }, RecordTrials{}, trk.t ? &trk : nullptr))
-        return -1;
-    if (n_deleted) *n_deleted = m;
-    return 0;
+    return kv_write(kv_image(S, trk), what, put, l, table_key16, keys, key_bytes, values, n, n_deleted);
 }
 }  // namespace
 
@@ -958,21 +925,18 @@ int spiral_gpu_server_kv_get(spiral_gpu_server* S, const void* table_key16, cons
     if (kv_call(S, "kv_get", value_bytes, &l)) return -1;
     if (n && (!values || !found)) return fail("kv_get: null argument");
     if (!S->img->loaded) return fail("no database loaded");
-    std::vector<KvKey> hk;
-    if (kv_hash_keys("kv_get", l.buckets, table_key16, keys, key_bytes, n, false, hk)) return -1;
-    KvTable table;
-    std::vector<KvSlot> at;
-    if (kv_probe("kv_get", S->xwork, S->tb, S->stream, S->img->export_source(), l, S->p.p_db, hk, table, at)) return -1;
-    for (uint64_t k = 0; k < n; k++) found[k] = (uint8_t)at[k].cand;
-    return read_record_pieces(
-        S->xwork, S->tb, S->stream, static_cast<uint8_t*>(values), value_bytes, RecordChunk{0, value_bytes}, l.coeff_bits, S->p.p_db, n,
-        [&](uint64_t k, RecordPiece* pc) {
-            if (!at[k].cand) return false;
-            const uint64_t bucket = hk[k].b[at[k].cand - 1];
-            *pc = RecordPiece{k, (uint32_t)(bucket / S->s.num_per), (uint32_t)(bucket % S->s.num_per), (uint32_t)(8u * l.slots + at[k].slot * value_bytes), (uint32_t)value_bytes};
-            return true;
-        },
-        S->img->export_source(), [&](uint64_t pos) { return pos; });
+    FpTrackCtx none;
+    return kv_get(kv_image(S, none), l, table_key16, keys, key_bytes, values, n, found);
+}
+
+// Table occupancy: one launch over the range's buckets, 257 words back (kv_host.h kv_stats); any server that references the image, on its own stream
+int spiral_gpu_server_kv_stats(spiral_gpu_server* S, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_stats* out) {
+    if (enter(S)) return -1;
+    if (!out) return fail("kv_stats: null argument");
+    spiral_gpu_kv_layout l;
+    if (kv_call(S, "kv_stats", value_bytes, &l)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    return kv_stats(S->xwork, S->tb, S->stream, S->img->export_source(), l, S->p.p_db, first_bucket, n_buckets, out);
 }
 
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {

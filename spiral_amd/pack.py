@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import U64P, PackShape, Params, TrackedFingerprint, check, fingerprint_call, fingerprint_key, fingerprint_range, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
+from ._lib import U64P, KeyedRecords, PackShape, Params, TrackedFingerprint, check, fingerprint_call, fingerprint_key, fingerprint_range, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
 
 N = 2048
 PACK_STAGE_NAMES = ["expansion_us", "conversion_us", "first_dim_us", "folding_us", "packing_us", "sweep_kernels_us", "total_us", "reserved"]
@@ -62,7 +62,7 @@ def fastMultiplyQueriesByDatabaseDim1(dbs, v_firstdims, dim0, num_per) -> np.nda
     return out
 
 
-class PackServer(TrackedFingerprint):
+class PackServer(TrackedFingerprint, KeyedRecords):
     def __init__(self, params: Params, out_n: int, device: int = 0, trial0: int = 0, trial1: int = 0):
         """trial0, trial1: this server's share [trial0, trial1) of the out_n^2 trials (N GPUs); 0, 0 = all of them"""
         self.params, self.out_n = params, out_n
@@ -158,6 +158,7 @@ class PackServer(TrackedFingerprint):
 
     # ---- tracked fingerprints: fingerprint_track, _untrack, _tracked, _tracked_polys, _scrub (_lib.TrackedFingerprint) ----
     _fp_prefix = "spiral_gpu_pack_server"
+    _kv_prefix = "spiral_gpu_pack_server"  # keyed records on the trial images: kv_load, kv_put, kv_delete, kv_get, kv_stats (_lib.KeyedRecords)
 
     def _fp_table(self):
         total = self.shape.dim0 * self.shape.num_per

@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, Params, Shape, TrackedFingerprint, check, fingerprint_call, fingerprint_key, fingerprint_range, kv_keys, kv_layout, kv_table_key, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
+from ._lib import FORM_NTT, FORM_SEEDED, FORM_WIRE, U64P, KeyedRecords, Params, Shape, TrackedFingerprint, check, fingerprint_call, fingerprint_key, fingerprint_range, lib, read_args, read_ids, record_array, record_layout, record_out, update_args, wire_bytes
 
 N = 2048
 
@@ -137,7 +137,7 @@ def answer_batch_instances(servers, instances, queries, wire: bool = False):
     return out, us.value
 
 
-class Server(TrackedFingerprint):
+class Server(TrackedFingerprint, KeyedRecords):
     def __init__(self, params: Params, device: int = 0, j_begin: int = 0, j_end: int = 0, share_db_of: "Server | None" = None, *,
                  col_rank: "int | None" = None, col_ranks: "int | None" = None):
         """share_db_of: make this server a query lane of that one -- same parameters, device and shard, sweeping ITS database
@@ -240,46 +240,8 @@ class Server(TrackedFingerprint):
         total = self.shape.dim0 * self.shape.num_per
         return self.dim0_shard * (self.shape.num_per // (self.col_ranks or 1)), 4, total
 
-    # ---- keyed records (include/spiral_gpu.h "Keyed records"): a bucket is an item, a key hashes to two candidate buckets ----
-    def _kv_args(self, table_key, keys, values=None, value_bytes=None):
-        tk, keys = kv_table_key(table_key), kv_keys(keys)
-        if values is not None:
-            values = np.ascontiguousarray(values)
-            if values.dtype != np.uint8 or values.ndim != 2 or values.shape[0] != keys.shape[0]:
-                raise ValueError(f"values are a uint8 array [n][value_bytes] with one row per key ({keys.shape[0]})")
-            value_bytes = values.shape[1]
-        kv_layout(self.params, value_bytes)
-        kp = keys.ctypes.data_as(C.c_void_p) if keys.size else None
-        return tk, keys, kp, values, int(value_bytes)
-
-    def kv_load(self, table_key, keys, values):
-        """a fresh keyed table from keys [n][key_bytes] and values [n][value_bytes]: placed from empty on the host, loaded through load_db_items"""
-        tk, keys, kp, values, vb = self._kv_args(table_key, keys, values)
-        check(lib().spiral_gpu_server_kv_load(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], values.ctypes.data_as(C.c_void_p), vb, keys.shape[0]))
-        return self
-
-    def kv_put(self, table_key, keys, values):
-        """insert or overwrite keys in place, in the image's current form: one probe launch, the placement rule on the host, update_records' write;
-        fails with nothing written where a key's two buckets are full; see include/spiral_gpu.h spiral_gpu_server_kv_put"""
-        tk, keys, kp, values, vb = self._kv_args(table_key, keys, values)
-        check(lib().spiral_gpu_server_kv_put(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], values.ctypes.data_as(C.c_void_p), vb, keys.shape[0]))
-
-    def kv_delete(self, table_key, keys, value_bytes: int) -> int:
-        """zero tag and value of every key that is present; returns how many were (an absent key is not an error)"""
-        tk, keys, kp, _, vb = self._kv_args(table_key, keys, None, value_bytes)
-        n = C.c_uint64()
-        check(lib().spiral_gpu_server_kv_delete(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], vb, keys.shape[0], C.byref(n)))
-        return n.value
-
-    def kv_get(self, table_key, keys, value_bytes: int, out: np.ndarray | None = None):
-        """(values uint8 [n][value_bytes], found uint8 [n]): found[k] is 0 (absent), 1 or 2 (the candidate bucket that holds the key); the bytes of an
-        absent key are left as they are in `out` (zero in a fresh array).  Any server that references the image, lanes included"""
-        tk, keys, kp, _, vb = self._kv_args(table_key, keys, None, value_bytes)
-        out = record_out(vb, keys.shape[0], out)
-        found = np.zeros(keys.shape[0], dtype=np.uint8)
-        check(lib().spiral_gpu_server_kv_get(self.h, tk.ctypes.data_as(C.c_void_p), kp, keys.shape[1], out.ctypes.data_as(C.c_void_p), vb, keys.shape[0],
-                                             found.ctypes.data_as(C.c_void_p)))
-        return out.reshape(keys.shape[0], vb), found
+    # ---- keyed records: kv_load, kv_put, kv_delete, kv_get, kv_stats (_lib.KeyedRecords) ----
+    _kv_prefix = "spiral_gpu_server"
 
     # ---- records of any byte size (include/spiral_gpu.h "Records"); instance: which chunk of each record this server's image holds ----
     def load_records(self, records, record_bytes: int, first_record: int = 0, instance: int = 0):
