@@ -102,6 +102,9 @@ int spiral_gpu_column_shard_has_limb_form(const spiral_gpu_params *p, uint32_t n
  *                     Same results either way; not measured yet, hence opt-in
  *   "query_batch_chunk" message polynomials per lane per staging pass of spiral_gpu_server_set_query_batch for messages too large to check on the
  *                     host (direct upload); default 512, at least 1.  Read per call; same results whatever the value
+ *   "kv_scan_chunk"   buckets per pass of spiral_gpu_server_kv_scan / _kv_scan_at and their SpiralPack twins: 0 (default) = automatic, the most that
+ *                     keeps a pass's staged tags within 2^22 (chunk * slots <= 2^22: 32 MiB) and chunk <= 2^16; 1 .. 2^16 sets it.  Read per call; same
+ *                     results whatever the value
  *   "graph_captures"  (get only) the hipGraphs the servers of this process have captured so far: a replayed call does not add to it
  *   "pack_lane_batches" (get only) the SpiralPack batch calls of this process that took the lane form
  *   "key_binds"       (get only) the lanes the bind_keys calls of this process have copied keys into (a lane that held them already is not counted)
@@ -519,6 +522,55 @@ typedef struct spiral_gpu_kv_stats {
     uint64_t hist[257]; /* hist[u] = buckets with exactly u used slots; entries above `slots` are 0 */
 } spiral_gpu_kv_stats;
 int spiral_gpu_server_kv_stats(spiral_gpu_server *s, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_stats *out);
+/* Listing.  The definition, stated once; csrc/kv_host.h, the Python wrappers and the tests' restatement quote it.  An ENTRY is a slot whose tag is not 0,
+ * reported as {tag, bucket, slot}.  A LISTING of a set of buckets is all their entries, in the order of the buckets, and within a bucket by ascending
+ * slot.  With values, row k of `values` is the value_bytes bytes of entry k: bytes [8 slots + slot V, + V) of the bucket's stream.
+ *
+ * kv_scan lists buckets [first_bucket, first_bucket + n_buckets) in ascending order; the range is checked against [0, nb] as kv_stats checks it, and
+ * n_buckets = 0 returns 0 entries.  kv_scan_at lists the buckets of a list, in the order of the list: ids need not be distinct (a bucket named twice
+ * is listed twice), an id >= nb is refused by position before any launch, and entry.bucket is the bucket's id, not its position.
+ *   - *n_entries is always the number of entries in the buckets named, whatever max_entries is.
+ *   - max_entries = 0 with entries = values = NULL is count-only: the result equals kv_stats(...).used over the same buckets; no tag is staged and no
+ *     compaction is launched.
+ *   - If the count exceeds max_entries the call fails with both numbers in the message; *n_entries is set and not one byte of `entries` or `values`
+ *     is written.
+ *   - `values` may be NULL (tags only).  `entries` must not be NULL when max_entries > 0.
+ *   - Who may call, and where, is kv_stats' contract: any server that references the image, lanes included, on its own stream; the call returns
+ *     synchronised; refused inside a capture; refused by name on a j-shard, a column shard and a trial shard; nb <= 2^31 - 1; the image is read in the
+ *     form it is in, nothing is converted, no epoch changes, no graph is re-captured; tracked fingerprints are untouched.
+ *   - A header coefficient that is no plaintext value below 2^w fails the call as kv_stats does, naming the lowest such bucket (kv_scan_at: the lowest
+ *     position in the list, and its bucket) and the coefficient.
+ * The device work runs in passes of option "kv_scan_chunk" buckets, three launches each on the caller's stream, none of which waits for another
+ * workgroup: (1) decode, one workgroup per bucket -- the probe's gather, inverse transform and header packing of polynomial 0, the tags staged, the
+ * bucket's count from the waves' ballots; (2) ONE workgroup's exclusive scan of the pass's counts on top of a running total that stream order carries
+ * from pass to pass; (3) compact, one workgroup per bucket -- each live slot's rank from the ballots, its 16-byte entry stored at offset + rank where
+ * that is below max_entries.  Staging is the server's export workspace: 8 bytes per slot of ONE pass (at most 32 MiB by default) and 16 bytes per
+ * entry that can come back, min(max_entries, slots of the buckets named).  After the last pass the error word, the total and the entries come back in
+ * one copy sequence and one wait; the values of the entries then go through read_records' path (passes of option db_stage_bytes), only where values
+ * are wanted and the count fits. */
+typedef struct spiral_gpu_kv_entry {
+    uint64_t tag;
+    uint32_t bucket;
+    uint32_t slot;
+} spiral_gpu_kv_entry; /* 16 bytes */
+int spiral_gpu_server_kv_scan(spiral_gpu_server *s, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_entry *entries,
+                              void *values, uint64_t max_entries, uint64_t *n_entries);
+int spiral_gpu_server_kv_scan_at(spiral_gpu_server *s, uint64_t value_bytes, const uint64_t *buckets, uint64_t n_buckets, spiral_gpu_kv_entry *entries,
+                                 void *values, uint64_t max_entries, uint64_t *n_entries);
+/* Host only, no device needed: a listing of the WHOLE table against a key set.  `entries` must be strictly ascending in (bucket, slot), with buckets
+ * below nb and tags that are not 0, else the call refuses by position; two keys with equal tags are refused by position, as kv_put refuses them.  The
+ * hash is the definition's and depends only on nb and the table key, so base and SpiralPack parameter sets share this function.
+ *   where[k]        the position in `entries` of the entry a lookup of key k finds (b1 first, the lowest slot), or -1
+ *   entry_class[e]  0 held: some key's where;  1 shadowed: a key's tag in one of that key's candidate buckets, but a lookup finds another entry first;
+ *                   2 misplaced: a key's tag in a bucket that is neither of its candidates, so no lookup reaches it;  3 orphan: the tag of no key given
+ *   counts          the totals; missing = the number of -1 in where
+ * where, entry_class and counts may each be NULL. */
+typedef struct spiral_gpu_kv_reconcile_counts {
+    uint64_t held, missing, shadowed, misplaced, orphans;
+} spiral_gpu_kv_reconcile_counts;
+int spiral_gpu_kv_reconcile(const spiral_gpu_params *p, const void *table_key16, const void *keys, uint64_t key_bytes, uint64_t n_keys,
+                            const spiral_gpu_kv_entry *entries, uint64_t n_entries, int64_t *where, uint8_t *entry_class,
+                            spiral_gpu_kv_reconcile_counts *counts);
 
 /* read the device database back in reference layouts (tests): plaintext `item` as its n0 x n2 NTT-form MatPoly
  * (pts_encd, :1128), or slabs z_begin .. z_begin+nz-1 of load_db's layout restricted to this server's j-range:
@@ -952,6 +1004,12 @@ int spiral_gpu_pack_server_kv_get(spiral_gpu_pack_server *s, const void *table_k
                                   uint64_t value_bytes, uint64_t n, uint8_t *found);
 int spiral_gpu_pack_server_kv_stats(spiral_gpu_pack_server *s, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets,
                                     spiral_gpu_kv_stats *out);
+/* "Listing" on a SpiralPack server: the base calls' arguments and contract.  The headers are read from trial image 0; an entry's value spans the trial
+ * images and comes back through pack_server_read_records' path.  A trial shard and its shard lane refuse by name. */
+int spiral_gpu_pack_server_kv_scan(spiral_gpu_pack_server *s, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets,
+                                   spiral_gpu_kv_entry *entries, void *values, uint64_t max_entries, uint64_t *n_entries);
+int spiral_gpu_pack_server_kv_scan_at(spiral_gpu_pack_server *s, uint64_t value_bytes, const uint64_t *buckets, uint64_t n_buckets,
+                                      spiral_gpu_kv_entry *entries, void *values, uint64_t max_entries, uint64_t *n_entries);
 /* W_exp_left / W_exp_right (expansion only), V base_dim x base_dim*t_conv (expansion only), v_W out_n x ((out_n+1) x t_conv).  A null pointer
  * among those the geometry needs fails before anything is written: the previous public parameters stay (as for spiral_gpu_server_set_pub_params). */
 int spiral_gpu_pack_server_set_pub_params(spiral_gpu_pack_server *s, const uint64_t *w_left, const uint64_t *w_right,

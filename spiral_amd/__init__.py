@@ -5,6 +5,7 @@ include/spiral_gpu.h).  This package is the thin host-side mirror of the referen
 interface for that path (names and argument meaning of src/spiral.cpp / src/poly.cpp / src/core.cpp),
 used by the parity tests and the benchmark.  numpy uint64 arrays carry the reference layouts.
 """
+from ._lib import KV_ENTRY_DTYPE, KvReconcile, KvScan, KvScanOverflow, kv_reconcile  # noqa: F401
 from ._lib import KvLayout, KvStats, PackShape, Params, RecordLayout, Shape, SpiralGpuError, build, db_items_bytes, kv_hash, kv_layout, lib, pack_kv_layout, record_layout  # noqa: F401
 from ._lib import FINGERPRINT_MODULUS, fingerprint_add, fingerprint_host, fingerprint_of_polys  # noqa: F401
 from .client import Client, ResponseNoise, client_noise_table  # noqa: F401

@@ -79,6 +79,21 @@ class KvStatsStruct(C.Structure):
                 ("hist", C.c_uint64 * 257)]
 
 
+class KvEntry(C.Structure):
+    """spiral_gpu_kv_entry (include/spiral_gpu.h "Listing"): a slot whose tag is not 0, 16 bytes"""
+
+    _fields_ = [("tag", C.c_uint64), ("bucket", C.c_uint32), ("slot", C.c_uint32)]
+
+
+KV_ENTRY_DTYPE = np.dtype([("tag", "<u8"), ("bucket", "<u4"), ("slot", "<u4")])  # the same 16 bytes as a numpy record
+
+
+class KvReconcileCounts(C.Structure):
+    """spiral_gpu_kv_reconcile_counts"""
+
+    _fields_ = [(n, C.c_uint64) for n in ("held", "missing", "shadowed", "misplaced", "orphans")]
+
+
 U64P = C.POINTER(C.c_uint64)
 
 # name -> (restype, argtypes); every symbol include/spiral_gpu.h declares
@@ -317,6 +332,12 @@ PROTOTYPES = {
     "spiral_gpu_pack_server_kv_delete": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, U64P]),
     "spiral_gpu_pack_server_kv_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "spiral_gpu_pack_server_kv_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(KvStatsStruct)]),
+    "spiral_gpu_server_kv_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, U64P]),
+    "spiral_gpu_server_kv_scan_at": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, U64P]),
+    "spiral_gpu_pack_server_kv_scan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, U64P]),
+    "spiral_gpu_pack_server_kv_scan_at": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, U64P]),
+    "spiral_gpu_kv_reconcile": (C.c_int, [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                          C.POINTER(KvReconcileCounts)]),
     "spiral_gpu_client_kv_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "spiral_gpu_client_kv_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p]),
     "spiral_gpu_client_record_queries": (C.c_int, [C.c_void_p, C.c_uint64, U64P, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
@@ -492,6 +513,38 @@ class KvStats:
         return self.used / (self.buckets * self.slots) if self.buckets else 0.0
 
 
+class KvScanOverflow(SpiralGpuError):
+    """a listing that holds more entries than max_entries: .count is the number of entries in the buckets named; nothing was written"""
+
+    def __init__(self, message: str, count: int, max_entries: int):
+        super().__init__(message)
+        self.count, self.max_entries = count, max_entries
+
+
+@dataclass(frozen=True)
+class KvScan:
+    """a listing (include/spiral_gpu.h "Listing"): the entries -- slots whose tag is not 0 -- of a set of buckets, in the order of the buckets and within
+    a bucket by ascending slot; values[k] (where asked for) is the value of entry k.  first_bucket / n_buckets: the range of a kv_scan, None for a
+    kv_scan_at; table_buckets: nb of the table listed"""
+
+    tags: np.ndarray  # uint64 [n]
+    buckets: np.ndarray  # uint32 [n]
+    slots: np.ndarray  # uint32 [n]
+    values: np.ndarray | None  # uint8 [n][V]
+    first_bucket: int | None
+    n_buckets: int | None
+    table_buckets: int
+
+    def __len__(self) -> int:
+        return len(self.tags)
+
+    def entries(self) -> np.ndarray:
+        """the entries as the structured array (tag u64, bucket u32, slot u32) that spiral_gpu_kv_reconcile takes"""
+        out = np.empty(len(self.tags), dtype=KV_ENTRY_DTYPE)
+        out["tag"], out["bucket"], out["slot"] = self.tags, self.buckets, self.slots
+        return out
+
+
 class KeyedRecords:
     """the keyed-record calls of Server and PackServer (include/spiral_gpu.h "Keyed records"): a bucket is an item, a key hashes to two candidate
     buckets.  The class says which library calls are its own (_kv_prefix); out_n (PackServer) selects the SpiralPack layout"""
@@ -549,6 +602,95 @@ class KeyedRecords:
         out = KvStatsStruct()
         check(self._kv("stats")(self.h, int(value_bytes), int(first_bucket), int(n_buckets), C.byref(out)))
         return KvStats(int(out.buckets), int(out.used), int(out.full_buckets), int(out.max_used), int(out.slots), tuple(int(x) for x in out.hist))
+
+    def _kv_scan(self, name, value_bytes, head, values, max_entries, out_entries, out_values, about):
+        """the shared body of kv_scan and kv_scan_at; head: the call's arguments between value_bytes and entries"""
+        lay = kv_layout_for(self.params, value_bytes, getattr(self, "out_n", 0))
+        vb, fn, n = int(value_bytes), self._kv(name), C.c_uint64()
+        if max_entries is None:  # a count-only call first, then exactly that many entries
+            check(fn(self.h, vb, *head, None, None, 0, C.byref(n)))
+            max_entries = n.value
+        max_entries = int(max_entries)
+        ent = np.zeros(max_entries, dtype=KV_ENTRY_DTYPE) if out_entries is None else out_entries
+        if ent.dtype != KV_ENTRY_DTYPE or ent.ndim != 1 or len(ent) < max_entries or not ent.flags.c_contiguous:
+            raise ValueError(f"out_entries is a contiguous array of at least max_entries = {max_entries} records of {KV_ENTRY_DTYPE}")
+        val = None
+        if values:
+            val = np.zeros((max_entries, vb), dtype=np.uint8) if out_values is None else out_values
+            if val.dtype != np.uint8 or val.shape[1:] != (vb,) or len(val) < max_entries or not val.flags.c_contiguous:
+                raise ValueError(f"out_values is a contiguous uint8 array [at least max_entries = {max_entries}][{vb}]")
+        rc = fn(self.h, vb, *head, ent.ctypes.data_as(C.c_void_p) if max_entries else None, val.ctypes.data_as(C.c_void_p) if values and max_entries else None,
+                max_entries, C.byref(n))
+        if rc != 0:
+            message = lib().spiral_gpu_last_error().decode()
+            if n.value > max_entries:
+                raise KvScanOverflow(message, n.value, max_entries)
+            raise SpiralGpuError(message)
+        if n.value > max_entries:  # (max_entries = 0 is the C call's count-only form: it succeeds)
+            raise KvScanOverflow(f"{name}: the buckets named hold {n.value} entries, max_entries is {max_entries}; nothing was written", n.value, max_entries)
+        ent = ent[:n.value]
+        return KvScan(ent["tag"].copy(), ent["bucket"].copy(), ent["slot"].copy(), val[:n.value] if values else None, *about, int(lay.buckets))
+
+    def kv_scan(self, value_bytes: int, first_bucket: int = 0, n_buckets: int | None = None, values: bool = True, max_entries: int | None = None, *,
+                out_entries: np.ndarray | None = None, out_values: np.ndarray | None = None) -> KvScan:
+        """the listing of buckets [first_bucket, first_bucket + n_buckets) (n_buckets None: to the table's end), compacted on the device: only live
+        entries come back, with their values unless values=False.  max_entries None: a count-only call first, then exactly that many; an explicit
+        max_entries is passed through, and a listing that holds more raises KvScanOverflow (.count) with nothing written.  out_entries / out_values: the
+        caller's buffers (KV_ENTRY_DTYPE [max_entries], uint8 [max_entries][V]) in place of fresh ones.  Any server that references the image, lanes
+        included"""
+        lay = kv_layout_for(self.params, value_bytes, getattr(self, "out_n", 0))
+        if n_buckets is None:
+            n_buckets = max(lay.buckets - first_bucket, 0)
+        head = (int(first_bucket), int(n_buckets))
+        return self._kv_scan("scan", value_bytes, head, values, max_entries, out_entries, out_values, head)
+
+    def kv_scan_at(self, value_bytes: int, buckets, values: bool = True, max_entries: int | None = None, *, out_entries: np.ndarray | None = None,
+                   out_values: np.ndarray | None = None) -> KvScan:
+        """the listing of the buckets of a list, in the order of the list (a bucket named twice is listed twice; .buckets are bucket ids); otherwise as
+        kv_scan"""
+        ids = np.ascontiguousarray(buckets, dtype=np.uint64).reshape(-1)
+        head = (ids.ctypes.data_as(C.c_void_p) if ids.size else None, ids.size)
+        return self._kv_scan("scan_at", value_bytes, head, values, max_entries, out_entries, out_values, (None, None))
+
+
+@dataclass(frozen=True)
+class KvReconcile:
+    """spiral_gpu_kv_reconcile's result: where[k] = the entry a lookup of key k finds, or -1; entry_class[e] = 0 held, 1 shadowed, 2 misplaced, 3 orphan;
+    and the totals"""
+
+    where: np.ndarray  # int64 [n_keys]
+    entry_class: np.ndarray  # uint8 [n_entries]
+    held: int
+    missing: int
+    shadowed: int
+    misplaced: int
+    orphans: int
+
+    def missing_keys(self) -> np.ndarray:
+        """positions of the keys no lookup finds"""
+        return np.flatnonzero(self.where < 0)
+
+    def orphan_entries(self) -> np.ndarray:
+        """positions of the entries whose tag belongs to no key given"""
+        return np.flatnonzero(self.entry_class == 3)
+
+    def misplaced_entries(self) -> np.ndarray:
+        """positions of the entries that carry a key's tag in a bucket that is neither of its candidates"""
+        return np.flatnonzero(self.entry_class == 2)
+
+
+def kv_reconcile(params: Params, table_key, keys, scan: KvScan) -> KvReconcile:
+    """a listing of the WHOLE table against a key set (spiral_gpu_kv_reconcile; host only, base and SpiralPack parameter sets alike): which keys are
+    missing, which entries are held, shadowed, misplaced or orphans.  A KvScan that does not cover [0, table_buckets) is refused"""
+    if scan.first_bucket != 0 or scan.n_buckets != scan.table_buckets:
+        what = "a kv_scan_at listing" if scan.first_bucket is None else f"buckets [{scan.first_bucket}, +{scan.n_buckets})"
+        raise SpiralGpuError(f"kv_reconcile takes a listing of the whole table, buckets [0, {scan.table_buckets}): this one is {what}")
+    tk, keys, ent = kv_table_key(table_key), kv_keys(keys), scan.entries()
+    where, cls, counts = np.empty(keys.shape[0], dtype=np.int64), np.empty(len(ent), dtype=np.uint8), KvReconcileCounts()
+    check(lib().spiral_gpu_kv_reconcile(C.byref(params), tk.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p) if keys.size else None, keys.shape[1],
+                                        keys.shape[0], ent.ctypes.data_as(C.c_void_p) if len(ent) else None, len(ent), where.ctypes.data_as(C.c_void_p),
+                                        cls.ctypes.data_as(C.c_void_p), C.byref(counts)))
+    return KvReconcile(where, cls, int(counts.held), int(counts.missing), int(counts.shadowed), int(counts.misplaced), int(counts.orphans))
 
 
 def record_array(records, record_bytes: int, n: int | None = None) -> np.ndarray:

@@ -553,7 +553,9 @@ static int run_pack_records(const spiral_gpu_params& p, uint32_t out_n, uint64_t
 // number K is looked up privately (kv_queries, two answers, kv_decode) and compared with the generator, or, for K >= n, must not be found; it is
 // written by kv_put in generation 1 and looked up again; one key that was never stored is looked up; kv_stats reports the table's load.  On a base
 // server, or with --high-rate on a SpiralPack server with OUTN as out_n.
-static int run_kv(const spiral_gpu_params& p, uint32_t out_n, uint64_t key_no, uint64_t V, uint64_t seed, bool nonoise) {
+// --kv-scan: after those steps the whole table is listed with values (kv_scan: a count-only call, then the entries), reconciled against every key the
+// run stored -- the key written by kv_put included -- and every held value is compared with the generator.
+static int run_kv(const spiral_gpu_params& p, uint32_t out_n, uint64_t key_no, uint64_t V, uint64_t seed, bool nonoise, bool scan) {
     if (out_n) cout << "Using n=" << out_n << endl;
     spiral_gpu_kv_layout lay;
     GPU_OK(out_n ? spiral_gpu_pack_kv_layout_of(&p, out_n, V, &lay) : spiral_gpu_kv_layout_of(&p, V, &lay));
@@ -658,6 +660,36 @@ static int run_kv(const spiral_gpu_params& p, uint32_t out_n, uint64_t key_no, u
     all_ok = all_ok && st.used == stored_now;
     cout << "Table load (kv_stats): " << st.used << " of " << lay.capacity << " slots used, load " << (double)st.used / (double)lay.capacity << ", fullest bucket "
          << st.max_used << " of " << st.slots << ", full buckets " << st.full_buckets << endl;
+    if (scan) {
+        auto list = [&](spiral_gpu_kv_entry* entries, void* values, uint64_t max_entries, uint64_t* n) {
+            return out_n ? spiral_gpu_pack_server_kv_scan(pack, V, 0, lay.buckets, entries, values, max_entries, n)
+                         : spiral_gpu_server_kv_scan(base, V, 0, lay.buckets, entries, values, max_entries, n);
+        };
+        uint64_t count = 0, listed = 0;
+        GPU_OK(list(nullptr, nullptr, 0, &count));
+        std::vector<spiral_gpu_kv_entry> entries((size_t)count);
+        std::vector<uint8_t> listed_vals((size_t)(count * V));
+        if (count) GPU_OK(list(entries.data(), listed_vals.data(), count, &listed));
+        // the keys the run stored: 0 .. n_loaded - 1, and key K where the put added it (its value is generation 1's either way)
+        const bool put_is_new = key_no >= n_loaded;
+        const uint64_t n_keys = n_loaded + (put_is_new ? 1 : 0);
+        std::vector<uint8_t> all_keys((size_t)(n_keys * KB));
+        memcpy(all_keys.data(), keys.data(), (size_t)(n_loaded * KB));
+        if (put_is_new) key_of(key_no, all_keys.data() + n_loaded * KB);
+        std::vector<int64_t> where((size_t)n_keys);
+        std::vector<uint8_t> entry_class((size_t)count);
+        spiral_gpu_kv_reconcile_counts rc{};
+        GPU_OK(spiral_gpu_kv_reconcile(&p, tk, all_keys.data(), KB, n_keys, entries.data(), listed, where.data(), entry_class.data(), &rc));
+        bool values_ok = listed == count && count == st.used;
+        for (uint64_t k = 0; k < n_keys && values_ok; k++) {
+            if (where[k] < 0) continue;
+            const uint64_t number = k < n_loaded ? k : key_no;
+            record_bytes_of(number == key_no ? 1 : 0, number, V, want.data());
+            values_ok = !memcmp(want.data(), listed_vals.data() + (size_t)where[k] * V, (size_t)V);
+        }
+        all_ok = all_ok && values_ok && rc.missing == 0 && rc.orphans == 0 && rc.shadowed == 0 && rc.misplaced == 0 && rc.held == n_keys;
+        cout << "Scan: " << listed << " entries, missing: " << rc.missing << ", orphans: " << rc.orphans << ", values correct: " << (values_ok ? 1 : 0) << endl;
+    }
     cout << "Is correct?: " << (all_ok ? 1 : 0) << endl;
     if (pack) spiral_gpu_pack_server_destroy(pack);
     if (base) spiral_gpu_server_destroy(base);
@@ -681,7 +713,7 @@ int main(int argc, char** argv) {
     uint64_t pack_record_bytes = 0;  // --high-rate --pack-record-bytes S: the same on SpiralPack servers (run_pack_records above)
     bool pack_record_run = false;
     uint64_t kv_value_bytes = 0;  // --kv-value-bytes V --device-client [--high-rate]: IDX_TARGET is a key number (run_kv above)
-    bool kv_run = false;
+    bool kv_run = false, kv_scan = false;  // --kv-scan: list and reconcile the table at the end of the keyed run
     // as the reference (random_device, src/core.cpp:202; it labels its own generator NOT SECURE): two words of it.
     // This client is a test harness for the server path, not a hardened client.
     std::random_device rd;
@@ -740,6 +772,12 @@ int main(int argc, char** argv) {
             kv_run = true;
             if (i + 1 < argc) kv_value_bytes = strtoull(argv[++i], nullptr, 10);
         }
+        // --kv-scan with --kv-value-bytes: the run ends with a listing of the whole table, reconciled against the keys it stored
+        if (!strcmp(argv[i], "--kv-scan")) kv_scan = true;
+    }
+    if (kv_scan && !kv_run) {
+        fprintf(stderr, "spiral: --kv-scan takes --kv-value-bytes V (it lists the keyed table that run builds)\n");
+        return 1;
     }
     if (kv_run) {
         if (kv_value_bytes == 0) {
@@ -836,7 +874,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "spiral: no ROCm device found; this build has no CPU path\n");
         return 1;
     }
-    if (kv_run) return run_kv(p, high_rate ? (uint32_t)param(argc, argv, "OUTN", 2) : 0u, idx_target, kv_value_bytes, seed, nonoise);
+    if (kv_run) return run_kv(p, high_rate ? (uint32_t)param(argc, argv, "OUTN", 2) : 0u, idx_target, kv_value_bytes, seed, nonoise, kv_scan);
     if (record_run) return run_records(p, idx_target, record_bytes, seed, nonoise);
     if (pack_record_run) return run_pack_records(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, pack_record_bytes, seed, nonoise);
     if (high_rate) return run_high_rate(p, (uint32_t)param(argc, argv, "OUTN", 2), idx_target, seed, nonoise, show_diff, qnum_first, batch, instances);

@@ -41,6 +41,7 @@ struct Options {
                            // read only where that is decided (db_image.h DbLayout::limbs_ok), never by what works on a converted image
     uint32_t query_batch_chunk = 512;  // set_query_batch: message polynomials per lane per staging pass of messages too large to check on the host
                                        // (= message.h kWireChunkPolys / kMaxLanes: all lanes together fill set_query_wire's staging), at least 1
+    uint32_t kv_scan_chunk = 0;  // kv_scan / kv_scan_at: buckets per pass, 0 = automatic (kv_host.h kv_scan_pass), else 1 .. 2^16
 };
 Options& options();  // server.cpp; the three documented environment variables are read once, on first use
 
@@ -853,6 +854,33 @@ struct KvStatsParams {
     uint64_t p_db;
 };
 void launch_kv_stats(const DeviceTables& t, const KvStatsParams& p, bool pack, hipStream_t s);
+// Listing (include/spiral_gpu.h "Listing", spiral_gpu_server_kv_scan / _kv_scan_at): one pass over n_buckets <= 2^16 buckets, three launches in stream
+// order, no workgroup waits for another.  Workgroup g of the pass has bucket first + g (ids == null: the range form), or ids[first + g] (the list form:
+// first is the pass's position in the list).
+//   decode:  the probe's work on the bucket; stage[g * slots + s] = tag s (stage == null in a count-only call: not stored), counts[g] = tags that are not
+//            0.  *err as for kv_stats with (first + g) in the bucket's place: the bucket of the range form, the POSITION of the list form.
+//   offsets: ONE workgroup; offsets[g] = *total + the exclusive prefix sum of counts, then *total += the pass's sum: stream order carries the running
+//            total from pass to pass.
+//   compact: entry offsets[g] + (rank of slot s among the bucket's non-zero tags) = {tag, bucket, s}, where that index is below max_entries.
+struct KvScanParams {
+    const uint64_t* db;  // as KvProbeParams
+    const uint32_t* ids;
+    uint64_t* stage;
+    uint32_t* counts;
+    unsigned long long* offsets;
+    unsigned long long* total;
+    unsigned long long* err;
+    ulonglong2* entries;  // spiral_gpu_kv_entry as one 16-byte store: {tag, bucket | slot << 32}
+    unsigned long long max_entries;
+    uint32_t first, n_buckets;
+    uint32_t form;
+    uint32_t num_per, dim0;
+    uint32_t w, slots;
+    uint64_t p_db;
+};
+void launch_kv_scan_decode(const DeviceTables& t, const KvScanParams& p, bool pack, hipStream_t s);
+void launch_kv_scan_offsets(const KvScanParams& p, hipStream_t s);
+void launch_kv_scan_compact(const KvScanParams& p, hipStream_t s);
 
 // ---- client session (client.hip; the format: client_device.h) ---------------------------------------------------------------
 // noise polynomials of n_msgs messages, `per_msg` each: polynomial j of message b is noise polynomial first + j under the 32-byte noise key keys[b]

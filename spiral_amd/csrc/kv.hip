@@ -11,6 +11,10 @@
 // Table occupancy (spiral_gpu_server_kv_stats / spiral_gpu_pack_server_kv_stats; kernels.h KvStatsParams): the probe's gather, transform and header
 // packing over a range of buckets, whose (j, ii) come from the block index -- no table goes up -- and ONE integer atomic add per bucket into a
 // histogram of used slots, 257 words that come back instead of the headers.
+//
+// Listing (spiral_gpu_server_kv_scan / _kv_scan_at and the SpiralPack twins; kernels.h KvScanParams): the same gather and header decode over a pass of
+// buckets, then a stream compaction in three launches -- per-bucket counts, one workgroup's exclusive scan on top of a running total, entries written
+// densely in (bucket, slot) order -- so only live entries come back.  No launch waits for another workgroup.
 #include "db_plain_device.h"
 #include "kernels.h"
 #include "ntt_device.h"
@@ -106,7 +110,101 @@ void launch_kv_stats_form(const Tables& tb, const KvStatsParams& p, hipStream_t 
     }
 }
 
+// ---- Listing (kernels.h KvScanParams): decode, offsets, compact; three launches per pass, none of which waits for another workgroup ----------------
+// the bucket of workgroup g of a pass: first + g, or the list's ids[first + g]
+__device__ __forceinline__ uint32_t kv_scan_bucket(const KvScanParams& p, uint32_t g) { return p.ids ? p.ids[p.first + g] : p.first + g; }
+
+// One bucket per workgroup, as kv_stats_kernel and for its reason.  The error word carries (first + g): the bucket of the range form, the position of
+// the list form.
+template <uint32_t FORM, bool PACK>
+__global__ __launch_bounds__(256, 6) void kv_scan_decode_kernel(Tables t, KvScanParams p) {
+    __shared__ uint64_t sh[kLdsWords];
+    __shared__ uint32_t used[4];
+    const uint32_t tid = threadIdx.x, g = blockIdx.x, bucket = kv_scan_bucket(p, g);
+    const unsigned long long err_base = (unsigned long long)(p.first + g) * kN;
+    const uint32_t bad = image_poly_plain<FORM, PACK>(p.db, bucket / p.num_per, bucket % p.num_per, 0u, p.num_per, p.dim0, p.p_db, t.inv, sh, tid);
+    if (bad < kN) atomicMin(p.err, err_base + bad);
+    __syncthreads();
+    const uint64_t tag = kv_header_tag(sh, tid, p.slots, p.w, p.err, err_base);
+    if (p.stage && tid < p.slots) p.stage[(size_t)g * p.slots + tid] = tag;
+    const unsigned long long ballot = __ballot(tag != 0);
+    if ((tid & 63u) == 0) used[tid >> 6] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    if (tid == 0) p.counts[g] = used[0] + used[1] + used[2] + used[3];
+}
+
+// ONE workgroup: the exclusive prefix sums of the pass's counts on top of the running total, 256 buckets a step (a wave's inclusive scan by shuffles,
+// the four waves' sums through LDS), then the total moves on by the pass's sum.
+__global__ __launch_bounds__(256) void kv_scan_offsets_kernel(KvScanParams p) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    unsigned long long run = *p.total;  // (read by every thread; written below, behind the loop's barriers: n_buckets >= 1)
+    for (uint32_t i0 = 0; i0 < p.n_buckets; i0 += 256u) {
+        const uint32_t i = i0 + tid, c = i < p.n_buckets ? p.counts[i] : 0u;
+        uint32_t x = c;
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t k = 0; k < 4u; k++) {
+            if (k < wave) before += wsum[k];
+            all += wsum[k];
+        }
+        if (i < p.n_buckets) p.offsets[i] = run + before + (x - c);
+        run += all;
+        __syncthreads();
+    }
+    if (tid == 0) *p.total = run;
+}
+
+// One workgroup per bucket: thread s has tag s of the staged header; its rank among the bucket's non-zero tags is the lower waves' counts plus the
+// lower lanes of its own wave's ballot.  An entry goes out as ONE 16-byte vector store, and only where its index is below max_entries (the host's
+// buffer holds min(max_entries, every slot of the call) entries).
+__global__ __launch_bounds__(256) void kv_scan_compact_kernel(KvScanParams p) {
+    __shared__ uint32_t used[4];
+    const uint32_t tid = threadIdx.x, g = blockIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint64_t tag = tid < p.slots ? p.stage[(size_t)g * p.slots + tid] : 0ull;
+    const unsigned long long ballot = __ballot(tag != 0);
+    if (lane == 0) used[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    if (tag == 0) return;
+    uint32_t rank = (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    for (uint32_t k = 0; k < wave; k++) rank += used[k];
+    const unsigned long long at = p.offsets[g] + rank;
+    if (at < p.max_entries) p.entries[at] = make_ulonglong2(tag, (unsigned long long)kv_scan_bucket(p, g) | ((unsigned long long)tid << 32));
+}
+
 }  // namespace
+
+void launch_kv_scan_decode(const DeviceTables& t, const KvScanParams& p, bool pack, hipStream_t s) {
+    if (p.n_buckets == 0) return;
+    const Tables tb{t.fwd, t.inv};
+    const dim3 grid(p.n_buckets), block(256);
+    if (!pack) {
+        if (p.form == DBX_PACKED)
+            hipLaunchKernelGGL((kv_scan_decode_kernel<DBX_PACKED, false>), grid, block, 0, s, tb, p);
+        else
+            hipLaunchKernelGGL((kv_scan_decode_kernel<DBX_LIMBS, false>), grid, block, 0, s, tb, p);
+    } else if (p.form == DBX_PACKED)
+        hipLaunchKernelGGL((kv_scan_decode_kernel<DBX_PACKED, true>), grid, block, 0, s, tb, p);
+    else if (p.form == DBX_LIMBS)
+        hipLaunchKernelGGL((kv_scan_decode_kernel<DBX_LIMBS, true>), grid, block, 0, s, tb, p);
+    else
+        hipLaunchKernelGGL((kv_scan_decode_kernel<DBX_LIMBS8, true>), grid, block, 0, s, tb, p);
+}
+
+void launch_kv_scan_offsets(const KvScanParams& p, hipStream_t s) {
+    if (p.n_buckets == 0) return;
+    hipLaunchKernelGGL(kv_scan_offsets_kernel, dim3(1), dim3(256), 0, s, p);
+}
+
+void launch_kv_scan_compact(const KvScanParams& p, hipStream_t s) {
+    if (p.n_buckets == 0) return;
+    hipLaunchKernelGGL(kv_scan_compact_kernel, dim3(p.n_buckets), dim3(256), 0, s, p);
+}
 
 void launch_kv_probe(const DeviceTables& t, const KvProbeParams& p, bool pack, hipStream_t s) {
     if (p.n_entries == 0) return;

@@ -90,9 +90,9 @@ inline KvKey kv_hash(uint64_t nb, const uint8_t* table_key16, const uint8_t* key
 }
 // the n keys of a call, [n][key_bytes]; two equal tags are refused by position
 inline int kv_hash_keys(const char* what, uint64_t nb, const void* table_key16, const void* keys, uint64_t key_bytes, uint64_t n, bool distinct,
-                        std::vector<KvKey>& out) {
+                        std::vector<KvKey>& out, bool bounded = true) {
     if (!table_key16 || (n && key_bytes && !keys)) return fail("%s: null argument", what);
-    if (n > (1ull << 24)) return fail("%s: at most 2^24 keys per call", what);
+    if (bounded && n > (1ull << 24)) return fail("%s: at most 2^24 keys per call", what);  // (kv_reconcile takes a whole table's key set: unbounded)
     out.resize((size_t)n);
     static const uint8_t none = 0;
     for (uint64_t k = 0; k < n; k++)
@@ -374,6 +374,178 @@ inline int kv_stats(ExportWork& W, const DeviceTables& tb, hipStream_t st, const
     }
     s.full_buckets = s.hist[l.slots];
     *out = s;
+    return 0;
+}
+
+// ---- Listing (include/spiral_gpu.h "Listing"): an entry is a slot whose tag is not 0; a listing of a set of buckets is all their entries in the order
+// of the buckets, and within a bucket by ascending slot; with values, row k is bytes [8 slots + slot V, + V) of entry k's bucket stream --------------
+static_assert(sizeof(spiral_gpu_kv_entry) == 16 && sizeof(ulonglong2) == 16, "an entry is one 16-byte store: {tag, bucket | slot << 32}");
+
+// buckets per pass: option kv_scan_chunk, or the most that keeps a pass's staged tags within 2^22 (32 MiB) and the pass within 2^16 buckets
+inline uint32_t kv_scan_pass(uint32_t slots) {
+    const uint32_t set = options().kv_scan_chunk;
+    return set ? set : std::max<uint32_t>(1u, std::min<uint32_t>(1u << 16, (1u << 22) / slots));
+}
+
+// kv_scan (ids == null: buckets [first, first + n)) and kv_scan_at (the n buckets of ids, in that order) after the server's own checks, ONE body for both
+// servers.  Passes of kv_scan_pass buckets on I.st, three launches each -- decode, offsets, compact (kv.hip; count-only: no staging, no compact) --
+// with nothing read back in between: the running total lives on the device.  Then one copy of the error word, the total and the entries, one wait.
+// Values, where wanted and the count fits: one RecordPiece per entry, the one kv_get builds, through read_record_pieces.
+inline int kv_scan(const KvImage& I, const char* what, const spiral_gpu_kv_layout& l, uint64_t first, const uint64_t* ids, uint64_t n, spiral_gpu_kv_entry* entries,
+                   void* values, uint64_t max_entries, uint64_t* n_entries) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_OK(hipStreamIsCapturing(I.st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail("%s cannot be called while the server's stream is being captured", what);
+    if (l.buckets > 0x7FFFFFFFull) return fail("%s: a table of %llu buckets, at most 2^31 - 1", what, (unsigned long long)l.buckets);
+    if (max_entries > 0 && !entries) return fail("%s: entries is NULL with max_entries = %llu (count-only: max_entries = 0, entries = values = NULL)", what, (unsigned long long)max_entries);
+    std::vector<uint32_t> id32;
+    if (ids) {
+        if (n > 0x7FFFFFFFull) return fail("%s: at most 2^31 - 1 buckets per call", what);
+        id32.resize((size_t)n);
+        for (uint64_t k = 0; k < n; k++) {
+            if (ids[k] >= l.buckets) return fail("%s: bucket %llu at position %llu outside the table of %llu", what, (unsigned long long)ids[k], (unsigned long long)k, (unsigned long long)l.buckets);
+            id32[(size_t)k] = (uint32_t)ids[k];
+        }
+    } else if (first > l.buckets || n > l.buckets - first)
+        return fail("%s: buckets [%llu, +%llu) outside the table of %llu", what, (unsigned long long)first, (unsigned long long)n, (unsigned long long)l.buckets);
+    *n_entries = 0;
+    if (n == 0) return 0;
+    const bool count_only = max_entries == 0 && !entries && !values;
+    const uint64_t cap_entries = count_only ? 0 : std::min<uint64_t>(max_entries, n * l.slots);  // what can come back
+    const uint32_t pass = (uint32_t)std::min<uint64_t>(kv_scan_pass(l.slots), n);
+    // one buffer: [error word][running total][ids of the call][counts of a pass][offsets of a pass][staged tags of a pass][entries of the call]
+    auto up16 = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    const size_t o_ids = 16, o_counts = up16(o_ids + id32.size() * 4), o_offsets = up16(o_counts + (size_t)pass * 4), o_stage = up16(o_offsets + (size_t)pass * 8);
+    const size_t o_entries = up16(o_stage + (count_only ? 0 : (size_t)pass * l.slots * 8)), dev_bytes = o_entries + (size_t)cap_entries * 16;
+    ExportWork& W = I.xwork;
+    if (W.dev.words * 8 < dev_bytes) {
+        W.dev.release();
+        W.dev.words = 0;
+        if (W.dev.alloc((dev_bytes + 7) / 8)) {
+            (void)hipGetLastError();
+            W.dev.p = nullptr;
+            W.dev.words = 0;
+            return fail("no device memory for the listing's staging (%zu bytes)", dev_bytes);
+        }
+    }
+    if (W.host_bytes < cap_entries * 16) {
+        if (W.host) (void)hipHostFree(W.host);
+        W.host = nullptr;
+        W.host_bytes = 0;
+        if (hipHostMalloc((void**)&W.host, (size_t)cap_entries * 16, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail("no pinned host memory for the listing's bounce buffer (%zu bytes)", (size_t)cap_entries * 16);
+        }
+        W.host_bytes = (size_t)cap_entries * 16;
+    }
+    uint8_t* d = reinterpret_cast<uint8_t*>(W.dev.p);
+    HIP_OK(hipMemsetAsync(d, 0xFF, 8, I.st));  // the error word: ~0 = every coefficient read so far is a plaintext value
+    HIP_OK(hipMemsetAsync(d + 8, 0, 8, I.st));  // the running total
+    if (ids) HIP_OK(hipMemcpyAsync(d + o_ids, id32.data(), id32.size() * 4, hipMemcpyHostToDevice, I.st));
+    KvScanParams sp{};
+    sp.db = I.src.db;
+    sp.ids = ids ? reinterpret_cast<const uint32_t*>(d + o_ids) : nullptr;
+    sp.stage = count_only ? nullptr : reinterpret_cast<uint64_t*>(d + o_stage);
+    sp.counts = reinterpret_cast<uint32_t*>(d + o_counts);
+    sp.offsets = reinterpret_cast<unsigned long long*>(d + o_offsets);
+    sp.total = reinterpret_cast<unsigned long long*>(d + 8);
+    sp.err = reinterpret_cast<unsigned long long*>(d);
+    sp.entries = reinterpret_cast<ulonglong2*>(d + o_entries);
+    sp.max_entries = cap_entries;
+    sp.form = I.src.form;
+    sp.num_per = I.src.num_per;
+    sp.dim0 = I.src.dim0;
+    sp.w = l.coeff_bits;
+    sp.slots = l.slots;
+    sp.p_db = I.p_db;
+    for (uint64_t done = 0; done < n; done += pass) {
+        sp.first = (uint32_t)((ids ? 0 : first) + done);
+        sp.n_buckets = (uint32_t)std::min<uint64_t>(pass, n - done);
+        launch_kv_scan_decode(I.tb, sp, I.src.pack != 0, I.st);
+        launch_kv_scan_offsets(sp, I.st);
+        if (!count_only) launch_kv_scan_compact(sp, I.st);
+        HIP_OK(hipGetLastError());
+    }
+    unsigned long long back[2] = {~0ull, 0};  // the error word and the total
+    HIP_OK(hipMemcpyAsync(back, d, sizeof(back), hipMemcpyDeviceToHost, I.st));
+    // (the entries' count is the total, which is not known here: what can come back is copied to the bounce buffer, and min(total, max_entries) of it
+    // goes on to the caller.  A caller that sized its buffer by a count-only call copies exactly the live entries.)
+    if (cap_entries) HIP_OK(hipMemcpyAsync(W.host, d + o_entries, (size_t)cap_entries * 16, hipMemcpyDeviceToHost, I.st));
+    HIP_OK(hipStreamSynchronize(I.st));
+    if (back[0] != ~0ull) {
+        const uint64_t at = back[0] / kN;
+        if (ids)
+            return fail("%s: the image holds no keyed table at position %llu of the list, bucket %llu (polynomial 0, coefficient %u is no plaintext value below "
+                        "2^coeff_bits): not a record database (fill_db_random, a load_db of arbitrary words, or items loaded with larger coefficients)",
+                        what, (unsigned long long)at, (unsigned long long)ids[at], (uint32_t)(back[0] % kN));
+        return fail("%s: the image holds no keyed table at bucket %llu (polynomial 0, coefficient %u is no plaintext value below 2^coeff_bits): not a record "
+                    "database (fill_db_random, a load_db of arbitrary words, or items loaded with larger coefficients)",
+                    what, (unsigned long long)at, (uint32_t)(back[0] % kN));
+    }
+    const uint64_t total = back[1];
+    *n_entries = total;
+    if (count_only) return 0;
+    if (total > max_entries)
+        return fail("%s: the buckets named hold %llu entries, max_entries is %llu; nothing was written", what, (unsigned long long)total, (unsigned long long)max_entries);
+    memcpy(entries, W.host, (size_t)total * 16);
+    if (!values || total == 0) return 0;
+    const uint64_t V = l.value_bytes;
+    return read_record_pieces(
+        I.xwork, I.tb, I.st, static_cast<uint8_t*>(values), V, RecordChunk{0, V}, l.coeff_bits, I.p_db, total,
+        [&](uint64_t k, RecordPiece* pc) {
+            const spiral_gpu_kv_entry& e = entries[k];
+            *pc = RecordPiece{k, e.bucket / I.num_per, e.bucket % I.num_per, (uint32_t)(8u * l.slots + e.slot * V), (uint32_t)V};
+            return true;
+        },
+        I.src, [&](uint64_t pos) { return pos; }, I.tr);
+}
+
+// spiral_gpu_kv_reconcile (include/spiral_gpu.h "Listing"): a whole table's listing against a key set, on the host.  nb: the table's buckets.
+inline int kv_reconcile(uint64_t nb, const void* table_key16, const void* keys, uint64_t key_bytes, uint64_t n_keys, const spiral_gpu_kv_entry* entries, uint64_t n_entries,
+                        int64_t* where, uint8_t* entry_class, spiral_gpu_kv_reconcile_counts* counts) {
+    const char* what = "kv_reconcile";
+    if (n_entries && !entries) return fail("%s: null argument", what);
+    for (uint64_t e = 0; e < n_entries; e++) {
+        if (entries[e].bucket >= nb) return fail("%s: entry %llu names bucket %u outside the table of %llu", what, (unsigned long long)e, entries[e].bucket, (unsigned long long)nb);
+        if (entries[e].tag == 0) return fail("%s: entry %llu has tag 0 (an empty slot is no entry)", what, (unsigned long long)e);
+        if (e && (entries[e].bucket < entries[e - 1].bucket || (entries[e].bucket == entries[e - 1].bucket && entries[e].slot <= entries[e - 1].slot)))
+            return fail("%s: entry %llu (bucket %u, slot %u) does not follow entry %llu (bucket %u, slot %u): a listing ascends strictly in (bucket, slot)", what,
+                        (unsigned long long)e, entries[e].bucket, entries[e].slot, (unsigned long long)(e - 1), entries[e - 1].bucket, entries[e - 1].slot);
+    }
+    std::vector<KvKey> hk;
+    if (kv_hash_keys(what, nb, table_key16, keys, key_bytes, n_keys, true, hk, false)) return -1;
+    // the entries of bucket b: [lower bound of b, lower bound of b + 1)
+    auto bucket_begin = [&](uint64_t b) {
+        return (uint64_t)(std::lower_bound(entries, entries + n_entries, b, [](const spiral_gpu_kv_entry& e, uint64_t bucket) { return e.bucket < bucket; }) - entries);
+    };
+    // what a lookup of key k finds: b1 first, the lowest slot
+    auto find = [&](const KvKey& h) -> int64_t {
+        for (uint32_t c = 0; c < 2; c++)
+            for (uint64_t e = bucket_begin(h.b[c]); e < n_entries && entries[e].bucket == h.b[c]; e++)
+                if (entries[e].tag == h.tag) return (int64_t)e;
+        return -1;
+    };
+    spiral_gpu_kv_reconcile_counts ct{};
+    std::vector<std::pair<uint64_t, uint64_t>> byt((size_t)n_keys);  // (tag, key), tags distinct
+    std::vector<int64_t> at((size_t)n_keys);
+    for (uint64_t k = 0; k < n_keys; k++) {
+        byt[(size_t)k] = {hk[(size_t)k].tag, k};
+        at[(size_t)k] = find(hk[(size_t)k]);
+        if (at[(size_t)k] < 0) ct.missing++;
+        if (where) where[k] = at[(size_t)k];
+    }
+    std::sort(byt.begin(), byt.end());
+    for (uint64_t e = 0; e < n_entries; e++) {
+        uint8_t cls = 3;
+        const auto it = std::lower_bound(byt.begin(), byt.end(), std::make_pair(entries[e].tag, (uint64_t)0));
+        if (it != byt.end() && it->first == entries[e].tag) {
+            const KvKey& h = hk[(size_t)it->second];
+            cls = at[(size_t)it->second] == (int64_t)e ? 0 : (entries[e].bucket == h.b[0] || entries[e].bucket == h.b[1]) ? 1 : 2;
+        }
+        (cls == 0 ? ct.held : cls == 1 ? ct.shadowed : cls == 2 ? ct.misplaced : ct.orphans)++;
+        if (entry_class) entry_class[e] = cls;
+    }
+    if (counts) *counts = ct;
     return 0;
 }
 

@@ -869,6 +869,31 @@ int spiral_gpu_pack_server_kv_stats(spiral_gpu_pack_server* S, uint64_t value_by
     return kv_stats(S->xwork, S->tb, S->stream, S->img->export_source(0), l, S->p.p_db, first_bucket, n_buckets, out);
 }
 
+// Listing: the headers from trial image 0, the entries' values across the trials through read_records' path (kv_host.h kv_scan); the owner or a lane,
+// on its own stream
+namespace {
+int pk_kv_scan_call(spiral_gpu_pack_server* S, const char* what, uint64_t value_bytes, uint64_t first_bucket, const uint64_t* buckets, uint64_t n_buckets,
+                    spiral_gpu_kv_entry* entries, void* values, uint64_t max_entries, uint64_t* n_entries) {
+    if (enter(S)) return -1;
+    if (!n_entries) return fail("%s: null argument", what);
+    spiral_gpu_kv_layout l;
+    if (pk_kv_call(S, what, value_bytes, &l)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    FpTrackCtx none;
+    return kv_scan(pk_kv_image(S, none), what, l, first_bucket, buckets, n_buckets, entries, values, max_entries, n_entries);
+}
+}  // namespace
+int spiral_gpu_pack_server_kv_scan(spiral_gpu_pack_server* S, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_entry* entries, void* values,
+                                   uint64_t max_entries, uint64_t* n_entries) {
+    return pk_kv_scan_call(S, "kv_scan", value_bytes, first_bucket, nullptr, n_buckets, entries, values, max_entries, n_entries);
+}
+int spiral_gpu_pack_server_kv_scan_at(spiral_gpu_pack_server* S, uint64_t value_bytes, const uint64_t* buckets, uint64_t n_buckets, spiral_gpu_kv_entry* entries,
+                                      void* values, uint64_t max_entries, uint64_t* n_entries) {
+    static const uint64_t none = 0;  // (an empty list may be NULL)
+    if (n_buckets && !buckets) return fail("kv_scan_at: null argument");
+    return pk_kv_scan_call(S, "kv_scan_at", value_bytes, 0, buckets ? buckets : &none, n_buckets, entries, values, max_entries, n_entries);
+}
+
 int spiral_gpu_pack_server_fill_db_random(spiral_gpu_pack_server* S, uint64_t seed) {
     if (!S) return fail("null server");
     if (pk_refuse_lane(S, "load")) return -1;

@@ -54,6 +54,7 @@ int spiral_gpu_set_option(const char* name, int64_t value) {
     else if (n == "pack_pair_blocks" && (value == 0 || value == 1)) o.pack_pair_blocks = (int)value;
     else if (n == "sweep_narrow" && (value == 0 || value == 1)) o.sweep_narrow = (int)value;
     else if (n == "query_batch_chunk" && value >= 1 && value <= 0xFFFFFFFFll) o.query_batch_chunk = (uint32_t)value;
+    else if (n == "kv_scan_chunk" && value >= 0 && value <= (1ll << 16)) o.kv_scan_chunk = (uint32_t)value;
     else return fail("unknown option '%s' or value %lld out of range", name, (long long)value);
     return 0;
 }
@@ -74,6 +75,7 @@ int spiral_gpu_get_option(const char* name, int64_t* value) {
     else if (n == "pack_pair_blocks") *value = o.pack_pair_blocks;
     else if (n == "sweep_narrow") *value = o.sweep_narrow;
     else if (n == "query_batch_chunk") *value = o.query_batch_chunk;
+    else if (n == "kv_scan_chunk") *value = o.kv_scan_chunk;
     else if (n == "graph_captures") *value = (int64_t)g_captures.load();  // (read only)
     else if (n == "pack_lane_batches") *value = (int64_t)g_pack_lane_batches.load();  // (read only)
     else if (n == "key_binds") *value = (int64_t)g_key_binds.load();  // (read only)

@@ -939,6 +939,38 @@ int spiral_gpu_server_kv_stats(spiral_gpu_server* S, uint64_t value_bytes, uint6
     return kv_stats(S->xwork, S->tb, S->stream, S->img->export_source(), l, S->p.p_db, first_bucket, n_buckets, out);
 }
 
+// Listing: passes of three launches over the buckets named, the live entries back, their values through read_records' path (kv_host.h kv_scan); any
+// server that references the image, on its own stream
+namespace {
+int kv_scan_call(spiral_gpu_server* S, const char* what, uint64_t value_bytes, uint64_t first_bucket, const uint64_t* buckets, uint64_t n_buckets,
+                 spiral_gpu_kv_entry* entries, void* values, uint64_t max_entries, uint64_t* n_entries) {
+    if (enter(S)) return -1;
+    if (!n_entries) return fail("%s: null argument", what);
+    spiral_gpu_kv_layout l;
+    if (kv_call(S, what, value_bytes, &l)) return -1;
+    if (!S->img->loaded) return fail("no database loaded");
+    FpTrackCtx none;
+    return kv_scan(kv_image(S, none), what, l, first_bucket, buckets, n_buckets, entries, values, max_entries, n_entries);
+}
+}  // namespace
+int spiral_gpu_server_kv_scan(spiral_gpu_server* S, uint64_t value_bytes, uint64_t first_bucket, uint64_t n_buckets, spiral_gpu_kv_entry* entries, void* values,
+                              uint64_t max_entries, uint64_t* n_entries) {
+    return kv_scan_call(S, "kv_scan", value_bytes, first_bucket, nullptr, n_buckets, entries, values, max_entries, n_entries);
+}
+int spiral_gpu_server_kv_scan_at(spiral_gpu_server* S, uint64_t value_bytes, const uint64_t* buckets, uint64_t n_buckets, spiral_gpu_kv_entry* entries, void* values,
+                                 uint64_t max_entries, uint64_t* n_entries) {
+    static const uint64_t none = 0;  // (an empty list may be NULL)
+    if (n_buckets && !buckets) return fail("kv_scan_at: null argument");
+    return kv_scan_call(S, "kv_scan_at", value_bytes, 0, buckets ? buckets : &none, n_buckets, entries, values, max_entries, n_entries);
+}
+
+int spiral_gpu_kv_reconcile(const spiral_gpu_params* p, const void* table_key16, const void* keys, uint64_t key_bytes, uint64_t n_keys, const spiral_gpu_kv_entry* entries,
+                            uint64_t n_entries, int64_t* where, uint8_t* entry_class, spiral_gpu_kv_reconcile_counts* counts) {
+    uint64_t nb;
+    if (kv_buckets(p, 0, &nb)) return -1;  // (nb = 2^(nu1 + nu2), whatever out_n: one function for base and SpiralPack tables)
+    return kv_reconcile(nb, table_key16, keys, key_bytes, n_keys, entries, n_entries, where, entry_class, counts);
+}
+
 int spiral_gpu_server_read_db_item(spiral_gpu_server* S, uint64_t item, uint64_t* out) {
     if (!S || !out) return fail("null argument");
     if (refuse_column(S, "read_db_item (read its items with read_db_items_at)")) return -1;
